@@ -1,9 +1,21 @@
 #!/usr/bin/env python3
 """bench.py -- depth frames/sec fused into the TSDF (1080x1920), 1/2/4/8 MI355X.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps, writes the outputs (--dump-outputs) and prints the line: roofline,
+cpu_baseline, rows and config.hw_queues are null.  --full adds everything below that takes runs of its own: the roofline
+(counting pass + timed re-run, the one-frame-per-launch re-run), the CPU baselines, the other rows of the path and the
+stream-concurrency probe.
+--dump-outputs DIR: after the timed steps rank 0 writes what they computed, as float64 .npy files (exact: the grids hold
+integers), at most 18 MB (39 MB with --centroid) at any --grid: the TSDF records of the grid (int32 sum and weight per
+voxel, record order) as the sums of each of 65 536 equal runs of records (tsdf_chunk_sums) and 2^20 records at fixed seeded
+positions (tsdf_sample); with --centroid the same of the centroid records (each uint64 word split into its high and low 32 bits:
+centroid_chunk_sums, centroid_sample, 2^18 records); with --icp the registration results of the last step's pairs (icp_T,
+icp_fitness, icp_rmse, icp_n_corr, icp_iters_run, icp_status).  The inputs are synthetic and fixed: the same arguments give
+the same inputs on every run.
 
 A step = one pass of the hot path over one batch of --frames-per-step synthetic frames per GPU (512 = one turn of a
 512-frame orbit, frames 0.7 degrees apart): each frame, already resident in HBM, is integrated into that GPU's 512^3 TSDF
@@ -12,13 +24,13 @@ grid with ONE foreign call per 64 frames (tl3d_fuse_frames); the library updates
 roofline.single_frame_per_sweep).  With N > 1 the frames shard across ranks (weak scaling: per-GPU batch fixed) and the
 per-GPU grids are summed with the product's merge inside the timed region.  Rank 0 prints ONE JSON line.
 
-roofline: algorithmic bytes per launch are COUNTED by the kernel (8 B x (records read + records written),
+roofline (--full): algorithmic bytes per launch are COUNTED by the kernel (8 B x (records read + records written),
 SURVEY.md section 8d) plus the depth bytes of the launch's frames; time is hipEvent time on the launching stream over
 the timed region.  roofline.bound / achieved / peak / frac price the algorithmic bytes against HBM, as the measurement contract
 defines them; roofline.limited_by names what really limits the kernel (vector-instruction issue: DESIGN.md 7.5).  roofline.traffic and the
 two sub-objects scattered_reads / vector_alu come from the builder's own rocprofv3 --pmc passes (profiles/pmc_traffic.json,
 keyed by workload): counters need passes of their own, they are NOT counters of this run, and the line says so.
-cpu_baseline: the C oracle (oracle/tl3d_oracle.c, OpenMP) on the host cores, bounded sample.  rows: the other rows of the
+cpu_baseline (--full): the C oracle (oracle/tl3d_oracle.c, OpenMP) on the host cores, bounded sample.  rows (--full): the other rows of the
 path, each timed over 5 repetitions (median; [min, max] in rows.spread).
 """
 import argparse
@@ -50,9 +62,14 @@ def parse():
     ap.add_argument("--centroid", action="store_true", help="also accumulate the voxel-centroid channel each frame")
     ap.add_argument("--icp", action="store_true", help="also run frame-to-frame ICP each frame (poses still analytic)")
     ap.add_argument("--icp-iters", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-single", action="store_true", help="skip the one-frame-per-launch measurement beside the roofline (profiling runs)")
-    ap.add_argument("--no-rows", action="store_true", help="skip the per-row rates of the rest of the path (N = 1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline, the CPU baselines, the other rows of the path and the stream concurrency "
+                         "(runs of their own after the timed steps); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what they computed (grid samples, registration results) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-single", action="store_true", help="with --full: skip the one-frame-per-launch measurement beside the roofline (profiling runs)")
+    ap.add_argument("--no-rows", action="store_true", help="with --full: skip the per-row rates of the rest of the path (N = 1 only)")
     ap.add_argument("--cpu-merge-frames", type=int, default=6, help="frames of the numpy back-project -> vstack -> voxel centroid -> SOR sample")
     ap.add_argument("--force-dist", action="store_true", help="init torch.distributed (RCCL) even with one rank: exercises the merge path")
     ap.add_argument("--cpu-frames", type=int, default=4, help="distinct frames the CPU baseline cycles over")
@@ -74,6 +91,52 @@ def spawn_ranks(n):
     call (the parent only watches its ranks and passes rank 0's line through).  A rank that dies -- by a signal too -- ends the
     group with a non-zero status instead of leaving the others in a collective; the wait is bounded (TL3D_RANK_TIMEOUT_S)."""
     return load_launcher().spawn_ranks(os.path.abspath(__file__), sys.argv[1:], n)
+
+
+def dump_outputs(out_dir, ctx, centroid, icp):
+    """--dump-outputs: what the timed steps left in the grid (and the last step's registration results), as float64 .npy files.
+    The grid is read in place (zero-copy view, pending free-space counts folded in) on the context's stream; only the sums and
+    the sample leave the GPU."""
+    import numpy as np
+    import torch
+    import tl3d
+
+    CHUNKS, SEED = 65536, 20240611
+    os.makedirs(out_dir, exist_ok=True)
+    out = {}
+
+    def split(x):                       # int64 words -> their high and low 32 bits, side by side (exact in float64)
+        return torch.stack([(x >> 32) & 0xFFFFFFFF, x & 0xFFFFFFFF], dim=2).reshape(x.shape[0], -1)
+
+    def channel(name, ch, words, n_sample, widen):
+        recs = ctx.grid_tensor(ch).view(-1, words)
+        nrec = recs.shape[0]
+        n_chunks = min(CHUNKS, nrec)
+        run = -(-nrec // n_chunks)                                  # records per run (the last runs may be short or empty)
+        sums = []
+        per_batch = max(1, (1 << 23) // run)                        # runs summed per pass: bounded temporaries
+        for c0 in range(0, n_chunks, per_batch):
+            c1 = min(n_chunks, c0 + per_batch)
+            seg = widen(recs[min(nrec, c0 * run):min(nrec, c1 * run)])
+            pad = (c1 - c0) * run - seg.shape[0]
+            if pad:
+                seg = torch.cat([seg, seg.new_zeros((pad, seg.shape[1]))])
+            sums.append(seg.view(c1 - c0, run, -1).sum(1))
+        out[f"{name}_chunk_sums"] = torch.cat(sums).cpu().numpy()
+        idx = np.sort(np.random.default_rng(SEED).integers(0, nrec, n_sample))
+        out[f"{name}_sample"] = widen(recs[torch.from_numpy(idx).to(recs.device)]).cpu().numpy()
+        del recs
+
+    channel("tsdf", tl3d.CH_TSDF, 2, 1 << 20, lambda x: x.to(torch.int64))
+    if centroid:
+        channel("centroid", tl3d.CH_CENTROID, 4, 1 << 18, split)
+    if icp:
+        out["icp_T"] = np.stack([r["T"] for r in icp])
+        for k in ("fitness", "rmse", "n_corr", "iters_run", "status"):
+            out[f"icp_{k}"] = np.asarray([r[k] for r in icp])
+    torch.cuda.synchronize()
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.ascontiguousarray(v, dtype=np.float64))
 
 
 def main():
@@ -126,7 +189,8 @@ def main():
     deg = 360.0 / max(1, args.resident_frames)
     scene = synth.object_scene(with_room=True)
     poses = synth.orbit_poses(n_res, 1.0, deg, start_deg=rank * deg / world)
-    want_rows = world == 1 and not args.no_rows
+    want_rows = args.full and world == 1 and not args.no_rows
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     channels = tl3d.CH_TSDF | (tl3d.CH_CENTROID if (args.centroid or want_rows) else 0)
     spec = tl3d.GridSpec.cube(n, args.voxel, centre=(0.0, -0.1, 0.0), channels=channels)
     # one explicit stream shared by torch (frame synthesis, RCCL) and the library, so every hand-over is ordered
@@ -146,11 +210,11 @@ def main():
         if args.depth_format == "u16":            # what a 16-bit PNG holds: round(metres * 1000), converted back by / 1000
             mm = torch.clamp(torch.round(d * 1000.0), 0, 65535).to(torch.int32).to(torch.uint16).contiguous()
             ctx.upload(i, mm, c)
-            d_host = (mm.cpu().numpy().astype(np.float32) / np.float32(1000.0)) if (rank == 0 and i < args.cpu_frames) else None
+            d_host = (mm.cpu().numpy().astype(np.float32) / np.float32(1000.0)) if (want_cpu and i < args.cpu_frames) else None
             del mm
         else:
             ctx.upload(i, d, c)
-            d_host = d.cpu().numpy() if (rank == 0 and i < args.cpu_frames) else None
+            d_host = d.cpu().numpy() if (want_cpu and i < args.cpu_frames) else None
         stream.synchronize()                      # the tensors are freed right after: finish the copy first
         if d_host is not None:
             host_keep.append((d_host, p))
@@ -177,10 +241,14 @@ def main():
     t_all = np.ascontiguousarray(np.stack([np.asarray(p[1], np.float64).reshape(3) for p in poses]))
     ones_all = np.ones(n_res)
 
+    icp_last = []                                    # the registration results of the latest step (--dump-outputs)
+
     def step(s, icp=args.icp, centroid=args.centroid, frames=F):
         # registration of group g+1 (one batched launch: every pair through all its iterations) runs while group g is fused
         G = 64
         groups = [[(s * frames + j) % n_res for j in range(j0, min(frames, j0 + G))] for j0 in range(0, frames, G)]
+        if icp:
+            icp_last.clear()
 
         def enqueue(gi):
             ks = groups[gi]
@@ -190,7 +258,7 @@ def main():
             enqueue(0)
         for gi, ks in enumerate(groups):
             if icp:
-                ctx.icp_batch_collect()
+                icp_last.extend(ctx.icp_batch_collect())
                 if gi + 1 < len(groups):
                     enqueue(gi + 1)
             idx = np.asarray(ks, np.int32)
@@ -223,13 +291,19 @@ def main():
     # A job longer than that is a sequence of scans: merge, hand the grid on (here: drop it), start the next scan.  All of it
     # stays inside the timed region.
     scan_frames = max(F, abi.TSDF_MAX_WEIGHT // world)
+    in_scan = 0
     for s in range(args.warmup):
+        if in_scan + F > scan_frames:                           # a long warm-up is a sequence of scans too
+            ctx.reset()
+            in_scan = 0
         step(s)
+        in_scan += F
     if dist is not None and args.warmup > 0:
         merge()                                                 # warm the communicator
         merge_ms.clear()
         merge_info.clear()
     ctx.reset()
+    ctx.reset_stats()                                           # update launches of the timed steps (frames per launch)
     barrier()
     ctx.event_record(0)
     t0 = time.perf_counter()
@@ -252,13 +326,17 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    timed_launches = ctx.stats()["tsdf_launches"]
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx, args.centroid, icp_last if args.icp else None)
 
     # ---- roofline of the dominant kernel (tsdf_integrate), rank 0 ----------------------------------------
     depth_bpp = 2.0 if args.depth_format == "u16" else 4.0
 
     def measure_roofline(c_, steps_, nres_=None, F_=None):
         """Counted algorithmic bytes per launch (a counting pass over the resident frames) and the kernel's own duration
-        (hipEvent pairs around every batch of back-to-back launches, on the launching stream) over `steps_` steps.  A launch
+        (hipEvent pairs around every batch of back-to-back launches, on the launching stream) over `steps_` steps, one scan at most.  A launch
         may update two consecutive frames (frames_per_sweep = frames / launches): the bytes are what the launch moves."""
         nres_ = n_res if nres_ is None else nres_
         F_ = F if F_ is None else F_
@@ -274,6 +352,8 @@ def main():
         c_.reset_stats()
         c_.reset()
         c_.set_profile(count_records=False, time_kernels=True)
+        # at most one scan (TSDF_MAX_WEIGHT frames): the grid's int32 headroom, and a bounded re-run however long the timed loop
+        steps_ = max(1, min(steps_, abi.TSDF_MAX_WEIGHT // F_))
         for s_ in range(steps_):
             for j in range(F_):
                 c_.integrate((s_ * F_ + j) % nres_, poses[(s_ * F_ + j) % nres_])
@@ -291,7 +371,7 @@ def main():
                 "ms_per_launch": round(k_ms, 4), "frames_per_sweep": round(fps_, 3), "us_per_frame": round(1e3 * k_ms / fps_, 2)}
 
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         launches = total_frames_rank
         m = measure_roofline(ctx, args.steps)
         region_ms = dev_ms / launches
@@ -348,7 +428,7 @@ def main():
 
     # ---- CPU baseline: the oracle on the host cores, bounded sample, rank 0 at N=1 only --------------------
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if want_cpu:
         from oracle import c_oracle
         c_oracle.Oracle.set_threads(c_oracle.usable_cpus())       # the box shows 256 CPUs and grants a quota of 16
         orc = c_oracle.Oracle(W, H, cam["fx"], cam["fy"], cam["cx"], cam["cy"], 0.1, 50.0, dims=spec.dims,
@@ -488,7 +568,8 @@ def main():
     if rank == 0:
         total = world * total_frames_rank
         # effective stream concurrency of THIS process, measured after everything that is timed (the probe creates streams)
-        hwq = abi.probe_hw_queues(local_rank, 16, 1.0)
+        hwq = abi.probe_hw_queues(local_rank, 16, 1.0) if args.full else None
+        fps_timed = total_frames_rank / timed_launches if timed_launches else 2
         out = {
             "metric": "depth frames/sec fused into TSDF (1080x1920)",
             "value": round(total / elapsed, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
@@ -498,7 +579,7 @@ def main():
                                    f"case -- ray-miss pixels only remove bricks; camera radius 1 m) "
                                    f"integrated into a {n}^3 TSDF @ {args.voxel * 1e3:g} mm, 8 B/voxel, "
                                    f"{args.resident_frames} frames per turn of the orbit ({360.0 / max(1, args.resident_frames):.2f} degrees apart on every rank), "
-                                   f"{roof['frames_per_sweep'] if roof else 2:g} frames per update launch; frames resident in HBM as "
+                                   f"{roof['frames_per_sweep'] if roof else fps_timed:g} frames per update launch; frames resident in HBM as "
                                    + ("16-bit millimetres (PNG depth)" if args.depth_format == "u16" else "float32 metres"),
                        "depth_format": args.depth_format,
                        "frames_per_step_per_gpu": F, "resident_frames_per_gpu": n_res, "grid": n,

@@ -1,10 +1,11 @@
-"""GPU: bench.py's output contract on a reduced workload (the driver parses this line), and a one-rank rehearsal of the
-RCCL merge path (all-reduce on the library's own grid memory)."""
+"""GPU: bench.py's output contract on a reduced workload (the driver parses this line), the plain run against --full, the
+outputs it writes (--dump-outputs), and a one-rank rehearsal of the RCCL merge path (all-reduce on the library's own grid memory)."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -25,7 +26,7 @@ def _run(extra, env=None):
 
 
 def test_bench_json_contract():
-    d = _run([])
+    d = _run(["--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -68,7 +69,7 @@ def test_bench_json_contract():
 
 
 def test_single_rank_rccl_merge_rehearsal():
-    d = _run(["--force-dist", "--no-cpu-baseline", "--no-rows", "--centroid", "--depth-format", "u16"], env={"MASTER_PORT": "29541"})
+    d = _run(["--full", "--force-dist", "--no-cpu-baseline", "--no-rows", "--centroid", "--depth-format", "u16"], env={"MASTER_PORT": "29541"})
     assert d["value"] > 0 and d["config"]["centroid_channel"] is True and d["config"]["depth_format"] == "u16"
     assert d["config"]["grid_merges_in_timed_region"] == 1 and d["rows"] is None
     r = d["roofline"]
@@ -86,3 +87,54 @@ def test_two_ranks_on_one_gpu_rehearse_the_multi_gpu_bench():
     assert one["config"]["dist_ranks"] == 1 and "90.00 degrees apart on every rank" in one["config"]["workload"]
     assert "90.00 degrees apart on every rank" in c["workload"]
     assert abs(d["ms_per_step"] - 1e3 * 2 * 4 / d["value"]) / d["ms_per_step"] < 0.05
+
+
+def test_full_run_longer_than_one_scan():
+    """More frames than one grid may hold (TL3D_TSDF_MAX_WEIGHT observations per voxel) in the warm-up and in the timed steps:
+    both run as a sequence of scans, and --full's roofline re-run stays within one scan."""
+    steps = 65536 // 64 + 2
+    d = _run(["--full", "--no-cpu-baseline", "--no-rows", "--no-single", "--frames-per-step", "64", "--steps", str(steps),
+              "--warmup", str(steps)])
+    assert d["steps"] == steps and d["warmup"] == steps and d["value"] > 0
+    assert d["roofline"]["achieved"] > 0 and d["roofline"]["ms_per_launch"] > 0
+
+
+def _load_dir(d):
+    return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d)) if f.endswith(".npy")}
+
+
+def test_plain_run_times_the_headline_only_and_dumps_what_it_computed(tmp_path):
+    """A plain run (no --full) prints the headline fields and nothing that needs runs of its own; --dump-outputs writes the
+    grid the timed steps left (float64, bounded size), and the same arguments give the same outputs on a second run."""
+    a, b = tmp_path / "a", tmp_path / "b"
+    d = _run(["--dump-outputs", str(a)])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["unit"] == "frames/s" and d["dtype"] == "f32"
+    assert abs(d["ms_per_step"] - 1e3 * 4 / d["value"]) / d["ms_per_step"] < 0.05
+    assert d["roofline"] is None and d["cpu_baseline"] is None and d["rows"] is None and d["config"]["hw_queues"] is None
+    per_launch = float(d["config"]["workload"].split(" frames per update launch")[0].rsplit(" ", 1)[1])   # counted in the timed steps
+    assert 1.0 <= per_launch <= 32.0
+    out = _load_dir(a)
+    assert set(out) == {"tsdf_chunk_sums", "tsdf_sample"}
+    assert all(v.dtype == np.float64 for v in out.values())
+    assert sum(os.path.getsize(os.path.join(a, f)) for f in os.listdir(a)) <= 64 << 20
+    sums = out["tsdf_chunk_sums"]
+    assert sums.shape == (65536, 2) and (sums[:, 1] >= 0).all() and sums[:, 1].sum() > 0       # observations were fused
+    assert out["tsdf_sample"].shape == (1 << 20, 2) and (out["tsdf_sample"] == np.round(out["tsdf_sample"])).all()
+    _run(["--dump-outputs", str(b)])
+    again = _load_dir(b)
+    assert set(again) == set(out) and all(np.array_equal(out[k], again[k]) for k in out)
+
+
+def test_dump_outputs_with_centroid_and_registration(tmp_path):
+    d = _run(["--centroid", "--icp", "--dump-outputs", str(tmp_path)])
+    assert d["config"]["centroid_channel"] is True and d["config"]["icp_in_loop"] is True
+    out = _load_dir(tmp_path)
+    assert out["centroid_chunk_sums"].shape == (65536, 8) and out["centroid_chunk_sums"].sum() > 0
+    assert out["centroid_sample"].shape == (1 << 18, 8) and (out["centroid_sample"] < 2.0 ** 32).all()
+    assert out["icp_T"].shape == (4, 4, 4) and np.allclose(out["icp_T"][:, 3], [0, 0, 0, 1])
+    for k in ("icp_fitness", "icp_rmse", "icp_n_corr", "icp_iters_run", "icp_status"):
+        assert out[k].shape == (4,), k
+    assert all(v.dtype == np.float64 for v in out.values())
+    assert sum(os.path.getsize(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)) <= 64 << 20

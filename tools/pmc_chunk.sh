@@ -1,10 +1,10 @@
 # usage (GPU box): bash tools/pmc_chunk.sh "VAR=val ..." ...   -- FETCH_SIZE per frame and L2 hit rate of tsdf_update_kernel per setting (experiments flavour); appends to gpurun_out/r03_pmc_chunk.txt
 set -uo pipefail
 export TMPDIR=/tmp
-cd /root/repo
+cd "$(dirname "${BASH_SOURCE[0]}")/.."
 LIB=$PWD/textureless-3d-reconstruction_amd/libtl3d_exp.so
 [[ -f "$LIB" ]] || TL3D_FLAVOUR=experiments bash textureless-3d-reconstruction_amd/csrc/build.sh >/dev/null
-ARGS=(--no-cpu-baseline --no-rows --no-single --steps 1 --warmup 0 --frames-per-step 64 --resident-frames 512)
+ARGS=(--full --no-cpu-baseline --no-rows --no-single --steps 1 --warmup 0 --frames-per-step 64 --resident-frames 512)
 for setting in "$@"; do
   OUT=/tmp/pmcc; rm -rf $OUT
   echo "[pmc_chunk] $setting" >> gpurun_out/r03_pmc_chunk.txt

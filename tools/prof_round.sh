@@ -13,12 +13,12 @@ TAG="${1:-r04}"
 export TMPDIR=/tmp
 OUT="$PWD/gpurun_out/prof_${TAG}"
 rm -rf "$OUT"; mkdir -p "$OUT"
-echo "[prof] kernel trace 1 (timed loop only): python3 bench.py --no-cpu-baseline --no-rows --no-single"
-timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace1" -- python3 bench.py --no-cpu-baseline --no-rows --no-single > "$OUT/bench_traced.json" 2> "$OUT/bench_traced.err"
+echo "[prof] kernel trace 1 (timed loop only): python3 bench.py --full --no-cpu-baseline --no-rows --no-single"
+timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace1" -- python3 bench.py --full --no-cpu-baseline --no-rows --no-single > "$OUT/bench_traced.json" 2> "$OUT/bench_traced.err"
 echo "rc=$?"
 f=$(find "$OUT/trace1" -name "*kernel_stats.csv" | head -1); [[ -n "$f" ]] && grep -E "^\"Name\"|tl3d" "$f" > "$OUT/kernel_stats.csv"
-echo "[prof] kernel trace 2 (the default command, rows and the one-frame-per-launch section included): python3 bench.py"
-timeout -k 5 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace2" -- python3 bench.py > "$OUT/bench_rows_traced.json" 2> "$OUT/bench_rows_traced.err"
+echo "[prof] kernel trace 2 (the full command, rows and the one-frame-per-launch section included): python3 bench.py --full"
+timeout -k 5 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace2" -- python3 bench.py --full > "$OUT/bench_rows_traced.json" 2> "$OUT/bench_rows_traced.err"
 echo "rc=$?"
 f=$(find "$OUT/trace2" -name "*kernel_stats.csv" | head -1); [[ -n "$f" ]] && grep -E "^\"Name\"|tl3d" "$f" > "$OUT/rows_kernel_stats.csv"
 python3 - "$OUT" <<'PY' > "$OUT/update_by_phase.txt"
@@ -41,7 +41,7 @@ if b and rows:
     per_step = 512 // 32
     n_head = (b["warmup"] + 2 * b["steps"]) * per_step
     head, rest = [d for _, d in rows[:n_head]], [d for _, d in rows[n_head:]]
-    print(f"tsdf_update_pairs_kernel<false, ...> dispatches of `python3 bench.py`: {len(rows)}")
+    print(f"tsdf_update_pairs_kernel<false, ...> dispatches of `python3 bench.py --full`: {len(rows)}")
     print(f"  first {len(head)} (warm-up, timed region, profiled re-run: 32 frames per launch): mean {sum(head) / len(head):.1f} us  min {min(head):.1f}  max {max(head):.1f}")
     print(f"  last {len(head) - b['warmup'] * per_step - b['steps'] * per_step} of those (the profiled re-run): mean {sum(head[-b['steps'] * per_step:]) / (b['steps'] * per_step):.1f} us;  bench.py's hipEvent figure: {1e3 * b['roofline']['ms_per_launch']:.1f} us")
     if rest: print(f"  the other {len(rest)} (one frame per launch, rows): mean {sum(rest) / len(rest):.1f} us  min {min(rest):.1f}  max {max(rest):.1f}")
@@ -68,9 +68,9 @@ PY
 cat "$OUT/pmc_calibration.txt"
 python3 tools/prof_summary.py "$OUT" "gpurun_out/pmc_${TAG}" > "$OUT/traffic.log" 2>&1; cat "$OUT/traffic.log"
 echo "[prof] bench lines"
-timeout -k 5 300 python3 bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"; echo "rc=$?"
-timeout -k 5 300 python3 bench.py --depth-format u16 --no-rows --no-cpu-baseline > "$OUT/bench_u16_frames.json" 2>/dev/null; echo "rc=$?"
-timeout -k 5 300 python3 bench.py --width 3840 --height 2160 --grid 1024 --voxel 0.002 --resident-frames 256 --frames-per-step 256 --steps 4 --no-rows --no-cpu-baseline > "$OUT/bench_config5_size.json" 2>/dev/null; echo "rc=$?"
+timeout -k 5 300 python3 bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"; echo "rc=$?"
+timeout -k 5 300 python3 bench.py --full --depth-format u16 --no-rows --no-cpu-baseline > "$OUT/bench_u16_frames.json" 2>/dev/null; echo "rc=$?"
+timeout -k 5 300 python3 bench.py --full --width 3840 --height 2160 --grid 1024 --voxel 0.002 --resident-frames 256 --frames-per-step 256 --steps 4 --no-rows --no-cpu-baseline > "$OUT/bench_config5_size.json" 2>/dev/null; echo "rc=$?"
 find "$OUT" -name "*kernel_trace.csv" -delete; find "$OUT" -name "*counter_collection.csv" -delete; find "$OUT" -name "*agent_info.csv" -delete
 rm -rf "$OUT/trace1" "$OUT/trace2" "$OUT/cal"
 du -sh "$OUT"

@@ -9,7 +9,7 @@ LIB="$HERE/textureless-3d-reconstruction_amd/libtl3d_exp.so"
 [[ -f "$LIB" ]] || TL3D_FLAVOUR=experiments bash "$HERE/textureless-3d-reconstruction_amd/csrc/build.sh" >/dev/null
 : > "$OUT"
 for setting in "$@"; do
-  line=$(env TL3D_LIB="$LIB" $setting timeout -k 5 120 python3 "$HERE/bench.py" --no-cpu-baseline --no-rows --steps ${STEPS:-4} ${BENCH_ARGS:-} 2>/dev/null)
+  line=$(env TL3D_LIB="$LIB" $setting timeout -k 5 120 python3 "$HERE/bench.py" --full --no-cpu-baseline --no-rows --steps ${STEPS:-4} ${BENCH_ARGS:-} 2>/dev/null)
   python3 - "$setting" "$line" >> "$OUT" <<'PY'
 import json, sys
 s, line = sys.argv[1], sys.argv[2]
