@@ -71,6 +71,8 @@ def main(argv=None):
     parser.add_argument("--scale-update-weight", type=float, default=0.3, help="weight of a view's own scale estimate in the running scale")
     parser.add_argument("--tsdf-min-weight", type=int, default=0, help="> 0: keep only voxels the TSDF saw this often")
     parser.add_argument("--ascii", action="store_true", help="write the reference's ASCII fallback PLY instead of binary")
+    parser.add_argument("--mesh-output", type=str, default=None,
+                        help="also write the marching-cubes triangle mesh of the fused TSDF to this PLY (binary, or ASCII with --ascii)")
     parser.add_argument("--device", type=int, default=0)
     parser.add_argument("--stream", dest="stream", action="store_true", default=True,
                         help="(default) decode on worker threads into pinned buffers with asynchronous uploads; host RAM never holds the sequence")
@@ -95,7 +97,7 @@ def main(argv=None):
                                   subsample_factor=args.subsample, depth_scale=args.depth_scale, grid_dim=args.grid,
                                   sdf_trunc_voxels=args.sdf_trunc, icp_iters=args.icp_iters, icp_stride=args.icp_stride,
                                   icp_max_dist=args.icp_max_dist, tsdf_min_weight=args.tsdf_min_weight, device=args.device,
-                                  scale_update_weight=args.scale_update_weight)
+                                  scale_update_weight=args.scale_update_weight, extract_mesh=args.mesh_output is not None)
     pipeline = DepthToReconstructionPipeline(config)
     # a rank decodes every frame on its host (pose chain and scale rule run over the whole sequence) and uploads its share
     streaming = args.stream and dist is None
@@ -127,6 +129,8 @@ def main(argv=None):
         points, colors, poses = pipeline.reconstruct(anchors=anchors, estimate_scale=args.estimate_scale)
     if points is not None and len(points) > 0:
         pipeline.save_reconstruction(points, colors, args.output, ascii=args.ascii)
+        if args.mesh_output:
+            pipeline.save_mesh(args.mesh_output, ascii=args.ascii)
         if not args.no_vis:
             print("(interactive Plotly viewer of the reference is not part of the device path; pass --no-vis to silence)")
     else:

@@ -341,6 +341,16 @@ int tl3d_allreduce_grid(tl3d_ctx *ctx, uint32_t channels /* TL3D_CH_* mask; 0 = 
 int tl3d_extract(tl3d_ctx *ctx, int mode, int min_count, int min_weight, double max_abs_tsdf,
                  float *out_xyz_hd, uint8_t *out_rgb_hd, int64_t cap, int64_t *out_n);
 
+/* marching cubes over the TSDF channel: vertices = owned zero-crossing edges, record order;
+ * triangles by cell, uint32 indices, wound so (v1-v0)x(v2-v0) points to t > 0.
+ * Call with NULL buffers for the counts, then with capacities >= the counts (host or device pointers).
+ * TL3D_E_STATE without a TSDF channel; TL3D_E_CAPACITY on short buffers, or when the mesh has 2^31 vertices or more
+ * (the counts are stored first).  No reference code: the reference has no TSDF. */
+int tl3d_extract_mesh(tl3d_ctx *ctx, int min_weight,
+                      float *out_xyz_hd, uint8_t *out_rgb_hd, int64_t vert_cap,
+                      uint32_t *out_tri_hd, int64_t tri_cap,
+                      int64_t *out_n_vert, int64_t *out_n_tri);
+
 /* f1: statistical outlier removal on a point list (Open3D remove_statistical_outlier, D2R:412-415) */
 int tl3d_statistical_outlier(tl3d_ctx *ctx, const float *xyz_hd, int64_t n, int nb_neighbors, double std_ratio,
                              double cell_size, uint8_t *keep_out_hd, int64_t *out_kept);

@@ -51,6 +51,8 @@ class ReconstructionConfig:
     outlier_nb_neighbors: int = 20
     outlier_std_ratio: float = 2.0
     device: int = 0
+    # marching-cubes mesh of the TSDF after the fusion (DepthToReconstructionPipeline.mesh / save_mesh)
+    extract_mesh: bool = False
 
     @property
     def K(self) -> np.ndarray:

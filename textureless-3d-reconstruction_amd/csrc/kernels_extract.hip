@@ -14,23 +14,6 @@ struct ExtArgs {
     double max_abs;
 };
 
-__device__ __forceinline__ void rec_coords(size_t idx, int nbx, int nby, int &i, int &j, int &k) {
-    const size_t b = idx >> 9;
-    const int l = (int)(idx & 511);
-    const int bx = (int)(b % (size_t)nbx), by = (int)((b / (size_t)nbx) % (size_t)nby);
-    const int bz = (int)(b / ((size_t)nbx * (size_t)nby));
-    in_brick_coords(l, i, j, k);
-    i |= bx << 3;
-    j |= by << 3;
-    k |= bz << 3;
-}
-
-__device__ __forceinline__ void mean_colour(const unsigned long long *__restrict__ rec, unsigned long long n, uint8_t c[3]) {
-    c[0] = (uint8_t)((rec[2] & 0xffffffffull) / n);
-    c[1] = (uint8_t)((rec[2] >> 32) / n);
-    c[2] = (uint8_t)((rec[3] & 0xffffffffull) / n);
-}
-
 // Returns the number of points record idx emits; when WRITE, stores them at out index o, o+1, ...
 template <bool WRITE>
 __device__ __forceinline__ int extract_record(const Grid &g, const ExtArgs &a, const int2 *__restrict__ tsdf,

@@ -628,6 +628,9 @@ int tl3d_destroy(tl3d_ctx *ctx) {
         if (ctx->prep_stream[q]) (void)hipStreamDestroy(ctx->prep_stream[q]);
     if (ctx->block_counts) (void)hipFree(ctx->block_counts);
     if (ctx->block_offsets) (void)hipFree(ctx->block_offsets);
+    if (ctx->mesh_counts) (void)hipFree(ctx->mesh_counts);
+    if (ctx->mesh_offsets) (void)hipFree(ctx->mesh_offsets);
+    if (ctx->mesh_first) (void)hipFree(ctx->mesh_first);
     if (ctx->bp_state) (void)hipFree(ctx->bp_state);
     if (ctx->bp_factors) (void)hipFree(ctx->bp_factors);
     if (ctx->bp_stage_xyz) (void)hipFree(ctx->bp_stage_xyz);
@@ -2224,6 +2227,100 @@ int tl3d_extract(tl3d_ctx *ctx, int mode, int min_count, int min_weight, double 
     if (!direct) { (void)hipFree(dxyz); (void)hipFree(drgb); }
     if (rc) return rc;
     if (e != hipSuccess || e2 != hipSuccess) return set_err(TL3D_E_HIP, "extract copy/sync failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+    return TL3D_OK;
+}
+
+// ------------------------------------------------------------------------------------------- mesh
+static int ensure_mesh_scratch(tl3d_ctx *ctx, size_t nblocks, size_t nfirst) {
+    if (nblocks > ctx->mesh_blocks) {
+        if (ctx->mesh_counts) (void)hipFree(ctx->mesh_counts);
+        if (ctx->mesh_offsets) (void)hipFree(ctx->mesh_offsets);
+        ctx->mesh_counts = nullptr;
+        ctx->mesh_offsets = nullptr;
+        ctx->mesh_blocks = 0;
+        if (hipMalloc(&ctx->mesh_counts, 2 * nblocks * sizeof(unsigned)) != hipSuccess) return set_err(TL3D_E_NOMEM, "mesh scratch alloc failed");
+        if (hipMalloc(&ctx->mesh_offsets, 2 * nblocks * sizeof(unsigned long long)) != hipSuccess) return set_err(TL3D_E_NOMEM, "mesh scratch alloc failed");
+        ctx->mesh_blocks = nblocks;
+    }
+    if (nfirst > ctx->mesh_first_n) {
+        if (ctx->mesh_first) (void)hipFree(ctx->mesh_first);
+        ctx->mesh_first = nullptr;
+        ctx->mesh_first_n = 0;
+        if (hipMalloc(&ctx->mesh_first, nfirst * sizeof(unsigned)) != hipSuccess)
+            return set_err(TL3D_E_NOMEM, "mesh vertex-id scratch alloc (%zu B) failed", nfirst * sizeof(unsigned));
+        ctx->mesh_first_n = nfirst;
+    }
+    return TL3D_OK;
+}
+
+int tl3d_extract_mesh(tl3d_ctx *ctx, int min_weight, float *out_xyz, uint8_t *out_rgb, int64_t vert_cap, uint32_t *out_tri,
+                      int64_t tri_cap, int64_t *out_n_vert, int64_t *out_n_tri) {
+    REQUIRE(ctx && out_n_vert && out_n_tri, TL3D_E_INVALID, "null argument");
+    REQUIRE(ctx->tsdf != nullptr, TL3D_E_STATE, "TSDF channel not enabled");
+    FLUSH_AND_FOLD(ctx);
+    TL3D_HIP(hipSetDevice(ctx->device));
+    const int nblocks = (int)((ctx->nvox + EXTRACT_CHUNK - 1) / EXTRACT_CHUNK);
+    const size_t mb = (size_t)nblocks + 1;
+    int rc = ensure_mesh_scratch(ctx, mb, (size_t)ctx->grid.tsdf_cap << 9);
+    if (rc) return rc;
+    unsigned *vcounts = ctx->mesh_counts, *tcounts = ctx->mesh_counts + mb;
+    unsigned long long *voffs = ctx->mesh_offsets, *toffs = ctx->mesh_offsets + mb;
+    unsigned long long nv = 0, nt = 0;
+    if (ctx->mesh_valid && ctx->mesh_epoch == ctx->grid_epoch && ctx->mesh_min_weight == min_weight) {
+        nv = ctx->mesh_nv;                              // the size query just before this call already counted and scanned
+        nt = ctx->mesh_nt;
+    } else {
+        ctx->mesh_valid = false;
+        rc = launch_mesh_count(ctx->stream, ctx->grid, min_weight, ctx->tsdf, vcounts, tcounts, nblocks);
+        if (rc) return rc;
+        rc = launch_scan(ctx->stream, vcounts, voffs, nblocks, voffs + nblocks);
+        if (rc) return rc;
+        rc = launch_scan(ctx->stream, tcounts, toffs, nblocks, toffs + nblocks);
+        if (rc) return rc;
+        unsigned long long h[2] = {0, 0};
+        TL3D_HIP(hipMemcpyAsync(&h[0], voffs + nblocks, sizeof(h[0]), hipMemcpyDeviceToHost, ctx->stream));
+        TL3D_HIP(hipMemcpyAsync(&h[1], toffs + nblocks, sizeof(h[1]), hipMemcpyDeviceToHost, ctx->stream));
+        TL3D_HIP(hipStreamSynchronize(ctx->stream));
+        nv = h[0];
+        nt = h[1];
+        ctx->mesh_valid = true; ctx->mesh_epoch = ctx->grid_epoch; ctx->mesh_min_weight = min_weight;
+        ctx->mesh_nv = nv; ctx->mesh_nt = nt;
+    }
+    *out_n_vert = (int64_t)nv;
+    *out_n_tri = (int64_t)nt;
+    // uint32 indices, and PLY's int vertex_indices: fewer than 2^31 vertices
+    if (nv >= (1ull << 31)) return set_err(TL3D_E_CAPACITY, "mesh has %llu vertices: indices need fewer than 2^31", nv);
+    if (!out_xyz || !out_rgb || !out_tri) return TL3D_OK;
+    if ((int64_t)nv > vert_cap || (int64_t)nt > tri_cap)
+        return set_err(TL3D_E_CAPACITY, "need %llu vertices / %llu triangles, capacities %lld / %lld", nv, nt, (long long)vert_cap,
+                       (long long)tri_cap);
+    if (nv == 0) return TL3D_OK;                        // (no vertex: no meshed cell either)
+    const bool direct = is_device_ptr(out_xyz) && is_device_ptr(out_rgb) && is_device_ptr(out_tri);
+    float *dxyz = out_xyz;
+    uint8_t *drgb = out_rgb;
+    uint32_t *dtri = out_tri;
+    if (!direct) {
+        dxyz = nullptr; drgb = nullptr; dtri = nullptr;
+        if (hipMalloc(&dxyz, nv * 12) != hipSuccess || hipMalloc(&drgb, nv * 3) != hipSuccess ||
+            (nt && hipMalloc(&dtri, nt * 12) != hipSuccess)) {
+            (void)hipGetLastError();
+            if (dxyz) (void)hipFree(dxyz);
+            if (drgb) (void)hipFree(drgb);
+            return set_err(TL3D_E_NOMEM, "mesh output staging alloc failed");
+        }
+    }
+    rc = launch_mesh_write(ctx->stream, ctx->grid, min_weight, ctx->tsdf, ctx->centroid, voffs, toffs, nblocks, ctx->mesh_first,
+                           dxyz, drgb, nv, dtri, nt);
+    hipError_t e = hipSuccess;
+    if (rc == TL3D_OK && !direct) {
+        e = hipMemcpyAsync(out_xyz, dxyz, nv * 12, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(out_rgb, drgb, nv * 3, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && nt) e = hipMemcpyAsync(out_tri, dtri, nt * 12, hipMemcpyDeviceToHost, ctx->stream);
+    }
+    hipError_t e2 = hipStreamSynchronize(ctx->stream);
+    if (!direct) { (void)hipFree(dxyz); (void)hipFree(drgb); if (dtri) (void)hipFree(dtri); }
+    if (rc) return rc;
+    if (e != hipSuccess || e2 != hipSuccess) return set_err(TL3D_E_HIP, "mesh copy/sync failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
     return TL3D_OK;
 }
 

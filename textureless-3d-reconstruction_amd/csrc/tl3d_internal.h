@@ -208,6 +208,16 @@ struct tl3d_ctx {
     int ext_mode, ext_min_count, ext_min_weight;
     double ext_max_abs;
     bool ext_valid;
+    // tl3d_extract_mesh: counts of the size query (same reuse rule), per-block vertex / triangle counts and their offsets,
+    // and each vertex owner's first vertex id ([TSDF pool slots][512] u32, grown on demand)
+    unsigned long long mesh_epoch, mesh_nv, mesh_nt;
+    int mesh_min_weight;
+    bool mesh_valid;
+    unsigned *mesh_counts;                  // [2][mesh_blocks]
+    unsigned long long *mesh_offsets;       // [2][mesh_blocks]
+    size_t mesh_blocks;
+    unsigned *mesh_first;
+    size_t mesh_first_n;
     unsigned long long *bp_state;        // one-launch back-projection: ticket, error word, per-tile granules, [bp_state_words - 1] = total
     size_t bp_state_words;
     float *bp_stage_xyz;                 // staging for host-side outputs, sized for a full frame at subsample 1
@@ -311,6 +321,24 @@ __host__ __device__ __forceinline__ void in_brick_coords(int l, int &i, int &j, 
 }
 __device__ __forceinline__ size_t vox_index(int i, int j, int k, int nbx, int nby) {
     return brick_base(i >> 3, j >> 3, k >> 3, nbx, nby) + (size_t)in_brick_index(i, j, k);
+}
+
+// coordinates of virtual record index idx (brick-major, in-brick order above); extraction and mesh kernels
+__device__ __forceinline__ void rec_coords(size_t idx, int nbx, int nby, int &i, int &j, int &k) {
+    const size_t b = idx >> 9;
+    const int l = (int)(idx & 511);
+    const int bx = (int)(b % (size_t)nbx), by = (int)((b / (size_t)nbx) % (size_t)nby);
+    const int bz = (int)(b / ((size_t)nbx * (size_t)nby));
+    in_brick_coords(l, i, j, k);
+    i |= bx << 3;
+    j |= by << 3;
+    k |= bz << 3;
+}
+
+__device__ __forceinline__ void mean_colour(const unsigned long long *__restrict__ rec, unsigned long long n, uint8_t c[3]) {
+    c[0] = (uint8_t)((rec[2] & 0xffffffffull) / n);
+    c[1] = (uint8_t)((rec[2] >> 32) / n);
+    c[2] = (uint8_t)((rec[3] & 0xffffffffull) / n);
 }
 
 // ---- brick tables ---------------------------------------------------------------------------------------------------------
@@ -429,6 +457,12 @@ int launch_extract_count(hipStream_t s, const Grid &g, int mode, int min_count, 
 int launch_extract_write(hipStream_t s, const Grid &g, int mode, int min_count, int min_weight, double max_abs,
                          const int2 *tsdf, const unsigned long long *cen, const unsigned long long *offsets, int nblocks,
                          float *xyz, uint8_t *rgb, unsigned long long cap);
+// mesh
+int launch_mesh_count(hipStream_t s, const Grid &g, int min_weight, const int2 *tsdf, unsigned *vcounts, unsigned *tcounts,
+                      int nblocks);
+int launch_mesh_write(hipStream_t s, const Grid &g, int min_weight, const int2 *tsdf, const unsigned long long *cen,
+                      const unsigned long long *voffsets, const unsigned long long *toffsets, int nblocks, unsigned *first_id,
+                      float *xyz, uint8_t *rgb, unsigned long long vcap, unsigned *tris, unsigned long long tcap);
 // grids
 int launch_max_weight(hipStream_t s, const Grid &g, const int2 *pool, int *d_out);
 int launch_max_weight_dense(hipStream_t s, const int2 *grid, size_t nvox, int *d_out);

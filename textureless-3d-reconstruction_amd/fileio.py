@@ -543,6 +543,42 @@ def write_ply_binary(path, points, colors, double_xyz: bool = True):
         f.write(rec.tobytes())
 
 
+def write_ply_mesh(path, xyz, rgb, tris, ascii: bool = False):
+    """Triangle mesh as PLY: vertices `float x, y, z, uchar red, green, blue`, faces `list uchar int vertex_indices`;
+    binary little-endian, or ASCII.  Parent directories are created."""
+    xyz = np.asarray(xyz, dtype=np.float32).reshape(-1, 3)
+    rgb = np.asarray(rgb, dtype=np.uint8).reshape(-1, 3)
+    tris = np.asarray(tris).reshape(-1, 3)
+    assert len(xyz) == len(rgb) and len(xyz) < 2 ** 31
+    assert len(tris) == 0 or (int(tris.min()) >= 0 and int(tris.max()) < len(xyz)), "triangle index out of range"
+    header = "\n".join(["ply", "format ascii 1.0" if ascii else "format binary_little_endian 1.0", f"element vertex {len(xyz)}",
+                        "property float x", "property float y", "property float z", "property uchar red", "property uchar green",
+                        "property uchar blue", f"element face {len(tris)}", "property list uchar int vertex_indices",
+                        "end_header"]) + "\n"
+    filepath = Path(path)
+    filepath.parent.mkdir(parents=True, exist_ok=True)
+    if ascii:
+        with open(filepath, "w", newline="\n") as f:
+            f.write(header)
+            for p, c in zip(xyz, rgb):
+                f.write(f"{p[0]} {p[1]} {p[2]} {int(c[0])} {int(c[1])} {int(c[2])}\n")
+            for t in tris:
+                f.write(f"3 {int(t[0])} {int(t[1])} {int(t[2])}\n")
+        return
+    vrec = np.empty(len(xyz), dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("r", "u1"), ("g", "u1"), ("b", "u1")])
+    if len(xyz):
+        vrec["x"], vrec["y"], vrec["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+        vrec["r"], vrec["g"], vrec["b"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
+    frec = np.empty(len(tris), dtype=[("n", "u1"), ("v", "<i4", (3,))])
+    if len(tris):
+        frec["n"] = 3
+        frec["v"] = tris.astype(np.int64)
+    with open(filepath, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(vrec.tobytes())
+        f.write(frec.tobytes())
+
+
 def save_reconstruction(points, colors, output_path, ascii: bool = False) -> bool:
     """DepthToReconstructionPipeline.save_reconstruction (D2R:673-703): empty input prints `No points to save` and
     writes nothing; parent directories are created; prints `Saved to <path>`."""

@@ -577,6 +577,20 @@ class FusionContext:
                                              abi.ptr(xyz), abi.ptr(rgb), n.value, C.byref(n)))
         return xyz, rgb
 
+    def extract_mesh(self, min_weight: int = 0):
+        """Marching-cubes mesh of the TSDF channel: (xyz f32 [V,3], rgb u8 [V,3], tris u32 [T,3]).  The
+        vertices are the zero crossings of the usable voxel edges in record order; every triangle is wound so that
+        (v1 - v0) x (v2 - v0) points to t > 0 (towards the cameras)."""
+        nv, nt = C.c_int64(0), C.c_int64(0)
+        abi.check(self._lib.tl3d_extract_mesh(self._h, int(min_weight), None, None, 0, None, 0, C.byref(nv), C.byref(nt)))
+        xyz = np.empty((nv.value, 3), np.float32)
+        rgb = np.empty((nv.value, 3), np.uint8)
+        tris = np.empty((nt.value, 3), np.uint32)
+        if nv.value:
+            abi.check(self._lib.tl3d_extract_mesh(self._h, int(min_weight), abi.ptr(xyz), abi.ptr(rgb), nv.value, abi.ptr(tris),
+                                                  nt.value, C.byref(nv), C.byref(nt)))
+        return xyz, rgb, tris
+
     def statistical_outlier(self, xyz, nb_neighbors=20, std_ratio=2.0, cell_size=None):
         xyz = np.ascontiguousarray(xyz, dtype=np.float32)
         keep = np.zeros(len(xyz), np.uint8)

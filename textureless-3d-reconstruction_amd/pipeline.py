@@ -195,6 +195,7 @@ class DepthToReconstructionPipeline:
         self.stats: dict = {}
         self.timings: dict = {}                   # wall seconds per stage of the last reconstruct()
         self.grid: Optional[GridSpec] = None      # the fusion volume of the last reconstruct()
+        self.mesh = None                          # (xyz f32 [V,3], rgb u8 [V,3], tris u32 [T,3]) of the last reconstruct(), config.extract_mesh
 
     # ---- a2 --------------------------------------------------------------------------------------
     def load_data(self, rgb_folder: str, depth_folder: str) -> int:
@@ -390,6 +391,7 @@ class DepthToReconstructionPipeline:
         estimate_scale: relative depth with no anchors -- every view's scale is estimated by its registration (Sim(3) ICP,
         _register_with_scale); view 0 keeps config.depth_scale (or its anchors' estimate).
         """
+        self.mesh = None
         if len(self.images) < 2:
             print("Need at least 2 images")
             return None, None, None
@@ -487,6 +489,9 @@ class DepthToReconstructionPipeline:
                     print(f"  Warning: {st['pool_refused']} bricks found the record pool full and are missing from the result "
                           "(raise --grid, the memory budget of the volume)")
             marks.append(("extract_and_filter", clock()))
+            if cfg.extract_mesh:
+                self.mesh = self._extract_mesh(ctx)
+                marks.append(("mesh", clock()))
             # wall time of each stage of this call (host clock; stages end at a point where the host has the stage's result)
             self.timings = {name + "_s": round(t1 - t0, 4) for (name, t1), (_, t0) in zip(marks[1:], marks[:-1])}
         finally:
@@ -544,6 +549,7 @@ class DepthToReconstructionPipeline:
         Every frame must be loaded on every rank's host (load_data); only the rank's own range goes to its GPU."""
         from . import distributed as dd
         world, rank = dist.get_world_size(), dist.get_rank()
+        self.mesh = None
         if len(self.images) < 2:
             print("Need at least 2 images")
             return None, None, None
@@ -668,6 +674,10 @@ class DepthToReconstructionPipeline:
                     keep = ctx.statistical_outlier(xyz, cfg.outlier_nb_neighbors, cfg.outlier_std_ratio, cell_size=2.0 * grid.voxel_size)
                     xyz, rgb = xyz[keep], rgb[keep]
                 self.stats = dict(points_accumulated=tot[0], points_dropped=tot[1], voxels=n_vox, after_outlier_filter=len(xyz))
+                if cfg.extract_mesh:
+                    t0 = time.perf_counter()
+                    self.mesh = self._extract_mesh(ctx)
+                    self.timings["mesh_s"] = round(time.perf_counter() - t0, 4)
                 say(f"\nFinal reconstruction: {len(xyz)} points, {len(self.camera_poses)} cameras")
                 xyz = xyz.astype(np.float64)
         finally:
@@ -695,6 +705,21 @@ class DepthToReconstructionPipeline:
                 fileio.write_ply_binary(out / f"{Path(name).stem}.ply", pts.astype(np.float64), col)
                 n_written += 1
         return n_written
+
+    def _extract_mesh(self, ctx: FusionContext):
+        """marching-cubes mesh of the fused TSDF (gate: config.tsdf_min_weight); stats gain its size"""
+        xyz, rgb, tris = ctx.extract_mesh(min_weight=self.config.tsdf_min_weight)
+        self.stats["mesh_vertices"] = len(xyz)
+        self.stats["mesh_triangles"] = len(tris)
+        print(f"  Mesh: {len(xyz)} vertices, {len(tris)} triangles")
+        return xyz, rgb, tris
+
+    def save_mesh(self, path: str, ascii: bool = False):
+        """Writes the mesh of the last reconstruct() (config.extract_mesh) as PLY (fileio.write_ply_mesh)."""
+        if self.mesh is None:
+            raise ValueError("no mesh: run reconstruct() with config.extract_mesh = True")
+        fileio.write_ply_mesh(path, *self.mesh, ascii=ascii)
+        print(f"Saved mesh to {path}")
 
     def save_reconstruction(self, points, colors, output_path: str, ascii: bool = False):
         fileio.save_reconstruction(points, colors, output_path, ascii=ascii)
