@@ -159,35 +159,57 @@ __global__ __launch_bounds__(256) void depth_tiles_kernel(Cam cam, BatchBufs B, 
     for (int region = blockIdx.x * 4 + wid; region < nrx * nry; region += gridDim.x * 4) {
         const int rx = region % nrx, ry = region / nrx;
         const int u0 = rx * REGION + q4 * 4, v0 = ry * REGION + rq * 4;
-        const int nv = min(4, cam.W - u0);
-        float dd[4][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            dd[i][0] = dd[i][1] = dd[i][2] = dd[i][3] = 0.0f;
-            if (v0 + i < cam.H && u0 < cam.W) {
-                if (vec) {
-                    ld_depth4(depth, (size_t)(v0 + i) * cam.W + u0, dd[i]);
-                } else {
-                    for (int k = 0; k < 4; ++k) dd[i][k] = (k < nv) ? ld_depth(depth, (size_t)(v0 + i) * cam.W + u0 + k) : 0.0f;
-                }
-            }
-        }
         // the lane's block: lowest / highest VALID scaled depth, and whether a pixel of it (inside the image) is not valid
         float mn = qnan, mx = qnan;
         bool bad = false;
+        if (vec && (rx + 1) * REGION <= cam.W && (ry + 1) * REGION <= cam.H) {
+            // (wave-uniform) the region lies wholly inside the image -- all but the last region column and row: no per-pixel
+            // in-image tests, one 64-bit row address per lane
+            const DT *__restrict__ p = depth + ((size_t)v0 * (unsigned)cam.W + (unsigned)u0);
+            float dd[4][4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            float t[4];
+            for (int i = 0; i < 4; ++i) ld_depth4(p, (size_t)i * (unsigned)cam.W, dd[i]);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float d = dd[i][k] * c.sc;
-                const bool in_img = (v0 + i < cam.H) && (k < nv) && (u0 < cam.W);
-                const bool ok = d > c.mind && d < c.maxd;
-                t[k] = (ok && in_img) ? d : qnan;
-                bad = bad || (in_img && !ok);
+            for (int i = 0; i < 4; ++i) {
+                float t[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float d = dd[i][k] * c.sc;
+                    const bool ok = d > c.mind && d < c.maxd;
+                    t[k] = ok ? d : qnan;
+                    bad = bad || !ok;
+                }
+                mn = fminf(fminf(mn, t[0]), fminf(t[1], fminf(t[2], t[3])));    // (NaN operands are passed over)
+                mx = fmaxf(fmaxf(mx, t[0]), fmaxf(t[1], fmaxf(t[2], t[3])));
             }
-            mn = fminf(fminf(mn, t[0]), fminf(t[1], fminf(t[2], t[3])));        // (NaN operands are passed over)
-            mx = fmaxf(fmaxf(mx, t[0]), fmaxf(t[1], fmaxf(t[2], t[3])));
+        } else {
+            const int nv = min(4, cam.W - u0);
+            float dd[4][4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                dd[i][0] = dd[i][1] = dd[i][2] = dd[i][3] = 0.0f;
+                if (v0 + i < cam.H && u0 < cam.W) {
+                    if (vec) {
+                        ld_depth4(depth, (size_t)(v0 + i) * cam.W + u0, dd[i]);
+                    } else {
+                        for (int k = 0; k < 4; ++k) dd[i][k] = (k < nv) ? ld_depth(depth, (size_t)(v0 + i) * cam.W + u0 + k) : 0.0f;
+                    }
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                float t[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float d = dd[i][k] * c.sc;
+                    const bool in_img = (v0 + i < cam.H) && (k < nv) && (u0 < cam.W);
+                    const bool ok = d > c.mind && d < c.maxd;
+                    t[k] = (ok && in_img) ? d : qnan;
+                    bad = bad || (in_img && !ok);
+                }
+                mn = fminf(fminf(mn, t[0]), fminf(t[1], fminf(t[2], t[3])));    // (NaN operands are passed over)
+                mx = fmaxf(fmaxf(mx, t[0]), fmaxf(t[1], fmaxf(t[2], t[3])));
+            }
         }
         // from here on: +inf / -inf for "no valid pixel" (the format of the pyramid), the flag as a number
         mn = (mn == mn) ? mn : INFINITY;
