@@ -351,6 +351,17 @@ int tl3d_extract_mesh(tl3d_ctx *ctx, int min_weight,
                       uint32_t *out_tri_hd, int64_t tri_cap,
                       int64_t *out_n_vert, int64_t *out_n_tri);
 
+/* ray casting of the TSDF channel from one camera: one ray per pixel of the context's camera, pose (R, t)
+ * world->camera as tl3d_integrate.  depth [H][W] f32 (0 = no hit), normals [H][W][3] f32 in the camera frame facing the
+ * camera ((0,0,0) where undefined), colour [H][W][3] BGR (TSDF-mode extraction colour of the hit voxel, 128 without one).
+ * Voxels with weight < max(1, min_weight) are unusable.  z_near <= 0: the context's min_depth; z_far <= 0: its max_depth.
+ * Each output may be NULL, host or device memory.  slot >= 0: the depth (and the colour, when the slot has a colour buffer)
+ * is also written into that frame slot, which then reads as an uploaded f32 frame (tl3d_build_normals, ICP, fusion).
+ * TL3D_E_STATE without a TSDF channel; TL3D_E_INVALID for a null pose or a slot >= n_slots.  No reference code: the
+ * reference has no TSDF. */
+int tl3d_raycast(tl3d_ctx *ctx, const double R[9], const double t[3], int min_weight, double z_near, double z_far,
+                 int slot, float *depth_out_hd, float *normal_out_hd, uint8_t *bgr_out_hd);
+
 /* f1: statistical outlier removal on a point list (Open3D remove_statistical_outlier, D2R:412-415) */
 int tl3d_statistical_outlier(tl3d_ctx *ctx, const float *xyz_hd, int64_t n, int nb_neighbors, double std_ratio,
                              double cell_size, uint8_t *keep_out_hd, int64_t *out_kept);

@@ -8,6 +8,7 @@ additive fields at the end configure the device grid and the ICP pose source.
 from __future__ import annotations
 
 from dataclasses import dataclass
+from typing import Optional
 
 import numpy as np
 
@@ -53,6 +54,8 @@ class ReconstructionConfig:
     device: int = 0
     # marching-cubes mesh of the TSDF after the fusion (DepthToReconstructionPipeline.mesh / save_mesh)
     extract_mesh: bool = False
+    # folder for renders of the fused model at every kept camera (DepthToReconstructionPipeline.reconstruct)
+    render_dir: Optional[str] = None
 
     @property
     def K(self) -> np.ndarray:

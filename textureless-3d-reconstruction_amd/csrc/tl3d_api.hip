@@ -631,6 +631,9 @@ int tl3d_destroy(tl3d_ctx *ctx) {
     if (ctx->mesh_counts) (void)hipFree(ctx->mesh_counts);
     if (ctx->mesh_offsets) (void)hipFree(ctx->mesh_offsets);
     if (ctx->mesh_first) (void)hipFree(ctx->mesh_first);
+    if (ctx->ray_depth) (void)hipFree(ctx->ray_depth);
+    if (ctx->ray_nrm) (void)hipFree(ctx->ray_nrm);
+    if (ctx->ray_bgr) (void)hipFree(ctx->ray_bgr);
     if (ctx->bp_state) (void)hipFree(ctx->bp_state);
     if (ctx->bp_factors) (void)hipFree(ctx->bp_factors);
     if (ctx->bp_stage_xyz) (void)hipFree(ctx->bp_stage_xyz);
@@ -2321,6 +2324,73 @@ int tl3d_extract_mesh(tl3d_ctx *ctx, int min_weight, float *out_xyz, uint8_t *ou
     if (!direct) { (void)hipFree(dxyz); (void)hipFree(drgb); if (dtri) (void)hipFree(dtri); }
     if (rc) return rc;
     if (e != hipSuccess || e2 != hipSuccess) return set_err(TL3D_E_HIP, "mesh copy/sync failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+    return TL3D_OK;
+}
+
+// ------------------------------------------------------------------------------------------- ray casting
+// a device buffer for each output the caller wants on the host (allocated on first use; the camera never changes)
+static int ray_target(void *out, void **staging, size_t bytes, void **dev) {
+    *dev = nullptr;
+    if (!out) return TL3D_OK;
+    if (is_device_ptr(out)) {
+        *dev = out;
+        return TL3D_OK;
+    }
+    if (!*staging && hipMalloc(staging, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        *staging = nullptr;
+        return set_err(TL3D_E_NOMEM, "ray-cast staging alloc (%zu B) failed", bytes);
+    }
+    *dev = *staging;
+    return TL3D_OK;
+}
+
+int tl3d_raycast(tl3d_ctx *ctx, const double R[9], const double t[3], int min_weight, double z_near, double z_far, int slot,
+                 float *depth_out, float *normal_out, uint8_t *bgr_out) {
+    REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
+    REQUIRE(R && t, TL3D_E_INVALID, "null pose");
+    REQUIRE(ctx->tsdf != nullptr, TL3D_E_STATE, "ray casting needs a grid with a TSDF channel");
+    if (slot >= 0) {
+        const int src = check_slot(ctx, slot, false);
+        if (src) return src;
+    }
+    FLUSH_AND_FOLD(ctx);
+    TL3D_HIP(hipSetDevice(ctx->device));
+    const size_t npx = (size_t)ctx->cam.W * ctx->cam.H;
+    void *dd = nullptr, *dn = nullptr, *dc = nullptr;
+    int rc = ray_target(depth_out, (void **)&ctx->ray_depth, npx * sizeof(float), &dd);
+    if (!rc) rc = ray_target(normal_out, (void **)&ctx->ray_nrm, npx * 3 * sizeof(float), &dn);
+    if (!rc) rc = ray_target(bgr_out, (void **)&ctx->ray_bgr, npx * 3, &dc);
+    if (rc) return rc;
+    float *sd = nullptr;
+    uint8_t *sc = nullptr;
+    if (slot >= 0) {
+        Slot &s = ctx->slots[slot];
+        rc = order_after_lanes(ctx, slot, true, true);  // an uncollected ICP run may still read this slot
+        if (rc) return rc;
+        if (!s.depth && !(s.depth = (float *)pool_take(ctx->pool_depth))) return set_err(TL3D_E_NOMEM, "frame alloc failed");
+        sd = s.depth;
+        sc = s.bgr;                                      // colour only into a slot that has a colour buffer
+    }
+    const float zn = (float)(z_near > 0.0 ? z_near : ctx->cfg.min_depth);
+    const float zf = (float)(z_far > 0.0 ? z_far : ctx->cfg.max_depth);
+    rc = launch_raycast(ctx->stream, ctx->cam, ctx->grid, R, t, min_weight, zn, zf, ctx->tsdf, ctx->centroid, (float *)dd, sd,
+                        (float *)dn, (uint8_t *)dc, sc);
+    if (rc) return rc;
+    if (slot >= 0) {                                     // the slot now holds an f32 frame, as after an upload
+        Slot &s = ctx->slots[slot];
+        s.has_u16 = false;
+        s.has_color = s.bgr != nullptr;
+        s.loaded = true;
+        s.has_normals = false;
+        s.smooth_radius = 0;
+        if (!s.ev_upload) TL3D_HIP(hipEventCreateWithFlags(&s.ev_upload, hipEventDisableTiming));
+        TL3D_HIP(hipEventRecord(s.ev_upload, ctx->stream));
+    }
+    if (depth_out && dd != depth_out) TL3D_HIP(hipMemcpyAsync(depth_out, dd, npx * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (normal_out && dn != normal_out) TL3D_HIP(hipMemcpyAsync(normal_out, dn, npx * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (bgr_out && dc != bgr_out) TL3D_HIP(hipMemcpyAsync(bgr_out, dc, npx * 3, hipMemcpyDeviceToHost, ctx->stream));
+    TL3D_HIP(hipStreamSynchronize(ctx->stream));
     return TL3D_OK;
 }
 

@@ -218,6 +218,9 @@ struct tl3d_ctx {
     size_t mesh_blocks;
     unsigned *mesh_first;
     size_t mesh_first_n;
+    // tl3d_raycast: device staging of the outputs a caller wants on the host ([H][W] f32, [H][W][3] f32, [H][W][3] u8; grown on demand)
+    float *ray_depth, *ray_nrm;
+    uint8_t *ray_bgr;
     unsigned long long *bp_state;        // one-launch back-projection: ticket, error word, per-tile granules, [bp_state_words - 1] = total
     size_t bp_state_words;
     float *bp_stage_xyz;                 // staging for host-side outputs, sized for a full frame at subsample 1
@@ -463,6 +466,10 @@ int launch_mesh_count(hipStream_t s, const Grid &g, int min_weight, const int2 *
 int launch_mesh_write(hipStream_t s, const Grid &g, int min_weight, const int2 *tsdf, const unsigned long long *cen,
                       const unsigned long long *voffsets, const unsigned long long *toffsets, int nblocks, unsigned *first_id,
                       float *xyz, uint8_t *rgb, unsigned long long vcap, unsigned *tris, unsigned long long tcap);
+// ray casting
+int launch_raycast(hipStream_t s, const Cam &cam, const Grid &g, const double R[9], const double t[3], int min_weight, float z_near,
+                   float z_far, const int2 *tsdf, const unsigned long long *cen, float *depth, float *depth2, float *nrm, uint8_t *bgr,
+                   uint8_t *bgr2);
 // grids
 int launch_max_weight(hipStream_t s, const Grid &g, const int2 *pool, int *d_out);
 int launch_max_weight_dense(hipStream_t s, const int2 *grid, size_t nvox, int *d_out);

@@ -591,6 +591,23 @@ class FusionContext:
                                                   nt.value, C.byref(nv), C.byref(nt)))
         return xyz, rgb, tris
 
+    def raycast(self, pose, min_weight: int = 0, z_near=None, z_far=None, slot=None, out=None):
+        """Ray-cast the TSDF channel from the camera at pose = (R, t) (world->camera, as integrate):
+        (depth f32 [H,W] with 0 = no hit, normals f32 [H,W,3] in the camera frame, bgr u8 [H,W,3]).  z_near / z_far default to
+        the context's depth range.  slot: also write the view into that frame slot (an f32 frame with colour for
+        build_normals, icp and fusion).  out: (depth, normals, bgr) host arrays or device tensors to fill (entries may be None)
+        instead of new arrays; they are returned."""
+        r, t = abi.d9(pose[0]), abi.d3(pose[1])
+        if out is None:
+            out = (np.empty((self.height, self.width), np.float32), np.empty((self.height, self.width, 3), np.float32),
+                   np.empty((self.height, self.width, 3), np.uint8))
+        for a, shape in zip(out, ((self.height, self.width), (self.height, self.width, 3), (self.height, self.width, 3))):
+            assert a is None or tuple(a.shape) == shape, f"output {tuple(a.shape)} != {shape}"
+        abi.check(self._lib.tl3d_raycast(self._h, abi.ptr(r), abi.ptr(t), int(min_weight),
+                                         float(z_near) if z_near is not None else 0.0, float(z_far) if z_far is not None else 0.0,
+                                         -1 if slot is None else int(slot), abi.ptr(out[0]), abi.ptr(out[1]), abi.ptr(out[2])))
+        return tuple(out)
+
     def statistical_outlier(self, xyz, nb_neighbors=20, std_ratio=2.0, cell_size=None):
         xyz = np.ascontiguousarray(xyz, dtype=np.float32)
         keep = np.zeros(len(xyz), np.uint8)

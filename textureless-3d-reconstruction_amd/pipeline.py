@@ -492,6 +492,9 @@ class DepthToReconstructionPipeline:
             if cfg.extract_mesh:
                 self.mesh = self._extract_mesh(ctx)
                 marks.append(("mesh", clock()))
+            if cfg.render_dir:
+                self._render_views(ctx)
+                marks.append(("render", clock()))
             # wall time of each stage of this call (host clock; stages end at a point where the host has the stage's result)
             self.timings = {name + "_s": round(t1 - t0, 4) for (name, t1), (_, t0) in zip(marks[1:], marks[:-1])}
         finally:
@@ -713,6 +716,28 @@ class DepthToReconstructionPipeline:
         self.stats["mesh_triangles"] = len(tris)
         print(f"  Mesh: {len(xyz)} vertices, {len(tris)} triangles")
         return xyz, rgb, tris
+
+    def _render_views(self, ctx: FusionContext):
+        """The fused model rendered at every kept camera (FusionContext.raycast, gate config.tsdf_min_weight) into
+        config.render_dir: <stem>_model_depth.npy / .png (fileio.save_depth_like_processor) and <stem>_model_color.png (RGB).
+        stats gain render_views and render_residual_mm: per camera the median of |z_model - z_frame * scale| over the pixels
+        valid in both, in millimetres (None when no pixel is)."""
+        from pathlib import Path
+        from PIL import Image
+        out = Path(self.config.render_dir)
+        out.mkdir(parents=True, exist_ok=True)
+        residual = []
+        for fi, pose in zip(self.frame_index, self.camera_poses):
+            depth, _, bgr = ctx.raycast(pose, min_weight=self.config.tsdf_min_weight)
+            stem = Path(self.image_names[fi]).stem
+            fileio.save_depth_like_processor(depth, out, f"{stem}_model")
+            Image.fromarray(np.ascontiguousarray(bgr[..., ::-1])).save(str(out / f"{stem}_model_color.png"))
+            z = ctx.download_depth(fi).astype(np.float64) * float(self.scales[fi])
+            both = (depth > 0) & np.isfinite(z) & (z > 0)
+            residual.append(round(float(np.median(np.abs(depth[both] - z[both]))) * 1e3, 4) if both.any() else None)
+        self.stats["render_views"] = len(residual)
+        self.stats["render_residual_mm"] = residual
+        print(f"  Rendered the model at {len(residual)} cameras into {out}")
 
     def save_mesh(self, path: str, ascii: bool = False):
         """Writes the mesh of the last reconstruct() (config.extract_mesh) as PLY (fileio.write_ply_mesh)."""
