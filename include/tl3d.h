@@ -100,8 +100,11 @@ typedef struct tl3d_config {
     int64_t voxel_offset[3];    /* the grid is a BLOCK of a larger voxel lattice: its voxel (0,0,0) is voxel voxel_offset of the lattice that
                                    starts at `origin` (multiples of TL3D_BRICK).  Voxel indices are computed against `origin` as ever (Open3D:
                                    floor((p - origin) / voxel), D2R:404-410) and the offset is subtracted: a lattice of more than 2^32
-                                   voxels is fused block by block with identical voxels (DenseReconstructor.merge_pointclouds does).  Centroid
-                                   channel only: a grid with a TSDF channel must have offset 0.                                      */
+                                   voxels is fused block by block with identical voxels (DenseReconstructor.merge_pointclouds does).  Both
+                                   channels: the TSDF kernels place voxel i at the lattice index offset + i, so a block's TSDF records are
+                                   the single lattice's bit for bit; a grid with a TSDF channel must end within 2^23 voxels of the lattice
+                                   origin on every axis (offset + n <= 2^23: the f32 index arithmetic stays exact).  tl3d_raycast refuses
+                                   a grid with an offset.                                                                            */
 } tl3d_config;
 
 /* Result of an ICP run (device solve, read back once at the end). */
@@ -302,6 +305,19 @@ int tl3d_icp_batch_collect(tl3d_ctx *ctx, tl3d_icp_result *out /* [n_pairs] */, 
 /* Give a context created with channels = 0 its grid later (geometry fields of cfg: channels, nx, ny, nz, origin,
  * voxel_size, sdf_trunc, ext_*): frames stay resident while poses and scene bounds are still being computed. */
 int tl3d_attach_grid(tl3d_ctx *ctx, const tl3d_config *cfg);
+/* Free the grid of a context: channels, brick tables, free-space counters and every grid-sized scratch (pending updates are
+ * issued first).  Frames, normal maps and ICP state stay resident, and tl3d_attach_grid works again: one context fuses a lattice
+ * of more than 2^32 voxels block after block.  TL3D_E_STATE on a context without a grid.  Clears the block core. */
+int tl3d_detach_grid(tl3d_ctx *ctx);
+/* Make the attached grid one BLOCK of a lattice of lattice_dims voxels (whose voxel 0 is the grid's voxel -voxel_offset) and give it
+ * a CORE [lo, hi) of grid-local voxels (multiples of TL3D_BRICK; the rest of the grid is its halo).  With a core: tl3d_extract emits
+ * only the voxels in the core (centroid mode) or the owner voxels in the core (TSDF mode); tl3d_extract_mesh emits the triangles of
+ * the cells whose min corner lies in the core (vertices as without a core); tl3d_stats.centroid_points counts the samples that
+ * landed in the core and centroid_dropped the rest (samples in the halo are still accumulated).  Disjoint cores that tile the
+ * lattice, each with a halo of one brick on the + sides that have a neighbour, give the single lattice's points and mesh
+ * (DESIGN §3).  NULL arguments clear the core (tl3d_detach_grid does too).  TL3D_E_INVALID for a lattice of 2^61 voxels or more
+ * (mesh keys would overflow); TL3D_E_STATE without a grid. */
+int tl3d_set_block_core(tl3d_ctx *ctx, const int64_t lattice_dims[3], const int32_t lo[3], const int32_t hi[3]);
 int tl3d_grid_reset(tl3d_ctx *ctx);
 int tl3d_grid_device_ptr(tl3d_ctx *ctx, uint32_t channel, void **ptr, size_t *bytes);
 int tl3d_grid_download(tl3d_ctx *ctx, uint32_t channel, void *out_hd, size_t bytes);
@@ -350,6 +366,13 @@ int tl3d_extract_mesh(tl3d_ctx *ctx, int min_weight,
                       float *out_xyz_hd, uint8_t *out_rgb_hd, int64_t vert_cap,
                       uint32_t *out_tri_hd, int64_t tri_cap,
                       int64_t *out_n_vert, int64_t *out_n_tri);
+/* The same, plus one int64 KEY per vertex: 3 * (lattice linear index of the owner voxel, x fastest, over the lattice of
+ * tl3d_set_block_core -- without a core: voxel_offset + grid dims) + axis.  Equal keys = the same vertex in another block: what
+ * lets a host weld the meshes of neighbouring blocks exactly. */
+int tl3d_extract_mesh_keyed(tl3d_ctx *ctx, int min_weight,
+                            float *out_xyz_hd, uint8_t *out_rgb_hd, int64_t vert_cap,
+                            uint32_t *out_tri_hd, int64_t tri_cap, int64_t *out_key_hd,
+                            int64_t *out_n_vert, int64_t *out_n_tri);
 
 /* ray casting of the TSDF channel from one camera: one ray per pixel of the context's camera, pose (R, t)
  * world->camera as tl3d_integrate.  depth [H][W] f32 (0 = no hit), normals [H][W][3] f32 in the camera frame facing the
@@ -357,8 +380,8 @@ int tl3d_extract_mesh(tl3d_ctx *ctx, int min_weight,
  * Voxels with weight < max(1, min_weight) are unusable.  z_near <= 0: the context's min_depth; z_far <= 0: its max_depth.
  * Each output may be NULL, host or device memory.  slot >= 0: the depth (and the colour, when the slot has a colour buffer)
  * is also written into that frame slot, which then reads as an uploaded f32 frame (tl3d_build_normals, ICP, fusion).
- * TL3D_E_STATE without a TSDF channel; TL3D_E_INVALID for a null pose or a slot >= n_slots.  No reference code: the
- * reference has no TSDF. */
+ * TL3D_E_STATE without a TSDF channel, and on a block (a grid with a voxel offset or a core: blocked ray casting does not
+ * exist); TL3D_E_INVALID for a null pose or a slot >= n_slots.  No reference code: the reference has no TSDF. */
 int tl3d_raycast(tl3d_ctx *ctx, const double R[9], const double t[3], int min_weight, double z_near, double z_far,
                  int slot, float *depth_out_hd, float *normal_out_hd, uint8_t *bgr_out_hd);
 

@@ -23,10 +23,10 @@ TSDF_MAX_WEIGHT = 65536
 SYMBOLS = [
     "tl3d_last_error", "tl3d_version", "tl3d_device_count", "tl3d_runtime_info", "tl3d_probe_hw_queues", "tl3d_grid_max_weight", "tl3d_create", "tl3d_destroy", "tl3d_sync", "tl3d_get_stream", "tl3d_release_cached_memory",
     "tl3d_upload_frame", "tl3d_download_depth", "tl3d_pinned_alloc", "tl3d_pinned_free", "tl3d_upload_frame_async",
-    "tl3d_slot_wait", "tl3d_attach_grid", "tl3d_backproject", "tl3d_backproject_device", "tl3d_frame_bounds", "tl3d_frames_bounds", "tl3d_count_bricks", "tl3d_accumulate_centroid",
+    "tl3d_slot_wait", "tl3d_attach_grid", "tl3d_detach_grid", "tl3d_set_block_core", "tl3d_backproject", "tl3d_backproject_device", "tl3d_frame_bounds", "tl3d_frames_bounds", "tl3d_count_bricks", "tl3d_accumulate_centroid",
     "tl3d_accumulate_points", "tl3d_points_bounds", "tl3d_integrate", "tl3d_build_normals",
     "tl3d_download_normals", "tl3d_icp_p2plane", "tl3d_icp_enqueue", "tl3d_icp_collect", "tl3d_icp_batch_enqueue", "tl3d_icp_batch_collect", "tl3d_host_pack_bgr_rows", "tl3d_host_copy_rows", "tl3d_build_normals_many", "tl3d_fuse_frames", "tl3d_grid_reset", "tl3d_grid_device_ptr",
-    "tl3d_grid_download", "tl3d_grid_upload", "tl3d_grid_add", "tl3d_grid_touched_bricks", "tl3d_grid_pack_bricks", "tl3d_grid_unpack_bricks", "tl3d_rccl_unique_id", "tl3d_rccl_init", "tl3d_allreduce_grid", "tl3d_extract", "tl3d_extract_mesh", "tl3d_raycast", "tl3d_statistical_outlier",
+    "tl3d_grid_download", "tl3d_grid_upload", "tl3d_grid_add", "tl3d_grid_touched_bricks", "tl3d_grid_pack_bricks", "tl3d_grid_unpack_bricks", "tl3d_rccl_unique_id", "tl3d_rccl_init", "tl3d_allreduce_grid", "tl3d_extract", "tl3d_extract_mesh", "tl3d_extract_mesh_keyed", "tl3d_raycast", "tl3d_statistical_outlier",
     "tl3d_set_profile", "tl3d_set_normal_smoothing", "tl3d_set_tsdf_pairing", "tl3d_get_stats", "tl3d_reset_stats", "tl3d_event_record", "tl3d_event_elapsed_ms",
 ]
 
@@ -171,6 +171,8 @@ def load():
         "tl3d_upload_frame_async": [vp, i32, vp, i32, vp],
         "tl3d_slot_wait": [vp, i32],
         "tl3d_attach_grid": [vp, C.POINTER(Config)],
+        "tl3d_detach_grid": [vp],
+        "tl3d_set_block_core": [vp, vp, vp, vp],
         "tl3d_backproject": [vp, i32, vp, vp, dbl, u32, i32, dbl, dbl, vp, vp, i64, C.POINTER(i64)],
         "tl3d_backproject_device": [vp, i32, vp, vp, dbl, u32, i32, dbl, dbl, vp, vp, i64, vp],
         "tl3d_frame_bounds": [vp, i32, vp, vp, dbl, u32, i32, dbl, dbl, vp, vp, vp],
@@ -201,6 +203,7 @@ def load():
         "tl3d_allreduce_grid": [vp, u32],
         "tl3d_extract": [vp, i32, i32, i32, dbl, vp, vp, i64, C.POINTER(i64)],
         "tl3d_extract_mesh": [vp, i32, vp, vp, i64, vp, i64, C.POINTER(i64), C.POINTER(i64)],
+        "tl3d_extract_mesh_keyed": [vp, i32, vp, vp, i64, vp, i64, vp, C.POINTER(i64), C.POINTER(i64)],
         "tl3d_raycast": [vp, vp, vp, i32, dbl, dbl, i32, vp, vp, vp],
         "tl3d_statistical_outlier": [vp, vp, i64, i32, dbl, dbl, vp, C.POINTER(i64)],
         "tl3d_set_profile": [vp, i32, i32],

@@ -17,11 +17,13 @@ namespace tl3d {
 struct CenAdd {
     unsigned long long rec;      // record index, ~0ull if none
     unsigned long long a, b, c, d;
+    bool core;                   // the voxel lies in the grid's block core (statistics: tl3d_stats.centroid_points)
 };
 
 __device__ __forceinline__ CenAdd centroid_key(const Grid &g, const float p[3], unsigned r8, unsigned g8, unsigned b8) {
     CenAdd o;
     o.rec = ~0ull;
+    o.core = false;
     const double org[3] = {g.oxd, g.oyd, g.ozd};
     const double off[3] = {g.offx, g.offy, g.offz};
     const int dims[3] = {g.nx, g.ny, g.nz};
@@ -39,6 +41,7 @@ __device__ __forceinline__ CenAdd centroid_key(const Grid &g, const float p[3], 
         q[a] = (unsigned long long)qq;
     }
     o.rec = (unsigned long long)vox_index(idx[0], idx[1], idx[2], g.nbx, g.nby);
+    o.core = in_core(g, idx[0], idx[1], idx[2]);
     o.a = q[0] | (q[1] << 32);
     o.b = q[2] | (1ull << 32);
     o.c = (unsigned long long)r8 | ((unsigned long long)g8 << 32);
@@ -223,7 +226,7 @@ __global__ __launch_bounds__(256) void centroid_frame_kernel(Cam cam, Grid g, co
         bool valid;
         CenAdd k = centroid_sample(cam, g, a, p, depth, VAR == 4 ? nullptr : bgr, xf, yf, us, vs, valid);
         nvalid += valid ? 1 : 0;
-        nkept += (k.rec != ~0ull) ? 1 : 0;
+        nkept += (k.rec != ~0ull && k.core) ? 1 : 0;
         if (VAR == 3) { if (k.rec == 12345ull) nkept += (int)k.a; continue; }      // timing ablation: samples only
         if (centroid_reduce_runs(k)) {                            // one lane per run of equal voxels: into the LDS table
             const unsigned long long key = k.rec + 1ull;
@@ -284,7 +287,7 @@ __global__ __launch_bounds__(256) void centroid_direct_kernel(Cam cam, Grid g, c
     const int vs = (int)(s / a.Ws), us = (int)(s - (long long)vs * a.Ws);
     bool valid;
     CenAdd k = centroid_sample(cam, g, a, p, depth, bgr, xf, yf, s < ns ? us : a.Ws, vs, valid);
-    centroid_stats(valid ? 1 : 0, (k.rec != ~0ull) ? 1 : 0, counters);
+    centroid_stats(valid ? 1 : 0, (k.rec != ~0ull && k.core) ? 1 : 0, counters);
     __shared__ unsigned long long s_stage[4][64][5];
     centroid_commit_runs(g, k, grid, s_stage[threadIdx.x >> 6], counters);
 }
@@ -302,7 +305,7 @@ __global__ __launch_bounds__(256) void centroid_points_kernel(Grid g, const floa
         const float pt[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
         k = centroid_key(g, pt, rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]);
     }
-    centroid_stats(valid ? 1 : 0, (k.rec != ~0ull) ? 1 : 0, counters);
+    centroid_stats(valid ? 1 : 0, (k.rec != ~0ull && k.core) ? 1 : 0, counters);
     __shared__ unsigned long long s_stage[4][64][5];
     centroid_commit_runs(g, k, grid, s_stage[threadIdx.x >> 6], counters);
 }

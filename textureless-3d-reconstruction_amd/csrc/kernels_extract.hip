@@ -21,6 +21,7 @@ __device__ __forceinline__ int extract_record(const Grid &g, const ExtArgs &a, c
                                               uint8_t *__restrict__ rgb, unsigned long long o, unsigned long long cap) {
     int ijk[3];
     rec_coords(idx, g.nbx, g.nby, ijk[0], ijk[1], ijk[2]);
+    if (!in_core(g, ijk[0], ijk[1], ijk[2])) return 0;           // a block emits what its core owns (tl3d_set_block_core)
     const double org[3] = {g.oxd, g.oyd, g.ozd};
     const double off[3] = {g.offx, g.offy, g.offz};
     if (a.mode == TL3D_EXTRACT_CENTROID) {
@@ -74,7 +75,7 @@ __device__ __forceinline__ int extract_record(const Grid &g, const ExtArgs &a, c
             const double frac = r0 / (r0 + r1);
 #pragma unroll
             for (int ax = 0; ax < 3; ++ax) {
-                const double cc = org[ax] + ((double)ijk[ax] + 0.5) * g.vsd;
+                const double cc = org[ax] + ((off[ax] + (double)ijk[ax]) + 0.5) * g.vsd;     // lattice index: exact in fp64
                 xyz[3 * oo + ax] = (float)(ax == e ? cc + frac * g.vsd : cc);
             }
             uint8_t c[3] = {128, 128, 128};

@@ -18,6 +18,7 @@ namespace tl3d {
 struct MeshArgs {
     int mw;                      // max(1, min_weight)
     int nx, ny, nz;
+    long long lx, ly;            // keyed extraction: lattice dims along x and y (key = 3 * lattice linear index of the owner + axis)
 };
 
 // t of voxel (i, j, k), which must lie in the grid; returns usability
@@ -58,6 +59,7 @@ __device__ __forceinline__ void analyse(const Grid &g, const MeshArgs &a, const 
     if (!load_t(g, tsdf, a.mw, r.i + 1, r.j, r.k + 1, t5)) return;
     if (!load_t(g, tsdf, a.mw, r.i, r.j + 1, r.k + 1, t6)) return;
     if (!load_t(g, tsdf, a.mw, r.i + 1, r.j + 1, r.k + 1, t7)) return;
+    if (!in_core(g, r.i, r.j, r.k)) return;                         // a block meshes the cells its core owns (tl3d_set_block_core)
     r.cas = (in0 ? 1u : 0u) | (ix ? 2u : 0u) | (iy ? 4u : 0u) | (t3 < 0.0 ? 8u : 0u) | (iz ? 16u : 0u) | (t5 < 0.0 ? 32u : 0u) |
             (t6 < 0.0 ? 64u : 0u) | (t7 < 0.0 ? 128u : 0u);
 }
@@ -119,11 +121,13 @@ __global__ __launch_bounds__(256) void mesh_count_kernel(Grid g, MeshArgs a, con
 __global__ __launch_bounds__(256) void mesh_vert_kernel(Grid g, MeshArgs a, const int2 *__restrict__ tsdf,
                                                         const unsigned long long *__restrict__ cen, size_t nvox,
                                                         const unsigned long long *__restrict__ offsets, unsigned *__restrict__ first_id,
-                                                        float *__restrict__ xyz, uint8_t *__restrict__ rgb, unsigned long long cap) {
+                                                        float *__restrict__ xyz, uint8_t *__restrict__ rgb, unsigned long long cap,
+                                                        long long *__restrict__ keys) {
     __shared__ unsigned sm[4];
     unsigned long long run = offsets[blockIdx.x];
     const size_t base = (size_t)blockIdx.x * EXTRACT_CHUNK;
     const double org[3] = {g.oxd, g.oyd, g.ozd};
+    const double off[3] = {g.offx, g.offy, g.offz};
 #pragma unroll 1
     for (int it = 0; it < EXTRACT_CHUNK / 256; ++it) {
         const size_t idx = base + (size_t)it * 256 + threadIdx.x;
@@ -149,9 +153,11 @@ __global__ __launch_bounds__(256) void mesh_vert_kernel(Grid g, MeshArgs a, cons
                 const double frac = r0 / (r0 + r1);
 #pragma unroll
                 for (int ax = 0; ax < 3; ++ax) {
-                    const double cc = org[ax] + ((double)ijk[ax] + 0.5) * g.vsd;
+                    const double cc = org[ax] + ((off[ax] + (double)ijk[ax]) + 0.5) * g.vsd;     // lattice index: exact in fp64
                     xyz[3 * oo + ax] = (float)(ax == e ? cc + frac * g.vsd : cc);
                 }
+                if (keys)
+                    keys[oo] = 3 * ((((long long)g.voz + r.k) * a.ly + ((long long)g.voy + r.j)) * a.lx + ((long long)g.vox + r.i)) + e;
                 uint8_t col[3] = {128, 128, 128};
                 if (cen) {
                     const size_t jdx = vox_index(r.i + (e == 0), r.j + (e == 1), r.k + (e == 2), g.nbx, g.nby);
@@ -232,8 +238,8 @@ __global__ __launch_bounds__(256) void mesh_tri_kernel(Grid g, MeshArgs a, const
     }
 }
 
-static MeshArgs mesh_args(const Grid &g, int min_weight) {
-    return MeshArgs{min_weight < 1 ? 1 : min_weight, g.nx, g.ny, g.nz};
+static MeshArgs mesh_args(const Grid &g, int min_weight, const long long *lat = nullptr) {
+    return MeshArgs{min_weight < 1 ? 1 : min_weight, g.nx, g.ny, g.nz, lat ? lat[0] : 0ll, lat ? lat[1] : 0ll};
 }
 
 int launch_mesh_count(hipStream_t s, const Grid &g, int min_weight, const int2 *tsdf, unsigned *vcounts, unsigned *tcounts,
@@ -246,10 +252,11 @@ int launch_mesh_count(hipStream_t s, const Grid &g, int min_weight, const int2 *
 
 int launch_mesh_write(hipStream_t s, const Grid &g, int min_weight, const int2 *tsdf, const unsigned long long *cen,
                       const unsigned long long *voffsets, const unsigned long long *toffsets, int nblocks, unsigned *first_id,
-                      float *xyz, uint8_t *rgb, unsigned long long vcap, unsigned *tris, unsigned long long tcap) {
+                      float *xyz, uint8_t *rgb, unsigned long long vcap, unsigned *tris, unsigned long long tcap,
+                      long long *keys, const long long *lat) {
     const size_t nvox = (size_t)g.nx * g.ny * g.nz;
-    const MeshArgs a = mesh_args(g, min_weight);
-    hipLaunchKernelGGL(mesh_vert_kernel, dim3(nblocks), dim3(256), 0, s, g, a, tsdf, cen, nvox, voffsets, first_id, xyz, rgb, vcap);
+    const MeshArgs a = mesh_args(g, min_weight, lat);
+    hipLaunchKernelGGL(mesh_vert_kernel, dim3(nblocks), dim3(256), 0, s, g, a, tsdf, cen, nvox, voffsets, first_id, xyz, rgb, vcap, keys);
     TL3D_HIP(hipGetLastError());
     hipLaunchKernelGGL(mesh_tri_kernel, dim3(nblocks), dim3(256), 0, s, g, a, tsdf, nvox, toffsets, first_id, tris, tcap);
     TL3D_HIP(hipGetLastError());

@@ -267,8 +267,8 @@ __global__ __launch_bounds__(256) void tile_pyramid_kernel(Cam cam, Grid g, Frus
             bool in = false;
             if (cell < ncx * ncy * ncz) {
                 const int ccx = cell % ncx, ccy = (cell / ncx) % ncy, ccz = cell / (ncx * ncy);
-                const float qx = fmaf((float)(ccx * 32 + 16), g.vs, g.ox), qy = fmaf((float)(ccy * 32 + 16), g.vs, g.oy);
-                const float qz = fmaf((float)(ccz * 32 + 16), g.vs, g.oz);
+                const float qx = fmaf((float)(g.vox + ccx * 32 + 16), g.vs, g.ox), qy = fmaf((float)(g.voy + ccy * 32 + 16), g.vs, g.oy);
+                const float qz = fmaf((float)(g.voz + ccz * 32 + 16), g.vs, g.oz);
                 const float ex = pose.r[0] * qx + pose.r[1] * qy + pose.r[2] * qz + pose.t[0];
                 const float ey = pose.r[3] * qx + pose.r[4] * qy + pose.r[5] * qz + pose.t[1];
                 const float ez = pose.r[6] * qx + pose.r[7] * qy + pose.r[8] * qz + pose.t[2];
@@ -363,16 +363,16 @@ __global__ __launch_bounds__(256) void brick_cull_kernel(Cam cam, Grid g, BatchB
         const bool in_grid = bx < g.nbx && by < g.nby && bz < g.nbz;
         brick = (bz * g.nby + by) * g.nbx + bx;
         const float crad = 27.712812f * g.vs * 1.01f;               // half diagonal of a 32^3-voxel cell, +1 %
-        const float qx = fmaf((float)(ccx * 32 + 16), g.vs, g.ox), qy = fmaf((float)(ccy * 32 + 16), g.vs, g.oy);
-        const float qz = fmaf((float)(ccz * 32 + 16), g.vs, g.oz);
+        const float qx = fmaf((float)(g.vox + ccx * 32 + 16), g.vs, g.ox), qy = fmaf((float)(g.voy + ccy * 32 + 16), g.vs, g.oy);
+        const float qz = fmaf((float)(g.voz + ccz * 32 + 16), g.vs, g.oz);
         const float ex = pose.r[0] * qx + pose.r[1] * qy + pose.r[2] * qz + pose.t[0];
         const float ey = pose.r[3] * qx + pose.r[4] * qy + pose.r[5] * qz + pose.t[1];
         const float ez = pose.r[6] * qx + pose.r[7] * qy + pose.r[8] * qz + pose.t[2];
         if (sphere_in_view(fr, ex, ey, ez, crad) && in_grid) {
             const float rad = 6.9282032f * g.vs * 1.01f;             // half diagonal of a brick, +1 %
-            const float wx = fmaf((float)(bx * 8 + 4), g.vs, g.ox);
-            const float wy = fmaf((float)(by * 8 + 4), g.vs, g.oy);
-            const float wz = fmaf((float)(bz * 8 + 4), g.vs, g.oz);
+            const float wx = fmaf((float)(g.vox + bx * 8 + 4), g.vs, g.ox);
+            const float wy = fmaf((float)(g.voy + by * 8 + 4), g.vs, g.oy);
+            const float wz = fmaf((float)(g.voz + bz * 8 + 4), g.vs, g.oz);
             const float cxm = pose.r[0] * wx + pose.r[1] * wy + pose.r[2] * wz + pose.t[0];
             const float cym = pose.r[3] * wx + pose.r[4] * wy + pose.r[5] * wz + pose.t[1];
             const float czm = pose.r[6] * wx + pose.r[7] * wy + pose.r[8] * wz + pose.t[2];
@@ -533,9 +533,9 @@ __device__ __forceinline__ int classify_subbrick(const Cam &cam, const Grid &g, 
     float wx[2], wy[2], wz[2];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-        wx[h] = fmaf((float)(i0 + 3 * h) + 0.5f, g.vs, g.ox);
-        wy[h] = fmaf((float)(j0 + 3 * h) + 0.5f, g.vs, g.oy);
-        wz[h] = fmaf((float)(k0 + 3 * h) + 0.5f, g.vs, g.oz);
+        wx[h] = fmaf((float)(g.vox + i0 + 3 * h) + 0.5f, g.vs, g.ox);
+        wy[h] = fmaf((float)(g.voy + j0 + 3 * h) + 0.5f, g.vs, g.oy);
+        wz[h] = fmaf((float)(g.voz + k0 + 3 * h) + 0.5f, g.vs, g.oz);
     }
     float x[8], y[8], z[8];
     float zmin = INFINITY, zmax = -INFINITY;
@@ -780,9 +780,9 @@ __global__ __launch_bounds__(256, TL3D_UPD_WAVES) void tsdf_update_kernel(Cam ca
         float wx[2], wy[2], wz[2];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            wx[h] = fmaf((float)(bx * 8 + 4 * h + (lane & 3)) + 0.5f, g.vs, g.ox);
-            wy[h] = fmaf((float)(by * 8 + 4 * h + ((lane >> 2) & 3)) + 0.5f, g.vs, g.oy);
-            wz[h] = fmaf((float)(bz * 8 + 4 * h + (lane >> 4)) + 0.5f, g.vs, g.oz);
+            wx[h] = fmaf((float)(g.vox + bx * 8 + 4 * h + (lane & 3)) + 0.5f, g.vs, g.ox);
+            wy[h] = fmaf((float)(g.voy + by * 8 + 4 * h + ((lane >> 2) & 3)) + 0.5f, g.vs, g.oy);
+            wz[h] = fmaf((float)(g.voz + bz * 8 + 4 * h + (lane >> 4)) + 0.5f, g.vs, g.oz);
         }
         // running sums of the lane's eight voxels, packed: bits 0-20 sum of (q + 32768) (<= 32 x 65535 < 2^21), bits 21-26 weight
         unsigned acc[8];
@@ -1036,11 +1036,13 @@ __global__ __launch_bounds__(256, UPD_WAVES) void tsdf_update_pairs_kernel(Cam c
         if (lane >= B.n_frames) subv = 0u;
         const int bx = (int)(brick % (unsigned)g.nbx), by = (int)((brick / (unsigned)g.nbx) % (unsigned)g.nby), bz = (int)(brick / (unsigned)(g.nbx * g.nby));
         // the lane's voxel in sub-brick s is (4 (s & 1) + (lane & 3), 4 (s >> 1 & 1) + (lane >> 2 & 3), 4 (s >> 2) + (lane >> 4)); its
-        // centre along an axis: fma(i + 0.5, voxel, origin) -- two values per axis (named scalars: an array indexed by a bit of s
-        // would be moved to LDS by the compiler)
-        const float wx0 = fmaf((float)(bx * 8 + (lane & 3)) + 0.5f, g.vs, g.ox), wx1 = fmaf((float)(bx * 8 + 4 + (lane & 3)) + 0.5f, g.vs, g.ox);
-        const float wy0 = fmaf((float)(by * 8 + ((lane >> 2) & 3)) + 0.5f, g.vs, g.oy), wy1 = fmaf((float)(by * 8 + 4 + ((lane >> 2) & 3)) + 0.5f, g.vs, g.oy);
-        const float wz0 = fmaf((float)(bz * 8 + (lane >> 4)) + 0.5f, g.vs, g.oz), wz1 = fmaf((float)(bz * 8 + 4 + (lane >> 4)) + 0.5f, g.vs, g.oz);
+        // centre along an axis: fma(i + 0.5, voxel, origin) with i the LATTICE index (the grid's offset + its own: one scalar add
+        // per brick; a multiple of 8, so the in-brick part goes in with an OR: 55 VGPRs, where an add took 58) -- two values per axis
+        // (named scalars: an array indexed by a bit of s would be moved to LDS by the compiler)
+        const int lx = g.vox + bx * 8, ly = g.voy + by * 8, lz = g.voz + bz * 8;
+        const float wx0 = fmaf((float)(lx | (lane & 3)) + 0.5f, g.vs, g.ox), wx1 = fmaf((float)(lx | 4 | (lane & 3)) + 0.5f, g.vs, g.ox);
+        const float wy0 = fmaf((float)(ly | ((lane >> 2) & 3)) + 0.5f, g.vs, g.oy), wy1 = fmaf((float)(ly | 4 | ((lane >> 2) & 3)) + 0.5f, g.vs, g.oy);
+        const float wz0 = fmaf((float)(lz | (lane >> 4)) + 0.5f, g.vs, g.oz), wz1 = fmaf((float)(lz | 4 | (lane >> 4)) + 0.5f, g.vs, g.oz);
         // the brick's pairs: lane f holds frame f's masks.  Pairs = set MIXED bits; FREE sub-bricks are counted per sub-brick over
         // the frames and start the running sums; touched = sub-bricks anything adds to
         unsigned npairs = 0, touched = 0;

@@ -234,9 +234,14 @@ static int validate_grid(const tl3d_config *cfg) {
     for (int a = 0; a < 3; ++a)
         REQUIRE(cfg->voxel_offset[a] >= 0 && cfg->voxel_offset[a] % TL3D_BRICK == 0 && cfg->voxel_offset[a] < (1ll << 40), TL3D_E_INVALID,
                 "voxel_offset must be non-negative multiples of %d", TL3D_BRICK);
-    if (cfg->channels & TL3D_CH_TSDF)
-        REQUIRE(cfg->voxel_offset[0] == 0 && cfg->voxel_offset[1] == 0 && cfg->voxel_offset[2] == 0, TL3D_E_INVALID,
-                "a grid with a TSDF channel cannot be a block of a larger lattice (voxel_offset must be 0)");
+    // the TSDF kernels place a voxel centre at fma((float)(offset + i) + 0.5f, voxel, origin): exact while offset + i < 2^23
+    if (cfg->channels & TL3D_CH_TSDF) {
+        const int64_t dims[3] = {cfg->nx, cfg->ny, cfg->nz};
+        for (int a = 0; a < 3; ++a)
+            REQUIRE(cfg->voxel_offset[a] + dims[a] <= (1ll << 23), TL3D_E_INVALID,
+                    "a TSDF grid must end within 2^23 voxels of the lattice origin (axis %d: offset %lld + %lld)", a,
+                    (long long)cfg->voxel_offset[a], (long long)dims[a]);
+    }
     if (cfg->pool_bricks_tsdf > 0 || cfg->pool_bricks_centroid > 0)
         REQUIRE(cfg->ext_tsdf == nullptr && cfg->ext_centroid == nullptr, TL3D_E_INVALID, "a sparse grid (pool_bricks_*) cannot live in caller-owned dense memory");
     return TL3D_OK;
@@ -272,6 +277,10 @@ static void grid_geometry(Grid &g, const tl3d_config *cfg) {
     g.nbx = cfg->nx / 8; g.nby = cfg->ny / 8; g.nbz = cfg->nz / 8;
     g.oxd = cfg->origin[0]; g.oyd = cfg->origin[1]; g.ozd = cfg->origin[2]; g.vsd = cfg->voxel_size;
     g.offx = (double)cfg->voxel_offset[0]; g.offy = (double)cfg->voxel_offset[1]; g.offz = (double)cfg->voxel_offset[2];
+    // (a centroid-only grid may sit further out than 2^31; its TSDF-path offsets are never read)
+    g.vox = (int)(cfg->voxel_offset[0] & 0x7fffffff); g.voy = (int)(cfg->voxel_offset[1] & 0x7fffffff); g.voz = (int)(cfg->voxel_offset[2] & 0x7fffffff);
+    g.clo[0] = g.clo[1] = g.clo[2] = 0;
+    g.chi[0] = g.nx; g.chi[1] = g.ny; g.chi[2] = g.nz;
     g.ox = (float)g.oxd; g.oy = (float)g.oyd; g.oz = (float)g.ozd; g.vs = (float)g.vsd;
     g.trunc = (float)cfg->sdf_trunc;
     g.inv_trunc = (cfg->channels & TL3D_CH_TSDF) ? 1.0f / g.trunc : 0.0f;
@@ -371,8 +380,11 @@ static int alloc_grid(tl3d_ctx *ctx, const tl3d_config *cfg) {
             if (hipMemsetAsync(ctx->centroid, 0, pool_b, ctx->stream) != hipSuccess) return set_err(TL3D_E_HIP, "memset failed");
         }
     }
+    ctx->has_core = false;
+    for (int i = 0; i < 3; ++i) ctx->lat[i] = (long long)cfg->voxel_offset[i] + (i == 0 ? cfg->nx : i == 1 ? cfg->ny : cfg->nz);
     ctx->cfg.channels = cfg->channels;
     ctx->cfg.nx = cfg->nx; ctx->cfg.ny = cfg->ny; ctx->cfg.nz = cfg->nz;
+    for (int i = 0; i < 3; ++i) ctx->cfg.voxel_offset[i] = cfg->voxel_offset[i];
     for (int i = 0; i < 3; ++i) ctx->cfg.origin[i] = cfg->origin[i];
     ctx->cfg.voxel_size = cfg->voxel_size;
     ctx->cfg.sdf_trunc = cfg->sdf_trunc;
@@ -752,6 +764,91 @@ int tl3d_attach_grid(tl3d_ctx *ctx, const tl3d_config *cfg) {
     rc = alloc_grid(ctx, cfg);
     if (rc) return rc;
     TL3D_HIP(hipStreamSynchronize(ctx->stream));
+    return TL3D_OK;
+}
+
+int tl3d_detach_grid(tl3d_ctx *ctx) {
+    REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
+    REQUIRE(ctx->tsdf != nullptr || ctx->centroid != nullptr, TL3D_E_STATE, "context has no grid");
+    FLUSH_UPDATES(ctx);
+    TL3D_HIP(hipSetDevice(ctx->device));
+    for (int q = 0; q < 4; ++q)
+        if (ctx->prep_stream[q]) TL3D_HIP(hipStreamSynchronize(ctx->prep_stream[q]));
+    TL3D_HIP(hipStreamSynchronize(ctx->stream));
+    // the grid channels, brick tables, free-space counters and every grid-sized scratch; frames, normal maps, ICP state, streams
+    // and the camera-sized buffers stay
+    if (ctx->brick_tabs) (void)hipFree(ctx->brick_tabs);
+    if (ctx->own_tsdf && ctx->tsdf) (void)hipFree(ctx->tsdf);
+    if (ctx->own_centroid && ctx->centroid) (void)hipFree(ctx->centroid);
+    if (ctx->free_cnt) (void)hipFree(ctx->free_cnt);
+    if (ctx->tsdf_scratch_slab) (void)hipFree(ctx->tsdf_scratch_slab);
+    if (ctx->block_counts) (void)hipFree(ctx->block_counts);
+    if (ctx->block_offsets) (void)hipFree(ctx->block_offsets);
+    if (ctx->mesh_counts) (void)hipFree(ctx->mesh_counts);
+    if (ctx->mesh_offsets) (void)hipFree(ctx->mesh_offsets);
+    if (ctx->mesh_first) (void)hipFree(ctx->mesh_first);
+    for (int h = 0; h < TSDF_SCRATCHES; ++h) {
+        if (ctx->ev_upd[h]) (void)hipEventDestroy(ctx->ev_upd[h]);      // (alloc_grid creates them anew)
+        ctx->ev_upd[h] = nullptr;
+        ctx->upd_recorded[h] = false;
+        ctx->tsdf_scratch[h] = nullptr;
+    }
+    ctx->brick_tabs = nullptr;
+    ctx->tsdf = nullptr;
+    ctx->centroid = nullptr;
+    ctx->own_tsdf = ctx->own_centroid = false;
+    ctx->sparse = false;
+    ctx->free_cnt = nullptr;
+    ctx->free_dirty = false;
+    ctx->tsdf_scratch_slab = nullptr;
+    ctx->block_counts = nullptr;
+    ctx->block_offsets = nullptr;
+    ctx->scratch_blocks = 0;
+    ctx->mesh_counts = nullptr;
+    ctx->mesh_offsets = nullptr;
+    ctx->mesh_blocks = 0;
+    ctx->mesh_first = nullptr;
+    ctx->mesh_first_n = 0;
+    ctx->ext_valid = ctx->mesh_valid = false;
+    ctx->grid_epoch++;
+    ctx->has_core = false;
+    ctx->tsdf_w_upper = 0;
+    ctx->tsdf_w_unknown = false;
+    memset(&ctx->grid, 0, sizeof(ctx->grid));
+    ctx->nvox = 0;
+    ctx->cfg.channels = 0;
+    for (int i = 0; i < 3; ++i) ctx->cfg.voxel_offset[i] = 0;
+    return TL3D_OK;
+}
+
+int tl3d_set_block_core(tl3d_ctx *ctx, const int64_t lattice_dims[3], const int32_t lo[3], const int32_t hi[3]) {
+    REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
+    REQUIRE(ctx->tsdf != nullptr || ctx->centroid != nullptr, TL3D_E_STATE, "context has no grid");
+    Grid &g = ctx->grid;
+    const int dims[3] = {g.nx, g.ny, g.nz};
+    const int64_t off[3] = {ctx->cfg.voxel_offset[0], ctx->cfg.voxel_offset[1], ctx->cfg.voxel_offset[2]};
+    if (lattice_dims || lo || hi) {
+        REQUIRE(lattice_dims && lo && hi, TL3D_E_INVALID, "lattice_dims, lo and hi are all given or all NULL");
+        double nlat = 1.0;
+        for (int a = 0; a < 3; ++a) {
+            REQUIRE(lo[a] >= 0 && lo[a] < hi[a] && hi[a] <= dims[a] && lo[a] % TL3D_BRICK == 0 && hi[a] % TL3D_BRICK == 0, TL3D_E_INVALID,
+                    "core [%d, %d) on axis %d must be a non-empty range of multiples of %d within the grid's %d voxels", lo[a], hi[a], a,
+                    TL3D_BRICK, dims[a]);
+            REQUIRE(lattice_dims[a] >= off[a] + dims[a], TL3D_E_INVALID, "lattice of %lld voxels on axis %d does not hold the grid (%lld + %d)",
+                    (long long)lattice_dims[a], a, (long long)off[a], dims[a]);
+            nlat *= (double)lattice_dims[a];
+        }
+        REQUIRE(nlat < 2305843009213693952.0, TL3D_E_INVALID, "lattice of 2^61 voxels or more: mesh keys would overflow");
+    }
+    FLUSH_UPDATES(ctx);
+    for (int a = 0; a < 3; ++a) {
+        g.clo[a] = lattice_dims ? lo[a] : 0;
+        g.chi[a] = lattice_dims ? hi[a] : dims[a];
+        ctx->lat[a] = lattice_dims ? (long long)lattice_dims[a] : (long long)off[a] + dims[a];
+    }
+    ctx->has_core = lattice_dims != nullptr;
+    ctx->ext_valid = ctx->mesh_valid = false;
+    ctx->grid_epoch++;
     return TL3D_OK;
 }
 
@@ -2256,8 +2353,10 @@ static int ensure_mesh_scratch(tl3d_ctx *ctx, size_t nblocks, size_t nfirst) {
     return TL3D_OK;
 }
 
-int tl3d_extract_mesh(tl3d_ctx *ctx, int min_weight, float *out_xyz, uint8_t *out_rgb, int64_t vert_cap, uint32_t *out_tri,
-                      int64_t tri_cap, int64_t *out_n_vert, int64_t *out_n_tri) {
+}  // extern "C"
+
+static int extract_mesh_impl(tl3d_ctx *ctx, int min_weight, float *out_xyz, uint8_t *out_rgb, int64_t vert_cap, uint32_t *out_tri,
+                             int64_t tri_cap, int64_t *out_n_vert, int64_t *out_n_tri, int64_t *out_key) {
     REQUIRE(ctx && out_n_vert && out_n_tri, TL3D_E_INVALID, "null argument");
     REQUIRE(ctx->tsdf != nullptr, TL3D_E_STATE, "TSDF channel not enabled");
     FLUSH_AND_FOLD(ctx);
@@ -2298,33 +2397,49 @@ int tl3d_extract_mesh(tl3d_ctx *ctx, int min_weight, float *out_xyz, uint8_t *ou
         return set_err(TL3D_E_CAPACITY, "need %llu vertices / %llu triangles, capacities %lld / %lld", nv, nt, (long long)vert_cap,
                        (long long)tri_cap);
     if (nv == 0) return TL3D_OK;                        // (no vertex: no meshed cell either)
-    const bool direct = is_device_ptr(out_xyz) && is_device_ptr(out_rgb) && is_device_ptr(out_tri);
+    const bool direct = is_device_ptr(out_xyz) && is_device_ptr(out_rgb) && is_device_ptr(out_tri) && (!out_key || is_device_ptr(out_key));
     float *dxyz = out_xyz;
     uint8_t *drgb = out_rgb;
     uint32_t *dtri = out_tri;
+    int64_t *dkey = out_key;
     if (!direct) {
-        dxyz = nullptr; drgb = nullptr; dtri = nullptr;
+        dxyz = nullptr; drgb = nullptr; dtri = nullptr; dkey = nullptr;
         if (hipMalloc(&dxyz, nv * 12) != hipSuccess || hipMalloc(&drgb, nv * 3) != hipSuccess ||
-            (nt && hipMalloc(&dtri, nt * 12) != hipSuccess)) {
+            (nt && hipMalloc(&dtri, nt * 12) != hipSuccess) || (out_key && hipMalloc(&dkey, nv * 8) != hipSuccess)) {
             (void)hipGetLastError();
             if (dxyz) (void)hipFree(dxyz);
             if (drgb) (void)hipFree(drgb);
+            if (dtri) (void)hipFree(dtri);
             return set_err(TL3D_E_NOMEM, "mesh output staging alloc failed");
         }
     }
     rc = launch_mesh_write(ctx->stream, ctx->grid, min_weight, ctx->tsdf, ctx->centroid, voffs, toffs, nblocks, ctx->mesh_first,
-                           dxyz, drgb, nv, dtri, nt);
+                           dxyz, drgb, nv, dtri, nt, (long long *)dkey, ctx->lat);
     hipError_t e = hipSuccess;
     if (rc == TL3D_OK && !direct) {
         e = hipMemcpyAsync(out_xyz, dxyz, nv * 12, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(out_rgb, drgb, nv * 3, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess && nt) e = hipMemcpyAsync(out_tri, dtri, nt * 12, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && out_key) e = hipMemcpyAsync(out_key, dkey, nv * 8, hipMemcpyDeviceToHost, ctx->stream);
     }
     hipError_t e2 = hipStreamSynchronize(ctx->stream);
-    if (!direct) { (void)hipFree(dxyz); (void)hipFree(drgb); if (dtri) (void)hipFree(dtri); }
+    if (!direct) { (void)hipFree(dxyz); (void)hipFree(drgb); if (dtri) (void)hipFree(dtri); if (dkey) (void)hipFree(dkey); }
     if (rc) return rc;
     if (e != hipSuccess || e2 != hipSuccess) return set_err(TL3D_E_HIP, "mesh copy/sync failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
     return TL3D_OK;
+}
+
+extern "C" {
+
+int tl3d_extract_mesh(tl3d_ctx *ctx, int min_weight, float *out_xyz, uint8_t *out_rgb, int64_t vert_cap, uint32_t *out_tri,
+                      int64_t tri_cap, int64_t *out_n_vert, int64_t *out_n_tri) {
+    return extract_mesh_impl(ctx, min_weight, out_xyz, out_rgb, vert_cap, out_tri, tri_cap, out_n_vert, out_n_tri, nullptr);
+}
+
+int tl3d_extract_mesh_keyed(tl3d_ctx *ctx, int min_weight, float *out_xyz, uint8_t *out_rgb, int64_t vert_cap, uint32_t *out_tri,
+                            int64_t tri_cap, int64_t *out_key, int64_t *out_n_vert, int64_t *out_n_tri) {
+    REQUIRE(ctx && (out_key || !out_xyz), TL3D_E_INVALID, "null key buffer");
+    return extract_mesh_impl(ctx, min_weight, out_xyz, out_rgb, vert_cap, out_tri, tri_cap, out_n_vert, out_n_tri, out_key);
 }
 
 // ------------------------------------------------------------------------------------------- ray casting
@@ -2350,6 +2465,8 @@ int tl3d_raycast(tl3d_ctx *ctx, const double R[9], const double t[3], int min_we
     REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
     REQUIRE(R && t, TL3D_E_INVALID, "null pose");
     REQUIRE(ctx->tsdf != nullptr, TL3D_E_STATE, "ray casting needs a grid with a TSDF channel");
+    REQUIRE(!ctx->has_core && ctx->cfg.voxel_offset[0] == 0 && ctx->cfg.voxel_offset[1] == 0 && ctx->cfg.voxel_offset[2] == 0, TL3D_E_STATE,
+            "ray casting needs a whole lattice: this grid is a block (voxel offset or core set)");
     if (slot >= 0) {
         const int src = check_slot(ctx, slot, false);
         if (src) return src;

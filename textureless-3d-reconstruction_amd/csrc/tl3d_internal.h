@@ -33,6 +33,8 @@ struct Grid {
     float ox, oy, oz, vs;        // f32 origin / voxel size (TSDF path)
     double oxd, oyd, ozd, vsd;   // fp64 (centroid path, Open3D index semantics)
     double offx, offy, offz;     // the grid's voxel (0,0,0) is voxel (offx, offy, offz) of the lattice that starts at the origin (integers; centroid path)
+    int vox, voy, voz;           // the same offset as integers (TSDF path: a voxel centre is fma((float)(off + i) + 0.5f, vs, origin), exact below 2^23)
+    int clo[3], chi[3];          // block core, grid-local voxels [clo, chi) (tl3d_set_block_core); [0, n) without one
     float trunc, inv_trunc;
     // Brick tables: the records of virtual brick b of a channel sit in pool slot table[b] (512 records each).  A dense grid has
     // the identity table and a pool of every brick; a SPARSE grid starts with an empty table and hands out slots on first
@@ -218,6 +220,9 @@ struct tl3d_ctx {
     size_t mesh_blocks;
     unsigned *mesh_first;
     size_t mesh_first_n;
+    // tl3d_set_block_core: the grid is one block of a lattice of lat[] voxels and emits only what its core (grid.clo / chi) owns
+    bool has_core;
+    long long lat[3];
     // tl3d_raycast: device staging of the outputs a caller wants on the host ([H][W] f32, [H][W][3] f32, [H][W][3] u8; grown on demand)
     float *ray_depth, *ray_nrm;
     uint8_t *ray_bgr;
@@ -336,6 +341,10 @@ __device__ __forceinline__ void rec_coords(size_t idx, int nbx, int nby, int &i,
     i |= bx << 3;
     j |= by << 3;
     k |= bz << 3;
+}
+
+__host__ __device__ __forceinline__ bool in_core(const Grid &g, int i, int j, int k) {
+    return i >= g.clo[0] && i < g.chi[0] && j >= g.clo[1] && j < g.chi[1] && k >= g.clo[2] && k < g.chi[2];
 }
 
 __device__ __forceinline__ void mean_colour(const unsigned long long *__restrict__ rec, unsigned long long n, uint8_t c[3]) {
@@ -465,7 +474,8 @@ int launch_mesh_count(hipStream_t s, const Grid &g, int min_weight, const int2 *
                       int nblocks);
 int launch_mesh_write(hipStream_t s, const Grid &g, int min_weight, const int2 *tsdf, const unsigned long long *cen,
                       const unsigned long long *voffsets, const unsigned long long *toffsets, int nblocks, unsigned *first_id,
-                      float *xyz, uint8_t *rgb, unsigned long long vcap, unsigned *tris, unsigned long long tcap);
+                      float *xyz, uint8_t *rgb, unsigned long long vcap, unsigned *tris, unsigned long long tcap,
+                      long long *keys = nullptr, const long long *lat = nullptr);
 // ray casting
 int launch_raycast(hipStream_t s, const Cam &cam, const Grid &g, const double R[9], const double t[3], int min_weight, float z_near,
                    float z_far, const int2 *tsdf, const unsigned long long *cen, float *depth, float *depth2, float *nrm, uint8_t *bgr,

@@ -27,7 +27,7 @@ class GridSpec:
     pool_tsdf: int = 0
     pool_centroid: int = 0
     # the grid is a BLOCK of a larger voxel lattice that starts at `origin`: index of its voxel (0, 0, 0) in that lattice (multiples of 8;
-    # centroid channel only -- tl3d.h: tl3d_config.voxel_offset)
+    # both channels, a TSDF grid within 2^23 voxels of the lattice origin -- tl3d.h: tl3d_config.voxel_offset)
     voxel_offset: Tuple[int, int, int] = (0, 0, 0)
 
     @property
@@ -256,6 +256,24 @@ class FusionContext:
         self._keep = (ext_tsdf, ext_centroid)
         self.grid = grid
 
+    def detach_grid(self):
+        """Free the grid (channels, brick tables, grid-sized scratch); frames, normal maps and ICP state stay, and attach_grid
+        works again (tl3d.h: tl3d_detach_grid)."""
+        abi.check(self._lib.tl3d_detach_grid(self._h))
+        self._keep = (None, None)
+        self.grid = None
+
+    def set_block_core(self, lattice_dims=None, lo=None, hi=None):
+        """The attached grid is one block of a lattice of `lattice_dims` voxels; extraction, the mesh and the centroid statistics
+        keep to the core [lo, hi) (grid-local voxels, multiples of 8).  No arguments: no core (tl3d.h: tl3d_set_block_core)."""
+        if lattice_dims is None:
+            abi.check(self._lib.tl3d_set_block_core(self._h, None, None, None))
+            return
+        ld = np.ascontiguousarray([int(x) for x in lattice_dims], np.int64)
+        lo_ = np.ascontiguousarray([int(x) for x in lo], np.int32)
+        hi_ = np.ascontiguousarray([int(x) for x in hi], np.int32)
+        abi.check(self._lib.tl3d_set_block_core(self._h, abi.ptr(ld), abi.ptr(lo_), abi.ptr(hi_)))
+
     def download_depth(self, slot: int) -> np.ndarray:
         out = np.empty((self.height, self.width), np.float32)
         abi.check(self._lib.tl3d_download_depth(self._h, int(slot), abi.ptr(out)))
@@ -327,6 +345,7 @@ class FusionContext:
         cfg.nx, cfg.ny, cfg.nz = (int(d) for d in grid.dims)
         cfg.origin = (C.c_double * 3)(*[float(o) for o in grid.origin])
         cfg.voxel_size, cfg.sdf_trunc = float(grid.voxel_size), float(grid.sdf_trunc)
+        cfg.voxel_offset = (C.c_int64 * 3)(*[int(o) for o in grid.voxel_offset])
         sl = np.ascontiguousarray(slots, np.int32)
         R = np.ascontiguousarray(np.stack([np.asarray(p[0], np.float64).reshape(3, 3) for p in poses]))
         t = np.ascontiguousarray(np.stack([np.asarray(p[1], np.float64).reshape(3) for p in poses]))
@@ -577,19 +596,25 @@ class FusionContext:
                                              abi.ptr(xyz), abi.ptr(rgb), n.value, C.byref(n)))
         return xyz, rgb
 
-    def extract_mesh(self, min_weight: int = 0):
+    def extract_mesh(self, min_weight: int = 0, keys: bool = False):
         """Marching-cubes mesh of the TSDF channel: (xyz f32 [V,3], rgb u8 [V,3], tris u32 [T,3]).  The
         vertices are the zero crossings of the usable voxel edges in record order; every triangle is wound so that
-        (v1 - v0) x (v2 - v0) points to t > 0 (towards the cameras)."""
+        (v1 - v0) x (v2 - v0) points to t > 0 (towards the cameras).  keys=True: a fourth array, int64 [V], 3 * (lattice index of the
+        vertex's owner voxel) + axis, which names a vertex across the blocks of a lattice (tl3d.h: tl3d_extract_mesh_keyed)."""
         nv, nt = C.c_int64(0), C.c_int64(0)
         abi.check(self._lib.tl3d_extract_mesh(self._h, int(min_weight), None, None, 0, None, 0, C.byref(nv), C.byref(nt)))
         xyz = np.empty((nv.value, 3), np.float32)
         rgb = np.empty((nv.value, 3), np.uint8)
         tris = np.empty((nt.value, 3), np.uint32)
+        key = np.empty(nv.value, np.int64)
         if nv.value:
-            abi.check(self._lib.tl3d_extract_mesh(self._h, int(min_weight), abi.ptr(xyz), abi.ptr(rgb), nv.value, abi.ptr(tris),
-                                                  nt.value, C.byref(nv), C.byref(nt)))
-        return xyz, rgb, tris
+            if keys:
+                abi.check(self._lib.tl3d_extract_mesh_keyed(self._h, int(min_weight), abi.ptr(xyz), abi.ptr(rgb), nv.value, abi.ptr(tris),
+                                                            nt.value, abi.ptr(key), C.byref(nv), C.byref(nt)))
+            else:
+                abi.check(self._lib.tl3d_extract_mesh(self._h, int(min_weight), abi.ptr(xyz), abi.ptr(rgb), nv.value, abi.ptr(tris),
+                                                      nt.value, C.byref(nv), C.byref(nt)))
+        return (xyz, rgb, tris, key) if keys else (xyz, rgb, tris)
 
     def raycast(self, pose, min_weight: int = 0, z_near=None, z_far=None, slot=None, out=None):
         """Ray-cast the TSDF channel from the camera at pose = (R, t) (world->camera, as integrate):

@@ -12,6 +12,7 @@ what D2R itself falls back to (D2R:555-558).
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import List, Optional, Tuple
 
 import time
@@ -87,7 +88,8 @@ def layout_from_counts(grid: GridSpec, bricks_tsdf: int, bricks_centroid: int) -
     if grid.channels & abi.CH_CENTROID:
         want = int(bricks_centroid * 1.03) + 2048
         pool_c = want if 2 * want < nbr else 0
-    return GridSpec(grid.dims, grid.origin, grid.voxel_size, grid.sdf_trunc, grid.channels, pool_tsdf=pool_t, pool_centroid=pool_c)
+    return GridSpec(grid.dims, grid.origin, grid.voxel_size, grid.sdf_trunc, grid.channels, pool_tsdf=pool_t, pool_centroid=pool_c,
+                    voxel_offset=grid.voxel_offset)
 
 
 def choose_layout(ctx: FusionContext, grid: GridSpec, slots, poses, scales, centroid_subsample, dist=None, log=print) -> GridSpec:
@@ -98,7 +100,7 @@ def choose_layout(ctx: FusionContext, grid: GridSpec, slots, poses, scales, cent
     from the extent.  Small grids are dense without asking.  With `dist` (reconstruct_sharded) every rank counts its own frames and
     all take the SUM (an upper bound of the union the merge will bring to every rank), so that all ranks choose alike."""
     nbr = grid.nvox // 512
-    dense = GridSpec(grid.dims, grid.origin, grid.voxel_size, grid.sdf_trunc, grid.channels)
+    dense = GridSpec(grid.dims, grid.origin, grid.voxel_size, grid.sdf_trunc, grid.channels, voxel_offset=grid.voxel_offset)
     if dense.device_bytes() <= DENSE_WITHOUT_ASKING:
         return dense
     nt, nc = ctx.count_bricks(grid, slots, poses, scales, centroid_subsample=centroid_subsample) if len(slots) else (0, 0)
@@ -109,6 +111,120 @@ def choose_layout(ctx: FusionContext, grid: GridSpec, slots, poses, scales, cent
     log(f"  Occupancy: {nt} TSDF bricks, {nc} centroid bricks of {nbr}: "
         f"{'sparse' if out.sparse else 'dense'} volume, {out.device_bytes() / 2**30:.2f} GiB (dense: {dense.device_bytes() / 2**30:.2f} GiB)")
     return out
+
+
+MAX_BLOCK_VOXELS = 1 << 32            # voxels of one grid, halo included: its brick table is direct-indexed
+BLOCK_MEMORY_MARGIN = 2 << 30         # device bytes a block leaves free for the fusion, extraction and mesh scratch
+
+
+@dataclass
+class Block:
+    """One block of a lattice: its grid (core + halo, grid.voxel_offset = the core's first lattice voxel) and its core [lo, hi) in
+    grid-local voxels.  The halo is one brick on every + side that has a next block: what the last cell layer of the core reads."""
+    grid: GridSpec
+    lo: Tuple[int, int, int]
+    hi: Tuple[int, int, int]
+
+
+def device_free_bytes(device: int) -> int:
+    """Free device memory (hipMemGetInfo of the HIP runtime libtl3d.so runs on: no second runtime, no torch context)."""
+    import ctypes as C
+    lib = abi.load()
+    free, total = C.c_size_t(0), C.c_size_t(0)
+    if lib.hipSetDevice(int(device)) != 0 or lib.hipMemGetInfo(C.byref(free), C.byref(total)) != 0:
+        raise RuntimeError("hipMemGetInfo failed")
+    return int(free.value)
+
+
+def plan_lattice(bounds_min, bounds_max, voxel_size, grid_dim, channels=abi.CH_TSDF | abi.CH_CENTROID, trunc_voxels=4.0) -> GridSpec:
+    """The whole lattice of the scene, never shaved: Open3D's voxel origin (min_bound - voxel/2) and the dims from the bounds.  A
+    lattice of at most 2^32 voxels is plan_grid()'s grid exactly (its layout guess included); a larger one is fused block by block
+    (plan_blocks) and each block chooses its own layout."""
+    grid, clipped = plan_grid(bounds_min, bounds_max, voxel_size, grid_dim, channels=channels, trunc_voxels=trunc_voxels)
+    if not clipped:
+        return grid
+    v = float(voxel_size)
+    mn, mx = np.asarray(bounds_min, np.float64), np.asarray(bounds_max, np.float64)
+    origin = mn - 0.5 * v
+    dims = np.maximum(8, ((np.floor((mx - origin) / v).astype(np.int64) + 1 + 7) // 8) * 8)
+    return GridSpec(tuple(int(d) for d in dims), tuple(float(o) for o in origin), v, trunc_voxels * v, channels)
+
+
+def _make_block(lattice: GridSpec, off, core) -> Block:
+    dims = tuple(int(core[a]) + (8 if int(off[a]) + int(core[a]) < int(lattice.dims[a]) else 0) for a in range(3))
+    grid = GridSpec(dims, lattice.origin, lattice.voxel_size, lattice.sdf_trunc, lattice.channels,
+                    voxel_offset=tuple(int(o) for o in off))
+    return Block(grid, (0, 0, 0), tuple(int(c) for c in core))
+
+
+def split_block(lattice: GridSpec, block: Block) -> List[Block]:
+    """The block's core halved along its longest axis (at a multiple of 8), each half with its own halo."""
+    off, core = np.asarray(block.grid.voxel_offset, np.int64), np.asarray(block.hi, np.int64) - np.asarray(block.lo, np.int64)
+    a = int(np.argmax(core))
+    if core[a] <= 8:
+        raise ValueError(f"block {tuple(core)} at {tuple(off)} cannot be split further")
+    h = ((int(core[a]) // 2 + 7) // 8) * 8
+    c0, c1, o1 = core.copy(), core.copy(), off.copy()
+    c0[a], c1[a], o1[a] = h, core[a] - h, off[a] + h
+    return [_make_block(lattice, off, c0), _make_block(lattice, o1, c1)]
+
+
+def plan_blocks(lattice: GridSpec, max_voxels: Optional[int] = None) -> List[Block]:
+    """Disjoint block cores that tile the lattice, each block's grid (core + halo) of at most max_voxels (default MAX_BLOCK_VOXELS):
+    the longest axis of a core is halved at a multiple of 8 until every block fits (DenseReconstructor's _lattice_blocks, plus the
+    halo).  A lattice within the limit is ONE block: the lattice grid itself, offset 0, no halo, no core."""
+    limit = MAX_BLOCK_VOXELS if max_voxels is None else int(max_voxels)
+    if lattice.nvox <= limit:
+        return [Block(lattice, (0, 0, 0), tuple(int(d) for d in lattice.dims))]
+    out, todo = [], [_make_block(lattice, (0, 0, 0), lattice.dims)]
+    while todo:
+        b = todo.pop()
+        if b.grid.nvox <= limit:
+            out.append(b)
+        else:
+            todo.extend(split_block(lattice, b))
+    return sorted(out, key=lambda b: tuple(reversed(b.grid.voxel_offset)))
+
+
+def _core_owned(keys, lattice_dims, lo, hi):
+    """Which keyed vertices (key = 3 * lattice linear index of the owner voxel + axis) have their owner in the lattice box [lo, hi)."""
+    lx, ly = int(lattice_dims[0]), int(lattice_dims[1])
+    idx = np.asarray(keys, np.int64) // 3
+    x, y, z = idx % lx, (idx // lx) % ly, idx // (lx * ly)
+    return ((x >= lo[0]) & (x < hi[0]) & (y >= lo[1]) & (y < hi[1]) & (z >= lo[2]) & (z < hi[2]))
+
+
+def weld_meshes(parts, lattice_dims):
+    """One mesh from the keyed meshes of the blocks of a lattice.  parts: [(xyz, rgb, tris, keys, core_lo, core_hi)] with the core
+    in LATTICE voxels.  Every vertex whose owner voxel lies in its block's core is kept (each owned edge vertex exists in exactly one
+    core, the unreferenced ones included, as in a single grid); a triangle's halo-owned vertices are found through their keys among
+    the kept ones.  Returns (xyz, rgb, tris, keys)."""
+    kx, kr, kk = [], [], []
+    for xyz, rgb, _tris, keys, lo, hi in parts:
+        own = _core_owned(keys, lattice_dims, lo, hi)
+        kx.append(np.asarray(xyz)[own])
+        kr.append(np.asarray(rgb)[own])
+        kk.append(np.asarray(keys, np.int64)[own])
+    xyz = np.concatenate(kx) if kx else np.zeros((0, 3), np.float32)
+    rgb = np.concatenate(kr) if kr else np.zeros((0, 3), np.uint8)
+    allk = np.concatenate(kk) if kk else np.zeros(0, np.int64)
+    order = np.argsort(allk, kind="stable")
+    sk = allk[order]
+    if len(sk) > 1 and np.any(sk[1:] == sk[:-1]):
+        raise ValueError("weld_meshes: a vertex is owned by two block cores (the cores overlap)")
+    out = []
+    for _xyz, _rgb, tris, keys, _lo, _hi in parts:
+        tris = np.asarray(tris)
+        if len(tris) == 0:
+            continue
+        tk = np.asarray(keys, np.int64)[tris.astype(np.int64)]
+        pos = np.searchsorted(sk, tk)
+        pos = np.minimum(pos, max(0, len(sk) - 1))
+        if len(sk) == 0 or not np.array_equal(sk[pos], tk):
+            raise ValueError("weld_meshes: a triangle references a vertex no block core owns (a halo is missing)")
+        out.append(order[pos].astype(np.uint32))
+    tris = np.concatenate(out) if out else np.zeros((0, 3), np.uint32)
+    return xyz, rgb, tris, allk
 
 
 class ScaleTracker:
@@ -194,7 +310,8 @@ class DepthToReconstructionPipeline:
         self.icp_log: List[dict] = []
         self.stats: dict = {}
         self.timings: dict = {}                   # wall seconds per stage of the last reconstruct()
-        self.grid: Optional[GridSpec] = None      # the fusion volume of the last reconstruct()
+        self.grid: Optional[GridSpec] = None      # the fusion volume of the last reconstruct(): the whole lattice (nvox may exceed 2^32)
+        self.blocks: List[GridSpec] = []          # the grids it was fused in (one, or the blocks of a lattice beyond one grid)
         self.mesh = None                          # (xyz f32 [V,3], rgb u8 [V,3], tris u32 [T,3]) of the last reconstruct(), config.extract_mesh
 
     # ---- a2 --------------------------------------------------------------------------------------
@@ -445,6 +562,7 @@ class DepthToReconstructionPipeline:
             if len(self.camera_poses) < 2:
                 print("Pose estimation failed")
                 return None, None, None
+            blocks = None
             if grid is None:
                 print("\n--- Step 2: Bound the scene ---")
                 # extent of the union of the frames' clouds, on the device
@@ -453,14 +571,19 @@ class DepthToReconstructionPipeline:
                 if not np.all(np.isfinite(mn)):
                     print("Reconstruction failed")
                     return None, None, None
-                grid, clipped = plan_grid(mn, mx, cfg.voxel_size, cfg.grid_dim, trunc_voxels=cfg.sdf_trunc_voxels)
-                if clipped:
-                    print(f"  Warning: scene extent {np.round(mx - mn, 3)} m at {cfg.voxel_size} m voxels exceeds the budget of "
-                          f"{cfg.grid_dim}^3 voxels; the grid {grid.dims} is centred on the scene and points outside it are dropped "
-                          "(raise --grid or --voxel-size)")
+                # the whole lattice, never shaved; more than one grid's worth of voxels is fused block by block
+                grid = plan_lattice(mn, mx, cfg.voxel_size, cfg.grid_dim, trunc_voxels=cfg.sdf_trunc_voxels)
+                blocks = plan_blocks(grid)
+                if len(blocks) > 1:
+                    if cfg.render_dir:
+                        raise ValueError(f"render_dir: the scene's lattice {grid.dims} ({grid.nvox} voxels) is fused in {len(blocks)} "
+                                         "blocks, and ray casting across blocks does not exist (raise --voxel-size)")
+                    self.grid = grid
+                    return self._reconstruct_blocked(ctx, grid, blocks, marks, clock)
                 # dense or sparse: from the bricks these frames will really touch, not from the extent
                 grid = choose_layout(ctx, grid, self.frame_index, self.camera_poses, [self.scales[fi] for fi in self.frame_index],
                                      cfg.subsample_factor)
+            self.blocks = [grid]
             print(f"  Grid {grid.dims} @ {grid.voxel_size * 1e3:g} mm, origin {np.round(grid.origin, 4)}")
             self.grid = grid
             ctx.attach_grid(grid)
@@ -481,7 +604,8 @@ class DepthToReconstructionPipeline:
                 xyz, rgb = xyz[keep], rgb[keep]
             self.stats = dict(points_accumulated=st["centroid_points"], points_dropped=st["centroid_dropped"],
                               voxels=n_vox, after_outlier_filter=len(xyz), sparse=bool(grid.sparse),
-                              bricks_tsdf=st["pool_slots_tsdf"], bricks_centroid=st["pool_slots_centroid"], pool_refused=st["pool_refused"])
+                              bricks_tsdf=st["pool_slots_tsdf"], bricks_centroid=st["pool_slots_centroid"], pool_refused=st["pool_refused"],
+                              blocks=1)
             if grid.sparse:
                 print(f"  Sparse volume: {st['pool_slots_tsdf']} TSDF bricks and {st['pool_slots_centroid']} centroid bricks hold records "
                       f"(of {grid.nvox // 512}); {grid.device_bytes() / 2**30:.2f} GiB")
@@ -499,6 +623,97 @@ class DepthToReconstructionPipeline:
             self.timings = {name + "_s": round(t1 - t0, 4) for (name, t1), (_, t0) in zip(marks[1:], marks[:-1])}
         finally:
             ctx.close()
+        print(f"\nFinal reconstruction: {len(xyz)} points, {len(self.camera_poses)} cameras")
+        return xyz.astype(np.float64), rgb, self.camera_poses
+
+    def _reconstruct_blocked(self, ctx: FusionContext, lattice: GridSpec, blocks: List[Block], marks, clock):
+        """reconstruct() for a lattice of more than one grid's voxels: per block, in the one context whose frames stay resident,
+        attach the block's grid (layout from its own brick count), set its core, fuse every kept frame (the cull drops the frames
+        that miss the block), extract the core's points (and its keyed mesh), detach.  Then one statistical outlier filter over the
+        whole cloud and the blocks' meshes welded by their keys.  The blocks' cores tile the lattice and their
+        halos carry the neighbours' voxels bit for bit: the points and the mesh are the single lattice's."""
+        cfg = self.config
+        scales = [self.scales[fi] for fi in self.frame_index]
+        print(f"  Lattice {lattice.dims} @ {lattice.voxel_size * 1e3:g} mm, origin {np.round(lattice.origin, 4)}: {lattice.nvox} voxels "
+              f"in {len(blocks)} blocks")
+        todo, done = list(reversed(blocks)), []
+        pts, cols, mesh_parts = [], [], []
+        core_points, valid_points = 0, None
+        sums = dict(bricks_tsdf=0, bricks_centroid=0, pool_refused=0)
+        sparse = False
+        stage = dict(bound_and_allocate=0.0, fuse=0.0, extract_and_filter=0.0, mesh=0.0)
+        print("\n--- Step 3: Fuse depth frames block by block (TSDF + voxel centroids) ---")
+        while todo:
+            b = todo.pop()
+            t0 = clock()
+            layout = choose_layout(ctx, b.grid, self.frame_index, self.camera_poses, scales, cfg.subsample_factor)
+            need = layout.device_bytes()
+            if cfg.extract_mesh and layout.channels & abi.CH_TSDF:
+                need += (layout.pool_tsdf or layout.nvox // 512) * 2048          # the mesh's vertex-id scratch: 4 B per TSDF record
+            if need > device_free_bytes(cfg.device) - BLOCK_MEMORY_MARGIN:
+                halves = split_block(lattice, b)
+                print(f"  Block at {b.grid.voxel_offset}: {need / 2**30:.2f} GiB does not fit, split in two")
+                todo.extend(reversed(halves))
+                continue
+            ctx.attach_grid(layout)
+            ctx.set_block_core(lattice.dims, b.lo, b.hi)
+            ctx.reset_stats()
+            t1 = clock()
+            ctx.fuse_frames(self.frame_index, self.camera_poses, scales, centroid_subsample=cfg.subsample_factor)
+            st = ctx.stats()
+            t2 = clock()
+            xyz, rgb = ctx.extract(abi.EXTRACT_CENTROID, min_count=1, min_weight=cfg.tsdf_min_weight, max_abs_tsdf=cfg.tsdf_max_abs)
+            pts.append(xyz)
+            cols.append(rgb)
+            t3 = clock()
+            if cfg.extract_mesh:
+                mx, mr, mt, mk = ctx.extract_mesh(min_weight=cfg.tsdf_min_weight, keys=True)
+                off = np.asarray(b.grid.voxel_offset, np.int64)
+                mesh_parts.append((mx, mr, mt, mk, off + np.asarray(b.lo), off + np.asarray(b.hi)))
+            t4 = clock()
+            ctx.detach_grid()
+            core_points += int(st["centroid_points"])
+            if valid_points is None:                     # every block sees every kept frame's samples: in its core or elsewhere
+                valid_points = int(st["centroid_points"]) + int(st["centroid_dropped"])
+            sums["bricks_tsdf"] += int(st["pool_slots_tsdf"])
+            sums["bricks_centroid"] += int(st["pool_slots_centroid"])
+            sums["pool_refused"] += int(st["pool_refused"])
+            sparse = sparse or layout.sparse
+            done.append(layout)
+            stage["bound_and_allocate"] += (t1 - t0) + (clock() - t4)
+            stage["fuse"] += t2 - t1
+            stage["extract_and_filter"] += t3 - t2
+            stage["mesh"] += t4 - t3
+            print(f"  Block {len(done)} at {layout.voxel_offset}, grid {layout.dims} ({'sparse' if layout.sparse else 'dense'}, "
+                  f"{layout.device_bytes() / 2**30:.2f} GiB): {len(xyz)} voxels")
+        self.blocks = done
+        for fi in self.frame_index:
+            print(f"Camera {fi}: fused")
+        print("\n--- Step 4: Extract and clean point cloud ---")
+        t0 = clock()
+        xyz = np.concatenate(pts) if pts else np.zeros((0, 3), np.float32)
+        rgb = np.concatenate(cols) if cols else np.zeros((0, 3), np.uint8)
+        n_vox = len(xyz)
+        if len(xyz) > 0 and cfg.outlier_filter:         # D2R:413-415, once over the whole cloud
+            keep = ctx.statistical_outlier(xyz, cfg.outlier_nb_neighbors, cfg.outlier_std_ratio, cell_size=2.0 * lattice.voxel_size)
+            xyz, rgb = xyz[keep], rgb[keep]
+        stage["extract_and_filter"] += clock() - t0
+        self.stats = dict(points_accumulated=core_points, points_dropped=(valid_points or 0) - core_points, voxels=n_vox,
+                          after_outlier_filter=len(xyz), sparse=sparse, blocks=len(done), **sums)
+        if sums["pool_refused"]:
+            print(f"  Warning: {sums['pool_refused']} bricks found the record pool full and are missing from the result")
+        if cfg.extract_mesh:
+            t0 = clock()
+            vx, vr, vt, _ = weld_meshes(mesh_parts, lattice.dims)
+            self.mesh = (vx, vr, vt)
+            self.stats["mesh_vertices"] = len(vx)
+            self.stats["mesh_triangles"] = len(vt)
+            print(f"  Mesh: {len(vx)} vertices, {len(vt)} triangles (welded from {len(done)} blocks)")
+            stage["mesh"] += clock() - t0
+        # wall time per stage, summed over the blocks (as reconstruct() reports it), and of the whole blocked fusion
+        self.timings = {name + "_s": round(t1 - t0, 4) for (name, t1), (_, t0) in zip(marks[1:], marks[:-1])}
+        self.timings.update({k + "_s": round(v, 4) for k, v in stage.items() if k != "mesh" or cfg.extract_mesh})
+        self.timings["blocks_s"] = round(clock() - marks[-1][1], 4)
         print(f"\nFinal reconstruction: {len(xyz)} points, {len(self.camera_poses)} cameras")
         return xyz.astype(np.float64), rgb, self.camera_poses
 
