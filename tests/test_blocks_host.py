@@ -154,3 +154,190 @@ def test_layout_helpers_keep_the_voxel_offset():
 def test_binding_declares_the_block_entry_points():
     for name in ("tl3d_detach_grid", "tl3d_set_block_core", "tl3d_extract_mesh_keyed"):
         assert name in abi.SYMBOLS
+
+
+# ---- the tiler, against what it gave before the two copies of the halving rule became one ------------------------------
+
+# (core offset, core dims, grid dims = core + halo) in plan_blocks' order
+_BLOCKS_60_26_3 = [
+    ((0, 0, 0), (1504, 2608, 608), (1512, 2616, 608)), ((1504, 0, 0), (1504, 2608, 608), (1512, 2616, 608)),
+    ((3008, 0, 0), (1504, 2608, 608), (1512, 2616, 608)), ((4512, 0, 0), (1496, 2608, 608), (1504, 2616, 608)),
+    ((6008, 0, 0), (1504, 2608, 608), (1512, 2616, 608)), ((7512, 0, 0), (1496, 2608, 608), (1504, 2616, 608)),
+    ((9008, 0, 0), (1504, 2608, 608), (1512, 2616, 608)), ((10512, 0, 0), (1496, 2608, 608), (1496, 2616, 608)),
+    ((0, 2608, 0), (1504, 2600, 608), (1512, 2600, 608)), ((1504, 2608, 0), (1504, 2600, 608), (1512, 2600, 608)),
+    ((3008, 2608, 0), (1504, 2600, 608), (1512, 2600, 608)), ((4512, 2608, 0), (1496, 2600, 608), (1504, 2600, 608)),
+    ((6008, 2608, 0), (1504, 2600, 608), (1512, 2600, 608)), ((7512, 2608, 0), (1496, 2600, 608), (1504, 2600, 608)),
+    ((9008, 2608, 0), (1504, 2600, 608), (1512, 2600, 608)), ((10512, 2608, 0), (1496, 2600, 608), (1496, 2600, 608))]
+_BLOCKS_256_200_96_EIGHT = [
+    ((0, 0, 0), (64, 104, 96), (72, 112, 96)), ((64, 0, 0), (64, 104, 96), (72, 112, 96)),
+    ((128, 0, 0), (64, 104, 96), (72, 112, 96)), ((192, 0, 0), (64, 104, 96), (64, 112, 96)),
+    ((0, 104, 0), (64, 96, 96), (72, 96, 96)), ((64, 104, 0), (64, 96, 96), (72, 96, 96)),
+    ((128, 104, 0), (64, 96, 96), (72, 96, 96)), ((192, 104, 0), (64, 96, 96), (64, 96, 96))]
+_BLOCKS_256_200_96 = {
+    1 << 20: _BLOCKS_256_200_96_EIGHT,
+    3 * (1 << 18) + 4096: _BLOCKS_256_200_96_EIGHT,
+    136 ** 3: [((0, 0, 0), (128, 104, 96), (136, 112, 96)), ((128, 0, 0), (128, 200, 96), (128, 200, 96)),
+               ((0, 104, 0), (128, 96, 96), (136, 96, 96))]}
+
+
+def _as_rows(blocks):
+    return [(tuple(b.grid.voxel_offset), tuple(b.hi), tuple(b.grid.dims)) for b in blocks]
+
+
+def test_plan_blocks_gives_the_recorded_blocks_in_the_recorded_order():
+    lat = _lattice((60.0, 26.0, 3.0))
+    assert lat.dims == (12008, 5208, 608)
+    assert _as_rows(pl.plan_blocks(lat)) == _BLOCKS_60_26_3
+    lat = GridSpec((256, 200, 96), (0.0, 0.0, 0.0), 0.01, 0.04)
+    for limit, want in _BLOCKS_256_200_96.items():
+        assert _as_rows(pl.plan_blocks(lat, limit)) == want, limit
+
+
+def test_tile_without_halo_gives_the_recorded_merge_blocks():
+    """What DenseReconstructor's merge fuses a 61 m x 26 m x 3 m cloud at 5 mm in: cores of at most 2^31 voxels, no halo."""
+    from tl3d.lattice import lattice_extent, tile
+    _origin, dims = lattice_extent(np.zeros(3), np.array([61.0, 26.0, 3.0]), 0.005)
+    assert tuple(dims) == (12208, 5208, 608)
+    want = [((x, y, 0), (dx, dy, 608)) for y, dy in ((0, 1304), (1304, 1304), (2608, 1304), (3912, 1296))
+            for x, dx in ((0, 1528), (1528, 1528), (3056, 1528), (4584, 1520), (6104, 1528), (7632, 1528), (9160, 1528), (10688, 1520))]
+    got = tile(dims, lambda off, d: d[0] * d[1] * d[2] <= 1 << 31)
+    assert [(tuple(o), tuple(d)) for o, d in got] == want
+
+
+# ---- the fusion body, driven with a stand-in for FusionContext ---------------------------------------------------------
+
+class _RecordingContext:
+    """Logs (method, args, kwargs) and answers with tiny arrays.  Every block reports 12 valid samples, 5, 4, 3, ... of them in its
+    core, two points, and one triangle on three vertices its own core owns."""
+    H, W = 4, 6
+
+    def __init__(self):
+        self.log, self.grid, self.core, self.fused = [], None, None, 0
+
+    def __getattr__(self, name):
+        if name.startswith("_"):
+            raise AttributeError(name)
+
+        def call(*a, **k):
+            self.log.append((name, a, k))
+            answer = type(self).__dict__.get("_" + name)
+            return answer(self, *a, **k) if answer else None
+        return call
+
+    def names(self):
+        return [n for n, _a, _k in self.log]
+
+    def _attach_grid(self, grid):
+        self.grid, self.core = grid, None
+
+    def _set_block_core(self, lattice_dims, lo, hi):
+        self.core = (lattice_dims, lo, hi)
+
+    def _fuse_frames(self, *a, **k):
+        self.fused += 1
+
+    def _stats(self):
+        return dict(centroid_points=6 - self.fused, centroid_dropped=6 + self.fused, pool_slots_tsdf=0, pool_slots_centroid=0, pool_refused=0)
+
+    def _extract(self, *a, **k):
+        return np.full((2, 3), self.fused, np.float32), np.full((2, 3), self.fused, np.uint8)
+
+    def _extract_mesh(self, min_weight=0, keys=False):
+        xyz = np.arange(9, dtype=np.float32).reshape(3, 3) + 100 * self.fused
+        mesh = (xyz, np.full((3, 3), self.fused, np.uint8), np.array([[2, 0, 1]], np.uint32))
+        if not keys:
+            return mesh
+        L, off = self.core[0], np.asarray(self.grid.voxel_offset) + np.asarray(self.core[1])
+        return mesh + (np.array([_key(*off, axis, L) for axis in range(3)], np.int64),)
+
+    def _statistical_outlier(self, xyz, *a, **k):
+        keep = np.ones(len(xyz), bool)
+        keep[0] = False
+        return keep
+
+    def _raycast(self, pose, **k):
+        return np.ones((self.H, self.W), np.float32), None, np.zeros((self.H, self.W, 3), np.uint8)
+
+    def _download_depth(self, slot):
+        return np.full((self.H, self.W), 1.5, np.float32)
+
+
+def _pipe(monkeypatch, **cfg):
+    from tl3d.config import ReconstructionConfig
+    monkeypatch.setattr(pl, "device_free_bytes", lambda device: 1 << 40)
+    pipe = pl.DepthToReconstructionPipeline(ReconstructionConfig(extract_mesh=True, outlier_filter=True, **cfg))
+    pipe.frame_index, pipe.scales, pipe.image_names = [0, 1], [1.0, 1.0], ["a.png", "b.png"]
+    pipe.camera_poses = [(np.eye(3), np.zeros((3, 1)))] * 2
+    return pipe
+
+
+_LATTICE = GridSpec((256, 200, 96), (0.0, 0.0, 0.0), 0.01, 0.04)
+_PER_BLOCK = ["attach_grid", "set_block_core", "reset_stats", "fuse_frames", "stats", "extract", "extract_mesh", "detach_grid"]
+
+
+def test_fusion_body_one_block_has_no_core_no_keys_and_stays_attached_for_the_ray_caster(monkeypatch, tmp_path, capsys):
+    pipe, ctx = _pipe(monkeypatch, render_dir=str(tmp_path)), _RecordingContext()
+    blocks = pl.plan_blocks(_LATTICE)
+    assert len(blocks) == 1
+    xyz, rgb = pipe._fuse_blocks(ctx, _LATTICE, blocks)
+    names = ctx.names()
+    assert names == ["attach_grid", "reset_stats", "fuse_frames", "stats", "extract", "extract_mesh", "statistical_outlier",
+                     "raycast", "download_depth", "raycast", "download_depth"]
+    assert "set_block_core" not in names and "detach_grid" not in names[:names.index("raycast")]
+    assert [k for n, _a, k in ctx.log if n == "extract_mesh"] == [dict(min_weight=pipe.config.tsdf_min_weight, keys=False)]
+    assert len(xyz) == 1 and len(rgb) == 1                                  # the stand-in's filter drops the first of two points
+    want = _RecordingContext()
+    want.fused = 1
+    for got, ref in zip(pipe.mesh, want._extract_mesh()):                   # the mesh as extracted: same vertices, same order
+        assert np.array_equal(got, ref)
+    assert pipe.stats == dict(points_accumulated=5, points_dropped=7, voxels=2, after_outlier_filter=1, sparse=False, bricks_tsdf=0,
+                              bricks_centroid=0, pool_refused=0, blocks=1, mesh_vertices=3, mesh_triangles=1, render_views=2,
+                              render_residual_mm=[500.0, 500.0])
+    assert sorted(pipe.timings) == ["bound_and_allocate_s", "extract_and_filter_s", "fuse_s", "mesh_s", "render_s"]
+    assert pipe.grid == ctx.log[0][1][0] and pipe.blocks == [pipe.grid] and pipe.grid.dims == _LATTICE.dims
+    out = capsys.readouterr().out.splitlines()
+    assert out[0].startswith("  Grid (256, 200, 96) @ 10 mm, origin")
+    assert out[1:] == ["", "--- Step 3: Fuse depth frames (TSDF + voxel centroids) ---", "Camera 0: fused", "Camera 1: fused", "",
+                       "--- Step 4: Extract and clean point cloud ---", "  Mesh: 3 vertices, 1 triangles",
+                       f"  Rendered the model at 2 cameras into {tmp_path}", "", "Final reconstruction: 1 points, 2 cameras"]
+
+
+def test_fusion_body_takes_a_given_layout_as_it_is(monkeypatch):
+    pipe, ctx = _pipe(monkeypatch), _RecordingContext()
+    grid = GridSpec((1024, 1024, 1024), (0.0, 0.0, 0.0), 0.005, 0.02, pool_tsdf=5000, pool_centroid=4000)     # 40 GiB if dense: would be counted
+    pipe._fuse_blocks(ctx, grid, [pl.Block(grid, (0, 0, 0), grid.dims)], layout_given=True)
+    assert ctx.names()[0] == "attach_grid" and ctx.log[0][1][0] is grid and "count_bricks" not in ctx.names()
+    assert pipe.grid is grid and pipe.stats["sparse"] and "render_s" not in pipe.timings and "blocks_s" not in pipe.timings
+
+
+def test_fusion_body_three_blocks_attach_core_fuse_extract_detach_then_one_filter(monkeypatch, capsys):
+    pipe, ctx = _pipe(monkeypatch), _RecordingContext()
+    blocks = pl.plan_blocks(_LATTICE, 136 ** 3)
+    assert len(blocks) == 3
+    xyz, rgb = pipe._fuse_blocks(ctx, _LATTICE, blocks)
+    assert ctx.names() == _PER_BLOCK * 3 + ["statistical_outlier"]
+    calls = [c for c in ctx.log if c[0] in ("attach_grid", "set_block_core", "extract_mesh")]
+    for k, b in enumerate(blocks):
+        attach, core, mesh = calls[3 * k:3 * k + 3]
+        assert attach[1][0] == b.grid and core[1] == (_LATTICE.dims, b.lo, b.hi) and mesh[2]["keys"] is True
+    assert np.array_equal(xyz[:, 0], [1, 2, 2, 3, 3]) and len(rgb) == 5       # the three clouds in block order, filtered once
+    vx, vr, vt = pipe.mesh
+    assert vx[:, 0].tolist() == [100, 103, 106, 200, 203, 206, 300, 303, 306] and vr[:, 0].tolist() == [1, 1, 1, 2, 2, 2, 3, 3, 3]
+    assert vt.tolist() == [[2, 0, 1], [5, 3, 4], [8, 6, 7]]
+    assert pipe.stats == dict(points_accumulated=12, points_dropped=0, voxels=6, after_outlier_filter=5, sparse=False, bricks_tsdf=0,
+                              bricks_centroid=0, pool_refused=0, blocks=3, mesh_vertices=9, mesh_triangles=3)
+    assert sorted(pipe.timings) == ["blocks_s", "bound_and_allocate_s", "extract_and_filter_s", "fuse_s", "mesh_s"]
+    assert pipe.grid is _LATTICE and pipe.blocks == [b.grid for b in blocks]
+    out = capsys.readouterr().out.splitlines()
+    assert out[0] == "  Lattice (256, 200, 96) @ 10 mm, origin [0. 0. 0.]: 4915200 voxels in 3 blocks"
+    assert out[1:3] == ["", "--- Step 3: Fuse depth frames block by block (TSDF + voxel centroids) ---"]
+    assert [l.split(",")[0] for l in out[3:6]] == ["  Block 1 at (0", "  Block 2 at (128", "  Block 3 at (0"]
+    assert out[6:] == ["Camera 0: fused", "Camera 1: fused", "", "--- Step 4: Extract and clean point cloud ---",
+                       "  Mesh: 9 vertices, 3 triangles (welded from 3 blocks)", "", "Final reconstruction: 5 points, 2 cameras"]
+
+
+def test_fusion_body_refuses_render_dir_with_three_blocks_before_attaching(monkeypatch, tmp_path):
+    pipe, ctx = _pipe(monkeypatch, render_dir=str(tmp_path)), _RecordingContext()
+    with pytest.raises(ValueError, match="render_dir"):
+        pipe._fuse_blocks(ctx, _LATTICE, pl.plan_blocks(_LATTICE, 136 ** 3))
+    assert ctx.log == []

@@ -389,3 +389,42 @@ def test_read_npy_into_fills_a_staging_buffer_or_declines(tmp_path):
     assert not fileio.read_npy_into(tmp_path / "missing.npy", dst)
     fileio.keep_pil_blocks(4)                                                                        # harmless wherever Pillow lacks the hook
     assert np.array_equal(fileio.DepthImageLoader.load_depth(tmp_path / "a.npy"), a)
+
+
+def _random_pose(rng):
+    q, _ = np.linalg.qr(rng.standard_normal((3, 3)))
+    return q * np.sign(np.linalg.det(q)), rng.standard_normal((3, 1))
+
+
+def test_relative_prior_takes_pose_a_to_pose_b_and_back():
+    """relative_prior(P, a, b) composed with pose a is pose b, and (b, a) is its inverse: to 1e-12, the fp64 round-off of a handful
+    of 3x3 products on unit-scale data."""
+    from tl3d.pipeline import relative_prior
+    rng = np.random.default_rng(11)
+    P = [_random_pose(rng) for _ in range(6)]
+    for a in range(6):
+        for b in range(6):
+            T = relative_prior(P, a, b)
+            assert T.shape == (4, 4) and T.dtype == np.float64 and np.array_equal(T[3], [0, 0, 0, 1])
+            r, t = compose(T[:3, :3], T[:3, 3], *P[a])
+            assert np.abs(r - P[b][0]).max() < 1e-12 and np.abs(t - P[b][1]).max() < 1e-12
+            assert np.abs(relative_prior(P, b, a) @ T - np.eye(4)).max() < 1e-12
+
+
+def test_icp_levels_come_from_the_config_once():
+    """The dicts handed to icp_batch: the coarse levels then the fine one; Sim(3) puts the wide level in front, adds estimate_scale
+    and keeps the last ICP_MAX_LEVELS."""
+    from tl3d import _cabi as abi
+    from tl3d.pipeline import DepthToReconstructionPipeline
+    c = ReconstructionConfig()
+    common = dict(damping=c.icp_damping, eig_rel=c.icp_eig_rel, eps=c.icp_eps)
+    rows = [tuple(l) for l in c.icp_coarse] + [(c.icp_iters, c.icp_stride, c.icp_max_dist)]
+    pipe = DepthToReconstructionPipeline(c)
+    assert pipe._icp_levels() == [dict(iters=int(i), stride=int(s), max_dist=float(d), **common) for i, s, d in rows]
+    wide = [(15, max(2, 2 * int(c.icp_stride)), 1.0)] + rows
+    assert pipe._icp_levels(sim3=True) == [dict(iters=int(i), stride=int(s), max_dist=float(d), estimate_scale=True, **common)
+                                            for i, s, d in wide][-abi.ICP_MAX_LEVELS:]
+    c.icp_coarse = [(3, 8, 0.5)] * abi.ICP_MAX_LEVELS                  # too many for Sim(3): the front ones go, the wide one first
+    got = DepthToReconstructionPipeline(c)._icp_levels(sim3=True)
+    assert len(got) == abi.ICP_MAX_LEVELS and got[-1]["iters"] == int(c.icp_iters) and got[0]["max_dist"] == 0.5
+    assert len(DepthToReconstructionPipeline(c)._icp_levels()) == abi.ICP_MAX_LEVELS + 1

@@ -18,6 +18,7 @@ import numpy as np
 from . import _cabi as abi
 from .config import CameraIntrinsics, ReconstructionConfig
 from .fusion import FusionContext, GridSpec
+from .lattice import lattice_extent, tile
 
 MERGE_GRID_BUDGET_BYTES = 96 << 30      # dense centroid grid the merge may allocate (HBM is 288 GB)
 
@@ -103,15 +104,13 @@ class _DeviceDense:
                 mn, mx = np.minimum(mn, a), np.maximum(mx, b)
         finally:
             boot.close()
-        origin = mn - 0.5 * v
-        dims = np.floor((mx - origin) / v).astype(np.int64) + 1
-        dims = ((dims + 7) // 8) * 8
+        origin, dims = lattice_extent(mn, mx, v)
         # Open3D's hash map holds the occupied voxels only, whatever the extent (D2R:404-410; the reference's defaults reach
         # 50 m at 5 mm: D2R:57, :64).  Here a grid's brick table is direct-indexed: up to 2^32 voxels per grid.  A larger lattice is
         # fused BLOCK BY BLOCK: blocks of at most 2^31 voxels (multiples of 8 per axis) of the one lattice that starts at `origin`
         # (tl3d_config.voxel_offset: indices are computed against `origin` and the block's offset subtracted, so the voxels are the
         # single-grid voxels exactly); every point list goes to every block, a block keeps the points that fall into it.
-        blocks = _lattice_blocks(dims, 1 << 31)
+        blocks = tile(dims, lambda off, d: d[0] * d[1] * d[2] <= 1 << 31)
         n_points = int(sum(len(p) for p in pts))
         out_xyz, out_rgb = [], []
         for off, bdims in blocks:
@@ -145,25 +144,6 @@ class _DeviceDense:
         for c in self._bp_ctx.values():
             c.close()
         self._bp_ctx.clear()
-
-
-def _lattice_blocks(dims, max_voxels):
-    """[(offset, dims)] of blocks that tile a lattice of `dims` voxels (multiples of 8), each of at most max_voxels: the longest axis
-    is halved (at a multiple of 8) until every block fits."""
-    out, todo = [], [(np.zeros(3, np.int64), np.asarray(dims, np.int64))]
-    while todo:
-        off, d = todo.pop()
-        if int(d[0]) * int(d[1]) * int(d[2]) <= max_voxels:
-            out.append((off, d))
-            continue
-        a = int(np.argmax(d))
-        h = ((int(d[a]) // 2 + 7) // 8) * 8
-        lo, hi = d.copy(), d.copy()
-        lo[a], hi[a] = h, d[a] - h
-        off_hi = off.copy()
-        off_hi[a] += h
-        todo += [(off_hi, hi), (off, lo)]
-    return sorted(out, key=lambda b: (int(b[0][2]), int(b[0][1]), int(b[0][0])))
 
 
 class DenseReconstructor(_DeviceDense):

@@ -12,7 +12,7 @@ what D2R itself falls back to (D2R:555-558).
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
+from collections import defaultdict
 from typing import List, Optional, Tuple
 
 import time
@@ -24,6 +24,8 @@ from . import fileio
 from .config import ReconstructionConfig
 from .dense import DenseReconstructor
 from .fusion import FusionContext, GridSpec
+from .lattice import (MAX_BLOCK_VOXELS, Block, _make_block, align_grid_to_open3d, layout_from_counts, plan_blocks,  # noqa: F401
+                      plan_grid, plan_lattice, split_block, weld_meshes)
 
 
 def compose(r_rel, t_rel, r_prev, t_prev):
@@ -32,64 +34,16 @@ def compose(r_rel, t_rel, r_prev, t_prev):
     return r_rel @ np.asarray(r_prev, np.float64), r_rel @ np.asarray(t_prev, np.float64).reshape(3, 1) + np.asarray(t_rel, np.float64).reshape(3, 1)
 
 
-def plan_grid(bounds_min, bounds_max, voxel_size, grid_dim, channels=abi.CH_TSDF | abi.CH_CENTROID, trunc_voxels=4.0,
-              max_voxels=None, sparse_bytes=None):
-    """Grid with Open3D's voxel origin (min_bound - voxel/2) covering the bounds.
-
-    Up to a voxel BUDGET (default grid_dim^3 voxels in total; not a cube: a 2 m x 2.4 m x 12 m corridor at 5 mm becomes
-    400 x 480 x 2400 voxels) the grid is dense.  Beyond it the grid is SPARSE, as the reference's hash-map merge is
-    (D2R:404-410): the same dims, records only for the bricks the data touches, pools sized by sparse_bytes (default: the dense
-    budget's bytes) -- a GUESS when nothing is known about the frames; choose_layout() replaces it by a count.  Only a scene of
-    more than 2^32 voxels is shrunk about its centre -- longest axis first -- and `clipped` returned True (points outside are
-    dropped and counted by the accumulation kernels; the caller prints the warning)."""
-    v = float(voxel_size)
-    mn, mx = np.asarray(bounds_min, np.float64), np.asarray(bounds_max, np.float64)
-    origin = mn - 0.5 * v
-    dims = np.floor((mx - origin) / v).astype(np.int64) + 1
-    dims = np.maximum(8, ((dims + 7) // 8) * 8)
-    budget = int(grid_dim) ** 3 if max_voxels is None else int(max_voxels)
-    budget = max(512, min(budget, 1 << 32))
-    clipped = False
-    want = dims.copy()
-    while int(dims[0]) * int(dims[1]) * int(dims[2]) > (1 << 32):    # shave the (currently) longest axis, 8 voxels at a time
-        a = int(np.argmax(dims))
-        if dims[a] <= 8:
-            break
-        dims[a] -= 8
-        clipped = True
-    for a in range(3):
-        if dims[a] < want[a]:
-            origin[a] = 0.5 * (mn[a] + mx[a]) - 0.5 * dims[a] * v
-    nvox = int(dims[0]) * int(dims[1]) * int(dims[2])
-    pool_t = pool_c = 0
-    if nvox > budget:
-        per_vox = (8 if channels & abi.CH_TSDF else 0) + (32 if channels & abi.CH_CENTROID else 0)
-        mem = int(sparse_bytes) if sparse_bytes is not None else budget * per_vox
-        # surfaces: the TSDF band is ~3 bricks thick where the centroid channel holds one layer: 12 KB + 16 KB per surface brick
-        unit = (3 * 4096 if channels & abi.CH_TSDF else 0) + (16384 if channels & abi.CH_CENTROID else 0)
-        surf = max(4096, mem // unit)
-        pool_t = int(min(nvox // 512, 3 * surf)) if channels & abi.CH_TSDF else 0
-        pool_c = int(min(nvox // 512, surf)) if channels & abi.CH_CENTROID else 0
-    return GridSpec(tuple(int(d) for d in dims), tuple(float(o) for o in origin), v, trunc_voxels * v, channels,
-                    pool_tsdf=pool_t, pool_centroid=pool_c), clipped
+def relative_prior(init_poses, a, b):
+    """The 4x4 that takes frame a's camera coordinates to frame b's, from the two absolute priors: R = R_b R_a^T, t = t_b - R t_a."""
+    (ra, ta), (rb, tb) = init_poses[a], init_poses[b]
+    rr = np.asarray(rb) @ np.asarray(ra).T
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = rr, (np.asarray(tb).reshape(3) - rr @ np.asarray(ta).reshape(3))
+    return T
 
 
 DENSE_WITHOUT_ASKING = 1 << 30        # bytes: below this a dense grid is allocated (and cleared) faster than its occupancy is counted
-
-
-def layout_from_counts(grid: GridSpec, bricks_tsdf: int, bricks_centroid: int) -> GridSpec:
-    """Per channel: a pool of the counted bricks (+ 3 % + 2048: a slot lost to a race between two waves is not reused) when that
-    is less than half of the dense channel, else the dense channel."""
-    nbr = grid.nvox // 512
-    pool_t = pool_c = 0
-    if grid.channels & abi.CH_TSDF:
-        want = int(bricks_tsdf * 1.03) + 2048
-        pool_t = want if 2 * want < nbr else 0
-    if grid.channels & abi.CH_CENTROID:
-        want = int(bricks_centroid * 1.03) + 2048
-        pool_c = want if 2 * want < nbr else 0
-    return GridSpec(grid.dims, grid.origin, grid.voxel_size, grid.sdf_trunc, grid.channels, pool_tsdf=pool_t, pool_centroid=pool_c,
-                    voxel_offset=grid.voxel_offset)
 
 
 def choose_layout(ctx: FusionContext, grid: GridSpec, slots, poses, scales, centroid_subsample, dist=None, log=print) -> GridSpec:
@@ -113,17 +67,7 @@ def choose_layout(ctx: FusionContext, grid: GridSpec, slots, poses, scales, cent
     return out
 
 
-MAX_BLOCK_VOXELS = 1 << 32            # voxels of one grid, halo included: its brick table is direct-indexed
 BLOCK_MEMORY_MARGIN = 2 << 30         # device bytes a block leaves free for the fusion, extraction and mesh scratch
-
-
-@dataclass
-class Block:
-    """One block of a lattice: its grid (core + halo, grid.voxel_offset = the core's first lattice voxel) and its core [lo, hi) in
-    grid-local voxels.  The halo is one brick on every + side that has a next block: what the last cell layer of the core reads."""
-    grid: GridSpec
-    lo: Tuple[int, int, int]
-    hi: Tuple[int, int, int]
 
 
 def device_free_bytes(device: int) -> int:
@@ -134,97 +78,6 @@ def device_free_bytes(device: int) -> int:
     if lib.hipSetDevice(int(device)) != 0 or lib.hipMemGetInfo(C.byref(free), C.byref(total)) != 0:
         raise RuntimeError("hipMemGetInfo failed")
     return int(free.value)
-
-
-def plan_lattice(bounds_min, bounds_max, voxel_size, grid_dim, channels=abi.CH_TSDF | abi.CH_CENTROID, trunc_voxels=4.0) -> GridSpec:
-    """The whole lattice of the scene, never shaved: Open3D's voxel origin (min_bound - voxel/2) and the dims from the bounds.  A
-    lattice of at most 2^32 voxels is plan_grid()'s grid exactly (its layout guess included); a larger one is fused block by block
-    (plan_blocks) and each block chooses its own layout."""
-    grid, clipped = plan_grid(bounds_min, bounds_max, voxel_size, grid_dim, channels=channels, trunc_voxels=trunc_voxels)
-    if not clipped:
-        return grid
-    v = float(voxel_size)
-    mn, mx = np.asarray(bounds_min, np.float64), np.asarray(bounds_max, np.float64)
-    origin = mn - 0.5 * v
-    dims = np.maximum(8, ((np.floor((mx - origin) / v).astype(np.int64) + 1 + 7) // 8) * 8)
-    return GridSpec(tuple(int(d) for d in dims), tuple(float(o) for o in origin), v, trunc_voxels * v, channels)
-
-
-def _make_block(lattice: GridSpec, off, core) -> Block:
-    dims = tuple(int(core[a]) + (8 if int(off[a]) + int(core[a]) < int(lattice.dims[a]) else 0) for a in range(3))
-    grid = GridSpec(dims, lattice.origin, lattice.voxel_size, lattice.sdf_trunc, lattice.channels,
-                    voxel_offset=tuple(int(o) for o in off))
-    return Block(grid, (0, 0, 0), tuple(int(c) for c in core))
-
-
-def split_block(lattice: GridSpec, block: Block) -> List[Block]:
-    """The block's core halved along its longest axis (at a multiple of 8), each half with its own halo."""
-    off, core = np.asarray(block.grid.voxel_offset, np.int64), np.asarray(block.hi, np.int64) - np.asarray(block.lo, np.int64)
-    a = int(np.argmax(core))
-    if core[a] <= 8:
-        raise ValueError(f"block {tuple(core)} at {tuple(off)} cannot be split further")
-    h = ((int(core[a]) // 2 + 7) // 8) * 8
-    c0, c1, o1 = core.copy(), core.copy(), off.copy()
-    c0[a], c1[a], o1[a] = h, core[a] - h, off[a] + h
-    return [_make_block(lattice, off, c0), _make_block(lattice, o1, c1)]
-
-
-def plan_blocks(lattice: GridSpec, max_voxels: Optional[int] = None) -> List[Block]:
-    """Disjoint block cores that tile the lattice, each block's grid (core + halo) of at most max_voxels (default MAX_BLOCK_VOXELS):
-    the longest axis of a core is halved at a multiple of 8 until every block fits (DenseReconstructor's _lattice_blocks, plus the
-    halo).  A lattice within the limit is ONE block: the lattice grid itself, offset 0, no halo, no core."""
-    limit = MAX_BLOCK_VOXELS if max_voxels is None else int(max_voxels)
-    if lattice.nvox <= limit:
-        return [Block(lattice, (0, 0, 0), tuple(int(d) for d in lattice.dims))]
-    out, todo = [], [_make_block(lattice, (0, 0, 0), lattice.dims)]
-    while todo:
-        b = todo.pop()
-        if b.grid.nvox <= limit:
-            out.append(b)
-        else:
-            todo.extend(split_block(lattice, b))
-    return sorted(out, key=lambda b: tuple(reversed(b.grid.voxel_offset)))
-
-
-def _core_owned(keys, lattice_dims, lo, hi):
-    """Which keyed vertices (key = 3 * lattice linear index of the owner voxel + axis) have their owner in the lattice box [lo, hi)."""
-    lx, ly = int(lattice_dims[0]), int(lattice_dims[1])
-    idx = np.asarray(keys, np.int64) // 3
-    x, y, z = idx % lx, (idx // lx) % ly, idx // (lx * ly)
-    return ((x >= lo[0]) & (x < hi[0]) & (y >= lo[1]) & (y < hi[1]) & (z >= lo[2]) & (z < hi[2]))
-
-
-def weld_meshes(parts, lattice_dims):
-    """One mesh from the keyed meshes of the blocks of a lattice.  parts: [(xyz, rgb, tris, keys, core_lo, core_hi)] with the core
-    in LATTICE voxels.  Every vertex whose owner voxel lies in its block's core is kept (each owned edge vertex exists in exactly one
-    core, the unreferenced ones included, as in a single grid); a triangle's halo-owned vertices are found through their keys among
-    the kept ones.  Returns (xyz, rgb, tris, keys)."""
-    kx, kr, kk = [], [], []
-    for xyz, rgb, _tris, keys, lo, hi in parts:
-        own = _core_owned(keys, lattice_dims, lo, hi)
-        kx.append(np.asarray(xyz)[own])
-        kr.append(np.asarray(rgb)[own])
-        kk.append(np.asarray(keys, np.int64)[own])
-    xyz = np.concatenate(kx) if kx else np.zeros((0, 3), np.float32)
-    rgb = np.concatenate(kr) if kr else np.zeros((0, 3), np.uint8)
-    allk = np.concatenate(kk) if kk else np.zeros(0, np.int64)
-    order = np.argsort(allk, kind="stable")
-    sk = allk[order]
-    if len(sk) > 1 and np.any(sk[1:] == sk[:-1]):
-        raise ValueError("weld_meshes: a vertex is owned by two block cores (the cores overlap)")
-    out = []
-    for _xyz, _rgb, tris, keys, _lo, _hi in parts:
-        tris = np.asarray(tris)
-        if len(tris) == 0:
-            continue
-        tk = np.asarray(keys, np.int64)[tris.astype(np.int64)]
-        pos = np.searchsorted(sk, tk)
-        pos = np.minimum(pos, max(0, len(sk) - 1))
-        if len(sk) == 0 or not np.array_equal(sk[pos], tk):
-            raise ValueError("weld_meshes: a triangle references a vertex no block core owns (a halo is missing)")
-        out.append(order[pos].astype(np.uint32))
-    tris = np.concatenate(out) if out else np.zeros((0, 3), np.uint32)
-    return xyz, rgb, tris, allk
 
 
 class ScaleTracker:
@@ -287,17 +140,6 @@ def per_frame_scales(depths, anchors, default: float = 1.0, fetch=None):
     return tr.history[:n]
 
 
-def align_grid_to_open3d(grid: GridSpec, min_bound) -> GridSpec:
-    """Shift a grid by less than one voxel so its lattice coincides with Open3D's (voxel origin = min_bound - voxel/2,
-    depth_to_reconstruction.py:410).  With the lattices in phase the fused centroids are the reference's centroids up
-    to the accumulator quantum; out of phase, two 5 mm samplings of one surface sit 1-2 mm apart."""
-    v = float(grid.voxel_size)
-    o3d = np.asarray(min_bound, np.float64) - 0.5 * v
-    org = np.asarray(grid.origin, np.float64)
-    shift = np.mod(o3d - org, v)                       # in [0, v)
-    return GridSpec(grid.dims, tuple(float(x) for x in org + shift - v), grid.voxel_size, grid.sdf_trunc, grid.channels)
-
-
 class DepthToReconstructionPipeline:
     def __init__(self, config: ReconstructionConfig = None):
         self.config = config or ReconstructionConfig()
@@ -355,20 +197,10 @@ class DepthToReconstructionPipeline:
         """Frame-to-frame registration.  Consecutive pairs are independent: they go to the device in batches, every pair of
         a batch through all its levels and iterations inside one launch.  A failed pair drops its frame (reference rule,
         D2R:598-615): the following pair is then re-registered against the last kept frame."""
-        cfg = self.config
         n = len(self.depths)
         if not isinstance(scales, (list, tuple)):
             scales = [float(scales)] * n
-        # coarse-to-fine: each level is (iterations, pixel stride, correspondence gate); every level starts from the
-        # previous level's pose.  A wide first gate takes frame steps of 0.5 m / 30 degrees that the 5 cm gate alone loses
-        # from 15 cm / 8 degrees on (tools/icp_basin.py); a level that has converged stops after one iteration.
-        levels = [tuple(l) for l in cfg.icp_coarse] + [(cfg.icp_iters, cfg.icp_stride, cfg.icp_max_dist)]
-        common = dict(damping=cfg.icp_damping, eig_rel=cfg.icp_eig_rel, eps=cfg.icp_eps)
-
-        def level_kw(lv):
-            return dict(iters=int(lv[0]), stride=int(lv[1]), max_dist=float(lv[2]), **common)
-
-        level_list = [level_kw(lv) for lv in levels]
+        level_list = self._icp_levels()
 
         def blocking(src, cur, T0):
             return ctx.icp_batch([(src, cur)], level_list, T_init=[T0], scales=[scales[src]])[0]
@@ -379,14 +211,7 @@ class DepthToReconstructionPipeline:
         T_guess = np.eye(4)
 
         def prior(a, b_):
-            if init_poses is None:
-                return T_guess
-            r0, t0 = init_poses[a]
-            r1, t1 = init_poses[b_]
-            rr = np.asarray(r1) @ np.asarray(r0).T
-            T = np.eye(4)
-            T[:3, :3], T[:3, 3] = rr, (np.asarray(t1).reshape(3) - rr @ np.asarray(t0).reshape(3))
-            return T
+            return T_guess if init_poses is None else relative_prior(init_poses, a, b_)
 
         i = 1
         while i < n:
@@ -416,11 +241,18 @@ class DepthToReconstructionPipeline:
             i = batch[-1] + 1
         return poses, index
 
-    def _sim3_levels(self):
+    def _icp_levels(self, sim3: bool = False):
+        """The levels handed to ctx.icp_batch.  Coarse-to-fine: each level is (iterations, pixel stride, correspondence gate); every
+        level starts from the previous level's pose.  A wide first gate takes frame steps of 0.5 m / 30 degrees that the 5 cm gate
+        alone loses from 15 cm / 8 degrees on (tools/icp_basin.py); a level that has converged stops after one iteration.
+        sim3: a wider level still in front, the scale as 7th unknown, the last abi.ICP_MAX_LEVELS of them."""
         cfg = self.config
-        wide = [(15, max(2, int(cfg.icp_stride) * 2), 1.0)] + [tuple(l) for l in cfg.icp_coarse] + [(cfg.icp_iters, cfg.icp_stride, cfg.icp_max_dist)]
-        common = dict(damping=cfg.icp_damping, eig_rel=cfg.icp_eig_rel, eps=cfg.icp_eps, estimate_scale=True)
-        return [dict(iters=int(lv[0]), stride=int(lv[1]), max_dist=float(lv[2]), **common) for lv in wide][-abi.ICP_MAX_LEVELS:]
+        levels = [tuple(l) for l in cfg.icp_coarse] + [(cfg.icp_iters, cfg.icp_stride, cfg.icp_max_dist)]
+        common = dict(damping=cfg.icp_damping, eig_rel=cfg.icp_eig_rel, eps=cfg.icp_eps)
+        if sim3:
+            levels = ([(15, max(2, int(cfg.icp_stride) * 2), 1.0)] + levels)[-abi.ICP_MAX_LEVELS:]
+            common["estimate_scale"] = True
+        return [dict(iters=int(lv[0]), stride=int(lv[1]), max_dist=float(lv[2]), **common) for lv in levels]
 
     def _sim3_chain(self, ctx: FusionContext, frames, slot_of, state, init_poses=None, weight: float = 0.3):
         """One stretch of the Sim(3) registration chain: the views `frames` (ascending global indices), one after the other,
@@ -429,18 +261,12 @@ class DepthToReconstructionPipeline:
         comes back advanced, so that the next stretch (the next rank, reconstruct_sharded) continues exactly where this one ends.
         Returns {cur: row}; row: T (prev -> cur, the (R_rel, t_rel) the reference chains), against, ok, scale_raw (the
         registration's own estimate), scale (the running value the view is fused with), statistics."""
-        level_list = self._sim3_levels()
+        level_list = self._icp_levels(sim3=True)
         rows = {}
         prev, avg, T_guess = int(state["prev"]), float(state["avg"]), np.asarray(state["T_guess"], np.float64).reshape(4, 4)
         for cur in frames:
             print(f"\nProcessing image {cur}...")
-            T0 = T_guess
-            if init_poses is not None:
-                r0, t0 = init_poses[prev]
-                r1, t1 = init_poses[cur]
-                rr = np.asarray(r0) @ np.asarray(r1).T       # cur -> prev
-                T0 = np.eye(4)
-                T0[:3, :3], T0[:3, 3] = rr, (np.asarray(t0).reshape(3) - rr @ np.asarray(t1).reshape(3))
+            T0 = T_guess if init_poses is None else relative_prior(init_poses, cur, prev)
             res = ctx.icp_batch([(slot_of[cur], slot_of[prev])], level_list, T_init=[T0], scales=[avg])[0]
             ok = not (res["status"] == 2 or res["n_corr"] < 8 or not np.isfinite(res["scale"]) or not (1e-3 < res["scale"] < 1e3))
             row = dict(T=np.eye(4), against=prev, ok=ok, scale_raw=float(res["scale"]) if np.isfinite(res["scale"]) else 0.0, scale=avg,
@@ -562,8 +388,10 @@ class DepthToReconstructionPipeline:
             if len(self.camera_poses) < 2:
                 print("Pose estimation failed")
                 return None, None, None
-            blocks = None
-            if grid is None:
+            given = grid is not None
+            if given:
+                blocks = [Block(grid, (0, 0, 0), tuple(grid.dims))]          # the caller's grid: one block, its layout taken as given
+            else:
                 print("\n--- Step 2: Bound the scene ---")
                 # extent of the union of the frames' clouds, on the device
                 mn, mx = ctx.frames_bounds(self.frame_index, self.camera_poses, [self.scales[fi] for fi in self.frame_index],
@@ -573,170 +401,147 @@ class DepthToReconstructionPipeline:
                     return None, None, None
                 # the whole lattice, never shaved; more than one grid's worth of voxels is fused block by block
                 grid = plan_lattice(mn, mx, cfg.voxel_size, cfg.grid_dim, trunc_voxels=cfg.sdf_trunc_voxels)
-                blocks = plan_blocks(grid)
-                if len(blocks) > 1:
-                    if cfg.render_dir:
-                        raise ValueError(f"render_dir: the scene's lattice {grid.dims} ({grid.nvox} voxels) is fused in {len(blocks)} "
-                                         "blocks, and ray casting across blocks does not exist (raise --voxel-size)")
-                    self.grid = grid
-                    return self._reconstruct_blocked(ctx, grid, blocks, marks, clock)
-                # dense or sparse: from the bricks these frames will really touch, not from the extent
-                grid = choose_layout(ctx, grid, self.frame_index, self.camera_poses, [self.scales[fi] for fi in self.frame_index],
-                                     cfg.subsample_factor)
-            self.blocks = [grid]
-            print(f"  Grid {grid.dims} @ {grid.voxel_size * 1e3:g} mm, origin {np.round(grid.origin, 4)}")
-            self.grid = grid
-            ctx.attach_grid(grid)
-            marks.append(("bound_and_allocate", clock()))
-            print("\n--- Step 3: Fuse depth frames (TSDF + voxel centroids) ---")
-            ctx.fuse_frames(self.frame_index, self.camera_poses, [self.scales[fi] for fi in self.frame_index],
-                            centroid_subsample=cfg.subsample_factor)           # TSDF + centroids of every kept frame, in order
-            for fi in self.frame_index:
-                print(f"Camera {fi}: fused")
-            st = ctx.stats()
-            marks.append(("fuse", clock()))
-            print("\n--- Step 4: Extract and clean point cloud ---")
-            xyz, rgb = ctx.extract(abi.EXTRACT_CENTROID, min_count=1, min_weight=cfg.tsdf_min_weight,
-                                   max_abs_tsdf=cfg.tsdf_max_abs)
-            n_vox = len(xyz)
-            if len(xyz) > 0 and cfg.outlier_filter:         # D2R:413-415; DER's merge has none (DER:615-645)
-                keep = ctx.statistical_outlier(xyz, cfg.outlier_nb_neighbors, cfg.outlier_std_ratio, cell_size=2.0 * grid.voxel_size)
-                xyz, rgb = xyz[keep], rgb[keep]
-            self.stats = dict(points_accumulated=st["centroid_points"], points_dropped=st["centroid_dropped"],
-                              voxels=n_vox, after_outlier_filter=len(xyz), sparse=bool(grid.sparse),
-                              bricks_tsdf=st["pool_slots_tsdf"], bricks_centroid=st["pool_slots_centroid"], pool_refused=st["pool_refused"],
-                              blocks=1)
-            if grid.sparse:
-                print(f"  Sparse volume: {st['pool_slots_tsdf']} TSDF bricks and {st['pool_slots_centroid']} centroid bricks hold records "
-                      f"(of {grid.nvox // 512}); {grid.device_bytes() / 2**30:.2f} GiB")
-                if st["pool_refused"]:
-                    print(f"  Warning: {st['pool_refused']} bricks found the record pool full and are missing from the result "
-                          "(raise --grid, the memory budget of the volume)")
-            marks.append(("extract_and_filter", clock()))
-            if cfg.extract_mesh:
-                self.mesh = self._extract_mesh(ctx)
-                marks.append(("mesh", clock()))
-            if cfg.render_dir:
-                self._render_views(ctx)
-                marks.append(("render", clock()))
-            # wall time of each stage of this call (host clock; stages end at a point where the host has the stage's result)
-            self.timings = {name + "_s": round(t1 - t0, 4) for (name, t1), (_, t0) in zip(marks[1:], marks[:-1])}
+                blocks = plan_blocks(grid, MAX_BLOCK_VOXELS)
+            xyz, rgb = self._fuse_blocks(ctx, grid, blocks, marks, layout_given=given)
         finally:
             ctx.close()
-        print(f"\nFinal reconstruction: {len(xyz)} points, {len(self.camera_poses)} cameras")
         return xyz.astype(np.float64), rgb, self.camera_poses
 
-    def _reconstruct_blocked(self, ctx: FusionContext, lattice: GridSpec, blocks: List[Block], marks, clock):
-        """reconstruct() for a lattice of more than one grid's voxels: per block, in the one context whose frames stay resident,
-        attach the block's grid (layout from its own brick count), set its core, fuse every kept frame (the cull drops the frames
-        that miss the block), extract the core's points (and its keyed mesh), detach.  Then one statistical outlier filter over the
-        whole cloud and the blocks' meshes welded by their keys.  The blocks' cores tile the lattice and their
-        halos carry the neighbours' voxels bit for bit: the points and the mesh are the single lattice's."""
+    def _extract_points(self, ctx: FusionContext):
         cfg = self.config
+        return ctx.extract(abi.EXTRACT_CENTROID, min_count=1, min_weight=cfg.tsdf_min_weight, max_abs_tsdf=cfg.tsdf_max_abs)
+
+    def _clean_cloud(self, ctx: FusionContext, clouds, voxel_size):
+        """The extracted clouds [(xyz, rgb)] as one, through the statistical outlier filter (D2R:413-415, once over the whole cloud;
+        DER's merge has none, DER:615-645).  Returns xyz, rgb and the two counts of `stats`."""
+        cfg = self.config
+        xyz, rgb = clouds[0] if len(clouds) == 1 else [np.concatenate(c) for c in zip(*clouds)]
+        n_vox = len(xyz)
+        if n_vox > 0 and cfg.outlier_filter:
+            keep = ctx.statistical_outlier(xyz, cfg.outlier_nb_neighbors, cfg.outlier_std_ratio, cell_size=2.0 * voxel_size)
+            xyz, rgb = xyz[keep], rgb[keep]
+        return xyz, rgb, dict(voxels=n_vox, after_outlier_filter=len(xyz))
+
+    def _fuse_blocks(self, ctx: FusionContext, lattice: GridSpec, blocks: List[Block], marks=None, layout_given: bool = False):
+        """The fusion of reconstruct(), for a lattice planned as one block as for many.  Per block, in the one context whose frames
+        stay resident: the block's layout (from its own brick count), attach its grid, set its core, fuse every kept frame (the cull
+        drops the frames that miss the block), extract the core's points (and its keyed mesh), detach.  Then once: the statistical
+        outlier filter over the whole cloud, the blocks' meshes welded by their keys, `stats`, `timings`.  The blocks'
+        cores tile the lattice and their halos carry the neighbours' voxels bit for bit: the points and the mesh are the single
+        lattice's.  A plan of ONE block is the lattice grid itself: no core and no keys (its mesh is returned as extracted, nothing
+        to weld), and it stays attached, because the ray caster (config.render_dir) reads an attached grid without a core.
+        Returns (xyz f32, rgb)."""
+        cfg, clock = self.config, time.perf_counter
+        marks = marks or [("start", clock())]
+        one = len(blocks) == 1
+        if cfg.render_dir and not one:
+            raise ValueError(f"render_dir: the scene's lattice {lattice.dims} ({lattice.nvox} voxels) is fused in {len(blocks)} "
+                             "blocks, and ray casting across blocks does not exist (raise --voxel-size)")
         scales = [self.scales[fi] for fi in self.frame_index]
-        print(f"  Lattice {lattice.dims} @ {lattice.voxel_size * 1e3:g} mm, origin {np.round(lattice.origin, 4)}: {lattice.nvox} voxels "
-              f"in {len(blocks)} blocks")
-        todo, done = list(reversed(blocks)), []
-        pts, cols, mesh_parts = [], [], []
-        core_points, valid_points = 0, None
+        # wall time per stage, summed over the blocks (host clock; a stage ends where the host has its result); the bounding and
+        # planning since the last mark count as allocation
+        stage = defaultdict(float, bound_and_allocate=clock() - marks[-1][1])
+        if not one:
+            print(f"  Lattice {lattice.dims} @ {lattice.voxel_size * 1e3:g} mm, origin {np.round(lattice.origin, 4)}: {lattice.nvox} voxels "
+                  f"in {len(blocks)} blocks")
+            print("\n--- Step 3: Fuse depth frames block by block (TSDF + voxel centroids) ---")
+        todo, done, clouds, mesh_parts = list(reversed(blocks)), [], [], []
+        core_points = valid_points = 0
         sums = dict(bricks_tsdf=0, bricks_centroid=0, pool_refused=0)
-        sparse = False
-        stage = dict(bound_and_allocate=0.0, fuse=0.0, extract_and_filter=0.0, mesh=0.0)
-        print("\n--- Step 3: Fuse depth frames block by block (TSDF + voxel centroids) ---")
         while todo:
             b = todo.pop()
             t0 = clock()
-            layout = choose_layout(ctx, b.grid, self.frame_index, self.camera_poses, scales, cfg.subsample_factor)
-            need = layout.device_bytes()
-            if cfg.extract_mesh and layout.channels & abi.CH_TSDF:
-                need += (layout.pool_tsdf or layout.nvox // 512) * 2048          # the mesh's vertex-id scratch: 4 B per TSDF record
-            if need > device_free_bytes(cfg.device) - BLOCK_MEMORY_MARGIN:
-                halves = split_block(lattice, b)
-                print(f"  Block at {b.grid.voxel_offset}: {need / 2**30:.2f} GiB does not fit, split in two")
-                todo.extend(reversed(halves))
-                continue
+            # dense or sparse: from the bricks these frames will really touch, not from the extent
+            layout = b.grid if layout_given else choose_layout(ctx, b.grid, self.frame_index, self.camera_poses, scales, cfg.subsample_factor)
+            if one:         # (a single grid that does not fit fails in attach_grid: splitting it instead would change behaviour)
+                print(f"  Grid {layout.dims} @ {layout.voxel_size * 1e3:g} mm, origin {np.round(layout.origin, 4)}")
+                print("\n--- Step 3: Fuse depth frames (TSDF + voxel centroids) ---")
+            else:
+                need = layout.device_bytes()
+                if cfg.extract_mesh and layout.channels & abi.CH_TSDF:
+                    need += (layout.pool_tsdf or layout.nvox // 512) * 2048          # the mesh's vertex-id scratch: 4 B per TSDF record
+                if need > device_free_bytes(cfg.device) - BLOCK_MEMORY_MARGIN:
+                    print(f"  Block at {b.grid.voxel_offset}: {need / 2**30:.2f} GiB does not fit, split in two")
+                    todo.extend(reversed(split_block(lattice, b)))
+                    continue
             ctx.attach_grid(layout)
-            ctx.set_block_core(lattice.dims, b.lo, b.hi)
+            if not one:
+                ctx.set_block_core(lattice.dims, b.lo, b.hi)
             ctx.reset_stats()
             t1 = clock()
+            # TSDF + centroids of every kept frame, in order
             ctx.fuse_frames(self.frame_index, self.camera_poses, scales, centroid_subsample=cfg.subsample_factor)
             st = ctx.stats()
             t2 = clock()
-            xyz, rgb = ctx.extract(abi.EXTRACT_CENTROID, min_count=1, min_weight=cfg.tsdf_min_weight, max_abs_tsdf=cfg.tsdf_max_abs)
-            pts.append(xyz)
-            cols.append(rgb)
+            clouds.append(self._extract_points(ctx))
             t3 = clock()
             if cfg.extract_mesh:
-                mx, mr, mt, mk = ctx.extract_mesh(min_weight=cfg.tsdf_min_weight, keys=True)
                 off = np.asarray(b.grid.voxel_offset, np.int64)
-                mesh_parts.append((mx, mr, mt, mk, off + np.asarray(b.lo), off + np.asarray(b.hi)))
+                mesh = ctx.extract_mesh(min_weight=cfg.tsdf_min_weight, keys=not one)
+                mesh_parts.append(tuple(mesh) + (off + np.asarray(b.lo), off + np.asarray(b.hi)))
+                stage["mesh"] += clock() - t3
             t4 = clock()
-            ctx.detach_grid()
+            if not one:
+                ctx.detach_grid()
             core_points += int(st["centroid_points"])
-            if valid_points is None:                     # every block sees every kept frame's samples: in its core or elsewhere
+            if not done:                                 # every block sees every kept frame's samples: in its core or elsewhere
                 valid_points = int(st["centroid_points"]) + int(st["centroid_dropped"])
             sums["bricks_tsdf"] += int(st["pool_slots_tsdf"])
             sums["bricks_centroid"] += int(st["pool_slots_centroid"])
             sums["pool_refused"] += int(st["pool_refused"])
-            sparse = sparse or layout.sparse
             done.append(layout)
             stage["bound_and_allocate"] += (t1 - t0) + (clock() - t4)
             stage["fuse"] += t2 - t1
             stage["extract_and_filter"] += t3 - t2
-            stage["mesh"] += t4 - t3
-            print(f"  Block {len(done)} at {layout.voxel_offset}, grid {layout.dims} ({'sparse' if layout.sparse else 'dense'}, "
-                  f"{layout.device_bytes() / 2**30:.2f} GiB): {len(xyz)} voxels")
-        self.blocks = done
+            if not one:
+                print(f"  Block {len(done)} at {layout.voxel_offset}, grid {layout.dims} ({'sparse' if layout.sparse else 'dense'}, "
+                      f"{layout.device_bytes() / 2**30:.2f} GiB): {len(clouds[-1][0])} voxels")
+        self.blocks, self.grid = done, (done[0] if one else lattice)
         for fi in self.frame_index:
             print(f"Camera {fi}: fused")
         print("\n--- Step 4: Extract and clean point cloud ---")
         t0 = clock()
-        xyz = np.concatenate(pts) if pts else np.zeros((0, 3), np.float32)
-        rgb = np.concatenate(cols) if cols else np.zeros((0, 3), np.uint8)
-        n_vox = len(xyz)
-        if len(xyz) > 0 and cfg.outlier_filter:         # D2R:413-415, once over the whole cloud
-            keep = ctx.statistical_outlier(xyz, cfg.outlier_nb_neighbors, cfg.outlier_std_ratio, cell_size=2.0 * lattice.voxel_size)
-            xyz, rgb = xyz[keep], rgb[keep]
+        xyz, rgb, counts = self._clean_cloud(ctx, clouds, lattice.voxel_size)
         stage["extract_and_filter"] += clock() - t0
-        self.stats = dict(points_accumulated=core_points, points_dropped=(valid_points or 0) - core_points, voxels=n_vox,
-                          after_outlier_filter=len(xyz), sparse=sparse, blocks=len(done), **sums)
+        self.stats = dict(points_accumulated=core_points, points_dropped=valid_points - core_points, **counts,
+                          sparse=any(g.sparse for g in done), **sums, blocks=len(done))
+        if one and done[0].sparse:
+            print(f"  Sparse volume: {sums['bricks_tsdf']} TSDF bricks and {sums['bricks_centroid']} centroid bricks hold records "
+                  f"(of {done[0].nvox // 512}); {done[0].device_bytes() / 2**30:.2f} GiB")
         if sums["pool_refused"]:
-            print(f"  Warning: {sums['pool_refused']} bricks found the record pool full and are missing from the result")
+            print(f"  Warning: {sums['pool_refused']} bricks found the record pool full and are missing from the result"
+                  + (" (raise --grid, the memory budget of the volume)" if one else ""))
         if cfg.extract_mesh:
             t0 = clock()
-            vx, vr, vt, _ = weld_meshes(mesh_parts, lattice.dims)
+            vx, vr, vt = mesh_parts[0][:3] if one else weld_meshes(mesh_parts, lattice.dims)[:3]
             self.mesh = (vx, vr, vt)
             self.stats["mesh_vertices"] = len(vx)
             self.stats["mesh_triangles"] = len(vt)
-            print(f"  Mesh: {len(vx)} vertices, {len(vt)} triangles (welded from {len(done)} blocks)")
+            print(f"  Mesh: {len(vx)} vertices, {len(vt)} triangles" + ("" if one else f" (welded from {len(done)} blocks)"))
             stage["mesh"] += clock() - t0
-        # wall time per stage, summed over the blocks (as reconstruct() reports it), and of the whole blocked fusion
+        if cfg.render_dir:
+            t0 = clock()
+            self._render_views(ctx)
+            stage["render"] = clock() - t0
         self.timings = {name + "_s": round(t1 - t0, 4) for (name, t1), (_, t0) in zip(marks[1:], marks[:-1])}
-        self.timings.update({k + "_s": round(v, 4) for k, v in stage.items() if k != "mesh" or cfg.extract_mesh})
-        self.timings["blocks_s"] = round(clock() - marks[-1][1], 4)
+        self.timings.update({k + "_s": round(v, 4) for k, v in stage.items()})
+        if not one:
+            self.timings["blocks_s"] = round(clock() - marks[-1][1], 4)          # the whole blocked fusion
         print(f"\nFinal reconstruction: {len(xyz)} points, {len(self.camera_poses)} cameras")
-        return xyz.astype(np.float64), rgb, self.camera_poses
+        return xyz, rgb
 
     # ---- multi-GPU: frames shard across ranks, one exchange step at merge time (SURVEY.md section 8e) -------------
     def _register_pairs(self, ctx: FusionContext, pairs, slot_of, scales, init_poses=None, T_guess=None):
         """Independent registrations (src, cur) -> result dict, every pair through the coarse-to-fine levels inside one
         launch per batch.  slot_of maps a global frame index to its resident slot."""
-        cfg = self.config
-        levels = [tuple(l) for l in cfg.icp_coarse] + [(cfg.icp_iters, cfg.icp_stride, cfg.icp_max_dist)]
-        common = dict(damping=cfg.icp_damping, eig_rel=cfg.icp_eig_rel, eps=cfg.icp_eps)
         out = {}
 
         def prior(a, b_):
             if init_poses is None:
                 return np.eye(4) if T_guess is None else T_guess
-            r0, t0 = init_poses[a]
-            r1, t1 = init_poses[b_]
-            rr = np.asarray(r1) @ np.asarray(r0).T
-            T = np.eye(4)
-            T[:3, :3], T[:3, 3] = rr, (np.asarray(t1).reshape(3) - rr @ np.asarray(t0).reshape(3))
-            return T
+            return relative_prior(init_poses, a, b_)
 
-        level_list = [dict(iters=int(lv[0]), stride=int(lv[1]), max_dist=float(lv[2]), **common) for lv in levels]
+        level_list = self._icp_levels()
         for i0 in range(0, len(pairs), 256):
             batch = pairs[i0:i0 + 256]
             results = ctx.icp_batch([(slot_of[a], slot_of[b_]) for a, b_ in batch], level_list, T_init=[prior(a, b_) for a, b_ in batch],
@@ -886,12 +691,8 @@ class DepthToReconstructionPipeline:
             xyz = rgb = None
             if rank == 0:
                 say("\n--- Step 5: Extract and clean point cloud ---")
-                xyz, rgb = ctx.extract(abi.EXTRACT_CENTROID, min_count=1, min_weight=cfg.tsdf_min_weight, max_abs_tsdf=cfg.tsdf_max_abs)
-                n_vox = len(xyz)
-                if len(xyz) > 0 and cfg.outlier_filter:
-                    keep = ctx.statistical_outlier(xyz, cfg.outlier_nb_neighbors, cfg.outlier_std_ratio, cell_size=2.0 * grid.voxel_size)
-                    xyz, rgb = xyz[keep], rgb[keep]
-                self.stats = dict(points_accumulated=tot[0], points_dropped=tot[1], voxels=n_vox, after_outlier_filter=len(xyz))
+                xyz, rgb, counts = self._clean_cloud(ctx, [self._extract_points(ctx)], grid.voxel_size)
+                self.stats = dict(points_accumulated=tot[0], points_dropped=tot[1], **counts)
                 if cfg.extract_mesh:
                     t0 = time.perf_counter()
                     self.mesh = self._extract_mesh(ctx)
