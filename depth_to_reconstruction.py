@@ -76,6 +76,9 @@ def main(argv=None):
     parser.add_argument("--render-output", type=str, default=None,
                         help="also render the fused model at every kept camera into this folder: <stem>_model_depth.npy / .png "
                              "(metres / u16 millimetres) and <stem>_model_color.png (one GPU only)")
+    parser.add_argument("--loop-closure", action="store_true",
+                        help="find revisits among the registered poses, register them too and optimise every pose over the resulting "
+                             "graph before fusing (one GPU only; not with --estimate-scale)")
     parser.add_argument("--device", type=int, default=0)
     parser.add_argument("--stream", dest="stream", action="store_true", default=True,
                         help="(default) decode on worker threads into pinned buffers with asynchronous uploads; host RAM never holds the sequence")
@@ -89,6 +92,10 @@ def main(argv=None):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.render_output and (args.gpus > 1 or world > 1):
         parser.error("--render-output needs a single GPU: with --gpus > 1 rank 0 does not hold the other ranks' frames")
+    if args.loop_closure and (args.gpus > 1 or world > 1):
+        parser.error("--loop-closure needs a single GPU: every kept frame must be resident where the revisits are registered")
+    if args.loop_closure and args.estimate_scale:
+        parser.error("--loop-closure does not go with --estimate-scale: the pose graph's edges carry no scale")
     if args.gpus > 1 and world == 1:
         return _spawn_ranks(args.gpus, sys.argv[1:] if argv is None else list(argv))
     dist = None
@@ -103,7 +110,7 @@ def main(argv=None):
                                   sdf_trunc_voxels=args.sdf_trunc, icp_iters=args.icp_iters, icp_stride=args.icp_stride,
                                   icp_max_dist=args.icp_max_dist, tsdf_min_weight=args.tsdf_min_weight, device=args.device,
                                   scale_update_weight=args.scale_update_weight, extract_mesh=args.mesh_output is not None,
-                                  render_dir=args.render_output)
+                                  render_dir=args.render_output, loop_closure=args.loop_closure)
     pipeline = DepthToReconstructionPipeline(config)
     # a rank decodes every frame on its host (pose chain and scale rule run over the whole sequence) and uploads its share
     streaming = args.stream and dist is None

@@ -301,6 +301,24 @@ typedef struct tl3d_icp_pair {
 int tl3d_icp_batch_enqueue(tl3d_ctx *ctx, const tl3d_icp_pair *pairs, int n_pairs, const tl3d_icp_params *levels, int n_levels);
 int tl3d_icp_batch_collect(tl3d_ctx *ctx, tl3d_icp_result *out /* [n_pairs] */, int n_pairs);
 
+/* a10, evaluation: ONE point-to-plane pass for each pair at the pose pairs[i].T_init (src camera -> tgt camera), no update: the
+ * normal equations a registration pass forms there (same source vertex -- the window-averaged depth when normal smoothing is on --
+ * same association, gate, residual and J = [p x n, n] as tl3d_icp_*; f32 values, fp64 sums of fp64 products).  A is the weight of
+ * the pair as an edge of a pose graph (the Hessian of its point-to-plane cost at T); n_corr / n_src score a candidate pair without
+ * registering it.  One launch per call (chunks of pairs beyond the scratch buffer), then a fixed-order sum per pair: a pair's
+ * result is bit for bit the same in every run, whatever n_pairs and wherever the pair stands in the batch.  n_pairs >= 0.  Blocks
+ * and fills `out`; ordered behind the uploads and normal maps issued before it.  TL3D_E_STATE while an ICP batch is uncollected or
+ * when a slot holds no frame / a target slot has no normal map; TL3D_E_INVALID for slots out of range, stride < 1, max_dist <= 0. */
+typedef struct tl3d_icp_eval {
+    double A[21];               /* upper triangle of sum J J^T, row-major, J = [p x n, n]          */
+    double b[6];                /* sum J r                                                         */
+    double e;                   /* sum r^2                                                         */
+    int64_t n_corr;             /* correspondences at T                                            */
+    int64_t n_src;              /* valid source samples                                            */
+} tl3d_icp_eval;
+int tl3d_icp_evaluate_pairs(tl3d_ctx *ctx, const tl3d_icp_pair *pairs, int n_pairs, int stride, double max_dist,
+                            tl3d_icp_eval *out /* [n_pairs] */);
+
 /* grids */
 /* Give a context created with channels = 0 its grid later (geometry fields of cfg: channels, nx, ny, nz, origin,
  * voxel_size, sdf_trunc, ext_*): frames stay resident while poses and scene bounds are still being computed. */

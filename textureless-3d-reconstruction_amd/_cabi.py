@@ -25,7 +25,7 @@ SYMBOLS = [
     "tl3d_upload_frame", "tl3d_download_depth", "tl3d_pinned_alloc", "tl3d_pinned_free", "tl3d_upload_frame_async",
     "tl3d_slot_wait", "tl3d_attach_grid", "tl3d_detach_grid", "tl3d_set_block_core", "tl3d_backproject", "tl3d_backproject_device", "tl3d_frame_bounds", "tl3d_frames_bounds", "tl3d_count_bricks", "tl3d_accumulate_centroid",
     "tl3d_accumulate_points", "tl3d_points_bounds", "tl3d_integrate", "tl3d_build_normals",
-    "tl3d_download_normals", "tl3d_icp_p2plane", "tl3d_icp_enqueue", "tl3d_icp_collect", "tl3d_icp_batch_enqueue", "tl3d_icp_batch_collect", "tl3d_host_pack_bgr_rows", "tl3d_host_copy_rows", "tl3d_build_normals_many", "tl3d_fuse_frames", "tl3d_grid_reset", "tl3d_grid_device_ptr",
+    "tl3d_download_normals", "tl3d_icp_p2plane", "tl3d_icp_enqueue", "tl3d_icp_collect", "tl3d_icp_batch_enqueue", "tl3d_icp_batch_collect", "tl3d_icp_evaluate_pairs", "tl3d_host_pack_bgr_rows", "tl3d_host_copy_rows", "tl3d_build_normals_many", "tl3d_fuse_frames", "tl3d_grid_reset", "tl3d_grid_device_ptr",
     "tl3d_grid_download", "tl3d_grid_upload", "tl3d_grid_add", "tl3d_grid_touched_bricks", "tl3d_grid_pack_bricks", "tl3d_grid_unpack_bricks", "tl3d_rccl_unique_id", "tl3d_rccl_init", "tl3d_allreduce_grid", "tl3d_extract", "tl3d_extract_mesh", "tl3d_extract_mesh_keyed", "tl3d_raycast", "tl3d_statistical_outlier",
     "tl3d_set_profile", "tl3d_set_normal_smoothing", "tl3d_set_tsdf_pairing", "tl3d_get_stats", "tl3d_reset_stats", "tl3d_event_record", "tl3d_event_elapsed_ms",
 ]
@@ -62,6 +62,10 @@ class IcpParams(C.Structure):
 
 class IcpPair(C.Structure):
     _fields_ = [("slot_src", C.c_int32), ("slot_tgt", C.c_int32), ("scale_src", C.c_double), ("T_init", C.c_double * 16)]
+
+
+class IcpEval(C.Structure):
+    _fields_ = [("A", C.c_double * 21), ("b", C.c_double * 6), ("e", C.c_double), ("n_corr", C.c_int64), ("n_src", C.c_int64)]
 
 
 ICP_MAX_LEVELS = 4
@@ -189,6 +193,7 @@ def load():
         "tl3d_icp_collect": [vp, i32, C.POINTER(IcpResult)],
         "tl3d_icp_batch_enqueue": [vp, C.POINTER(IcpPair), i32, C.POINTER(IcpParams), i32],
         "tl3d_icp_batch_collect": [vp, C.POINTER(IcpResult), i32],
+        "tl3d_icp_evaluate_pairs": [vp, C.POINTER(IcpPair), i32, i32, dbl, C.POINTER(IcpEval)],
         "tl3d_build_normals_many": [vp, i32, vp, vp, dbl],
         "tl3d_fuse_frames": [vp, i32, vp, vp, vp, vp, u32, i32, dbl, dbl],
         "tl3d_host_pack_bgr_rows": [vp, vp, i32, i32],

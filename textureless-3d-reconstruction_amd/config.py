@@ -56,6 +56,15 @@ class ReconstructionConfig:
     extract_mesh: bool = False
     # folder for renders of the fused model at every kept camera (DepthToReconstructionPipeline.reconstruct)
     render_dir: Optional[str] = None
+    # loop closure: revisits found from the chain's poses, registered with the same ICP, and every pose
+    # optimised over the resulting graph before bounding and fusing.  Off: nothing changes.
+    loop_closure: bool = False
+    loop_min_gap: int = 30              # kept frames between the two ends of a candidate
+    loop_max_dist: float = 0.3          # metres between the camera centres, at the chain's poses
+    loop_max_angle_deg: float = 20.0    # between the view axes
+    loop_edges_per_frame: int = 2       # candidates registered per (later) frame: the best by correspondences
+    loop_min_fitness: float = 0.5       # of a candidate at the chain-relative pose, and of a closure at its registered pose
+    loop_max_residual: float = 0.05     # metres of residual translation at the optimum above which a closure is dropped
 
     @property
     def K(self) -> np.ndarray:

@@ -664,6 +664,9 @@ int tl3d_destroy(tl3d_ctx *ctx) {
     }
     if (ctx->icp_batch.stream) (void)hipStreamSynchronize(ctx->icp_batch.stream);
     icp_batch_free(ctx->icp_batch);
+    if (ctx->icp_eval.pairs) (void)hipFree(ctx->icp_eval.pairs);
+    if (ctx->icp_eval.slab) (void)hipFree(ctx->icp_eval.slab);
+    if (ctx->icp_eval.sums) (void)hipFree(ctx->icp_eval.sums);
     if (ctx->bounds_slab) (void)hipFree(ctx->bounds_slab);
     for (int i = 0; i < 2; ++i)
         if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
@@ -1892,6 +1895,84 @@ int tl3d_icp_batch_collect(tl3d_ctx *ctx, tl3d_icp_result *out, int n_out) {
         out[i].iters_run = h.iters_run;
         out[i].status = h.status;
         out[i].scale = h.scale;
+    }
+    return TL3D_OK;
+}
+
+// ---- pairs scored at given poses: one pass each, no update (kernels_icp_eval.hip) ---------------------------------------
+int tl3d_icp_evaluate_pairs(tl3d_ctx *ctx, const tl3d_icp_pair *pairs, int n_pairs, int stride, double max_dist, tl3d_icp_eval *out) {
+    REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
+    REQUIRE(n_pairs >= 0, TL3D_E_INVALID, "n_pairs %d is negative", n_pairs);
+    REQUIRE(stride >= 1, TL3D_E_INVALID, "stride must be >= 1");
+    REQUIRE(max_dist > 0 && max_dist < 1e18, TL3D_E_INVALID, "max_dist must be positive and finite");
+    REQUIRE(n_pairs == 0 || (pairs && out), TL3D_E_INVALID, "null argument");
+    REQUIRE(!ctx->icp_batch.busy, TL3D_E_STATE, "an ICP batch is still uncollected");
+    for (int i = 0; i < n_pairs; ++i) {
+        REQUIRE(pairs[i].slot_src >= 0 && pairs[i].slot_src < ctx->cfg.n_slots && pairs[i].slot_tgt >= 0 && pairs[i].slot_tgt < ctx->cfg.n_slots,
+                TL3D_E_INVALID, "pair %d: slots (%d, %d) out of range [0,%d)", i, pairs[i].slot_src, pairs[i].slot_tgt, ctx->cfg.n_slots);
+        REQUIRE(ctx->slots[pairs[i].slot_src].loaded && ctx->slots[pairs[i].slot_tgt].loaded, TL3D_E_STATE, "pair %d: slot %d or %d holds no frame", i,
+                pairs[i].slot_src, pairs[i].slot_tgt);
+        REQUIRE(ctx->slots[pairs[i].slot_tgt].has_normals, TL3D_E_STATE, "target slot %d has no normal map (call tl3d_build_normals)", pairs[i].slot_tgt);
+    }
+    if (n_pairs == 0) return TL3D_OK;
+    const int Ws = (ctx->cam.W + stride - 1) / stride, Hs = (ctx->cam.H + stride - 1) / stride;
+    const int members = icp_eval_members(Ws, Hs);
+    size_t chunk = ICP_EVAL_SLAB_DOUBLES / ((size_t)members * ICP_EVAL_SUMS);
+    if (chunk < 1) chunk = 1;
+    if (chunk > 32768) chunk = 32768;                      // the pair is the launch's grid.y
+    if (chunk > (size_t)n_pairs) chunk = (size_t)n_pairs;
+    TL3D_HIP(hipSetDevice(ctx->device));
+    tl3d_ctx::IcpEval &b = ctx->icp_eval;
+    if (chunk > b.cap_pairs) {
+        if (b.pairs) (void)hipFree(b.pairs);
+        if (b.sums) (void)hipFree(b.sums);
+        b.pairs = nullptr; b.sums = nullptr; b.cap_pairs = 0;
+        const size_t cap = chunk < 64 ? 64 : chunk;
+        if (hipMalloc(&b.pairs, cap * sizeof(IcpEvalPair)) != hipSuccess || hipMalloc(&b.sums, cap * ICP_EVAL_SUMS * sizeof(double)) != hipSuccess) {
+            (void)hipGetLastError();
+            return set_err(TL3D_E_NOMEM, "ICP evaluation: buffer allocation failed");
+        }
+        b.cap_pairs = cap;
+    }
+    if (chunk * members * ICP_EVAL_SUMS > b.cap_slab) {
+        if (b.slab) (void)hipFree(b.slab);
+        b.slab = nullptr; b.cap_slab = 0;
+        if (hipMalloc(&b.slab, chunk * members * ICP_EVAL_SUMS * sizeof(double)) != hipSuccess) {
+            (void)hipGetLastError();
+            return set_err(TL3D_E_NOMEM, "ICP evaluation: buffer allocation failed");
+        }
+        b.cap_slab = chunk * members * ICP_EVAL_SUMS;
+    }
+    std::vector<IcpEvalPair> hp(chunk);
+    std::vector<double> hs(chunk * ICP_EVAL_SUMS);
+    const float md = (float)max_dist;
+    // the main stream: behind every upload and normal map issued so far
+    for (size_t i0 = 0; i0 < (size_t)n_pairs; i0 += chunk) {
+        const size_t m = (size_t)n_pairs - i0 < chunk ? (size_t)n_pairs - i0 : chunk;
+        for (size_t k = 0; k < m; ++k) {
+            const tl3d_icp_pair &p = pairs[i0 + k];
+            const Slot &ss = ctx->slots[p.slot_src], &st = ctx->slots[p.slot_tgt];
+            hp[k].depth_src = ss.smooth_radius > 0 ? ss.sdepth : ss.depth;
+            hp[k].nmap_tgt = st.nmap;
+            hp[k].scale = (float)p.scale_src;
+            hp[k].src_pm = ss.smooth_radius > 0 ? 1 : 0;
+            for (int j = 0; j < 12; ++j) hp[k].T[j] = (float)p.T_init[j];
+        }
+        TL3D_HIP(hipMemcpyAsync(b.pairs, hp.data(), m * sizeof(IcpEvalPair), hipMemcpyHostToDevice, ctx->stream));
+        const int rc = launch_icp_eval(ctx->stream, ctx->cam, b.pairs, (int)m, members, (float)ctx->cfg.min_depth, (float)ctx->cfg.max_depth, md * md, stride,
+                                       Ws, Hs, b.slab, b.sums);
+        if (rc) return rc;
+        TL3D_HIP(hipMemcpyAsync(hs.data(), b.sums, m * ICP_EVAL_SUMS * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        TL3D_HIP(hipStreamSynchronize(ctx->stream));
+        for (size_t k = 0; k < m; ++k) {
+            const double *s = &hs[k * ICP_EVAL_SUMS];
+            tl3d_icp_eval &o = out[i0 + k];
+            memcpy(o.A, s, 21 * sizeof(double));
+            memcpy(o.b, s + 21, 6 * sizeof(double));
+            o.e = s[27];
+            o.n_corr = (int64_t)s[28];
+            o.n_src = (int64_t)s[29];
+        }
     }
     return TL3D_OK;
 }

@@ -126,6 +126,15 @@ struct IcpBatchArgs {
     IcpLevel lv[ICP_MAX_LEVELS];
 };
 
+// Evaluation of pairs at given poses (kernels_icp_eval.hip, tl3d_icp_evaluate_pairs): one pass, no update.  Workgroups per pair: a
+// function of the level geometry only (a pair's sums do not depend on the batch it is in); 8192 samples per workgroup = 32 per
+// thread, eight trips of the sample loop, against one partial of 256 B written and read back.
+constexpr int ICP_EVAL_SAMPLES_PER_MEMBER = 8192;
+constexpr int ICP_EVAL_MEMBERS_CAP = 256;
+constexpr int ICP_EVAL_SUMS = 32;            // doubles per partial and per result: a[21] b[6] e cnt nsrc 0 0 (the head of IcpState::sums)
+constexpr size_t ICP_EVAL_SLAB_DOUBLES = (size_t)1 << 23;   // partials of one chunk of pairs: 64 MB at most (a chunk is never less than one pair)
+struct IcpEvalPair { const float *depth_src; const float4 *nmap_tgt; float scale; int src_pm; float T[12]; };    // T: rows 0..2 of the pose, f32
+
 // Frame buffers come from slabs, not one hipMalloc per buffer: a 1000-frame context used to make (and, slower, free) 4000
 // allocations.  One pool per buffer kind (equal-sized blocks); a slab holds up to 64 blocks and lives until tl3d_destroy.
 constexpr int FRAME_SLAB_BLOCKS = 64;
@@ -290,6 +299,11 @@ struct tl3d_ctx {
         int dbg_members;
         bool busy;
     } icp_batch;
+    struct IcpEval {             // tl3d_icp_evaluate_pairs: device buffers of one chunk of pairs (main stream), grown on demand
+        tl3d::IcpEvalPair *pairs;
+        double *slab, *sums;     // [pairs][members][ICP_EVAL_SUMS] partials, [pairs][ICP_EVAL_SUMS] totals
+        size_t cap_pairs, cap_slab;
+    } icp_eval;
     float *bounds_slab;
     // stats / profiling
     tl3d_stats stats;
@@ -463,6 +477,9 @@ int launch_normals(hipStream_t s, const Cam &cam, const float *depth, float scal
 int launch_icp_batch(hipStream_t s, const Cam &cam, const IcpBatchArgs &a);
 int launch_icp_iteration(hipStream_t s, const Cam &cam, const IcpRun *run, int final_pass, double *slab, IcpState *state, int nblocks,
                          unsigned *ticket);
+int icp_eval_members(int Ws, int Hs);
+int launch_icp_eval(hipStream_t s, const Cam &cam, const IcpEvalPair *pairs, int n_pairs, int members, float mind, float maxd, float md2, int stride,
+                    int Ws, int Hs, double *slab, double *out);
 // extraction
 int launch_extract_count(hipStream_t s, const Grid &g, int mode, int min_count, int min_weight, double max_abs,
                          const int2 *tsdf, const unsigned long long *cen, unsigned *block_counts, int nblocks);

@@ -143,7 +143,10 @@ def release_cached_memory():
 _ICP_PAIR_DT = np.dtype([("slot_src", "<i4"), ("slot_tgt", "<i4"), ("scale_src", "<f8"), ("T_init", "<f8", (16,))])
 _ICP_RESULT_DT = np.dtype([("T", "<f8", (16,)), ("fitness", "<f8"), ("rmse", "<f8"), ("n_corr", "<i8"), ("n_src", "<i8"),
                            ("iters_run", "<i4"), ("status", "<i4"), ("scale", "<f8")])
+_ICP_EVAL_DT = np.dtype([("A", "<f8", (21,)), ("b", "<f8", (6,)), ("e", "<f8"), ("n_corr", "<i8"), ("n_src", "<i8")])
 assert _ICP_PAIR_DT.itemsize == C.sizeof(abi.IcpPair) and _ICP_RESULT_DT.itemsize == C.sizeof(abi.IcpResult)
+assert _ICP_EVAL_DT.itemsize == C.sizeof(abi.IcpEval)
+_TRIU6 = np.triu_indices(6)
 
 
 class FusionContext:
@@ -496,6 +499,34 @@ class FusionContext:
     def icp_batch(self, pairs, levels, T_init=None, scales=None):
         self.icp_batch_enqueue(pairs, levels, T_init, scales)
         return self.icp_batch_collect()
+
+    def icp_evaluate(self, pairs, T, stride=2, max_dist=0.05, scales=None):
+        """One point-to-plane pass for every (slot_src, slot_tgt) of `pairs` at the pose T[i] (src camera -> tgt camera), no update
+        (tl3d_icp_evaluate_pairs).  Returns one dict per pair: A (6 x 6, sum J J^T with J = [p x n, n]: the weight of the pair as an
+        edge of a pose graph), b (sum J r), e (sum r^2), n_corr, n_src, fitness = n_corr / n_src, rmse = sqrt(e / n_corr).
+        T: one 4x4 per pair (None entries = identity); scales: metric scale of each pair's source depth."""
+        n = len(pairs)
+        arr = np.zeros(n, _ICP_PAIR_DT)
+        pr = np.asarray(pairs, np.int64).reshape(n, 2)
+        arr["slot_src"], arr["slot_tgt"] = pr[:, 0], pr[:, 1]
+        arr["scale_src"] = 1.0 if scales is None else np.asarray(scales, np.float64)
+        arr["T_init"] = np.eye(4).ravel()
+        if T is not None:
+            for i, T0 in enumerate(T):
+                if T0 is not None:
+                    arr["T_init"][i] = np.asarray(T0, np.float64).reshape(16)
+        res = np.zeros(max(1, n), _ICP_EVAL_DT)
+        abi.check(self._lib.tl3d_icp_evaluate_pairs(self._h, arr.ctypes.data_as(C.POINTER(abi.IcpPair)), n, int(stride), float(max_dist),
+                                                    res.ctypes.data_as(C.POINTER(abi.IcpEval))))
+        A = np.zeros((n, 6, 6))
+        A[:, _TRIU6[0], _TRIU6[1]] = res["A"][:n]
+        A[:, _TRIU6[1], _TRIU6[0]] = res["A"][:n]
+        out = []
+        for i in range(n):
+            nc, ns, e = int(res["n_corr"][i]), int(res["n_src"][i]), float(res["e"][i])
+            out.append(dict(A=A[i], b=res["b"][i].copy(), e=e, n_corr=nc, n_src=ns, fitness=nc / ns if ns > 0 else 0.0,
+                            rmse=float(np.sqrt(e / nc)) if nc > 0 else 0.0))
+        return out
 
     # ---- grids -----------------------------------------------------------------------------
     def reset(self):

@@ -149,6 +149,7 @@ class DepthToReconstructionPipeline:
         self.depths: List[np.ndarray] = []
         self.camera_poses: List[Tuple[np.ndarray, np.ndarray]] = []
         self.frame_index: List[int] = []          # which loaded frame each pose belongs to
+        self.chain_poses: List[Tuple[np.ndarray, np.ndarray]] = []   # the poses as registration chained them (config.loop_closure: before the optimisation)
         self.icp_log: List[dict] = []
         self.stats: dict = {}
         self.timings: dict = {}                   # wall seconds per stage of the last reconstruct()
@@ -240,6 +241,71 @@ class DepthToReconstructionPipeline:
                 prev = cur
             i = batch[-1] + 1
         return poses, index
+
+    def _close_loops(self, ctx: FusionContext):
+        """config.loop_closure: detect revisits from the chain's poses, register them with the chain's own
+        ICP, and optimise every pose over the graph of odometry and loop edges (posegraph).  An edge (i, j) is the registration of
+        src = kept frame i against tgt = kept frame j; its weight is the 6 x 6 A of the point-to-plane pass at its pose
+        (FusionContext.icp_evaluate, final level's stride and gate).  Returns (poses, stats); the poses ARE self.camera_poses when
+        nothing was optimised."""
+        from . import posegraph as pg
+        cfg = self.config
+        poses, index = self.camera_poses, self.frame_index
+        n = len(poses)
+        stats = dict(candidates=0, scored=0, registered=0, accepted=0, pruned=0, iterations=0, cost_before=0.0, cost_after=0.0,
+                     max_correction_mm=0.0, max_correction_deg=0.0)
+        cands = pg.loop_candidates(poses, cfg.loop_min_gap, cfg.loop_max_dist, cfg.loop_max_angle_deg)
+        stats["candidates"] = len(cands)
+        if not cands:
+            print("Loop closure: no revisit among the chain's poses, nothing to optimise")
+            return poses, stats
+        print("\n--- Step 1b: Close loops (pose graph over ICP edges) ---")
+        if n > pg.MAX_NODES:
+            raise ValueError(f"loop_closure: {n} kept frames exceed the {pg.MAX_NODES} nodes the dense pose-graph solve holds")
+        T = pg.poses_to_matrices(poses)
+        levels = self._icp_levels()
+        stride, gate, coarse_gate = levels[-1]["stride"], levels[-1]["max_dist"], levels[0]["max_dist"]
+        slot = lambda k: index[k]                            # kept frame k lives in slot index[k]
+        scale = lambda k: self.scales[index[k]]
+        # 1. the odometry edges: every chain pair at its result
+        chain_pairs = [(k, k + 1) for k in range(n - 1)]
+        chain_Z = [pg.relative_pose(T[i], T[j]) for i, j in chain_pairs]
+        ev = ctx.icp_evaluate([(slot(i), slot(j)) for i, j in chain_pairs], chain_Z, stride, gate, scales=[scale(i) for i, _ in chain_pairs])
+        edges = [(i, j, Z, e["A"]) for (i, j), Z, e in zip(chain_pairs, chain_Z, ev)]
+        # 2.-4. score every candidate at the chain-relative pose (coarse gate), keep the best few per frame
+        rel = [pg.relative_pose(T[i], T[j]) for i, j in cands]
+        sc = ctx.icp_evaluate([(slot(i), slot(j)) for i, j in cands], rel, stride, coarse_gate, scales=[scale(i) for i, _ in cands])
+        stats["scored"] = len(sc)
+        keep = pg.select_candidates(cands, [e["n_corr"] for e in sc], [e["fitness"] for e in sc], cfg.loop_edges_per_frame, cfg.loop_min_fitness)
+        stats["registered"] = len(keep)
+        loops = []
+        if keep:
+            # 5. register them from the chain-relative pose, through the chain's levels
+            kp = [cands[k] for k in keep]
+            res = []
+            for i0 in range(0, len(kp), 256):
+                part = kp[i0:i0 + 256]
+                res += ctx.icp_batch([(slot(i), slot(j)) for i, j in part], levels, T_init=[rel[k] for k in keep[i0:i0 + 256]],
+                                     scales=[scale(i) for i, _ in part])
+            # 6. their weights at the result; accept by status and fitness there
+            ev = ctx.icp_evaluate([(slot(i), slot(j)) for i, j in kp], [r["T"] for r in res], stride, gate, scales=[scale(i) for i, _ in kp])
+            for (i, j), r, e in zip(kp, res, ev):
+                if r["status"] != 2 and e["fitness"] >= cfg.loop_min_fitness:
+                    loops.append((i, j, np.array(r["T"]), e["A"]))
+        stats["accepted"] = len(loops)
+        if not loops:
+            print(f"  Loop closure: {len(cands)} candidates, none accepted, nothing to optimise")
+            return poses, stats
+        # 7., 8. optimise, drop the closures that keep a large residual, optimise again
+        import torch
+        device = torch.device("cuda", int(cfg.device)) if torch.cuda.is_available() else "cpu"
+        out, info = pg.optimise_and_prune(poses, edges + loops, [False] * len(edges) + [True] * len(loops), cfg.loop_max_residual, device=device)
+        mm, deg = pg.largest_correction(poses, out)
+        stats.update(pruned=len(info["pruned"]), iterations=info["iterations"], cost_before=info["cost_before"], cost_after=info["cost_after"],
+                     max_correction_mm=round(mm, 4), max_correction_deg=round(deg, 5))
+        print(f"  Loop closure: {len(cands)} candidates, {len(keep)} registered, {len(loops)} accepted, {len(info['pruned'])} pruned; "
+              f"{info['iterations']} iterations, cost {info['cost_before']:.4g} -> {info['cost_after']:.4g}, largest correction {mm:.2f} mm / {deg:.3f} deg")
+        return out, stats
 
     def _icp_levels(self, sim3: bool = False):
         """The levels handed to ctx.icp_batch.  Coarse-to-fine: each level is (iterations, pixel stride, correspondence gate); every
@@ -335,10 +401,13 @@ class DepthToReconstructionPipeline:
         _register_with_scale); view 0 keeps config.depth_scale (or its anchors' estimate).
         """
         self.mesh = None
+        cfg = self.config
+        loop = bool(getattr(cfg, "loop_closure", False)) and poses is None      # with poses given nothing is registered: the option is ignored
+        if loop and estimate_scale:
+            raise ValueError("loop_closure does not go with estimate_scale: the pose graph's edges carry no scale")
         if len(self.images) < 2:
             print("Need at least 2 images")
             return None, None, None
-        cfg = self.config
         print("\n" + "=" * 70)
         print("DEPTH-ENHANCED RECONSTRUCTION PIPELINE (MI355X: ICP + voxel fusion)")
         print("=" * 70)
@@ -388,6 +457,11 @@ class DepthToReconstructionPipeline:
             if len(self.camera_poses) < 2:
                 print("Pose estimation failed")
                 return None, None, None
+            self.chain_poses = list(self.camera_poses)
+            loop_stats = None
+            if loop:
+                self.camera_poses, loop_stats = self._close_loops(ctx)
+                marks.append(("loop_closure", clock()))
             given = grid is not None
             if given:
                 blocks = [Block(grid, (0, 0, 0), tuple(grid.dims))]          # the caller's grid: one block, its layout taken as given
@@ -403,6 +477,8 @@ class DepthToReconstructionPipeline:
                 grid = plan_lattice(mn, mx, cfg.voxel_size, cfg.grid_dim, trunc_voxels=cfg.sdf_trunc_voxels)
                 blocks = plan_blocks(grid, MAX_BLOCK_VOXELS)
             xyz, rgb = self._fuse_blocks(ctx, grid, blocks, marks, layout_given=given)
+            if loop_stats is not None:
+                self.stats["loop_closure"] = loop_stats
         finally:
             ctx.close()
         return xyz.astype(np.float64), rgb, self.camera_poses
@@ -571,6 +647,8 @@ class DepthToReconstructionPipeline:
         cloud are those of the single-process run bit for bit; fusion and merge stay parallel.
         Every frame must be loaded on every rank's host (load_data); only the rank's own range goes to its GPU."""
         from . import distributed as dd
+        if getattr(self.config, "loop_closure", False) and poses is None:
+            raise ValueError("loop_closure needs a single GPU: every kept frame must be resident where the revisits are registered")
         world, rank = dist.get_world_size(), dist.get_rank()
         self.mesh = None
         if len(self.images) < 2:
