@@ -40,6 +40,8 @@ def main(argv=None):
     parser.add_argument("--grid", type=int, default=1024, help="fusion volume budget: at most GRID^3 voxels in total")
     parser.add_argument("--loop-closure", action="store_true",
                         help="find revisits among the registered poses, register them too and optimise every pose over the resulting graph before fusing")
+    parser.add_argument("--model-tracking", action="store_true",
+                        help="after the registration, register every kept frame against the TSDF fused from the frames before it and fuse at those poses")
     parser.add_argument("--device", type=int, default=0)
     args = parser.parse_args(argv)
 
@@ -58,7 +60,7 @@ def main(argv=None):
         return 1
     config = ReconstructionConfig(fx=args.fx, fy=args.fy, cx=args.cx, cy=args.cy, min_depth=0.1, max_depth=100.0,
                                   voxel_size=0.005, subsample_factor=4, grid_dim=args.grid, device=args.device,
-                                  depth_scale=args.depth_scale, loop_closure=args.loop_closure,
+                                  depth_scale=args.depth_scale, loop_closure=args.loop_closure, model_tracking=args.model_tracking,
                                   outlier_filter=False)                   # DER's merge_pointclouds has no outlier filter (DER:615-645)
     pipeline = DepthToReconstructionPipeline(config)
     if args.depth_model:

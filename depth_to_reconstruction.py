@@ -79,6 +79,9 @@ def main(argv=None):
     parser.add_argument("--loop-closure", action="store_true",
                         help="find revisits among the registered poses, register them too and optimise every pose over the resulting "
                              "graph before fusing (one GPU only; not with --estimate-scale)")
+    parser.add_argument("--model-tracking", action="store_true",
+                        help="after the registration, register every kept frame against the TSDF fused from the frames before it "
+                             "(point-to-SDF) and fuse at those poses (one GPU only; not with --estimate-scale)")
     parser.add_argument("--device", type=int, default=0)
     parser.add_argument("--stream", dest="stream", action="store_true", default=True,
                         help="(default) decode on worker threads into pinned buffers with asynchronous uploads; host RAM never holds the sequence")
@@ -96,6 +99,10 @@ def main(argv=None):
         parser.error("--loop-closure needs a single GPU: every kept frame must be resident where the revisits are registered")
     if args.loop_closure and args.estimate_scale:
         parser.error("--loop-closure does not go with --estimate-scale: the pose graph's edges carry no scale")
+    if args.model_tracking and (args.gpus > 1 or world > 1):
+        parser.error("--model-tracking needs a single GPU: every kept frame is registered against one model, in order")
+    if args.model_tracking and args.estimate_scale:
+        parser.error("--model-tracking does not go with --estimate-scale: tracking against the model estimates no scale")
     if args.gpus > 1 and world == 1:
         return _spawn_ranks(args.gpus, sys.argv[1:] if argv is None else list(argv))
     dist = None
@@ -110,7 +117,8 @@ def main(argv=None):
                                   sdf_trunc_voxels=args.sdf_trunc, icp_iters=args.icp_iters, icp_stride=args.icp_stride,
                                   icp_max_dist=args.icp_max_dist, tsdf_min_weight=args.tsdf_min_weight, device=args.device,
                                   scale_update_weight=args.scale_update_weight, extract_mesh=args.mesh_output is not None,
-                                  render_dir=args.render_output, loop_closure=args.loop_closure)
+                                  render_dir=args.render_output, loop_closure=args.loop_closure,
+                                  model_tracking=args.model_tracking)
     pipeline = DepthToReconstructionPipeline(config)
     # a rank decodes every frame on its host (pose chain and scale rule run over the whole sequence) and uploads its share
     streaming = args.stream and dist is None

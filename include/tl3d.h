@@ -403,6 +403,24 @@ int tl3d_extract_mesh_keyed(tl3d_ctx *ctx, int min_weight,
 int tl3d_raycast(tl3d_ctx *ctx, const double R[9], const double t[3], int min_weight, double z_near, double z_far,
                  int slot, float *depth_out_hd, float *normal_out_hd, uint8_t *bgr_out_hd);
 
+/* Point-to-SDF registration of a frame against the TSDF channel (no reference code: the reference has no
+ * TSDF).  The residual of a sampled pixel of `slot` (f32 depth * scale, the context's depth range) is the trilinearly interpolated
+ * signed distance at its back-projection under the world->camera pose (R, t), in metres; the analytic gradient of the field plays
+ * the part of the normal; a sample is a correspondence when its cell is defined (all 8 voxels with weight >= max(1, min_weight),
+ * as tl3d_raycast) and |F| <= min(max_dist / sdf_trunc, 0.98).  J = [p x n, n] for moving the camera-frame point: the same 6x6
+ * normal equations as tl3d_icp_*.
+ * tl3d_track_evaluate: ONE pass at (R, t), no update; sums laid out as tl3d_icp_evaluate_pairs gives them, bit for bit the same in
+ * every run.  tl3d_track_frame: `levels` coarse to fine (iters, stride, max_dist as the gate, damping, eps, eig_rel;
+ * estimate_scale must be 0), every iteration on the device, then a final pass at the result; out->T is the world->camera pose as a
+ * row-major 4x4, out->scale echoes `scale`; status 2 (fewer than 8 correspondences or a singular system) leaves T at the last good
+ * pose.  Both first issue pending TSDF batches and fold the free-space counts, are ordered behind uploads into the slot and block
+ * for their result.  TL3D_E_STATE without a TSDF channel, on a block (voxel offset or core), for an empty slot and while an ICP
+ * batch is uncollected; TL3D_E_INVALID for a bad slot, stride < 1, max_dist <= 0, n_levels outside 1..TL3D_ICP_MAX_LEVELS, a null pose. */
+int tl3d_track_evaluate(tl3d_ctx *ctx, int slot, double scale, const double R[9], const double t[3], int min_weight, int stride,
+                        double max_dist, tl3d_icp_eval *out);
+int tl3d_track_frame(tl3d_ctx *ctx, int slot, double scale, const double R_init[9], const double t_init[3], int min_weight,
+                     const tl3d_icp_params *levels, int n_levels, tl3d_icp_result *out);
+
 /* f1: statistical outlier removal on a point list (Open3D remove_statistical_outlier, D2R:412-415) */
 int tl3d_statistical_outlier(tl3d_ctx *ctx, const float *xyz_hd, int64_t n, int nb_neighbors, double std_ratio,
                              double cell_size, uint8_t *keep_out_hd, int64_t *out_kept);

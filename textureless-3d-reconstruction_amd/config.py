@@ -65,6 +65,14 @@ class ReconstructionConfig:
     loop_edges_per_frame: int = 2       # candidates registered per (later) frame: the best by correspondences
     loop_min_fitness: float = 0.5       # of a candidate at the chain-relative pose, and of a closure at its registered pose
     loop_max_residual: float = 0.05     # metres of residual translation at the optimum above which a closure is dropped
+    # model tracking: after the chain (and the loop closure), every kept frame is registered against the
+    # TSDF fused from the frames before it (point-to-SDF) and its pose replaces the chain's.  Off: nothing changes.
+    model_tracking: bool = False
+    track_voxel_size: Optional[float] = None   # voxel of the tracking grid; None: voxel_size.  Doubled until the grid is one block and fits in memory
+    track_margin: float = 0.05          # metres added around the bounds of the frames at the chain's poses
+    track_min_weight: int = 1           # a voxel takes part once this many frames saw it
+    track_min_fitness: float = 0.5      # below it (or with status 2) a frame is lost: it keeps the chain-relative pose
+    track_levels: Optional[tuple] = None   # ((iterations, stride, gate in metres), ...) coarse to fine; None: the chain's levels
 
     @property
     def K(self) -> np.ndarray:

@@ -214,4 +214,27 @@ __device__ __forceinline__ void icp_accumulate_core(const Cam &cam, const float 
     }
 }
 
+// The wave reduction above as a function of its own, for kernels that keep 32 fp64 sums per lane (kernels_track.hip): same tree,
+// same totals; the total of sum c ends in v[0] of lanes 2c and 2c + 1.  Every lane of the wave must call it.
+// (icp_accumulate_core keeps its copy in place: calling this from there changed the instruction schedule of the registration
+// kernels, and their code objects are pinned.)
+template <int HALF, int DIST>
+__device__ __forceinline__ void wave_reduce_step(double (&v)[32], const int lane) {
+    const bool up = (lane & DIST) != 0;
+#pragma unroll
+    for (int k = 0; k < HALF; ++k) {
+        const double send = up ? v[k] : v[k + HALF];
+        const double keep = up ? v[k + HALF] : v[k];
+        v[k] = keep + __shfl_xor(send, DIST);
+    }
+}
+__device__ __forceinline__ void wave_reduce32(double (&v)[32], const int lane) {
+    wave_reduce_step<16, 32>(v, lane);
+    wave_reduce_step<8, 16>(v, lane);
+    wave_reduce_step<4, 8>(v, lane);
+    wave_reduce_step<2, 4>(v, lane);
+    wave_reduce_step<1, 2>(v, lane);
+    v[0] += __shfl_xor(v[0], 1);
+}
+
 }  // namespace tl3d

@@ -896,6 +896,64 @@ int launch_icp_batch(hipStream_t s, const Cam &cam, const IcpBatchArgs &a) {
     return TL3D_OK;
 }
 
+// Point-to-SDF tracking (kernels_track.hip), the step behind a pass: ONE wave adds the pass's partials in member order (lane c owns
+// sum c), keeps them in state->sums and, unless this is a final pass, solves the damped system with the solvers above and updates
+// the pose in device memory.  It lives here because the solvers do.  The pass's J is the Jacobian for moving the POINT (kernels_track.hip,
+// SIGN): the camera moves by y = -x.  final_pass: 0 an iteration; 1 the pass that ends a level which another one follows: the run
+// is over when the level failed or ended with fewer than 8 correspondences, else done / status / iters_run are re-armed for the next
+// level (what a host does between tl3d_icp_p2plane calls); 2 the pass that ends the last level.  Everything it reads was written by
+// earlier launches on the same stream.
+__global__ __launch_bounds__(64) void track_step_kernel(const double *__restrict__ slab, int members, IcpState *state, double damping, double eps,
+                                                        double eig_rel, int final_pass) {
+    if (state->over || (!final_pass && state->done)) return;
+    __shared__ double sums[TRACK_SUMS];
+    const int c = threadIdx.x;
+    if (c < TRACK_SUMS) {
+        double s = 0.0;
+        for (int m = 0; m < members; ++m) s += slab[(size_t)m * TRACK_SUMS + c];
+        sums[c] = s;
+        state->sums[c] = s;
+    }
+    __syncthreads();
+    if (final_pass) {
+        if (c == 0) {
+            if (final_pass == 2 || state->status == 2 || sums[28] < 8.0) {
+                state->over = 1;
+            } else {
+                state->done = 0;
+                state->status = 0;
+                state->iters_run = 0;
+            }
+        }
+        return;
+    }
+    double x[6];
+    const int fail = (sums[28] < 8.0) ? 1 : solve6_wave(sums, sums + 21, damping, eig_rel, x);      // wave-uniform
+    if (c != 0) return;
+    if (fail) {                                            // T stays the last good pose
+        state->done = 1;
+        state->status = 2;
+        return;
+    }
+    double y[6], mx = 0.0;
+    for (int i = 0; i < 6; ++i) {
+        y[i] = -x[i];
+        mx = fmax(mx, fabs(x[i]));
+    }
+    se3_apply(y, state->T);
+    state->iters_run = state->iters_run + 1;
+    if (mx < eps) {
+        state->done = 1;
+        state->status = 1;
+    }
+}
+
+int launch_track_step(hipStream_t s, const double *slab, int members, IcpState *state, double damping, double eps, double eig_rel, int final_pass) {
+    hipLaunchKernelGGL(track_step_kernel, dim3(1), dim3(64), 0, s, slab, members, state, damping, eps, eig_rel, final_pass);
+    TL3D_HIP(hipGetLastError());
+    return TL3D_OK;
+}
+
 // a normal map (phase-major rows) as the row-major [H][W] image the caller of tl3d_download_normals gets
 __global__ __launch_bounds__(256) void nmap_rowmajor_kernel(int W, int H, const float4 *__restrict__ nmap, float4 *__restrict__ out) {
     const int u = blockIdx.x * 64 + (threadIdx.x & 63);

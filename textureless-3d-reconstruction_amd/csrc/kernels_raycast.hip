@@ -9,6 +9,7 @@
 //   sample with F <= 0 ends the ray: a hit when the sample before it was defined (then F > 0 there), z* = z_k + (dz_k * F_k) /
 //   (F_k - F_k+1); no hit otherwise (the ray started behind or inside a surface, or came out of unobserved space behind one).
 #include "tl3d_internal.h"
+#include "tsdf_cell.h"
 
 namespace tl3d {
 
@@ -26,53 +27,8 @@ struct RayArgs {
     uint8_t *bgr, *bgr2;         // [H][W][3]
 };
 
-// one-entry cache of a brick's pool slot and pending free-space count: about two in three corner cubes lie in one brick
-struct BrickCache {
-    unsigned brick, slot, fc;
-};
-
-__device__ __forceinline__ int2 corner_record(const Grid &g, const int2 *__restrict__ pool, int i, int j, int k, BrickCache &bc) {
-    const unsigned brick = (unsigned)((((size_t)(k >> 3) * (size_t)g.nby + (size_t)(j >> 3)) * (size_t)g.nbx) + (size_t)(i >> 3));
-    if (brick != bc.brick) {
-        bc.brick = brick;
-        bc.slot = brick_slot(g.tsdf_tab, brick);
-        bc.fc = g.free_cnt ? g.free_cnt[brick] : 0u;
-    }
-    int2 r = make_int2(0, 0);
-    if (bc.slot < SLOT_FULL) r = pool[((size_t)bc.slot << 9) | (size_t)in_brick_index(i, j, k)];
-    r.x += (int)(bc.fc * 32767u);
-    r.y += (int)bc.fc;
-    return r;
-}
-
-// the 8 corner values of the cell whose lowest corner is floor(x); false when the cell is not inside the grid or a corner
-// is not usable.  f: the fractions x - floor(x).
-__device__ __forceinline__ bool load_cell(const Grid &g, const int2 *__restrict__ pool, int mw, const float x[3], float tc[8],
-                                          float f[3], BrickCache &bc) {
-    if (!(x[0] >= 0.0f && x[0] < (float)(g.nx - 1) && x[1] >= 0.0f && x[1] < (float)(g.ny - 1) && x[2] >= 0.0f &&
-          x[2] < (float)(g.nz - 1)))
-        return false;
-    const int i = (int)x[0], j = (int)x[1], k = (int)x[2];
-    f[0] = x[0] - (float)i;
-    f[1] = x[1] - (float)j;
-    f[2] = x[2] - (float)k;
-    bool ok = true;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        const int2 r = corner_record(g, pool, i + (c & 1), j + ((c >> 1) & 1), k + ((c >> 2) & 1), bc);
-        ok = ok && r.y >= mw;
-        tc[c] = (float)r.x / ((float)r.y * 32767.0f);
-    }
-    return ok;
-}
-
-__device__ __forceinline__ float lerpf(float a, float b, float t) { return a + t * (b - a); }
-
-__device__ __forceinline__ float trilinear(const float tc[8], const float f[3]) {
-    const float c00 = lerpf(tc[0], tc[1], f[0]), c10 = lerpf(tc[2], tc[3], f[0]);
-    const float c01 = lerpf(tc[4], tc[5], f[0]), c11 = lerpf(tc[6], tc[7], f[0]);
-    return lerpf(lerpf(c00, c10, f[1]), lerpf(c01, c11, f[1]), f[2]);
-}
+// BrickCache, corner_record, load_cell, lerpf, trilinear and trilinear_dx / dy / dz -- the cell gather and the field -- live in
+// tsdf_cell.h (shared with kernels_track.hip)
 
 __global__ __launch_bounds__(256) void raycast_kernel(Cam cam, Grid g, RayArgs a, const int2 *__restrict__ pool,
                                                       const unsigned long long *__restrict__ cen) {
@@ -129,9 +85,7 @@ __global__ __launch_bounds__(256) void raycast_kernel(Cam cam, Grid g, RayArgs a
         const float x[3] = {cg[0] + hit * dg[0], cg[1] + hit * dg[1], cg[2] + hit * dg[2]};
         float tc[8], f[3];
         if (load_cell(g, pool, a.mw, x, tc, f, bc)) {
-            const float gx = lerpf(lerpf(tc[1] - tc[0], tc[3] - tc[2], f[1]), lerpf(tc[5] - tc[4], tc[7] - tc[6], f[1]), f[2]);
-            const float gy = lerpf(lerpf(tc[2] - tc[0], tc[3] - tc[1], f[0]), lerpf(tc[6] - tc[4], tc[7] - tc[5], f[0]), f[2]);
-            const float gz = lerpf(lerpf(tc[4] - tc[0], tc[5] - tc[1], f[0]), lerpf(tc[6] - tc[2], tc[7] - tc[3], f[0]), f[1]);
+            const float gx = trilinear_dx(tc, f), gy = trilinear_dy(tc, f), gz = trilinear_dz(tc, f);
             const float len2 = (gx * gx + gy * gy) + gz * gz;
             if (len2 > 1e-30f) {
                 const float inv = 1.0f / sqrtf(len2);

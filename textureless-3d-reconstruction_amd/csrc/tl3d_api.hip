@@ -667,6 +667,9 @@ int tl3d_destroy(tl3d_ctx *ctx) {
     if (ctx->icp_eval.pairs) (void)hipFree(ctx->icp_eval.pairs);
     if (ctx->icp_eval.slab) (void)hipFree(ctx->icp_eval.slab);
     if (ctx->icp_eval.sums) (void)hipFree(ctx->icp_eval.sums);
+    if (ctx->track.state) (void)hipFree(ctx->track.state);
+    if (ctx->track.host) (void)hipHostFree(ctx->track.host);
+    if (ctx->track.slab) (void)hipFree(ctx->track.slab);
     if (ctx->bounds_slab) (void)hipFree(ctx->bounds_slab);
     for (int i = 0; i < 2; ++i)
         if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
@@ -2589,6 +2592,116 @@ int tl3d_raycast(tl3d_ctx *ctx, const double R[9], const double t[3], int min_we
     if (normal_out && dn != normal_out) TL3D_HIP(hipMemcpyAsync(normal_out, dn, npx * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     if (bgr_out && dc != bgr_out) TL3D_HIP(hipMemcpyAsync(bgr_out, dc, npx * 3, hipMemcpyDeviceToHost, ctx->stream));
     TL3D_HIP(hipStreamSynchronize(ctx->stream));
+    return TL3D_OK;
+}
+
+// ------------------------------------------------------------------------------------------- tracking against the TSDF
+// the checks, the flush and the buffers both tracking calls share; on return the main stream is behind every upload into the slot
+static int track_prepare(tl3d_ctx *ctx, int slot, const double R[9], const double t[3]) {
+    REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
+    REQUIRE(R && t, TL3D_E_INVALID, "null pose");
+    int rc = check_slot(ctx, slot, false);
+    if (rc) return rc;
+    REQUIRE(ctx->tsdf != nullptr, TL3D_E_STATE, "tracking needs a grid with a TSDF channel");
+    REQUIRE(!ctx->has_core && ctx->cfg.voxel_offset[0] == 0 && ctx->cfg.voxel_offset[1] == 0 && ctx->cfg.voxel_offset[2] == 0, TL3D_E_STATE,
+            "tracking needs a whole lattice: this grid is a block (voxel offset or core set)");
+    REQUIRE(ctx->slots[slot].loaded, TL3D_E_STATE, "slot %d holds no frame", slot);
+    REQUIRE(!ctx->icp_batch.busy, TL3D_E_STATE, "an ICP batch is still uncollected");
+    FLUSH_AND_FOLD(ctx);
+    TL3D_HIP(hipSetDevice(ctx->device));
+    tl3d_ctx::Track &tr = ctx->track;
+    if (!tr.state) {
+        bool ok = hipMalloc(&tr.state, sizeof(IcpState)) == hipSuccess;
+        ok = ok && hipHostMalloc(&tr.host, sizeof(IcpState), hipHostMallocDefault) == hipSuccess;
+        ok = ok && hipMalloc(&tr.slab, (size_t)track_members(ctx->cam.W, ctx->cam.H) * TRACK_SUMS * sizeof(double)) == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            if (tr.state) (void)hipFree(tr.state);
+            if (tr.host) (void)hipHostFree(tr.host);
+            if (tr.slab) (void)hipFree(tr.slab);
+            tr.state = nullptr; tr.host = nullptr; tr.slab = nullptr;
+            return set_err(TL3D_E_NOMEM, "tracking: buffer allocation failed");
+        }
+    }
+    IcpState *h = tr.host;
+    memset(h, 0, sizeof(*h));
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) h->T[4 * i + j] = R[3 * i + j];
+        h->T[4 * i + 3] = t[i];
+    }
+    h->T[15] = 1.0;
+    TL3D_HIP(hipMemcpyAsync(tr.state, h, sizeof(IcpState), hipMemcpyHostToDevice, ctx->stream));
+    return TL3D_OK;
+}
+
+// one pass and the step behind it (the sums in member order; final_pass 0: solve and pose update too)
+static int track_pass_step(tl3d_ctx *ctx, int slot, double scale, int min_weight, int stride, double max_dist, double damping, double eps,
+                           double eig_rel, int final_pass) {
+    tl3d_ctx::Track &tr = ctx->track;
+    int rc = launch_track_pass(ctx->stream, ctx->cam, ctx->grid, ctx->slots[slot].depth, (float)scale, (float)ctx->cfg.min_depth,
+                               (float)ctx->cfg.max_depth, min_weight, stride, max_dist, ctx->tsdf, tr.state, final_pass, tr.slab);
+    if (rc) return rc;
+    const int Ws = (ctx->cam.W + stride - 1) / stride, Hs = (ctx->cam.H + stride - 1) / stride;
+    return launch_track_step(ctx->stream, tr.slab, track_members(Ws, Hs), tr.state, damping, eps, eig_rel, final_pass);
+}
+
+static int track_collect(tl3d_ctx *ctx) {
+    tl3d_ctx::Track &tr = ctx->track;
+    TL3D_HIP(hipMemcpyAsync(tr.host, tr.state, sizeof(IcpState), hipMemcpyDeviceToHost, ctx->stream));
+    TL3D_HIP(hipStreamSynchronize(ctx->stream));
+    return TL3D_OK;
+}
+
+int tl3d_track_evaluate(tl3d_ctx *ctx, int slot, double scale, const double R[9], const double t[3], int min_weight, int stride,
+                        double max_dist, tl3d_icp_eval *out) {
+    REQUIRE(out != nullptr, TL3D_E_INVALID, "null argument");
+    REQUIRE(stride >= 1, TL3D_E_INVALID, "stride must be >= 1");
+    REQUIRE(max_dist > 0 && max_dist < 1e18, TL3D_E_INVALID, "max_dist must be positive and finite");
+    int rc = track_prepare(ctx, slot, R, t);
+    if (rc) return rc;
+    rc = track_pass_step(ctx, slot, scale, min_weight, stride, max_dist, 0.0, 0.0, 0.0, 2);
+    if (!rc) rc = track_collect(ctx);
+    if (rc) return rc;
+    const double *s = ctx->track.host->sums;
+    memcpy(out->A, s, 21 * sizeof(double));
+    memcpy(out->b, s + 21, 6 * sizeof(double));
+    out->e = s[27];
+    out->n_corr = (int64_t)s[28];
+    out->n_src = (int64_t)s[29];
+    return TL3D_OK;
+}
+
+int tl3d_track_frame(tl3d_ctx *ctx, int slot, double scale, const double R_init[9], const double t_init[3], int min_weight,
+                     const tl3d_icp_params *levels, int n_levels, tl3d_icp_result *out) {
+    REQUIRE(out != nullptr, TL3D_E_INVALID, "null argument");
+    REQUIRE(n_levels >= 1 && n_levels <= TL3D_ICP_MAX_LEVELS, TL3D_E_INVALID, "n_levels %d outside [1,%d]", n_levels, TL3D_ICP_MAX_LEVELS);
+    REQUIRE(levels != nullptr, TL3D_E_INVALID, "null argument");
+    for (int l = 0; l < n_levels; ++l) {
+        REQUIRE(levels[l].iters >= 0 && levels[l].iters <= 1000, TL3D_E_INVALID, "level %d: iters out of range", l);
+        REQUIRE(levels[l].stride >= 1, TL3D_E_INVALID, "level %d: stride must be >= 1", l);
+        REQUIRE(levels[l].max_dist > 0 && levels[l].max_dist < 1e18, TL3D_E_INVALID, "level %d: max_dist must be positive and finite", l);
+        REQUIRE(!levels[l].estimate_scale, TL3D_E_INVALID, "level %d: tracking does not estimate the scale (estimate_scale must be 0)", l);
+    }
+    int rc = track_prepare(ctx, slot, R_init, t_init);
+    if (rc) return rc;
+    // every launch of every level is enqueued now; launches behind a converged or failed level return at once
+    for (int l = 0; l < n_levels && !rc; ++l) {
+        const tl3d_icp_params &p = levels[l];
+        for (int it = 0; it < p.iters && !rc; ++it)
+            rc = track_pass_step(ctx, slot, scale, min_weight, p.stride, p.max_dist, p.damping, p.eps, p.eig_rel, 0);
+        if (!rc) rc = track_pass_step(ctx, slot, scale, min_weight, p.stride, p.max_dist, p.damping, p.eps, p.eig_rel, l == n_levels - 1 ? 2 : 1);
+    }
+    if (!rc) rc = track_collect(ctx);
+    if (rc) return rc;
+    const IcpState &h = *ctx->track.host;
+    memcpy(out->T, h.T, sizeof(out->T));
+    out->n_corr = (int64_t)h.sums[28];
+    out->n_src = (int64_t)h.sums[29];
+    out->fitness = h.sums[29] > 0 ? h.sums[28] / h.sums[29] : 0.0;
+    out->rmse = h.sums[28] > 0 ? sqrt(h.sums[27] / h.sums[28]) : 0.0;
+    out->iters_run = h.iters_run;
+    out->status = h.status;
+    out->scale = scale;
     return TL3D_OK;
 }
 

@@ -135,6 +135,18 @@ constexpr int ICP_EVAL_SUMS = 32;            // doubles per partial and per resu
 constexpr size_t ICP_EVAL_SLAB_DOUBLES = (size_t)1 << 23;   // partials of one chunk of pairs: 64 MB at most (a chunk is never less than one pair)
 struct IcpEvalPair { const float *depth_src; const float4 *nmap_tgt; float scale; int src_pm; float T[12]; };    // T: rows 0..2 of the pose, f32
 
+// Point-to-SDF tracking (kernels_track.hip): the arguments of one pass; the pose is read from an IcpState in device memory
+struct TrackArgs {
+    const float *depth;          // the slot's f32 depth, row-major [H][W]
+    float scale, mind, maxd;
+    float ivs;                   // (float)(1 / voxel size), as RayArgs
+    float gate;                  // |F| <= gate: min((float)max_dist / trunc, 0.98f)
+    float nk;                    // trunc * ivs: a per-voxel gradient of F -> metres per metre
+    int mw;                      // max(1, min_weight)
+    int stride, Ws, Hs, tx, ty;  // sampled extent (ceil) and its 8 x 8 tiles
+};
+constexpr int TRACK_SUMS = 32;   // doubles per partial: the head of IcpState::sums
+
 // Frame buffers come from slabs, not one hipMalloc per buffer: a 1000-frame context used to make (and, slower, free) 4000
 // allocations.  One pool per buffer kind (equal-sized blocks); a slab holds up to 64 blocks and lives until tl3d_destroy.
 constexpr int FRAME_SLAB_BLOCKS = 64;
@@ -304,6 +316,10 @@ struct tl3d_ctx {
         double *slab, *sums;     // [pairs][members][ICP_EVAL_SUMS] partials, [pairs][ICP_EVAL_SUMS] totals
         size_t cap_pairs, cap_slab;
     } icp_eval;
+    struct Track {               // tl3d_track_*: device state, partial-sum slab, pinned state for the way in and out (main stream)
+        tl3d::IcpState *state, *host;
+        double *slab;            // [track_members][TRACK_SUMS]
+    } track;
     float *bounds_slab;
     // stats / profiling
     tl3d_stats stats;
@@ -480,6 +496,11 @@ int launch_icp_iteration(hipStream_t s, const Cam &cam, const IcpRun *run, int f
 int icp_eval_members(int Ws, int Hs);
 int launch_icp_eval(hipStream_t s, const Cam &cam, const IcpEvalPair *pairs, int n_pairs, int members, float mind, float maxd, float md2, int stride,
                     int Ws, int Hs, double *slab, double *out);
+// tracking against the TSDF (kernels_track.hip: the pass; kernels_icp.hip: the step, next to the solvers it uses)
+int track_members(int Ws, int Hs);
+int launch_track_pass(hipStream_t s, const Cam &cam, const Grid &g, const float *depth, float scale, float mind, float maxd, int min_weight,
+                      int stride, double max_dist, const int2 *tsdf, const IcpState *state, int final_pass, double *slab);
+int launch_track_step(hipStream_t s, const double *slab, int members, IcpState *state, double damping, double eps, double eig_rel, int final_pass);
 // extraction
 int launch_extract_count(hipStream_t s, const Grid &g, int mode, int min_count, int min_weight, double max_abs,
                          const int2 *tsdf, const unsigned long long *cen, unsigned *block_counts, int nblocks);

@@ -528,6 +528,39 @@ class FusionContext:
                             rmse=float(np.sqrt(e / nc)) if nc > 0 else 0.0))
         return out
 
+    def track_evaluate(self, slot: int, pose, stride=2, max_dist=0.05, min_weight: int = 1, scale=1.0):
+        """One point-to-SDF pass of the frame in `slot` against the TSDF channel at pose = (R, t) (world->camera, as integrate), no
+        update (tl3d_track_evaluate).  A dict like icp_evaluate's: A (6 x 6, sum J J^T, J = [p x n, n] with n the
+        field's gradient in the camera frame), b (sum J r), e (sum r^2, r in metres), n_corr, n_src, fitness, rmse."""
+        r, t = abi.d9(pose[0]), abi.d3(pose[1])
+        res = abi.IcpEval()
+        abi.check(self._lib.tl3d_track_evaluate(self._h, int(slot), float(scale), abi.ptr(r), abi.ptr(t), int(min_weight), int(stride),
+                                                float(max_dist), C.byref(res)))
+        A = np.zeros((6, 6))
+        A[_TRIU6] = np.array(res.A)
+        A = A + np.triu(A, 1).T
+        nc, ns, e = int(res.n_corr), int(res.n_src), float(res.e)
+        return dict(A=A, b=np.array(res.b), e=e, n_corr=nc, n_src=ns, fitness=nc / ns if ns > 0 else 0.0,
+                    rmse=float(np.sqrt(e / nc)) if nc > 0 else 0.0)
+
+    def track(self, slot: int, pose_init, levels, min_weight: int = 1, scale=1.0):
+        """Register the frame in `slot` against the TSDF channel, starting at pose_init = (R, t) (world->camera), through `levels`
+        coarse to fine (dicts with icp()'s keywords: iters, stride, max_dist -- the gate on the signed distance --, damping, eps,
+        eig_rel), all on the device (tl3d_track_frame).  A dict like icp()'s, T being the world->camera pose, plus pose = (R, t);
+        status 2 (fewer than 8 correspondences or a singular system) leaves the last good pose."""
+        r, t = abi.d9(pose_init[0]), abi.d3(pose_init[1])
+        lv = (abi.IcpParams * max(1, len(levels)))()
+        for i, kw in enumerate(levels):
+            lv[i] = abi.IcpParams(int(kw.get("iters", 10)), int(kw.get("stride", 4)), float(kw.get("max_dist", 0.05)),
+                                  float(kw.get("damping", 1e-6)), float(kw.get("eps", 1e-9)), float(kw.get("eig_rel", 1e-4)),
+                                  1 if kw.get("estimate_scale", False) else 0, 0)
+        res = abi.IcpResult()
+        abi.check(self._lib.tl3d_track_frame(self._h, int(slot), float(scale), abi.ptr(r), abi.ptr(t), int(min_weight), lv, len(levels),
+                                             C.byref(res)))
+        T = np.array(res.T).reshape(4, 4)
+        return dict(T=T, pose=(T[:3, :3].copy(), T[:3, 3].copy()), fitness=res.fitness, rmse=res.rmse, n_corr=res.n_corr, n_src=res.n_src,
+                    iters_run=res.iters_run, status=res.status, scale=res.scale)
+
     # ---- grids -----------------------------------------------------------------------------
     def reset(self):
         abi.check(self._lib.tl3d_grid_reset(self._h))

@@ -149,7 +149,7 @@ class DepthToReconstructionPipeline:
         self.depths: List[np.ndarray] = []
         self.camera_poses: List[Tuple[np.ndarray, np.ndarray]] = []
         self.frame_index: List[int] = []          # which loaded frame each pose belongs to
-        self.chain_poses: List[Tuple[np.ndarray, np.ndarray]] = []   # the poses as registration chained them (config.loop_closure: before the optimisation)
+        self.chain_poses: List[Tuple[np.ndarray, np.ndarray]] = []   # the poses as registration chained them (config.loop_closure / model_tracking: before the optimisation / the tracking)
         self.icp_log: List[dict] = []
         self.stats: dict = {}
         self.timings: dict = {}                   # wall seconds per stage of the last reconstruct()
@@ -307,6 +307,65 @@ class DepthToReconstructionPipeline:
               f"{info['iterations']} iterations, cost {info['cost_before']:.4g} -> {info['cost_after']:.4g}, largest correction {mm:.2f} mm / {deg:.3f} deg")
         return out, stats
 
+    def _track_model(self, ctx: FusionContext):
+        """config.model_tracking: register every kept frame against the TSDF fused from the kept frames before
+        it (FusionContext.track, point-to-SDF), in order.  Frame 0 is integrated at its pose; frame k starts from the chain's step
+        applied to the tracked pose of frame k - 1, M0_k = (M_k M_k-1^-1)(chain) M_k-1(tracked), takes the registration's pose
+        unless it failed (status 2) or its fitness is below track_min_fitness (then it keeps M0_k and counts as lost), and is
+        integrated there.  The tracking grid is a TSDF-only grid of its own over the frames' bounds at the chain's poses, detached
+        again; the fusion that follows starts afresh.  Returns (poses, stats)."""
+        cfg = self.config
+        index, chain = self.frame_index, self.camera_poses
+        scales = [self.scales[fi] for fi in index]
+        mn, mx = ctx.frames_bounds(index, chain, scales, subsample=cfg.subsample_factor)
+        if not np.all(np.isfinite(mn)):
+            raise ValueError("model_tracking: the frames at the chain's poses hold no valid point")
+        mn, mx = np.asarray(mn, np.float64) - cfg.track_margin, np.asarray(mx, np.float64) + cfg.track_margin
+        voxel = float(cfg.track_voxel_size or cfg.voxel_size)
+        while True:                                          # one block that fits: the tracker reads a whole lattice
+            lattice = plan_lattice(mn, mx, voxel, cfg.grid_dim, channels=abi.CH_TSDF, trunc_voxels=cfg.sdf_trunc_voxels)
+            if lattice.nvox <= MAX_BLOCK_VOXELS:
+                layout = choose_layout(ctx, lattice, index, chain, scales, cfg.subsample_factor, log=lambda *a: None)
+                if layout.device_bytes() <= device_free_bytes(cfg.device) - BLOCK_MEMORY_MARGIN:
+                    break
+            voxel *= 2.0
+        print(f"\n--- Step 1c: Track frames against the fused model (point-to-SDF, grid {layout.dims} @ {voxel * 1e3:g} mm) ---")
+        if cfg.track_levels is None:
+            levels = self._icp_levels()
+        else:
+            common = dict(damping=cfg.icp_damping, eig_rel=cfg.icp_eig_rel, eps=cfg.icp_eps)
+            levels = [dict(iters=int(lv[0]), stride=int(lv[1]), max_dist=float(lv[2]), **common) for lv in cfg.track_levels]
+        mat = lambda p: np.block([[np.asarray(p[0], np.float64).reshape(3, 3), np.asarray(p[1], np.float64).reshape(3, 1)], [np.zeros((1, 3)), np.ones((1, 1))]])
+        M_chain = [mat(p) for p in chain]
+        out, fit, rmse, lost, mm, deg = [M_chain[0]], [], [], 0, 0.0, 0.0
+        ctx.attach_grid(layout)
+        try:
+            ctx.integrate(index[0], chain[0], scales[0])
+            for k in range(1, len(index)):
+                M0 = (M_chain[k] @ np.linalg.inv(M_chain[k - 1])) @ out[-1]
+                res = ctx.track(index[k], (M0[:3, :3], M0[:3, 3]), levels, min_weight=cfg.track_min_weight, scale=scales[k])
+                M = M0
+                if res["status"] != 2 and res["fitness"] >= cfg.track_min_fitness:
+                    M = np.array(res["T"])
+                    fit.append(res["fitness"])
+                    rmse.append(res["rmse"])
+                    D = M @ np.linalg.inv(M0)
+                    mm = max(mm, 1e3 * float(np.linalg.norm(M0[:3, :3].T @ M0[:3, 3] - M[:3, :3].T @ M[:3, 3])))
+                    deg = max(deg, float(np.degrees(np.arccos(np.clip(0.5 * (np.trace(D[:3, :3]) - 1.0), -1.0, 1.0)))))
+                else:
+                    lost += 1
+                out.append(M)
+                ctx.integrate(index[k], (M[:3, :3], M[:3, 3]), scales[k])
+        finally:
+            ctx.detach_grid()
+        stats = dict(frames=len(index), tracked=len(index) - 1 - lost, lost=lost, mean_fitness=round(float(np.mean(fit)), 4) if fit else 0.0,
+                     mean_rmse_mm=round(1e3 * float(np.mean(rmse)), 4) if rmse else 0.0, max_correction_mm=round(mm, 4),
+                     max_correction_deg=round(deg, 5), voxel_size=voxel)
+        print(f"  Model tracking: {stats['tracked']} of {len(index) - 1} frames tracked, {lost} lost; mean fitness {stats['mean_fitness']:.3f}, "
+              f"mean rmse {stats['mean_rmse_mm']:.2f} mm, largest correction {mm:.2f} mm / {deg:.3f} deg")
+        shape = np.shape(chain[0][1])
+        return [(M[:3, :3].copy(), M[:3, 3].reshape(shape).copy()) for M in out], stats
+
     def _icp_levels(self, sim3: bool = False):
         """The levels handed to ctx.icp_batch.  Coarse-to-fine: each level is (iterations, pixel stride, correspondence gate); every
         level starts from the previous level's pose.  A wide first gate takes frame steps of 0.5 m / 30 degrees that the 5 cm gate
@@ -405,6 +464,9 @@ class DepthToReconstructionPipeline:
         loop = bool(getattr(cfg, "loop_closure", False)) and poses is None      # with poses given nothing is registered: the option is ignored
         if loop and estimate_scale:
             raise ValueError("loop_closure does not go with estimate_scale: the pose graph's edges carry no scale")
+        track = bool(getattr(cfg, "model_tracking", False)) and poses is None   # ... and so is this one
+        if track and estimate_scale:
+            raise ValueError("model_tracking does not go with estimate_scale: tracking against the model estimates no scale")
         if len(self.images) < 2:
             print("Need at least 2 images")
             return None, None, None
@@ -462,6 +524,10 @@ class DepthToReconstructionPipeline:
             if loop:
                 self.camera_poses, loop_stats = self._close_loops(ctx)
                 marks.append(("loop_closure", clock()))
+            track_stats = None
+            if track:
+                self.camera_poses, track_stats = self._track_model(ctx)
+                marks.append(("track", clock()))
             given = grid is not None
             if given:
                 blocks = [Block(grid, (0, 0, 0), tuple(grid.dims))]          # the caller's grid: one block, its layout taken as given
@@ -479,6 +545,8 @@ class DepthToReconstructionPipeline:
             xyz, rgb = self._fuse_blocks(ctx, grid, blocks, marks, layout_given=given)
             if loop_stats is not None:
                 self.stats["loop_closure"] = loop_stats
+            if track_stats is not None:
+                self.stats["model_tracking"] = track_stats
         finally:
             ctx.close()
         return xyz.astype(np.float64), rgb, self.camera_poses
@@ -649,6 +717,8 @@ class DepthToReconstructionPipeline:
         from . import distributed as dd
         if getattr(self.config, "loop_closure", False) and poses is None:
             raise ValueError("loop_closure needs a single GPU: every kept frame must be resident where the revisits are registered")
+        if getattr(self.config, "model_tracking", False) and poses is None:
+            raise ValueError("model_tracking needs a single GPU: every kept frame is registered against one model, in order")
         world, rank = dist.get_world_size(), dist.get_rank()
         self.mesh = None
         if len(self.images) < 2:
