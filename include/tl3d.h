@@ -421,9 +421,17 @@ int tl3d_track_evaluate(tl3d_ctx *ctx, int slot, double scale, const double R[9]
 int tl3d_track_frame(tl3d_ctx *ctx, int slot, double scale, const double R_init[9], const double t_init[3], int min_weight,
                      const tl3d_icp_params *levels, int n_levels, tl3d_icp_result *out);
 
-/* f1: statistical outlier removal on a point list (Open3D remove_statistical_outlier, D2R:412-415) */
+/* f1: statistical outlier removal on a point list (Open3D remove_statistical_outlier, D2R:412-415): keep_out[i] = 1 when
+ * 0 < mean_i < mu + std_ratio * sigma, with mean_i as tl3d_knn_mean_distance gives it and mu / sigma (Bessel-corrected) taken over
+ * the points with mean_i > 0; *out_kept = the number of ones.  Host or device pointers for xyz and keep_out. */
 int tl3d_statistical_outlier(tl3d_ctx *ctx, const float *xyz_hd, int64_t n, int nb_neighbors, double std_ratio,
                              double cell_size, uint8_t *keep_out_hd, int64_t *out_kept);
+
+/* per point: mean fp64 distance to its nb_neighbors nearest neighbours (itself included, k clamped to n); the quantity
+ * tl3d_statistical_outlier thresholds, from the same stage of the filter (no reference code: Open3D keeps it internal).  Host or
+ * device pointers.  The same argument checks: nb_neighbors in [1,64], cell_size > 0, n == 0 is TL3D_OK.  cell_size only sets the
+ * search grid (doubled until it has at most 2^27 cells); the result does not depend on it. */
+int tl3d_knn_mean_distance(tl3d_ctx *ctx, const float *xyz_hd, int64_t n, int nb_neighbors, double cell_size, double *mean_out_hd);
 
 /* measurement */
 int tl3d_set_profile(tl3d_ctx *ctx, int count_records, int time_kernels);

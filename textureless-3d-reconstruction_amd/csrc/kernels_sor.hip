@@ -181,13 +181,14 @@ __global__ __launch_bounds__(256) void sor_stat_kernel(const double *__restrict_
         if (e__ != hipSuccess) { rc = set_err(TL3D_E_HIP, "%s failed: %s", #x, hipGetErrorString(e__)); goto done; } \
     } while (0)
 
-int sor_run(tl3d_ctx *ctx, const float *xyz, long long n, int k, double std_ratio, double cell, uint8_t *keep, long long *kept) {
+// the mean-distance stage alone: mean_d[i] (device, n doubles) = mean fp64 distance of point i to its min(k, n) nearest
+// neighbours, itself included.  tl3d_knn_mean_distance returns it as it is; sor_run thresholds it.
+int sor_mean_distance(tl3d_ctx *ctx, const float *xyz, long long n, int k, double cell, double *mean_d) {
     hipStream_t s = ctx->stream;
     int rc = TL3D_OK;
     unsigned *cell_count = nullptr, *cell_start = nullptr, *cell_fill = nullptr, *chunk_sums = nullptr;
     unsigned long long *chunk_off = nullptr;
     float *sorted = nullptr;
-    double *mean_d = nullptr, *slab = nullptr;
     if (k > n) k = (int)n;
     // bounds
     double mn[3], mx[3];
@@ -209,17 +210,12 @@ int sor_run(tl3d_ctx *ctx, const float *xyz, long long n, int k, double std_rati
         const long long ncell = (long long)cg.nx * cg.ny * cg.nz;
         const int nchunks = (int)((ncell + 1023) / 1024);
         const unsigned nb = (unsigned)((n + 255) / 256);
-        const int nred = 1024;
-        std::vector<double> h(2 * nred);
-        double m = 0, sum = 0, mu = 0, sq = 0, sigma = 0, thr = 0, cnt = 0;
         SOR_HIP(hipMalloc(&cell_count, ncell * sizeof(unsigned)));
         SOR_HIP(hipMalloc(&cell_start, ncell * sizeof(unsigned)));
         SOR_HIP(hipMalloc(&cell_fill, ncell * sizeof(unsigned)));
         SOR_HIP(hipMalloc(&chunk_sums, (size_t)nchunks * sizeof(unsigned)));
         SOR_HIP(hipMalloc(&chunk_off, ((size_t)nchunks + 1) * sizeof(unsigned long long)));
         SOR_HIP(hipMalloc(&sorted, (size_t)n * 3 * sizeof(float)));
-        SOR_HIP(hipMalloc(&mean_d, (size_t)n * sizeof(double)));
-        SOR_HIP(hipMalloc(&slab, 2 * nred * sizeof(double)));
         SOR_HIP(hipMemsetAsync(cell_count, 0, ncell * sizeof(unsigned), s));
         SOR_HIP(hipMemsetAsync(cell_fill, 0, ncell * sizeof(unsigned), s));
         hipLaunchKernelGGL(sor_count_kernel, dim3(nb), dim3(256), 0, s, cg, xyz, n, cell_count);
@@ -233,6 +229,30 @@ int sor_run(tl3d_ctx *ctx, const float *xyz, long long n, int k, double std_rati
         else
             hipLaunchKernelGGL(sor_knn_kernel<64>, dim3(nb), dim3(256), 0, s, cg, xyz, n, k, cell_start, cell_count, sorted, mean_d);
         SOR_HIP(hipGetLastError());
+    }
+done:
+    (void)hipStreamSynchronize(s);
+    if (cell_count) (void)hipFree(cell_count);
+    if (cell_start) (void)hipFree(cell_start);
+    if (cell_fill) (void)hipFree(cell_fill);
+    if (chunk_sums) (void)hipFree(chunk_sums);
+    if (chunk_off) (void)hipFree(chunk_off);
+    if (sorted) (void)hipFree(sorted);
+    return rc;
+}
+
+int sor_run(tl3d_ctx *ctx, const float *xyz, long long n, int k, double std_ratio, double cell, uint8_t *keep, long long *kept) {
+    hipStream_t s = ctx->stream;
+    int rc = TL3D_OK;
+    double *mean_d = nullptr, *slab = nullptr;
+    {
+        const int nred = 1024;
+        std::vector<double> h(2 * nred);
+        double m = 0, sum = 0, mu = 0, sq = 0, sigma = 0, thr = 0, cnt = 0;
+        SOR_HIP(hipMalloc(&mean_d, (size_t)n * sizeof(double)));
+        SOR_HIP(hipMalloc(&slab, 2 * nred * sizeof(double)));
+        rc = sor_mean_distance(ctx, xyz, n, k, cell, mean_d);
+        if (rc) goto done;
         // mu, sigma over the positive means (fixed-order sums of the block partials)
         hipLaunchKernelGGL(sor_stat_kernel, dim3(nred), dim3(256), 0, s, mean_d, n, 0, 0.0, 0.0, slab, keep);
         SOR_HIP(hipMemcpyAsync(h.data(), slab, 2 * nred * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -257,12 +277,6 @@ int sor_run(tl3d_ctx *ctx, const float *xyz, long long n, int k, double std_rati
     }
 done:
     (void)hipStreamSynchronize(s);
-    if (cell_count) (void)hipFree(cell_count);
-    if (cell_start) (void)hipFree(cell_start);
-    if (cell_fill) (void)hipFree(cell_fill);
-    if (chunk_sums) (void)hipFree(chunk_sums);
-    if (chunk_off) (void)hipFree(chunk_off);
-    if (sorted) (void)hipFree(sorted);
     if (mean_d) (void)hipFree(mean_d);
     if (slab) (void)hipFree(slab);
     return rc;

@@ -2742,6 +2742,37 @@ int tl3d_statistical_outlier(tl3d_ctx *ctx, const float *xyz, int64_t n, int nb_
     return TL3D_OK;
 }
 
+int tl3d_knn_mean_distance(tl3d_ctx *ctx, const float *xyz, int64_t n, int nb_neighbors, double cell_size, double *mean_out) {
+    REQUIRE(ctx && mean_out, TL3D_E_INVALID, "null argument");
+    REQUIRE(n >= 0 && (n == 0 || xyz), TL3D_E_INVALID, "bad point list");
+    REQUIRE(nb_neighbors >= 1 && nb_neighbors <= 64, TL3D_E_INVALID, "nb_neighbors must be in [1,64]");
+    REQUIRE(cell_size > 0, TL3D_E_INVALID, "cell_size must be positive");
+    if (n == 0) return TL3D_OK;
+    TL3D_HIP(hipSetDevice(ctx->device));
+    const bool din = is_device_ptr(xyz), dout = is_device_ptr(mean_out);
+    float *tx = nullptr;
+    double *tm = nullptr;
+    const float *dx = xyz;
+    double *dm = mean_out;
+    if (!din) {
+        if (hipMalloc(&tx, (size_t)n * 12) != hipSuccess) return set_err(TL3D_E_NOMEM, "staging alloc failed");
+        if (hipMemcpyAsync(tx, xyz, (size_t)n * 12, hipMemcpyDefault, ctx->stream) != hipSuccess) { (void)hipFree(tx); return set_err(TL3D_E_HIP, "upload failed"); }
+        dx = tx;
+    }
+    if (!dout) {
+        if (hipMalloc(&tm, (size_t)n * sizeof(double)) != hipSuccess) { if (tx) (void)hipFree(tx); return set_err(TL3D_E_NOMEM, "staging alloc failed"); }
+        dm = tm;
+    }
+    int rc = sor_mean_distance(ctx, dx, n, nb_neighbors, cell_size, dm);
+    if (rc == TL3D_OK && !dout) {
+        if (hipMemcpyAsync(mean_out, dm, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = set_err(TL3D_E_HIP, "download failed");
+    }
+    (void)hipStreamSynchronize(ctx->stream);
+    if (tx) (void)hipFree(tx);
+    if (tm) (void)hipFree(tm);
+    return rc;
+}
+
 // ------------------------------------------------------------------------------------------- measurement
 int tl3d_set_profile(tl3d_ctx *ctx, int count_records, int time_kernels) {
     REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");

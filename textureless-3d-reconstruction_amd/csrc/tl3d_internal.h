@@ -527,7 +527,8 @@ int launch_iota(hipStream_t s, unsigned *t, unsigned n);
 int probe_hw_queues(int n_streams, double spin_ms, double *elapsed_ms);
 int launch_add_i32(hipStream_t s, int *dst, const int *src, size_t n);
 int launch_add_u64(hipStream_t s, unsigned long long *dst, const unsigned long long *src, size_t n);
-// outlier filter
+// outlier filter: the k-NN mean-distance stage alone (mean_dev: n doubles), and the whole filter, which thresholds it
+int sor_mean_distance(tl3d_ctx *ctx, const float *xyz_dev, long long n, int k, double cell, double *mean_dev);
 int sor_run(tl3d_ctx *ctx, const float *xyz_dev, long long n, int k, double std_ratio, double cell, uint8_t *keep_dev, long long *kept);
 
 constexpr int EXTRACT_CHUNK = 2048;   // records per block in the extraction kernels

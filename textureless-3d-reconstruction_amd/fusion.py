@@ -706,6 +706,15 @@ class FusionContext:
                                                      cell, abi.ptr(keep), C.byref(kept)))
         return keep.astype(bool)
 
+    def knn_mean_distance(self, xyz, nb_neighbors=20, cell_size=None):
+        """float64 [n]: per point the mean distance to its nb_neighbors nearest neighbours, itself included (k clamped to n) --
+        what statistical_outlier thresholds.  cell_size sets the search grid only; the result does not depend on it."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32)
+        mean = np.zeros(len(xyz), np.float64)
+        cell = float(cell_size if cell_size is not None else (self.grid.voxel_size * 2 if self.grid else 0.01))
+        abi.check(self._lib.tl3d_knn_mean_distance(self._h, abi.ptr(xyz), len(xyz), int(nb_neighbors), cell, abi.ptr(mean)))
+        return mean
+
     # ---- measurement -----------------------------------------------------------------------
     def set_profile(self, count_records=False, time_kernels=False):
         abi.check(self._lib.tl3d_set_profile(self._h, int(count_records), int(time_kernels)))
