@@ -36,3 +36,25 @@ def ulp_diff(a, b):
     a = np.where(a < 0, -(a & 0x7fffffff), a)
     b = np.where(b < 0, -(b & 0x7fffffff), b)
     return np.abs(a - b)
+
+
+# The smallest scene the staging tests need: a 64 x 48 camera orbiting two spheres inside a 32^3 grid at 1 cm (64 bricks, 16
+# extraction chunks of 2048 records).  Sparse: pools of 64 bricks per channel behind brick tables.
+TINY = dict(width=64, height=48, fx=60.0, fy=60.0, cx=31.5, cy=23.5)
+
+
+def tiny_fused(sparse, n=3, fuse=True):
+    """An open FusionContext (close it, or use `with`) with n frames of the tiny scene uploaded and, unless fuse=False, fused
+    into both channels; its .tiny_poses holds the poses."""
+    scene = synth.Scene(spheres=[((0.0, 0.0, 0.0), 0.10), ((0.07, 0.03, 0.0), 0.06)])
+    poses = synth.orbit_poses(n, 0.5, 15.0)
+    pool = 64 if sparse else 0
+    spec = tl3d.GridSpec((32, 32, 32), (-0.16, -0.16, -0.16), 0.01, 0.04, pool_tsdf=pool, pool_centroid=pool)
+    ctx = tl3d.FusionContext(TINY["width"], TINY["height"], TINY["fx"], TINY["fy"], TINY["cx"], TINY["cy"], n_slots=n, grid=spec)
+    for i, p in enumerate(poses):
+        d, c = synth.render(scene, p, **TINY)
+        ctx.upload(i, d, c)
+    if fuse:
+        ctx.fuse_frames(list(range(n)), poses, centroid_subsample=1)
+    ctx.tiny_poses = poses
+    return ctx

@@ -109,6 +109,9 @@ def test_offset_blocks_hold_the_single_lattice_records(single, sparse):
 
 
 def test_detach_then_attach_equals_a_fresh_context(single):
+    """Three attach -> fuse -> extract -> mesh -> detach cycles on one context (dense, sparse, dense): after each detach the grid,
+    its tables and the grid-sized extraction and mesh scratch have gone back to the device, and the last cycle's grid is a fresh
+    context's."""
     import torch
     poses, frames = single["poses"], single["frames"]
     b = GridSpec((136, 128, 136), LATTICE.origin, VOXEL, LATTICE.sdf_trunc, voxel_offset=(120, 0, 64))
@@ -121,17 +124,28 @@ def test_detach_then_attach_equals_a_fresh_context(single):
         ctx.sync()
         torch.cuda.synchronize()
         free0 = torch.cuda.mem_get_info(0)[0]
+
+        def extract_and_detach():
+            ctx.extract(tl3d.EXTRACT_CENTROID)              # the extraction and the mesh scratch exist before the detach
+            ctx.extract_mesh()
+            ctx.detach_grid()
+            assert torch.cuda.mem_get_info(0)[0] > free0 - (64 << 20)      # the grid and its scratch went back
+
         ctx.attach_grid(LATTICE)
         _fuse(ctx, poses)
         ctx.sync()
         assert torch.cuda.mem_get_info(0)[0] < free0 - LATTICE.device_bytes() // 2
-        ctx.detach_grid()
-        assert torch.cuda.mem_get_info(0)[0] > free0 - (64 << 20)      # the grid and its scratch went back
+        extract_and_detach()
         for call in (lambda: ctx.integrate(0, poses[0]), lambda: ctx.extract(tl3d.EXTRACT_CENTROID), lambda: ctx.extract_mesh(),
                      lambda: ctx.grid_ptr(tl3d.CH_TSDF), lambda: ctx.detach_grid(), lambda: ctx.set_block_core()):
             with pytest.raises(abi.Tl3dError) as e:
                 call()
             assert e.value.code == abi.E_STATE
+        t, c = ctx.count_bricks(b, list(range(len(poses))), poses, centroid_subsample=1)
+        ctx.attach_grid(GridSpec(b.dims, b.origin, VOXEL, b.sdf_trunc, pool_tsdf=t + 64, pool_centroid=c + 64, voxel_offset=b.voxel_offset))
+        _fuse(ctx, poses)
+        assert ctx.stats()["pool_refused"] == 0 and np.array_equal(ctx.download_grid(tl3d.CH_TSDF), want[0])
+        extract_and_detach()
         ctx.attach_grid(b)
         with pytest.raises(abi.Tl3dError) as e:
             ctx.attach_grid(b)
@@ -139,6 +153,7 @@ def test_detach_then_attach_equals_a_fresh_context(single):
         _fuse(ctx, poses)
         assert np.array_equal(ctx.download_grid(tl3d.CH_TSDF), want[0])
         assert np.array_equal(ctx.download_grid(tl3d.CH_CENTROID), want[1])
+        extract_and_detach()
 
 
 @pytest.mark.parametrize("sparse", [False, True])

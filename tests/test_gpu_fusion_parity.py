@@ -4,7 +4,8 @@ import numpy as np
 import pytest
 
 import tl3d
-from helpers import SMALL, make_pair, small_scene_frames, ulp_diff
+from helpers import SMALL, make_pair, small_scene_frames, tiny_fused, ulp_diff
+from tl3d import _cabi as abi
 
 pytestmark = pytest.mark.gpu
 
@@ -1028,3 +1029,84 @@ def test_a_full_brick_pool_refuses_bricks_and_says_so():
         assert st["pool_slots_tsdf"] == 16 and st["pool_slots_centroid"] == 8 and st["pool_refused"] > 100
         xyz, _ = sp.extract(tl3d.EXTRACT_CENTROID)
         assert 0 < len(xyz) <= 8 * 512
+
+
+# ---- every entry point that stages host arrays: host and device arguments give the same bits ------------------------------------
+def _dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).to(torch.device("cuda", 0))
+
+
+def _raw_extract(ctx, mode, xyz, rgb, cap):
+    import ctypes as C
+    n = C.c_int64(-1)
+    abi.check(ctx._lib.tl3d_extract(ctx._h, mode, 1, 1 if mode == tl3d.EXTRACT_TSDF else 0, 0.9, abi.ptr(xyz), abi.ptr(rgb), cap, C.byref(n)))
+    return n.value
+
+
+@pytest.mark.parametrize("sparse", [False, True])
+@pytest.mark.parametrize("mode", [tl3d.EXTRACT_CENTROID, tl3d.EXTRACT_TSDF])
+def test_extract_into_device_tensors_equals_extract_into_host_arrays(mode, sparse):
+    import torch
+    with tiny_fused(sparse) as ctx:
+        n = _raw_extract(ctx, mode, None, None, 0)
+        assert n > 200
+        xyz, rgb = np.full((n, 3), -1, np.float32), np.full((n, 3), 7, np.uint8)
+        dxyz = torch.full((n, 3), -1.0, dtype=torch.float32, device="cuda:0")
+        drgb = torch.full((n, 3), 7, dtype=torch.uint8, device="cuda:0")
+        assert _raw_extract(ctx, mode, xyz, rgb, n) == n and _raw_extract(ctx, mode, dxyz, drgb, n) == n
+        # (no synchronisation here: device outputs are complete when the call returns, like host outputs)
+        assert np.array_equal(dxyz.cpu().numpy().view(np.int32), xyz.view(np.int32)) and np.array_equal(drgb.cpu().numpy(), rgb)
+        assert np.isfinite(xyz).all() and np.abs(xyz).max() < 0.16
+
+
+@pytest.mark.parametrize("sparse", [False, True])
+def test_point_list_calls_take_host_and_device_points_alike(sparse):
+    import ctypes as C
+    with tiny_fused(sparse) as src:
+        xyz, rgb = src.extract(tl3d.EXTRACT_CENTROID)
+    assert len(xyz) > 200
+    got = []
+    for on_dev in (False, True):
+        with tiny_fused(sparse, fuse=False) as ctx:
+            p, c = (_dev(xyz), _dev(rgb)) if on_dev else (xyz, rgb)
+            lo, hi = np.zeros(3), np.zeros(3)
+            abi.check(ctx._lib.tl3d_points_bounds(ctx._h, abi.ptr(p), len(xyz), abi.ptr(lo), abi.ptr(hi)))
+            abi.check(ctx._lib.tl3d_accumulate_points(ctx._h, abi.ptr(p), abi.ptr(c), len(xyz)))
+            got.append((lo, hi, ctx.download_grid(tl3d.CH_CENTROID)))      # (the download is ordered behind the device-path launch)
+            assert ctx.stats()["pool_refused"] == 0
+    assert np.array_equal(got[0][0], xyz.min(axis=0).astype(np.float64)) and np.array_equal(got[0][1], xyz.max(axis=0).astype(np.float64))
+    assert np.array_equal(got[0][0], got[1][0]) and np.array_equal(got[0][1], got[1][1])
+    assert got[0][2].any() and np.array_equal(got[0][2], got[1][2])
+
+
+@pytest.mark.parametrize("channel", [tl3d.CH_TSDF, tl3d.CH_CENTROID])
+def test_sparse_grid_download_and_upload_through_device_tensors(channel):
+    import torch
+    with tiny_fused(True) as ctx:
+        image = ctx.download_grid(channel)
+        assert image.any()
+        nb = image.nbytes
+        dev = torch.zeros(nb, dtype=torch.uint8, device="cuda:0")
+        abi.check(ctx._lib.tl3d_grid_download(ctx._h, channel, abi.ptr(dev), nb))
+        assert np.array_equal(dev.cpu().numpy(), image.view(np.uint8).ravel())
+        # upload: from the device tensor and from the host array, each into a grid that holds something else
+        other = np.ascontiguousarray(image[::-1])
+        for src in (dev, image):
+            ctx.upload_grid(channel, other)
+            assert np.array_equal(ctx.download_grid(channel), other)
+            abi.check(ctx._lib.tl3d_grid_upload(ctx._h, channel, abi.ptr(src), nb))
+            assert np.array_equal(ctx.download_grid(channel), image)
+
+
+@pytest.mark.parametrize("sparse", [False, True])
+@pytest.mark.parametrize("channel", [tl3d.CH_TSDF, tl3d.CH_CENTROID])
+def test_grid_add_from_a_device_tensor_equals_grid_add_from_the_host(channel, sparse):
+    with tiny_fused(sparse) as ctx:
+        image = ctx.download_grid(channel)
+        want = image + image                                               # integer sums: the merge is an addition
+        for src in (image, _dev(image)):
+            ctx.upload_grid(channel, image)
+            abi.check(ctx._lib.tl3d_grid_add(ctx._h, channel, abi.ptr(src), image.nbytes))
+            assert np.array_equal(ctx.download_grid(channel), want)
+        assert image.any()

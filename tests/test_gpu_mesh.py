@@ -10,7 +10,7 @@ import pytest
 
 import mesh_reference as mr
 import tl3d
-from helpers import SMALL, make_pair, small_scene_frames
+from helpers import SMALL, make_pair, small_scene_frames, tiny_fused
 from tl3d import _cabi as abi
 from tl3d import synth
 from tl3d.config import ReconstructionConfig
@@ -164,6 +164,29 @@ def test_repeatability_and_short_buffers():
         with pytest.raises(abi.Tl3dError) as e:
             cen_only.extract_mesh()
         assert e.value.code == abi.E_STATE
+
+
+@pytest.mark.parametrize("sparse", [False, True])
+def test_keyed_mesh_into_device_tensors_equals_keyed_mesh_into_host_arrays(sparse):
+    """tl3d_extract_mesh_keyed with all four arrays on the host (staged on the device, copied back) and all four on the device"""
+    import torch
+    with tiny_fused(sparse) as ctx:
+        lib = ctx._lib
+        nv, nt = C.c_int64(0), C.c_int64(0)
+        abi.check(lib.tl3d_extract_mesh_keyed(ctx._h, 1, None, None, 0, None, 0, None, C.byref(nv), C.byref(nt)))
+        nv, nt = nv.value, nt.value
+        assert nv > 100 and nt > 100
+        host = (np.full((nv, 3), -1, np.float32), np.full((nv, 3), 7, np.uint8), np.full((nt, 3), 7, np.uint32), np.full(nv, -1, np.int64))
+        dev = tuple(torch.from_numpy(h.view(np.int32) if h.dtype == np.uint32 else h).to("cuda:0") for h in host)
+        for xyz, rgb, tri, key in (host, dev):
+            onv, ont = C.c_int64(0), C.c_int64(0)
+            abi.check(lib.tl3d_extract_mesh_keyed(ctx._h, 1, abi.ptr(xyz), abi.ptr(rgb), nv, abi.ptr(tri), nt, abi.ptr(key), C.byref(onv), C.byref(ont)))
+            assert (onv.value, ont.value) == (nv, nt)
+        # (no synchronisation: device outputs are complete when the call returns, like host outputs)
+        for h, d in zip(host, dev):
+            assert np.array_equal(d.cpu().numpy().view(np.uint8), h.view(np.uint8))
+        assert host[2].max() == nv - 1 and len(np.unique(host[3])) == nv and host[3].min() >= 0
+        _assert_same(host[:3], ctx.extract_mesh(1))
 
 
 # ---- pipeline and command line --------------------------------------------------------------------------------------

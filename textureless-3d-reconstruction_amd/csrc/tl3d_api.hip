@@ -103,6 +103,90 @@ static bool is_device_ptr(const void *p) {
     return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
 }
 
+// Per-call device staging of caller arrays that may live in host or in device memory.  A device pointer is used as it is; a host
+// input gets a temporary and an upload on the context's stream, a host output a temporary that finish() copies back; scratch() is
+// a temporary of the call's own.  The destructor waits for the stream before it frees, on every way out of the call, so nothing
+// in flight loses its memory; a call that staged nothing never waits here.
+namespace {
+class Staging {
+  public:
+    explicit Staging(tl3d_ctx *ctx) : ctx_(ctx) {}
+    Staging(const Staging &) = delete;
+    Staging &operator=(const Staging &) = delete;
+    ~Staging() {
+        if (n_) (void)hipStreamSynchronize(ctx_->stream);
+        for (int i = 0; i < n_; ++i) (void)hipFree(tmp_[i].dev);
+    }
+    template <class T> int in(const T *p, size_t bytes, const T **dev) {
+        *dev = p;
+        if (is_device_ptr(p)) return TL3D_OK;
+        void *d = nullptr;
+        const int rc = take(bytes, nullptr, &d);
+        if (rc) return rc;
+        *dev = (const T *)d;
+        if (hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, ctx_->stream) != hipSuccess) return set_err(TL3D_E_HIP, "staging upload (%zu B) failed", bytes);
+        return TL3D_OK;
+    }
+    template <class T> int out(T *p, size_t bytes, T **dev) {
+        *dev = p;
+        if (is_device_ptr(p) || bytes == 0) return TL3D_OK;
+        return take(bytes, p, (void **)dev);
+    }
+    template <class T> int scratch(size_t bytes, T **dev) { return take(bytes, nullptr, (void **)dev); }
+    // rc: what the launchers returned; it wins.  Otherwise the host outputs are copied back, and the stream is waited for when
+    // anything was staged (or `wait`: the call promises finished device outputs too)
+    int finish(int rc, bool wait = false) {
+        if (rc) return rc;
+        hipError_t e = hipSuccess;
+        for (int i = 0; i < n_ && e == hipSuccess; ++i)
+            if (tmp_[i].host_out) e = hipMemcpyAsync(tmp_[i].host_out, tmp_[i].dev, tmp_[i].bytes, hipMemcpyDeviceToHost, ctx_->stream);
+        if (e == hipSuccess && (n_ || wait)) e = hipStreamSynchronize(ctx_->stream);
+        if (e != hipSuccess) return set_err(TL3D_E_HIP, "staging copy / sync failed: %s", hipGetErrorString(e));
+        return TL3D_OK;
+    }
+
+  private:
+    int take(size_t bytes, void *host_out, void **dev) {
+        *dev = nullptr;
+        if (n_ == MAX) return set_err(TL3D_E_STATE, "more than %d staged arrays in one call", MAX);
+        if (hipMalloc(dev, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            *dev = nullptr;
+            return set_err(TL3D_E_NOMEM, "staging alloc (%zu B) failed", bytes);
+        }
+        tmp_[n_++] = {*dev, host_out, bytes};
+        return TL3D_OK;
+    }
+    static constexpr int MAX = 4;
+    struct Tmp { void *dev, *host_out; size_t bytes; };
+    tl3d_ctx *ctx_;
+    Tmp tmp_[MAX];
+    int n_ = 0;
+};
+}  // namespace
+
+// grow-on-demand device scratch of `need` elements: on failure the buffer is gone and its capacity 0
+template <class T> static int grow(T **p, size_t *cap, size_t need, const char *what) {
+    if (need <= *cap) return TL3D_OK;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    if (hipMalloc(p, need * sizeof(T)) != hipSuccess) {
+        (void)hipGetLastError();
+        return set_err(TL3D_E_NOMEM, "%s alloc (%zu B) failed", what, need * sizeof(T));
+    }
+    *cap = need;
+    return TL3D_OK;
+}
+// two buffers that share one capacity (*cap counts elements of each)
+template <class A, class B> static int grow_pair(A **a, B **b, size_t *cap, size_t need, const char *what) {
+    size_t cap_b = *cap;
+    int rc = grow(a, cap, need, what);
+    if (!rc) rc = grow(b, &cap_b, need, what);
+    if (rc) *cap = 0;
+    return rc;
+}
+
 static PoseF make_pose_f(const double R[9], const double t[3]) {
     PoseF p;
     for (int i = 0; i < 9; ++i) p.r[i] = (float)R[i];
@@ -133,19 +217,6 @@ static Frustum make_frustum(const Cam &c) {
     n = sqrt(1.0 + aT * aT); f.ty = (float)(1.0 / n);  f.tz = (float)(-aT / n);
     n = sqrt(1.0 + aB * aB); f.by = (float)(-1.0 / n); f.bz = (float)(aB / n);
     return f;
-}
-
-static int ensure_scratch_blocks(tl3d_ctx *ctx, size_t nblocks) {
-    if (nblocks <= ctx->scratch_blocks) return TL3D_OK;
-    if (ctx->block_counts) (void)hipFree(ctx->block_counts);
-    if (ctx->block_offsets) (void)hipFree(ctx->block_offsets);
-    ctx->block_counts = nullptr;
-    ctx->block_offsets = nullptr;
-    ctx->scratch_blocks = 0;
-    if (hipMalloc(&ctx->block_counts, nblocks * sizeof(unsigned)) != hipSuccess) return set_err(TL3D_E_NOMEM, "scratch alloc failed");
-    if (hipMalloc(&ctx->block_offsets, nblocks * sizeof(unsigned long long)) != hipSuccess) return set_err(TL3D_E_NOMEM, "scratch alloc failed");
-    ctx->scratch_blocks = nblocks;
-    return TL3D_OK;
 }
 
 static int check_slot(tl3d_ctx *ctx, int slot, bool need_loaded) {
@@ -286,8 +357,43 @@ static void grid_geometry(Grid &g, const tl3d_config *cfg) {
     g.inv_trunc = (cfg->channels & TL3D_CH_TSDF) ? 1.0f / g.trunc : 0.0f;
 }
 
-// allocates (or borrows) the grid channels of cfg and the TSDF side stream / scratch; ctx->stream must exist
+// Frees everything of tl3d_grid_state and leaves the context without a grid.  Nothing on the device may still use the grid: the
+// caller has issued the deferred updates and waited for the streams.  Frames, normal maps, ICP state, streams and the camera-sized
+// buffers are not touched.
+static void release_grid(tl3d_ctx *ctx) {
+    tl3d_grid_state &gs = *ctx;
+    if (gs.brick_tabs) (void)hipFree(gs.brick_tabs);
+    if (gs.own_tsdf && gs.tsdf) (void)hipFree(gs.tsdf);
+    if (gs.own_centroid && gs.centroid) (void)hipFree(gs.centroid);
+    if (gs.free_cnt) (void)hipFree(gs.free_cnt);
+    if (gs.tsdf_scratch_slab) (void)hipFree(gs.tsdf_scratch_slab);
+    if (gs.block_counts) (void)hipFree(gs.block_counts);
+    if (gs.block_offsets) (void)hipFree(gs.block_offsets);
+    if (gs.mesh_counts) (void)hipFree(gs.mesh_counts);
+    if (gs.mesh_offsets) (void)hipFree(gs.mesh_offsets);
+    if (gs.mesh_first) (void)hipFree(gs.mesh_first);
+    for (int h = 0; h < TSDF_SCRATCHES; ++h)
+        if (gs.ev_upd[h]) (void)hipEventDestroy(gs.ev_upd[h]);      // (build_grid creates them anew)
+    memset(&gs, 0, sizeof(gs));
+    ctx->grid_epoch++;
+    ctx->cfg.channels = 0;
+    for (int i = 0; i < 3; ++i) ctx->cfg.voxel_offset[i] = 0;
+}
+
+static int build_grid(tl3d_ctx *ctx, const tl3d_config *cfg);
+
+// allocates (or borrows) the grid channels of cfg and the TSDF side streams / scratch; ctx->stream must exist.  On failure
+// whatever was allocated has been released again: the context has no grid, as before the call.
 static int alloc_grid(tl3d_ctx *ctx, const tl3d_config *cfg) {
+    const int rc = build_grid(ctx, cfg);
+    if (rc) {
+        (void)hipStreamSynchronize(ctx->stream);        // clears of the buffers allocated so far may be in flight
+        release_grid(ctx);
+    }
+    return rc;
+}
+
+static int build_grid(tl3d_ctx *ctx, const tl3d_config *cfg) {
     Grid &g = ctx->grid;
     grid_geometry(g, cfg);
     ctx->nvox = (size_t)g.nx * g.ny * g.nz;
@@ -626,23 +732,13 @@ int tl3d_destroy(tl3d_ctx *ctx) {
     pool_release(ctx->pool_bgr);
     pool_release(ctx->pool_nmap);
     pool_release(ctx->pool_sdepth);
-    if (ctx->brick_tabs) (void)hipFree(ctx->brick_tabs);
-    if (ctx->own_tsdf && ctx->tsdf) (void)hipFree(ctx->tsdf);
-    if (ctx->own_centroid && ctx->centroid) (void)hipFree(ctx->centroid);
     for (int q = 0; q < 4; ++q)
         if (ctx->prep_stream[q]) (void)hipStreamSynchronize(ctx->prep_stream[q]);
-    if (ctx->tsdf_scratch_slab) (void)hipFree(ctx->tsdf_scratch_slab);
-    for (int b = 0; b < TSDF_SCRATCHES; ++b) {
+    release_grid(ctx);
+    for (int b = 0; b < TSDF_SCRATCHES; ++b)
         if (ctx->ev_prep[b]) (void)hipEventDestroy(ctx->ev_prep[b]);
-        if (ctx->ev_upd[b]) (void)hipEventDestroy(ctx->ev_upd[b]);
-    }
     for (int q = 0; q < 4; ++q)
         if (ctx->prep_stream[q]) (void)hipStreamDestroy(ctx->prep_stream[q]);
-    if (ctx->block_counts) (void)hipFree(ctx->block_counts);
-    if (ctx->block_offsets) (void)hipFree(ctx->block_offsets);
-    if (ctx->mesh_counts) (void)hipFree(ctx->mesh_counts);
-    if (ctx->mesh_offsets) (void)hipFree(ctx->mesh_offsets);
-    if (ctx->mesh_first) (void)hipFree(ctx->mesh_first);
     if (ctx->ray_depth) (void)hipFree(ctx->ray_depth);
     if (ctx->ray_nrm) (void)hipFree(ctx->ray_nrm);
     if (ctx->ray_bgr) (void)hipFree(ctx->ray_bgr);
@@ -655,7 +751,6 @@ int tl3d_destroy(tl3d_ctx *ctx) {
     if (ctx->d_cen_counters) (void)hipFree(ctx->d_cen_counters);
     if (ctx->rccl_comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(ctx->rccl_comm);
     if (ctx->d_maxw) (void)hipFree(ctx->d_maxw);
-    if (ctx->free_cnt) (void)hipFree(ctx->free_cnt);
     if (ctx->ev_free) (void)hipEventDestroy(ctx->ev_free);
     for (int l = 0; l < TL3D_ICP_LANES; ++l) {
         tl3d_ctx::IcpLane &ln = ctx->icp_lanes[l];
@@ -781,49 +876,7 @@ int tl3d_detach_grid(tl3d_ctx *ctx) {
     for (int q = 0; q < 4; ++q)
         if (ctx->prep_stream[q]) TL3D_HIP(hipStreamSynchronize(ctx->prep_stream[q]));
     TL3D_HIP(hipStreamSynchronize(ctx->stream));
-    // the grid channels, brick tables, free-space counters and every grid-sized scratch; frames, normal maps, ICP state, streams
-    // and the camera-sized buffers stay
-    if (ctx->brick_tabs) (void)hipFree(ctx->brick_tabs);
-    if (ctx->own_tsdf && ctx->tsdf) (void)hipFree(ctx->tsdf);
-    if (ctx->own_centroid && ctx->centroid) (void)hipFree(ctx->centroid);
-    if (ctx->free_cnt) (void)hipFree(ctx->free_cnt);
-    if (ctx->tsdf_scratch_slab) (void)hipFree(ctx->tsdf_scratch_slab);
-    if (ctx->block_counts) (void)hipFree(ctx->block_counts);
-    if (ctx->block_offsets) (void)hipFree(ctx->block_offsets);
-    if (ctx->mesh_counts) (void)hipFree(ctx->mesh_counts);
-    if (ctx->mesh_offsets) (void)hipFree(ctx->mesh_offsets);
-    if (ctx->mesh_first) (void)hipFree(ctx->mesh_first);
-    for (int h = 0; h < TSDF_SCRATCHES; ++h) {
-        if (ctx->ev_upd[h]) (void)hipEventDestroy(ctx->ev_upd[h]);      // (alloc_grid creates them anew)
-        ctx->ev_upd[h] = nullptr;
-        ctx->upd_recorded[h] = false;
-        ctx->tsdf_scratch[h] = nullptr;
-    }
-    ctx->brick_tabs = nullptr;
-    ctx->tsdf = nullptr;
-    ctx->centroid = nullptr;
-    ctx->own_tsdf = ctx->own_centroid = false;
-    ctx->sparse = false;
-    ctx->free_cnt = nullptr;
-    ctx->free_dirty = false;
-    ctx->tsdf_scratch_slab = nullptr;
-    ctx->block_counts = nullptr;
-    ctx->block_offsets = nullptr;
-    ctx->scratch_blocks = 0;
-    ctx->mesh_counts = nullptr;
-    ctx->mesh_offsets = nullptr;
-    ctx->mesh_blocks = 0;
-    ctx->mesh_first = nullptr;
-    ctx->mesh_first_n = 0;
-    ctx->ext_valid = ctx->mesh_valid = false;
-    ctx->grid_epoch++;
-    ctx->has_core = false;
-    ctx->tsdf_w_upper = 0;
-    ctx->tsdf_w_unknown = false;
-    memset(&ctx->grid, 0, sizeof(ctx->grid));
-    ctx->nvox = 0;
-    ctx->cfg.channels = 0;
-    for (int i = 0; i < 3; ++i) ctx->cfg.voxel_offset[i] = 0;
+    release_grid(ctx);
     return TL3D_OK;
 }
 
@@ -1093,28 +1146,25 @@ int tl3d_count_bricks(tl3d_ctx *ctx, const tl3d_config *cfg, int n_frames, const
     memset(&g, 0, sizeof(g));
     grid_geometry(g, cfg);
     const size_t nbr = ((size_t)g.nx * g.ny * g.nz) >> 9;
-    unsigned *tabs = nullptr, *free_cnt = nullptr;
+    Staging st(ctx);                                    // the temporaries below go when the call returns, behind the stream
+    unsigned *tabs, *free_cnt = nullptr;
     void *scratch = nullptr;
-    auto done = [&](int code) {
-        (void)hipStreamSynchronize(ctx->stream);
-        if (tabs) (void)hipFree(tabs);
-        if (free_cnt) (void)hipFree(free_cnt);
-        if (scratch) (void)hipFree(scratch);
-        return code;
-    };
-    if (hipMalloc(&tabs, (2 * nbr + 64) * sizeof(unsigned)) != hipSuccess) return done(set_err(TL3D_E_NOMEM, "brick table alloc failed"));
-    if (hipMemsetAsync(tabs, 0xff, 2 * nbr * sizeof(unsigned), ctx->stream) != hipSuccess || hipMemsetAsync(tabs + 2 * nbr, 0, 64 * sizeof(unsigned), ctx->stream) != hipSuccess)
-        return done(set_err(TL3D_E_HIP, "memset failed"));
+    rc = st.scratch((2 * nbr + 64) * sizeof(unsigned), &tabs);
+    if (rc) return rc;
+    TL3D_HIP(hipMemsetAsync(tabs, 0xff, 2 * nbr * sizeof(unsigned), ctx->stream));
+    TL3D_HIP(hipMemsetAsync(tabs + 2 * nbr, 0, 64 * sizeof(unsigned), ctx->stream));
     g.tsdf_tab = tabs; g.cen_tab = tabs + nbr; g.cursors = tabs + 2 * nbr;
     g.tsdf_cap = g.cen_cap = (unsigned)nbr;
     const float mind = (float)min_depth, maxd = (float)max_depth;
     if (cfg->channels & TL3D_CH_TSDF) {
         const int batch = TL3D_TSDF_MAXBATCH;
         const size_t sb = tsdf_batch_scratch_bytes(ctx->cam, g, batch);
-        if (hipMalloc(&free_cnt, nbr * sizeof(unsigned)) != hipSuccess || hipMalloc(&scratch, sb) != hipSuccess) return done(set_err(TL3D_E_NOMEM, "scratch alloc (%zu B) failed", sb));
+        rc = st.scratch(nbr * sizeof(unsigned), &free_cnt);
+        if (!rc) rc = st.scratch(sb, &scratch);
+        if (rc) return rc;
         size_t zoff = 0, zbytes = 0;
         tsdf_batch_scratch_zero_range(ctx->cam, g, batch, &zoff, &zbytes);
-        if (hipMemsetAsync(free_cnt, 0, nbr * sizeof(unsigned), ctx->stream) != hipSuccess) return done(set_err(TL3D_E_HIP, "memset failed"));
+        TL3D_HIP(hipMemsetAsync(free_cnt, 0, nbr * sizeof(unsigned), ctx->stream));
         const Frustum fr = make_frustum(ctx->cam);
         for (int i0 = 0; i0 < n_frames; i0 += batch) {
             const int m = n_frames - i0 < batch ? n_frames - i0 : batch;
@@ -1126,27 +1176,27 @@ int tl3d_count_bricks(tl3d_ctx *ctx, const tl3d_config *cfg, int n_frames, const
                 depths[j] = ctx->slots[slots[i0 + j]].depth;
                 sc[j] = (float)(scales ? scales[i0 + j] : 1.0);
             }
-            if (hipMemsetAsync((char *)scratch + zoff, 0, zbytes, ctx->stream) != hipSuccess) return done(set_err(TL3D_E_HIP, "memset failed"));    // (no update re-arms the frame masks)
+            TL3D_HIP(hipMemsetAsync((char *)scratch + zoff, 0, zbytes, ctx->stream));    // (no update re-arms the frame masks)
             rc = launch_tsdf_prepare(ctx->stream, ctx->cam, g, m, batch, poses, fr, depths, false, sc, mind, maxd, scratch, free_cnt, true);
-            if (rc) return done(rc);
+            if (rc) return rc;
         }
     }
     if ((cfg->channels & TL3D_CH_CENTROID) && centroid_subsample >= 1) {
         for (int i = 0; i < n_frames; ++i) {
             BpArgs a;
             rc = make_bp_args(ctx, scales ? scales[i] : 1.0, 0, centroid_subsample, min_depth, max_depth, &a);
-            if (rc) return done(rc);
+            if (rc) return rc;
             const PoseD p = make_pose_d(R + (size_t)9 * i, t + (size_t)3 * i, false);
             rc = launch_centroid_mark(ctx->stream, ctx->cam, g, a, p, ctx->slots[slots[i]].depth, ctx->bp_factors, ctx->bp_factors + ctx->cam.W);
-            if (rc) return done(rc);
+            if (rc) return rc;
         }
     }
     unsigned cur[4] = {0, 0, 0, 0};
-    if (hipMemcpyAsync(cur, g.cursors, sizeof(cur), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return done(set_err(TL3D_E_HIP, "copy failed"));
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return done(set_err(TL3D_E_HIP, "sync failed"));
+    TL3D_HIP(hipMemcpyAsync(cur, g.cursors, sizeof(cur), hipMemcpyDeviceToHost, ctx->stream));
+    TL3D_HIP(hipStreamSynchronize(ctx->stream));
     *bricks_tsdf = (int64_t)(cur[0] < nbr ? cur[0] : nbr);
     *bricks_centroid = (int64_t)(cur[2] < nbr ? cur[2] : nbr);
-    return done(TL3D_OK);
+    return TL3D_OK;
 }
 
 // ------------------------------------------------------------------------------------------- centroid accumulation
@@ -1181,28 +1231,14 @@ int tl3d_accumulate_points(tl3d_ctx *ctx, const float *xyz, const uint8_t *rgb, 
     REQUIRE(n >= 0 && (n == 0 || (xyz && rgb)), TL3D_E_INVALID, "bad point list");
     if (n == 0) return TL3D_OK;
     TL3D_HIP(hipSetDevice(ctx->device));
-    const bool direct = is_device_ptr(xyz) && is_device_ptr(rgb);
-    const float *dxyz = xyz;
-    const uint8_t *drgb = rgb;
-    float *tx = nullptr;
-    uint8_t *tc = nullptr;
-    if (!direct) {
-        if (hipMalloc(&tx, (size_t)n * 12) != hipSuccess) return set_err(TL3D_E_NOMEM, "point staging alloc failed");
-        if (hipMalloc(&tc, (size_t)n * 3) != hipSuccess) { (void)hipFree(tx); return set_err(TL3D_E_NOMEM, "point staging alloc failed"); }
-        hipError_t e = hipMemcpyAsync(tx, xyz, (size_t)n * 12, hipMemcpyDefault, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(tc, rgb, (size_t)n * 3, hipMemcpyDefault, ctx->stream);
-        if (e != hipSuccess) { (void)hipFree(tx); (void)hipFree(tc); return set_err(TL3D_E_HIP, "point upload failed: %s", hipGetErrorString(e)); }
-        dxyz = tx;
-        drgb = tc;
-    }
+    Staging st(ctx);
+    const float *dxyz;
+    const uint8_t *drgb;
+    int rc = st.in(xyz, (size_t)n * 12, &dxyz);
+    if (!rc) rc = st.in(rgb, (size_t)n * 3, &drgb);
+    if (rc) return rc;
     ctx->grid_epoch++;
-    int rc = launch_centroid_points(ctx->stream, ctx->grid, dxyz, drgb, n, ctx->centroid, ctx->d_cen_counters);
-    if (!direct) {
-        hipError_t e = hipStreamSynchronize(ctx->stream);
-        (void)hipFree(tx);
-        (void)hipFree(tc);
-        if (rc == TL3D_OK && e != hipSuccess) return set_err(TL3D_E_HIP, "sync failed: %s", hipGetErrorString(e));
-    }
+    rc = st.finish(launch_centroid_points(ctx->stream, ctx->grid, dxyz, drgb, n, ctx->centroid, ctx->d_cen_counters));
     if (rc) return rc;
     ctx->stats.centroid_launches++;
     return TL3D_OK;
@@ -1212,24 +1248,17 @@ int tl3d_points_bounds(tl3d_ctx *ctx, const float *xyz, int64_t n, double out_mi
     REQUIRE(ctx && xyz && out_min && out_max, TL3D_E_INVALID, "null argument");
     REQUIRE(n > 0, TL3D_E_INVALID, "empty point list has no bounds");
     TL3D_HIP(hipSetDevice(ctx->device));
-    const bool direct = is_device_ptr(xyz);
-    const float *d = xyz;
-    float *tx = nullptr;
-    if (!direct) {
-        if (hipMalloc(&tx, (size_t)n * 12) != hipSuccess) return set_err(TL3D_E_NOMEM, "point staging alloc failed");
-        hipError_t e = hipMemcpyAsync(tx, xyz, (size_t)n * 12, hipMemcpyDefault, ctx->stream);
-        if (e != hipSuccess) { (void)hipFree(tx); return set_err(TL3D_E_HIP, "point upload failed"); }
-        d = tx;
-    }
+    Staging st(ctx);
+    const float *d;
+    int rc = st.in(xyz, (size_t)n * 12, &d);
+    if (rc) return rc;
     int nb = (int)((n + 255) / 256);
     if (nb > 1024) nb = 1024;
-    int rc = launch_bounds(ctx->stream, d, n, ctx->bounds_slab, nb);
-    std::vector<float> h((size_t)nb * 6);
-    hipError_t e = hipMemcpyAsync(h.data(), ctx->bounds_slab, h.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
-    hipError_t e2 = hipStreamSynchronize(ctx->stream);
-    if (tx) (void)hipFree(tx);
+    rc = launch_bounds(ctx->stream, d, n, ctx->bounds_slab, nb);
     if (rc) return rc;
-    if (e != hipSuccess || e2 != hipSuccess) return set_err(TL3D_E_HIP, "bounds read-back failed");
+    std::vector<float> h((size_t)nb * 6);
+    TL3D_HIP(hipMemcpyAsync(h.data(), ctx->bounds_slab, h.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    TL3D_HIP(hipStreamSynchronize(ctx->stream));
     for (int a = 0; a < 3; ++a) { out_min[a] = INFINITY; out_max[a] = -INFINITY; }
     for (int b = 0; b < nb; ++b)
         for (int a = 0; a < 3; ++a) {
@@ -1926,26 +1955,9 @@ int tl3d_icp_evaluate_pairs(tl3d_ctx *ctx, const tl3d_icp_pair *pairs, int n_pai
     if (chunk > (size_t)n_pairs) chunk = (size_t)n_pairs;
     TL3D_HIP(hipSetDevice(ctx->device));
     tl3d_ctx::IcpEval &b = ctx->icp_eval;
-    if (chunk > b.cap_pairs) {
-        if (b.pairs) (void)hipFree(b.pairs);
-        if (b.sums) (void)hipFree(b.sums);
-        b.pairs = nullptr; b.sums = nullptr; b.cap_pairs = 0;
-        const size_t cap = chunk < 64 ? 64 : chunk;
-        if (hipMalloc(&b.pairs, cap * sizeof(IcpEvalPair)) != hipSuccess || hipMalloc(&b.sums, cap * ICP_EVAL_SUMS * sizeof(double)) != hipSuccess) {
-            (void)hipGetLastError();
-            return set_err(TL3D_E_NOMEM, "ICP evaluation: buffer allocation failed");
-        }
-        b.cap_pairs = cap;
-    }
-    if (chunk * members * ICP_EVAL_SUMS > b.cap_slab) {
-        if (b.slab) (void)hipFree(b.slab);
-        b.slab = nullptr; b.cap_slab = 0;
-        if (hipMalloc(&b.slab, chunk * members * ICP_EVAL_SUMS * sizeof(double)) != hipSuccess) {
-            (void)hipGetLastError();
-            return set_err(TL3D_E_NOMEM, "ICP evaluation: buffer allocation failed");
-        }
-        b.cap_slab = chunk * members * ICP_EVAL_SUMS;
-    }
+    int grc = chunk <= b.cap_pairs ? TL3D_OK : grow_pair(&b.pairs, &b.sums, &b.cap_pairs, chunk < 64 ? 64 : chunk, "ICP evaluation");
+    if (!grc) grc = grow(&b.slab, &b.cap_slab, chunk * members * ICP_EVAL_SUMS, "ICP evaluation slab");
+    if (grc) return grc;
     std::vector<IcpEvalPair> hp(chunk);
     std::vector<double> hs(chunk * ICP_EVAL_SUMS);
     const float md = (float)max_dist;
@@ -1963,7 +1975,7 @@ int tl3d_icp_evaluate_pairs(tl3d_ctx *ctx, const tl3d_icp_pair *pairs, int n_pai
         }
         TL3D_HIP(hipMemcpyAsync(b.pairs, hp.data(), m * sizeof(IcpEvalPair), hipMemcpyHostToDevice, ctx->stream));
         const int rc = launch_icp_eval(ctx->stream, ctx->cam, b.pairs, (int)m, members, (float)ctx->cfg.min_depth, (float)ctx->cfg.max_depth, md * md, stride,
-                                       Ws, Hs, b.slab, b.sums);
+                                       Ws, Hs, b.slab, *b.sums);
         if (rc) return rc;
         TL3D_HIP(hipMemcpyAsync(hs.data(), b.sums, m * ICP_EVAL_SUMS * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         TL3D_HIP(hipStreamSynchronize(ctx->stream));
@@ -2050,21 +2062,11 @@ int tl3d_grid_download(tl3d_ctx *ctx, uint32_t channel, void *out, size_t bytes)
     TL3D_HIP(hipSetDevice(ctx->device));
     if (ctx->sparse) {
         // the dense image of the channel (what a dense grid would hold, free-space counts folded in): bricks gathered through the table
-        void *tmp = nullptr;
-        void *dst = out;
-        const bool dev_out = is_device_ptr(out);
-        if (!dev_out) {
-            if (hipMalloc(&tmp, nb) != hipSuccess) return set_err(TL3D_E_NOMEM, "dense image of the sparse grid (%zu B) does not fit", nb);
-            dst = tmp;
-        }
-        rc = launch_brick_rows(ctx->stream, ctx->grid, 0, channel == TL3D_CH_TSDF, p, nullptr, (long long)(ctx->nvox >> 9), dst, true);
-        hipError_t e = hipSuccess;
-        if (rc == TL3D_OK && !dev_out) e = hipMemcpyAsync(out, tmp, nb, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (tmp) (void)hipFree(tmp);
+        Staging st(ctx);
+        void *dst;
+        rc = st.out(out, nb, &dst);
         if (rc) return rc;
-        TL3D_HIP(e);
-        return TL3D_OK;
+        return st.finish(launch_brick_rows(ctx->stream, ctx->grid, 0, channel == TL3D_CH_TSDF, p, nullptr, (long long)(ctx->nvox >> 9), dst, true), true);
     }
     TL3D_HIP(hipMemcpyAsync(out, p, nb, hipMemcpyDefault, ctx->stream));
     TL3D_HIP(hipStreamSynchronize(ctx->stream));
@@ -2091,18 +2093,11 @@ int tl3d_grid_upload(tl3d_ctx *ctx, uint32_t channel, const void *in, size_t byt
     }
     if (ctx->sparse) {
         // the channel becomes the dense image `in`: bricks that hold anything get records, the others' records are cleared
-        void *tmp = nullptr;
-        const void *src = in;
-        if (!is_device_ptr(in)) {
-            if (hipMalloc(&tmp, nb) != hipSuccess) return set_err(TL3D_E_NOMEM, "grid staging alloc failed");
-            hipError_t e = hipMemcpyAsync(tmp, in, nb, hipMemcpyHostToDevice, ctx->stream);
-            if (e != hipSuccess) { (void)hipFree(tmp); return set_err(TL3D_E_HIP, "grid upload failed"); }
-            src = tmp;
-        }
-        rc = launch_brick_rows(ctx->stream, ctx->grid, 1, channel == TL3D_CH_TSDF, p, nullptr, (long long)(ctx->nvox >> 9), const_cast<void *>(src), false);
-        (void)hipStreamSynchronize(ctx->stream);
-        if (tmp) (void)hipFree(tmp);
-        return rc;
+        Staging st(ctx);
+        const void *src;
+        rc = st.in(in, nb, &src);
+        if (rc) return rc;
+        return st.finish(launch_brick_rows(ctx->stream, ctx->grid, 1, channel == TL3D_CH_TSDF, p, nullptr, (long long)(ctx->nvox >> 9), const_cast<void *>(src), false), true);
     }
     TL3D_HIP(hipMemcpyAsync(p, in, nb, hipMemcpyDefault, ctx->stream));
     TL3D_HIP(hipStreamSynchronize(ctx->stream));
@@ -2118,14 +2113,10 @@ int tl3d_grid_add(tl3d_ctx *ctx, uint32_t channel, const void *other, size_t byt
     ctx->grid_epoch++;
     REQUIRE(other && bytes == nb, TL3D_E_INVALID, "buffer is %zu B, grid channel is %zu B", bytes, nb);
     TL3D_HIP(hipSetDevice(ctx->device));
-    const void *src = other;
-    void *tmp = nullptr;
-    if (!is_device_ptr(other)) {
-        if (hipMalloc(&tmp, nb) != hipSuccess) return set_err(TL3D_E_NOMEM, "grid staging alloc failed");
-        hipError_t e = hipMemcpyAsync(tmp, other, nb, hipMemcpyDefault, ctx->stream);
-        if (e != hipSuccess) { (void)hipFree(tmp); return set_err(TL3D_E_HIP, "grid upload failed"); }
-        src = tmp;
-    }
+    Staging st(ctx);
+    const void *src;
+    rc = st.in(other, nb, &src);
+    if (rc) return rc;
     if (channel == TL3D_CH_TSDF) {
         // the merged weights must keep the int32 sums in range: largest weight here + largest weight there
         long long wa = ctx->tsdf_w_upper, wb = 0;
@@ -2143,11 +2134,7 @@ int tl3d_grid_add(tl3d_ctx *ctx, uint32_t channel, const void *other, size_t byt
     } else
         rc = ctx->sparse ? launch_brick_rows(ctx->stream, ctx->grid, 2, false, p, nullptr, (long long)(ctx->nvox >> 9), const_cast<void *>(src), false)
                          : launch_add_u64(ctx->stream, (unsigned long long *)p, (const unsigned long long *)src, nb / 8);
-    if (tmp) {
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(tmp);
-    }
-    return rc;
+    return st.finish(rc);
 }
 
 int tl3d_grid_touched_bricks(tl3d_ctx *ctx, uint32_t channels, uint8_t *map_dev, int64_t n_bricks) {
@@ -2272,14 +2259,15 @@ int tl3d_allreduce_grid(tl3d_ctx *ctx, uint32_t channels) {
         long long w = 0;
         int rc = measure_max_weight(ctx, ctx->tsdf, &w);
         if (rc) return rccl_abandon(ctx, rc);
-        long long *d_w = nullptr;
-        REQUIRE_OR_ABANDON(hipMalloc(&d_w, sizeof(long long)) == hipSuccess, TL3D_E_NOMEM, "alloc failed");
+        Staging st(ctx);
+        long long *d_w;
+        rc = st.scratch(sizeof(long long), &d_w);
+        if (rc) return rccl_abandon(ctx, rc);
         hipError_t e = hipMemcpyAsync(d_w, &w, sizeof(w), hipMemcpyHostToDevice, ctx->stream);
         int nrc = e == hipSuccess ? g_rccl.AllReduce(d_w, d_w, 1, 4 /* ncclInt64 */, 0 /* ncclSum */, ctx->rccl_comm, ctx->stream) : -1;
         long long total = 0;
         if (nrc == 0) e = hipMemcpyAsync(&total, d_w, sizeof(total), hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        (void)hipFree(d_w);
         REQUIRE_OR_ABANDON(nrc == 0 && e == hipSuccess, TL3D_E_HIP, "weight all-reduce failed: %s", nrc ? rccl_msg(nrc) : hipGetErrorString(e));
         REQUIRE_OR_ABANDON(total <= TL3D_TSDF_MAX_WEIGHT, TL3D_E_STATE,
                 "the merged TSDF grid could hold %lld observations per voxel (limit %d): merge more often or extract between scans", total,
@@ -2291,12 +2279,14 @@ int tl3d_allreduce_grid(tl3d_ctx *ctx, uint32_t channels) {
     // is less than half of the grid only those bricks' records travel (packed, summed, unpacked); a frame-sharded run of a
     // few dozen frames per rank touches a few per cent of a 1024^3 grid.
     const size_t nbr = ctx->nvox >> 9;
-    unsigned char *d_map = nullptr;
-    REQUIRE_OR_ABANDON(hipMalloc(&d_map, nbr) == hipSuccess, TL3D_E_NOMEM, "brick map alloc failed");
     std::vector<unsigned char> h_map(nbr);
     std::vector<unsigned> h_idx;
     int rc = TL3D_OK;
     {
+        Staging st(ctx);
+        unsigned char *d_map;
+        rc = st.scratch(nbr, &d_map);
+        if (rc) return rccl_abandon(ctx, rc);
         hipError_t e = hipMemsetAsync(d_map, 0, nbr, ctx->stream);
         if (e == hipSuccess)
             rc = launch_touched_bricks(ctx->stream, ctx->grid, (channels & TL3D_CH_TSDF) ? ctx->tsdf : nullptr, (channels & TL3D_CH_CENTROID) ? ctx->centroid : nullptr,
@@ -2304,7 +2294,6 @@ int tl3d_allreduce_grid(tl3d_ctx *ctx, uint32_t channels) {
         int nrc = (e == hipSuccess && rc == TL3D_OK) ? g_rccl.AllReduce(d_map, d_map, nbr, 1 /* ncclUint8 */, 2 /* ncclMax */, ctx->rccl_comm, ctx->stream) : -1;
         if (nrc == 0) e = hipMemcpyAsync(h_map.data(), d_map, nbr, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        (void)hipFree(d_map);
         REQUIRE_OR_ABANDON(rc == TL3D_OK && nrc == 0 && e == hipSuccess, TL3D_E_HIP, "brick-map all-reduce failed: %s", nrc > 0 ? rccl_msg(nrc) : hipGetErrorString(e));
     }
     for (size_t b = 0; b < nbr; ++b)
@@ -2333,30 +2322,26 @@ int tl3d_allreduce_grid(tl3d_ctx *ctx, uint32_t channels) {
         REQUIRE_OR_ABANDON(hipStreamSynchronize(ctx->stream) == hipSuccess, TL3D_E_HIP, "sync failed");
         return TL3D_OK;
     }
-    unsigned *d_idx = nullptr;
-    void *d_pack = nullptr;
+    Staging st(ctx);
+    const unsigned *d_idx;
+    void *d_pack;
     const size_t n = h_idx.size();
     const size_t row = (channels & TL3D_CH_CENTROID) ? 16384 : 4096;
-    if (hipMalloc(&d_idx, n * sizeof(unsigned)) != hipSuccess || hipMalloc(&d_pack, n * row) != hipSuccess) {
-        (void)hipGetLastError();
-        if (d_idx) (void)hipFree(d_idx);
-        return rccl_abandon(ctx, set_err(TL3D_E_NOMEM, "merge staging alloc (%zu B) failed", n * row));
-    }
-    hipError_t e = hipMemcpyAsync(d_idx, h_idx.data(), n * sizeof(unsigned), hipMemcpyHostToDevice, ctx->stream);
+    rc = st.in(h_idx.data(), n * sizeof(unsigned), &d_idx);
+    if (!rc) rc = st.scratch(n * row, &d_pack);
+    if (rc) return rccl_abandon(ctx, rc);
     int nrc = 0;
-    if (e == hipSuccess && (channels & TL3D_CH_TSDF)) {
+    if (channels & TL3D_CH_TSDF) {
         rc = launch_brick_rows(ctx->stream, ctx->grid, 0, true, ctx->tsdf, d_idx, (long long)n, d_pack, false);
         if (rc == TL3D_OK) nrc = g_rccl.AllReduce(d_pack, d_pack, n * 1024, 2 /* ncclInt32 */, 0, ctx->rccl_comm, ctx->stream);
         if (rc == TL3D_OK && nrc == 0) rc = launch_brick_rows(ctx->stream, ctx->grid, 1, true, ctx->tsdf, d_idx, (long long)n, d_pack, false);
     }
-    if (e == hipSuccess && rc == TL3D_OK && nrc == 0 && (channels & TL3D_CH_CENTROID)) {
+    if (rc == TL3D_OK && nrc == 0 && (channels & TL3D_CH_CENTROID)) {
         rc = launch_brick_rows(ctx->stream, ctx->grid, 0, false, ctx->centroid, d_idx, (long long)n, d_pack, false);
         if (rc == TL3D_OK) nrc = g_rccl.AllReduce(d_pack, d_pack, n * 2048, 5 /* ncclUint64 */, 0, ctx->rccl_comm, ctx->stream);
         if (rc == TL3D_OK && nrc == 0) rc = launch_brick_rows(ctx->stream, ctx->grid, 1, false, ctx->centroid, d_idx, (long long)n, d_pack, false);
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_idx);
-    (void)hipFree(d_pack);
+    const hipError_t e = hipStreamSynchronize(ctx->stream);
     REQUIRE_OR_ABANDON(rc == TL3D_OK && nrc == 0 && e == hipSuccess, TL3D_E_HIP, "sparse grid all-reduce failed: %s", nrc ? rccl_msg(nrc) : hipGetErrorString(e));
     return TL3D_OK;
 }
@@ -2371,7 +2356,7 @@ int tl3d_extract(tl3d_ctx *ctx, int mode, int min_count, int min_weight, double 
     FLUSH_AND_FOLD(ctx);
     TL3D_HIP(hipSetDevice(ctx->device));
     const int nblocks = (int)((ctx->nvox + EXTRACT_CHUNK - 1) / EXTRACT_CHUNK);
-    int rc = ensure_scratch_blocks(ctx, (size_t)nblocks + 1);
+    int rc = grow_pair(&ctx->block_counts, &ctx->block_offsets, &ctx->scratch_blocks, (size_t)nblocks + 1, "extraction scratch");
     if (rc) return rc;
     unsigned long long total = 0;
     const bool reuse = ctx->ext_valid && ctx->ext_epoch == ctx->grid_epoch && ctx->ext_mode == mode && ctx->ext_min_count == min_count &&
@@ -2393,51 +2378,20 @@ int tl3d_extract(tl3d_ctx *ctx, int mode, int min_count, int min_weight, double 
     if (!out_xyz || !out_rgb) return TL3D_OK;
     if ((int64_t)total > cap) return set_err(TL3D_E_CAPACITY, "need %llu points, capacity %lld", total, (long long)cap);
     if (total == 0) return TL3D_OK;
-    const bool direct = is_device_ptr(out_xyz) && is_device_ptr(out_rgb);
-    float *dxyz = out_xyz;
-    uint8_t *drgb = out_rgb;
-    if (!direct) {
-        if (hipMalloc(&dxyz, total * 12) != hipSuccess) return set_err(TL3D_E_NOMEM, "output staging alloc failed");
-        if (hipMalloc(&drgb, total * 3) != hipSuccess) { (void)hipFree(dxyz); return set_err(TL3D_E_NOMEM, "output staging alloc failed"); }
-    }
+    Staging st(ctx);
+    float *dxyz;
+    uint8_t *drgb;
+    rc = st.out(out_xyz, total * 12, &dxyz);
+    if (!rc) rc = st.out(out_rgb, total * 3, &drgb);
+    if (rc) return rc;
     rc = launch_extract_write(ctx->stream, ctx->grid, mode, min_count, min_weight, max_abs_tsdf, ctx->tsdf, ctx->centroid,
                               ctx->block_offsets, nblocks, dxyz, drgb, total);
-    hipError_t e = hipSuccess;
-    if (rc == TL3D_OK && !direct) {
-        e = hipMemcpyAsync(out_xyz, dxyz, total * 12, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(out_rgb, drgb, total * 3, hipMemcpyDeviceToHost, ctx->stream);
-    }
-    hipError_t e2 = hipStreamSynchronize(ctx->stream);
-    if (!direct) { (void)hipFree(dxyz); (void)hipFree(drgb); }
-    if (rc) return rc;
-    if (e != hipSuccess || e2 != hipSuccess) return set_err(TL3D_E_HIP, "extract copy/sync failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
-    return TL3D_OK;
-}
-
-// ------------------------------------------------------------------------------------------- mesh
-static int ensure_mesh_scratch(tl3d_ctx *ctx, size_t nblocks, size_t nfirst) {
-    if (nblocks > ctx->mesh_blocks) {
-        if (ctx->mesh_counts) (void)hipFree(ctx->mesh_counts);
-        if (ctx->mesh_offsets) (void)hipFree(ctx->mesh_offsets);
-        ctx->mesh_counts = nullptr;
-        ctx->mesh_offsets = nullptr;
-        ctx->mesh_blocks = 0;
-        if (hipMalloc(&ctx->mesh_counts, 2 * nblocks * sizeof(unsigned)) != hipSuccess) return set_err(TL3D_E_NOMEM, "mesh scratch alloc failed");
-        if (hipMalloc(&ctx->mesh_offsets, 2 * nblocks * sizeof(unsigned long long)) != hipSuccess) return set_err(TL3D_E_NOMEM, "mesh scratch alloc failed");
-        ctx->mesh_blocks = nblocks;
-    }
-    if (nfirst > ctx->mesh_first_n) {
-        if (ctx->mesh_first) (void)hipFree(ctx->mesh_first);
-        ctx->mesh_first = nullptr;
-        ctx->mesh_first_n = 0;
-        if (hipMalloc(&ctx->mesh_first, nfirst * sizeof(unsigned)) != hipSuccess)
-            return set_err(TL3D_E_NOMEM, "mesh vertex-id scratch alloc (%zu B) failed", nfirst * sizeof(unsigned));
-        ctx->mesh_first_n = nfirst;
-    }
-    return TL3D_OK;
+    return st.finish(rc, true);
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------- mesh
 
 static int extract_mesh_impl(tl3d_ctx *ctx, int min_weight, float *out_xyz, uint8_t *out_rgb, int64_t vert_cap, uint32_t *out_tri,
                              int64_t tri_cap, int64_t *out_n_vert, int64_t *out_n_tri, int64_t *out_key) {
@@ -2447,7 +2401,8 @@ static int extract_mesh_impl(tl3d_ctx *ctx, int min_weight, float *out_xyz, uint
     TL3D_HIP(hipSetDevice(ctx->device));
     const int nblocks = (int)((ctx->nvox + EXTRACT_CHUNK - 1) / EXTRACT_CHUNK);
     const size_t mb = (size_t)nblocks + 1;
-    int rc = ensure_mesh_scratch(ctx, mb, (size_t)ctx->grid.tsdf_cap << 9);
+    int rc = grow_pair(&ctx->mesh_counts, &ctx->mesh_offsets, &ctx->mesh_blocks, 2 * mb, "mesh scratch");
+    if (!rc) rc = grow(&ctx->mesh_first, &ctx->mesh_first_n, (size_t)ctx->grid.tsdf_cap << 9, "mesh vertex-id scratch");
     if (rc) return rc;
     unsigned *vcounts = ctx->mesh_counts, *tcounts = ctx->mesh_counts + mb;
     unsigned long long *voffs = ctx->mesh_offsets, *toffs = ctx->mesh_offsets + mb;
@@ -2481,36 +2436,19 @@ static int extract_mesh_impl(tl3d_ctx *ctx, int min_weight, float *out_xyz, uint
         return set_err(TL3D_E_CAPACITY, "need %llu vertices / %llu triangles, capacities %lld / %lld", nv, nt, (long long)vert_cap,
                        (long long)tri_cap);
     if (nv == 0) return TL3D_OK;                        // (no vertex: no meshed cell either)
-    const bool direct = is_device_ptr(out_xyz) && is_device_ptr(out_rgb) && is_device_ptr(out_tri) && (!out_key || is_device_ptr(out_key));
-    float *dxyz = out_xyz;
-    uint8_t *drgb = out_rgb;
-    uint32_t *dtri = out_tri;
-    int64_t *dkey = out_key;
-    if (!direct) {
-        dxyz = nullptr; drgb = nullptr; dtri = nullptr; dkey = nullptr;
-        if (hipMalloc(&dxyz, nv * 12) != hipSuccess || hipMalloc(&drgb, nv * 3) != hipSuccess ||
-            (nt && hipMalloc(&dtri, nt * 12) != hipSuccess) || (out_key && hipMalloc(&dkey, nv * 8) != hipSuccess)) {
-            (void)hipGetLastError();
-            if (dxyz) (void)hipFree(dxyz);
-            if (drgb) (void)hipFree(drgb);
-            if (dtri) (void)hipFree(dtri);
-            return set_err(TL3D_E_NOMEM, "mesh output staging alloc failed");
-        }
-    }
+    Staging st(ctx);
+    float *dxyz;
+    uint8_t *drgb;
+    uint32_t *dtri;
+    int64_t *dkey = nullptr;
+    rc = st.out(out_xyz, nv * 12, &dxyz);
+    if (!rc) rc = st.out(out_rgb, nv * 3, &drgb);
+    if (!rc) rc = st.out(out_tri, nt * 12, &dtri);              // (no triangle: nothing staged, nothing written)
+    if (!rc && out_key) rc = st.out(out_key, nv * 8, &dkey);
+    if (rc) return rc;
     rc = launch_mesh_write(ctx->stream, ctx->grid, min_weight, ctx->tsdf, ctx->centroid, voffs, toffs, nblocks, ctx->mesh_first,
                            dxyz, drgb, nv, dtri, nt, (long long *)dkey, ctx->lat);
-    hipError_t e = hipSuccess;
-    if (rc == TL3D_OK && !direct) {
-        e = hipMemcpyAsync(out_xyz, dxyz, nv * 12, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(out_rgb, drgb, nv * 3, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && nt) e = hipMemcpyAsync(out_tri, dtri, nt * 12, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && out_key) e = hipMemcpyAsync(out_key, dkey, nv * 8, hipMemcpyDeviceToHost, ctx->stream);
-    }
-    hipError_t e2 = hipStreamSynchronize(ctx->stream);
-    if (!direct) { (void)hipFree(dxyz); (void)hipFree(drgb); if (dtri) (void)hipFree(dtri); if (dkey) (void)hipFree(dkey); }
-    if (rc) return rc;
-    if (e != hipSuccess || e2 != hipSuccess) return set_err(TL3D_E_HIP, "mesh copy/sync failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
-    return TL3D_OK;
+    return st.finish(rc, true);
 }
 
 extern "C" {
@@ -2715,28 +2653,14 @@ int tl3d_statistical_outlier(tl3d_ctx *ctx, const float *xyz, int64_t n, int nb_
     *out_kept = 0;
     if (n == 0) return TL3D_OK;
     TL3D_HIP(hipSetDevice(ctx->device));
-    const bool din = is_device_ptr(xyz), dout = is_device_ptr(keep_out);
-    float *tx = nullptr;
-    uint8_t *tk = nullptr;
-    const float *dx = xyz;
-    uint8_t *dk = keep_out;
-    if (!din) {
-        if (hipMalloc(&tx, (size_t)n * 12) != hipSuccess) return set_err(TL3D_E_NOMEM, "staging alloc failed");
-        if (hipMemcpyAsync(tx, xyz, (size_t)n * 12, hipMemcpyDefault, ctx->stream) != hipSuccess) { (void)hipFree(tx); return set_err(TL3D_E_HIP, "upload failed"); }
-        dx = tx;
-    }
-    if (!dout) {
-        if (hipMalloc(&tk, (size_t)n) != hipSuccess) { if (tx) (void)hipFree(tx); return set_err(TL3D_E_NOMEM, "staging alloc failed"); }
-        dk = tk;
-    }
+    Staging st(ctx);
+    const float *dx;
+    uint8_t *dk;
+    int rc = st.in(xyz, (size_t)n * 12, &dx);
+    if (!rc) rc = st.out(keep_out, (size_t)n, &dk);
+    if (rc) return rc;
     long long kept = 0;
-    int rc = sor_run(ctx, dx, n, nb_neighbors, std_ratio, cell_size, dk, &kept);
-    if (rc == TL3D_OK && !dout) {
-        if (hipMemcpyAsync(keep_out, dk, (size_t)n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = set_err(TL3D_E_HIP, "download failed");
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    if (tx) (void)hipFree(tx);
-    if (tk) (void)hipFree(tk);
+    rc = st.finish(sor_run(ctx, dx, n, nb_neighbors, std_ratio, cell_size, dk, &kept), true);
     if (rc) return rc;
     *out_kept = kept;
     return TL3D_OK;
@@ -2749,28 +2673,13 @@ int tl3d_knn_mean_distance(tl3d_ctx *ctx, const float *xyz, int64_t n, int nb_ne
     REQUIRE(cell_size > 0, TL3D_E_INVALID, "cell_size must be positive");
     if (n == 0) return TL3D_OK;
     TL3D_HIP(hipSetDevice(ctx->device));
-    const bool din = is_device_ptr(xyz), dout = is_device_ptr(mean_out);
-    float *tx = nullptr;
-    double *tm = nullptr;
-    const float *dx = xyz;
-    double *dm = mean_out;
-    if (!din) {
-        if (hipMalloc(&tx, (size_t)n * 12) != hipSuccess) return set_err(TL3D_E_NOMEM, "staging alloc failed");
-        if (hipMemcpyAsync(tx, xyz, (size_t)n * 12, hipMemcpyDefault, ctx->stream) != hipSuccess) { (void)hipFree(tx); return set_err(TL3D_E_HIP, "upload failed"); }
-        dx = tx;
-    }
-    if (!dout) {
-        if (hipMalloc(&tm, (size_t)n * sizeof(double)) != hipSuccess) { if (tx) (void)hipFree(tx); return set_err(TL3D_E_NOMEM, "staging alloc failed"); }
-        dm = tm;
-    }
-    int rc = sor_mean_distance(ctx, dx, n, nb_neighbors, cell_size, dm);
-    if (rc == TL3D_OK && !dout) {
-        if (hipMemcpyAsync(mean_out, dm, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = set_err(TL3D_E_HIP, "download failed");
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    if (tx) (void)hipFree(tx);
-    if (tm) (void)hipFree(tm);
-    return rc;
+    Staging st(ctx);
+    const float *dx;
+    double *dm;
+    int rc = st.in(xyz, (size_t)n * 12, &dx);
+    if (!rc) rc = st.out(mean_out, (size_t)n * sizeof(double), &dm);
+    if (rc) return rc;
+    return st.finish(sor_mean_distance(ctx, dx, n, nb_neighbors, cell_size, dm), true);
 }
 
 // ------------------------------------------------------------------------------------------- measurement

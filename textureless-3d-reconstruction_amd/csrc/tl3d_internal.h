@@ -188,35 +188,74 @@ constexpr int ICP_SLAB = 40;     // doubles per block partial: 30 sums of the po
 #define TL3D_TSDF_MAXBATCH 32
 constexpr int TSDF_SCRATCHES = 4;
 
-struct tl3d_ctx {
-    tl3d_config cfg;
-    int device;
-    hipStream_t stream;
-    bool own_stream;
-    tl3d::Cam cam;
+// Everything that lives exactly as long as the context's grid (tl3d_create with channels / tl3d_attach_grid ... tl3d_detach_grid /
+// tl3d_destroy): the channels, their brick tables, and every buffer, event and cached result whose size or meaning depends on the
+// grid.  All zero = "no grid".  release_grid (tl3d_api.hip) is the one place that frees it, and it resets the whole struct, so a
+// new grid-sized member needs a line there only if it owns something.
+struct tl3d_grid_state {
     tl3d::Grid grid;
     size_t nvox;
-    tl3d::Slot *slots;
-    tl3d::FramePool pool_depth, pool_u16, pool_bgr, pool_nmap, pool_sdepth;
-    int normal_radius;           // tl3d_set_normal_smoothing: window radius of the next normal maps (0: none)
     int2 *tsdf;                  // record pool of the TSDF channel: [tsdf_cap bricks][512] {sum_q, weight}; a dense grid's pool is the grid
     unsigned long long *centroid;// record pool of the centroid channel: [cen_cap bricks][512][4]
     bool own_tsdf, own_centroid;
     bool sparse;                 // pools smaller than the grid, slots handed out on first touch (tl3d_config.pool_bricks_*)
     unsigned *brick_tabs;        // one allocation: TSDF table [nbricks], centroid table [nbricks], cursors [4]
+    void *tsdf_scratch[TSDF_SCRATCHES];   // batch scratch (descriptors, tile pyramids, brick lists, frame masks, sub-brick masks), one per batch in
+                                          // flight: the update of batch k on the main stream, the prep chains of the next batches on the prep streams
+    void *tsdf_scratch_slab;              // the one allocation they are carved from
+    hipEvent_t ev_upd[TSDF_SCRATCHES];                 // the update of the last batch that used scratch h is done (main stream)
+    bool upd_recorded[TSDF_SCRATCHES];
+    // extraction is called twice (size query, then with buffers): the block counts of the query are kept while nothing
+    // has touched the grids in between (every grid-modifying or pointer-exposing call bumps tl3d_ctx::grid_epoch)
+    unsigned long long ext_epoch, ext_total;
+    int ext_mode, ext_min_count, ext_min_weight;
+    double ext_max_abs;
+    bool ext_valid;
+    unsigned *block_counts;      // compaction counts
+    unsigned long long *block_offsets;
+    size_t scratch_blocks;       // capacity of both, in blocks
+    // tl3d_extract_mesh: counts of the size query (same reuse rule), per-block vertex / triangle counts and their offsets,
+    // and each vertex owner's first vertex id ([TSDF pool slots][512] u32, grown on demand)
+    unsigned long long mesh_epoch, mesh_nv, mesh_nt;
+    int mesh_min_weight;
+    bool mesh_valid;
+    unsigned *mesh_counts;                  // [2][blocks]: vertices, then triangles
+    unsigned long long *mesh_offsets;       // [2][blocks]
+    size_t mesh_blocks;                     // capacity of both, in entries (two per block)
+    unsigned *mesh_first;
+    size_t mesh_first_n;
+    // tl3d_set_block_core: the grid is one block of a lattice of lat[] voxels and emits only what its core (grid.clo / chi) owns
+    bool has_core;
+    long long lat[3];
+    // Free-space counters: a brick that is wholly free space in a frame gets +1 here (one integer add by the classification
+    // kernel) instead of (+32767, +1) on each of its 512 records; the pending counts are folded into the records before
+    // anything reads the TSDF channel.
+    unsigned *free_cnt;
+    bool free_dirty;
+    // int32 headroom of the TSDF sums: |sum_q| <= weight * 32767 stays below 2^31 while weight <= TL3D_TSDF_MAX_WEIGHT.
+    // tsdf_w_upper bounds the largest voxel weight from above (+1 per integrated frame); when it reaches the limit, or after
+    // a merge the library could not see (grid upload, grid pointer handed out), it is re-measured by a reduction over the grid
+    long long tsdf_w_upper;
+    bool tsdf_w_unknown;
+};
+
+struct tl3d_ctx : tl3d_grid_state {
+    tl3d_config cfg;
+    int device;
+    hipStream_t stream;
+    bool own_stream;
+    tl3d::Cam cam;
+    tl3d::Slot *slots;
+    tl3d::FramePool pool_depth, pool_u16, pool_bgr, pool_nmap, pool_sdepth;
+    int normal_radius;           // tl3d_set_normal_smoothing: window radius of the next normal maps (0: none)
     // scratch
-    // TSDF integration is double-buffered over two streams: the tile/pyramid/cull kernels of frame i+1 run on
-    // prep_stream while the update kernel of frame i streams the grid on the main stream.
+    // TSDF integration: the prep chain of a batch (tiles, pyramid, cull, brick classes) runs on a prep stream while the update
+    // kernel of the batch before it streams the grid on the main stream.
     hipStream_t prep_stream[4];  // consecutive BATCHES take them in turn (three by default: one per batch scratch)
     int n_prep_streams;
-    void *tsdf_scratch[TSDF_SCRATCHES];   // batch scratch (descriptors, tile pyramids, brick lists, frame masks, sub-brick masks): three batches in flight
-                                          // (the update of batch k, the prep chains of batches k+1 and k+2)
-    void *tsdf_scratch_slab;              // the one allocation they are carved from
     bool tsdf_pairing;                    // frames of a batch share ONE update launch (tl3d_set_tsdf_pairing(ctx, 0): one frame per launch)
     bool pend_u16;                        // depth kind of the pending batch (a batch holds one kind)
     hipEvent_t ev_prep[TSDF_SCRATCHES];                // prep of the batch using scratch h is done (recorded on its prep stream)
-    hipEvent_t ev_upd[TSDF_SCRATCHES];                 // the update of the last batch that used scratch h is done (main stream)
-    bool upd_recorded[TSDF_SCRATCHES];
     bool tsdf_use_u16;                    // gather from the millimetre image when the slot has one (env TL3D_U16_GATHER=0: never)
     int tsdf_batch;                       // frames per batch (env TL3D_TSDF_BATCH, default 32; 1 = no deferral)
     unsigned tsdf_seq, tsdf_batch_no;
@@ -225,25 +264,7 @@ struct tl3d_ctx {
     int n_cen_pend = 0;
     tl3d::CenFrame *d_cen_frames = nullptr;              // their descriptors on the device
     int n_pend;                           // frames of the batch being collected
-    // extraction is called twice (size query, then with buffers): the block counts of the query are kept while nothing
-    // has touched the grids in between (every grid-modifying or pointer-exposing call bumps grid_epoch)
-    unsigned long long grid_epoch, ext_epoch, ext_total;
-    int ext_mode, ext_min_count, ext_min_weight;
-    double ext_max_abs;
-    bool ext_valid;
-    // tl3d_extract_mesh: counts of the size query (same reuse rule), per-block vertex / triangle counts and their offsets,
-    // and each vertex owner's first vertex id ([TSDF pool slots][512] u32, grown on demand)
-    unsigned long long mesh_epoch, mesh_nv, mesh_nt;
-    int mesh_min_weight;
-    bool mesh_valid;
-    unsigned *mesh_counts;                  // [2][mesh_blocks]
-    unsigned long long *mesh_offsets;       // [2][mesh_blocks]
-    size_t mesh_blocks;
-    unsigned *mesh_first;
-    size_t mesh_first_n;
-    // tl3d_set_block_core: the grid is one block of a lattice of lat[] voxels and emits only what its core (grid.clo / chi) owns
-    bool has_core;
-    long long lat[3];
+    unsigned long long grid_epoch;        // bumped by every call that changes a grid or hands out a pointer into one (see ext_epoch / mesh_epoch)
     // tl3d_raycast: device staging of the outputs a caller wants on the host ([H][W] f32, [H][W][3] f32, [H][W][3] u8; grown on demand)
     float *ray_depth, *ray_nrm;
     uint8_t *ray_bgr;
@@ -253,25 +274,12 @@ struct tl3d_ctx {
     uint8_t *bp_stage_rgb;
     bool bp_async_pending;
     double *bp_factors;                  // projection factors (D2R:287-295): [0, W) xf[u] = (u - cx) / fx, [W, W + H) yf[v] = (v - cy) / fy
-    unsigned *block_counts;      // compaction counts
-    unsigned long long *block_offsets;
-    size_t scratch_blocks;
-    // int32 headroom of the TSDF sums: |sum_q| <= weight * 32767 stays below 2^31 while weight <= TL3D_TSDF_MAX_WEIGHT.
-    // tsdf_w_upper bounds the largest voxel weight from above (+1 per integrated frame); when it reaches the limit, or after
-    // a merge the library could not see (grid upload, grid pointer handed out), it is re-measured by a reduction over the grid
-    // Free-space counters: a brick that is wholly free space in a frame gets +1 here (one integer add by the classification
-    // kernel) instead of (+32767, +1) on each of its 512 records; the pending counts are folded into the records before
-    // anything reads the TSDF channel.  TL3D_FREE_COUNTERS=0 keeps the round-1 behaviour (records streamed every frame).
-    unsigned *free_cnt;
-    bool free_dirty;
     hipEvent_t ev_free;                   // recorded on the main stream behind its last write to free_cnt (clear, fold); prep chains wait for it
     bool ev_free_recorded;
-    int tsdf_max_blocks, tsdf_xcd_group;  // launch geometry of the update kernel (1536 workgroups, XCD-grouped lists)
+    int tsdf_max_blocks, tsdf_xcd_group;  // launch geometry of the update kernel (12 workgroups per CU, XCD-grouped lists)
     bool tsdf_single_stream;
     void *rccl_comm;             // ncclComm_t of tl3d_rccl_init (RCCL is dlopen'ed: tl3d_api.hip)
     int rccl_world;
-    long long tsdf_w_upper;
-    bool tsdf_w_unknown;
     int *d_maxw;
     unsigned long long *d_counters;   // device counters [16]
     unsigned long long *d_cen_counters;   // centroid statistics, sharded: [256 lines][8] (points kept, points dropped)
@@ -313,8 +321,9 @@ struct tl3d_ctx {
     } icp_batch;
     struct IcpEval {             // tl3d_icp_evaluate_pairs: device buffers of one chunk of pairs (main stream), grown on demand
         tl3d::IcpEvalPair *pairs;
-        double *slab, *sums;     // [pairs][members][ICP_EVAL_SUMS] partials, [pairs][ICP_EVAL_SUMS] totals
-        size_t cap_pairs, cap_slab;
+        double *slab;                            // [pairs][members][ICP_EVAL_SUMS] partials
+        double (*sums)[tl3d::ICP_EVAL_SUMS];     // [pairs] totals
+        size_t cap_pairs, cap_slab;              // of pairs and sums, in pairs; of slab, in doubles
     } icp_eval;
     struct Track {               // tl3d_track_*: device state, partial-sum slab, pinned state for the way in and out (main stream)
         tl3d::IcpState *state, *host;

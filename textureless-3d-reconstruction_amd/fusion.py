@@ -149,6 +149,86 @@ assert _ICP_EVAL_DT.itemsize == C.sizeof(abi.IcpEval)
 _TRIU6 = np.triu_indices(6)
 
 
+# ---- marshalling shared by the methods below (each said once) ------------------------------------------------------------
+def _grid_config(grid: GridSpec, cfg=None):
+    """`cfg` (default: a fresh abi.Config) with the grid fields of tl3d_config filled from a GridSpec."""
+    if cfg is None:
+        cfg = abi.Config()
+        cfg.abi_version = abi.ABI_VERSION
+    cfg.channels = int(grid.channels)
+    cfg.nx, cfg.ny, cfg.nz = (int(d) for d in grid.dims)
+    cfg.origin = (C.c_double * 3)(*[float(o) for o in grid.origin])
+    cfg.voxel_size, cfg.sdf_trunc = float(grid.voxel_size), float(grid.sdf_trunc)
+    cfg.pool_bricks_tsdf, cfg.pool_bricks_centroid = int(grid.pool_tsdf), int(grid.pool_centroid)
+    cfg.voxel_offset = (C.c_int64 * 3)(*[int(o) for o in grid.voxel_offset])
+    return cfg
+
+
+def _frame_arrays(slots, poses, scales):
+    """(slots int32 [n], R float64 [n,3,3], t float64 [n,3], scales float64 [n]) of many frames; poses: one (R, t) per frame."""
+    sl = np.ascontiguousarray(slots, np.int32)
+    R = np.ascontiguousarray(np.stack([np.asarray(p[0], np.float64).reshape(3, 3) for p in poses]))
+    t = np.ascontiguousarray(np.stack([np.asarray(p[1], np.float64).reshape(3) for p in poses]))
+    sc = np.ascontiguousarray(np.ones(len(slots)) if scales is None else np.asarray(scales, np.float64))
+    return sl, R, t, sc
+
+
+def _icp_params(kw) -> "abi.IcpParams":
+    """tl3d_icp_params from a level dict (the keywords of icp(), with its defaults)."""
+    return abi.IcpParams(int(kw.get("iters", 10)), int(kw.get("stride", 4)), float(kw.get("max_dist", 0.05)),
+                         float(kw.get("damping", 1e-6)), float(kw.get("eps", 1e-9)), float(kw.get("eig_rel", 1e-4)),
+                         1 if kw.get("estimate_scale", False) else 0, 0)
+
+
+def _icp_levels(levels):
+    lv = (abi.IcpParams * max(1, len(levels)))()
+    for i, kw in enumerate(levels):
+        lv[i] = _icp_params(kw)
+    return lv
+
+
+def _icp_result_dicts(res, n: int = 1) -> list:
+    """The first n of tl3d_icp_result records (a numpy record array, or one ctypes structure) as the dicts icp() returns."""
+    if not isinstance(res, np.ndarray):
+        res = np.frombuffer(res, _ICP_RESULT_DT)
+    T = res["T"].reshape(-1, 4, 4)
+    fit, rmse, nc, ns, it, st, sc = (res[k].tolist() for k in ("fitness", "rmse", "n_corr", "n_src", "iters_run", "status", "scale"))
+    return [dict(T=T[i], fitness=fit[i], rmse=rmse[i], n_corr=nc[i], n_src=ns[i], iters_run=it[i], status=st[i], scale=sc[i])
+            for i in range(n)]
+
+
+def _pair_records(pairs, T_init, scales):
+    """The request as one numpy record array laid out like tl3d_icp_pair (a Python loop over ctypes fields costs ~10 us per pair:
+    as much as the registration of a pair inside a large batch).  T_init: one 4x4 per pair, None entries = identity."""
+    n = len(pairs)
+    arr = np.zeros(n, _ICP_PAIR_DT)
+    pr = np.asarray(pairs, np.int64).reshape(n, 2)
+    arr["slot_src"], arr["slot_tgt"] = pr[:, 0], pr[:, 1]
+    arr["scale_src"] = 1.0 if scales is None else np.asarray(scales, np.float64)
+    arr["T_init"] = np.eye(4).ravel()
+    if T_init is not None:
+        for i, T0 in enumerate(T_init):
+            if T0 is not None:
+                arr["T_init"][i] = np.asarray(T0, np.float64).reshape(16)
+    return arr
+
+
+def _eval_dicts(res, n: int = 1) -> list:
+    """The first n of tl3d_icp_eval records (a numpy record array, or one ctypes structure) as the dicts icp_evaluate() returns:
+    the packed upper triangle unfolded into the symmetric 6 x 6 A, and the statistics derived from the sums."""
+    if not isinstance(res, np.ndarray):
+        res = np.frombuffer(res, _ICP_EVAL_DT)
+    A = np.zeros((n, 6, 6))
+    A[:, _TRIU6[0], _TRIU6[1]] = res["A"][:n]
+    A[:, _TRIU6[1], _TRIU6[0]] = res["A"][:n]
+    out = []
+    for i in range(n):
+        nc, ns, e = int(res["n_corr"][i]), int(res["n_src"][i]), float(res["e"][i])
+        out.append(dict(A=A[i], b=res["b"][i].copy(), e=e, n_corr=nc, n_src=ns, fitness=nc / ns if ns > 0 else 0.0,
+                        rmse=float(np.sqrt(e / nc)) if nc > 0 else 0.0))
+    return out
+
+
 class FusionContext:
     def __init__(self, width: int, height: int, fx: float, fy: float, cx: float, cy: float,
                  min_depth: float = 0.1, max_depth: float = 50.0, n_slots: int = 2,
@@ -164,13 +244,7 @@ class FusionContext:
         cfg.min_depth, cfg.max_depth = float(min_depth), float(max_depth)
         cfg.n_slots = int(n_slots)
         if grid is not None:
-            cfg.channels = int(grid.channels)
-            cfg.nx, cfg.ny, cfg.nz = (int(d) for d in grid.dims)
-            cfg.origin = (C.c_double * 3)(*[float(o) for o in grid.origin])
-            cfg.voxel_size = float(grid.voxel_size)
-            cfg.sdf_trunc = float(grid.sdf_trunc)
-            cfg.pool_bricks_tsdf, cfg.pool_bricks_centroid = int(grid.pool_tsdf), int(grid.pool_centroid)
-            cfg.voxel_offset = (C.c_int64 * 3)(*[int(o) for o in grid.voxel_offset])
+            _grid_config(grid, cfg)
         cfg.ext_tsdf = abi.ptr(ext_tsdf)
         cfg.ext_centroid = abi.ptr(ext_centroid)
         cfg.stream = abi.ptr(stream)
@@ -246,14 +320,7 @@ class FusionContext:
 
     def attach_grid(self, grid: "GridSpec", ext_tsdf=None, ext_centroid=None):
         """Give a grid-less context its fusion grid (frames stay resident across registration and fusion)."""
-        cfg = abi.Config()
-        cfg.abi_version = abi.ABI_VERSION
-        cfg.channels = int(grid.channels)
-        cfg.nx, cfg.ny, cfg.nz = (int(d) for d in grid.dims)
-        cfg.origin = (C.c_double * 3)(*[float(o) for o in grid.origin])
-        cfg.voxel_size, cfg.sdf_trunc = float(grid.voxel_size), float(grid.sdf_trunc)
-        cfg.pool_bricks_tsdf, cfg.pool_bricks_centroid = int(grid.pool_tsdf), int(grid.pool_centroid)
-        cfg.voxel_offset = (C.c_int64 * 3)(*[int(o) for o in grid.voxel_offset])
+        cfg = _grid_config(grid)
         cfg.ext_tsdf, cfg.ext_centroid = abi.ptr(ext_tsdf), abi.ptr(ext_centroid)
         abi.check(self._lib.tl3d_attach_grid(self._h, C.byref(cfg)))
         self._keep = (ext_tsdf, ext_centroid)
@@ -290,11 +357,13 @@ class FusionContext:
         r, t = pose
         return abi.d9(r), abi.d3(t), flags
 
+    def _depth_range(self, min_depth, max_depth):
+        return (self.min_depth if min_depth is None else float(min_depth), self.max_depth if max_depth is None else float(max_depth))
+
     def backproject(self, slot: int, pose=None, scale=1.0, subsample: int = 1, min_depth=None, max_depth=None,
                     scale_f64: bool = False):
         r, t, flags = self._pose_args(pose, abi.F_SCALE_F64 if scale_f64 else 0)
-        mn = self.min_depth if min_depth is None else float(min_depth)
-        mx = self.max_depth if max_depth is None else float(max_depth)
+        mn, mx = self._depth_range(min_depth, max_depth)
         cap = -(-self.height // subsample) * -(-self.width // subsample)
         xyz = np.empty((cap, 3), np.float32)
         rgb = np.empty((cap, 3), np.uint8)
@@ -308,8 +377,7 @@ class FusionContext:
         """Asynchronous, device-only form: out_xyz (float32 [cap,3]), out_rgb (uint8 [cap,3]) and out_n (int64 [1]) are
         device tensors (anything with data_ptr()); nothing is read back, the call returns once its kernel is enqueued."""
         r, t, flags = self._pose_args(pose, abi.F_SCALE_F64 if scale_f64 else 0)
-        mn = self.min_depth if min_depth is None else float(min_depth)
-        mx = self.max_depth if max_depth is None else float(max_depth)
+        mn, mx = self._depth_range(min_depth, max_depth)
         cap = int(out_xyz.shape[0]) if cap is None else int(cap)
         abi.check(self._lib.tl3d_backproject_device(self._h, int(slot), abi.ptr(r), abi.ptr(t), float(scale), flags, int(subsample),
                                                     mn, mx, abi.ptr(out_xyz), abi.ptr(out_rgb), cap, abi.ptr(out_n)))
@@ -317,8 +385,7 @@ class FusionContext:
     def frame_bounds(self, slot: int, pose=None, scale=1.0, subsample: int = 1, min_depth=None, max_depth=None, scale_f64: bool = False):
         """(min[3], max[3]) of the points backproject() would return, computed on the device (+-inf when there are none)."""
         r, t, flags = self._pose_args(pose, abi.F_SCALE_F64 if scale_f64 else 0)
-        mn_d = self.min_depth if min_depth is None else float(min_depth)
-        mx_d = self.max_depth if max_depth is None else float(max_depth)
+        mn_d, mx_d = self._depth_range(min_depth, max_depth)
         lo, hi = np.zeros(3), np.zeros(3)
         abi.check(self._lib.tl3d_frame_bounds(self._h, int(slot), abi.ptr(r), abi.ptr(t), float(scale), flags, int(subsample), mn_d, mx_d,
                                               abi.ptr(lo), abi.ptr(hi), None))
@@ -327,12 +394,8 @@ class FusionContext:
     def frames_bounds(self, slots, poses, scales=None, subsample: int = 1, min_depth=None, max_depth=None):
         """(min[3], max[3]) over the clouds of many frames (poses: one (R, t) per frame), one read-back per 16 frames."""
         n = len(slots)
-        sl = np.ascontiguousarray(slots, np.int32)
-        R = np.ascontiguousarray(np.stack([np.asarray(p[0], np.float64).reshape(3, 3) for p in poses]))
-        t = np.ascontiguousarray(np.stack([np.asarray(p[1], np.float64).reshape(3) for p in poses]))
-        sc = np.ascontiguousarray(np.ones(n) if scales is None else np.asarray(scales, np.float64))
-        mn_d = self.min_depth if min_depth is None else float(min_depth)
-        mx_d = self.max_depth if max_depth is None else float(max_depth)
+        sl, R, t, sc = _frame_arrays(slots, poses, scales)
+        mn_d, mx_d = self._depth_range(min_depth, max_depth)
         lo, hi = np.zeros(3), np.zeros(3)
         abi.check(self._lib.tl3d_frames_bounds(self._h, n, abi.ptr(sl), abi.ptr(R), abi.ptr(t), abi.ptr(sc), 0, int(subsample), mn_d, mx_d,
                                                abi.ptr(lo), abi.ptr(hi)))
@@ -342,19 +405,9 @@ class FusionContext:
         """(TSDF bricks, centroid bricks) a fusion of these frames into `grid` would give records to -- geometry only, nothing is
         allocated or written: what a sparse grid's pools must hold (tl3d.h: tl3d_count_bricks)."""
         n = len(slots)
-        cfg = abi.Config()
-        cfg.abi_version = abi.ABI_VERSION
-        cfg.channels = int(grid.channels)
-        cfg.nx, cfg.ny, cfg.nz = (int(d) for d in grid.dims)
-        cfg.origin = (C.c_double * 3)(*[float(o) for o in grid.origin])
-        cfg.voxel_size, cfg.sdf_trunc = float(grid.voxel_size), float(grid.sdf_trunc)
-        cfg.voxel_offset = (C.c_int64 * 3)(*[int(o) for o in grid.voxel_offset])
-        sl = np.ascontiguousarray(slots, np.int32)
-        R = np.ascontiguousarray(np.stack([np.asarray(p[0], np.float64).reshape(3, 3) for p in poses]))
-        t = np.ascontiguousarray(np.stack([np.asarray(p[1], np.float64).reshape(3) for p in poses]))
-        sc = np.ascontiguousarray(np.ones(n) if scales is None else np.asarray(scales, np.float64))
-        mn_d = self.min_depth if min_depth is None else float(min_depth)
-        mx_d = self.max_depth if max_depth is None else float(max_depth)
+        cfg = _grid_config(grid)                 # (the pool sizes are not read: the count is what sizes them)
+        sl, R, t, sc = _frame_arrays(slots, poses, scales)
+        mn_d, mx_d = self._depth_range(min_depth, max_depth)
         nt, nc = C.c_int64(0), C.c_int64(0)
         abi.check(self._lib.tl3d_count_bricks(self._h, C.byref(cfg), n, abi.ptr(sl), abi.ptr(R), abi.ptr(t), abi.ptr(sc), int(centroid_subsample),
                                               mn_d, mx_d, C.byref(nt), C.byref(nc)))
@@ -364,8 +417,7 @@ class FusionContext:
     def accumulate_centroid(self, slot: int, pose=None, scale=1.0, subsample: int = 1, min_depth=None, max_depth=None,
                             scale_f64: bool = False):
         r, t, flags = self._pose_args(pose, abi.F_SCALE_F64 if scale_f64 else 0)
-        mn = self.min_depth if min_depth is None else float(min_depth)
-        mx = self.max_depth if max_depth is None else float(max_depth)
+        mn, mx = self._depth_range(min_depth, max_depth)
         abi.check(self._lib.tl3d_accumulate_centroid(self._h, int(slot), abi.ptr(r), abi.ptr(t), float(scale), flags,
                                                      int(subsample), mn, mx))
 
@@ -392,12 +444,8 @@ class FusionContext:
         n = len(slots)
         if n == 0:
             return
-        sl = np.ascontiguousarray(slots, np.int32)
-        R = np.ascontiguousarray(np.stack([np.asarray(p[0], np.float64).reshape(3, 3) for p in poses]))
-        t = np.ascontiguousarray(np.stack([np.asarray(p[1], np.float64).reshape(3) for p in poses]))
-        sc = np.ascontiguousarray(np.ones(n) if scales is None else np.asarray(scales, np.float64))
-        mn_d = self.min_depth if min_depth is None else float(min_depth)
-        mx_d = self.max_depth if max_depth is None else float(max_depth)
+        sl, R, t, sc = _frame_arrays(slots, poses, scales)
+        mn_d, mx_d = self._depth_range(min_depth, max_depth)
         abi.check(self._lib.tl3d_fuse_frames(self._h, n, abi.ptr(sl), abi.ptr(R), abi.ptr(t), abi.ptr(sc), 0, int(centroid_subsample), mn_d, mx_d))
 
     def fuse_frames_packed(self, slots_i32, R_f64, t_f64, scales_f64=None, centroid_subsample: int = 0):
@@ -440,26 +488,24 @@ class FusionContext:
         """Point-to-plane ICP; returns T (src camera -> tgt camera) and statistics.  With src = previous frame and
         tgt = current frame, (T[:3,:3], T[:3,3]) is (R_rel, t_rel) of depth_to_reconstruction.py:618-620."""
         T0 = np.ascontiguousarray(np.eye(4) if T_init is None else np.asarray(T_init, np.float64).reshape(4, 4))
-        prm = abi.IcpParams(int(iters), int(stride), float(max_dist), float(damping), float(eps), float(eig_rel), 1 if estimate_scale else 0, 0)
+        prm = _icp_params(dict(iters=iters, stride=stride, max_dist=max_dist, damping=damping, eps=eps, eig_rel=eig_rel, estimate_scale=estimate_scale))
         res = abi.IcpResult()
         abi.check(self._lib.tl3d_icp_p2plane(self._h, int(slot_src), float(scale_src), int(slot_tgt), abi.ptr(T0),
                                              C.byref(prm), C.byref(res)))
-        return dict(T=np.array(res.T).reshape(4, 4), fitness=res.fitness, rmse=res.rmse, n_corr=res.n_corr,
-                    n_src=res.n_src, iters_run=res.iters_run, status=res.status, scale=res.scale)
+        return _icp_result_dicts(res)[0]
 
     def icp_enqueue(self, lane: int, slot_src: int, slot_tgt: int, T_init=None, iters=10, stride=4, max_dist=0.05,
                     damping=1e-6, eps=1e-9, scale_src=1.0, eig_rel=1e-4, estimate_scale=False):
         """Asynchronous form: up to abi.ICP_LANES independent registrations in flight (one per lane)."""
         T0 = np.ascontiguousarray(np.eye(4) if T_init is None else np.asarray(T_init, np.float64).reshape(4, 4))
-        prm = abi.IcpParams(int(iters), int(stride), float(max_dist), float(damping), float(eps), float(eig_rel), 1 if estimate_scale else 0, 0)
+        prm = _icp_params(dict(iters=iters, stride=stride, max_dist=max_dist, damping=damping, eps=eps, eig_rel=eig_rel, estimate_scale=estimate_scale))
         abi.check(self._lib.tl3d_icp_enqueue(self._h, int(lane), int(slot_src), float(scale_src), int(slot_tgt), abi.ptr(T0),
                                              C.byref(prm)))
 
     def icp_collect(self, lane: int):
         res = abi.IcpResult()
         abi.check(self._lib.tl3d_icp_collect(self._h, int(lane), C.byref(res)))
-        return dict(T=np.array(res.T).reshape(4, 4), fitness=res.fitness, rmse=res.rmse, n_corr=res.n_corr,
-                    n_src=res.n_src, iters_run=res.iters_run, status=res.status, scale=res.scale)
+        return _icp_result_dicts(res)[0]
 
     def icp_batch_enqueue(self, pairs, levels, T_init=None, scales=None):
         """Register every (slot_src, slot_tgt) of `pairs` through all of `levels` in ONE launch (asynchronous).
@@ -467,22 +513,8 @@ class FusionContext:
         levels: sequence of dicts with the keyword arguments of icp() (iters, stride, max_dist, damping, eps, eig_rel),
         coarse to fine.  T_init: one 4x4 per pair (default identity); scales: metric scale of each pair's source depth."""
         n = len(pairs)
-        # the request as one numpy record array laid out like tl3d_icp_pair (a Python loop over ctypes fields costs ~10 us per pair:
-        # as much as the registration of a pair inside a large batch)
-        arr = np.zeros(n, _ICP_PAIR_DT)
-        pr = np.asarray(pairs, np.int64).reshape(n, 2)
-        arr["slot_src"], arr["slot_tgt"] = pr[:, 0], pr[:, 1]
-        arr["scale_src"] = 1.0 if scales is None else np.asarray(scales, np.float64)
-        arr["T_init"] = np.eye(4).ravel()
-        if T_init is not None:
-            for i, T0 in enumerate(T_init):
-                if T0 is not None:
-                    arr["T_init"][i] = np.asarray(T0, np.float64).reshape(16)
-        lv = (abi.IcpParams * len(levels))()
-        for i, kw in enumerate(levels):
-            lv[i] = abi.IcpParams(int(kw.get("iters", 10)), int(kw.get("stride", 4)), float(kw.get("max_dist", 0.05)),
-                                  float(kw.get("damping", 1e-6)), float(kw.get("eps", 1e-9)), float(kw.get("eig_rel", 1e-4)),
-                                  1 if kw.get("estimate_scale", False) else 0, 0)
+        arr = _pair_records(pairs, T_init, scales)
+        lv = _icp_levels(levels)
         abi.check(self._lib.tl3d_icp_batch_enqueue(self._h, arr.ctypes.data_as(C.POINTER(abi.IcpPair)), n, lv, len(levels)))
         self._icp_batch_n = n
 
@@ -491,10 +523,7 @@ class FusionContext:
         res = np.zeros(max(1, n), _ICP_RESULT_DT)
         abi.check(self._lib.tl3d_icp_batch_collect(self._h, res.ctypes.data_as(C.POINTER(abi.IcpResult)), n))
         self._icp_batch_n = 0
-        T = res["T"].reshape(-1, 4, 4)
-        cols = [res[k].tolist() for k in ("fitness", "rmse", "n_corr", "n_src", "iters_run", "status", "scale")]
-        return [dict(T=T[i], fitness=cols[0][i], rmse=cols[1][i], n_corr=cols[2][i], n_src=cols[3][i], iters_run=cols[4][i],
-                     status=cols[5][i], scale=cols[6][i]) for i in range(n)]
+        return _icp_result_dicts(res, n)
 
     def icp_batch(self, pairs, levels, T_init=None, scales=None):
         self.icp_batch_enqueue(pairs, levels, T_init, scales)
@@ -506,27 +535,11 @@ class FusionContext:
         edge of a pose graph), b (sum J r), e (sum r^2), n_corr, n_src, fitness = n_corr / n_src, rmse = sqrt(e / n_corr).
         T: one 4x4 per pair (None entries = identity); scales: metric scale of each pair's source depth."""
         n = len(pairs)
-        arr = np.zeros(n, _ICP_PAIR_DT)
-        pr = np.asarray(pairs, np.int64).reshape(n, 2)
-        arr["slot_src"], arr["slot_tgt"] = pr[:, 0], pr[:, 1]
-        arr["scale_src"] = 1.0 if scales is None else np.asarray(scales, np.float64)
-        arr["T_init"] = np.eye(4).ravel()
-        if T is not None:
-            for i, T0 in enumerate(T):
-                if T0 is not None:
-                    arr["T_init"][i] = np.asarray(T0, np.float64).reshape(16)
+        arr = _pair_records(pairs, T, scales)
         res = np.zeros(max(1, n), _ICP_EVAL_DT)
         abi.check(self._lib.tl3d_icp_evaluate_pairs(self._h, arr.ctypes.data_as(C.POINTER(abi.IcpPair)), n, int(stride), float(max_dist),
                                                     res.ctypes.data_as(C.POINTER(abi.IcpEval))))
-        A = np.zeros((n, 6, 6))
-        A[:, _TRIU6[0], _TRIU6[1]] = res["A"][:n]
-        A[:, _TRIU6[1], _TRIU6[0]] = res["A"][:n]
-        out = []
-        for i in range(n):
-            nc, ns, e = int(res["n_corr"][i]), int(res["n_src"][i]), float(res["e"][i])
-            out.append(dict(A=A[i], b=res["b"][i].copy(), e=e, n_corr=nc, n_src=ns, fitness=nc / ns if ns > 0 else 0.0,
-                            rmse=float(np.sqrt(e / nc)) if nc > 0 else 0.0))
-        return out
+        return _eval_dicts(res, n)
 
     def track_evaluate(self, slot: int, pose, stride=2, max_dist=0.05, min_weight: int = 1, scale=1.0):
         """One point-to-SDF pass of the frame in `slot` against the TSDF channel at pose = (R, t) (world->camera, as integrate), no
@@ -536,12 +549,7 @@ class FusionContext:
         res = abi.IcpEval()
         abi.check(self._lib.tl3d_track_evaluate(self._h, int(slot), float(scale), abi.ptr(r), abi.ptr(t), int(min_weight), int(stride),
                                                 float(max_dist), C.byref(res)))
-        A = np.zeros((6, 6))
-        A[_TRIU6] = np.array(res.A)
-        A = A + np.triu(A, 1).T
-        nc, ns, e = int(res.n_corr), int(res.n_src), float(res.e)
-        return dict(A=A, b=np.array(res.b), e=e, n_corr=nc, n_src=ns, fitness=nc / ns if ns > 0 else 0.0,
-                    rmse=float(np.sqrt(e / nc)) if nc > 0 else 0.0)
+        return _eval_dicts(res)[0]
 
     def track(self, slot: int, pose_init, levels, min_weight: int = 1, scale=1.0):
         """Register the frame in `slot` against the TSDF channel, starting at pose_init = (R, t) (world->camera), through `levels`
@@ -549,17 +557,12 @@ class FusionContext:
         eig_rel), all on the device (tl3d_track_frame).  A dict like icp()'s, T being the world->camera pose, plus pose = (R, t);
         status 2 (fewer than 8 correspondences or a singular system) leaves the last good pose."""
         r, t = abi.d9(pose_init[0]), abi.d3(pose_init[1])
-        lv = (abi.IcpParams * max(1, len(levels)))()
-        for i, kw in enumerate(levels):
-            lv[i] = abi.IcpParams(int(kw.get("iters", 10)), int(kw.get("stride", 4)), float(kw.get("max_dist", 0.05)),
-                                  float(kw.get("damping", 1e-6)), float(kw.get("eps", 1e-9)), float(kw.get("eig_rel", 1e-4)),
-                                  1 if kw.get("estimate_scale", False) else 0, 0)
+        lv = _icp_levels(levels)
         res = abi.IcpResult()
         abi.check(self._lib.tl3d_track_frame(self._h, int(slot), float(scale), abi.ptr(r), abi.ptr(t), int(min_weight), lv, len(levels),
                                              C.byref(res)))
-        T = np.array(res.T).reshape(4, 4)
-        return dict(T=T, pose=(T[:3, :3].copy(), T[:3, 3].copy()), fitness=res.fitness, rmse=res.rmse, n_corr=res.n_corr, n_src=res.n_src,
-                    iters_run=res.iters_run, status=res.status, scale=res.scale)
+        out = _icp_result_dicts(res)[0]
+        return dict(out, pose=(out["T"][:3, :3].copy(), out["T"][:3, 3].copy()))
 
     # ---- grids -----------------------------------------------------------------------------
     def reset(self):
