@@ -73,6 +73,10 @@ def main(argv=None):
     parser.add_argument("--ascii", action="store_true", help="write the reference's ASCII fallback PLY instead of binary")
     parser.add_argument("--mesh-output", type=str, default=None,
                         help="also write the marching-cubes triangle mesh of the fused TSDF to this PLY (binary, or ASCII with --ascii)")
+    parser.add_argument("--mesh-min-component", type=int, default=0, metavar="N",
+                        help="drop the mesh's connected components with fewer than N triangles (needs --mesh-output)")
+    parser.add_argument("--mesh-largest-component", action="store_true",
+                        help="keep only the mesh's connected component with the most triangles (needs --mesh-output)")
     parser.add_argument("--render-output", type=str, default=None,
                         help="also render the fused model at every kept camera into this folder: <stem>_model_depth.npy / .png "
                              "(metres / u16 millimetres) and <stem>_model_color.png (one GPU only)")
@@ -95,6 +99,8 @@ def main(argv=None):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.render_output and (args.gpus > 1 or world > 1):
         parser.error("--render-output needs a single GPU: with --gpus > 1 rank 0 does not hold the other ranks' frames")
+    if (args.mesh_min_component > 0 or args.mesh_largest_component) and not args.mesh_output:
+        parser.error("--mesh-min-component / --mesh-largest-component filter the mesh: they need --mesh-output")
     if args.loop_closure and (args.gpus > 1 or world > 1):
         parser.error("--loop-closure needs a single GPU: every kept frame must be resident where the revisits are registered")
     if args.loop_closure and args.estimate_scale:
@@ -118,7 +124,8 @@ def main(argv=None):
                                   icp_max_dist=args.icp_max_dist, tsdf_min_weight=args.tsdf_min_weight, device=args.device,
                                   scale_update_weight=args.scale_update_weight, extract_mesh=args.mesh_output is not None,
                                   render_dir=args.render_output, loop_closure=args.loop_closure,
-                                  model_tracking=args.model_tracking)
+                                  model_tracking=args.model_tracking, mesh_min_component_triangles=max(0, args.mesh_min_component),
+                                  mesh_largest_component=args.mesh_largest_component)
     pipeline = DepthToReconstructionPipeline(config)
     # a rank decodes every frame on its host (pose chain and scale rule run over the whole sequence) and uploads its share
     streaming = args.stream and dist is None

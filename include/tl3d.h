@@ -392,6 +392,31 @@ int tl3d_extract_mesh_keyed(tl3d_ctx *ctx, int min_weight,
                             uint32_t *out_tri_hd, int64_t tri_cap, int64_t *out_key_hd,
                             int64_t *out_n_vert, int64_t *out_n_tri);
 
+/* Connected components of an indexed triangle list: n_vert vertices, n_tri rows of three uint32 indices, any mesh
+ * (the calls need no grid).  Two vertices are connected when one triangle names both; label[v] = the smallest vertex index of v's
+ * component; a vertex no triangle names is a component of its own with 0 triangles; a triangle belongs to the component of its
+ * vertices, and (a, a, b) counts as one and connects a and b.  Labels, counts and the filtered mesh are functions of the input
+ * alone: every run gives the same bytes.  No reference code: the reference has no mesh (Open3D clusters by shared EDGES; this
+ * clusters by shared vertices).  Host or device pointers throughout.
+ * The labelling call: label_out [n_vert]; tri_count_out [n_vert] or NULL: the component's triangle count at index = label, 0
+ * elsewhere; *out_n_components = the number of labels.
+ * The filter call keeps the components with at least min_triangles triangles (<= 0: every component, isolated vertices
+ * included: the identity; from 1 upward the vertices no triangle uses go); largest_only: only the component with the most
+ * triangles (ties: the smaller label), and only if it also passes min_triangles; a mesh without triangles then keeps nothing.
+ * Kept vertices (xyz, and rgb unless rgb_hd is NULL) and re-indexed triangles keep their relative order; keep_vert_out [n_vert] or
+ * NULL: 1 for a kept vertex.  No size query: pass vert_cap = n_vert and tri_cap = n_tri; short capacities give TL3D_E_CAPACITY
+ * with the four counts stored (vertices and triangles kept, components found and kept).
+ * TL3D_E_INVALID (decided before any device call, except the index check, which is a pass of its own in front of every indexed
+ * access): a null ctx, negative sizes, n_vert >= 2^31, n_tri >= 2^32, an index >= n_vert, an output that overlaps an input.
+ * n_tri == 0 or n_vert == 0 is TL3D_OK (n_vert == 0: nothing is read). */
+int tl3d_mesh_components(tl3d_ctx *ctx, const uint32_t *tri_hd, int64_t n_tri, int64_t n_vert,
+                         uint32_t *label_out_hd, uint32_t *tri_count_out_hd, int64_t *out_n_components);
+int tl3d_mesh_filter_components(tl3d_ctx *ctx, const float *xyz_hd, const uint8_t *rgb_hd, int64_t n_vert,
+                                const uint32_t *tri_hd, int64_t n_tri, int64_t min_triangles, int largest_only,
+                                float *out_xyz_hd, uint8_t *out_rgb_hd, int64_t vert_cap, uint32_t *out_tri_hd, int64_t tri_cap,
+                                uint8_t *keep_vert_out_hd,
+                                int64_t *out_n_vert, int64_t *out_n_tri, int64_t *out_n_components, int64_t *out_n_kept);
+
 /* ray casting of the TSDF channel from one camera: one ray per pixel of the context's camera, pose (R, t)
  * world->camera as tl3d_integrate.  depth [H][W] f32 (0 = no hit), normals [H][W][3] f32 in the camera frame facing the
  * camera ((0,0,0) where undefined), colour [H][W][3] BGR (TSDF-mode extraction colour of the hit voxel, 128 without one).

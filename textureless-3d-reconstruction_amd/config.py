@@ -54,6 +54,10 @@ class ReconstructionConfig:
     device: int = 0
     # marching-cubes mesh of the TSDF after the fusion (DepthToReconstructionPipeline.mesh / save_mesh)
     extract_mesh: bool = False
+    # drop the mesh's small connected components (both need extract_mesh): components with fewer
+    # triangles than this go (0: none does), and / or only the component with the most triangles stays
+    mesh_min_component_triangles: int = 0
+    mesh_largest_component: bool = False
     # folder for renders of the fused model at every kept camera (DepthToReconstructionPipeline.reconstruct)
     render_dir: Optional[str] = None
     # loop closure: revisits found from the chain's poses, registered with the same ICP, and every pose

@@ -157,7 +157,7 @@ class Staging {
         tmp_[n_++] = {*dev, host_out, bytes};
         return TL3D_OK;
     }
-    static constexpr int MAX = 4;
+    static constexpr int MAX = 8;
     struct Tmp { void *dev, *host_out; size_t bytes; };
     tl3d_ctx *ctx_;
     Tmp tmp_[MAX];
@@ -372,6 +372,12 @@ static void release_grid(tl3d_ctx *ctx) {
     if (gs.mesh_counts) (void)hipFree(gs.mesh_counts);
     if (gs.mesh_offsets) (void)hipFree(gs.mesh_offsets);
     if (gs.mesh_first) (void)hipFree(gs.mesh_first);
+    if (gs.cc_parent) (void)hipFree(gs.cc_parent);
+    if (gs.cc_count) (void)hipFree(gs.cc_count);
+    if (gs.cc_remap) (void)hipFree(gs.cc_remap);
+    if (gs.cc_counts) (void)hipFree(gs.cc_counts);
+    if (gs.cc_offsets) (void)hipFree(gs.cc_offsets);
+    if (gs.cc_info) (void)hipFree(gs.cc_info);
     for (int h = 0; h < TSDF_SCRATCHES; ++h)
         if (gs.ev_upd[h]) (void)hipEventDestroy(gs.ev_upd[h]);      // (build_grid creates them anew)
     memset(&gs, 0, sizeof(gs));
@@ -2680,6 +2686,154 @@ int tl3d_knn_mean_distance(tl3d_ctx *ctx, const float *xyz, int64_t n, int nb_ne
     if (!rc) rc = st.out(mean_out, (size_t)n * sizeof(double), &dm);
     if (rc) return rc;
     return st.finish(sor_mean_distance(ctx, dx, n, nb_neighbors, cell_size, dm), true);
+}
+
+// ------------------------------------------------------------------------------------------- mesh components
+// [a, a + na) and [b, b + nb) share a byte (host and device pointers live in one address space)
+static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
+    if (!a || !b || !na || !nb) return false;
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+
+// the argument checks both calls share; none of them needs a device
+static int cc_check_mesh(const uint32_t *tri, int64_t n_tri, int64_t n_vert) {
+    REQUIRE(n_tri >= 0 && n_vert >= 0, TL3D_E_INVALID, "negative size (n_tri %lld, n_vert %lld)", (long long)n_tri, (long long)n_vert);
+    REQUIRE(n_vert < (1ll << 31), TL3D_E_INVALID, "n_vert %lld: indices need fewer than 2^31 vertices", (long long)n_vert);
+    REQUIRE(n_tri < (1ll << 32), TL3D_E_INVALID, "n_tri %lld: the component key needs fewer than 2^32 triangles", (long long)n_tri);
+    REQUIRE(n_tri == 0 || tri, TL3D_E_INVALID, "null triangle list");
+    return TL3D_OK;
+}
+
+static int cc_grow(tl3d_ctx *ctx, int64_t n_tri, int64_t n_vert) {
+    size_t cap2 = ctx->cc_verts, cap3 = ctx->cc_verts;
+    int rc = grow(&ctx->cc_parent, &ctx->cc_verts, (size_t)n_vert, "mesh component scratch");
+    if (!rc) rc = grow(&ctx->cc_count, &cap2, (size_t)n_vert, "mesh component scratch");
+    if (!rc) rc = grow(&ctx->cc_remap, &cap3, (size_t)n_vert, "mesh component scratch");
+    if (rc) {
+        ctx->cc_verts = 0;
+        return rc;
+    }
+    const size_t chunks = (size_t)((n_vert + EXTRACT_CHUNK - 1) / EXTRACT_CHUNK) + (size_t)((n_tri + EXTRACT_CHUNK - 1) / EXTRACT_CHUNK) + 2;
+    rc = grow_pair(&ctx->cc_counts, &ctx->cc_offsets, &ctx->cc_chunks, chunks, "mesh component scratch");
+    if (rc) return rc;
+    if (!ctx->cc_info && hipMalloc(&ctx->cc_info, 8 * sizeof(unsigned long long)) != hipSuccess) {
+        (void)hipGetLastError();
+        ctx->cc_info = nullptr;
+        return set_err(TL3D_E_NOMEM, "mesh component scratch alloc failed");
+    }
+    return TL3D_OK;
+}
+
+// The validation pass and, only when every index is below n_vert, the labelling: cc_parent = labels, cc_count = triangles per
+// label, h_info = the report words (largest index, components, key of the largest component).  Waits for the stream twice.
+static int cc_label(tl3d_ctx *ctx, const uint32_t *dtri, int64_t n_tri, int64_t n_vert, unsigned long long h_info[4]) {
+    TL3D_HIP(hipMemsetAsync(ctx->cc_info, 0, 8 * sizeof(unsigned long long), ctx->stream));
+    int rc = launch_cc_validate(ctx->stream, dtri, n_tri, ctx->cc_info);
+    if (rc) return rc;
+    TL3D_HIP(hipMemcpyAsync(h_info, ctx->cc_info, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    TL3D_HIP(hipStreamSynchronize(ctx->stream));
+    REQUIRE(n_tri == 0 || (int64_t)h_info[0] < n_vert, TL3D_E_INVALID, "triangle index %llu out of range [0, %lld)", h_info[0], (long long)n_vert);
+    return launch_cc_label(ctx->stream, dtri, n_tri, n_vert, ctx->cc_parent, ctx->cc_count, ctx->cc_info);
+}
+
+int tl3d_mesh_components(tl3d_ctx *ctx, const uint32_t *tri, int64_t n_tri, int64_t n_vert, uint32_t *label_out, uint32_t *tri_count_out,
+                         int64_t *out_n_components) {
+    int rc = cc_check_mesh(tri, n_tri, n_vert);
+    if (rc) return rc;
+    REQUIRE(out_n_components != nullptr && (n_vert == 0 || label_out), TL3D_E_INVALID, "null argument");
+    const size_t tb = (size_t)n_tri * 12, vb = (size_t)n_vert * 4;
+    REQUIRE(!ranges_overlap(label_out, vb, tri, tb) && !ranges_overlap(tri_count_out, vb, tri, tb) && !ranges_overlap(label_out, vb, tri_count_out, vb),
+            TL3D_E_INVALID, "an output aliases an input (or the other output)");
+    REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
+    *out_n_components = 0;
+    if (n_vert == 0) return TL3D_OK;
+    TL3D_HIP(hipSetDevice(ctx->device));
+    rc = cc_grow(ctx, n_tri, n_vert);
+    if (rc) return rc;
+    Staging st(ctx);
+    const uint32_t *dtri = nullptr;
+    if (n_tri) rc = st.in(tri, tb, &dtri);
+    if (rc) return rc;
+    unsigned long long h[4] = {0, 0, 0, 0};
+    rc = cc_label(ctx, dtri, n_tri, n_vert, h);
+    if (rc) return rc;
+    TL3D_HIP(hipMemcpyAsync(label_out, ctx->cc_parent, vb, hipMemcpyDefault, ctx->stream));
+    if (tri_count_out) TL3D_HIP(hipMemcpyAsync(tri_count_out, ctx->cc_count, vb, hipMemcpyDefault, ctx->stream));
+    TL3D_HIP(hipMemcpyAsync(h, ctx->cc_info, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    TL3D_HIP(hipStreamSynchronize(ctx->stream));
+    *out_n_components = (int64_t)h[1];
+    return TL3D_OK;
+}
+
+int tl3d_mesh_filter_components(tl3d_ctx *ctx, const float *xyz, const uint8_t *rgb, int64_t n_vert, const uint32_t *tri, int64_t n_tri,
+                                int64_t min_triangles, int largest_only, float *out_xyz, uint8_t *out_rgb, int64_t vert_cap,
+                                uint32_t *out_tri, int64_t tri_cap, uint8_t *keep_vert_out, int64_t *out_n_vert, int64_t *out_n_tri,
+                                int64_t *out_n_components, int64_t *out_n_kept) {
+    int rc = cc_check_mesh(tri, n_tri, n_vert);
+    if (rc) return rc;
+    REQUIRE(vert_cap >= 0 && tri_cap >= 0, TL3D_E_INVALID, "negative capacity");
+    REQUIRE(out_n_vert && out_n_tri && out_n_components && out_n_kept, TL3D_E_INVALID, "null argument");
+    REQUIRE(n_vert == 0 || xyz, TL3D_E_INVALID, "null vertex list");
+    REQUIRE((vert_cap == 0 || (out_xyz && (out_rgb || !rgb))) && (tri_cap == 0 || out_tri), TL3D_E_INVALID, "null output with a capacity");
+    {
+        const void *ins[3] = {xyz, rgb, tri};
+        const size_t in_b[3] = {(size_t)n_vert * 12, (size_t)n_vert * 3, (size_t)n_tri * 12};
+        const void *outs[4] = {out_xyz, rgb ? out_rgb : nullptr, out_tri, keep_vert_out};
+        const size_t out_b[4] = {(size_t)vert_cap * 12, (size_t)vert_cap * 3, (size_t)tri_cap * 12, (size_t)n_vert};
+        for (int o = 0; o < 4; ++o)
+            for (int i = 0; i < 3; ++i)
+                REQUIRE(!ranges_overlap(outs[o], out_b[o], ins[i], in_b[i]), TL3D_E_INVALID, "an output aliases an input");
+    }
+    REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
+    *out_n_vert = *out_n_tri = *out_n_components = *out_n_kept = 0;
+    if (n_vert == 0) return TL3D_OK;
+    TL3D_HIP(hipSetDevice(ctx->device));
+    rc = cc_grow(ctx, n_tri, n_vert);
+    if (rc) return rc;
+    Staging st(ctx);
+    const float *dxyz = nullptr;
+    const uint8_t *drgb = nullptr;
+    const uint32_t *dtri = nullptr;
+    uint8_t *dkeep = nullptr;
+    rc = st.in(xyz, (size_t)n_vert * 12, &dxyz);
+    if (!rc && rgb) rc = st.in(rgb, (size_t)n_vert * 3, &drgb);
+    if (!rc && n_tri) rc = st.in(tri, (size_t)n_tri * 12, &dtri);
+    if (!rc && keep_vert_out) rc = st.out(keep_vert_out, (size_t)n_vert, &dkeep);
+    if (rc) return rc;
+    unsigned long long h[4] = {0, 0, 0, 0};
+    rc = cc_label(ctx, dtri, n_tri, n_vert, h);
+    if (rc) return rc;
+    const int vchunks = (int)((n_vert + EXTRACT_CHUNK - 1) / EXTRACT_CHUNK), tchunks = (int)((n_tri + EXTRACT_CHUNK - 1) / EXTRACT_CHUNK);
+    unsigned *vcounts = ctx->cc_counts, *tcounts = ctx->cc_counts + vchunks + 1;
+    unsigned long long *voffs = ctx->cc_offsets, *toffs = ctx->cc_offsets + vchunks + 1;
+    rc = launch_cc_keep_count(ctx->stream, (long long)min_triangles, largest_only != 0, dtri, n_tri, n_vert, ctx->cc_parent, ctx->cc_count,
+                              vcounts, tcounts, dkeep, ctx->cc_info);
+    if (!rc) rc = launch_scan(ctx->stream, vcounts, voffs, vchunks, voffs + vchunks);
+    if (!rc) rc = launch_scan(ctx->stream, tcounts, toffs, tchunks, toffs + tchunks);       // (no triangle: the total is 0)
+    if (rc) return rc;
+    unsigned long long tot[2] = {0, 0};
+    TL3D_HIP(hipMemcpyAsync(&tot[0], voffs + vchunks, sizeof(tot[0]), hipMemcpyDeviceToHost, ctx->stream));
+    TL3D_HIP(hipMemcpyAsync(&tot[1], toffs + tchunks, sizeof(tot[1]), hipMemcpyDeviceToHost, ctx->stream));
+    TL3D_HIP(hipMemcpyAsync(h, ctx->cc_info, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    TL3D_HIP(hipStreamSynchronize(ctx->stream));
+    *out_n_vert = (int64_t)tot[0];
+    *out_n_tri = (int64_t)tot[1];
+    *out_n_components = (int64_t)h[1];
+    *out_n_kept = (int64_t)h[3];
+    if ((int64_t)tot[0] > vert_cap || (int64_t)tot[1] > tri_cap)
+        return set_err(TL3D_E_CAPACITY, "need %llu vertices / %llu triangles, capacities %lld / %lld", tot[0], tot[1], (long long)vert_cap,
+                       (long long)tri_cap);
+    float *oxyz = nullptr;
+    uint8_t *orgb = nullptr;
+    uint32_t *otri = nullptr;
+    rc = st.out(out_xyz, (size_t)tot[0] * 12, &oxyz);
+    if (!rc && rgb) rc = st.out(out_rgb, (size_t)tot[0] * 3, &orgb);
+    if (!rc) rc = st.out(out_tri, (size_t)tot[1] * 12, &otri);
+    if (rc) return rc;
+    rc = launch_cc_compact(ctx->stream, (long long)min_triangles, largest_only != 0, dtri, n_tri, n_vert, ctx->cc_parent, ctx->cc_count, voffs,
+                           toffs, dxyz, drgb, oxyz, orgb, tot[0], otri, tot[1], ctx->cc_remap, ctx->cc_info);
+    return st.finish(rc, true);
 }
 
 // ------------------------------------------------------------------------------------------- measurement

@@ -224,6 +224,16 @@ struct tl3d_grid_state {
     size_t mesh_blocks;                     // capacity of both, in entries (two per block)
     unsigned *mesh_first;
     size_t mesh_first_n;
+    // tl3d_mesh_components / tl3d_mesh_filter_components: union-find parents (= labels), triangles per label and new vertex ids
+    // (12 B per vertex), kept counts and offsets per chunk of vertices / triangles, the words the kernels report through.  None of
+    // it depends on the grid (the calls work without one); it lives here so that release_grid stays the one place that frees
+    // device scratch grown on demand.
+    unsigned *cc_parent, *cc_count, *cc_remap;
+    size_t cc_verts;                        // capacity of each, in vertices
+    unsigned *cc_counts;                    // [vertex chunks + 1][triangle chunks + 1]
+    unsigned long long *cc_offsets;
+    size_t cc_chunks;                       // capacity of both, in entries
+    unsigned long long *cc_info;            // [8]: largest index, components, key of the largest component, kept components
     // tl3d_set_block_core: the grid is one block of a lattice of lat[] voxels and emits only what its core (grid.clo / chi) owns
     bool has_core;
     long long lat[3];
@@ -537,6 +547,16 @@ int probe_hw_queues(int n_streams, double spin_ms, double *elapsed_ms);
 int launch_add_i32(hipStream_t s, int *dst, const int *src, size_t n);
 int launch_add_u64(hipStream_t s, unsigned long long *dst, const unsigned long long *src, size_t n);
 // outlier filter: the k-NN mean-distance stage alone (mean_dev: n doubles), and the whole filter, which thresholds it
+int launch_cc_validate(hipStream_t s, const unsigned *tri, long long n_tri, unsigned long long *info);
+int launch_cc_label(hipStream_t s, const unsigned *tri, long long n_tri, long long n_vert, unsigned *parent, unsigned *count,
+                    unsigned long long *info);
+int launch_cc_keep_count(hipStream_t s, long long min_tri, int largest, const unsigned *tri, long long n_tri, long long n_vert,
+                         const unsigned *label, const unsigned *count, unsigned *vcounts, unsigned *tcounts, uint8_t *keep_out,
+                         unsigned long long *info);
+int launch_cc_compact(hipStream_t s, long long min_tri, int largest, const unsigned *tri, long long n_tri, long long n_vert,
+                      const unsigned *label, const unsigned *count, const unsigned long long *voffsets, const unsigned long long *toffsets,
+                      const float *xyz, const uint8_t *rgb, float *out_xyz, uint8_t *out_rgb, unsigned long long vcap, unsigned *out_tri,
+                      unsigned long long tcap, unsigned *remap, const unsigned long long *info);
 int sor_mean_distance(tl3d_ctx *ctx, const float *xyz_dev, long long n, int k, double cell, double *mean_dev);
 int sor_run(tl3d_ctx *ctx, const float *xyz_dev, long long n, int k, double std_ratio, double cell, uint8_t *keep_dev, long long *kept);
 

@@ -683,6 +683,67 @@ class FusionContext:
                                                       nt.value, C.byref(nv), C.byref(nt)))
         return (xyz, rgb, tris, key) if keys else (xyz, rgb, tris)
 
+    @staticmethod
+    def _mesh_arrays(xyz, rgb, tris):
+        """The caller's mesh as the library wants it, and a factory for outputs of the same kind: numpy arrays stay on the host,
+        torch tensors (indices as int32 bit patterns, torch having little uint32 support) stay where they are."""
+        if hasattr(tris, "data_ptr"):
+            import torch
+            dev = tris.device
+            names = {np.float32: torch.float32, np.uint8: torch.uint8, np.uint32: torch.int32}
+            tris = tris.reshape(-1, 3).contiguous()
+            assert tris.dtype in (torch.int32, torch.uint32), "triangle indices must be 32-bit"
+            if xyz is not None:
+                xyz = xyz.to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+            if rgb is not None:
+                rgb = rgb.to(device=dev, dtype=torch.uint8).reshape(-1, 3).contiguous()
+
+            def empty(shape, dtype):
+                return torch.empty(shape, dtype=names[dtype], device=dev)
+        else:
+            tris = np.ascontiguousarray(tris, dtype=np.uint32).reshape(-1, 3)
+            if xyz is not None:
+                xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+            if rgb is not None:
+                rgb = np.ascontiguousarray(rgb, dtype=np.uint8).reshape(-1, 3)
+            empty = np.empty
+        return xyz, rgb, tris, empty
+
+    def mesh_components(self, tris, n_vert: int):
+        """Connected components of an indexed triangle list over n_vert vertices (needs no grid):
+        (labels u32 [n_vert], tri_counts u32 [n_vert], n_components).  Two vertices are connected when one triangle names both;
+        labels[v] is the smallest vertex index of v's component; tri_counts holds a component's triangle count at index = label
+        and 0 elsewhere.  numpy in, numpy out; a torch device tensor of int32 indices in, int32 device tensors out."""
+        _, _, tris, empty = self._mesh_arrays(None, None, tris)
+        n_vert = int(n_vert)
+        labels, counts = empty((max(n_vert, 0),), np.uint32), empty((max(n_vert, 0),), np.uint32)
+        n = C.c_int64(0)
+        abi.check(self._lib.tl3d_mesh_components(self._h, abi.ptr(tris) if len(tris) else None, len(tris), n_vert,
+                                                 abi.ptr(labels) if n_vert > 0 else None, abi.ptr(counts) if n_vert > 0 else None, C.byref(n)))
+        return labels, counts, n.value
+
+    def filter_mesh(self, xyz, rgb, tris, min_triangles: int = 0, largest_only: bool = False):
+        """Drop the small connected components of a mesh (needs no grid): keeps the components with at
+        least min_triangles triangles (<= 0: all of them, the identity; from 1 upward the vertices no triangle uses go), or with
+        largest_only the one with the most triangles (if it passes min_triangles too).  Survivors keep their order.  rgb may be
+        None.  Returns (xyz, rgb, tris, info); info: components, components_kept, vertices_dropped, triangles_dropped and
+        keep_vert (bool [V] over the input vertices)."""
+        xyz, rgb, tris, empty = self._mesh_arrays(xyz, rgb, tris)
+        nv, nt = len(xyz), len(tris)
+        oxyz, otri = empty((nv, 3), np.float32), empty((nt, 3), np.uint32)
+        orgb = empty((nv, 3), np.uint8) if rgb is not None else None
+        keep = empty((nv,), np.uint8)
+        kv, kt, nc, nk = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+
+        def p(a):
+            return abi.ptr(a) if a is not None and len(a) else None
+        abi.check(self._lib.tl3d_mesh_filter_components(self._h, p(xyz), p(rgb), nv, p(tris), nt, int(min_triangles), 1 if largest_only else 0,
+                                                        p(oxyz), p(orgb), nv, p(otri), nt, p(keep), C.byref(kv), C.byref(kt), C.byref(nc),
+                                                        C.byref(nk)))
+        info = dict(components=nc.value, components_kept=nk.value, vertices_dropped=nv - kv.value, triangles_dropped=nt - kt.value,
+                    keep_vert=keep.astype(bool) if isinstance(keep, np.ndarray) else keep.bool())
+        return oxyz[:kv.value], (orgb[:kv.value] if orgb is not None else None), otri[:kt.value], info
+
     def raycast(self, pose, min_weight: int = 0, z_near=None, z_far=None, slot=None, out=None):
         """Ray-cast the TSDF channel from the camera at pose = (R, t) (world->camera, as integrate):
         (depth f32 [H,W] with 0 = no hit, normals f32 [H,W,3] in the camera frame, bgr u8 [H,W,3]).  z_near / z_far default to

@@ -461,6 +461,7 @@ class DepthToReconstructionPipeline:
         """
         self.mesh = None
         cfg = self.config
+        self._check_mesh_filter_config()
         loop = bool(getattr(cfg, "loop_closure", False)) and poses is None      # with poses given nothing is registered: the option is ignored
         if loop and estimate_scale:
             raise ValueError("loop_closure does not go with estimate_scale: the pose graph's edges carry no scale")
@@ -658,11 +659,15 @@ class DepthToReconstructionPipeline:
         if cfg.extract_mesh:
             t0 = clock()
             vx, vr, vt = mesh_parts[0][:3] if one else weld_meshes(mesh_parts, lattice.dims)[:3]
+            print(f"  Mesh: {len(vx)} vertices, {len(vt)} triangles" + ("" if one else f" (welded from {len(done)} blocks)"))
+            stage["mesh"] += clock() - t0
+            if self._mesh_filter_on():                   # on the WELDED mesh: a surface that crosses a block seam is counted whole
+                t0 = clock()
+                vx, vr, vt = self._filter_mesh(ctx, (vx, vr, vt))
+                stage["mesh_filter"] = clock() - t0
             self.mesh = (vx, vr, vt)
             self.stats["mesh_vertices"] = len(vx)
             self.stats["mesh_triangles"] = len(vt)
-            print(f"  Mesh: {len(vx)} vertices, {len(vt)} triangles" + ("" if one else f" (welded from {len(done)} blocks)"))
-            stage["mesh"] += clock() - t0
         if cfg.render_dir:
             t0 = clock()
             self._render_views(ctx)
@@ -719,6 +724,7 @@ class DepthToReconstructionPipeline:
             raise ValueError("loop_closure needs a single GPU: every kept frame must be resident where the revisits are registered")
         if getattr(self.config, "model_tracking", False) and poses is None:
             raise ValueError("model_tracking needs a single GPU: every kept frame is registered against one model, in order")
+        self._check_mesh_filter_config()
         world, rank = dist.get_world_size(), dist.get_rank()
         self.mesh = None
         if len(self.images) < 2:
@@ -845,6 +851,11 @@ class DepthToReconstructionPipeline:
                     t0 = time.perf_counter()
                     self.mesh = self._extract_mesh(ctx)
                     self.timings["mesh_s"] = round(time.perf_counter() - t0, 4)
+                    if self._mesh_filter_on():
+                        t0 = time.perf_counter()
+                        self.mesh = self._filter_mesh(ctx, self.mesh)
+                        self.stats["mesh_vertices"], self.stats["mesh_triangles"] = len(self.mesh[0]), len(self.mesh[2])
+                        self.timings["mesh_filter_s"] = round(time.perf_counter() - t0, 4)
                 say(f"\nFinal reconstruction: {len(xyz)} points, {len(self.camera_poses)} cameras")
                 xyz = xyz.astype(np.float64)
         finally:
@@ -879,6 +890,26 @@ class DepthToReconstructionPipeline:
         self.stats["mesh_vertices"] = len(xyz)
         self.stats["mesh_triangles"] = len(tris)
         print(f"  Mesh: {len(xyz)} vertices, {len(tris)} triangles")
+        return xyz, rgb, tris
+
+    def _mesh_filter_on(self) -> bool:
+        cfg = self.config
+        return int(getattr(cfg, "mesh_min_component_triangles", 0)) > 0 or bool(getattr(cfg, "mesh_largest_component", False))
+
+    def _check_mesh_filter_config(self):
+        if self._mesh_filter_on() and not self.config.extract_mesh:
+            raise ValueError("mesh_min_component_triangles / mesh_largest_component filter the mesh: they need extract_mesh = True")
+
+    def _filter_mesh(self, ctx: FusionContext, mesh):
+        """The mesh without its small connected components (config.mesh_min_component_triangles, mesh_largest_component;
+        FusionContext.filter_mesh); stats["mesh_components"] says what was found and what went."""
+        cfg = self.config
+        xyz, rgb, tris, info = ctx.filter_mesh(*mesh, min_triangles=int(getattr(cfg, "mesh_min_component_triangles", 0)),
+                                               largest_only=bool(getattr(cfg, "mesh_largest_component", False)))
+        info.pop("keep_vert")
+        self.stats["mesh_components"] = info
+        print(f"  Mesh filter: {info['components_kept']} of {info['components']} components kept, {info['vertices_dropped']} vertices and "
+              f"{info['triangles_dropped']} triangles dropped")
         return xyz, rgb, tris
 
     def _render_views(self, ctx: FusionContext):

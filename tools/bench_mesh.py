@@ -5,7 +5,11 @@ times, with device events after a warm-up, one complete tl3d_extract(TL3D_EXTRAC
 (size query + fill into device buffers, as a caller makes them), median of --reps calls each.  Prints V, T, both times and the
 algorithmic bytes of the three mesh passes over the mesh time as a fraction of 8 TB/s.
 
-    python tools/bench_mesh.py [--reps 20] [--frames 512]
+    python tools/bench_mesh.py [--reps 20] [--frames 512] [--components]
+
+--components adds the mesh component filter: one complete tl3d_mesh_filter_components of the extracted
+mesh (device buffers in, device buffers out, threshold --min-triangles) timed the same way beside the extraction it follows, and
+the scipy restatement of the same filter (tests/mesh_components_reference.py) on the host, wall clock.
 """
 import argparse
 import ctypes as C
@@ -22,6 +26,8 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--frames", type=int, default=512)
     ap.add_argument("--group", type=int, default=64, help="frames resident at once")
+    ap.add_argument("--components", action="store_true", help="also time the component filter on the extracted mesh, and its host reference")
+    ap.add_argument("--min-triangles", type=int, default=100)
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -105,6 +111,30 @@ def main():
         a = ctx.extract_mesh()
         b = ctx.extract_mesh()
         same = all(np.array_equal(x, y) for x, y in zip(a, b))
+        comp = None
+        if args.components:
+            import time
+            sys.path.insert(0, os.path.join(ROOT, "tests"))
+            import mesh_components_reference as mcr
+            run_mesh()                                              # mxyz / mrgb / mtri hold the mesh
+            fxyz, frgb, ftri = torch.empty_like(mxyz), torch.empty_like(mrgb), torch.empty_like(mtri)
+            cnt = [C.c_int64(0) for _ in range(4)]
+
+            def run_filter():
+                abi.check(lib.tl3d_mesh_filter_components(ctx._h, abi.ptr(mxyz), abi.ptr(mrgb), nv, abi.ptr(mtri), nt, args.min_triangles, 0,
+                                                          abi.ptr(fxyz), abi.ptr(frgb), nv, abi.ptr(ftri), nt, None,
+                                                          *[C.byref(c) for c in cnt]))
+            t_filter = timed(run_filter, lambda: None)
+            t0 = time.perf_counter()
+            want = mcr.filter_mesh(*a, args.min_triangles)
+            t_host = time.perf_counter() - t0
+            kv, kt = cnt[0].value, cnt[1].value
+            equal = (kv == len(want[0]) and kt == len(want[2]) and np.array_equal(fxyz[:kv].cpu().numpy(), want[0])
+                     and np.array_equal(frgb[:kv].cpu().numpy(), want[1]) and np.array_equal(ftri[:kt].cpu().numpy().view(np.uint32), want[2]))
+            comp = dict(min_triangles=args.min_triangles, components=cnt[2].value, components_kept=cnt[3].value, vertices_kept=kv,
+                        triangles_kept=kt, filter_ms_median=round(t_filter[0], 3), filter_ms_min=round(t_filter[1], 3),
+                        filter_over_mesh_extract=round(t_filter[0] / t_mesh[0], 3), host_reference_ms=round(1e3 * t_host, 1),
+                        host_over_filter=round(1e3 * t_host / t_filter[0], 1), equals_host_reference=bool(equal))
     nvox = spec.nvox
     # algorithmic bytes of the three mesh passes: every TSDF record read once per pass, the vertex / triangle outputs, the
     # first-id scratch written once per vertex owner (<= V) and read three times per triangle, colour records (two per vertex at most)
@@ -117,6 +147,8 @@ def main():
                mesh_alg_bytes=bytes_mesh, mesh_frac_of_8TBps=round(bytes_mesh / (t_mesh[0] * 1e-3) / 8e12, 4),
                tsdf_alg_bytes=bytes_tsdf, tsdf_frac_of_8TBps=round(bytes_tsdf / (t_tsdf[0] * 1e-3) / 8e12, 4),
                repeat_identical=bool(same), reps=args.reps)
+    if comp is not None:
+        res["components"] = comp
     print(json.dumps(res))
 
 
