@@ -417,6 +417,37 @@ int tl3d_mesh_filter_components(tl3d_ctx *ctx, const float *xyz_hd, const uint8_
                                 uint8_t *keep_vert_out_hd,
                                 int64_t *out_n_vert, int64_t *out_n_tri, int64_t *out_n_components, int64_t *out_n_kept);
 
+/* Vertex-clustering simplification of an indexed triangle mesh: n_vert vertices (xyz f32 [V][3], rgb u8 [V][3] or
+ * NULL), n_tri rows of three uint32 indices, any mesh (the call needs no grid), a cell size in metres and an origin (NULL: 0, 0, 0).
+ * No reference code: the reference has no mesh (Open3D's simplify_vertex_clustering is the model); the rules are ours, chosen so
+ * that the output is a function of the input alone, bit for bit, in every run.
+ * Cell of a vertex, per axis a, in fp64 with every operation rounded once: d = (double)x_a - o_a; i_a = floor(d / cell);
+ * r = d - (double)i_a * cell; q_a = (int64)rint((r / cell) * 16777216.0) (half to even; q_a may be slightly negative or slightly
+ * above 2^24).  Every vertex, named by a triangle or not, must be finite with -2^20 <= i_a < 2^20.
+ * A cluster is the set of vertices with equal (i_x, i_y, i_z): a member count n, exact integer sums S_a = sum q_a and C_c = sum
+ * rgb_c.  Clusters are numbered in the order of their smallest member vertex index, and EVERY cluster becomes an output vertex,
+ * also one that no surviving triangle names (tl3d_mesh_filter_components with min_triangles = 1 drops those):
+ *   position (float)(o_a + ((double)i_a + (double)S_a / ((double)n * 16777216.0)) * cell), operations in that order;
+ *   colour (2 C_c + n) / (2 n) in integers: the mean, halves rounded up;
+ *   vert_map_out [n_vert] or NULL: the output index of each input vertex's cluster.
+ * Triangles: the three indices go through vert_map; a triangle with two equal mapped indices is dropped (degenerate); of the
+ * triangles with the same canonical triple (the cyclic rotation that puts the smallest index first, which keeps the winding) the one
+ * with the smallest input index stays and the others are dropped (duplicate) -- (A, B, C) and (A, C, B) are different triangles
+ * and both stay; survivors are written in input order, mapped but not rotated.
+ * Every output vertex lies in the closed box of its cell, up to the f32 rounding of the result; winding is preserved; the result
+ * may be non-manifold.
+ * Host or device pointers throughout.  No size query: vert_cap = n_vert and tri_cap = n_tri always suffice; short capacities give
+ * TL3D_E_CAPACITY with the four counts stored (vertices and triangles out, triangles dropped as degenerate and as duplicate).
+ * TL3D_E_INVALID: a null ctx, negative sizes, n_vert >= 2^31, n_tri >= 2^32, cell or origin not finite, cell <= 0, an output that
+ * overlaps an input (all decided before any device call); an index >= n_vert, a vertex that is not finite or whose cell index is
+ * out of range (two passes of their own in front of every indexed access).  n_vert == 0 or n_tri == 0 is TL3D_OK (n_vert == 0:
+ * nothing is read; n_tri == 0: the vertices are clustered all the same). */
+int tl3d_mesh_simplify_clusters(tl3d_ctx *ctx, const float *xyz_hd, const uint8_t *rgb_hd, int64_t n_vert,
+                                const uint32_t *tri_hd, int64_t n_tri, double cell, const double origin[3],
+                                float *out_xyz_hd, uint8_t *out_rgb_hd, int64_t vert_cap, uint32_t *out_tri_hd, int64_t tri_cap,
+                                uint32_t *vert_map_out_hd,
+                                int64_t *out_n_vert, int64_t *out_n_tri, int64_t *out_n_degenerate, int64_t *out_n_duplicate);
+
 /* ray casting of the TSDF channel from one camera: one ray per pixel of the context's camera, pose (R, t)
  * world->camera as tl3d_integrate.  depth [H][W] f32 (0 = no hit), normals [H][W][3] f32 in the camera frame facing the
  * camera ((0,0,0) where undefined), colour [H][W][3] BGR (TSDF-mode extraction colour of the hit voxel, 128 without one).

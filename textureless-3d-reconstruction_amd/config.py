@@ -58,6 +58,9 @@ class ReconstructionConfig:
     # triangles than this go (0: none does), and / or only the component with the most triangles stays
     mesh_min_component_triangles: int = 0
     mesh_largest_component: bool = False
+    # vertex-clustering simplification of the mesh (needs extract_mesh): the vertices of one cell of this
+    # size, in metres, become one vertex (0: off); applied after the component filter when both are on
+    mesh_simplify_cell: float = 0.0
     # folder for renders of the fused model at every kept camera (DepthToReconstructionPipeline.reconstruct)
     render_dir: Optional[str] = None
     # loop closure: revisits found from the chain's poses, registered with the same ICP, and every pose

@@ -378,6 +378,16 @@ static void release_grid(tl3d_ctx *ctx) {
     if (gs.cc_counts) (void)hipFree(gs.cc_counts);
     if (gs.cc_offsets) (void)hipFree(gs.cc_offsets);
     if (gs.cc_info) (void)hipFree(gs.cc_info);
+    if (gs.ms_keys) (void)hipFree(gs.ms_keys);
+    if (gs.ms_leader) (void)hipFree(gs.ms_leader);
+    if (gs.ms_slot) (void)hipFree(gs.ms_slot);
+    if (gs.ms_vmap) (void)hipFree(gs.ms_vmap);
+    if (gs.ms_acc) (void)hipFree(gs.ms_acc);
+    if (gs.ms_ttab) (void)hipFree(gs.ms_ttab);
+    if (gs.ms_flag) (void)hipFree(gs.ms_flag);
+    if (gs.ms_counts) (void)hipFree(gs.ms_counts);
+    if (gs.ms_offsets) (void)hipFree(gs.ms_offsets);
+    if (gs.ms_info) (void)hipFree(gs.ms_info);
     for (int h = 0; h < TSDF_SCRATCHES; ++h)
         if (gs.ev_upd[h]) (void)hipEventDestroy(gs.ev_upd[h]);      // (build_grid creates them anew)
     memset(&gs, 0, sizeof(gs));
@@ -2833,6 +2843,114 @@ int tl3d_mesh_filter_components(tl3d_ctx *ctx, const float *xyz, const uint8_t *
     if (rc) return rc;
     rc = launch_cc_compact(ctx->stream, (long long)min_triangles, largest_only != 0, dtri, n_tri, n_vert, ctx->cc_parent, ctx->cc_count, voffs,
                            toffs, dxyz, drgb, oxyz, orgb, tot[0], otri, tot[1], ctx->cc_remap, ctx->cc_info);
+    return st.finish(rc, true);
+}
+
+// ------------------------------------------------------------------------------------------- mesh simplification
+static size_t ms_table_slots(int64_t n) {
+    size_t cap = 1024;
+    while (cap < 2 * (size_t)n) cap <<= 1;
+    return cap;
+}
+
+static int ms_grow(tl3d_ctx *ctx, int64_t n_tri, int64_t n_vert) {
+    const char *what = "mesh simplification scratch";
+    int rc = grow_pair(&ctx->ms_keys, &ctx->ms_leader, &ctx->ms_vslots, ms_table_slots(n_vert), what);
+    if (!rc) rc = grow_pair(&ctx->ms_slot, &ctx->ms_vmap, &ctx->ms_verts, (size_t)n_vert, what);
+    if (!rc) rc = grow(&ctx->ms_acc, &ctx->ms_acc_n, 7 * (size_t)n_vert, what);
+    if (!rc && n_tri) rc = grow(&ctx->ms_ttab, &ctx->ms_tslots, ms_table_slots(n_tri), what);
+    if (!rc && n_tri) rc = grow(&ctx->ms_flag, &ctx->ms_tris, (size_t)n_tri, what);
+    const size_t chunks = (size_t)((n_vert + EXTRACT_CHUNK - 1) / EXTRACT_CHUNK) + (size_t)((n_tri + EXTRACT_CHUNK - 1) / EXTRACT_CHUNK) + 2;
+    if (!rc) rc = grow_pair(&ctx->ms_counts, &ctx->ms_offsets, &ctx->ms_chunks, chunks, what);
+    if (rc) return rc;
+    if (!ctx->ms_info && hipMalloc(&ctx->ms_info, 8 * sizeof(unsigned long long)) != hipSuccess) {
+        (void)hipGetLastError();
+        ctx->ms_info = nullptr;
+        return set_err(TL3D_E_NOMEM, "%s alloc failed", what);
+    }
+    return TL3D_OK;
+}
+
+int tl3d_mesh_simplify_clusters(tl3d_ctx *ctx, const float *xyz, const uint8_t *rgb, int64_t n_vert, const uint32_t *tri, int64_t n_tri,
+                                double cell, const double origin[3], float *out_xyz, uint8_t *out_rgb, int64_t vert_cap,
+                                uint32_t *out_tri, int64_t tri_cap, uint32_t *vert_map_out, int64_t *out_n_vert, int64_t *out_n_tri,
+                                int64_t *out_n_degenerate, int64_t *out_n_duplicate) {
+    int rc = cc_check_mesh(tri, n_tri, n_vert);
+    if (rc) return rc;
+    REQUIRE(vert_cap >= 0 && tri_cap >= 0, TL3D_E_INVALID, "negative capacity");
+    REQUIRE(out_n_vert && out_n_tri && out_n_degenerate && out_n_duplicate, TL3D_E_INVALID, "null argument");
+    REQUIRE(std::isfinite(cell) && cell > 0.0, TL3D_E_INVALID, "cell size %g: must be finite and > 0", cell);
+    const double o[3] = {origin ? origin[0] : 0.0, origin ? origin[1] : 0.0, origin ? origin[2] : 0.0};
+    REQUIRE(std::isfinite(o[0]) && std::isfinite(o[1]) && std::isfinite(o[2]), TL3D_E_INVALID, "origin (%g, %g, %g) is not finite", o[0], o[1], o[2]);
+    REQUIRE(n_vert == 0 || xyz, TL3D_E_INVALID, "null vertex list");
+    REQUIRE((vert_cap == 0 || (out_xyz && (out_rgb || !rgb))) && (tri_cap == 0 || out_tri), TL3D_E_INVALID, "null output with a capacity");
+    {
+        const void *ins[3] = {xyz, rgb, tri};
+        const size_t in_b[3] = {(size_t)n_vert * 12, (size_t)n_vert * 3, (size_t)n_tri * 12};
+        const void *outs[4] = {out_xyz, rgb ? out_rgb : nullptr, out_tri, vert_map_out};
+        const size_t out_b[4] = {(size_t)vert_cap * 12, (size_t)vert_cap * 3, (size_t)tri_cap * 12, (size_t)n_vert * 4};
+        for (int k = 0; k < 4; ++k)
+            for (int i = 0; i < 3; ++i)
+                REQUIRE(!ranges_overlap(outs[k], out_b[k], ins[i], in_b[i]), TL3D_E_INVALID, "an output aliases an input");
+    }
+    REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
+    *out_n_vert = *out_n_tri = *out_n_degenerate = *out_n_duplicate = 0;
+    if (n_vert == 0) return TL3D_OK;
+    TL3D_HIP(hipSetDevice(ctx->device));
+    rc = ms_grow(ctx, n_tri, n_vert);
+    if (rc) return rc;
+    Staging st(ctx);
+    const float *dxyz = nullptr;
+    const uint8_t *drgb = nullptr;
+    const uint32_t *dtri = nullptr;
+    rc = st.in(xyz, (size_t)n_vert * 12, &dxyz);
+    if (!rc && rgb) rc = st.in(rgb, (size_t)n_vert * 3, &drgb);
+    if (!rc && n_tri) rc = st.in(tri, (size_t)n_tri * 12, &dtri);
+    if (rc) return rc;
+    // the validation passes: nothing is indexed, and no cell is computed for a table, before the host has seen their words
+    unsigned long long h[4] = {0, 0, 0, 0};
+    TL3D_HIP(hipMemsetAsync(ctx->ms_info, 0, 8 * sizeof(unsigned long long), ctx->stream));
+    rc = launch_cc_validate(ctx->stream, dtri, n_tri, ctx->ms_info);
+    if (!rc) rc = launch_ms_validate(ctx->stream, cell, o, dxyz, n_vert, ctx->ms_info);
+    if (rc) return rc;
+    TL3D_HIP(hipMemcpyAsync(h, ctx->ms_info, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    TL3D_HIP(hipStreamSynchronize(ctx->stream));
+    REQUIRE(n_tri == 0 || (int64_t)h[0] < n_vert, TL3D_E_INVALID, "triangle index %llu out of range [0, %lld)", h[0], (long long)n_vert);
+    REQUIRE(h[1] == 0, TL3D_E_INVALID, "%llu vertices are not finite or lie 2^20 cells or more from the origin", h[1]);
+    const size_t vslots = ms_table_slots(n_vert), tslots = ms_table_slots(n_tri);
+    const int vchunks = (int)((n_vert + EXTRACT_CHUNK - 1) / EXTRACT_CHUNK), tchunks = (int)((n_tri + EXTRACT_CHUNK - 1) / EXTRACT_CHUNK);
+    unsigned *vcounts = ctx->ms_counts, *tcounts = ctx->ms_counts + vchunks + 1;
+    unsigned long long *voffs = ctx->ms_offsets, *toffs = ctx->ms_offsets + vchunks + 1;
+    TL3D_HIP(hipMemsetAsync(ctx->ms_keys, 0xFF, vslots * sizeof(unsigned long long), ctx->stream));
+    TL3D_HIP(hipMemsetAsync(ctx->ms_leader, 0xFF, vslots * sizeof(unsigned), ctx->stream));
+    TL3D_HIP(hipMemsetAsync(ctx->ms_acc, 0, 7 * (size_t)n_vert * sizeof(unsigned long long), ctx->stream));
+    if (n_tri) TL3D_HIP(hipMemsetAsync(ctx->ms_ttab, 0xFF, tslots * sizeof(unsigned), ctx->stream));
+    rc = launch_ms_cluster(ctx->stream, cell, o, dxyz, drgb, n_vert, ctx->ms_keys, ctx->ms_leader, vslots, ctx->ms_slot, ctx->ms_vmap,
+                           ctx->ms_acc, vcounts, voffs);
+    if (!rc) rc = launch_ms_triangles(ctx->stream, dtri, n_tri, ctx->ms_vmap, ctx->ms_ttab, tslots, ctx->ms_flag, tcounts, toffs, ctx->ms_info);
+    if (rc) return rc;
+    unsigned long long tot[2] = {0, 0};
+    TL3D_HIP(hipMemcpyAsync(&tot[0], voffs + vchunks, sizeof(tot[0]), hipMemcpyDeviceToHost, ctx->stream));
+    TL3D_HIP(hipMemcpyAsync(&tot[1], toffs + tchunks, sizeof(tot[1]), hipMemcpyDeviceToHost, ctx->stream));
+    TL3D_HIP(hipMemcpyAsync(h, ctx->ms_info, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    TL3D_HIP(hipStreamSynchronize(ctx->stream));
+    *out_n_vert = (int64_t)tot[0];
+    *out_n_tri = (int64_t)tot[1];
+    *out_n_degenerate = (int64_t)h[2];
+    *out_n_duplicate = (int64_t)h[3];
+    if ((int64_t)tot[0] > vert_cap || (int64_t)tot[1] > tri_cap)
+        return set_err(TL3D_E_CAPACITY, "need %llu vertices / %llu triangles, capacities %lld / %lld", tot[0], tot[1], (long long)vert_cap,
+                       (long long)tri_cap);
+    float *oxyz = nullptr;
+    uint8_t *orgb = nullptr;
+    uint32_t *otri = nullptr;
+    rc = st.out(out_xyz, (size_t)tot[0] * 12, &oxyz);
+    if (!rc && rgb) rc = st.out(out_rgb, (size_t)tot[0] * 3, &orgb);
+    if (!rc) rc = st.out(out_tri, (size_t)tot[1] * 12, &otri);
+    if (rc) return rc;
+    rc = launch_ms_write(ctx->stream, cell, o, dxyz, rgb != nullptr, n_vert, ctx->ms_slot, ctx->ms_leader, ctx->ms_vmap, ctx->ms_acc, oxyz, orgb,
+                         tot[0], dtri, n_tri, ctx->ms_flag, toffs, otri, tot[1]);
+    if (!rc && vert_map_out) TL3D_HIP(hipMemcpyAsync(vert_map_out, ctx->ms_vmap, (size_t)n_vert * 4, hipMemcpyDefault, ctx->stream));
     return st.finish(rc, true);
 }
 

@@ -234,6 +234,24 @@ struct tl3d_grid_state {
     unsigned long long *cc_offsets;
     size_t cc_chunks;                       // capacity of both, in entries
     unsigned long long *cc_info;            // [8]: largest index, components, key of the largest component, kept components
+    // tl3d_mesh_simplify_clusters: the vertex table (a 64-bit key and a leader word per slot, a power of
+    // two >= 2 n_vert slots), per vertex its slot and its cluster number, per cluster seven 64-bit sums (n, S, C), the triangle
+    // table (one index per slot, a power of two >= 2 n_tri slots), a class byte per triangle, counts and offsets per chunk, the
+    // report words.  Grid-independent like the cc_ scratch, and here for the same reason.
+    unsigned long long *ms_keys;
+    unsigned *ms_leader;
+    size_t ms_vslots;                       // capacity of both, in slots
+    unsigned *ms_slot, *ms_vmap;
+    unsigned long long *ms_acc;             // [7 per vertex]
+    size_t ms_verts, ms_acc_n;              // capacity of ms_slot / ms_vmap in vertices, of ms_acc in words
+    unsigned *ms_ttab;
+    size_t ms_tslots;
+    uint8_t *ms_flag;
+    size_t ms_tris;
+    unsigned *ms_counts;                    // [vertex chunks + 1][triangle chunks + 1]
+    unsigned long long *ms_offsets;
+    size_t ms_chunks;
+    unsigned long long *ms_info;            // [8]: largest index, vertices without a cell, degenerate, duplicate
     // tl3d_set_block_core: the grid is one block of a lattice of lat[] voxels and emits only what its core (grid.clo / chi) owns
     bool has_core;
     long long lat[3];
@@ -557,6 +575,17 @@ int launch_cc_compact(hipStream_t s, long long min_tri, int largest, const unsig
                       const unsigned *label, const unsigned *count, const unsigned long long *voffsets, const unsigned long long *toffsets,
                       const float *xyz, const uint8_t *rgb, float *out_xyz, uint8_t *out_rgb, unsigned long long vcap, unsigned *out_tri,
                       unsigned long long tcap, unsigned *remap, const unsigned long long *info);
+// vertex clustering (kernels_meshsimplify.hip)
+int launch_ms_validate(hipStream_t s, double cell, const double o[3], const float *xyz, long long n_vert, unsigned long long *info);
+int launch_ms_cluster(hipStream_t s, double cell, const double o[3], const float *xyz, const uint8_t *rgb, long long n_vert,
+                      unsigned long long *keys, unsigned *leader, unsigned long long vcap, unsigned *slot, unsigned *vmap,
+                      unsigned long long *acc, unsigned *vcounts, unsigned long long *voffsets);
+int launch_ms_triangles(hipStream_t s, const unsigned *tri, long long n_tri, const unsigned *vmap, unsigned *ttab, unsigned long long tcap,
+                        uint8_t *flag, unsigned *tcounts, unsigned long long *toffsets, unsigned long long *info);
+int launch_ms_write(hipStream_t s, double cell, const double o[3], const float *xyz, bool colours, long long n_vert, const unsigned *slot,
+                    const unsigned *leader, const unsigned *vmap, const unsigned long long *acc, float *out_xyz, uint8_t *out_rgb,
+                    unsigned long long vcap, const unsigned *tri, long long n_tri, const uint8_t *flag, const unsigned long long *toffsets,
+                    unsigned *out_tri, unsigned long long tcap);
 int sor_mean_distance(tl3d_ctx *ctx, const float *xyz_dev, long long n, int k, double cell, double *mean_dev);
 int sor_run(tl3d_ctx *ctx, const float *xyz_dev, long long n, int k, double std_ratio, double cell, uint8_t *keep_dev, long long *kept);
 

@@ -744,6 +744,30 @@ class FusionContext:
                     keep_vert=keep.astype(bool) if isinstance(keep, np.ndarray) else keep.bool())
         return oxyz[:kv.value], (orgb[:kv.value] if orgb is not None else None), otri[:kt.value], info
 
+    def simplify_mesh(self, xyz, rgb, tris, cell: float, origin=None):
+        """Vertex-clustering simplification of a mesh (needs no grid): the vertices of one cell of
+        size `cell` (metres, on a lattice through `origin`, default (0, 0, 0)) become one vertex at their mean position and
+        colour, numbered in the order of each cell's first vertex; triangles are mapped, the ones that collapse and the repeats
+        of an earlier triangle go, the rest keep their order and winding.  Every cell becomes a vertex, also one no surviving
+        triangle names (filter_mesh(min_triangles=1) drops those).  Same bytes in every run.  rgb may be None.  Returns
+        (xyz, rgb, tris, info); info: clusters, vertices_in, triangles_in, degenerate_dropped, duplicates_dropped and
+        vert_map (u32 [V]: the output vertex of every input vertex)."""
+        xyz, rgb, tris, empty = self._mesh_arrays(xyz, rgb, tris)
+        nv, nt = len(xyz), len(tris)
+        oxyz, otri = empty((nv, 3), np.float32), empty((nt, 3), np.uint32)
+        orgb = empty((nv, 3), np.uint8) if rgb is not None else None
+        vmap = empty((nv,), np.uint32)
+        o = None if origin is None else (C.c_double * 3)(*[float(v) for v in origin])
+        kv, kt, ng, nd = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+
+        def p(a):
+            return abi.ptr(a) if a is not None and len(a) else None
+        abi.check(self._lib.tl3d_mesh_simplify_clusters(self._h, p(xyz), p(rgb), nv, p(tris), nt, float(cell), o, p(oxyz), p(orgb), nv,
+                                                        p(otri), nt, p(vmap), C.byref(kv), C.byref(kt), C.byref(ng), C.byref(nd)))
+        info = dict(clusters=kv.value, vertices_in=nv, triangles_in=nt, degenerate_dropped=ng.value, duplicates_dropped=nd.value,
+                    vert_map=vmap)
+        return oxyz[:kv.value], (orgb[:kv.value] if orgb is not None else None), otri[:kt.value], info
+
     def raycast(self, pose, min_weight: int = 0, z_near=None, z_far=None, slot=None, out=None):
         """Ray-cast the TSDF channel from the camera at pose = (R, t) (world->camera, as integrate):
         (depth f32 [H,W] with 0 = no hit, normals f32 [H,W,3] in the camera frame, bgr u8 [H,W,3]).  z_near / z_far default to

@@ -665,6 +665,10 @@ class DepthToReconstructionPipeline:
                 t0 = clock()
                 vx, vr, vt = self._filter_mesh(ctx, (vx, vr, vt))
                 stage["mesh_filter"] = clock() - t0
+            if self._mesh_simplify_on():                 # after the filter: specks are judged at full resolution
+                t0 = clock()
+                vx, vr, vt = self._simplify_mesh(ctx, (vx, vr, vt))
+                stage["mesh_simplify"] = clock() - t0
             self.mesh = (vx, vr, vt)
             self.stats["mesh_vertices"] = len(vx)
             self.stats["mesh_triangles"] = len(vt)
@@ -856,6 +860,11 @@ class DepthToReconstructionPipeline:
                         self.mesh = self._filter_mesh(ctx, self.mesh)
                         self.stats["mesh_vertices"], self.stats["mesh_triangles"] = len(self.mesh[0]), len(self.mesh[2])
                         self.timings["mesh_filter_s"] = round(time.perf_counter() - t0, 4)
+                    if self._mesh_simplify_on():
+                        t0 = time.perf_counter()
+                        self.mesh = self._simplify_mesh(ctx, self.mesh)
+                        self.stats["mesh_vertices"], self.stats["mesh_triangles"] = len(self.mesh[0]), len(self.mesh[2])
+                        self.timings["mesh_simplify_s"] = round(time.perf_counter() - t0, 4)
                 say(f"\nFinal reconstruction: {len(xyz)} points, {len(self.camera_poses)} cameras")
                 xyz = xyz.astype(np.float64)
         finally:
@@ -899,6 +908,26 @@ class DepthToReconstructionPipeline:
     def _check_mesh_filter_config(self):
         if self._mesh_filter_on() and not self.config.extract_mesh:
             raise ValueError("mesh_min_component_triangles / mesh_largest_component filter the mesh: they need extract_mesh = True")
+        cell = float(getattr(self.config, "mesh_simplify_cell", 0.0))
+        if not np.isfinite(cell) or cell < 0.0:
+            raise ValueError(f"mesh_simplify_cell = {cell}: must be a finite size in metres, or 0 for none")
+        if cell > 0.0 and not self.config.extract_mesh:
+            raise ValueError("mesh_simplify_cell simplifies the mesh: it needs extract_mesh = True")
+
+    def _mesh_simplify_on(self) -> bool:
+        return float(getattr(self.config, "mesh_simplify_cell", 0.0)) > 0.0
+
+    def _simplify_mesh(self, ctx: FusionContext, mesh):
+        """The mesh with the vertices of every cell of config.mesh_simplify_cell merged (FusionContext.simplify_mesh, DESIGN.md
+        section 4.2.2).  The cell lattice goes through (0, 0, 0), so the result does not depend on where grids or blocks were
+        placed; stats["mesh_simplify"] says what was merged and dropped."""
+        cell = float(self.config.mesh_simplify_cell)
+        xyz, rgb, tris, info = ctx.simplify_mesh(*mesh, cell=cell, origin=(0.0, 0.0, 0.0))
+        info.pop("vert_map")
+        self.stats["mesh_simplify"] = dict(info, cell=cell)
+        print(f"  Mesh simplify: cell {cell:g} m, {info['vertices_in']} -> {info['clusters']} vertices, {info['triangles_in']} -> {len(tris)} "
+              f"triangles ({info['degenerate_dropped']} degenerate, {info['duplicates_dropped']} duplicate)")
+        return xyz, rgb, tris
 
     def _filter_mesh(self, ctx: FusionContext, mesh):
         """The mesh without its small connected components (config.mesh_min_component_triangles, mesh_largest_component;
