@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import tl3d
+from extract_reference import record_index
 from helpers import SMALL, small_scene_frames
 from tl3d import _cabi as abi
 from tl3d import pipeline as pl
@@ -38,12 +39,8 @@ def _fuse(ctx, poses):
 
 
 def _xyz_major(rec, dims):
-    """brick-major records -> [nx, ny, nz, ...] (tl3d_internal.h: in_brick_index)"""
-    nx, ny, nz = dims
-    i, j, k = np.meshgrid(np.arange(nx), np.arange(ny), np.arange(nz), indexing="ij")
-    b = ((k >> 3) * (ny // 8) + (j >> 3)) * (nx // 8) + (i >> 3)
-    l = ((k & 4) << 6) | ((j & 4) << 5) | ((i & 4) << 4) | ((k & 3) << 4) | ((j & 3) << 2) | (i & 3)
-    return rec[(b << 9) | l]
+    """brick-major records -> [nx, ny, nz, ...]"""
+    return rec[record_index(dims)]
 
 
 def _sorted_rows(*cols):
