@@ -24,31 +24,6 @@ __global__ __launch_bounds__(256) void u16_to_f32_kernel(const uint16_t *__restr
     if (i < n) out[i] = mm_to_m(in[i]);              // == .astype(float32) / 1000.0 (D2R:90)
 }
 
-// single-block exclusive scan of n block counts -> 64-bit offsets (+ total)
-__global__ __launch_bounds__(1024) void scan_kernel(const unsigned *__restrict__ counts, unsigned long long *__restrict__ offsets,
-                                                    int n, unsigned long long *__restrict__ total) {
-    __shared__ unsigned long long part[1024];
-    const int t = threadIdx.x;
-    const int per = (n + 1023) / 1024;
-    const int lo = t * per, hi = min(n, lo + per);
-    unsigned long long s = 0;
-    for (int i = lo; i < hi; ++i) s += counts[i];
-    part[t] = s;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        unsigned long long v = (t >= off) ? part[t - off] : 0ull;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    unsigned long long run = part[t] - s;          // exclusive prefix of this thread's span
-    for (int i = lo; i < hi; ++i) {
-        offsets[i] = run;
-        run += counts[i];
-    }
-    if (t == 1023) *total = part[1023];
-}
-
 // ---- one-launch back-projection -------------------------------------------------------------------------------
 #ifndef TL3D_BP_SLEEP
 #define TL3D_BP_SLEEP 1                        // x 64 cycles between two polls of a granule
@@ -420,12 +395,6 @@ int launch_bp_fused(hipStream_t s, const Cam &cam, const BpArgs &a, const PoseD 
 int launch_u16_to_f32(hipStream_t s, const uint16_t *in, float *out, size_t n) {
     if (n == 0) return TL3D_OK;
     hipLaunchKernelGGL(u16_to_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, out, n);
-    TL3D_HIP(hipGetLastError());
-    return TL3D_OK;
-}
-
-int launch_scan(hipStream_t s, const unsigned *counts, unsigned long long *offsets, int n, unsigned long long *total) {
-    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, counts, offsets, n, total);
     TL3D_HIP(hipGetLastError());
     return TL3D_OK;
 }

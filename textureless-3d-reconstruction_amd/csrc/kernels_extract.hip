@@ -3,9 +3,9 @@
 //       Open3D voxel_down_sample returns to the reference (depth_to_reconstruction.py:410, 417-418), optionally gated
 //       by the TSDF (weight / |mean tsdf|) as an outlier filter.
 //   mode TL3D_EXTRACT_TSDF: zero crossings of the mean TSDF along the +x,+y,+z voxel edges (no reference code).
-// Two passes (count -> single-block scan -> write) so the output order is deterministic.
+// Two passes (count -> single-block scan -> write: compact.h) so the output order is deterministic.
 // Same fp64 expressions as oracle/tl3d_oracle.c: orc_extract.
-#include "tl3d_internal.h"
+#include "compact.h"
 
 namespace tl3d {
 
@@ -103,17 +103,11 @@ __global__ __launch_bounds__(256) void extract_count_kernel(Grid g, ExtArgs a, c
                                                             unsigned *__restrict__ block_counts) {
     __shared__ unsigned sm[4];
     unsigned cnt = 0;
-    const size_t base = (size_t)blockIdx.x * EXTRACT_CHUNK;
-#pragma unroll 1
-    for (int it = 0; it < EXTRACT_CHUNK / 256; ++it) {
-        const size_t idx = base + (size_t)it * 256 + threadIdx.x;
+    for_chunk([&](size_t idx) {
         if (idx < nvox) cnt += (unsigned)extract_record<false>(g, a, tsdf, cen, idx, nullptr, nullptr, 0, 0);
-    }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) cnt += __shfl_down(cnt, d);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) block_counts[blockIdx.x] = sm[0] + sm[1] + sm[2] + sm[3];
+    });
+    cnt = block_sum(cnt, sm);
+    if (threadIdx.x == 0) block_counts[blockIdx.x] = cnt;
 }
 
 __global__ __launch_bounds__(256) void extract_write_kernel(Grid g, ExtArgs a, const int2 *__restrict__ tsdf,
@@ -121,29 +115,9 @@ __global__ __launch_bounds__(256) void extract_write_kernel(Grid g, ExtArgs a, c
                                                             const unsigned long long *__restrict__ offsets,
                                                             float *__restrict__ xyz, uint8_t *__restrict__ rgb,
                                                             unsigned long long cap) {
-    __shared__ unsigned sm[4];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    unsigned long long run = offsets[blockIdx.x];
-    const size_t base = (size_t)blockIdx.x * EXTRACT_CHUNK;
-#pragma unroll 1
-    for (int it = 0; it < EXTRACT_CHUNK / 256; ++it) {
-        const size_t idx = base + (size_t)it * 256 + threadIdx.x;
-        const unsigned c = (idx < nvox) ? (unsigned)extract_record<false>(g, a, tsdf, cen, idx, nullptr, nullptr, 0, 0) : 0u;
-        unsigned inc = c;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned tv = __shfl_up(inc, d);
-            if (lane >= d) inc += tv;
-        }
-        if (lane == 63) sm[wid] = inc;
-        __syncthreads();
-        unsigned wbase = 0;
-        for (int w = 0; w < wid; ++w) wbase += sm[w];
-        const unsigned total = sm[0] + sm[1] + sm[2] + sm[3];
-        __syncthreads();
-        if (c) extract_record<true>(g, a, tsdf, cen, idx, xyz, rgb, run + wbase + (inc - c), cap);
-        run += total;
-    }
+    compact_chunk(
+        nvox, offsets, [&](size_t idx) { return (unsigned)extract_record<false>(g, a, tsdf, cen, idx, nullptr, nullptr, 0, 0); },
+        [&](size_t idx, unsigned long long o, unsigned) { extract_record<true>(g, a, tsdf, cen, idx, xyz, rgb, o, cap); });
 }
 
 int launch_extract_count(hipStream_t s, const Grid &g, int mode, int min_count, int min_weight, double max_abs,

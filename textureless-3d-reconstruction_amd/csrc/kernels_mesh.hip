@@ -4,11 +4,11 @@
 //   vertex: one per voxel edge (v, v + e_axis) whose ends are both usable and differ in inside-ness, owned by v; position and
 //       colour are extract_record's TSDF-mode expressions; order: owner record order, then axis x, y, z.
 //   cell:  the cube whose lowest corner is v; meshed iff its 8 corners are usable and not all alike (mc_tables.h).
-// Three passes over the records in chunks of EXTRACT_CHUNK, the extraction skeleton (block counts -> single-block scan -> in-block
-// wave scan for the write offsets): count (vertices and triangles), write vertices (and each owner's first vertex id into a u32
+// Three passes over the records in chunks of EXTRACT_CHUNK on the compaction of compact.h (block counts -> single-block scan ->
+// in-block wave scan for the write offsets): count (vertices and triangles), write vertices (and each owner's first vertex id into a u32
 // scratch indexed like the TSDF pool: slot * 512 + in_brick), write triangles (edge -> owner -> first id + rank of the edge's axis
 // among the owner's crossing axes).
-#include "tl3d_internal.h"
+#include "compact.h"
 
 #define MC_CONST static __device__ const
 #include "mc_tables.h"
@@ -66,50 +66,18 @@ __device__ __forceinline__ void analyse(const Grid &g, const MeshArgs &a, const 
 
 __device__ __forceinline__ unsigned tri_count(unsigned cas) { return MC_TRI_COUNT[cas]; }
 
-// block total of c over the 256 threads (every thread must call)
-__device__ __forceinline__ unsigned block_sum(unsigned c, unsigned *sm) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) c += __shfl_down(c, d);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = c;
-    __syncthreads();
-    const unsigned s = sm[0] + sm[1] + sm[2] + sm[3];
-    __syncthreads();
-    return s;
-}
-
-// exclusive prefix of c over the block (thread order = record order inside one iteration) and the block's total
-__device__ __forceinline__ unsigned block_excl(unsigned c, unsigned *sm, unsigned &total) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    unsigned inc = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned tv = __shfl_up(inc, d);
-        if (lane >= d) inc += tv;
-    }
-    if (lane == 63) sm[wid] = inc;
-    __syncthreads();
-    unsigned wbase = 0;
-    for (int w = 0; w < wid; ++w) wbase += sm[w];
-    total = sm[0] + sm[1] + sm[2] + sm[3];
-    __syncthreads();
-    return wbase + inc - c;
-}
-
 __global__ __launch_bounds__(256) void mesh_count_kernel(Grid g, MeshArgs a, const int2 *__restrict__ tsdf, size_t nvox,
                                                          unsigned *__restrict__ vcounts, unsigned *__restrict__ tcounts) {
     __shared__ unsigned sm[4];
     unsigned nv = 0, nt = 0;
-    const size_t base = (size_t)blockIdx.x * EXTRACT_CHUNK;
-#pragma unroll 1
-    for (int it = 0; it < EXTRACT_CHUNK / 256; ++it) {
-        const size_t idx = base + (size_t)it * 256 + threadIdx.x;
+    for_chunk([&](size_t idx) {
         if (idx < nvox) {
             RecInfo r;
             analyse(g, a, tsdf, idx, r);
             nv += (unsigned)__popc(r.vmask);
             nt += tri_count(r.cas);
         }
-    }
+    });
     nv = block_sum(nv, sm);
     nt = block_sum(nt, sm);
     if (threadIdx.x == 0) {
@@ -123,22 +91,16 @@ __global__ __launch_bounds__(256) void mesh_vert_kernel(Grid g, MeshArgs a, cons
                                                         const unsigned long long *__restrict__ offsets, unsigned *__restrict__ first_id,
                                                         float *__restrict__ xyz, uint8_t *__restrict__ rgb, unsigned long long cap,
                                                         long long *__restrict__ keys) {
-    __shared__ unsigned sm[4];
-    unsigned long long run = offsets[blockIdx.x];
-    const size_t base = (size_t)blockIdx.x * EXTRACT_CHUNK;
     const double org[3] = {g.oxd, g.oyd, g.ozd};
     const double off[3] = {g.offx, g.offy, g.offz};
-#pragma unroll 1
-    for (int it = 0; it < EXTRACT_CHUNK / 256; ++it) {
-        const size_t idx = base + (size_t)it * 256 + threadIdx.x;
-        RecInfo r;
-        r.vmask = 0;
-        if (idx < nvox) analyse(g, a, tsdf, idx, r);
-        const unsigned c = (unsigned)__popc(r.vmask);
-        unsigned total;
-        const unsigned ex = block_excl(c, sm, total);
-        if (c) {
-            const unsigned long long o = run + ex;
+    RecInfo r;                                                     // of the element at hand: filled by the count step, read by the emit step
+    compact_chunk(
+        nvox, offsets,
+        [&](size_t idx) {
+            analyse(g, a, tsdf, idx, r);
+            return (unsigned)__popc(r.vmask);
+        },
+        [&](size_t idx, unsigned long long o, unsigned) {
             const unsigned slot = brick_slot(g.tsdf_tab, (unsigned)(idx >> 9));
             if (slot < SLOT_FULL) first_id[((size_t)slot << 9) | (idx & 511)] = (unsigned)o;
             const int ijk[3] = {r.i, r.j, r.k};
@@ -174,9 +136,7 @@ __global__ __launch_bounds__(256) void mesh_vert_kernel(Grid g, MeshArgs a, cons
                 }
                 rgb[3 * oo + 0] = col[0]; rgb[3 * oo + 1] = col[1]; rgb[3 * oo + 2] = col[2];
             }
-        }
-        run += total;
-    }
+        });
 }
 
 // id of the vertex on edge e (mc_tables.h numbering) of the meshed cell of r: owner corner co, axis ax; the owner's vertices
@@ -214,28 +174,22 @@ __global__ __launch_bounds__(256) void mesh_tri_kernel(Grid g, MeshArgs a, const
                                                        const unsigned long long *__restrict__ offsets,
                                                        const unsigned *__restrict__ first_id, unsigned *__restrict__ tris,
                                                        unsigned long long cap) {
-    __shared__ unsigned sm[4];
-    unsigned long long run = offsets[blockIdx.x];
-    const size_t base = (size_t)blockIdx.x * EXTRACT_CHUNK;
+    RecInfo r;                                                     // as in mesh_vert_kernel
+    compact_chunk(
+        nvox, offsets,
+        [&](size_t idx) {
+            analyse(g, a, tsdf, idx, r);
+            return tri_count(r.cas);
+        },
+        [&](size_t, unsigned long long o, unsigned c) {
 #pragma unroll 1
-    for (int it = 0; it < EXTRACT_CHUNK / 256; ++it) {
-        const size_t idx = base + (size_t)it * 256 + threadIdx.x;
-        RecInfo r;
-        r.cas = 0;
-        if (idx < nvox) analyse(g, a, tsdf, idx, r);
-        const unsigned c = tri_count(r.cas);
-        unsigned total;
-        const unsigned ex = block_excl(c, sm, total);
-        const unsigned long long o = run + ex;
-#pragma unroll 1
-        for (unsigned t = 0; t < c; ++t) {
-            if (o + t >= cap) break;
+            for (unsigned t = 0; t < c; ++t) {
+                if (o + t >= cap) break;
 #pragma unroll
-            for (int v = 0; v < 3; ++v)
-                tris[3 * (o + t) + v] = edge_vertex(g, a, tsdf, first_id, r, MC_TRI_EDGES[r.cas][3 * t + v]);
-        }
-        run += total;
-    }
+                for (int v = 0; v < 3; ++v)
+                    tris[3 * (o + t) + v] = edge_vertex(g, a, tsdf, first_id, r, MC_TRI_EDGES[r.cas][3 * t + v]);
+            }
+        });
 }
 
 static MeshArgs mesh_args(const Grid &g, int min_weight, const long long *lat = nullptr) {

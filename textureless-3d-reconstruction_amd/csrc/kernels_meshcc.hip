@@ -13,7 +13,7 @@
 //   flatten   parent[v] = find(v): from here on parent IS the label array
 //   count     tri_count[label] += 1, aggregated per wave
 //   roots     number of components, largest component as one 64-bit max of (count << 32 | ~label): ties go to the smaller label
-//   compact   kept vertices / triangles per chunk -> single-block scan -> order-preserving writes (the extraction skeleton)
+//   compact   kept vertices / triangles per chunk -> single-block scan -> order-preserving writes (compact.h)
 //
 // Proof obligations of the union-find (hook and flatten).  Each line is kept by every statement that touches `parent`:
 //   I1  parent[v] <= v, always.                         init writes v; hook CASes a root r from r to a value < r; halving and flatten
@@ -28,11 +28,9 @@
 //   I5  no thread waits for another thread's store.     no flags, no polls, no spin loops; a CAS that fails is answered by walking on.
 //   I6  the smaller root always wins.                   the smallest index m of a component has parent[m] = m for ever (I1 + I3), so
 //                                                       when every triangle's unites are done the one root left is m.
-#include "tl3d_internal.h"
+#include "compact.h"
 
 namespace tl3d {
-
-constexpr int CC_CHUNK = EXTRACT_CHUNK;          // elements per block in the compaction passes
 
 __device__ __forceinline__ unsigned cc_load(const unsigned *p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -141,44 +139,13 @@ __device__ __forceinline__ bool cc_kept(const CcKeep &k, unsigned l, unsigned cn
     return !k.largest || (cnt > 0 && l == 0xFFFFFFFFu - (unsigned)k.info[2]);
 }
 
-__device__ __forceinline__ unsigned cc_block_sum(unsigned c, unsigned *sm) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) c += __shfl_down(c, d);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = c;
-    __syncthreads();
-    const unsigned s = sm[0] + sm[1] + sm[2] + sm[3];
-    __syncthreads();
-    return s;
-}
-
-// exclusive prefix of c over the block (thread order = element order inside one iteration) and the block's total
-__device__ __forceinline__ unsigned cc_block_excl(unsigned c, unsigned *sm, unsigned &total) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    unsigned inc = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned tv = __shfl_up(inc, d);
-        if (lane >= d) inc += tv;
-    }
-    if (lane == 63) sm[wid] = inc;
-    __syncthreads();
-    unsigned wbase = 0;
-    for (int w = 0; w < wid; ++w) wbase += sm[w];
-    total = sm[0] + sm[1] + sm[2] + sm[3];
-    __syncthreads();
-    return wbase + inc - c;
-}
-
 // kept vertices per chunk, the caller's keep mask, and info[3] += kept components
 __global__ __launch_bounds__(256) void cc_vert_count_kernel(CcKeep k, const unsigned *__restrict__ label, const unsigned *__restrict__ count,
                                                             unsigned n, unsigned *__restrict__ chunk_counts, uint8_t *__restrict__ keep_out,
                                                             unsigned long long *__restrict__ info) {
     __shared__ unsigned sm[4];
     unsigned nv = 0, nc = 0;
-    const unsigned long long base = (unsigned long long)blockIdx.x * CC_CHUNK;
-#pragma unroll 1
-    for (int it = 0; it < CC_CHUNK / 256; ++it) {
-        const unsigned long long v = base + (unsigned long long)it * 256 + threadIdx.x;
+    for_chunk([&](unsigned long long v) {
         if (v < n) {
             const unsigned l = label[v];
             const bool keep = cc_kept(k, l, count[l]);
@@ -186,9 +153,9 @@ __global__ __launch_bounds__(256) void cc_vert_count_kernel(CcKeep k, const unsi
             nc += keep && l == (unsigned)v ? 1u : 0u;
             if (keep_out) keep_out[v] = keep ? 1 : 0;
         }
-    }
-    nv = cc_block_sum(nv, sm);
-    nc = cc_block_sum(nc, sm);
+    });
+    nv = block_sum(nv, sm);
+    nc = block_sum(nc, sm);
     if (threadIdx.x == 0) {
         chunk_counts[blockIdx.x] = nv;
         if (nc) atomicAdd(info + 3, (unsigned long long)nc);
@@ -200,16 +167,13 @@ __global__ __launch_bounds__(256) void cc_tri_count_kernel(CcKeep k, const unsig
                                                            unsigned *__restrict__ chunk_counts) {
     __shared__ unsigned sm[4];
     unsigned nt = 0;
-    const unsigned long long base = (unsigned long long)blockIdx.x * CC_CHUNK;
-#pragma unroll 1
-    for (int it = 0; it < CC_CHUNK / 256; ++it) {
-        const unsigned long long t = base + (unsigned long long)it * 256 + threadIdx.x;
+    for_chunk([&](unsigned long long t) {
         if (t < n_tri) {
             const unsigned l = label[tri[3 * t]];
             nt += cc_kept(k, l, count[l]) ? 1u : 0u;
         }
-    }
-    nt = cc_block_sum(nt, sm);
+    });
+    nt = block_sum(nt, sm);
     if (threadIdx.x == 0) chunk_counts[blockIdx.x] = nt;
 }
 
@@ -219,63 +183,43 @@ __global__ __launch_bounds__(256) void cc_vert_write_kernel(CcKeep k, const unsi
                                                             const float *__restrict__ xyz, const uint8_t *__restrict__ rgb,
                                                             float *__restrict__ out_xyz, uint8_t *__restrict__ out_rgb, unsigned long long cap,
                                                             unsigned *__restrict__ remap) {
-    __shared__ unsigned sm[4];
-    unsigned long long run = offsets[blockIdx.x];
-    const unsigned long long base = (unsigned long long)blockIdx.x * CC_CHUNK;
-#pragma unroll 1
-    for (int it = 0; it < CC_CHUNK / 256; ++it) {
-        const unsigned long long v = base + (unsigned long long)it * 256 + threadIdx.x;
-        bool keep = false;
-        if (v < n) {
+    compact_chunk(
+        n, offsets,
+        [&](unsigned long long v) {
             const unsigned l = label[v];
-            keep = cc_kept(k, l, count[l]);
-        }
-        unsigned total;
-        const unsigned ex = cc_block_excl(keep ? 1u : 0u, sm, total);
-        const unsigned long long o = run + ex;
-        if (keep && o < cap) {
+            return cc_kept(k, l, count[l]) ? 1u : 0u;
+        },
+        [&](unsigned long long v, unsigned long long o, unsigned) {
+            if (o >= cap) return;
             remap[v] = (unsigned)o;
             out_xyz[3 * o + 0] = xyz[3 * v + 0]; out_xyz[3 * o + 1] = xyz[3 * v + 1]; out_xyz[3 * o + 2] = xyz[3 * v + 2];
             if (rgb) { out_rgb[3 * o + 0] = rgb[3 * v + 0]; out_rgb[3 * o + 1] = rgb[3 * v + 1]; out_rgb[3 * o + 2] = rgb[3 * v + 2]; }
-        }
-        run += total;
-    }
+        });
 }
 
 __global__ __launch_bounds__(256) void cc_tri_write_kernel(CcKeep k, const unsigned *__restrict__ tri, unsigned long long n_tri,
                                                            const unsigned *__restrict__ label, const unsigned *__restrict__ count,
                                                            const unsigned long long *__restrict__ offsets, const unsigned *__restrict__ remap,
                                                            unsigned *__restrict__ out_tri, unsigned long long cap) {
-    __shared__ unsigned sm[4];
-    unsigned long long run = offsets[blockIdx.x];
-    const unsigned long long base = (unsigned long long)blockIdx.x * CC_CHUNK;
-#pragma unroll 1
-    for (int it = 0; it < CC_CHUNK / 256; ++it) {
-        const unsigned long long t = base + (unsigned long long)it * 256 + threadIdx.x;
-        bool keep = false;
-        unsigned a = 0, b = 0, c = 0;
-        if (t < n_tri) {
+    unsigned a = 0, b = 0, c = 0;                // of the triangle at hand: read by the count step, mapped by the emit step
+    compact_chunk(
+        n_tri, offsets,
+        [&](unsigned long long t) {
             a = tri[3 * t]; b = tri[3 * t + 1]; c = tri[3 * t + 2];
             const unsigned l = label[a];
-            keep = cc_kept(k, l, count[l]);
-        }
-        unsigned total;
-        const unsigned ex = cc_block_excl(keep ? 1u : 0u, sm, total);
-        const unsigned long long o = run + ex;
-        if (keep && o < cap) {                   // a kept triangle's vertices are kept: their remap entries were written
+            return cc_kept(k, l, count[l]) ? 1u : 0u;
+        },
+        [&](unsigned long long, unsigned long long o, unsigned) {
+            if (o >= cap) return;                // a kept triangle's vertices are kept: their remap entries were written
             out_tri[3 * o + 0] = remap[a]; out_tri[3 * o + 1] = remap[b]; out_tri[3 * o + 2] = remap[c];
-        }
-        run += total;
-    }
+        });
 }
-
-static inline unsigned cc_blocks(unsigned long long n, unsigned per) { return (unsigned)((n + per - 1) / per); }
 
 // info[0] (a u32 word) = the largest index of tri[0, 3 * n_tri); the caller zeroed it
 int launch_cc_validate(hipStream_t s, const unsigned *tri, long long n_tri, unsigned long long *info) {
     if (n_tri <= 0) return TL3D_OK;
     const unsigned long long n = 3ull * (unsigned long long)n_tri;
-    unsigned blocks = cc_blocks(n, 256 * 8);
+    unsigned blocks = blocks_of(n, 256 * 8);
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(cc_validate_kernel, dim3(blocks), dim3(256), 0, s, tri, n, (unsigned *)info);
     TL3D_HIP(hipGetLastError());
@@ -286,7 +230,7 @@ int launch_cc_validate(hipStream_t s, const unsigned *tri, long long n_tri, unsi
 int launch_cc_label(hipStream_t s, const unsigned *tri, long long n_tri, long long n_vert, unsigned *parent, unsigned *count,
                     unsigned long long *info) {
     if (n_vert <= 0) return TL3D_OK;
-    const unsigned nv = (unsigned)n_vert, vb = cc_blocks((unsigned long long)n_vert, 256), tb = cc_blocks((unsigned long long)n_tri, 256);
+    const unsigned nv = (unsigned)n_vert, vb = blocks_of((unsigned long long)n_vert, 256), tb = blocks_of((unsigned long long)n_tri, 256);
     hipLaunchKernelGGL(cc_init_kernel, dim3(vb), dim3(256), 0, s, parent, count, nv);
     TL3D_HIP(hipGetLastError());
     if (n_tri > 0) {
@@ -310,12 +254,12 @@ int launch_cc_keep_count(hipStream_t s, long long min_tri, int largest, const un
                          unsigned long long *info) {
     const CcKeep k = cc_keep(min_tri, largest, info);
     if (n_vert > 0) {
-        hipLaunchKernelGGL(cc_vert_count_kernel, dim3(cc_blocks((unsigned long long)n_vert, CC_CHUNK)), dim3(256), 0, s, k, label, count,
+        hipLaunchKernelGGL(cc_vert_count_kernel, dim3(chunks_of(n_vert)), dim3(256), 0, s, k, label, count,
                            (unsigned)n_vert, vcounts, keep_out, info);
         TL3D_HIP(hipGetLastError());
     }
     if (n_tri > 0) {
-        hipLaunchKernelGGL(cc_tri_count_kernel, dim3(cc_blocks((unsigned long long)n_tri, CC_CHUNK)), dim3(256), 0, s, k, tri,
+        hipLaunchKernelGGL(cc_tri_count_kernel, dim3(chunks_of(n_tri)), dim3(256), 0, s, k, tri,
                            (unsigned long long)n_tri, label, count, tcounts);
         TL3D_HIP(hipGetLastError());
     }
@@ -328,12 +272,12 @@ int launch_cc_compact(hipStream_t s, long long min_tri, int largest, const unsig
                       unsigned long long tcap, unsigned *remap, const unsigned long long *info) {
     const CcKeep k = cc_keep(min_tri, largest, info);
     if (n_vert > 0 && vcap > 0) {
-        hipLaunchKernelGGL(cc_vert_write_kernel, dim3(cc_blocks((unsigned long long)n_vert, CC_CHUNK)), dim3(256), 0, s, k, label, count,
+        hipLaunchKernelGGL(cc_vert_write_kernel, dim3(chunks_of(n_vert)), dim3(256), 0, s, k, label, count,
                            (unsigned)n_vert, voffsets, xyz, rgb, out_xyz, out_rgb, vcap, remap);
         TL3D_HIP(hipGetLastError());
     }
     if (n_tri > 0 && tcap > 0) {
-        hipLaunchKernelGGL(cc_tri_write_kernel, dim3(cc_blocks((unsigned long long)n_tri, CC_CHUNK)), dim3(256), 0, s, k, tri,
+        hipLaunchKernelGGL(cc_tri_write_kernel, dim3(chunks_of(n_tri)), dim3(256), 0, s, k, tri,
                            (unsigned long long)n_tri, label, count, toffsets, remap, out_tri, tcap);
         TL3D_HIP(hipGetLastError());
     }

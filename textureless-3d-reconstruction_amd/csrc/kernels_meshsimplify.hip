@@ -14,7 +14,8 @@
 //                 before the host has looked at both
 //   insert        one thread per vertex: its key into the vertex table (64-bit CAS EMPTY -> key, linear probing), slot[v] = where
 //                 it sits, atomicMin(leader[slot], v)
-//   leaders       leader[slot[v]] == v per chunk -> single-block scan -> vert_map[leader] = cluster number, in order
+//   leaders       leader[slot[v]] == v per chunk -> single-block scan -> vert_map[leader] = cluster number, in order (compact.h,
+//                 as the triangle classes and the triangle write below)
 //   accumulate    one thread per vertex: vert_map[v] = vert_map[leader], atomicAdd of 1, q and rgb into the cluster's seven words
 //   tri insert    one thread per triangle: map, and unless degenerate its index into the triangle table (32-bit CAS EMPTY -> t, or
 //                 atomicMin into a slot whose occupant has the same canonical triple)
@@ -37,11 +38,10 @@
 //                                                       value it returned and probing on.
 //   H6  WHICH slot a key or a triple lands in may       nothing that is written out depends on a slot index: slots are only
 //       differ from run to run.                         compared for what they hold (leader, smallest triangle index).
-#include "tl3d_internal.h"
+#include "compact.h"
 
 namespace tl3d {
 
-constexpr int MS_CHUNK = EXTRACT_CHUNK;          // elements per block in the compaction passes
 constexpr unsigned long long MS_EMPTY_KEY = ~0ull;       // bit 63 set: no key (63 bits) equals it
 constexpr unsigned MS_EMPTY = 0xFFFFFFFFu;               // no vertex index (< 2^31) and no triangle index (< 2^32 - 1) equals it
 constexpr double MS_Q = 16777216.0;                      // 2^24 steps per cell
@@ -73,34 +73,6 @@ __device__ __forceinline__ unsigned long long ms_mix(unsigned long long x) {
     x ^= x >> 33; x *= 0xC4CEB9FE1A85EC53ull;
     x ^= x >> 33;
     return x;
-}
-
-__device__ __forceinline__ unsigned ms_block_sum(unsigned c, unsigned *sm) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) c += __shfl_down(c, d);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = c;
-    __syncthreads();
-    const unsigned s = sm[0] + sm[1] + sm[2] + sm[3];
-    __syncthreads();
-    return s;
-}
-
-// exclusive prefix of c over the block (thread order = element order inside one iteration) and the block's total
-__device__ __forceinline__ unsigned ms_block_excl(unsigned c, unsigned *sm, unsigned &total) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    unsigned inc = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned tv = __shfl_up(inc, d);
-        if (lane >= d) inc += tv;
-    }
-    if (lane == 63) sm[wid] = inc;
-    __syncthreads();
-    unsigned wbase = 0;
-    for (int w = 0; w < wid; ++w) wbase += sm[w];
-    total = sm[0] + sm[1] + sm[2] + sm[3];
-    __syncthreads();
-    return wbase + inc - c;
 }
 
 // info[1] += vertices without a cell
@@ -143,31 +115,19 @@ __global__ __launch_bounds__(256) void ms_leader_count_kernel(const unsigned *__
                                                               unsigned *__restrict__ chunk_counts) {
     __shared__ unsigned sm[4];
     unsigned c = 0;
-    const unsigned long long base = (unsigned long long)blockIdx.x * MS_CHUNK;
-#pragma unroll 1
-    for (int it = 0; it < MS_CHUNK / 256; ++it) {
-        const unsigned long long v = base + (unsigned long long)it * 256 + threadIdx.x;
+    for_chunk([&](unsigned long long v) {
         if (v < n) c += leader[slot[v]] == (unsigned)v ? 1u : 0u;
-    }
-    c = ms_block_sum(c, sm);
+    });
+    c = block_sum(c, sm);
     if (threadIdx.x == 0) chunk_counts[blockIdx.x] = c;
 }
 
 // vert_map[leader] = its cluster's number: leaders in index order
 __global__ __launch_bounds__(256) void ms_leader_write_kernel(const unsigned *__restrict__ slot, const unsigned *__restrict__ leader, unsigned n,
                                                               const unsigned long long *__restrict__ offsets, unsigned *__restrict__ vmap) {
-    __shared__ unsigned sm[4];
-    unsigned long long run = offsets[blockIdx.x];
-    const unsigned long long base = (unsigned long long)blockIdx.x * MS_CHUNK;
-#pragma unroll 1
-    for (int it = 0; it < MS_CHUNK / 256; ++it) {
-        const unsigned long long v = base + (unsigned long long)it * 256 + threadIdx.x;
-        const bool lead = v < n && leader[slot[v]] == (unsigned)v;
-        unsigned total;
-        const unsigned ex = ms_block_excl(lead ? 1u : 0u, sm, total);
-        if (lead) vmap[v] = (unsigned)(run + ex);
-        run += total;
-    }
+    compact_chunk(
+        n, offsets, [&](unsigned long long v) { return leader[slot[v]] == (unsigned)v ? 1u : 0u; },
+        [&](unsigned long long v, unsigned long long o, unsigned) { vmap[v] = (unsigned)o; });
 }
 
 // acc[7 c ..] += (1, qx, qy, qz, r, g, b) of every member of cluster c; vert_map of the members that are no leaders.  A leader's
@@ -285,10 +245,7 @@ __global__ __launch_bounds__(256) void ms_tri_count_kernel(const unsigned *__res
                                                            unsigned *__restrict__ chunk_counts, unsigned long long *__restrict__ info) {
     __shared__ unsigned sm[4];
     unsigned ns = 0, ng = 0, nd = 0;
-    const unsigned long long base = (unsigned long long)blockIdx.x * MS_CHUNK;
-#pragma unroll 1
-    for (int it = 0; it < MS_CHUNK / 256; ++it) {
-        const unsigned long long t = base + (unsigned long long)it * 256 + threadIdx.x;
+    for_chunk([&](unsigned long long t) {
         if (t < n_tri) {
             const uint8_t f = ms_classify(tri, vmap, t, ttab, mask);
             flag[t] = f;
@@ -296,10 +253,10 @@ __global__ __launch_bounds__(256) void ms_tri_count_kernel(const unsigned *__res
             ng += f == MS_DEGENERATE ? 1u : 0u;
             nd += f == MS_DUPLICATE ? 1u : 0u;
         }
-    }
-    ns = ms_block_sum(ns, sm);
-    ng = ms_block_sum(ng, sm);
-    nd = ms_block_sum(nd, sm);
+    });
+    ns = block_sum(ns, sm);
+    ng = block_sum(ng, sm);
+    nd = block_sum(nd, sm);
     if (threadIdx.x == 0) {
         chunk_counts[blockIdx.x] = ns;
         if (ng) atomicAdd(info + 2, (unsigned long long)ng);
@@ -312,30 +269,20 @@ __global__ __launch_bounds__(256) void ms_tri_write_kernel(const unsigned *__res
                                                            const unsigned *__restrict__ vmap, const uint8_t *__restrict__ flag,
                                                            const unsigned long long *__restrict__ offsets, unsigned *__restrict__ out_tri,
                                                            unsigned long long cap) {
-    __shared__ unsigned sm[4];
-    unsigned long long run = offsets[blockIdx.x];
-    const unsigned long long base = (unsigned long long)blockIdx.x * MS_CHUNK;
-#pragma unroll 1
-    for (int it = 0; it < MS_CHUNK / 256; ++it) {
-        const unsigned long long t = base + (unsigned long long)it * 256 + threadIdx.x;
-        const bool keep = t < n_tri && flag[t] == MS_SURVIVOR;
-        unsigned total;
-        const unsigned ex = ms_block_excl(keep ? 1u : 0u, sm, total);
-        const unsigned long long o = run + ex;
-        if (keep && o < cap) {
+    compact_chunk(
+        n_tri, offsets, [&](unsigned long long t) { return flag[t] == MS_SURVIVOR ? 1u : 0u; },
+        [&](unsigned long long t, unsigned long long o, unsigned) {
+            if (o >= cap) return;
             out_tri[3 * o + 0] = vmap[tri[3 * t]]; out_tri[3 * o + 1] = vmap[tri[3 * t + 1]]; out_tri[3 * o + 2] = vmap[tri[3 * t + 2]];
-        }
-        run += total;
-    }
+        });
 }
 
-static inline unsigned ms_blocks(unsigned long long n, unsigned per) { return (unsigned)((n + per - 1) / per); }
 static MsCell ms_cell(double cell, const double o[3]) { return MsCell{cell, {o[0], o[1], o[2]}}; }
 
 // info[1] = the number of vertices that are not finite or lie beyond 2^20 cells (the caller zeroed it)
 int launch_ms_validate(hipStream_t s, double cell, const double o[3], const float *xyz, long long n_vert, unsigned long long *info) {
     if (n_vert <= 0) return TL3D_OK;
-    hipLaunchKernelGGL(ms_validate_kernel, dim3(ms_blocks((unsigned long long)n_vert, 256)), dim3(256), 0, s, ms_cell(cell, o), xyz,
+    hipLaunchKernelGGL(ms_validate_kernel, dim3(blocks_of((unsigned long long)n_vert, 256)), dim3(256), 0, s, ms_cell(cell, o), xyz,
                        (unsigned)n_vert, info);
     TL3D_HIP(hipGetLastError());
     return TL3D_OK;
@@ -348,7 +295,7 @@ int launch_ms_cluster(hipStream_t s, double cell, const double o[3], const float
                       unsigned long long *acc, unsigned *vcounts, unsigned long long *voffsets) {
     if (n_vert <= 0) return TL3D_OK;
     const MsCell g = ms_cell(cell, o);
-    const unsigned nv = (unsigned)n_vert, vb = ms_blocks((unsigned long long)n_vert, 256), vchunks = ms_blocks((unsigned long long)n_vert, MS_CHUNK);
+    const unsigned nv = (unsigned)n_vert, vb = blocks_of((unsigned long long)n_vert, 256), vchunks = chunks_of(n_vert);
     hipLaunchKernelGGL(ms_insert_kernel, dim3(vb), dim3(256), 0, s, g, xyz, nv, keys, leader, vcap - 1, slot);
     TL3D_HIP(hipGetLastError());
     hipLaunchKernelGGL(ms_leader_count_kernel, dim3(vchunks), dim3(256), 0, s, slot, leader, nv, vcounts);
@@ -366,9 +313,9 @@ int launch_ms_cluster(hipStream_t s, double cell, const double o[3], const float
 // info[2] / info[3] = degenerate / duplicate
 int launch_ms_triangles(hipStream_t s, const unsigned *tri, long long n_tri, const unsigned *vmap, unsigned *ttab, unsigned long long tcap,
                         uint8_t *flag, unsigned *tcounts, unsigned long long *toffsets, unsigned long long *info) {
-    const unsigned tchunks = ms_blocks((unsigned long long)(n_tri > 0 ? n_tri : 0), MS_CHUNK);
+    const unsigned tchunks = chunks_of(n_tri > 0 ? n_tri : 0);
     if (n_tri > 0) {
-        hipLaunchKernelGGL(ms_tri_insert_kernel, dim3(ms_blocks((unsigned long long)n_tri, 256)), dim3(256), 0, s, tri, (unsigned long long)n_tri,
+        hipLaunchKernelGGL(ms_tri_insert_kernel, dim3(blocks_of((unsigned long long)n_tri, 256)), dim3(256), 0, s, tri, (unsigned long long)n_tri,
                            vmap, ttab, tcap - 1);
         TL3D_HIP(hipGetLastError());
         hipLaunchKernelGGL(ms_tri_count_kernel, dim3(tchunks), dim3(256), 0, s, tri, (unsigned long long)n_tri, vmap, ttab, tcap - 1, flag,
@@ -383,12 +330,12 @@ int launch_ms_write(hipStream_t s, double cell, const double o[3], const float *
                     unsigned long long vcap, const unsigned *tri, long long n_tri, const uint8_t *flag, const unsigned long long *toffsets,
                     unsigned *out_tri, unsigned long long tcap) {
     if (n_vert > 0 && vcap > 0) {
-        hipLaunchKernelGGL(ms_vert_write_kernel, dim3(ms_blocks((unsigned long long)n_vert, 256)), dim3(256), 0, s, ms_cell(cell, o), xyz, colours,
+        hipLaunchKernelGGL(ms_vert_write_kernel, dim3(blocks_of((unsigned long long)n_vert, 256)), dim3(256), 0, s, ms_cell(cell, o), xyz, colours,
                            (unsigned)n_vert, slot, leader, vmap, acc, out_xyz, out_rgb, vcap);
         TL3D_HIP(hipGetLastError());
     }
     if (n_tri > 0 && tcap > 0) {
-        hipLaunchKernelGGL(ms_tri_write_kernel, dim3(ms_blocks((unsigned long long)n_tri, MS_CHUNK)), dim3(256), 0, s, tri, (unsigned long long)n_tri,
+        hipLaunchKernelGGL(ms_tri_write_kernel, dim3(chunks_of(n_tri)), dim3(256), 0, s, tri, (unsigned long long)n_tri,
                            vmap, flag, toffsets, out_tri, tcap);
         TL3D_HIP(hipGetLastError());
     }

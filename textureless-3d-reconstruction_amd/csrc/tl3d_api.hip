@@ -187,6 +187,24 @@ template <class A, class B> static int grow_pair(A **a, B **b, size_t *cap, size
     return rc;
 }
 
+// A counts / offsets pair of the compaction (compact.h), cut into its halves: [n[0] chunks + 1] for the vertices (or the points),
+// then [n[1] chunks + 1] for the triangles; the entry behind a half's chunks takes its total.  One half when n1 < 0.
+struct ChunkHalves {
+    int n[2];
+    unsigned *counts[2];
+    unsigned long long *offs[2];
+    ChunkHalves(unsigned *c, unsigned long long *o, int n0, int n1 = -1) : n{n0, n1}, counts{c, c + n0 + 1}, offs{o, o + n0 + 1} {}
+    int scan(hipStream_t s, int h) const { return launch_scan(s, counts[h], offs[h], n[h], offs[h] + n[h]); }
+    // behind the caller's launches: the totals of the halves and, with `info`, its first four report words; one wait for all
+    int totals(hipStream_t s, unsigned long long *tot, const unsigned long long *info = nullptr, unsigned long long *h_info = nullptr) const {
+        for (int h = 0; h < (n[1] < 0 ? 1 : 2); ++h)
+            TL3D_HIP(hipMemcpyAsync(&tot[h], offs[h] + n[h], sizeof(tot[h]), hipMemcpyDeviceToHost, s));
+        if (info) TL3D_HIP(hipMemcpyAsync(h_info, info, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        TL3D_HIP(hipStreamSynchronize(s));
+        return TL3D_OK;
+    }
+};
+
 static PoseF make_pose_f(const double R[9], const double t[3]) {
     PoseF p;
     for (int i = 0; i < 9; ++i) p.r[i] = (float)R[i];
@@ -375,9 +393,6 @@ static void release_grid(tl3d_ctx *ctx) {
     if (gs.cc_parent) (void)hipFree(gs.cc_parent);
     if (gs.cc_count) (void)hipFree(gs.cc_count);
     if (gs.cc_remap) (void)hipFree(gs.cc_remap);
-    if (gs.cc_counts) (void)hipFree(gs.cc_counts);
-    if (gs.cc_offsets) (void)hipFree(gs.cc_offsets);
-    if (gs.cc_info) (void)hipFree(gs.cc_info);
     if (gs.ms_keys) (void)hipFree(gs.ms_keys);
     if (gs.ms_leader) (void)hipFree(gs.ms_leader);
     if (gs.ms_slot) (void)hipFree(gs.ms_slot);
@@ -385,9 +400,9 @@ static void release_grid(tl3d_ctx *ctx) {
     if (gs.ms_acc) (void)hipFree(gs.ms_acc);
     if (gs.ms_ttab) (void)hipFree(gs.ms_ttab);
     if (gs.ms_flag) (void)hipFree(gs.ms_flag);
-    if (gs.ms_counts) (void)hipFree(gs.ms_counts);
-    if (gs.ms_offsets) (void)hipFree(gs.ms_offsets);
-    if (gs.ms_info) (void)hipFree(gs.ms_info);
+    if (gs.mio_counts) (void)hipFree(gs.mio_counts);
+    if (gs.mio_offsets) (void)hipFree(gs.mio_offsets);
+    if (gs.mio_info) (void)hipFree(gs.mio_info);
     for (int h = 0; h < TSDF_SCRATCHES; ++h)
         if (gs.ev_upd[h]) (void)hipEventDestroy(gs.ev_upd[h]);      // (build_grid creates them anew)
     memset(&gs, 0, sizeof(gs));
@@ -2371,9 +2386,10 @@ int tl3d_extract(tl3d_ctx *ctx, int mode, int min_count, int min_weight, double 
     if (mode == TL3D_EXTRACT_TSDF) REQUIRE(ctx->tsdf != nullptr, TL3D_E_STATE, "TSDF channel not enabled");
     FLUSH_AND_FOLD(ctx);
     TL3D_HIP(hipSetDevice(ctx->device));
-    const int nblocks = (int)((ctx->nvox + EXTRACT_CHUNK - 1) / EXTRACT_CHUNK);
+    const int nblocks = chunks_of(ctx->nvox);
     int rc = grow_pair(&ctx->block_counts, &ctx->block_offsets, &ctx->scratch_blocks, (size_t)nblocks + 1, "extraction scratch");
     if (rc) return rc;
+    const ChunkHalves ch(ctx->block_counts, ctx->block_offsets, nblocks);
     unsigned long long total = 0;
     const bool reuse = ctx->ext_valid && ctx->ext_epoch == ctx->grid_epoch && ctx->ext_mode == mode && ctx->ext_min_count == min_count &&
                        ctx->ext_min_weight == min_weight && ctx->ext_max_abs == max_abs_tsdf;
@@ -2383,10 +2399,9 @@ int tl3d_extract(tl3d_ctx *ctx, int mode, int min_count, int min_weight, double 
         ctx->ext_valid = false;
         rc = launch_extract_count(ctx->stream, ctx->grid, mode, min_count, min_weight, max_abs_tsdf, ctx->tsdf, ctx->centroid, ctx->block_counts, nblocks);
         if (rc) return rc;
-        rc = launch_scan(ctx->stream, ctx->block_counts, ctx->block_offsets, nblocks, ctx->block_offsets + nblocks);
+        rc = ch.scan(ctx->stream, 0);
+        if (!rc) rc = ch.totals(ctx->stream, &total);
         if (rc) return rc;
-        TL3D_HIP(hipMemcpyAsync(&total, ctx->block_offsets + nblocks, sizeof(total), hipMemcpyDeviceToHost, ctx->stream));
-        TL3D_HIP(hipStreamSynchronize(ctx->stream));
         ctx->ext_valid = true; ctx->ext_epoch = ctx->grid_epoch; ctx->ext_total = total;
         ctx->ext_mode = mode; ctx->ext_min_count = min_count; ctx->ext_min_weight = min_weight; ctx->ext_max_abs = max_abs_tsdf;
     }
@@ -2415,29 +2430,23 @@ static int extract_mesh_impl(tl3d_ctx *ctx, int min_weight, float *out_xyz, uint
     REQUIRE(ctx->tsdf != nullptr, TL3D_E_STATE, "TSDF channel not enabled");
     FLUSH_AND_FOLD(ctx);
     TL3D_HIP(hipSetDevice(ctx->device));
-    const int nblocks = (int)((ctx->nvox + EXTRACT_CHUNK - 1) / EXTRACT_CHUNK);
-    const size_t mb = (size_t)nblocks + 1;
-    int rc = grow_pair(&ctx->mesh_counts, &ctx->mesh_offsets, &ctx->mesh_blocks, 2 * mb, "mesh scratch");
+    const int nblocks = chunks_of(ctx->nvox);
+    int rc = grow_pair(&ctx->mesh_counts, &ctx->mesh_offsets, &ctx->mesh_blocks, 2 * ((size_t)nblocks + 1), "mesh scratch");
     if (!rc) rc = grow(&ctx->mesh_first, &ctx->mesh_first_n, (size_t)ctx->grid.tsdf_cap << 9, "mesh vertex-id scratch");
     if (rc) return rc;
-    unsigned *vcounts = ctx->mesh_counts, *tcounts = ctx->mesh_counts + mb;
-    unsigned long long *voffs = ctx->mesh_offsets, *toffs = ctx->mesh_offsets + mb;
+    const ChunkHalves ch(ctx->mesh_counts, ctx->mesh_offsets, nblocks, nblocks);
     unsigned long long nv = 0, nt = 0;
     if (ctx->mesh_valid && ctx->mesh_epoch == ctx->grid_epoch && ctx->mesh_min_weight == min_weight) {
         nv = ctx->mesh_nv;                              // the size query just before this call already counted and scanned
         nt = ctx->mesh_nt;
     } else {
         ctx->mesh_valid = false;
-        rc = launch_mesh_count(ctx->stream, ctx->grid, min_weight, ctx->tsdf, vcounts, tcounts, nblocks);
-        if (rc) return rc;
-        rc = launch_scan(ctx->stream, vcounts, voffs, nblocks, voffs + nblocks);
-        if (rc) return rc;
-        rc = launch_scan(ctx->stream, tcounts, toffs, nblocks, toffs + nblocks);
-        if (rc) return rc;
+        rc = launch_mesh_count(ctx->stream, ctx->grid, min_weight, ctx->tsdf, ch.counts[0], ch.counts[1], nblocks);
+        if (!rc) rc = ch.scan(ctx->stream, 0);
+        if (!rc) rc = ch.scan(ctx->stream, 1);
         unsigned long long h[2] = {0, 0};
-        TL3D_HIP(hipMemcpyAsync(&h[0], voffs + nblocks, sizeof(h[0]), hipMemcpyDeviceToHost, ctx->stream));
-        TL3D_HIP(hipMemcpyAsync(&h[1], toffs + nblocks, sizeof(h[1]), hipMemcpyDeviceToHost, ctx->stream));
-        TL3D_HIP(hipStreamSynchronize(ctx->stream));
+        if (!rc) rc = ch.totals(ctx->stream, h);
+        if (rc) return rc;
         nv = h[0];
         nt = h[1];
         ctx->mesh_valid = true; ctx->mesh_epoch = ctx->grid_epoch; ctx->mesh_min_weight = min_weight;
@@ -2462,7 +2471,7 @@ static int extract_mesh_impl(tl3d_ctx *ctx, int min_weight, float *out_xyz, uint
     if (!rc) rc = st.out(out_tri, nt * 12, &dtri);              // (no triangle: nothing staged, nothing written)
     if (!rc && out_key) rc = st.out(out_key, nv * 8, &dkey);
     if (rc) return rc;
-    rc = launch_mesh_write(ctx->stream, ctx->grid, min_weight, ctx->tsdf, ctx->centroid, voffs, toffs, nblocks, ctx->mesh_first,
+    rc = launch_mesh_write(ctx->stream, ctx->grid, min_weight, ctx->tsdf, ctx->centroid, ch.offs[0], ch.offs[1], nblocks, ctx->mesh_first,
                            dxyz, drgb, nv, dtri, nt, (long long *)dkey, ctx->lat);
     return st.finish(rc, true);
 }
@@ -2715,6 +2724,18 @@ static int cc_check_mesh(const uint32_t *tri, int64_t n_tri, int64_t n_vert) {
     return TL3D_OK;
 }
 
+// the chunk counts / offsets and the report words of the mesh-in / mesh-out calls (tl3d_internal.h: mio_*)
+static int mio_grow(tl3d_ctx *ctx, int64_t n_tri, int64_t n_vert, const char *what) {
+    int rc = grow_pair(&ctx->mio_counts, &ctx->mio_offsets, &ctx->mio_chunks, (size_t)chunks_of(n_vert) + (size_t)chunks_of(n_tri) + 2, what);
+    if (rc) return rc;
+    if (!ctx->mio_info && hipMalloc(&ctx->mio_info, 8 * sizeof(unsigned long long)) != hipSuccess) {
+        (void)hipGetLastError();
+        ctx->mio_info = nullptr;
+        return set_err(TL3D_E_NOMEM, "%s alloc failed", what);
+    }
+    return TL3D_OK;
+}
+
 static int cc_grow(tl3d_ctx *ctx, int64_t n_tri, int64_t n_vert) {
     size_t cap2 = ctx->cc_verts, cap3 = ctx->cc_verts;
     int rc = grow(&ctx->cc_parent, &ctx->cc_verts, (size_t)n_vert, "mesh component scratch");
@@ -2724,27 +2745,67 @@ static int cc_grow(tl3d_ctx *ctx, int64_t n_tri, int64_t n_vert) {
         ctx->cc_verts = 0;
         return rc;
     }
-    const size_t chunks = (size_t)((n_vert + EXTRACT_CHUNK - 1) / EXTRACT_CHUNK) + (size_t)((n_tri + EXTRACT_CHUNK - 1) / EXTRACT_CHUNK) + 2;
-    rc = grow_pair(&ctx->cc_counts, &ctx->cc_offsets, &ctx->cc_chunks, chunks, "mesh component scratch");
-    if (rc) return rc;
-    if (!ctx->cc_info && hipMalloc(&ctx->cc_info, 8 * sizeof(unsigned long long)) != hipSuccess) {
-        (void)hipGetLastError();
-        ctx->cc_info = nullptr;
-        return set_err(TL3D_E_NOMEM, "mesh component scratch alloc failed");
-    }
-    return TL3D_OK;
+    return mio_grow(ctx, n_tri, n_vert, "mesh component scratch");
 }
+
+// What a call that takes an indexed mesh and returns one does with its arrays, whichever kernels run in between: the argument
+// checks (their order, codes and texts are part of the interface), staging the three inputs, the capacity error, staging the
+// three outputs.  The call's fourth output (one entry per input vertex) differs in size and stays with the call.
+struct MeshIO {
+    const float *xyz; const uint8_t *rgb; int64_t n_vert; const uint32_t *tri; int64_t n_tri;
+    float *out_xyz; uint8_t *out_rgb; int64_t vert_cap; uint32_t *out_tri; int64_t tri_cap;
+    const float *dxyz = nullptr; const uint8_t *drgb = nullptr; const uint32_t *dtri = nullptr;     // stage_in
+    float *oxyz = nullptr; uint8_t *orgb = nullptr; uint32_t *otri = nullptr;                       // stage_out
+
+    // sizes, capacities, and the call's count outputs (counts_given: none of them is null)
+    int check_sizes(bool counts_given) const {
+        const int rc = cc_check_mesh(tri, n_tri, n_vert);
+        if (rc) return rc;
+        REQUIRE(vert_cap >= 0 && tri_cap >= 0, TL3D_E_INVALID, "negative capacity");
+        REQUIRE(counts_given, TL3D_E_INVALID, "null argument");
+        return TL3D_OK;
+    }
+    // the arrays; extra_out: the call's fourth output, extra_bytes long
+    int check_arrays(const void *extra_out, size_t extra_bytes) const {
+        REQUIRE(n_vert == 0 || xyz, TL3D_E_INVALID, "null vertex list");
+        REQUIRE((vert_cap == 0 || (out_xyz && (out_rgb || !rgb))) && (tri_cap == 0 || out_tri), TL3D_E_INVALID, "null output with a capacity");
+        const void *ins[3] = {xyz, rgb, tri};
+        const size_t in_b[3] = {(size_t)n_vert * 12, (size_t)n_vert * 3, (size_t)n_tri * 12};
+        const void *outs[4] = {out_xyz, rgb ? out_rgb : nullptr, out_tri, extra_out};
+        const size_t out_b[4] = {(size_t)vert_cap * 12, (size_t)vert_cap * 3, (size_t)tri_cap * 12, extra_bytes};
+        for (int o = 0; o < 4; ++o)
+            for (int i = 0; i < 3; ++i)
+                REQUIRE(!ranges_overlap(outs[o], out_b[o], ins[i], in_b[i]), TL3D_E_INVALID, "an output aliases an input");
+        return TL3D_OK;
+    }
+    int stage_in(Staging &st) {
+        int rc = st.in(xyz, (size_t)n_vert * 12, &dxyz);
+        if (!rc && rgb) rc = st.in(rgb, (size_t)n_vert * 3, &drgb);
+        if (!rc && n_tri) rc = st.in(tri, (size_t)n_tri * 12, &dtri);
+        return rc;
+    }
+    // tot: the vertices and triangles the result has
+    int stage_out(Staging &st, const unsigned long long tot[2]) {
+        if ((int64_t)tot[0] > vert_cap || (int64_t)tot[1] > tri_cap)
+            return set_err(TL3D_E_CAPACITY, "need %llu vertices / %llu triangles, capacities %lld / %lld", tot[0], tot[1], (long long)vert_cap,
+                           (long long)tri_cap);
+        int rc = st.out(out_xyz, (size_t)tot[0] * 12, &oxyz);
+        if (!rc && rgb) rc = st.out(out_rgb, (size_t)tot[0] * 3, &orgb);
+        if (!rc) rc = st.out(out_tri, (size_t)tot[1] * 12, &otri);
+        return rc;
+    }
+};
 
 // The validation pass and, only when every index is below n_vert, the labelling: cc_parent = labels, cc_count = triangles per
 // label, h_info = the report words (largest index, components, key of the largest component).  Waits for the stream twice.
 static int cc_label(tl3d_ctx *ctx, const uint32_t *dtri, int64_t n_tri, int64_t n_vert, unsigned long long h_info[4]) {
-    TL3D_HIP(hipMemsetAsync(ctx->cc_info, 0, 8 * sizeof(unsigned long long), ctx->stream));
-    int rc = launch_cc_validate(ctx->stream, dtri, n_tri, ctx->cc_info);
+    TL3D_HIP(hipMemsetAsync(ctx->mio_info, 0, 8 * sizeof(unsigned long long), ctx->stream));
+    int rc = launch_cc_validate(ctx->stream, dtri, n_tri, ctx->mio_info);
     if (rc) return rc;
-    TL3D_HIP(hipMemcpyAsync(h_info, ctx->cc_info, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    TL3D_HIP(hipMemcpyAsync(h_info, ctx->mio_info, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     TL3D_HIP(hipStreamSynchronize(ctx->stream));
     REQUIRE(n_tri == 0 || (int64_t)h_info[0] < n_vert, TL3D_E_INVALID, "triangle index %llu out of range [0, %lld)", h_info[0], (long long)n_vert);
-    return launch_cc_label(ctx->stream, dtri, n_tri, n_vert, ctx->cc_parent, ctx->cc_count, ctx->cc_info);
+    return launch_cc_label(ctx->stream, dtri, n_tri, n_vert, ctx->cc_parent, ctx->cc_count, ctx->mio_info);
 }
 
 int tl3d_mesh_components(tl3d_ctx *ctx, const uint32_t *tri, int64_t n_tri, int64_t n_vert, uint32_t *label_out, uint32_t *tri_count_out,
@@ -2770,7 +2831,7 @@ int tl3d_mesh_components(tl3d_ctx *ctx, const uint32_t *tri, int64_t n_tri, int6
     if (rc) return rc;
     TL3D_HIP(hipMemcpyAsync(label_out, ctx->cc_parent, vb, hipMemcpyDefault, ctx->stream));
     if (tri_count_out) TL3D_HIP(hipMemcpyAsync(tri_count_out, ctx->cc_count, vb, hipMemcpyDefault, ctx->stream));
-    TL3D_HIP(hipMemcpyAsync(h, ctx->cc_info, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    TL3D_HIP(hipMemcpyAsync(h, ctx->mio_info, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
     TL3D_HIP(hipStreamSynchronize(ctx->stream));
     *out_n_components = (int64_t)h[1];
     return TL3D_OK;
@@ -2780,21 +2841,10 @@ int tl3d_mesh_filter_components(tl3d_ctx *ctx, const float *xyz, const uint8_t *
                                 int64_t min_triangles, int largest_only, float *out_xyz, uint8_t *out_rgb, int64_t vert_cap,
                                 uint32_t *out_tri, int64_t tri_cap, uint8_t *keep_vert_out, int64_t *out_n_vert, int64_t *out_n_tri,
                                 int64_t *out_n_components, int64_t *out_n_kept) {
-    int rc = cc_check_mesh(tri, n_tri, n_vert);
+    MeshIO m{xyz, rgb, n_vert, tri, n_tri, out_xyz, out_rgb, vert_cap, out_tri, tri_cap};
+    int rc = m.check_sizes(out_n_vert && out_n_tri && out_n_components && out_n_kept);
+    if (!rc) rc = m.check_arrays(keep_vert_out, (size_t)n_vert);
     if (rc) return rc;
-    REQUIRE(vert_cap >= 0 && tri_cap >= 0, TL3D_E_INVALID, "negative capacity");
-    REQUIRE(out_n_vert && out_n_tri && out_n_components && out_n_kept, TL3D_E_INVALID, "null argument");
-    REQUIRE(n_vert == 0 || xyz, TL3D_E_INVALID, "null vertex list");
-    REQUIRE((vert_cap == 0 || (out_xyz && (out_rgb || !rgb))) && (tri_cap == 0 || out_tri), TL3D_E_INVALID, "null output with a capacity");
-    {
-        const void *ins[3] = {xyz, rgb, tri};
-        const size_t in_b[3] = {(size_t)n_vert * 12, (size_t)n_vert * 3, (size_t)n_tri * 12};
-        const void *outs[4] = {out_xyz, rgb ? out_rgb : nullptr, out_tri, keep_vert_out};
-        const size_t out_b[4] = {(size_t)vert_cap * 12, (size_t)vert_cap * 3, (size_t)tri_cap * 12, (size_t)n_vert};
-        for (int o = 0; o < 4; ++o)
-            for (int i = 0; i < 3; ++i)
-                REQUIRE(!ranges_overlap(outs[o], out_b[o], ins[i], in_b[i]), TL3D_E_INVALID, "an output aliases an input");
-    }
     REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
     *out_n_vert = *out_n_tri = *out_n_components = *out_n_kept = 0;
     if (n_vert == 0) return TL3D_OK;
@@ -2802,47 +2852,29 @@ int tl3d_mesh_filter_components(tl3d_ctx *ctx, const float *xyz, const uint8_t *
     rc = cc_grow(ctx, n_tri, n_vert);
     if (rc) return rc;
     Staging st(ctx);
-    const float *dxyz = nullptr;
-    const uint8_t *drgb = nullptr;
-    const uint32_t *dtri = nullptr;
     uint8_t *dkeep = nullptr;
-    rc = st.in(xyz, (size_t)n_vert * 12, &dxyz);
-    if (!rc && rgb) rc = st.in(rgb, (size_t)n_vert * 3, &drgb);
-    if (!rc && n_tri) rc = st.in(tri, (size_t)n_tri * 12, &dtri);
+    rc = m.stage_in(st);
     if (!rc && keep_vert_out) rc = st.out(keep_vert_out, (size_t)n_vert, &dkeep);
     if (rc) return rc;
     unsigned long long h[4] = {0, 0, 0, 0};
-    rc = cc_label(ctx, dtri, n_tri, n_vert, h);
+    rc = cc_label(ctx, m.dtri, n_tri, n_vert, h);
     if (rc) return rc;
-    const int vchunks = (int)((n_vert + EXTRACT_CHUNK - 1) / EXTRACT_CHUNK), tchunks = (int)((n_tri + EXTRACT_CHUNK - 1) / EXTRACT_CHUNK);
-    unsigned *vcounts = ctx->cc_counts, *tcounts = ctx->cc_counts + vchunks + 1;
-    unsigned long long *voffs = ctx->cc_offsets, *toffs = ctx->cc_offsets + vchunks + 1;
-    rc = launch_cc_keep_count(ctx->stream, (long long)min_triangles, largest_only != 0, dtri, n_tri, n_vert, ctx->cc_parent, ctx->cc_count,
-                              vcounts, tcounts, dkeep, ctx->cc_info);
-    if (!rc) rc = launch_scan(ctx->stream, vcounts, voffs, vchunks, voffs + vchunks);
-    if (!rc) rc = launch_scan(ctx->stream, tcounts, toffs, tchunks, toffs + tchunks);       // (no triangle: the total is 0)
-    if (rc) return rc;
+    const ChunkHalves ch(ctx->mio_counts, ctx->mio_offsets, chunks_of(n_vert), chunks_of(n_tri));
+    rc = launch_cc_keep_count(ctx->stream, (long long)min_triangles, largest_only != 0, m.dtri, n_tri, n_vert, ctx->cc_parent, ctx->cc_count,
+                              ch.counts[0], ch.counts[1], dkeep, ctx->mio_info);
+    if (!rc) rc = ch.scan(ctx->stream, 0);
+    if (!rc) rc = ch.scan(ctx->stream, 1);                                                   // (no triangle: the total is 0)
     unsigned long long tot[2] = {0, 0};
-    TL3D_HIP(hipMemcpyAsync(&tot[0], voffs + vchunks, sizeof(tot[0]), hipMemcpyDeviceToHost, ctx->stream));
-    TL3D_HIP(hipMemcpyAsync(&tot[1], toffs + tchunks, sizeof(tot[1]), hipMemcpyDeviceToHost, ctx->stream));
-    TL3D_HIP(hipMemcpyAsync(h, ctx->cc_info, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-    TL3D_HIP(hipStreamSynchronize(ctx->stream));
+    if (!rc) rc = ch.totals(ctx->stream, tot, ctx->mio_info, h);
+    if (rc) return rc;
     *out_n_vert = (int64_t)tot[0];
     *out_n_tri = (int64_t)tot[1];
     *out_n_components = (int64_t)h[1];
     *out_n_kept = (int64_t)h[3];
-    if ((int64_t)tot[0] > vert_cap || (int64_t)tot[1] > tri_cap)
-        return set_err(TL3D_E_CAPACITY, "need %llu vertices / %llu triangles, capacities %lld / %lld", tot[0], tot[1], (long long)vert_cap,
-                       (long long)tri_cap);
-    float *oxyz = nullptr;
-    uint8_t *orgb = nullptr;
-    uint32_t *otri = nullptr;
-    rc = st.out(out_xyz, (size_t)tot[0] * 12, &oxyz);
-    if (!rc && rgb) rc = st.out(out_rgb, (size_t)tot[0] * 3, &orgb);
-    if (!rc) rc = st.out(out_tri, (size_t)tot[1] * 12, &otri);
+    rc = m.stage_out(st, tot);
     if (rc) return rc;
-    rc = launch_cc_compact(ctx->stream, (long long)min_triangles, largest_only != 0, dtri, n_tri, n_vert, ctx->cc_parent, ctx->cc_count, voffs,
-                           toffs, dxyz, drgb, oxyz, orgb, tot[0], otri, tot[1], ctx->cc_remap, ctx->cc_info);
+    rc = launch_cc_compact(ctx->stream, (long long)min_triangles, largest_only != 0, m.dtri, n_tri, n_vert, ctx->cc_parent, ctx->cc_count,
+                           ch.offs[0], ch.offs[1], m.dxyz, m.drgb, m.oxyz, m.orgb, tot[0], m.otri, tot[1], ctx->cc_remap, ctx->mio_info);
     return st.finish(rc, true);
 }
 
@@ -2860,39 +2892,22 @@ static int ms_grow(tl3d_ctx *ctx, int64_t n_tri, int64_t n_vert) {
     if (!rc) rc = grow(&ctx->ms_acc, &ctx->ms_acc_n, 7 * (size_t)n_vert, what);
     if (!rc && n_tri) rc = grow(&ctx->ms_ttab, &ctx->ms_tslots, ms_table_slots(n_tri), what);
     if (!rc && n_tri) rc = grow(&ctx->ms_flag, &ctx->ms_tris, (size_t)n_tri, what);
-    const size_t chunks = (size_t)((n_vert + EXTRACT_CHUNK - 1) / EXTRACT_CHUNK) + (size_t)((n_tri + EXTRACT_CHUNK - 1) / EXTRACT_CHUNK) + 2;
-    if (!rc) rc = grow_pair(&ctx->ms_counts, &ctx->ms_offsets, &ctx->ms_chunks, chunks, what);
-    if (rc) return rc;
-    if (!ctx->ms_info && hipMalloc(&ctx->ms_info, 8 * sizeof(unsigned long long)) != hipSuccess) {
-        (void)hipGetLastError();
-        ctx->ms_info = nullptr;
-        return set_err(TL3D_E_NOMEM, "%s alloc failed", what);
-    }
-    return TL3D_OK;
+    if (!rc) rc = mio_grow(ctx, n_tri, n_vert, what);
+    return rc;
 }
 
 int tl3d_mesh_simplify_clusters(tl3d_ctx *ctx, const float *xyz, const uint8_t *rgb, int64_t n_vert, const uint32_t *tri, int64_t n_tri,
                                 double cell, const double origin[3], float *out_xyz, uint8_t *out_rgb, int64_t vert_cap,
                                 uint32_t *out_tri, int64_t tri_cap, uint32_t *vert_map_out, int64_t *out_n_vert, int64_t *out_n_tri,
                                 int64_t *out_n_degenerate, int64_t *out_n_duplicate) {
-    int rc = cc_check_mesh(tri, n_tri, n_vert);
+    MeshIO m{xyz, rgb, n_vert, tri, n_tri, out_xyz, out_rgb, vert_cap, out_tri, tri_cap};
+    int rc = m.check_sizes(out_n_vert && out_n_tri && out_n_degenerate && out_n_duplicate);
     if (rc) return rc;
-    REQUIRE(vert_cap >= 0 && tri_cap >= 0, TL3D_E_INVALID, "negative capacity");
-    REQUIRE(out_n_vert && out_n_tri && out_n_degenerate && out_n_duplicate, TL3D_E_INVALID, "null argument");
     REQUIRE(std::isfinite(cell) && cell > 0.0, TL3D_E_INVALID, "cell size %g: must be finite and > 0", cell);
     const double o[3] = {origin ? origin[0] : 0.0, origin ? origin[1] : 0.0, origin ? origin[2] : 0.0};
     REQUIRE(std::isfinite(o[0]) && std::isfinite(o[1]) && std::isfinite(o[2]), TL3D_E_INVALID, "origin (%g, %g, %g) is not finite", o[0], o[1], o[2]);
-    REQUIRE(n_vert == 0 || xyz, TL3D_E_INVALID, "null vertex list");
-    REQUIRE((vert_cap == 0 || (out_xyz && (out_rgb || !rgb))) && (tri_cap == 0 || out_tri), TL3D_E_INVALID, "null output with a capacity");
-    {
-        const void *ins[3] = {xyz, rgb, tri};
-        const size_t in_b[3] = {(size_t)n_vert * 12, (size_t)n_vert * 3, (size_t)n_tri * 12};
-        const void *outs[4] = {out_xyz, rgb ? out_rgb : nullptr, out_tri, vert_map_out};
-        const size_t out_b[4] = {(size_t)vert_cap * 12, (size_t)vert_cap * 3, (size_t)tri_cap * 12, (size_t)n_vert * 4};
-        for (int k = 0; k < 4; ++k)
-            for (int i = 0; i < 3; ++i)
-                REQUIRE(!ranges_overlap(outs[k], out_b[k], ins[i], in_b[i]), TL3D_E_INVALID, "an output aliases an input");
-    }
+    rc = m.check_arrays(vert_map_out, (size_t)n_vert * 4);
+    if (rc) return rc;
     REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
     *out_n_vert = *out_n_tri = *out_n_degenerate = *out_n_duplicate = 0;
     if (n_vert == 0) return TL3D_OK;
@@ -2900,56 +2915,38 @@ int tl3d_mesh_simplify_clusters(tl3d_ctx *ctx, const float *xyz, const uint8_t *
     rc = ms_grow(ctx, n_tri, n_vert);
     if (rc) return rc;
     Staging st(ctx);
-    const float *dxyz = nullptr;
-    const uint8_t *drgb = nullptr;
-    const uint32_t *dtri = nullptr;
-    rc = st.in(xyz, (size_t)n_vert * 12, &dxyz);
-    if (!rc && rgb) rc = st.in(rgb, (size_t)n_vert * 3, &drgb);
-    if (!rc && n_tri) rc = st.in(tri, (size_t)n_tri * 12, &dtri);
+    rc = m.stage_in(st);
     if (rc) return rc;
     // the validation passes: nothing is indexed, and no cell is computed for a table, before the host has seen their words
     unsigned long long h[4] = {0, 0, 0, 0};
-    TL3D_HIP(hipMemsetAsync(ctx->ms_info, 0, 8 * sizeof(unsigned long long), ctx->stream));
-    rc = launch_cc_validate(ctx->stream, dtri, n_tri, ctx->ms_info);
-    if (!rc) rc = launch_ms_validate(ctx->stream, cell, o, dxyz, n_vert, ctx->ms_info);
+    TL3D_HIP(hipMemsetAsync(ctx->mio_info, 0, 8 * sizeof(unsigned long long), ctx->stream));
+    rc = launch_cc_validate(ctx->stream, m.dtri, n_tri, ctx->mio_info);
+    if (!rc) rc = launch_ms_validate(ctx->stream, cell, o, m.dxyz, n_vert, ctx->mio_info);
     if (rc) return rc;
-    TL3D_HIP(hipMemcpyAsync(h, ctx->ms_info, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    TL3D_HIP(hipMemcpyAsync(h, ctx->mio_info, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     TL3D_HIP(hipStreamSynchronize(ctx->stream));
     REQUIRE(n_tri == 0 || (int64_t)h[0] < n_vert, TL3D_E_INVALID, "triangle index %llu out of range [0, %lld)", h[0], (long long)n_vert);
     REQUIRE(h[1] == 0, TL3D_E_INVALID, "%llu vertices are not finite or lie 2^20 cells or more from the origin", h[1]);
     const size_t vslots = ms_table_slots(n_vert), tslots = ms_table_slots(n_tri);
-    const int vchunks = (int)((n_vert + EXTRACT_CHUNK - 1) / EXTRACT_CHUNK), tchunks = (int)((n_tri + EXTRACT_CHUNK - 1) / EXTRACT_CHUNK);
-    unsigned *vcounts = ctx->ms_counts, *tcounts = ctx->ms_counts + vchunks + 1;
-    unsigned long long *voffs = ctx->ms_offsets, *toffs = ctx->ms_offsets + vchunks + 1;
+    const ChunkHalves ch(ctx->mio_counts, ctx->mio_offsets, chunks_of(n_vert), chunks_of(n_tri));
     TL3D_HIP(hipMemsetAsync(ctx->ms_keys, 0xFF, vslots * sizeof(unsigned long long), ctx->stream));
     TL3D_HIP(hipMemsetAsync(ctx->ms_leader, 0xFF, vslots * sizeof(unsigned), ctx->stream));
     TL3D_HIP(hipMemsetAsync(ctx->ms_acc, 0, 7 * (size_t)n_vert * sizeof(unsigned long long), ctx->stream));
     if (n_tri) TL3D_HIP(hipMemsetAsync(ctx->ms_ttab, 0xFF, tslots * sizeof(unsigned), ctx->stream));
-    rc = launch_ms_cluster(ctx->stream, cell, o, dxyz, drgb, n_vert, ctx->ms_keys, ctx->ms_leader, vslots, ctx->ms_slot, ctx->ms_vmap,
-                           ctx->ms_acc, vcounts, voffs);
-    if (!rc) rc = launch_ms_triangles(ctx->stream, dtri, n_tri, ctx->ms_vmap, ctx->ms_ttab, tslots, ctx->ms_flag, tcounts, toffs, ctx->ms_info);
-    if (rc) return rc;
+    rc = launch_ms_cluster(ctx->stream, cell, o, m.dxyz, m.drgb, n_vert, ctx->ms_keys, ctx->ms_leader, vslots, ctx->ms_slot, ctx->ms_vmap,
+                           ctx->ms_acc, ch.counts[0], ch.offs[0]);
+    if (!rc) rc = launch_ms_triangles(ctx->stream, m.dtri, n_tri, ctx->ms_vmap, ctx->ms_ttab, tslots, ctx->ms_flag, ch.counts[1], ch.offs[1], ctx->mio_info);
     unsigned long long tot[2] = {0, 0};
-    TL3D_HIP(hipMemcpyAsync(&tot[0], voffs + vchunks, sizeof(tot[0]), hipMemcpyDeviceToHost, ctx->stream));
-    TL3D_HIP(hipMemcpyAsync(&tot[1], toffs + tchunks, sizeof(tot[1]), hipMemcpyDeviceToHost, ctx->stream));
-    TL3D_HIP(hipMemcpyAsync(h, ctx->ms_info, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-    TL3D_HIP(hipStreamSynchronize(ctx->stream));
+    if (!rc) rc = ch.totals(ctx->stream, tot, ctx->mio_info, h);
+    if (rc) return rc;
     *out_n_vert = (int64_t)tot[0];
     *out_n_tri = (int64_t)tot[1];
     *out_n_degenerate = (int64_t)h[2];
     *out_n_duplicate = (int64_t)h[3];
-    if ((int64_t)tot[0] > vert_cap || (int64_t)tot[1] > tri_cap)
-        return set_err(TL3D_E_CAPACITY, "need %llu vertices / %llu triangles, capacities %lld / %lld", tot[0], tot[1], (long long)vert_cap,
-                       (long long)tri_cap);
-    float *oxyz = nullptr;
-    uint8_t *orgb = nullptr;
-    uint32_t *otri = nullptr;
-    rc = st.out(out_xyz, (size_t)tot[0] * 12, &oxyz);
-    if (!rc && rgb) rc = st.out(out_rgb, (size_t)tot[0] * 3, &orgb);
-    if (!rc) rc = st.out(out_tri, (size_t)tot[1] * 12, &otri);
+    rc = m.stage_out(st, tot);
     if (rc) return rc;
-    rc = launch_ms_write(ctx->stream, cell, o, dxyz, rgb != nullptr, n_vert, ctx->ms_slot, ctx->ms_leader, ctx->ms_vmap, ctx->ms_acc, oxyz, orgb,
-                         tot[0], dtri, n_tri, ctx->ms_flag, toffs, otri, tot[1]);
+    rc = launch_ms_write(ctx->stream, cell, o, m.dxyz, rgb != nullptr, n_vert, ctx->ms_slot, ctx->ms_leader, ctx->ms_vmap, ctx->ms_acc, m.oxyz, m.orgb,
+                         tot[0], m.dtri, n_tri, ctx->ms_flag, ch.offs[1], m.otri, tot[1]);
     if (!rc && vert_map_out) TL3D_HIP(hipMemcpyAsync(vert_map_out, ctx->ms_vmap, (size_t)n_vert * 4, hipMemcpyDefault, ctx->stream));
     return st.finish(rc, true);
 }

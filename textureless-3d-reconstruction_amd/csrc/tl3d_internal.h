@@ -225,19 +225,14 @@ struct tl3d_grid_state {
     unsigned *mesh_first;
     size_t mesh_first_n;
     // tl3d_mesh_components / tl3d_mesh_filter_components: union-find parents (= labels), triangles per label and new vertex ids
-    // (12 B per vertex), kept counts and offsets per chunk of vertices / triangles, the words the kernels report through.  None of
-    // it depends on the grid (the calls work without one); it lives here so that release_grid stays the one place that frees
-    // device scratch grown on demand.
+    // (12 B per vertex).  None of it depends on the grid (the calls work without one); it lives here so that release_grid stays
+    // the one place that frees device scratch grown on demand.
     unsigned *cc_parent, *cc_count, *cc_remap;
     size_t cc_verts;                        // capacity of each, in vertices
-    unsigned *cc_counts;                    // [vertex chunks + 1][triangle chunks + 1]
-    unsigned long long *cc_offsets;
-    size_t cc_chunks;                       // capacity of both, in entries
-    unsigned long long *cc_info;            // [8]: largest index, components, key of the largest component, kept components
     // tl3d_mesh_simplify_clusters: the vertex table (a 64-bit key and a leader word per slot, a power of
     // two >= 2 n_vert slots), per vertex its slot and its cluster number, per cluster seven 64-bit sums (n, S, C), the triangle
-    // table (one index per slot, a power of two >= 2 n_tri slots), a class byte per triangle, counts and offsets per chunk, the
-    // report words.  Grid-independent like the cc_ scratch, and here for the same reason.
+    // table (one index per slot, a power of two >= 2 n_tri slots), a class byte per triangle.  Grid-independent like the cc_
+    // scratch, and here for the same reason.
     unsigned long long *ms_keys;
     unsigned *ms_leader;
     size_t ms_vslots;                       // capacity of both, in slots
@@ -248,10 +243,17 @@ struct tl3d_grid_state {
     size_t ms_tslots;
     uint8_t *ms_flag;
     size_t ms_tris;
-    unsigned *ms_counts;                    // [vertex chunks + 1][triangle chunks + 1]
-    unsigned long long *ms_offsets;
-    size_t ms_chunks;
-    unsigned long long *ms_info;            // [8]: largest index, vertices without a cell, degenerate, duplicate
+    // What the mesh-in / mesh-out calls above share, none of it live across calls: counts and offsets per chunk of vertices /
+    // triangles, and the eight words their kernels report through, zeroed by each call before use:
+    //   word   tl3d_mesh_components / _filter_components       tl3d_mesh_simplify_clusters
+    //   [0]    largest triangle index (its low u32 word)       the same
+    //   [1]    components                                      vertices without a cell
+    //   [2]    key of the largest component (cc_roots_kernel)  degenerate triangles
+    //   [3]    kept components                                 duplicate triangles
+    unsigned *mio_counts;                   // [vertex chunks + 1][triangle chunks + 1]
+    unsigned long long *mio_offsets;
+    size_t mio_chunks;                      // capacity of both, in entries
+    unsigned long long *mio_info;           // [8]
     // tl3d_set_block_core: the grid is one block of a lattice of lat[] voxels and emits only what its core (grid.clo / chi) owns
     bool has_core;
     long long lat[3];
@@ -495,8 +497,9 @@ __device__ __forceinline__ const unsigned long long *cen_record(const Grid &g, c
 // ---- kernel launchers (one per .hip file) -----------------------------------------------------
 // frames
 int launch_u16_to_f32(hipStream_t s, const uint16_t *in, float *out, size_t n);
-// back-projection
+// compaction (kernels_compact.hip; the device half is compact.h)
 int launch_scan(hipStream_t s, const unsigned *counts, unsigned long long *offsets, int n, unsigned long long *total);
+// back-projection
 int launch_bp_bounds(hipStream_t s, const Cam &cam, const BpArgs &a, const PoseD &p, const float *depth, const double *xf, const double *yf,
                      float *slab, int nblocks);
 int bp_fused_tiles(const BpArgs &a);
@@ -589,6 +592,8 @@ int launch_ms_write(hipStream_t s, double cell, const double o[3], const float *
 int sor_mean_distance(tl3d_ctx *ctx, const float *xyz_dev, long long n, int k, double cell, double *mean_dev);
 int sor_run(tl3d_ctx *ctx, const float *xyz_dev, long long n, int k, double std_ratio, double cell, uint8_t *keep_dev, long long *kept);
 
-constexpr int EXTRACT_CHUNK = 2048;   // records per block in the extraction kernels
+constexpr int EXTRACT_CHUNK = 2048;   // elements per block in the compaction passes (compact.h)
+inline unsigned blocks_of(unsigned long long n, unsigned per) { return (unsigned)((n + per - 1) / per); }
+inline int chunks_of(unsigned long long n) { return (int)blocks_of(n, EXTRACT_CHUNK); }
 
 }  // namespace tl3d
