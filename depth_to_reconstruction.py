@@ -79,6 +79,10 @@ def main(argv=None):
                         help="keep only the mesh's connected component with the most triangles (needs --mesh-output)")
     parser.add_argument("--mesh-simplify-cell", type=float, default=0.0, metavar="M",
                         help="merge the mesh's vertices per cell of M metres (vertex clustering, after the component filter; needs --mesh-output)")
+    parser.add_argument("--mesh-smooth", type=int, default=0, metavar="N",
+                        help="smooth the mesh with N Taubin iterations (after the component filter and the simplification; needs --mesh-output)")
+    parser.add_argument("--mesh-normals", action="store_true",
+                        help="write area-weighted vertex normals (nx ny nz) into the mesh PLY (needs --mesh-output)")
     parser.add_argument("--render-output", type=str, default=None,
                         help="also render the fused model at every kept camera into this folder: <stem>_model_depth.npy / .png "
                              "(metres / u16 millimetres) and <stem>_model_color.png (one GPU only)")
@@ -105,6 +109,8 @@ def main(argv=None):
         parser.error("--mesh-min-component / --mesh-largest-component filter the mesh: they need --mesh-output")
     if args.mesh_simplify_cell != 0.0 and not args.mesh_output:
         parser.error("--mesh-simplify-cell simplifies the mesh: it needs --mesh-output")
+    if (args.mesh_smooth != 0 or args.mesh_normals) and not args.mesh_output:
+        parser.error("--mesh-smooth / --mesh-normals work on the mesh: they need --mesh-output")
     if args.loop_closure and (args.gpus > 1 or world > 1):
         parser.error("--loop-closure needs a single GPU: every kept frame must be resident where the revisits are registered")
     if args.loop_closure and args.estimate_scale:
@@ -129,7 +135,8 @@ def main(argv=None):
                                   scale_update_weight=args.scale_update_weight, extract_mesh=args.mesh_output is not None,
                                   render_dir=args.render_output, loop_closure=args.loop_closure,
                                   model_tracking=args.model_tracking, mesh_min_component_triangles=max(0, args.mesh_min_component),
-                                  mesh_largest_component=args.mesh_largest_component, mesh_simplify_cell=args.mesh_simplify_cell)
+                                  mesh_largest_component=args.mesh_largest_component, mesh_simplify_cell=args.mesh_simplify_cell,
+                                  mesh_smooth_iterations=args.mesh_smooth, mesh_normals=args.mesh_normals)
     pipeline = DepthToReconstructionPipeline(config)
     # a rank decodes every frame on its host (pose chain and scale rule run over the whole sequence) and uploads its share
     streaming = args.stream and dist is None

@@ -448,6 +448,38 @@ int tl3d_mesh_simplify_clusters(tl3d_ctx *ctx, const float *xyz_hd, const uint8_
                                 uint32_t *vert_map_out_hd,
                                 int64_t *out_n_vert, int64_t *out_n_tri, int64_t *out_n_degenerate, int64_t *out_n_duplicate);
 
+/* Taubin smoothing and vertex normals of an indexed triangle mesh: n_vert vertices (xyz f32 [V][3]), n_tri rows of
+ * three uint32 indices, any mesh (the calls need no grid).  No reference code: the reference has no mesh (Open3D's
+ * filter_smooth_taubin is the model); the rules are ours, chosen so that the result is a function of the mesh alone, bit for bit, in
+ * every run, and does not depend on how vertices or triangles are numbered.
+ * Fixed point: Q(x) = (int64)rint((double)x * 16777216.0) (units of 2^-24 m; the product is exact, halves to even).  All sums are
+ * exact integers (up to 2^76 for positions, 2^123 for normals; exact for any valence below 2^31), hence order-free.
+ * dbl(N) of a wide integer N: |N| = hi * 2^64 + lo, both words unsigned; dbl = (double)hi * 18446744073709551616.0 + (double)lo,
+ * negated when N < 0.  Every fp64 operation is rounded once.
+ * Neighbours: u and v are neighbours iff u != v and some triangle names both; N(v) holds each neighbour once however many
+ * triangles share the edge; k = |N(v)| is the valence ((a, a, b) makes a and b neighbours).
+ * One step with factor s (Jacobi: every vertex reads the positions from before the step), per axis a:
+ *   D_a = sum_{j in N(v)} Q(x_j,a) - k * Q(x_v,a);  x'_a = (float)((double)x_a + s * (dbl(D_a) / ((double)k * 16777216.0))),
+ *   operations in that order; k = 0 copies the vertex.
+ * One iteration is a step with lambda, then a step with mu.  iterations = 0 copies the input.
+ * tl3d_mesh_smooth_taubin: out_xyz [V][3]; valence_out u32 [V] or NULL; *out_n_edges = the unique undirected edges.  Needs
+ * 0 < lambda <= 1, -2 <= mu <= 0, 0 <= iterations <= 1000.  A step that gives a coordinate that is not finite or lies beyond 2^20 m
+ * sets a flag; the call finishes its steps and returns TL3D_E_INVALID.
+ * Face vector of (a, b, c): F = (Q(p_b) - Q(p_a)) x (Q(p_c) - Q(p_a)) in exact integers (units of 2^-48 m^2); the same for the three
+ * cyclic rotations, 0 for a triangle that names a vertex twice.
+ * tl3d_mesh_vertex_normals: N_v = sum of F over the triangles that name v (area-weighted; it points to t > 0 as the extraction's
+ * winding does); n = dbl(N_v) per component, L = sqrt((n_x n_x + n_y n_y) + n_z n_z), out_normal [V][3] = (float)(n_a / L), and
+ * (0, 0, 0) when N_v is zero or no triangle names v; *out_n_zero = the number of such vertices.
+ * Host or device pointers throughout.  TL3D_E_INVALID: a null ctx or argument, negative sizes, n_vert >= 2^31, n_tri >= 2^32,
+ * parameters out of range, an output that overlaps an input (all decided before any device call); an index >= n_vert, a vertex that
+ * is not finite or has |x| > 2^20 m (two passes of their own in front of every indexed access).  n_vert == 0 is TL3D_OK and nothing
+ * is read; n_tri == 0 is TL3D_OK: positions are copied, normals and valences are zero. */
+int tl3d_mesh_smooth_taubin(tl3d_ctx *ctx, const float *xyz_hd, int64_t n_vert, const uint32_t *tri_hd, int64_t n_tri,
+                            int iterations, double lambda, double mu, float *out_xyz_hd, uint32_t *valence_out_hd,
+                            int64_t *out_n_edges);
+int tl3d_mesh_vertex_normals(tl3d_ctx *ctx, const float *xyz_hd, int64_t n_vert, const uint32_t *tri_hd, int64_t n_tri,
+                             float *out_normal_hd, int64_t *out_n_zero);
+
 /* ray casting of the TSDF channel from one camera: one ray per pixel of the context's camera, pose (R, t)
  * world->camera as tl3d_integrate.  depth [H][W] f32 (0 = no hit), normals [H][W][3] f32 in the camera frame facing the
  * camera ((0,0,0) where undefined), colour [H][W][3] BGR (TSDF-mode extraction colour of the hit voxel, 128 without one).

@@ -61,6 +61,13 @@ class ReconstructionConfig:
     # vertex-clustering simplification of the mesh (needs extract_mesh): the vertices of one cell of this
     # size, in metres, become one vertex (0: off); applied after the component filter when both are on
     mesh_simplify_cell: float = 0.0
+    # Taubin smoothing of the mesh's positions and area-weighted vertex normals (all need extract_mesh):
+    # iterations of a step with lambda and a step with mu (0: off), after the component filter and the simplification; the normals
+    # (DepthToReconstructionPipeline.mesh_normals, written by save_mesh) come last, from the final positions
+    mesh_smooth_iterations: int = 0
+    mesh_smooth_lambda: float = 0.5
+    mesh_smooth_mu: float = -0.53
+    mesh_normals: bool = False
     # folder for renders of the fused model at every kept camera (DepthToReconstructionPipeline.reconstruct)
     render_dir: Optional[str] = None
     # loop closure: revisits found from the chain's poses, registered with the same ICP, and every pose

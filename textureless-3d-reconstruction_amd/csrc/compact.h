@@ -14,29 +14,30 @@
 
 namespace tl3d {
 
-// block total of c over the 256 threads (every thread must call)
-__device__ __forceinline__ unsigned block_sum(unsigned c, unsigned *sm) {
+// block total of c over the 256 threads (every thread must call); T: unsigned, or unsigned long long where a chunk's total can
+// pass 2^32 (the adjacency rows of kernels_meshsmooth.hip)
+template <class T> __device__ __forceinline__ T block_sum(T c, T *sm) {
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) c += __shfl_down(c, d);
     if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = c;
     __syncthreads();
-    const unsigned s = sm[0] + sm[1] + sm[2] + sm[3];
+    const T s = sm[0] + sm[1] + sm[2] + sm[3];
     __syncthreads();
     return s;
 }
 
 // exclusive prefix of c over the block (thread order = element order inside one iteration) and the block's total
-__device__ __forceinline__ unsigned block_excl(unsigned c, unsigned *sm, unsigned &total) {
+template <class T> __device__ __forceinline__ T block_excl(T c, T *sm, T &total) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    unsigned inc = c;
+    T inc = c;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
-        const unsigned tv = __shfl_up(inc, d);
+        const T tv = __shfl_up(inc, d);
         if (lane >= d) inc += tv;
     }
     if (lane == 63) sm[wid] = inc;
     __syncthreads();
-    unsigned wbase = 0;
+    T wbase = 0;
     for (int w = 0; w < wid; ++w) wbase += sm[w];
     total = sm[0] + sm[1] + sm[2] + sm[3];
     __syncthreads();

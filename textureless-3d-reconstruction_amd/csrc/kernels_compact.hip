@@ -5,8 +5,10 @@
 
 namespace tl3d {
 
-// single-block exclusive scan of n block counts -> 64-bit offsets (+ total)
-__global__ __launch_bounds__(1024) void scan_kernel(const unsigned *__restrict__ counts, unsigned long long *__restrict__ offsets,
+// single-block exclusive scan of n block counts -> 64-bit offsets (+ total); C: the counts' type (64-bit for the adjacency rows of
+// kernels_meshsmooth.hip, where one chunk's count can pass 2^32)
+template <class C>
+__global__ __launch_bounds__(1024) void scan_kernel(const C *__restrict__ counts, unsigned long long *__restrict__ offsets,
                                                     int n, unsigned long long *__restrict__ total) {
     __shared__ unsigned long long part[1024];
     const int t = threadIdx.x;
@@ -31,7 +33,13 @@ __global__ __launch_bounds__(1024) void scan_kernel(const unsigned *__restrict__
 }
 
 int launch_scan(hipStream_t s, const unsigned *counts, unsigned long long *offsets, int n, unsigned long long *total) {
-    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, counts, offsets, n, total);
+    hipLaunchKernelGGL(scan_kernel<unsigned>, dim3(1), dim3(1024), 0, s, counts, offsets, n, total);
+    TL3D_HIP(hipGetLastError());
+    return TL3D_OK;
+}
+
+int launch_scan(hipStream_t s, const unsigned long long *counts, unsigned long long *offsets, int n, unsigned long long *total) {
+    hipLaunchKernelGGL(scan_kernel<unsigned long long>, dim3(1), dim3(1024), 0, s, counts, offsets, n, total);
     TL3D_HIP(hipGetLastError());
     return TL3D_OK;
 }

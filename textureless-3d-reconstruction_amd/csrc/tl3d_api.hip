@@ -400,6 +400,14 @@ static void release_grid(tl3d_ctx *ctx) {
     if (gs.ms_acc) (void)hipFree(gs.ms_acc);
     if (gs.ms_ttab) (void)hipFree(gs.ms_ttab);
     if (gs.ms_flag) (void)hipFree(gs.ms_flag);
+    if (gs.adj_keys) (void)hipFree(gs.adj_keys);
+    if (gs.adj_cnt) (void)hipFree(gs.adj_cnt);
+    if (gs.adj_cursor) (void)hipFree(gs.adj_cursor);
+    if (gs.adj_row) (void)hipFree(gs.adj_row);
+    if (gs.adj_list) (void)hipFree(gs.adj_list);
+    if (gs.adj_xyz) (void)hipFree(gs.adj_xyz);
+    if (gs.adj_ccounts) (void)hipFree(gs.adj_ccounts);
+    if (gs.adj_coffs) (void)hipFree(gs.adj_coffs);
     if (gs.mio_counts) (void)hipFree(gs.mio_counts);
     if (gs.mio_offsets) (void)hipFree(gs.mio_offsets);
     if (gs.mio_info) (void)hipFree(gs.mio_info);
@@ -2716,10 +2724,10 @@ static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
 }
 
 // the argument checks both calls share; none of them needs a device
-static int cc_check_mesh(const uint32_t *tri, int64_t n_tri, int64_t n_vert) {
+static int cc_check_mesh(const uint32_t *tri, int64_t n_tri, int64_t n_vert, const char *tri_reason = "the component key needs") {
     REQUIRE(n_tri >= 0 && n_vert >= 0, TL3D_E_INVALID, "negative size (n_tri %lld, n_vert %lld)", (long long)n_tri, (long long)n_vert);
     REQUIRE(n_vert < (1ll << 31), TL3D_E_INVALID, "n_vert %lld: indices need fewer than 2^31 vertices", (long long)n_vert);
-    REQUIRE(n_tri < (1ll << 32), TL3D_E_INVALID, "n_tri %lld: the component key needs fewer than 2^32 triangles", (long long)n_tri);
+    REQUIRE(n_tri < (1ll << 32), TL3D_E_INVALID, "n_tri %lld: %s fewer than 2^32 triangles", (long long)n_tri, tri_reason);
     REQUIRE(n_tri == 0 || tri, TL3D_E_INVALID, "null triangle list");
     return TL3D_OK;
 }
@@ -2949,6 +2957,148 @@ int tl3d_mesh_simplify_clusters(tl3d_ctx *ctx, const float *xyz, const uint8_t *
                          tot[0], m.dtri, n_tri, ctx->ms_flag, ch.offs[1], m.otri, tot[1]);
     if (!rc && vert_map_out) TL3D_HIP(hipMemcpyAsync(vert_map_out, ctx->ms_vmap, (size_t)n_vert * 4, hipMemcpyDefault, ctx->stream));
     return st.finish(rc, true);
+}
+
+// ------------------------------------------------------------------------------------------- mesh smoothing, vertex normals
+static size_t adj_table_slots(int64_t n_tri) {
+    size_t cap = 1024;
+    while (cap < 6 * (size_t)n_tri) cap <<= 1;             // at most 3 n_tri keys: load <= 0.5
+    return cap;
+}
+
+// what both calls need per vertex and per chunk; the edge table, the rows and the second position buffer grow where they are used
+static int adj_grow(tl3d_ctx *ctx, int64_t n_tri, int64_t n_vert, const char *what) {
+    int rc = grow_pair(&ctx->adj_cnt, &ctx->adj_cursor, &ctx->adj_verts, (size_t)n_vert, what);
+    if (!rc) rc = grow(&ctx->adj_row, &ctx->adj_rows, (size_t)n_vert, what);
+    if (!rc) rc = grow_pair(&ctx->adj_ccounts, &ctx->adj_coffs, &ctx->adj_chunks, (size_t)chunks_of(n_vert) + 1, what);
+    if (!rc) rc = mio_grow(ctx, n_tri, n_vert, what);
+    return rc;
+}
+
+// the two validation passes and the host's look at their words: nothing is indexed, and no coordinate is quantised, before it
+static int adj_validate(tl3d_ctx *ctx, const float *dxyz, int64_t n_vert, const uint32_t *dtri, int64_t n_tri) {
+    unsigned long long h[2] = {0, 0};
+    TL3D_HIP(hipMemsetAsync(ctx->mio_info, 0, 8 * sizeof(unsigned long long), ctx->stream));
+    int rc = launch_cc_validate(ctx->stream, dtri, n_tri, ctx->mio_info);
+    if (!rc) rc = launch_msm_validate(ctx->stream, dxyz, n_vert, ctx->mio_info);
+    if (rc) return rc;
+    TL3D_HIP(hipMemcpyAsync(h, ctx->mio_info, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    TL3D_HIP(hipStreamSynchronize(ctx->stream));
+    REQUIRE(n_tri == 0 || (int64_t)h[0] < n_vert, TL3D_E_INVALID, "triangle index %llu out of range [0, %lld)", h[0], (long long)n_vert);
+    REQUIRE(h[1] == 0, TL3D_E_INVALID, "%llu vertices are not finite or lie beyond 2^20 m", h[1]);
+    return TL3D_OK;
+}
+
+int tl3d_mesh_smooth_taubin(tl3d_ctx *ctx, const float *xyz, int64_t n_vert, const uint32_t *tri, int64_t n_tri, int iterations, double lambda,
+                            double mu, float *out_xyz, uint32_t *valence_out, int64_t *out_n_edges) {
+    const char *what = "mesh smoothing scratch";
+    int rc = cc_check_mesh(tri, n_tri, n_vert, "the triangle and corner counts need");
+    if (rc) return rc;
+    REQUIRE(out_n_edges != nullptr && (n_vert == 0 || (xyz && out_xyz)), TL3D_E_INVALID, "null argument");
+    REQUIRE(iterations >= 0 && iterations <= 1000, TL3D_E_INVALID, "iterations %d out of range [0, 1000]", iterations);
+    REQUIRE(lambda > 0.0 && lambda <= 1.0, TL3D_E_INVALID, "lambda %g out of range (0, 1]", lambda);             // (false for NaN)
+    REQUIRE(mu >= -2.0 && mu <= 0.0, TL3D_E_INVALID, "mu %g out of range [-2, 0]", mu);
+    const size_t xb = (size_t)n_vert * 12, tb = (size_t)n_tri * 12, vb = (size_t)n_vert * 4;
+    REQUIRE(!ranges_overlap(out_xyz, xb, xyz, xb) && !ranges_overlap(out_xyz, xb, tri, tb) && !ranges_overlap(valence_out, vb, xyz, xb) &&
+                !ranges_overlap(valence_out, vb, tri, tb) && !ranges_overlap(valence_out, vb, out_xyz, xb),
+            TL3D_E_INVALID, "an output aliases an input (or the other output)");
+    REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
+    *out_n_edges = 0;
+    if (n_vert == 0) return TL3D_OK;
+    TL3D_HIP(hipSetDevice(ctx->device));
+    rc = adj_grow(ctx, n_tri, n_vert, what);
+    const size_t slots = adj_table_slots(n_tri);
+    if (!rc && n_tri) rc = grow(&ctx->adj_keys, &ctx->adj_slots, slots, what);
+    if (!rc && n_tri && iterations) rc = grow(&ctx->adj_xyz, &ctx->adj_xyz_n, 3 * (size_t)n_vert, what);
+    if (rc) return rc;
+    Staging st(ctx);
+    const float *dxyz = nullptr;
+    const uint32_t *dtri = nullptr;
+    float *oxyz = nullptr;
+    uint32_t *oval = nullptr;
+    rc = st.in(xyz, xb, &dxyz);
+    if (!rc && n_tri) rc = st.in(tri, tb, &dtri);
+    if (!rc) rc = st.out(out_xyz, xb, &oxyz);
+    if (!rc && valence_out) rc = st.out(valence_out, vb, &oval);
+    if (!rc) rc = adj_validate(ctx, dxyz, n_vert, dtri, n_tri);
+    if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    TL3D_HIP(hipMemsetAsync(ctx->adj_cnt, 0, vb, s));
+    unsigned long long h[5] = {0, 0, 0, 0, 0};
+    if (n_tri) {
+        TL3D_HIP(hipMemsetAsync(ctx->adj_keys, 0xFF, slots * sizeof(unsigned long long), s));
+        rc = launch_msm_edges(s, dtri, n_tri, ctx->adj_keys, slots, ctx->adj_cnt, ctx->mio_info);
+        if (rc) return rc;
+        TL3D_HIP(hipMemcpyAsync(h, ctx->mio_info, sizeof(h), hipMemcpyDeviceToHost, s));
+        TL3D_HIP(hipStreamSynchronize(s));
+    }
+    *out_n_edges = (int64_t)h[2];
+    if (oval) TL3D_HIP(hipMemcpyAsync(oval, ctx->adj_cnt, vb, hipMemcpyDeviceToDevice, s));
+    if (h[2] == 0 || iterations == 0) {                    // nothing moves
+        TL3D_HIP(hipMemcpyAsync(oxyz, dxyz, xb, hipMemcpyDeviceToDevice, s));
+        return st.finish(TL3D_OK, true);
+    }
+    rc = grow(&ctx->adj_list, &ctx->adj_list_n, 2 * (size_t)h[2], what);
+    if (!rc) rc = launch_msm_rows(s, ctx->adj_cnt, n_vert, ctx->adj_ccounts, ctx->adj_coffs, ctx->adj_row, ctx->adj_cursor);
+    if (!rc) rc = launch_msm_edge_fill(s, ctx->adj_keys, slots, ctx->adj_cnt, ctx->adj_row, ctx->adj_cursor, ctx->adj_list);
+    // 2 * iterations steps between the scratch buffer and the output: in -> scratch -> out -> scratch -> out ...
+    const float *src = dxyz;
+    for (int i = 0; i < 2 * iterations && !rc; ++i) {
+        float *dst = (i & 1) ? oxyz : ctx->adj_xyz;
+        // the divergence flag: step i reports through word 3 + (i & 1) and reads the word of the step before it (both zero at first)
+        rc = launch_msm_step(s, src, dst, n_vert, ctx->adj_cnt, ctx->adj_row, ctx->adj_list, (i & 1) ? mu : lambda,
+                             ctx->mio_info + 4 - (i & 1), ctx->mio_info + 3 + (i & 1));
+        src = dst;
+    }
+    if (rc) return rc;
+    TL3D_HIP(hipMemcpyAsync(h, ctx->mio_info, sizeof(h), hipMemcpyDeviceToHost, s));
+    rc = st.finish(TL3D_OK, true);
+    if (rc) return rc;
+    REQUIRE((h[3] | h[4]) == 0, TL3D_E_INVALID,
+            "smoothing diverged: a step gave a coordinate that is not finite or lies beyond 2^20 m (lambda %g, mu %g)", lambda, mu);
+    return TL3D_OK;
+}
+
+int tl3d_mesh_vertex_normals(tl3d_ctx *ctx, const float *xyz, int64_t n_vert, const uint32_t *tri, int64_t n_tri, float *out_normal,
+                             int64_t *out_n_zero) {
+    const char *what = "mesh normal scratch";
+    int rc = cc_check_mesh(tri, n_tri, n_vert, "the triangle ids of the rows need");
+    if (rc) return rc;
+    REQUIRE(out_n_zero != nullptr && (n_vert == 0 || (xyz && out_normal)), TL3D_E_INVALID, "null argument");
+    const size_t xb = (size_t)n_vert * 12, tb = (size_t)n_tri * 12;
+    REQUIRE(!ranges_overlap(out_normal, xb, xyz, xb) && !ranges_overlap(out_normal, xb, tri, tb), TL3D_E_INVALID, "an output aliases an input");
+    REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
+    *out_n_zero = 0;
+    if (n_vert == 0) return TL3D_OK;
+    TL3D_HIP(hipSetDevice(ctx->device));
+    rc = adj_grow(ctx, n_tri, n_vert, what);
+    if (!rc && n_tri) rc = grow(&ctx->adj_list, &ctx->adj_list_n, 3 * (size_t)n_tri, what);
+    if (rc) return rc;
+    Staging st(ctx);
+    const float *dxyz = nullptr;
+    const uint32_t *dtri = nullptr;
+    float *onrm = nullptr;
+    rc = st.in(xyz, xb, &dxyz);
+    if (!rc && n_tri) rc = st.in(tri, tb, &dtri);
+    if (!rc) rc = st.out(out_normal, xb, &onrm);
+    if (!rc) rc = adj_validate(ctx, dxyz, n_vert, dtri, n_tri);
+    if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    if (n_tri == 0) {
+        TL3D_HIP(hipMemsetAsync(onrm, 0, xb, s));
+        *out_n_zero = n_vert;
+        return st.finish(TL3D_OK, true);
+    }
+    TL3D_HIP(hipMemsetAsync(ctx->adj_cnt, 0, (size_t)n_vert * 4, s));
+    rc = launch_msm_corners(s, dtri, n_tri, n_vert, ctx->adj_cnt, ctx->adj_ccounts, ctx->adj_coffs, ctx->adj_row, ctx->adj_cursor, ctx->adj_list);
+    if (!rc) rc = launch_msm_normals(s, dxyz, dtri, n_vert, ctx->adj_cnt, ctx->adj_row, ctx->adj_list, onrm, ctx->mio_info);
+    if (rc) return rc;
+    unsigned long long h[4] = {0, 0, 0, 0};
+    TL3D_HIP(hipMemcpyAsync(h, ctx->mio_info, sizeof(h), hipMemcpyDeviceToHost, s));
+    rc = st.finish(TL3D_OK, true);
+    if (rc) return rc;
+    *out_n_zero = (int64_t)h[3];
+    return TL3D_OK;
 }
 
 // ------------------------------------------------------------------------------------------- measurement

@@ -243,13 +243,30 @@ struct tl3d_grid_state {
     size_t ms_tslots;
     uint8_t *ms_flag;
     size_t ms_tris;
+    // tl3d_mesh_smooth_taubin / tl3d_mesh_vertex_normals: the edge table (one 64-bit key per slot, a power
+    // of two >= 6 n_tri slots), per vertex a count (valence, or incident corners) and a fill cursor, the 64-bit row offsets, the
+    // rows themselves (2 E neighbours, or 3 n_tri triangle ids), the second position buffer of the steps, and the 64-bit chunk
+    // sums and offsets of the row scan.  Grid-independent like the cc_ scratch, and here for the same reason.
+    unsigned long long *adj_keys;
+    size_t adj_slots;
+    unsigned *adj_cnt, *adj_cursor;
+    size_t adj_verts;                       // capacity of both, in vertices
+    unsigned long long *adj_row;
+    size_t adj_rows;
+    unsigned *adj_list;
+    size_t adj_list_n;
+    float *adj_xyz;
+    size_t adj_xyz_n;                       // in floats
+    unsigned long long *adj_ccounts, *adj_coffs;
+    size_t adj_chunks;                      // capacity of both, in entries
     // What the mesh-in / mesh-out calls above share, none of it live across calls: counts and offsets per chunk of vertices /
     // triangles, and the eight words their kernels report through, zeroed by each call before use:
-    //   word   tl3d_mesh_components / _filter_components       tl3d_mesh_simplify_clusters
-    //   [0]    largest triangle index (its low u32 word)       the same
-    //   [1]    components                                      vertices without a cell
-    //   [2]    key of the largest component (cc_roots_kernel)  degenerate triangles
-    //   [3]    kept components                                 duplicate triangles
+    //   word   tl3d_mesh_components / _filter_components       tl3d_mesh_simplify_clusters   tl3d_mesh_smooth_taubin / _vertex_normals
+    //   [0]    largest triangle index (its low u32 word)       the same                      the same
+    //   [1]    components                                      vertices without a cell       vertices out of range
+    //   [2]    key of the largest component (cc_roots_kernel)  degenerate triangles          unique edges
+    //   [3]    kept components                                 duplicate triangles           a step left the range / zero normals
+    //   [4]                                                                                  a step left the range (steps take [3], [4] in turn)
     unsigned *mio_counts;                   // [vertex chunks + 1][triangle chunks + 1]
     unsigned long long *mio_offsets;
     size_t mio_chunks;                      // capacity of both, in entries
@@ -499,6 +516,7 @@ __device__ __forceinline__ const unsigned long long *cen_record(const Grid &g, c
 int launch_u16_to_f32(hipStream_t s, const uint16_t *in, float *out, size_t n);
 // compaction (kernels_compact.hip; the device half is compact.h)
 int launch_scan(hipStream_t s, const unsigned *counts, unsigned long long *offsets, int n, unsigned long long *total);
+int launch_scan(hipStream_t s, const unsigned long long *counts, unsigned long long *offsets, int n, unsigned long long *total);
 // back-projection
 int launch_bp_bounds(hipStream_t s, const Cam &cam, const BpArgs &a, const PoseD &p, const float *depth, const double *xf, const double *yf,
                      float *slab, int nblocks);
@@ -591,6 +609,21 @@ int launch_ms_write(hipStream_t s, double cell, const double o[3], const float *
                     unsigned *out_tri, unsigned long long tcap);
 int sor_mean_distance(tl3d_ctx *ctx, const float *xyz_dev, long long n, int k, double cell, double *mean_dev);
 int sor_run(tl3d_ctx *ctx, const float *xyz_dev, long long n, int k, double std_ratio, double cell, uint8_t *keep_dev, long long *kept);
+
+// mesh smoothing and vertex normals (kernels_meshsmooth.hip)
+int launch_msm_validate(hipStream_t s, const float *xyz, long long n_vert, unsigned long long *info);
+int launch_msm_edges(hipStream_t s, const unsigned *tri, long long n_tri, unsigned long long *keys, unsigned long long slots, unsigned *deg,
+                     unsigned long long *info);
+int launch_msm_rows(hipStream_t s, const unsigned *cnt, long long n_vert, unsigned long long *ccounts, unsigned long long *coffs,
+                    unsigned long long *row, unsigned *cursor);
+int launch_msm_edge_fill(hipStream_t s, const unsigned long long *keys, unsigned long long slots, const unsigned *deg,
+                         const unsigned long long *row, unsigned *cursor, unsigned *nbr);
+int launch_msm_step(hipStream_t s, const float *in, float *out, long long n_vert, const unsigned *deg, const unsigned long long *row,
+                    const unsigned *nbr, double factor, const unsigned long long *flag_in, unsigned long long *flag_out);
+int launch_msm_corners(hipStream_t s, const unsigned *tri, long long n_tri, long long n_vert, unsigned *cnt, unsigned long long *ccounts,
+                       unsigned long long *coffs, unsigned long long *row, unsigned *cursor, unsigned *inc);
+int launch_msm_normals(hipStream_t s, const float *xyz, const unsigned *tri, long long n_vert, const unsigned *cnt, const unsigned long long *row,
+                       const unsigned *inc, float *out, unsigned long long *info);
 
 constexpr int EXTRACT_CHUNK = 2048;   // elements per block in the compaction passes (compact.h)
 inline unsigned blocks_of(unsigned long long n, unsigned per) { return (unsigned)((n + per - 1) / per); }

@@ -543,16 +543,21 @@ def write_ply_binary(path, points, colors, double_xyz: bool = True):
         f.write(rec.tobytes())
 
 
-def write_ply_mesh(path, xyz, rgb, tris, ascii: bool = False):
+def write_ply_mesh(path, xyz, rgb, tris, ascii: bool = False, normals=None):
     """Triangle mesh as PLY: vertices `float x, y, z, uchar red, green, blue`, faces `list uchar int vertex_indices`;
-    binary little-endian, or ASCII.  Parent directories are created."""
+    binary little-endian, or ASCII.  normals (f32 [V,3]): the vertex record becomes `float x, y, z, nx, ny, nz, uchar red, green,
+    blue`, the order MeshLab and Open3D read.  Parent directories are created."""
     xyz = np.asarray(xyz, dtype=np.float32).reshape(-1, 3)
     rgb = np.asarray(rgb, dtype=np.uint8).reshape(-1, 3)
     tris = np.asarray(tris).reshape(-1, 3)
     assert len(xyz) == len(rgb) and len(xyz) < 2 ** 31
     assert len(tris) == 0 or (int(tris.min()) >= 0 and int(tris.max()) < len(xyz)), "triangle index out of range"
+    if normals is not None:
+        normals = np.asarray(normals, dtype=np.float32).reshape(-1, 3)
+        assert len(normals) == len(xyz), "one normal per vertex"
+    nprops = [] if normals is None else ["property float nx", "property float ny", "property float nz"]
     header = "\n".join(["ply", "format ascii 1.0" if ascii else "format binary_little_endian 1.0", f"element vertex {len(xyz)}",
-                        "property float x", "property float y", "property float z", "property uchar red", "property uchar green",
+                        "property float x", "property float y", "property float z", *nprops, "property uchar red", "property uchar green",
                         "property uchar blue", f"element face {len(tris)}", "property list uchar int vertex_indices",
                         "end_header"]) + "\n"
     filepath = Path(path)
@@ -560,15 +565,19 @@ def write_ply_mesh(path, xyz, rgb, tris, ascii: bool = False):
     if ascii:
         with open(filepath, "w", newline="\n") as f:
             f.write(header)
-            for p, c in zip(xyz, rgb):
-                f.write(f"{p[0]} {p[1]} {p[2]} {int(c[0])} {int(c[1])} {int(c[2])}\n")
+            for i, (p, c) in enumerate(zip(xyz, rgb)):
+                n = "" if normals is None else f"{normals[i, 0]} {normals[i, 1]} {normals[i, 2]} "
+                f.write(f"{p[0]} {p[1]} {p[2]} {n}{int(c[0])} {int(c[1])} {int(c[2])}\n")
             for t in tris:
                 f.write(f"3 {int(t[0])} {int(t[1])} {int(t[2])}\n")
         return
-    vrec = np.empty(len(xyz), dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("r", "u1"), ("g", "u1"), ("b", "u1")])
+    nfields = [] if normals is None else [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+    vrec = np.empty(len(xyz), dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), *nfields, ("r", "u1"), ("g", "u1"), ("b", "u1")])
     if len(xyz):
         vrec["x"], vrec["y"], vrec["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
         vrec["r"], vrec["g"], vrec["b"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
+        if normals is not None:
+            vrec["nx"], vrec["ny"], vrec["nz"] = normals[:, 0], normals[:, 1], normals[:, 2]
     frec = np.empty(len(tris), dtype=[("n", "u1"), ("v", "<i4", (3,))])
     if len(tris):
         frec["n"] = 3

@@ -768,6 +768,34 @@ class FusionContext:
                     vert_map=vmap)
         return oxyz[:kv.value], (orgb[:kv.value] if orgb is not None else None), otri[:kt.value], info
 
+    def smooth_mesh(self, xyz, tris, iterations: int, lam: float = 0.5, mu: float = -0.53):
+        """Taubin lambda|mu smoothing of a mesh's positions (needs no grid): `iterations` times a Laplacian
+        step with `lam` and an inflating step with `mu` over the unique neighbours of every vertex, in exact integer sums, so the
+        result does not depend on the numbering and is the same bytes in every run.  Triangles and colours are not touched.
+        Returns (xyz, info); info: edges (unique undirected), valence (u32 [V]) and max_valence."""
+        xyz, _, tris, empty = self._mesh_arrays(xyz, None, tris)
+        nv, nt = len(xyz), len(tris)
+        oxyz, val = empty((nv, 3), np.float32), empty((nv,), np.uint32)
+        ne = C.c_int64(0)
+
+        def p(a):
+            return abi.ptr(a) if len(a) else None
+        abi.check(self._lib.tl3d_mesh_smooth_taubin(self._h, p(xyz), nv, p(tris), nt, int(iterations), float(lam), float(mu), p(oxyz),
+                                                    p(val), C.byref(ne)))
+        return oxyz, dict(edges=ne.value, valence=val, max_valence=int(val.max()) if nv else 0)
+
+    def mesh_normals(self, xyz, tris):
+        """Area-weighted unit vertex normals of a mesh (needs no grid): f32 [V,3], the normalised exact
+        integer sum of the face vectors of the triangles that name each vertex, pointing where the extraction's winding points;
+        (0, 0, 0) for a vertex without one."""
+        xyz, _, tris, empty = self._mesh_arrays(xyz, None, tris)
+        nv, nt = len(xyz), len(tris)
+        out = empty((nv, 3), np.float32)
+        nz = C.c_int64(0)
+        abi.check(self._lib.tl3d_mesh_vertex_normals(self._h, abi.ptr(xyz) if nv else None, nv, abi.ptr(tris) if nt else None, nt,
+                                                     abi.ptr(out) if nv else None, C.byref(nz)))
+        return out
+
     def raycast(self, pose, min_weight: int = 0, z_near=None, z_far=None, slot=None, out=None):
         """Ray-cast the TSDF channel from the camera at pose = (R, t) (world->camera, as integrate):
         (depth f32 [H,W] with 0 = no hit, normals f32 [H,W,3] in the camera frame, bgr u8 [H,W,3]).  z_near / z_far default to

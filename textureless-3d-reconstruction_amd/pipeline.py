@@ -155,6 +155,7 @@ class DepthToReconstructionPipeline:
         self.timings: dict = {}                   # wall seconds per stage of the last reconstruct()
         self.grid: Optional[GridSpec] = None      # the fusion volume of the last reconstruct(): the whole lattice (nvox may exceed 2^32)
         self.blocks: List[GridSpec] = []          # the grids it was fused in (one, or the blocks of a lattice beyond one grid)
+        self.mesh_normals = None                  # f32 [V,3] of that mesh when config.mesh_normals, else None
         self.mesh = None                          # (xyz f32 [V,3], rgb u8 [V,3], tris u32 [T,3]) of the last reconstruct(), config.extract_mesh
 
     # ---- a2 --------------------------------------------------------------------------------------
@@ -460,6 +461,7 @@ class DepthToReconstructionPipeline:
         _register_with_scale); view 0 keeps config.depth_scale (or its anchors' estimate).
         """
         self.mesh = None
+        self.mesh_normals = None
         cfg = self.config
         self._check_mesh_filter_config()
         loop = bool(getattr(cfg, "loop_closure", False)) and poses is None      # with poses given nothing is registered: the option is ignored
@@ -669,6 +671,14 @@ class DepthToReconstructionPipeline:
                 t0 = clock()
                 vx, vr, vt = self._simplify_mesh(ctx, (vx, vr, vt))
                 stage["mesh_simplify"] = clock() - t0
+            if self._mesh_smooth_on():                   # after both: it moves what they left, and changes no index
+                t0 = clock()
+                vx = self._smooth_mesh(ctx, (vx, vr, vt))[0]
+                stage["mesh_smooth"] = clock() - t0
+            if cfg.mesh_normals:                         # last: from the final positions
+                t0 = clock()
+                self.mesh_normals = ctx.mesh_normals(vx, vt)
+                stage["mesh_normals"] = clock() - t0
             self.mesh = (vx, vr, vt)
             self.stats["mesh_vertices"] = len(vx)
             self.stats["mesh_triangles"] = len(vt)
@@ -731,6 +741,7 @@ class DepthToReconstructionPipeline:
         self._check_mesh_filter_config()
         world, rank = dist.get_world_size(), dist.get_rank()
         self.mesh = None
+        self.mesh_normals = None
         if len(self.images) < 2:
             print("Need at least 2 images")
             return None, None, None
@@ -865,6 +876,14 @@ class DepthToReconstructionPipeline:
                         self.mesh = self._simplify_mesh(ctx, self.mesh)
                         self.stats["mesh_vertices"], self.stats["mesh_triangles"] = len(self.mesh[0]), len(self.mesh[2])
                         self.timings["mesh_simplify_s"] = round(time.perf_counter() - t0, 4)
+                    if self._mesh_smooth_on():
+                        t0 = time.perf_counter()
+                        self.mesh = self._smooth_mesh(ctx, self.mesh)
+                        self.timings["mesh_smooth_s"] = round(time.perf_counter() - t0, 4)
+                    if cfg.mesh_normals:
+                        t0 = time.perf_counter()
+                        self.mesh_normals = ctx.mesh_normals(self.mesh[0], self.mesh[2])
+                        self.timings["mesh_normals_s"] = round(time.perf_counter() - t0, 4)
                 say(f"\nFinal reconstruction: {len(xyz)} points, {len(self.camera_poses)} cameras")
                 xyz = xyz.astype(np.float64)
         finally:
@@ -913,6 +932,30 @@ class DepthToReconstructionPipeline:
             raise ValueError(f"mesh_simplify_cell = {cell}: must be a finite size in metres, or 0 for none")
         if cell > 0.0 and not self.config.extract_mesh:
             raise ValueError("mesh_simplify_cell simplifies the mesh: it needs extract_mesh = True")
+
+        it = getattr(self.config, "mesh_smooth_iterations", 0)
+        lam, mu = float(getattr(self.config, "mesh_smooth_lambda", 0.5)), float(getattr(self.config, "mesh_smooth_mu", -0.53))
+        if isinstance(it, bool) or int(it) != it or not 0 <= int(it) <= 1000:
+            raise ValueError(f"mesh_smooth_iterations = {it}: must be a whole number in [0, 1000]")
+        if not 0.0 < lam <= 1.0:                         # (false for NaN)
+            raise ValueError(f"mesh_smooth_lambda = {lam}: must lie in (0, 1]")
+        if not -2.0 <= mu <= 0.0:
+            raise ValueError(f"mesh_smooth_mu = {mu}: must lie in [-2, 0]")
+        if (int(it) > 0 or bool(getattr(self.config, "mesh_normals", False))) and not self.config.extract_mesh:
+            raise ValueError("mesh_smooth_iterations / mesh_normals work on the mesh: they need extract_mesh = True")
+
+    def _mesh_smooth_on(self) -> bool:
+        return int(getattr(self.config, "mesh_smooth_iterations", 0)) > 0
+
+    def _smooth_mesh(self, ctx: FusionContext, mesh):
+        """The mesh with its positions smoothed by config.mesh_smooth_iterations Taubin iterations (FusionContext.smooth_mesh,
+        DESIGN.md section 4.2.3); colours and triangles are passed through.  stats["mesh_smooth"] says what ran."""
+        cfg = self.config
+        it, lam, mu = int(cfg.mesh_smooth_iterations), float(cfg.mesh_smooth_lambda), float(cfg.mesh_smooth_mu)
+        xyz, info = ctx.smooth_mesh(mesh[0], mesh[2], it, lam=lam, mu=mu)
+        self.stats["mesh_smooth"] = dict(iterations=it, mu=mu, edges=info["edges"], max_valence=info["max_valence"], **{"lambda": lam})
+        print(f"  Mesh smooth: {it} iterations (lambda {lam:g}, mu {mu:g}) over {info['edges']} edges, largest valence {info['max_valence']}")
+        return xyz, mesh[1], mesh[2]
 
     def _mesh_simplify_on(self) -> bool:
         return float(getattr(self.config, "mesh_simplify_cell", 0.0)) > 0.0
@@ -967,7 +1010,7 @@ class DepthToReconstructionPipeline:
         """Writes the mesh of the last reconstruct() (config.extract_mesh) as PLY (fileio.write_ply_mesh)."""
         if self.mesh is None:
             raise ValueError("no mesh: run reconstruct() with config.extract_mesh = True")
-        fileio.write_ply_mesh(path, *self.mesh, ascii=ascii)
+        fileio.write_ply_mesh(path, *self.mesh, ascii=ascii, normals=self.mesh_normals)
         print(f"Saved mesh to {path}")
 
     def save_reconstruction(self, points, colors, output_path: str, ascii: bool = False):
