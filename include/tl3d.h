@@ -351,7 +351,21 @@ int tl3d_grid_max_weight(tl3d_ctx *ctx, int64_t *out);
  * memory, ascending brick indices) of ONE channel into `packed` (n x 4 KB for TL3D_CH_TSDF, n x 16 KB for TL3D_CH_CENTROID, device
  * memory); tl3d_grid_unpack_bricks writes such a block back (after the SUM all-reduce).  tl3d.distributed.merge_context_grids and
  * tl3d_allreduce_grid use them when fewer than half of the bricks are touched; tl3d.distributed passes TL3D_CH_FREE with the TSDF
- * channel and sums the counts separately (config-5 shape, 32 frames: 29 % of the bricks hold free-space counts, a few per cent records). */
+ * channel and sums the counts separately (config-5 shape, 32 frames: 29 % of the bricks hold free-space counts, a few per cent records).
+ *
+ * The contract (tests/test_gpu_grid_merge.py holds each of these against an integer model):
+ *  - row order is record order: the row of brick b is records [512 b, 512 b + 512); with TL3D_CH_SUB the row of id 8 b + s is
+ *    records [512 b + 64 s, + 64), the 4x4x4 cube s = x >> 2 | (y >> 2) << 1 | (z >> 2) << 2 of the brick;
+ *  - unpack SETS the listed rows to the block (it does not add: the caller has summed) and leaves every other record alone;
+ *  - ids must be ascending, unique and below the row count (nx ny nz / 512, times 8 with TL3D_CH_SUB).  n and the pointers are
+ *    checked on the host (TL3D_E_INVALID); the ids themselves are NOT validated on the device: an id out of range is an
+ *    out-of-bounds access, a duplicate id given to unpack a race between two rows;
+ *  - a sparse grid draws pool slots ON RECEIPT: unpack (like tl3d_grid_add and tl3d_grid_upload) gives a brick without records a
+ *    slot when its row holds a non-zero word; a row of zeros draws none; pack gives zeros for a brick without records.  With the
+ *    pool exhausted the row is dropped and the brick counted once in tl3d_stats.pool_refused (it reads as untouched afterwards);
+ *  - without TL3D_CH_FREE the pending free-space counts are folded into the records first (a brick of a sparse grid that has no
+ *    records keeps its count: pack gives zeros for it and touched_bricks does not mark it); with TL3D_CH_FREE nothing is folded,
+ *    a brick that holds nothing but a count is not marked and its rows are the records alone. */
 int tl3d_grid_touched_bricks(tl3d_ctx *ctx, uint32_t channels, uint8_t *map_dev, int64_t n_bricks);
 int tl3d_grid_pack_bricks(tl3d_ctx *ctx, uint32_t channel, const uint32_t *bricks_dev, int64_t n, void *packed_dev);
 int tl3d_grid_unpack_bricks(tl3d_ctx *ctx, uint32_t channel, const uint32_t *bricks_dev, int64_t n, const void *packed_dev);

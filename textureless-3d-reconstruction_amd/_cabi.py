@@ -203,6 +203,9 @@ def load():
         "tl3d_grid_download": [vp, u32, vp, C.c_size_t],
         "tl3d_grid_upload": [vp, u32, vp, C.c_size_t],
         "tl3d_grid_add": [vp, u32, vp, C.c_size_t],
+        "tl3d_grid_touched_bricks": [vp, u32, vp, i64],
+        "tl3d_grid_pack_bricks": [vp, u32, vp, i64, vp],
+        "tl3d_grid_unpack_bricks": [vp, u32, vp, i64, vp],
         "tl3d_rccl_unique_id": [vp],
         "tl3d_rccl_init": [vp, i32, i32, vp],
         "tl3d_allreduce_grid": [vp, u32],

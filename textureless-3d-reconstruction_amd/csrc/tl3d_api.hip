@@ -2167,6 +2167,7 @@ int tl3d_grid_add(tl3d_ctx *ctx, uint32_t channel, const void *other, size_t byt
         if (rc == TL3D_OK) {
             ctx->tsdf_w_upper = wa + wb;
             ctx->tsdf_w_unknown = false;
+            if (ctx->sparse && ctx->free_cnt) ctx->free_dirty = true;       // (as unpack: the next read folds the counts of bricks that get records here)
             rc = ctx->sparse ? launch_brick_rows(ctx->stream, ctx->grid, 2, true, p, nullptr, (long long)(ctx->nvox >> 9), const_cast<void *>(src), false)
                              : launch_add_i32(ctx->stream, (int *)p, (const int *)src, nb / 4);
         }
@@ -2210,7 +2211,10 @@ static int brick_rows(tl3d_ctx *ctx, uint32_t channel, const uint32_t *bricks_de
     else FLUSH_AND_FOLD(ctx);
     ctx->grid_epoch++;
     TL3D_HIP(hipSetDevice(ctx->device));
-    if (!pack && channel == TL3D_CH_TSDF) ctx->tsdf_w_unknown = true;      // the records now hold what the caller summed
+    if (!pack && channel == TL3D_CH_TSDF) {
+        ctx->tsdf_w_unknown = true;                                         // the records now hold what the caller summed
+        if (ctx->sparse && ctx->free_cnt) ctx->free_dirty = true;           // a brick that kept its count for want of records may get records now
+    }
     return launch_brick_rows(ctx->stream, ctx->grid, pack ? 0 : 1, channel == TL3D_CH_TSDF, p, bricks_dev, n, packed_dev, false, sub);
 }
 

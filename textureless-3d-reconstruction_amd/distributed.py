@@ -176,6 +176,8 @@ def allreduce_context_grids(ctx, dist, sparse: bool = True) -> dict:
                 if ctx.grid.sparse:                           # no dense layout to view: every sub-brick of the channel
                     idx = torch.arange(8 * nbr, dtype=torch.int32, device=dev)
                 else:
+                    if free_apart and channel == abi.CH_TSDF and dist.get_rank() != 0:
+                        cnt.zero_()                           # every rank holds the SUMMED counts and the view below folds them: once, on rank 0
                     t = ctx.grid_tensor(channel)              # (TSDF: folds the pending counts into the records first, on the context's stream)
                     reduce_(t)
                     sent[channel] = 8 * nbr
