@@ -83,6 +83,9 @@ def main(argv=None):
                         help="smooth the mesh with N Taubin iterations (after the component filter and the simplification; needs --mesh-output)")
     parser.add_argument("--mesh-normals", action="store_true",
                         help="write area-weighted vertex normals (nx ny nz) into the mesh PLY (needs --mesh-output)")
+    parser.add_argument("--mesh-weld", choices=("host", "device"), default="host",
+                        help="where the meshes of a scene fused block by block are welded: in numpy on the host (default), or on the "
+                             "GPU, the same bytes (needs --mesh-output)")
     parser.add_argument("--render-output", type=str, default=None,
                         help="also render the fused model at every kept camera into this folder: <stem>_model_depth.npy / .png "
                              "(metres / u16 millimetres) and <stem>_model_color.png (one GPU only)")
@@ -111,6 +114,8 @@ def main(argv=None):
         parser.error("--mesh-simplify-cell simplifies the mesh: it needs --mesh-output")
     if (args.mesh_smooth != 0 or args.mesh_normals) and not args.mesh_output:
         parser.error("--mesh-smooth / --mesh-normals work on the mesh: they need --mesh-output")
+    if args.mesh_weld != "host" and not args.mesh_output:
+        parser.error("--mesh-weld device welds the mesh: it needs --mesh-output")
     if args.loop_closure and (args.gpus > 1 or world > 1):
         parser.error("--loop-closure needs a single GPU: every kept frame must be resident where the revisits are registered")
     if args.loop_closure and args.estimate_scale:
@@ -136,7 +141,7 @@ def main(argv=None):
                                   render_dir=args.render_output, loop_closure=args.loop_closure,
                                   model_tracking=args.model_tracking, mesh_min_component_triangles=max(0, args.mesh_min_component),
                                   mesh_largest_component=args.mesh_largest_component, mesh_simplify_cell=args.mesh_simplify_cell,
-                                  mesh_smooth_iterations=args.mesh_smooth, mesh_normals=args.mesh_normals)
+                                  mesh_smooth_iterations=args.mesh_smooth, mesh_normals=args.mesh_normals, mesh_weld=args.mesh_weld)
     pipeline = DepthToReconstructionPipeline(config)
     # a rank decodes every frame on its host (pose chain and scale rule run over the whole sequence) and uploads its share
     streaming = args.stream and dist is None

@@ -494,6 +494,42 @@ int tl3d_mesh_smooth_taubin(tl3d_ctx *ctx, const float *xyz_hd, int64_t n_vert, 
 int tl3d_mesh_vertex_normals(tl3d_ctx *ctx, const float *xyz_hd, int64_t n_vert, const uint32_t *tri_hd, int64_t n_tri,
                              float *out_normal_hd, int64_t *out_n_zero);
 
+/* The weld of the keyed meshes of a lattice's blocks into one mesh: n_parts meshes as tl3d_extract_mesh_keyed
+ * writes them, each with the core [core_lo, core_hi) of its block in LATTICE voxels (the call needs no grid).  No reference code:
+ * the reference has no mesh; the result is a function of the input alone, the same bytes in every run.
+ * Owner voxel of a key: idx = key / 3, x = idx % Lx, y = (idx / Lx) % Ly, z = idx / (Lx Ly).  Vertex v of part p is KEPT iff its
+ * owner voxel lies in the part's core.  The output vertices (xyz, rgb, key) are the kept ones, in part order, then in the part's
+ * vertex order: kept vertices that no triangle names stay; the copies that are not kept (halo copies) go, named by a triangle or
+ * not.  The output triangles are all triangles of all parts, in part order, then triangle order, neither rotated nor dropped;
+ * corner i of a triangle of part p becomes the output index of the kept vertex whose key equals key_p[i], in whichever part it is.
+ * *out_n_twice = kept vertices minus distinct kept keys; *out_n_unowned = triangle corners whose key no kept vertex has.  Either
+ * non-zero: TL3D_E_INVALID ("a vertex is owned by two block cores" / "a triangle references a vertex no block core owns") with
+ * all four counts stored and the output arrays unspecified.
+ * Host or device pointers throughout (the part array itself is host memory).  rgb_hd is given in every part or in none (parts
+ * without vertices do not count); out_rgb_hd is required with rgb, and neither read nor written (it may be NULL) without;
+ * out_key_hd may be NULL.  No size query: vert_cap =
+ * the sum of n_vert and tri_cap = the sum of n_tri always suffice; short capacities, or 2^31 kept vertices or more, give
+ * TL3D_E_CAPACITY with the vertex and triangle counts stored.
+ * TL3D_E_INVALID, decided before any device call: a null argument, n_parts < 0, a negative size or capacity, a part with n_vert >=
+ * 2^31 or n_tri >= 2^32, 2^32 triangles or more in all, a lattice dimension <= 0 or a lattice of 2^61 voxels or more, a core with
+ * lo < 0, lo > hi or hi > L (an empty core is allowed and owns nothing; cores need not be multiples of 8 and need not tile the
+ * lattice), rgb in some parts only, an output that overlaps an input, a null ctx.  From a pass of its own in front of every indexed
+ * access: a triangle index >= its part's n_vert, a key outside [0, 3 Lx Ly Lz).  n_parts == 0, or no vertex in any part, is
+ * TL3D_OK with empty outputs. */
+typedef struct tl3d_mesh_part {
+    const float   *xyz_hd;      /* [n_vert][3]                                   */
+    const uint8_t *rgb_hd;      /* [n_vert][3], or NULL in EVERY part            */
+    const int64_t *key_hd;      /* [n_vert], as tl3d_extract_mesh_keyed writes   */
+    int64_t        n_vert;
+    const uint32_t *tri_hd;     /* [n_tri][3], indices into THIS part            */
+    int64_t        n_tri;
+    int64_t        core_lo[3], core_hi[3];   /* the part's core [lo, hi) in LATTICE voxels */
+} tl3d_mesh_part;
+int tl3d_mesh_weld_keyed(tl3d_ctx *ctx, const tl3d_mesh_part *parts, int n_parts, const int64_t lattice_dims[3],
+                         float *out_xyz_hd, uint8_t *out_rgb_hd, int64_t *out_key_hd, int64_t vert_cap,
+                         uint32_t *out_tri_hd, int64_t tri_cap,
+                         int64_t *out_n_vert, int64_t *out_n_tri, int64_t *out_n_twice, int64_t *out_n_unowned);
+
 /* ray casting of the TSDF channel from one camera: one ray per pixel of the context's camera, pose (R, t)
  * world->camera as tl3d_integrate.  depth [H][W] f32 (0 = no hit), normals [H][W][3] f32 in the camera frame facing the
  * camera ((0,0,0) where undefined), colour [H][W][3] BGR (TSDF-mode extraction colour of the hit voxel, 128 without one).

@@ -68,6 +68,10 @@ class ReconstructionConfig:
     mesh_smooth_lambda: float = 0.5
     mesh_smooth_mu: float = -0.53
     mesh_normals: bool = False
+    # where the meshes of a blocked run's blocks are welded ("device" needs extract_mesh): "host" is
+    # lattice.weld_meshes (numpy), "device" FusionContext.weld_meshes, the same bytes.  No effect on a run of one block (nothing to
+    # weld) or in reconstruct_sharded (never blocked).
+    mesh_weld: str = "host"
     # folder for renders of the fused model at every kept camera (DepthToReconstructionPipeline.reconstruct)
     render_dir: Optional[str] = None
     # loop closure: revisits found from the chain's poses, registered with the same ICP, and every pose

@@ -408,6 +408,10 @@ static void release_grid(tl3d_ctx *ctx) {
     if (gs.adj_xyz) (void)hipFree(gs.adj_xyz);
     if (gs.adj_ccounts) (void)hipFree(gs.adj_ccounts);
     if (gs.adj_coffs) (void)hipFree(gs.adj_coffs);
+    if (gs.wm_keys) (void)hipFree(gs.wm_keys);
+    if (gs.wm_vals) (void)hipFree(gs.wm_vals);
+    if (gs.wm_vmap) (void)hipFree(gs.wm_vmap);
+    if (gs.wm_parts) (void)hipFree(gs.wm_parts);
     if (gs.mio_counts) (void)hipFree(gs.mio_counts);
     if (gs.mio_offsets) (void)hipFree(gs.mio_offsets);
     if (gs.mio_info) (void)hipFree(gs.mio_info);
@@ -3102,6 +3106,179 @@ int tl3d_mesh_vertex_normals(tl3d_ctx *ctx, const float *xyz, int64_t n_vert, co
     rc = st.finish(TL3D_OK, true);
     if (rc) return rc;
     *out_n_zero = (int64_t)h[3];
+    return TL3D_OK;
+}
+
+// ------------------------------------------------------------------------------------------- mesh weld
+static size_t wm_table_slots(int64_t kept) {
+    size_t cap = 1024;
+    while (cap < 2 * (size_t)kept) cap <<= 1;              // load <= 0.5
+    return cap;
+}
+
+// Waits for the stream three times, however many parts there are: behind the validation pass, behind the scan (the number kept sizes
+// the table and is compared with the capacity), and at the end.
+int tl3d_mesh_weld_keyed(tl3d_ctx *ctx, const tl3d_mesh_part *parts, int n_parts, const int64_t lattice_dims[3], float *out_xyz,
+                         uint8_t *out_rgb, int64_t *out_key, int64_t vert_cap, uint32_t *out_tri, int64_t tri_cap, int64_t *out_n_vert,
+                         int64_t *out_n_tri, int64_t *out_n_twice, int64_t *out_n_unowned) {
+    const char *what = "mesh weld scratch";
+    REQUIRE(lattice_dims && out_n_vert && out_n_tri && out_n_twice && out_n_unowned && (n_parts <= 0 || parts), TL3D_E_INVALID, "null argument");
+    REQUIRE(n_parts >= 0, TL3D_E_INVALID, "n_parts %d is negative", n_parts);
+    REQUIRE(vert_cap >= 0 && tri_cap >= 0, TL3D_E_INVALID, "negative capacity");
+    int64_t nv_tot = 0, nt_tot = 0;
+    int with_rgb = 0, with_verts = 0;
+    for (int p = 0; p < n_parts; ++p) {
+        const tl3d_mesh_part &m = parts[p];
+        REQUIRE(m.n_vert >= 0 && m.n_tri >= 0, TL3D_E_INVALID, "part %d: negative size (n_vert %lld, n_tri %lld)", p, (long long)m.n_vert,
+                (long long)m.n_tri);
+        REQUIRE(m.n_vert < (1ll << 31), TL3D_E_INVALID, "part %d: n_vert %lld: indices need fewer than 2^31 vertices", p, (long long)m.n_vert);
+        REQUIRE(m.n_tri < (1ll << 32), TL3D_E_INVALID, "part %d: n_tri %lld: needs fewer than 2^32 triangles", p, (long long)m.n_tri);
+        REQUIRE((m.n_vert == 0 || (m.xyz_hd && m.key_hd)) && (m.n_tri == 0 || m.tri_hd), TL3D_E_INVALID, "null argument (part %d)", p);
+        nv_tot += m.n_vert;
+        nt_tot += m.n_tri;
+        with_verts += m.n_vert > 0;
+        with_rgb += m.n_vert > 0 && m.rgb_hd;
+    }
+    REQUIRE(nt_tot < (1ll << 32), TL3D_E_INVALID, "%lld triangles in all: the welded mesh needs fewer than 2^32 triangles", (long long)nt_tot);
+    REQUIRE(nv_tot < (1ll << 40), TL3D_E_INVALID, "%lld vertices in all: the weld needs fewer than 2^40 input vertices", (long long)nv_tot);
+    unsigned __int128 nlat = 1;
+    for (int a = 0; a < 3; ++a) {
+        REQUIRE(lattice_dims[a] > 0, TL3D_E_INVALID, "lattice of %lld voxels on axis %d", (long long)lattice_dims[a], a);
+        nlat *= (unsigned __int128)lattice_dims[a];
+        REQUIRE(nlat < ((unsigned __int128)1 << 61), TL3D_E_INVALID, "lattice of 2^61 voxels or more: mesh keys would overflow");
+    }
+    for (int p = 0; p < n_parts; ++p)
+        for (int a = 0; a < 3; ++a)
+            REQUIRE(parts[p].core_lo[a] >= 0 && parts[p].core_lo[a] <= parts[p].core_hi[a] && parts[p].core_hi[a] <= lattice_dims[a], TL3D_E_INVALID,
+                    "part %d: core [%lld, %lld) on axis %d must be a range within the lattice's %lld voxels", p, (long long)parts[p].core_lo[a],
+                    (long long)parts[p].core_hi[a], a, (long long)lattice_dims[a]);
+    REQUIRE(with_rgb == 0 || with_rgb == with_verts, TL3D_E_INVALID, "rgb given in some parts only (%d of %d)", with_rgb, with_verts);
+    const bool rgb = with_rgb > 0;
+    REQUIRE((vert_cap == 0 || (out_xyz && (out_rgb || !rgb))) && (tri_cap == 0 || out_tri), TL3D_E_INVALID, "null output with a capacity");
+    {
+        const void *outs[4] = {out_xyz, rgb ? out_rgb : nullptr, out_key, out_tri};
+        const size_t out_b[4] = {(size_t)vert_cap * 12, (size_t)vert_cap * 3, (size_t)vert_cap * 8, (size_t)tri_cap * 12};
+        for (int p = 0; p < n_parts; ++p) {
+            const tl3d_mesh_part &m = parts[p];
+            const void *ins[4] = {m.xyz_hd, m.rgb_hd, m.key_hd, m.tri_hd};
+            const size_t in_b[4] = {(size_t)m.n_vert * 12, (size_t)m.n_vert * 3, (size_t)m.n_vert * 8, (size_t)m.n_tri * 12};
+            for (int o = 0; o < 4; ++o)
+                for (int i = 0; i < 4; ++i)
+                    REQUIRE(!ranges_overlap(outs[o], out_b[o], ins[i], in_b[i]), TL3D_E_INVALID, "an output aliases an input (part %d)", p);
+        }
+    }
+    REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
+    *out_n_vert = *out_n_tri = *out_n_twice = *out_n_unowned = 0;
+    if (n_parts == 0 || nv_tot == 0) return TL3D_OK;
+    TL3D_HIP(hipSetDevice(ctx->device));
+    int rc = mio_grow(ctx, 0, nv_tot, what);
+    if (!rc) rc = grow(&ctx->wm_vmap, &ctx->wm_verts, (size_t)nv_tot, what);
+    if (!rc) rc = grow(&ctx->wm_parts, &ctx->wm_parts_n, (size_t)n_parts + 1, what);
+    if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    // the inputs: a device array is read where it is; the host arrays of a kind are uploaded into one temporary, part behind part
+    // (desc is declared in front of st: it is uploaded asynchronously, and st's destructor is what waits for the stream on every
+    // way out.  st holds at most 4 input temporaries and 4 output temporaries: exactly Staging's MAX.)
+    std::vector<WeldPart> desc((size_t)n_parts + 1);
+    Staging st(ctx);
+    {
+        const size_t unit[4] = {12, 3, 8, 12};
+        size_t host_b[4] = {0, 0, 0, 0};
+        std::vector<uint8_t> on_host((size_t)n_parts * 4, 0);
+        for (int p = 0; p < n_parts; ++p) {
+            const tl3d_mesh_part &m = parts[p];
+            const void *ins[4] = {m.xyz_hd, rgb ? m.rgb_hd : nullptr, m.key_hd, m.tri_hd};
+            const size_t in_b[4] = {(size_t)m.n_vert * 12, (size_t)m.n_vert * 3, (size_t)m.n_vert * 8, (size_t)m.n_tri * 12};
+            for (int k = 0; k < 4; ++k)
+                if (ins[k] && in_b[k] && !is_device_ptr(ins[k])) {
+                    on_host[(size_t)p * 4 + k] = 1;
+                    host_b[k] += in_b[k];
+                }
+        }
+        uint8_t *slab[4] = {nullptr, nullptr, nullptr, nullptr};
+        for (int k = 0; k < 4 && !rc; ++k)
+            if (host_b[k]) rc = st.scratch(host_b[k], &slab[k]);
+        if (rc) return rc;
+        size_t used[4] = {0, 0, 0, 0};
+        unsigned long long v0 = 0, t0 = 0;
+        for (int p = 0; p < n_parts; ++p) {
+            const tl3d_mesh_part &m = parts[p];
+            const void *ins[4] = {m.xyz_hd, rgb ? m.rgb_hd : nullptr, m.key_hd, m.tri_hd};
+            const size_t cnt[4] = {(size_t)m.n_vert, (size_t)m.n_vert, (size_t)m.n_vert, (size_t)m.n_tri};
+            for (int k = 0; k < 4; ++k)
+                if (on_host[(size_t)p * 4 + k]) {
+                    void *d = slab[k] + used[k];
+                    TL3D_HIP(hipMemcpyAsync(d, ins[k], cnt[k] * unit[k], hipMemcpyHostToDevice, s));
+                    used[k] += cnt[k] * unit[k];
+                    ins[k] = d;
+                }
+            WeldPart &w = desc[(size_t)p];
+            w.xyz = (const float *)ins[0];
+            w.rgb = (const uint8_t *)ins[1];
+            w.key = (const long long *)ins[2];
+            w.tri = (const unsigned *)ins[3];
+            w.v0 = v0;
+            w.t0 = t0;
+            for (int a = 0; a < 3; ++a) {
+                w.lo[a] = (long long)m.core_lo[a];
+                w.hi[a] = (long long)m.core_hi[a];
+            }
+            v0 += (unsigned long long)m.n_vert;
+            t0 += (unsigned long long)m.n_tri;
+        }
+        memset(&desc[(size_t)n_parts], 0, sizeof(WeldPart));
+        desc[(size_t)n_parts].v0 = v0;
+        desc[(size_t)n_parts].t0 = t0;
+        TL3D_HIP(hipMemcpyAsync(ctx->wm_parts, desc.data(), desc.size() * sizeof(WeldPart), hipMemcpyHostToDevice, s));
+    }
+    const long long lat[3] = {(long long)lattice_dims[0], (long long)lattice_dims[1], (long long)lattice_dims[2]};
+    const unsigned long long nv = (unsigned long long)nv_tot, nt = (unsigned long long)nt_tot;
+    // the validation pass: nothing is indexed, and no key is taken apart, before the host has seen its words
+    unsigned long long h[5] = {0, 0, 0, 0, 0};
+    TL3D_HIP(hipMemsetAsync(ctx->mio_info, 0, 8 * sizeof(unsigned long long), s));
+    rc = launch_wm_validate(s, ctx->wm_parts, n_parts, nv, nt, 3ull * (unsigned long long)nlat, ctx->mio_info);
+    if (rc) return rc;
+    TL3D_HIP(hipMemcpyAsync(h, ctx->mio_info, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    TL3D_HIP(hipStreamSynchronize(s));
+    REQUIRE(h[0] == 0, TL3D_E_INVALID, "%llu triangle indices out of range (the largest: %llu in part %llu, which has %lld vertices)", h[0],
+            h[2] & 0xffffffffull, h[2] >> 32, (long long)parts[h[2] >> 32].n_vert);
+    REQUIRE(h[1] == 0, TL3D_E_INVALID, "%llu keys outside [0, 3 * %llu lattice voxels)", h[1], (unsigned long long)nlat);
+    // the kept vertices
+    const int chunks = chunks_of(nv);
+    unsigned long long kept = 0;
+    rc = launch_wm_own_count(s, ctx->wm_parts, n_parts, nv, lat, ctx->mio_counts, ctx->mio_offsets);
+    if (rc) return rc;
+    TL3D_HIP(hipMemcpyAsync(&kept, ctx->mio_offsets + chunks, sizeof(kept), hipMemcpyDeviceToHost, s));
+    TL3D_HIP(hipStreamSynchronize(s));
+    *out_n_vert = (int64_t)kept;
+    *out_n_tri = nt_tot;
+    REQUIRE(kept < (1ull << 31), TL3D_E_CAPACITY, "%llu kept vertices: triangle indices need fewer than 2^31", kept);
+    if ((int64_t)kept > vert_cap || nt_tot > tri_cap)
+        return set_err(TL3D_E_CAPACITY, "need %llu vertices / %lld triangles, capacities %lld / %lld", kept, (long long)nt_tot, (long long)vert_cap,
+                       (long long)tri_cap);
+    float *oxyz = nullptr;
+    uint8_t *orgb = nullptr;
+    int64_t *okey = nullptr;
+    uint32_t *otri = nullptr;
+    rc = st.out(out_xyz, (size_t)kept * 12, &oxyz);
+    if (!rc && rgb) rc = st.out(out_rgb, (size_t)kept * 3, &orgb);
+    if (!rc && out_key) rc = st.out(out_key, (size_t)kept * 8, &okey);
+    if (!rc) rc = st.out(out_tri, (size_t)nt * 12, &otri);
+    const size_t slots = wm_table_slots((int64_t)kept);
+    if (!rc) rc = grow_pair(&ctx->wm_keys, &ctx->wm_vals, &ctx->wm_slots, slots, what);
+    if (rc) return rc;
+    TL3D_HIP(hipMemsetAsync(ctx->wm_keys, 0xFF, slots * sizeof(unsigned long long), s));
+    rc = launch_wm_own_write(s, ctx->wm_parts, n_parts, nv, lat, ctx->mio_offsets, oxyz, orgb, (long long *)okey, kept, ctx->wm_vmap, ctx->wm_keys,
+                             ctx->wm_vals, slots, ctx->mio_info);
+    if (!rc) rc = launch_wm_resolve(s, ctx->wm_parts, n_parts, nt, ctx->wm_vmap, ctx->wm_keys, ctx->wm_vals, slots, otri, ctx->mio_info);
+    if (rc) return rc;
+    TL3D_HIP(hipMemcpyAsync(h, ctx->mio_info, sizeof(h), hipMemcpyDeviceToHost, s));
+    rc = st.finish(TL3D_OK, true);
+    if (rc) return rc;
+    *out_n_twice = (int64_t)h[3];
+    *out_n_unowned = (int64_t)h[4];
+    REQUIRE(h[3] == 0, TL3D_E_INVALID, "a vertex is owned by two block cores (%llu kept vertices repeat a key: the cores overlap)", h[3]);
+    REQUIRE(h[4] == 0, TL3D_E_INVALID, "a triangle references a vertex no block core owns (%llu corners: a halo is missing)", h[4]);
     return TL3D_OK;
 }
 

@@ -176,6 +176,17 @@ struct Slot {
     bool has_normals = false;
 };
 
+// One part of a mesh weld (kernels_meshweld.hip) as the kernels see it: the part's arrays in device memory and the vertices and
+// triangles of the parts in front of it.  The list has one entry more than parts: its v0 / t0 are the totals.
+struct WeldPart {
+    const float *xyz;
+    const uint8_t *rgb;          // null in every part or in none
+    const long long *key;
+    const unsigned *tri;
+    unsigned long long v0, t0;
+    long long lo[3], hi[3];      // the core [lo, hi) in lattice voxels
+};
+
 constexpr int ICP_MAX_BLOCKS = 256;     // one reduce workgroup per CU; the solve sums the slab serially
 constexpr int ICP_SLAB = 40;     // doubles per block partial: 30 sums of the pose system (+ 2 unused), 8 of the scale column
 
@@ -259,6 +270,16 @@ struct tl3d_grid_state {
     size_t adj_xyz_n;                       // in floats
     unsigned long long *adj_ccounts, *adj_coffs;
     size_t adj_chunks;                      // capacity of both, in entries
+    // tl3d_mesh_weld_keyed: the key table (a 64-bit key and the kept vertex's output index per slot, a
+    // power of two >= 2 * kept slots), per input vertex its output index or NONE, the part descriptors.  Grid-independent like the
+    // cc_ scratch, and here for the same reason.
+    unsigned long long *wm_keys;
+    unsigned *wm_vals;
+    size_t wm_slots;                        // capacity of both, in slots
+    unsigned *wm_vmap;
+    size_t wm_verts;
+    tl3d::WeldPart *wm_parts;
+    size_t wm_parts_n;
     // What the mesh-in / mesh-out calls above share, none of it live across calls: counts and offsets per chunk of vertices /
     // triangles, and the eight words their kernels report through, zeroed by each call before use:
     //   word   tl3d_mesh_components / _filter_components       tl3d_mesh_simplify_clusters   tl3d_mesh_smooth_taubin / _vertex_normals
@@ -267,6 +288,8 @@ struct tl3d_grid_state {
     //   [2]    key of the largest component (cc_roots_kernel)  degenerate triangles          unique edges
     //   [3]    kept components                                 duplicate triangles           a step left the range / zero normals
     //   [4]                                                                                  a step left the range (steps take [3], [4] in turn)
+    // tl3d_mesh_weld_keyed: [0] indices out of range, [1] keys out of range, [2] the largest offending (part << 32 | index),
+    // [3] vertices owned twice, [4] unowned corners
     unsigned *mio_counts;                   // [vertex chunks + 1][triangle chunks + 1]
     unsigned long long *mio_offsets;
     size_t mio_chunks;                      // capacity of both, in entries
@@ -624,6 +647,17 @@ int launch_msm_corners(hipStream_t s, const unsigned *tri, long long n_tri, long
                        unsigned long long *coffs, unsigned long long *row, unsigned *cursor, unsigned *inc);
 int launch_msm_normals(hipStream_t s, const float *xyz, const unsigned *tri, long long n_vert, const unsigned *cnt, const unsigned long long *row,
                        const unsigned *inc, float *out, unsigned long long *info);
+
+// mesh weld (kernels_meshweld.hip)
+int launch_wm_validate(hipStream_t s, const WeldPart *parts, int n_parts, unsigned long long n_vert, unsigned long long n_tri,
+                       unsigned long long key_end, unsigned long long *info);
+int launch_wm_own_count(hipStream_t s, const WeldPart *parts, int n_parts, unsigned long long n_vert, const long long lat[3], unsigned *counts,
+                        unsigned long long *offsets);
+int launch_wm_own_write(hipStream_t s, const WeldPart *parts, int n_parts, unsigned long long n_vert, const long long lat[3],
+                        const unsigned long long *offsets, float *out_xyz, uint8_t *out_rgb, long long *out_key, unsigned long long vcap,
+                        unsigned *vert_map, unsigned long long *keys, unsigned *vals, unsigned long long slots, unsigned long long *info);
+int launch_wm_resolve(hipStream_t s, const WeldPart *parts, int n_parts, unsigned long long n_tri, const unsigned *vert_map,
+                      const unsigned long long *keys, const unsigned *vals, unsigned long long slots, unsigned *out_tri, unsigned long long *info);
 
 constexpr int EXTRACT_CHUNK = 2048;   // elements per block in the compaction passes (compact.h)
 inline unsigned blocks_of(unsigned long long n, unsigned per) { return (unsigned)((n + per - 1) / per); }

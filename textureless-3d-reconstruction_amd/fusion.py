@@ -796,6 +796,63 @@ class FusionContext:
                                                      abi.ptr(out) if nv else None, C.byref(nz)))
         return out
 
+    def weld_meshes(self, parts, lattice_dims):
+        """One mesh from the keyed meshes of the blocks of a lattice, welded on the device (needs no grid):
+        what lattice.weld_meshes computes on the host, byte for byte.  parts: [(xyz, rgb, tris, keys, core_lo, core_hi)] with the
+        core in LATTICE voxels; every vertex whose owner voxel lies in its part's core is kept, in part order, and every triangle
+        corner becomes the output index of the kept vertex with the corner's key.  rgb may be None, in every part or in none.  All
+        parts numpy arrays (numpy out), or all torch device tensors (indices int32, keys int64; device tensors out).  Raises
+        abi.Tl3dError when a vertex is owned by two cores or a triangle names a vertex no core owns.
+        Returns (xyz, rgb, tris, keys)."""
+        parts = list(parts)
+        kinds = {hasattr(p[2], "data_ptr") for p in parts}
+        if len(kinds) > 1:
+            raise TypeError("weld_meshes: the parts must be all numpy arrays or all torch tensors")
+        on_device = kinds == {True}
+        rgbs = {p[1] is None for p in parts}
+        if len(rgbs) > 1:
+            raise ValueError("weld_meshes: rgb is given in every part or in none")
+        has_rgb = rgbs != {True}                         # (no part at all: an empty colour array, as the host weld returns)
+        arr = (abi.MeshPart * max(1, len(parts)))()
+        hold = []
+        for m, (xyz, rgb, tris, keys, lo, hi) in zip(arr, parts):
+            xyz, rgb, tris, _ = self._mesh_arrays(xyz, rgb, tris)
+            if on_device:
+                import torch
+                keys = keys.to(device=tris.device, dtype=torch.int64).reshape(-1).contiguous()
+            else:
+                keys = np.ascontiguousarray(keys, dtype=np.int64).reshape(-1)
+            if len(keys) != len(xyz) or (rgb is not None and len(rgb) != len(xyz)):
+                raise ValueError(f"weld_meshes: a part has {len(xyz)} vertices, {len(keys)} keys"
+                                 + ("" if rgb is None else f" and {len(rgb)} colours"))
+            hold.append((xyz, rgb, tris, keys))
+            m.n_vert, m.n_tri = len(xyz), len(tris)
+            m.xyz_hd = abi.ptr(xyz).value if len(xyz) else None
+            m.rgb_hd = abi.ptr(rgb).value if rgb is not None and len(rgb) else None
+            m.key_hd = abi.ptr(keys).value if len(keys) else None
+            m.tri_hd = abi.ptr(tris).value if len(tris) else None
+            for a in range(3):
+                m.core_lo[a], m.core_hi[a] = int(lo[a]), int(hi[a])
+        nv, nt = sum(len(h[0]) for h in hold), sum(len(h[2]) for h in hold)
+        if on_device:
+            import torch
+            dev = hold[0][2].device
+            oxyz, otri = torch.empty((nv, 3), dtype=torch.float32, device=dev), torch.empty((nt, 3), dtype=torch.int32, device=dev)
+            orgb = torch.empty((nv, 3), dtype=torch.uint8, device=dev) if has_rgb else None
+            okey = torch.empty((nv,), dtype=torch.int64, device=dev)
+        else:
+            oxyz, otri = np.empty((nv, 3), np.float32), np.empty((nt, 3), np.uint32)
+            orgb = np.empty((nv, 3), np.uint8) if has_rgb else None
+            okey = np.empty((nv,), np.int64)
+        dims = (C.c_int64 * 3)(*[int(d) for d in lattice_dims])
+
+        def p(a):
+            return abi.ptr(a) if a is not None and len(a) else None
+        kv, kt, tw, un = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        abi.check(self._lib.tl3d_mesh_weld_keyed(self._h, arr, len(parts), dims, p(oxyz), p(orgb), p(okey), nv, p(otri), nt,
+                                                 C.byref(kv), C.byref(kt), C.byref(tw), C.byref(un)))
+        return oxyz[:kv.value], (orgb[:kv.value] if orgb is not None else None), otri[:kt.value], okey[:kv.value]
+
     def raycast(self, pose, min_weight: int = 0, z_near=None, z_far=None, slot=None, out=None):
         """Ray-cast the TSDF channel from the camera at pose = (R, t) (world->camera, as integrate):
         (depth f32 [H,W] with 0 = no hit, normals f32 [H,W,3] in the camera frame, bgr u8 [H,W,3]).  z_near / z_far default to

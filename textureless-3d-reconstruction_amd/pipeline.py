@@ -464,6 +464,7 @@ class DepthToReconstructionPipeline:
         self.mesh_normals = None
         cfg = self.config
         self._check_mesh_filter_config()
+        self._check_mesh_weld_config()
         loop = bool(getattr(cfg, "loop_closure", False)) and poses is None      # with poses given nothing is registered: the option is ignored
         if loop and estimate_scale:
             raise ValueError("loop_closure does not go with estimate_scale: the pose graph's edges carry no scale")
@@ -660,7 +661,13 @@ class DepthToReconstructionPipeline:
                   + (" (raise --grid, the memory budget of the volume)" if one else ""))
         if cfg.extract_mesh:
             t0 = clock()
-            vx, vr, vt = mesh_parts[0][:3] if one else weld_meshes(mesh_parts, lattice.dims)[:3]
+            if one or not self._mesh_weld_on_device():
+                vx, vr, vt = mesh_parts[0][:3] if one else weld_meshes(mesh_parts, lattice.dims)[:3]
+            else:                                        # (the last block is detached: its grid's memory is free for the table)
+                vx, vr, vt = ctx.weld_meshes(mesh_parts, lattice.dims)[:3]
+                self.stats["mesh_weld"] = dict(parts=len(mesh_parts), vertices_in=sum(len(m[0]) for m in mesh_parts), vertices=len(vx),
+                                               triangles=len(vt))
+                stage["mesh_weld"] = clock() - t0
             print(f"  Mesh: {len(vx)} vertices, {len(vt)} triangles" + ("" if one else f" (welded from {len(done)} blocks)"))
             stage["mesh"] += clock() - t0
             if self._mesh_filter_on():                   # on the WELDED mesh: a surface that crosses a block seam is counted whole
@@ -943,6 +950,18 @@ class DepthToReconstructionPipeline:
             raise ValueError(f"mesh_smooth_mu = {mu}: must lie in [-2, 0]")
         if (int(it) > 0 or bool(getattr(self.config, "mesh_normals", False))) and not self.config.extract_mesh:
             raise ValueError("mesh_smooth_iterations / mesh_normals work on the mesh: they need extract_mesh = True")
+
+    def _check_mesh_weld_config(self):
+        mode = getattr(self.config, "mesh_weld", "host")
+        if mode not in ("host", "device"):
+            raise ValueError(f"mesh_weld = {mode!r}: must be 'host' or 'device'")
+        if mode == "device" and not self.config.extract_mesh:
+            raise ValueError("mesh_weld = 'device' welds the blocks' meshes: it needs extract_mesh = True")
+
+    def _mesh_weld_on_device(self) -> bool:
+        """config.mesh_weld == "device": the blocks' meshes are welded by FusionContext.weld_meshes, not
+        by lattice.weld_meshes on the host -- the same bytes.  Only a run of more than one block welds anything."""
+        return getattr(self.config, "mesh_weld", "host") == "device"
 
     def _mesh_smooth_on(self) -> bool:
         return int(getattr(self.config, "mesh_smooth_iterations", 0)) > 0

@@ -2,7 +2,7 @@
 given poses).  Per block: count (choose_layout), attach + core, fuse, extract (centroid points), keyed mesh, detach -- wall time
 after a device sync each -- then the whole reconstruct() with extract_mesh.  One JSON line per block and one for the
 whole run.
-    python tools/bench_blocks.py [--frames 240] [--mesh 1]"""
+    python tools/bench_blocks.py [--frames 240] [--mesh 1] [--mesh-weld host|device]"""
 import argparse
 import json
 import os
@@ -24,6 +24,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=240)
     ap.add_argument("--mesh", type=int, default=1)
+    ap.add_argument("--mesh-weld", choices=("host", "device"), default="host", help="where reconstruct() welds the blocks' meshes")
     args = ap.parse_args()
     W, H = 640, 480
     cam = dict(fx=512.0, fy=512.0, cx=320.0, cy=240.0)
@@ -31,7 +32,7 @@ def main():
     poses = synth.dolly_poses(args.frames, (0.0, 0.0, 0.0), (0.0, 0.0, 0.5))
     frames = [synth.render(scene, p, W, H, **cam) for p in poses]
     cfg = ReconstructionConfig(**cam, voxel_size=0.005, subsample_factor=2, grid_dim=512, max_depth=4.0, outlier_filter=False,
-                               extract_mesh=bool(args.mesh))
+                               extract_mesh=bool(args.mesh), mesh_weld=args.mesh_weld if args.mesh else "host")
     n = len(frames)
     slots = list(range(n))
     clock = time.perf_counter
@@ -76,7 +77,7 @@ def main():
     print(json.dumps(dict(reconstruct_s=round(t1 - t0, 3), points=len(pts), blocks=pipe.stats["blocks"],
                           points_dropped=pipe.stats["points_dropped"], pool_refused=pipe.stats["pool_refused"],
                           mesh_vertices=pipe.stats.get("mesh_vertices"), mesh_triangles=pipe.stats.get("mesh_triangles"),
-                          timings=pipe.timings)))
+                          mesh_weld=cfg.mesh_weld, timings=pipe.timings)))
 
 
 if __name__ == "__main__":
