@@ -1,0 +1,48 @@
+"""What the white-box cases of the 64-bit key table need to know about it (tests/mesh_weld_common.py, tests/mesh_simplify_common.py):
+where a key's probe sequence starts and how many slots a table gets.  The cases fill the smallest table to exactly half with keys
+whose sequences all start in its last slots, so that every claim and every lookup runs into the end of the array and wraps."""
+import numpy as np
+
+MIN_SLOTS = 1024
+LAST = 8                                                  # the cases' keys start in the last LAST slots of a MIN_SLOTS table
+
+
+def kt_mix(keys):
+    """kt_mix of textureless-3d-reconstruction_amd/csrc/keytab.h (the finaliser of MurmurHash3) on an array of keys: uint64,
+    products modulo 2^64"""
+    x = np.array(keys, dtype=np.uint64)
+    x ^= x >> np.uint64(33)
+    x *= np.uint64(0xFF51AFD7ED558CCD)
+    x ^= x >> np.uint64(33)
+    x *= np.uint64(0xC4CEB9FE1A85EC53)
+    x ^= x >> np.uint64(33)
+    return x
+
+
+def kt_slots(max_keys):
+    """kt_slots of tl3d_api.hip: the smallest power of two >= 1024 and >= 2 * max_keys"""
+    cap = MIN_SLOTS
+    while cap < 2 * int(max_keys):
+        cap <<= 1
+    return cap
+
+
+def start_slot(keys, slots=MIN_SLOTS):
+    return (kt_mix(keys) & np.uint64(slots - 1)).astype(np.int64)
+
+
+def wrapping(rng, n, draw):
+    """The first n distinct keys of draw(rng, count) -> (keys, rows) whose probe sequence starts in the last LAST slots of a
+    MIN_SLOTS table: rejection sampling at a hit rate of LAST / MIN_SLOTS.  Returns the rows of the keys kept, in the order drawn;
+    rows is whatever the caller makes its keys from, one row per key."""
+    got_keys, got_rows = np.zeros(0, np.uint64), None
+    while len(got_keys) < n:
+        keys, rows = draw(rng, 4 * n * MIN_SLOTS // LAST)
+        hit = start_slot(keys) >= MIN_SLOTS - LAST
+        keys, rows = np.asarray(keys, np.uint64)[hit], rows[hit]
+        got_keys = np.concatenate([got_keys, keys])
+        got_rows = rows if got_rows is None else np.concatenate([got_rows, rows])
+        _, first = np.unique(got_keys, return_index=True)
+        first.sort()
+        got_keys, got_rows = got_keys[first], got_rows[first]
+    return got_rows[:n]

@@ -2,6 +2,7 @@
 topologies on which hashed vertex clustering goes wrong, and the speck scene of the component tests."""
 import numpy as np
 
+import keytab_common as kt
 from mesh_components_common import SPECK_GRID, SPECK_MIN_TRIANGLES, crafted_mesh, speck_scene  # noqa: F401  (shared with the tests)
 
 # crafted_mesh(0): 5135 vertices, 9188 triangles.  By cell size, origin 0: (vertices, triangles, duplicates dropped) out
@@ -40,8 +41,43 @@ def _axis_lines(cell):
     return xyz, _colours(rng, len(xyz)), np.ascontiguousarray(tris)
 
 
+WRAPPED = ("wrapped chains", "wrapped chains shared")
+WRAPPED_VERTS = 512                                       # n_vert of both: half of the smallest vertex table
+
+
+def cell_keys(i):
+    """ms_key of kernels_meshsimplify.hip for cell indices i [N, 3] within +-2^20"""
+    u = (np.asarray(i, np.int64) + (1 << 20)).astype(np.uint64)
+    return (u[:, 0] << np.uint64(42)) | (u[:, 1] << np.uint64(21)) | u[:, 2]
+
+
+def _wrapped_chains(shared):
+    """The vertex table at its smallest capacity, every probe sequence running into the end of the array: cells (cell 1, origin 0,
+    indices anywhere within +-2^20) whose keys' sequences start in the last 8 of 1024 slots (keytab_common.wrapping).
+    "wrapped chains": WRAPPED_VERTS vertices at the centres of as many distinct cells; the table is filled to exactly half.
+    "wrapped chains shared": the first half of those cells, and then as many vertices again a quarter cell off the centre of cells
+    already taken, which find their key at the end of a wrapped chain.  (The table is sized by n_vert, so vertices that share cells
+    cannot come on top of WRAPPED_VERTS distinct ones without doubling it: they take the place of half of them.)
+    400 triangles among all vertices.  Every coordinate is a multiple of 1/4 below 2^20: exact in f32."""
+    rng = np.random.default_rng(25)
+
+    def draw(rng, count):
+        i = rng.integers(-(1 << 20), 1 << 20, size=(count, 3))
+        return cell_keys(i), i
+    i = kt.wrapping(rng, WRAPPED_VERTS, draw)
+    xyz = i + 0.5
+    if shared:
+        half = WRAPPED_VERTS // 2
+        xyz = np.concatenate([xyz[:half], i[rng.integers(0, half, size=half)] + rng.choice([0.25, 0.75], size=(half, 3))])
+    xyz = xyz.astype(np.float32)
+    tris = rng.integers(0, len(xyz), size=(400, 3)).astype(np.uint32)
+    return xyz, _colours(rng, len(xyz)), tris, 1.0, None
+
+
 def topology(name):
     """(xyz f32 [V,3], rgb u8 [V,3], tris u32 [T,3], cell, origin or None)"""
+    if name in WRAPPED:
+        return _wrapped_chains(name.endswith("shared"))
     if name == "one hot cluster":                               # every add lands on one record
         rng = np.random.default_rng(21)
         xyz = (0.25 + 0.5 * rng.random((1 << 16, 3))).astype(np.float32)
@@ -80,7 +116,7 @@ TOPOLOGIES = ("one hot cluster", "doubled sheet", "soup") + AXIS_LINES + ("cell 
 FIGURES = {"one hot cluster": (1, 0, 131072, 0), "doubled sheet": (16384, 64516, 296442, 32258), "soup": (32759, 502853, 19714, 1721),
            "axis lines 0.25": (304, 902, 3, 2), "axis lines 0.25 shifted": (301, 902, 3, 2), "axis lines 0.1": (304, 900, 5, 2),
            "axis lines 0.1 shifted": (301, 902, 3, 2), "axis lines 0.005": (304, 899, 5, 3), "axis lines 0.005 shifted": (301, 902, 3, 2),
-           "cell finer than the spacing": (4225, 8192, 0, 0)}
+           "cell finer than the spacing": (4225, 8192, 0, 0), "wrapped chains": (512, 397, 3, 0), "wrapped chains shared": (256, 395, 5, 0)}
 
 _REFERENCES = {}
 

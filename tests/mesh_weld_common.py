@@ -13,6 +13,8 @@ import functools
 
 import numpy as np
 
+import keytab_common as kt
+
 
 def key_of(i, j, k, axis, L):
     return 3 * ((int(k) * int(L[1]) + int(j)) * int(L[0]) + int(i)) + int(axis)
@@ -146,6 +148,33 @@ def sized_parts(seed=5):
     return assemble(L, boxes, keys, xyz, rgb, lists, tris)
 
 
+WRAP_L = (1 << 21, 1 << 20, (1 << 20) - 8)                # (the lattice of soup_wide)
+WRAP_KEPT = 512                                           # half of the smallest key table
+
+
+def wrap_parts(seed=17):
+    """The key table at its smallest capacity, filled to exactly half, every probe sequence running into the end of the array:
+    WRAP_KEPT keys of the lower x half of WRAP_L whose sequences start in the last 8 of 1024 slots (keytab_common.wrapping).
+    Part 0 (core: the lower x half) owns them all and has some triangles of its own; part 1 (core: the upper half) owns nothing,
+    lists a halo copy of every one, and its triangles name each of them at least once, so every lookup walks a wrapped chain."""
+    rng = np.random.default_rng(seed)
+    L = WRAP_L
+
+    def draw(rng, count):
+        v = np.stack([rng.integers(0, L[0] // 2, count), rng.integers(0, L[1], count), rng.integers(0, L[2], count), rng.integers(0, 3, count)],
+                     axis=1)
+        return (3 * ((v[:, 2] * L[1] + v[:, 1]) * L[0] + v[:, 0]) + v[:, 3]).astype(np.uint64), v
+    v = kt.wrapping(rng, WRAP_KEPT, draw)
+    keys = np.array([key_of(i, j, k, axis, L) for i, j, k, axis in v], np.int64)
+    G = len(keys)
+    xyz, rgb = _vertices(rng, G)
+    t1 = rng.integers(0, G, (G + 88, 3))
+    t1[:G, 0] = rng.permutation(G)                        # every halo copy is named
+    lists = [rng.permutation(G), rng.permutation(G)]
+    tris = [rng.integers(0, G, (100, 3)), t1]
+    return assemble(L, _halves(L, (0,)), keys, xyz, rgb, lists, tris)
+
+
 def seam_case():
     """two blocks along x, six kept vertices (one of them unreferenced), one seam vertex (the case of tests/test_blocks_host.py)"""
     L = (16, 8, 8)
@@ -193,7 +222,7 @@ def _block_boxes(dims, max_voxels):
 
 
 SOUPS = ("soup_small", "soup_blocks", "soup_wide")
-CASES = SOUPS + ("sized", "seam", "coincident")
+CASES = SOUPS + ("sized", "wrap", "seam", "coincident")
 
 
 @functools.lru_cache(maxsize=None)
@@ -212,6 +241,8 @@ def case(name):
         return (L,) + soup_parts(L, _halves(L, (0, 1)), 1 << 16, 1 << 17, 13)
     if name == "sized":
         return (SIZED_L,) + sized_parts()
+    if name == "wrap":                  # the smallest key table, half full, every chain wrapping round its end
+        return (WRAP_L,) + wrap_parts()
     if name == "seam":
         return seam_case() + (None,)
     if name == "coincident":

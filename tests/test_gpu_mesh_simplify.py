@@ -14,8 +14,8 @@ import mesh_components_reference as mcr
 import mesh_simplify_reference as msr
 import tl3d
 from helpers import SMALL
-from mesh_simplify_common import (CRAFTED, CRAFTED_ORIGIN, FIGURES, SPECK_GRID, SPECK_MIN_TRIANGLES, TOPOLOGIES, crafted_mesh, reference,
-                                  speck_scene)
+from mesh_simplify_common import (CRAFTED, CRAFTED_ORIGIN, FIGURES, SPECK_GRID, SPECK_MIN_TRIANGLES, TOPOLOGIES, WRAPPED, crafted_mesh,
+                                  reference, speck_scene)
 from tl3d import _cabi as abi
 from tl3d import fileio, synth
 from tl3d import pipeline as pl
@@ -113,6 +113,23 @@ def test_topologies_where_hashed_clustering_goes_wrong(ctx, name):
     if name == "cell finer than the spacing":                       # the triangle list comes back unchanged
         _same_bytes(got[2], tris, "identity")
         assert np.array_equal(got[3]["vert_map"], np.arange(len(xyz)))
+
+
+@pytest.mark.parametrize("kind", ["host", "device"])
+@pytest.mark.parametrize("name", WRAPPED)
+def test_vertex_table_half_full_with_chains_that_wrap(ctx, name, kind):
+    """the vertex table at its smallest capacity (1024 slots for 512 vertices), every probe sequence starting in its last 8 slots
+    and wrapping round the end of the array: 512 distinct cells, and 256 cells that two or more vertices claim"""
+    (xyz, rgb, tris, cell, origin), want = reference(name)
+    assert (len(want[0]), len(want[2]), want[3]["degenerate_dropped"], want[3]["duplicates_dropped"]) == FIGURES[name]
+    for run in ("first run", "second run"):
+        if kind == "host":
+            got = ctx.simplify_mesh(xyz, rgb, tris, cell, origin)
+        else:
+            dx, dr, dt, dinfo = ctx.simplify_mesh(_dev(xyz), _dev(rgb), _dev(tris), cell, origin)
+            assert dx.is_cuda and dr.is_cuda and dt.is_cuda and dinfo["vert_map"].is_cuda
+            got = (_host(dx), _host(dr), _host(dt), dict(dinfo, vert_map=_host(dinfo["vert_map"])))
+        _assert_simplified(got, want, f"{name}, {kind}, {run}")
 
 
 def test_arguments(ctx):

@@ -50,6 +50,16 @@ def test_device_weld_gives_the_constructed_bytes(ctx, name, kind):
     assert mw.same_bytes(first, pl.weld_meshes(parts, L))
 
 
+def test_wrapped_chains_report_no_vertex_twice_and_no_corner_unowned(ctx):
+    """the key table at its smallest capacity, half full, every claim and every lookup wrapping round the end of the array: the call's
+    own counts (the bytes are in the test above)"""
+    L, parts, want, _info = mw.case("wrap")
+    rc, msg, counts, outs = mw.raw_call(ctx._h, parts, L)
+    assert rc == abi.OK, msg
+    assert counts == [mw.WRAP_KEPT, len(want[2]), 0, 0]
+    assert mw.same_bytes((outs[0][:counts[0]], outs[1][:counts[0]], outs[3], outs[2][:counts[0]]), want)
+
+
 def test_variants(ctx):
     L, parts, want, _info = mw.case("soup_small")
     # without rgb

@@ -7,8 +7,9 @@ import math
 import numpy as np
 import pytest
 
+import keytab_common as kt
 import mesh_simplify_reference as msr
-from mesh_simplify_common import CRAFTED, CRAFTED_ORIGIN, FIGURES, TOPOLOGIES, crafted_mesh, reference
+from mesh_simplify_common import CRAFTED, CRAFTED_ORIGIN, FIGURES, TOPOLOGIES, WRAPPED, WRAPPED_VERTS, cell_keys, crafted_mesh, reference
 from tl3d import _cabi as abi
 
 
@@ -181,6 +182,29 @@ def test_topology_figures(name):
         assert np.array_equal(want[2], inp[2]) and np.array_equal(want[3]["vert_map"], np.arange(len(inp[0])))
     if name.startswith("axis lines") or name == "doubled sheet":
         _assert_same(want, _loops(*inp), name)
+
+
+@pytest.mark.parametrize("name", WRAPPED)
+def test_wrapped_chains_fill_the_smallest_table_with_chains_that_wrap(name):
+    """the two conditions that keep the cases from going hollow, by the Python copy of the mixer and of the sizing rule; and their
+    pinned figures"""
+    inp, want = reference(name)
+    xyz, rgb, tris, cell, origin = inp
+    i, _ = msr.cells(xyz, cell, origin)
+    assert np.abs(i).max() < 1 << 20 and np.array_equal(cell_keys(i) >> np.uint64(42), (i[:, 0] + (1 << 20)).astype(np.uint64))
+    keys = cell_keys(i)
+    assert len(xyz) == WRAPPED_VERTS == 512 and kt.kt_slots(len(xyz)) == 1024 and kt.kt_slots(len(xyz) + 1) == 2048
+    assert kt.start_slot(keys, 1024).min() >= 1016                  # more keys than slots to the end: every chain wraps
+    distinct = len(np.unique(keys))
+    if name.endswith("shared"):                                     # the second half lies in cells of the first half
+        assert distinct == len(np.unique(keys[:256])) == 256 and np.isin(keys[256:], keys[:256]).all()
+        assert not (xyz[256:] == xyz[want[3]["vert_map"][256:]]).all(axis=1).any()       # ... and nowhere on their leaders
+    else:
+        assert distinct == 512                                      # exactly half of the table
+    assert (len(want[0]), len(want[2]), want[3]["degenerate_dropped"], want[3]["duplicates_dropped"]) == FIGURES[name]
+    assert want[3]["clusters"] == distinct and 300 <= len(tris) <= 500
+    _assert_box_property(inp, want)
+    _assert_same(want, _loops(*inp), name)
 
 
 # ---- the C-ABI without a GPU --------------------------------------------------------------------------------------------------

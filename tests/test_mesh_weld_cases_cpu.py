@@ -8,6 +8,7 @@ import re
 import numpy as np
 import pytest
 
+import keytab_common as kt
 import mesh_weld_common as mw
 from tl3d import _cabi as abi
 from tl3d import pipeline as pl
@@ -42,6 +43,19 @@ def test_cases_have_what_they_are_for(name):
         sizes = [(int((info["part"][info["order"]] == p).sum()), len(parts[p][0]), len(parts[p][2])) for p in range(len(parts))]
         assert sizes == [(o, o + h, t) for o, h, t in mw.SIZED]
         assert np.all(info["corner_owner"][3] != 3) and parts[4][2].tolist() == [[0, 0, 0]]
+
+
+def test_wrap_case_fills_the_smallest_table_to_half_with_chains_that_wrap():
+    """the two conditions that keep the case from going hollow, by the Python copy of the mixer and of the sizing rule"""
+    L, parts, want, info = mw.case("wrap")
+    keys = want[3]
+    assert len(keys) == len(np.unique(keys)) == mw.WRAP_KEPT == 512 and keys.min() >= 0 and keys.max() < 3 * L[0] * L[1] * L[2]
+    assert kt.kt_slots(len(keys)) == 1024 and kt.kt_slots(len(keys) + 1) == 2048      # exactly half of the smallest table
+    assert kt.start_slot(keys, 1024).min() >= 1016                                    # more keys than slots to the end: every chain wraps
+    assert [int((info["part"][info["order"]] == p).sum()) for p in (0, 1)] == [512, 0]          # part 1 owns nothing ...
+    assert len(parts[1][0]) == 512 and np.array_equal(np.sort(parts[1][3]), np.sort(keys))      # ... lists a halo copy of every key ...
+    assert np.array_equal(np.unique(parts[1][2]), np.arange(512)) and np.all(info["corner_owner"][1] == 0)     # ... and names each
+    assert np.all(info["corner_owner"][0] == 0) and len(parts[0][2]) > 0
 
 
 def test_host_weld_refuses_the_broken_cases_with_both_messages():

@@ -12,8 +12,8 @@
 // Passes, each its own launch on the context's stream (kernel boundaries are the ONLY ordering between them):
 //   validate      largest triangle index (cc_validate_kernel) and the number of vertices without a cell; nothing indexed runs
 //                 before the host has looked at both
-//   insert        one thread per vertex: its key into the vertex table (64-bit CAS EMPTY -> key, linear probing), slot[v] = where
-//                 it sits, atomicMin(leader[slot], v)
+//   insert        one thread per vertex: its key into the vertex table (keytab.h's kt_claim), slot[v] = where it sits,
+//                 atomicMin(leader[slot], v)
 //   leaders       leader[slot[v]] == v per chunk -> single-block scan -> vert_map[leader] = cluster number, in order (compact.h,
 //                 as the triangle classes and the triangle write below)
 //   accumulate    one thread per vertex: vert_map[v] = vert_map[leader], atomicAdd of 1, q and rgb into the cluster's seven words
@@ -22,27 +22,24 @@
 //   tri classify  per chunk: degenerate / duplicate / survivor (the slot of its triple holds t itself) -> flag, counts
 //   write         positions and colours per leader at its cluster number; surviving triangles at scanned offsets, mapped
 //
-// Proof obligations of the two tables.  Each line is kept by every statement that touches the words it names:
-//   H1  a key word changes once, EMPTY -> key, by the   the only store to keys[] after the fill is the atomicCAS(EMPTY, key) of
-//       CAS that writes it.                             ms_insert_kernel; a CAS that fails returns the key somebody else wrote.
+// Proof obligations of the two tables.  H1, H3 and H5 of the vertex table (64-bit keys) are keytab.h's and are kept there: n_vert
+// vertices bring at most n_vert keys into kt_slots(n_vert) slots.  The triangle table holds 32-bit triangle indices and compares
+// canonical triples, so it has loops of its own, and they keep the same three lines: its slots change only by the CAS and the
+// atomicMin of H2, n_tri triangles bring at most n_tri entries into kt_slots(n_tri) slots and both loops are bounded by the capacity,
+// and a failed CAS is answered by looking at what it returned and probing on.  The lines that are this file's own, each kept by
+// every statement that touches the words it names:
 //   H2  a triangle slot only ever changes among         EMPTY -> t by CAS sets the slot's canonical triple; from then on only
 //       triangles of ONE canonical triple.              atomicMin(slot, t') with triple(t') == triple(occupant) touches it.  So a
 //                                                       stale read of a slot names a triangle of the right triple, and every probe
 //                                                       sequence a thread has walked stays valid.
-//   H3  load <= 0.5, so probing ends.                   capacities are powers of two >= 2 n_vert / 2 n_tri, one entry per vertex /
-//                                                       triangle at most: an EMPTY slot or the own key lies ahead.  Every probe loop
-//                                                       is ALSO bounded by the capacity, so a broken table cannot hang the device.
 //   H4  results come only from integer min and add.     leader: atomicMin; n, S, C: atomicAdd on u64 (two's complement for S);
 //                                                       triangle slots: atomicMin.  No float atomics anywhere.
-//   H5  no thread waits for another thread's store.     no flags, no polls, no spin loops: a failed CAS is answered by looking at the
-//                                                       value it returned and probing on.
 //   H6  WHICH slot a key or a triple lands in may       nothing that is written out depends on a slot index: slots are only
 //       differ from run to run.                         compared for what they hold (leader, smallest triangle index).
-#include "compact.h"
+#include "keytab.h"
 
 namespace tl3d {
 
-constexpr unsigned long long MS_EMPTY_KEY = ~0ull;       // bit 63 set: no key (63 bits) equals it
 constexpr unsigned MS_EMPTY = 0xFFFFFFFFu;               // no vertex index (< 2^31) and no triangle index (< 2^32 - 1) equals it
 constexpr double MS_Q = 16777216.0;                      // 2^24 steps per cell
 enum : uint8_t { MS_DEGENERATE = 0, MS_DUPLICATE = 1, MS_SURVIVOR = 2 };
@@ -63,16 +60,10 @@ __device__ __forceinline__ bool ms_cell_of(const MsCell &g, const float *__restr
     return ok;
 }
 
+// (63 bits: never KT_EMPTY)
 __device__ __forceinline__ unsigned long long ms_key(const double fi[3]) {
     return ((unsigned long long)((long long)fi[0] + 1048576ll) << 42) | ((unsigned long long)((long long)fi[1] + 1048576ll) << 21) |
            (unsigned long long)((long long)fi[2] + 1048576ll);
-}
-
-__device__ __forceinline__ unsigned long long ms_mix(unsigned long long x) {
-    x ^= x >> 33; x *= 0xFF51AFD7ED558CCDull;
-    x ^= x >> 33; x *= 0xC4CEB9FE1A85EC53ull;
-    x ^= x >> 33;
-    return x;
 }
 
 // info[1] += vertices without a cell
@@ -83,8 +74,7 @@ __global__ __launch_bounds__(256) void ms_validate_kernel(MsCell g, const float 
         double d[3], fi[3];
         bad = !ms_cell_of(g, xyz + 3ull * v, d, fi);
     }
-    const unsigned long long m = __ballot(bad);
-    if (m && (threadIdx.x & 63) == __ffsll((long long)m) - 1) atomicAdd(info + 1, (unsigned long long)__popcll(m));
+    wave_count(bad, info + 1);
 }
 
 // (every vertex has a cell: the host has seen info[1] == 0)
@@ -94,21 +84,11 @@ __global__ __launch_bounds__(256) void ms_insert_kernel(MsCell g, const float *_
     if (v >= n) return;
     double d[3], fi[3];
     ms_cell_of(g, xyz + 3ull * v, d, fi);
-    const unsigned long long key = ms_key(fi);
-    unsigned long long h = ms_mix(key) & mask;
-    for (unsigned long long probe = 0; probe <= mask; ++probe) {       // (H3: ends long before the bound)
-        unsigned long long cur = __hip_atomic_load(keys + h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == MS_EMPTY_KEY) {
-            cur = atomicCAS(keys + h, MS_EMPTY_KEY, key);              // H1
-            if (cur == MS_EMPTY_KEY) cur = key;
-        }
-        if (cur == key) {
-            slot[v] = (unsigned)h;                                     // (capacity <= 2^32)
-            atomicMin(leader + h, v);
-            return;
-        }
-        h = (h + 1) & mask;
-    }
+    bool won;
+    const unsigned long long h = kt_claim(keys, mask, ms_key(fi), won);
+    if (h == KT_NONE) return;                                          // (keytab.h H3: never)
+    slot[v] = (unsigned)h;                                             // (capacity <= 2^32)
+    atomicMin(leader + h, v);
 }
 
 __global__ __launch_bounds__(256) void ms_leader_count_kernel(const unsigned *__restrict__ slot, const unsigned *__restrict__ leader, unsigned n,
@@ -194,7 +174,7 @@ __device__ __forceinline__ bool ms_canonical(const unsigned *__restrict__ tri, c
 }
 
 __device__ __forceinline__ unsigned long long ms_triple_hash(const unsigned k[3]) {
-    return ms_mix(ms_mix(((unsigned long long)k[1] << 32) | k[0]) + k[2]);
+    return kt_mix(kt_mix(((unsigned long long)k[1] << 32) | k[0]) + k[2]);
 }
 
 __global__ __launch_bounds__(256) void ms_tri_insert_kernel(const unsigned *__restrict__ tri, unsigned long long n_tri,
@@ -288,7 +268,7 @@ int launch_ms_validate(hipStream_t s, double cell, const double o[3], const floa
     return TL3D_OK;
 }
 
-// Vertices into clusters (validated input; keys / leader filled with 0xFF, acc with 0): slot, vert_map, the seven sums per
+// Vertices into clusters (validated input; keys / leader filled with 0xFF, vcap = kt_slots(n_vert) slots, acc with 0): slot, vert_map, the seven sums per
 // cluster, leaders per chunk (vcounts) and their scan (voffsets, total behind the last chunk = the number of clusters).
 int launch_ms_cluster(hipStream_t s, double cell, const double o[3], const float *xyz, const uint8_t *rgb, long long n_vert,
                       unsigned long long *keys, unsigned *leader, unsigned long long vcap, unsigned *slot, unsigned *vmap,

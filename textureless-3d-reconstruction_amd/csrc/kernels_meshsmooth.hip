@@ -16,8 +16,8 @@
 // Passes, each its own launch on the context's stream (kernel boundaries are the ONLY ordering between them):
 //   validate      largest triangle index (cc_validate_kernel), vertices that are not finite or beyond 2^20 m; nothing indexed
 //                 runs before the host has looked at both
-//   edge insert   one thread per triangle corner pair: key (min, max) into the edge table (64-bit CAS EMPTY -> key, linear
-//                 probing); the thread whose CAS wins adds 1 to both endpoints' valence and counts the edge
+//   edge insert   one thread per triangle corner pair: key (min, max) into the edge table (keytab.h's kt_claim); the thread whose
+//                 CAS wins adds 1 to both endpoints' valence and counts the edge
 //   rows          per-chunk sums of the valences (64-bit) -> single-block scan -> row[v] (compact.h's skeleton on block_excl)
 //   edge fill     one thread per table slot: an occupied slot appends each endpoint to the other's row through the row's cursor
 //   step          one thread per vertex gathers its row (a row longer than MSM_LONG_ROW is walked by the whole wave and summed by
@@ -25,27 +25,20 @@
 //                 the step before it set copies its input through
 //   normals       corner count -> rows -> corner fill (triangle ids per vertex) -> the same gather over incident triangles
 //
-// Proof obligations (numbering of DESIGN.md section 4.2.2):
-//   H1  a key word changes once, EMPTY -> key, by the   the only store to keys[] after the fill is the atomicCAS(EMPTY, key) of
-//       CAS that writes it.                             msm_edge_insert_kernel; a CAS that fails returns the key somebody else wrote.
-//   H3  load <= 0.5, so probing ends.                   the capacity is a power of two >= 6 n_tri, a triangle brings at most three
-//                                                       keys.  Every probe loop is ALSO bounded by the capacity.
+// Proof obligations (numbering of DESIGN.md section 4.2.2).  H1, H3 and H5 of the edge table are keytab.h's and are kept there: a
+// triangle brings at most three keys, 3 n_tri in all, into kt_slots(3 n_tri) slots.  The lines that are this file's own:
 //   H4  results come only from integer add.             valence, cursors, edge count: atomicAdd; flags: atomicOr.  No float atomics.
-//   H5  no thread waits for another thread's store.     no flags, no polls, no spin loops: a failed CAS is answered by looking at the
-//                                                       value it returned and probing on.
 //   H6  the order of a row may differ from run to run.  a row is only ever summed, in exact integers.
 //   B1  a row is never written beyond its end.          valence[v] counts exactly the keys that name v (one winner per key), and the
 //                                                       fill appends once per key and endpoint; the corner rows likewise (one count
 //                                                       and one append per corner).  The fills ALSO compare the cursor with the count.
-#include "compact.h"
+#include "keytab.h"
 
 namespace tl3d {
 
 typedef __int128 i128;
 typedef unsigned __int128 u128;
-typedef unsigned long long u64;
 
-constexpr u64 MSM_EMPTY_KEY = ~0ull;                     // bit 63 set: no key (two indices below 2^31) equals it
 constexpr double MSM_Q = 16777216.0;                     // 2^24 steps per metre
 constexpr float MSM_RANGE = 1048576.0f;                  // |x| <= 2^20 m
 constexpr unsigned MSM_LONG_ROW = 64;                    // rows longer than this are gathered by the wave
@@ -69,19 +62,6 @@ __device__ __forceinline__ i128 msm_wave_sum(i128 v) {
     return v;
 }
 
-__device__ __forceinline__ u64 msm_mix(u64 x) {
-    x ^= x >> 33; x *= 0xFF51AFD7ED558CCDull;
-    x ^= x >> 33; x *= 0xC4CEB9FE1A85EC53ull;
-    x ^= x >> 33;
-    return x;
-}
-
-// one add of `count` by the first of the wave's lanes that `flag`s
-__device__ __forceinline__ void msm_wave_count(bool flag, u64 *word) {
-    const u64 m = __ballot(flag);
-    if (m && (threadIdx.x & 63) == __ffsll((long long)m) - 1) atomicAdd(word, (u64)__popcll(m));
-}
-
 // info[1] += coordinates' vertices that are not finite or lie beyond 2^20 m
 __global__ __launch_bounds__(256) void msm_validate_kernel(const float *__restrict__ xyz, unsigned n, u64 *__restrict__ info) {
     const unsigned v = blockIdx.x * 256u + threadIdx.x;
@@ -90,7 +70,7 @@ __global__ __launch_bounds__(256) void msm_validate_kernel(const float *__restri
 #pragma unroll
         for (int a = 0; a < 3; ++a) bad = bad || !(fabsf(xyz[3ull * v + a]) <= MSM_RANGE);          // true for NaN and for an infinity
     }
-    msm_wave_count(bad, info + 1);
+    wave_count(bad, info + 1);
 }
 
 // (every index is below n_vert: the host has seen info[0])
@@ -103,27 +83,14 @@ __global__ __launch_bounds__(256) void msm_edge_insert_kernel(const unsigned *__
         const unsigned c = (unsigned)(e - 3 * t);
         const unsigned u = tri[e], v = tri[3 * t + (c == 2 ? 0 : c + 1)];
         if (u != v) {
-            const u64 key = ((u64)min(u, v) << 32) | (u64)max(u, v);
-            u64 h = msm_mix(key) & mask;
-            for (u64 probe = 0; probe <= mask; ++probe) {               // (H3: ends long before the bound)
-                u64 cur = __hip_atomic_load(keys + h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (cur == MSM_EMPTY_KEY) {
-                    cur = atomicCAS(keys + h, MSM_EMPTY_KEY, key);      // H1
-                    if (cur == MSM_EMPTY_KEY) {
-                        won = true;
-                        break;
-                    }
-                }
-                if (cur == key) break;
-                h = (h + 1) & mask;
-            }
+            kt_claim(keys, mask, ((u64)min(u, v) << 32) | (u64)max(u, v), won);         // (two indices below 2^31: never KT_EMPTY)
             if (won) {
                 atomicAdd(deg + u, 1u);
                 atomicAdd(deg + v, 1u);
             }
         }
     }
-    msm_wave_count(won, info + 2);
+    wave_count(won, info + 2);
 }
 
 __global__ __launch_bounds__(256) void msm_row_count_kernel(const unsigned *__restrict__ cnt, unsigned n, u64 *__restrict__ chunk_counts) {
@@ -158,7 +125,7 @@ __global__ __launch_bounds__(256) void msm_edge_fill_kernel(const u64 *__restric
     const u64 h = (u64)blockIdx.x * 256 + threadIdx.x;
     if (h >= slots) return;
     const u64 key = keys[h];
-    if (key == MSM_EMPTY_KEY) return;
+    if (key == KT_EMPTY) return;
     const unsigned u = (unsigned)(key >> 32), v = (unsigned)key;
     unsigned p = atomicAdd(cursor + u, 1u);
     if (p < deg[u]) nbr[row[u] + p] = v;                                 // (B1: always)
@@ -306,7 +273,7 @@ __global__ __launch_bounds__(256) void msm_normal_kernel(const float *__restrict
 #pragma unroll
         for (int a = 0; a < 3; ++a) out[3ull * v + a] = r[a];
     }
-    msm_wave_count(zero, info + 3);
+    wave_count(zero, info + 3);
 }
 
 // info[1] = the number of vertices that are not finite or lie beyond 2^20 m (the caller zeroed it)
@@ -317,7 +284,7 @@ int launch_msm_validate(hipStream_t s, const float *xyz, long long n_vert, unsig
     return TL3D_OK;
 }
 
-// The unique edges of validated triangles into the table (filled with 0xFF; `slots` a power of two >= 6 n_tri): deg[v] (zeroed by
+// The unique edges of validated triangles into the table (filled with 0xFF; `slots` = kt_slots(3 n_tri)): deg[v] (zeroed by
 // the caller) = valence, info[2] = edges
 int launch_msm_edges(hipStream_t s, const unsigned *tri, long long n_tri, unsigned long long *keys, unsigned long long slots, unsigned *deg,
                      unsigned long long *info) {

@@ -13,49 +13,28 @@
 //                 before the host has looked at both counts
 //   own count     per chunk of EXTRACT_CHUNK vertices the kept ones -> single-block scan -> the offsets and the number kept
 //   own write     compact.h's write pass: a kept vertex goes to its scanned offset o (xyz, rgb, key), vert_map[g] = o, and its
-//                 thread inserts the key (64-bit CAS EMPTY -> key, linear probing); the thread whose CAS wins stores o beside the
-//                 key, a thread that finds its key there already counts a vertex owned twice; vert_map[g] = NONE for the others
+//                 thread inserts the key (keytab.h's kt_claim); the thread whose CAS wins stores o beside the key, a thread that
+//                 finds its key there already counts a vertex owned twice; vert_map[g] = NONE for the others
 //   resolve       one thread per triangle corner: vert_map of the corner's own vertex, one gather, answers every corner whose
-//                 vertex is kept in the same part; only the others (halo corners) probe the table by their key, and one that
+//                 vertex is kept in the same part; only the others (halo corners) look their key up (kt_find), and one that
 //                 reaches EMPTY counts an unowned corner; corner e of the one list is written at e
 //
-// Proof obligations (numbering of DESIGN.md section 4.2.2):
-//   H1  a key word changes once, EMPTY -> key, by the   the only store to keys[] after the fill is the atomicCAS(EMPTY, key) of
-//       CAS that writes it.                             wm_insert; a CAS that fails returns the key somebody else wrote.
+// Proof obligations (numbering of DESIGN.md section 4.2.2).  H1, H3 and H5 of the key table are keytab.h's and are kept there: only
+// kept vertices insert, `kept` keys at most, into kt_slots(kept) slots.  The lines that are this file's own:
 //   H2  the word beside a key is written once, by the   vals[h] is stored only by the thread whose CAS on keys[h] won, and read
 //       winner, and read in a later launch.             only by wm_resolve_kernel.
-//   H3  load <= 0.5, so probing ends.                   the capacity is a power of two >= 2 * kept and only kept vertices insert.
-//                                                       Every probe loop is ALSO bounded by the capacity.
 //   H4  results come only from integer add and scans.   the offsets are a scan of integer counts, the two counts atomicAdd.  No
 //                                                       float is computed at all: positions and colours are copied.
-//   H5  no thread waits for another thread's store.     no flags, no polls, no spin loops: a failed CAS is answered by looking at the
-//                                                       value it returned and probing on.
 //   H6  the slot a key lands in may differ from run     nothing written out is a slot number: a corner takes vals[h] of the slot that
 //       to run.                                         holds its key, and with no key owned twice that is one value wherever h is
 //                                                       (with one owned twice the call fails and its arrays are unspecified).
 //   B1  nothing is written beyond an output's end.      o < kept <= vert_cap (the host compares before the write pass, the kernel
 //                                                       compares again); corners are written at e < 3 sum n_tri <= 3 tri_cap.
-#include "compact.h"
+#include "keytab.h"
 
 namespace tl3d {
 
-typedef unsigned long long u64;
-
-constexpr u64 WM_EMPTY_KEY = ~0ull;                      // bit 63 set: no key (below 3 * 2^61) equals it
 constexpr unsigned WM_NONE = 0xffffffffu;                // vert_map: not kept; a corner: unowned
-
-__device__ __forceinline__ u64 wm_mix(u64 x) {
-    x ^= x >> 33; x *= 0xFF51AFD7ED558CCDull;
-    x ^= x >> 33; x *= 0xC4CEB9FE1A85EC53ull;
-    x ^= x >> 33;
-    return x;
-}
-
-// `count` added once by the first of the wave's lanes that `flag`s
-__device__ __forceinline__ void wm_wave_count(bool flag, u64 *word) {
-    const u64 m = __ballot(flag);
-    if (m && (threadIdx.x & 63) == __ffsll((long long)m) - 1) atomicAdd(word, (u64)__popcll(m));
-}
 
 // the part that holds vertex g of the one list: the last p with v0[p] <= g (parts without vertices are stepped over)
 __device__ __forceinline__ int wm_part_of_vertex(const WeldPart *__restrict__ parts, int n_parts, u64 g) {
@@ -102,8 +81,8 @@ __global__ __launch_bounds__(256) void wm_validate_kernel(const WeldPart *__rest
         bad_idx = (u64)i >= parts[pi + 1].v0 - p.v0;
         if (bad_idx) atomicMax(info + 2, ((u64)pi << 32) | (u64)i);
     }
-    wm_wave_count(bad_idx, info);
-    wm_wave_count(bad_key, info + 1);
+    wave_count(bad_idx, info);
+    wave_count(bad_key, info + 1);
 }
 
 __global__ __launch_bounds__(256) void wm_own_count_kernel(const WeldPart *__restrict__ parts, int n_parts, u64 n_vert, u64 lx, u64 ly,
@@ -120,24 +99,12 @@ __global__ __launch_bounds__(256) void wm_own_count_kernel(const WeldPart *__res
     if (threadIdx.x == 0) counts[blockIdx.x] = c;
 }
 
-// key -> o into the table; *n_twice += 1 when the key is there already
+// key -> o into the table; *n_twice += 1 when the key is there already (a validated key is below 3 * 2^61: never KT_EMPTY)
 __device__ __forceinline__ void wm_insert(u64 *keys, unsigned *__restrict__ vals, u64 mask, u64 key, unsigned o, u64 *n_twice) {
-    u64 h = wm_mix(key) & mask;
-    for (u64 probe = 0; probe <= mask; ++probe) {                           // (H3: ends long before the bound)
-        u64 cur = __hip_atomic_load(keys + h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == WM_EMPTY_KEY) {
-            cur = atomicCAS(keys + h, WM_EMPTY_KEY, key);                   // H1
-            if (cur == WM_EMPTY_KEY) {
-                vals[h] = o;                                                // H2
-                return;
-            }
-        }
-        if (cur == key) {
-            atomicAdd(n_twice, 1ull);
-            return;
-        }
-        h = (h + 1) & mask;
-    }
+    bool won;
+    const u64 h = kt_claim(keys, mask, key, won);
+    if (won) vals[h] = o;                                                   // H2
+    else if (h != KT_NONE) atomicAdd(n_twice, 1ull);                        // (KT_NONE: keytab.h H3, never)
 }
 
 __global__ __launch_bounds__(256) void wm_own_write_kernel(const WeldPart *__restrict__ parts, int n_parts, u64 n_vert, u64 lx, u64 ly,
@@ -184,23 +151,13 @@ __global__ __launch_bounds__(256) void wm_resolve_kernel(const WeldPart *__restr
         const unsigned i = p.tri[e - 3 * p.t0];
         unsigned o = vert_map[p.v0 + i];
         if (o == WM_NONE) {                                                 // a halo corner: by its key
-            const u64 key = (u64)p.key[i];
-            u64 h = wm_mix(key) & mask;
-            unowned = true;
-            for (u64 probe = 0; probe <= mask; ++probe) {                   // (H3)
-                const u64 cur = keys[h];
-                if (cur == key) {
-                    o = vals[h];
-                    unowned = false;
-                    break;
-                }
-                if (cur == WM_EMPTY_KEY) break;
-                h = (h + 1) & mask;
-            }
+            const u64 h = kt_find(keys, mask, (u64)p.key[i]);
+            unowned = h == KT_NONE;
+            if (!unowned) o = vals[h];
         }
         out_tri[e] = o;
     }
-    wm_wave_count(unowned, info + 4);
+    wave_count(unowned, info + 4);
 }
 
 // info[0..2] (zeroed by the caller): bad indices, bad keys, the largest offender
@@ -222,7 +179,7 @@ int launch_wm_own_count(hipStream_t s, const WeldPart *parts, int n_parts, unsig
     return launch_scan(s, counts, offsets, chunks, offsets + chunks);
 }
 
-// The kept vertices to their offsets and into the table (filled with 0xFF; `slots` a power of two >= 2 * kept), vert_map [n_vert];
+// The kept vertices to their offsets and into the table (filled with 0xFF; `slots` = kt_slots(kept)), vert_map [n_vert];
 // info[3] (zeroed by the caller) = vertices owned twice
 int launch_wm_own_write(hipStream_t s, const WeldPart *parts, int n_parts, unsigned long long n_vert, const long long lat[3],
                         const unsigned long long *offsets, float *out_xyz, uint8_t *out_rgb, long long *out_key, unsigned long long vcap,

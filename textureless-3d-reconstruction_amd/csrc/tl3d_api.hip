@@ -4,6 +4,7 @@
 #include <stdlib.h>
 #include <math.h>
 
+#include <functional>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -393,14 +394,13 @@ static void release_grid(tl3d_ctx *ctx) {
     if (gs.cc_parent) (void)hipFree(gs.cc_parent);
     if (gs.cc_count) (void)hipFree(gs.cc_count);
     if (gs.cc_remap) (void)hipFree(gs.cc_remap);
-    if (gs.ms_keys) (void)hipFree(gs.ms_keys);
-    if (gs.ms_leader) (void)hipFree(gs.ms_leader);
+    if (gs.kt_keys) (void)hipFree(gs.kt_keys);
+    if (gs.kt_vals) (void)hipFree(gs.kt_vals);
     if (gs.ms_slot) (void)hipFree(gs.ms_slot);
     if (gs.ms_vmap) (void)hipFree(gs.ms_vmap);
     if (gs.ms_acc) (void)hipFree(gs.ms_acc);
     if (gs.ms_ttab) (void)hipFree(gs.ms_ttab);
     if (gs.ms_flag) (void)hipFree(gs.ms_flag);
-    if (gs.adj_keys) (void)hipFree(gs.adj_keys);
     if (gs.adj_cnt) (void)hipFree(gs.adj_cnt);
     if (gs.adj_cursor) (void)hipFree(gs.adj_cursor);
     if (gs.adj_row) (void)hipFree(gs.adj_row);
@@ -408,8 +408,6 @@ static void release_grid(tl3d_ctx *ctx) {
     if (gs.adj_xyz) (void)hipFree(gs.adj_xyz);
     if (gs.adj_ccounts) (void)hipFree(gs.adj_ccounts);
     if (gs.adj_coffs) (void)hipFree(gs.adj_coffs);
-    if (gs.wm_keys) (void)hipFree(gs.wm_keys);
-    if (gs.wm_vals) (void)hipFree(gs.wm_vals);
     if (gs.wm_vmap) (void)hipFree(gs.wm_vmap);
     if (gs.wm_parts) (void)hipFree(gs.wm_parts);
     if (gs.mio_counts) (void)hipFree(gs.mio_counts);
@@ -2752,6 +2750,41 @@ static int mio_grow(tl3d_ctx *ctx, int64_t n_tri, int64_t n_vert, const char *wh
     return TL3D_OK;
 }
 
+// slots of a table that takes max_keys entries at most (keytab.h H3): the smallest power of two >= 1024 and >= 2 * max_keys
+static size_t kt_slots(size_t max_keys) {
+    size_t cap = 1024;
+    while (cap < 2 * max_keys) cap <<= 1;                  // load <= 0.5
+    return cap;
+}
+
+// The context's key table (tl3d_internal.h: kt_*) with `slots` slots, every key EMPTY behind what the stream holds already; vals: the
+// caller keeps a 32-bit word beside each key (what it holds, and its fill if it needs one, are the caller's)
+static int kt_reserve(tl3d_ctx *ctx, size_t slots, bool vals, const char *what) {
+    int rc = grow(&ctx->kt_keys, &ctx->kt_key_slots, slots, what);
+    if (!rc && vals) rc = grow(&ctx->kt_vals, &ctx->kt_val_slots, slots, what);
+    if (rc) return rc;
+    TL3D_HIP(hipMemsetAsync(ctx->kt_keys, 0xFF, slots * sizeof(unsigned long long), ctx->stream));
+    return TL3D_OK;
+}
+
+// The validation sequence of the calls that take one indexed mesh: the report words zeroed, the largest triangle index
+// (cc_validate_kernel) into word 0, the caller's own validator (`second`, if it has one) into word 1, one wait, and the refusal of
+// an index beyond n_vert.  *word1 = what `second` counted: the caller refuses it in its own words.  Nothing of the call indexes by
+// a triangle, or takes a coordinate apart, before this has returned TL3D_OK.
+static int mio_validate(tl3d_ctx *ctx, const uint32_t *dtri, int64_t n_tri, int64_t n_vert, const std::function<int()> &second = nullptr,
+                        unsigned long long *word1 = nullptr) {
+    unsigned long long h[2] = {0, 0};
+    TL3D_HIP(hipMemsetAsync(ctx->mio_info, 0, 8 * sizeof(unsigned long long), ctx->stream));
+    int rc = launch_cc_validate(ctx->stream, dtri, n_tri, ctx->mio_info);
+    if (!rc && second) rc = second();
+    if (rc) return rc;
+    TL3D_HIP(hipMemcpyAsync(h, ctx->mio_info, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    TL3D_HIP(hipStreamSynchronize(ctx->stream));
+    REQUIRE(n_tri == 0 || (int64_t)h[0] < n_vert, TL3D_E_INVALID, "triangle index %llu out of range [0, %lld)", h[0], (long long)n_vert);
+    if (word1) *word1 = h[1];
+    return TL3D_OK;
+}
+
 static int cc_grow(tl3d_ctx *ctx, int64_t n_tri, int64_t n_vert) {
     size_t cap2 = ctx->cc_verts, cap3 = ctx->cc_verts;
     int rc = grow(&ctx->cc_parent, &ctx->cc_verts, (size_t)n_vert, "mesh component scratch");
@@ -2813,15 +2846,10 @@ struct MeshIO {
 };
 
 // The validation pass and, only when every index is below n_vert, the labelling: cc_parent = labels, cc_count = triangles per
-// label, h_info = the report words (largest index, components, key of the largest component).  Waits for the stream twice.
-static int cc_label(tl3d_ctx *ctx, const uint32_t *dtri, int64_t n_tri, int64_t n_vert, unsigned long long h_info[4]) {
-    TL3D_HIP(hipMemsetAsync(ctx->mio_info, 0, 8 * sizeof(unsigned long long), ctx->stream));
-    int rc = launch_cc_validate(ctx->stream, dtri, n_tri, ctx->mio_info);
-    if (rc) return rc;
-    TL3D_HIP(hipMemcpyAsync(h_info, ctx->mio_info, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    TL3D_HIP(hipStreamSynchronize(ctx->stream));
-    REQUIRE(n_tri == 0 || (int64_t)h_info[0] < n_vert, TL3D_E_INVALID, "triangle index %llu out of range [0, %lld)", h_info[0], (long long)n_vert);
-    return launch_cc_label(ctx->stream, dtri, n_tri, n_vert, ctx->cc_parent, ctx->cc_count, ctx->mio_info);
+// label, the report words: largest index, components, key of the largest component.  Waits for the stream once.
+static int cc_label(tl3d_ctx *ctx, const uint32_t *dtri, int64_t n_tri, int64_t n_vert) {
+    const int rc = mio_validate(ctx, dtri, n_tri, n_vert);
+    return rc ? rc : launch_cc_label(ctx->stream, dtri, n_tri, n_vert, ctx->cc_parent, ctx->cc_count, ctx->mio_info);
 }
 
 int tl3d_mesh_components(tl3d_ctx *ctx, const uint32_t *tri, int64_t n_tri, int64_t n_vert, uint32_t *label_out, uint32_t *tri_count_out,
@@ -2843,7 +2871,7 @@ int tl3d_mesh_components(tl3d_ctx *ctx, const uint32_t *tri, int64_t n_tri, int6
     if (n_tri) rc = st.in(tri, tb, &dtri);
     if (rc) return rc;
     unsigned long long h[4] = {0, 0, 0, 0};
-    rc = cc_label(ctx, dtri, n_tri, n_vert, h);
+    rc = cc_label(ctx, dtri, n_tri, n_vert);
     if (rc) return rc;
     TL3D_HIP(hipMemcpyAsync(label_out, ctx->cc_parent, vb, hipMemcpyDefault, ctx->stream));
     if (tri_count_out) TL3D_HIP(hipMemcpyAsync(tri_count_out, ctx->cc_count, vb, hipMemcpyDefault, ctx->stream));
@@ -2873,7 +2901,7 @@ int tl3d_mesh_filter_components(tl3d_ctx *ctx, const float *xyz, const uint8_t *
     if (!rc && keep_vert_out) rc = st.out(keep_vert_out, (size_t)n_vert, &dkeep);
     if (rc) return rc;
     unsigned long long h[4] = {0, 0, 0, 0};
-    rc = cc_label(ctx, m.dtri, n_tri, n_vert, h);
+    rc = cc_label(ctx, m.dtri, n_tri, n_vert);
     if (rc) return rc;
     const ChunkHalves ch(ctx->mio_counts, ctx->mio_offsets, chunks_of(n_vert), chunks_of(n_tri));
     rc = launch_cc_keep_count(ctx->stream, (long long)min_triangles, largest_only != 0, m.dtri, n_tri, n_vert, ctx->cc_parent, ctx->cc_count,
@@ -2895,18 +2923,13 @@ int tl3d_mesh_filter_components(tl3d_ctx *ctx, const float *xyz, const uint8_t *
 }
 
 // ------------------------------------------------------------------------------------------- mesh simplification
-static size_t ms_table_slots(int64_t n) {
-    size_t cap = 1024;
-    while (cap < 2 * (size_t)n) cap <<= 1;
-    return cap;
-}
-
+// the vertex table: a key per slot and, in the word beside it, the cluster's leader
 static int ms_grow(tl3d_ctx *ctx, int64_t n_tri, int64_t n_vert) {
     const char *what = "mesh simplification scratch";
-    int rc = grow_pair(&ctx->ms_keys, &ctx->ms_leader, &ctx->ms_vslots, ms_table_slots(n_vert), what);
+    int rc = kt_reserve(ctx, kt_slots((size_t)n_vert), true, what);
     if (!rc) rc = grow_pair(&ctx->ms_slot, &ctx->ms_vmap, &ctx->ms_verts, (size_t)n_vert, what);
     if (!rc) rc = grow(&ctx->ms_acc, &ctx->ms_acc_n, 7 * (size_t)n_vert, what);
-    if (!rc && n_tri) rc = grow(&ctx->ms_ttab, &ctx->ms_tslots, ms_table_slots(n_tri), what);
+    if (!rc && n_tri) rc = grow(&ctx->ms_ttab, &ctx->ms_tslots, kt_slots((size_t)n_tri), what);
     if (!rc && n_tri) rc = grow(&ctx->ms_flag, &ctx->ms_tris, (size_t)n_tri, what);
     if (!rc) rc = mio_grow(ctx, n_tri, n_vert, what);
     return rc;
@@ -2935,21 +2958,16 @@ int tl3d_mesh_simplify_clusters(tl3d_ctx *ctx, const float *xyz, const uint8_t *
     if (rc) return rc;
     // the validation passes: nothing is indexed, and no cell is computed for a table, before the host has seen their words
     unsigned long long h[4] = {0, 0, 0, 0};
-    TL3D_HIP(hipMemsetAsync(ctx->mio_info, 0, 8 * sizeof(unsigned long long), ctx->stream));
-    rc = launch_cc_validate(ctx->stream, m.dtri, n_tri, ctx->mio_info);
-    if (!rc) rc = launch_ms_validate(ctx->stream, cell, o, m.dxyz, n_vert, ctx->mio_info);
+    rc = mio_validate(ctx, m.dtri, n_tri, n_vert, [&] { return launch_ms_validate(ctx->stream, cell, o, m.dxyz, n_vert, ctx->mio_info); }, &h[1]);
     if (rc) return rc;
-    TL3D_HIP(hipMemcpyAsync(h, ctx->mio_info, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    TL3D_HIP(hipStreamSynchronize(ctx->stream));
-    REQUIRE(n_tri == 0 || (int64_t)h[0] < n_vert, TL3D_E_INVALID, "triangle index %llu out of range [0, %lld)", h[0], (long long)n_vert);
     REQUIRE(h[1] == 0, TL3D_E_INVALID, "%llu vertices are not finite or lie 2^20 cells or more from the origin", h[1]);
-    const size_t vslots = ms_table_slots(n_vert), tslots = ms_table_slots(n_tri);
+    const size_t vslots = kt_slots((size_t)n_vert), tslots = kt_slots((size_t)n_tri);
     const ChunkHalves ch(ctx->mio_counts, ctx->mio_offsets, chunks_of(n_vert), chunks_of(n_tri));
-    TL3D_HIP(hipMemsetAsync(ctx->ms_keys, 0xFF, vslots * sizeof(unsigned long long), ctx->stream));
-    TL3D_HIP(hipMemsetAsync(ctx->ms_leader, 0xFF, vslots * sizeof(unsigned), ctx->stream));
+    unsigned *leader = ctx->kt_vals;
+    TL3D_HIP(hipMemsetAsync(leader, 0xFF, vslots * sizeof(unsigned), ctx->stream));
     TL3D_HIP(hipMemsetAsync(ctx->ms_acc, 0, 7 * (size_t)n_vert * sizeof(unsigned long long), ctx->stream));
     if (n_tri) TL3D_HIP(hipMemsetAsync(ctx->ms_ttab, 0xFF, tslots * sizeof(unsigned), ctx->stream));
-    rc = launch_ms_cluster(ctx->stream, cell, o, m.dxyz, m.drgb, n_vert, ctx->ms_keys, ctx->ms_leader, vslots, ctx->ms_slot, ctx->ms_vmap,
+    rc = launch_ms_cluster(ctx->stream, cell, o, m.dxyz, m.drgb, n_vert, ctx->kt_keys, leader, vslots, ctx->ms_slot, ctx->ms_vmap,
                            ctx->ms_acc, ch.counts[0], ch.offs[0]);
     if (!rc) rc = launch_ms_triangles(ctx->stream, m.dtri, n_tri, ctx->ms_vmap, ctx->ms_ttab, tslots, ctx->ms_flag, ch.counts[1], ch.offs[1], ctx->mio_info);
     unsigned long long tot[2] = {0, 0};
@@ -2961,19 +2979,13 @@ int tl3d_mesh_simplify_clusters(tl3d_ctx *ctx, const float *xyz, const uint8_t *
     *out_n_duplicate = (int64_t)h[3];
     rc = m.stage_out(st, tot);
     if (rc) return rc;
-    rc = launch_ms_write(ctx->stream, cell, o, m.dxyz, rgb != nullptr, n_vert, ctx->ms_slot, ctx->ms_leader, ctx->ms_vmap, ctx->ms_acc, m.oxyz, m.orgb,
+    rc = launch_ms_write(ctx->stream, cell, o, m.dxyz, rgb != nullptr, n_vert, ctx->ms_slot, leader, ctx->ms_vmap, ctx->ms_acc, m.oxyz, m.orgb,
                          tot[0], m.dtri, n_tri, ctx->ms_flag, ch.offs[1], m.otri, tot[1]);
     if (!rc && vert_map_out) TL3D_HIP(hipMemcpyAsync(vert_map_out, ctx->ms_vmap, (size_t)n_vert * 4, hipMemcpyDefault, ctx->stream));
     return st.finish(rc, true);
 }
 
 // ------------------------------------------------------------------------------------------- mesh smoothing, vertex normals
-static size_t adj_table_slots(int64_t n_tri) {
-    size_t cap = 1024;
-    while (cap < 6 * (size_t)n_tri) cap <<= 1;             // at most 3 n_tri keys: load <= 0.5
-    return cap;
-}
-
 // what both calls need per vertex and per chunk; the edge table, the rows and the second position buffer grow where they are used
 static int adj_grow(tl3d_ctx *ctx, int64_t n_tri, int64_t n_vert, const char *what) {
     int rc = grow_pair(&ctx->adj_cnt, &ctx->adj_cursor, &ctx->adj_verts, (size_t)n_vert, what);
@@ -2985,15 +2997,10 @@ static int adj_grow(tl3d_ctx *ctx, int64_t n_tri, int64_t n_vert, const char *wh
 
 // the two validation passes and the host's look at their words: nothing is indexed, and no coordinate is quantised, before it
 static int adj_validate(tl3d_ctx *ctx, const float *dxyz, int64_t n_vert, const uint32_t *dtri, int64_t n_tri) {
-    unsigned long long h[2] = {0, 0};
-    TL3D_HIP(hipMemsetAsync(ctx->mio_info, 0, 8 * sizeof(unsigned long long), ctx->stream));
-    int rc = launch_cc_validate(ctx->stream, dtri, n_tri, ctx->mio_info);
-    if (!rc) rc = launch_msm_validate(ctx->stream, dxyz, n_vert, ctx->mio_info);
+    unsigned long long bad = 0;
+    const int rc = mio_validate(ctx, dtri, n_tri, n_vert, [&] { return launch_msm_validate(ctx->stream, dxyz, n_vert, ctx->mio_info); }, &bad);
     if (rc) return rc;
-    TL3D_HIP(hipMemcpyAsync(h, ctx->mio_info, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-    TL3D_HIP(hipStreamSynchronize(ctx->stream));
-    REQUIRE(n_tri == 0 || (int64_t)h[0] < n_vert, TL3D_E_INVALID, "triangle index %llu out of range [0, %lld)", h[0], (long long)n_vert);
-    REQUIRE(h[1] == 0, TL3D_E_INVALID, "%llu vertices are not finite or lie beyond 2^20 m", h[1]);
+    REQUIRE(bad == 0, TL3D_E_INVALID, "%llu vertices are not finite or lie beyond 2^20 m", bad);
     return TL3D_OK;
 }
 
@@ -3015,8 +3022,8 @@ int tl3d_mesh_smooth_taubin(tl3d_ctx *ctx, const float *xyz, int64_t n_vert, con
     if (n_vert == 0) return TL3D_OK;
     TL3D_HIP(hipSetDevice(ctx->device));
     rc = adj_grow(ctx, n_tri, n_vert, what);
-    const size_t slots = adj_table_slots(n_tri);
-    if (!rc && n_tri) rc = grow(&ctx->adj_keys, &ctx->adj_slots, slots, what);
+    const size_t slots = kt_slots(3 * (size_t)n_tri);      // the edge table: a triangle brings at most three keys
+    if (!rc && n_tri) rc = kt_reserve(ctx, slots, false, what);
     if (!rc && n_tri && iterations) rc = grow(&ctx->adj_xyz, &ctx->adj_xyz_n, 3 * (size_t)n_vert, what);
     if (rc) return rc;
     Staging st(ctx);
@@ -3034,8 +3041,7 @@ int tl3d_mesh_smooth_taubin(tl3d_ctx *ctx, const float *xyz, int64_t n_vert, con
     TL3D_HIP(hipMemsetAsync(ctx->adj_cnt, 0, vb, s));
     unsigned long long h[5] = {0, 0, 0, 0, 0};
     if (n_tri) {
-        TL3D_HIP(hipMemsetAsync(ctx->adj_keys, 0xFF, slots * sizeof(unsigned long long), s));
-        rc = launch_msm_edges(s, dtri, n_tri, ctx->adj_keys, slots, ctx->adj_cnt, ctx->mio_info);
+        rc = launch_msm_edges(s, dtri, n_tri, ctx->kt_keys, slots, ctx->adj_cnt, ctx->mio_info);
         if (rc) return rc;
         TL3D_HIP(hipMemcpyAsync(h, ctx->mio_info, sizeof(h), hipMemcpyDeviceToHost, s));
         TL3D_HIP(hipStreamSynchronize(s));
@@ -3048,7 +3054,7 @@ int tl3d_mesh_smooth_taubin(tl3d_ctx *ctx, const float *xyz, int64_t n_vert, con
     }
     rc = grow(&ctx->adj_list, &ctx->adj_list_n, 2 * (size_t)h[2], what);
     if (!rc) rc = launch_msm_rows(s, ctx->adj_cnt, n_vert, ctx->adj_ccounts, ctx->adj_coffs, ctx->adj_row, ctx->adj_cursor);
-    if (!rc) rc = launch_msm_edge_fill(s, ctx->adj_keys, slots, ctx->adj_cnt, ctx->adj_row, ctx->adj_cursor, ctx->adj_list);
+    if (!rc) rc = launch_msm_edge_fill(s, ctx->kt_keys, slots, ctx->adj_cnt, ctx->adj_row, ctx->adj_cursor, ctx->adj_list);
     // 2 * iterations steps between the scratch buffer and the output: in -> scratch -> out -> scratch -> out ...
     const float *src = dxyz;
     for (int i = 0; i < 2 * iterations && !rc; ++i) {
@@ -3110,12 +3116,6 @@ int tl3d_mesh_vertex_normals(tl3d_ctx *ctx, const float *xyz, int64_t n_vert, co
 }
 
 // ------------------------------------------------------------------------------------------- mesh weld
-static size_t wm_table_slots(int64_t kept) {
-    size_t cap = 1024;
-    while (cap < 2 * (size_t)kept) cap <<= 1;              // load <= 0.5
-    return cap;
-}
-
 // Waits for the stream three times, however many parts there are: behind the validation pass, behind the scan (the number kept sizes
 // the table and is compared with the capacity), and at the end.
 int tl3d_mesh_weld_keyed(tl3d_ctx *ctx, const tl3d_mesh_part *parts, int n_parts, const int64_t lattice_dims[3], float *out_xyz,
@@ -3264,13 +3264,12 @@ int tl3d_mesh_weld_keyed(tl3d_ctx *ctx, const tl3d_mesh_part *parts, int n_parts
     if (!rc && rgb) rc = st.out(out_rgb, (size_t)kept * 3, &orgb);
     if (!rc && out_key) rc = st.out(out_key, (size_t)kept * 8, &okey);
     if (!rc) rc = st.out(out_tri, (size_t)nt * 12, &otri);
-    const size_t slots = wm_table_slots((int64_t)kept);
-    if (!rc) rc = grow_pair(&ctx->wm_keys, &ctx->wm_vals, &ctx->wm_slots, slots, what);
+    const size_t slots = kt_slots((size_t)kept);           // the key table: a key per slot and, in the word beside it, the kept vertex's output index
+    if (!rc) rc = kt_reserve(ctx, slots, true, what);
     if (rc) return rc;
-    TL3D_HIP(hipMemsetAsync(ctx->wm_keys, 0xFF, slots * sizeof(unsigned long long), s));
-    rc = launch_wm_own_write(s, ctx->wm_parts, n_parts, nv, lat, ctx->mio_offsets, oxyz, orgb, (long long *)okey, kept, ctx->wm_vmap, ctx->wm_keys,
-                             ctx->wm_vals, slots, ctx->mio_info);
-    if (!rc) rc = launch_wm_resolve(s, ctx->wm_parts, n_parts, nt, ctx->wm_vmap, ctx->wm_keys, ctx->wm_vals, slots, otri, ctx->mio_info);
+    rc = launch_wm_own_write(s, ctx->wm_parts, n_parts, nv, lat, ctx->mio_offsets, oxyz, orgb, (long long *)okey, kept, ctx->wm_vmap, ctx->kt_keys,
+                             ctx->kt_vals, slots, ctx->mio_info);
+    if (!rc) rc = launch_wm_resolve(s, ctx->wm_parts, n_parts, nt, ctx->wm_vmap, ctx->kt_keys, ctx->kt_vals, slots, otri, ctx->mio_info);
     if (rc) return rc;
     TL3D_HIP(hipMemcpyAsync(h, ctx->mio_info, sizeof(h), hipMemcpyDeviceToHost, s));
     rc = st.finish(TL3D_OK, true);

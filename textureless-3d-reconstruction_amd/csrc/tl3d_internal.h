@@ -240,13 +240,19 @@ struct tl3d_grid_state {
     // the one place that frees device scratch grown on demand.
     unsigned *cc_parent, *cc_count, *cc_remap;
     size_t cc_verts;                        // capacity of each, in vertices
-    // tl3d_mesh_simplify_clusters: the vertex table (a 64-bit key and a leader word per slot, a power of
-    // two >= 2 n_vert slots), per vertex its slot and its cluster number, per cluster seven 64-bit sums (n, S, C), the triangle
-    // table (one index per slot, a power of two >= 2 n_tri slots), a class byte per triangle.  Grid-independent like the cc_
-    // scratch, and here for the same reason.
-    unsigned long long *ms_keys;
-    unsigned *ms_leader;
-    size_t ms_vslots;                       // capacity of both, in slots
+    // The 64-bit key table of the mesh calls (keytab.h): a key per slot and, for the callers that keep one,
+    // a 32-bit word beside it -- tl3d_mesh_simplify_clusters: cell keys of kt_slots(n_vert) slots, the word = the cluster's leader;
+    // tl3d_mesh_smooth_taubin: edge keys of kt_slots(3 n_tri) slots, no word; tl3d_mesh_weld_keyed: vertex keys of kt_slots(kept)
+    // slots, the word = the kept vertex's output index.  ONE table serves all three: every call fills the keys with 0xFF on the
+    // context's stream before its first insert (kt_reserve, tl3d_api.hip) and writes a word before it reads it, so no call reads
+    // what another left behind, and calls on one context run one behind the other.  Grid-independent like the cc_ scratch.
+    unsigned long long *kt_keys;
+    size_t kt_key_slots;                    // capacity, in slots
+    unsigned *kt_vals;
+    size_t kt_val_slots;
+    // tl3d_mesh_simplify_clusters: per vertex its slot in the key table and its cluster number, per cluster
+    // seven 64-bit sums (n, S, C), the triangle table (one index per slot, kt_slots(n_tri) slots), a class byte per triangle.
+    // Grid-independent like the cc_ scratch, and here for the same reason.
     unsigned *ms_slot, *ms_vmap;
     unsigned long long *ms_acc;             // [7 per vertex]
     size_t ms_verts, ms_acc_n;              // capacity of ms_slot / ms_vmap in vertices, of ms_acc in words
@@ -254,12 +260,10 @@ struct tl3d_grid_state {
     size_t ms_tslots;
     uint8_t *ms_flag;
     size_t ms_tris;
-    // tl3d_mesh_smooth_taubin / tl3d_mesh_vertex_normals: the edge table (one 64-bit key per slot, a power
-    // of two >= 6 n_tri slots), per vertex a count (valence, or incident corners) and a fill cursor, the 64-bit row offsets, the
-    // rows themselves (2 E neighbours, or 3 n_tri triangle ids), the second position buffer of the steps, and the 64-bit chunk
-    // sums and offsets of the row scan.  Grid-independent like the cc_ scratch, and here for the same reason.
-    unsigned long long *adj_keys;
-    size_t adj_slots;
+    // tl3d_mesh_smooth_taubin / tl3d_mesh_vertex_normals: per vertex a count (valence, or incident
+    // corners) and a fill cursor, the 64-bit row offsets, the rows themselves (2 E neighbours, or 3 n_tri triangle ids), the second
+    // position buffer of the steps, and the 64-bit chunk sums and offsets of the row scan.  Grid-independent like the cc_ scratch,
+    // and here for the same reason.
     unsigned *adj_cnt, *adj_cursor;
     size_t adj_verts;                       // capacity of both, in vertices
     unsigned long long *adj_row;
@@ -270,12 +274,8 @@ struct tl3d_grid_state {
     size_t adj_xyz_n;                       // in floats
     unsigned long long *adj_ccounts, *adj_coffs;
     size_t adj_chunks;                      // capacity of both, in entries
-    // tl3d_mesh_weld_keyed: the key table (a 64-bit key and the kept vertex's output index per slot, a
-    // power of two >= 2 * kept slots), per input vertex its output index or NONE, the part descriptors.  Grid-independent like the
-    // cc_ scratch, and here for the same reason.
-    unsigned long long *wm_keys;
-    unsigned *wm_vals;
-    size_t wm_slots;                        // capacity of both, in slots
+    // tl3d_mesh_weld_keyed: per input vertex its output index or NONE, the part descriptors.
+    // Grid-independent like the cc_ scratch, and here for the same reason.
     unsigned *wm_vmap;
     size_t wm_verts;
     tl3d::WeldPart *wm_parts;
