@@ -79,6 +79,9 @@ def main(argv=None):
                         help="keep only the mesh's connected component with the most triangles (needs --mesh-output)")
     parser.add_argument("--mesh-simplify-cell", type=float, default=0.0, metavar="M",
                         help="merge the mesh's vertices per cell of M metres (vertex clustering, after the component filter; needs --mesh-output)")
+    parser.add_argument("--mesh-simplify-placement", choices=("mean", "quadric"), default="mean",
+                        help="where --mesh-simplify-cell puts a merged vertex: at the mean of its members (default), or by quadric error, "
+                             "which keeps the creases and corners of planar scenes (needs --mesh-simplify-cell)")
     parser.add_argument("--mesh-smooth", type=int, default=0, metavar="N",
                         help="smooth the mesh with N Taubin iterations (after the component filter and the simplification; needs --mesh-output)")
     parser.add_argument("--mesh-normals", action="store_true",
@@ -112,6 +115,8 @@ def main(argv=None):
         parser.error("--mesh-min-component / --mesh-largest-component filter the mesh: they need --mesh-output")
     if args.mesh_simplify_cell != 0.0 and not args.mesh_output:
         parser.error("--mesh-simplify-cell simplifies the mesh: it needs --mesh-output")
+    if args.mesh_simplify_placement != "mean" and not args.mesh_simplify_cell > 0.0:
+        parser.error("--mesh-simplify-placement places the simplified mesh's vertices: it needs --mesh-simplify-cell")
     if (args.mesh_smooth != 0 or args.mesh_normals) and not args.mesh_output:
         parser.error("--mesh-smooth / --mesh-normals work on the mesh: they need --mesh-output")
     if args.mesh_weld != "host" and not args.mesh_output:
@@ -141,6 +146,7 @@ def main(argv=None):
                                   render_dir=args.render_output, loop_closure=args.loop_closure,
                                   model_tracking=args.model_tracking, mesh_min_component_triangles=max(0, args.mesh_min_component),
                                   mesh_largest_component=args.mesh_largest_component, mesh_simplify_cell=args.mesh_simplify_cell,
+                                  mesh_simplify_placement=args.mesh_simplify_placement,
                                   mesh_smooth_iterations=args.mesh_smooth, mesh_normals=args.mesh_normals, mesh_weld=args.mesh_weld)
     pipeline = DepthToReconstructionPipeline(config)
     # a rank decodes every frame on its host (pose chain and scale rule run over the whole sequence) and uploads its share

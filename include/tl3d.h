@@ -462,6 +462,46 @@ int tl3d_mesh_simplify_clusters(tl3d_ctx *ctx, const float *xyz_hd, const uint8_
                                 uint32_t *vert_map_out_hd,
                                 int64_t *out_n_vert, int64_t *out_n_tri, int64_t *out_n_degenerate, int64_t *out_n_duplicate);
 
+/* tl3d_mesh_simplify_clusters with every cluster's vertex placed by its quadric error instead of at the members' mean (Lindstrom's
+ * quadric clustering, Out-of-Core Simplification of Large Polygonal Models, 2000; the area^2-weighted plane quadric added per
+ * corner, as Open3D's quadric mode does).  Clusters, their numbering, vert_map, colours, the triangle rules, the
+ * validation and the error codes are exactly those of tl3d_mesh_simplify_clusters; only positions differ.  It keeps the creases
+ * and corners of piecewise planar surfaces, which the mean rounds off; on smooth curved surfaces it gains nothing.
+ * Quadric coordinates: 2^10 steps per cell, h_a = (q_a + 8192) >> 14 (arithmetic shift = floor division: q may be slightly
+ * negative or slightly above 2^24); seen from a cell I, a vertex v is p_a = (i(v)_a - I_a) * 1024 + h(v)_a.
+ * Contribution: for every input triangle (v0, v1, v2) and every corner k, with I = i(v_k): the corner contributes iff
+ * |i(v_j)_a - I_a| <= 3 for all three corners j and all axes a, otherwise it is skipped and counted.  With p_j seen from I:
+ * N = (p_1 - p_0) x (p_2 - p_0), d = -(N . p_0), exact integers; N_a N_b (00, 01, 02, 11, 12, 22) go into the sums A_ab and d N_a
+ * into the sums b_a of v_k's cluster.  A triangle that names a vertex twice, or has no area, adds zeros.
+ * Bounds: |p| <= 4097, |N_a| < 2^27, |d| < 2^41, |N_a N_b| < 2^54, |d N_a| < 2^68; fewer than 2^34 terms, so the sums stay below
+ * 2^102 in signed 128 bits: exact, hence independent of the order of the additions.
+ * Solve, per cluster, in fp64, every operation rounded once, dbl() as defined for the smoothing below:
+ *   1. A00 = A11 = A22 = 0 (no triangle, or only skipped and zero-area ones): the mean rule, the bytes of
+ *      tl3d_mesh_simplify_clusters.  Otherwise the cluster counts as placed by its quadric, and
+ *   2. T = (dbl(A00) + dbl(A11)) + dbl(A22); M_ab = dbl(A_ab) / T; g_a = dbl(b_a) / T; m_a = (double)S_a / ((double)n * 16384.0);
+ *   3. K = M + reg I; r_a = reg * m_a - g_a (Tikhonov regularisation towards the mean: K is symmetric positive definite with
+ *      eigenvalues in [reg, 1 + reg], so there is no eigen-decomposition, no rank decision and no square root);
+ *   4. K x = r by the adjugate: c00 = K11 K22 - K12 K12, c01 = K02 K12 - K01 K22, c02 = K01 K12 - K02 K11,
+ *      c11 = K00 K22 - K02 K02, c12 = K01 K02 - K00 K12, c22 = K00 K11 - K01 K01, det = (K00 c00 + K01 c01) + K02 c02,
+ *      x0 = ((c00 r0 + c01 r1) + c02 r2) / det, x1 = ((c01 r0 + c11 r1) + c12 r2) / det, x2 = ((c02 r0 + c12 r1) + c22 r2) / det;
+ *      then ONE step of refinement with the same cofactors: p_a = r_a - ((K_a0 x0 + K_a1 x1) + K_a2 x2),
+ *      x0 = x0 + ((c00 p0 + c01 p1) + c02 p2) / det, x1 and x2 likewise (on a single plane K has the eigenvalues 1 + reg, reg,
+ *      reg, the cofactors and det cancel, and the adjugate alone is off by eps / reg^2; the step brings that back to eps / reg);
+ *   5. each x_a is clamped to [0, 1024] (an x_a that is not a number, which takes a reg so small that det underflows, becomes 0);
+ *      a cluster with any axis clamped is counted; the output vertex stays in the closed box of its cell;
+ *   6. position (float)(o_a + ((double)i_a + x_a / 1024.0) * cell), operations in that order.
+ * reg: 0 < reg <= 1, finite; the pipeline passes 2^-10.  It bounds the refined solve's error near eps / reg relative and
+ * biases a rank-deficient solve (a plane, a crease) towards the mean by about reg / sigma_min of the mean's offset.
+ * The three further counts (clusters placed by their quadric, clusters clamped, corners skipped by the span rule) are stored with
+ * the other four, also on TL3D_E_CAPACITY.  TL3D_E_INVALID as for tl3d_mesh_simplify_clusters, and for a reg outside (0, 1] (before
+ * any device call).  Scratch: 144 B per input vertex on top of tl3d_mesh_simplify_clusters', only while this call is in use. */
+int tl3d_mesh_simplify_quadric(tl3d_ctx *ctx, const float *xyz_hd, const uint8_t *rgb_hd, int64_t n_vert,
+                               const uint32_t *tri_hd, int64_t n_tri, double cell, const double origin[3], double reg,
+                               float *out_xyz_hd, uint8_t *out_rgb_hd, int64_t vert_cap, uint32_t *out_tri_hd, int64_t tri_cap,
+                               uint32_t *vert_map_out_hd,
+                               int64_t *out_n_vert, int64_t *out_n_tri, int64_t *out_n_degenerate, int64_t *out_n_duplicate,
+                               int64_t *out_n_quadric, int64_t *out_n_clamped, int64_t *out_n_skipped);
+
 /* Taubin smoothing and vertex normals of an indexed triangle mesh: n_vert vertices (xyz f32 [V][3]), n_tri rows of
  * three uint32 indices, any mesh (the calls need no grid).  No reference code: the reference has no mesh (Open3D's
  * filter_smooth_taubin is the model); the rules are ours, chosen so that the result is a function of the mesh alone, bit for bit, in

@@ -61,6 +61,10 @@ class ReconstructionConfig:
     # vertex-clustering simplification of the mesh (needs extract_mesh): the vertices of one cell of this
     # size, in metres, become one vertex (0: off); applied after the component filter when both are on
     mesh_simplify_cell: float = 0.0
+    # where a merged vertex is put: "mean" (of its members), or "quadric" (where the planes of the triangles around it meet: keeps
+    # creases and corners of planar scenes, gains nothing on smooth surfaces; needs mesh_simplify_cell > 0).  Smoothing afterwards
+    # (mesh_smooth_iterations) rounds the creases again.
+    mesh_simplify_placement: str = "mean"
     # Taubin smoothing of the mesh's positions and area-weighted vertex normals (all need extract_mesh):
     # iterations of a step with lambda and a step with mu (0: off), after the component filter and the simplification; the normals
     # (DepthToReconstructionPipeline.mesh_normals, written by save_mesh) come last, from the final positions

@@ -6,6 +6,25 @@
 //   (the leader); position = (float)(o + ((double)i + (double)S / ((double)n * 2^24)) * cell), colour = (2 C + n) / (2 n);
 //   a triangle is mapped through vert_map, dropped when two mapped indices are equal (degenerate), and dropped when an earlier
 //   triangle has the same canonical triple (its rotation with the smallest index first: duplicate); survivors keep input order.
+// Quadric placement (tl3d_mesh_simplify_quadric; tests/mesh_simplify_quadric_reference.py restates it) changes only the position:
+//   h = (q + 8192) >> 14 (arithmetic shift: 2^10 steps per cell); seen from a cell I a vertex is p = (i - I) * 1024 + h.  Every
+//   corner k of every input triangle, with I = i(v_k): it contributes iff |i(v_j) - I| <= 3 on every axis for all three corners j
+//   (else it is skipped and counted); N = (p1 - p0) x (p2 - p0), d = -(N . p0) in exact integers; N_a N_b (00, 01, 02, 11, 12, 22)
+//   and d N_a go into the nine sums A, b of v_k's cluster (Lindstrom's area^2-weighted plane quadric, once per corner).
+//       bound                         because
+//       |p| <= 4097                   |i - I| <= 3, 0 <= h <= 1025 (q lies within [-8192, 2^24 + 8192) by far)
+//       |N_a| < 2^27                  two products of differences <= 8194: 2 * 8194^2
+//       |d| < 2^41                    3 * 2^27 * 4097
+//       |N_a N_b| < 2^54, |d N_a| < 2^68
+//       |sums| < 2^102                fewer than 3 * 2^32 < 2^34 terms: exact in signed 128 bits, hence order-free
+//   solve, per cluster, fp64, every operation rounded once, dbl() as in kernels_meshsmooth.hip: A00 = A11 = A22 = 0 -> the mean
+//   rule above (the same bytes).  Otherwise T = (dbl(A00) + dbl(A11)) + dbl(A22), M_ab = dbl(A_ab) / T, g_a = dbl(b_a) / T,
+//   m_a = (double)S_a / ((double)n * 16384.0), K = M + reg I, r_a = reg m_a - g_a (Tikhonov towards the mean: K is SPD with
+//   eigenvalues in [reg, 1 + reg], so no eigen-decomposition, no rank decision, no square root); K x = r by the adjugate in the
+//   order ms_quadric_solve spells out, then ONE step of refinement, x += adj(K) (r - K x) / det, in the same order (the adjugate
+//   alone is off by eps / reg^2 on a single plane); x_a clamped to [0, 1024] (a cluster with any axis clamped is counted; an x_a that is no
+//   number -- det underflows for reg below 1e-100 or so -- is taken as 0 and counts as clamped);
+//   position = (float)(o + ((double)i + x / 1024.0) * cell).
 // Everything below is a function of the input alone: results come from integer atomicMin / atomicAdd only, which commute, and the
 // compactions write at scanned offsets, so every run gives the same bytes.
 //
@@ -17,10 +36,12 @@
 //   leaders       leader[slot[v]] == v per chunk -> single-block scan -> vert_map[leader] = cluster number, in order (compact.h,
 //                 as the triangle classes and the triangle write below)
 //   accumulate    one thread per vertex: vert_map[v] = vert_map[leader], atomicAdd of 1, q and rgb into the cluster's seven words
+//   quadrics      (quadric placement only) one thread per triangle: i, q of its three vertices again, the at most three
+//                 (cluster, frame) contributions with equal clusters merged (k * term once), nine 128-bit adds each
 //   tri insert    one thread per triangle: map, and unless degenerate its index into the triangle table (32-bit CAS EMPTY -> t, or
 //                 atomicMin into a slot whose occupant has the same canonical triple)
 //   tri classify  per chunk: degenerate / duplicate / survivor (the slot of its triple holds t itself) -> flag, counts
-//   write         positions and colours per leader at its cluster number; surviving triangles at scanned offsets, mapped
+//   write         positions (mean, or the quadric solve) and colours per leader at its cluster number; surviving triangles at scanned offsets, mapped
 //
 // Proof obligations of the two tables.  H1, H3 and H5 of the vertex table (64-bit keys) are keytab.h's and are kept there: n_vert
 // vertices bring at most n_vert keys into kt_slots(n_vert) slots.  The triangle table holds 32-bit triangle indices and compares
@@ -33,7 +54,15 @@
 //                                                       stale read of a slot names a triangle of the right triple, and every probe
 //                                                       sequence a thread has walked stays valid.
 //   H4  results come only from integer min and add.     leader: atomicMin; n, S, C: atomicAdd on u64 (two's complement for S);
-//                                                       triangle slots: atomicMin.  No float atomics anywhere.
+//                                                       triangle slots: atomicMin.  No float atomics anywhere.  A, b: 128 bits as
+//                                                       two u64 words, old = atomicAdd(lo, t_lo), then atomicAdd(hi, t_hi + carry)
+//                                                       with carry = (old + t_lo < old).  The adds on lo are serialised by the
+//                                                       memory system in SOME order; in that order the word wraps exactly
+//                                                       floor((sum of all t_lo) / 2^64) times, whatever the order, and the add
+//                                                       that wraps it is the one that sees old + t_lo < old: one carry per wrap.
+//                                                       So hi ends at sum t_hi + wraps and (hi, lo) is the sum mod 2^128, exact by
+//                                                       the bounds above.  No CAS loop, nobody waits (H5).  (hi, lo) is read only
+//                                                       behind the kernel boundary.
 //   H6  WHICH slot a key or a triple lands in may       nothing that is written out depends on a slot index: slots are only
 //       differ from run to run.                         compared for what they hold (leader, smallest triangle index).
 #include "keytab.h"
@@ -159,6 +188,177 @@ __global__ __launch_bounds__(256) void ms_vert_write_kernel(MsCell g, const floa
     if (colours) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) out_rgb[3ull * c + k] = (uint8_t)((2ull * a[4 + k] + cnt) / (2ull * cnt));
+    }
+}
+
+typedef __int128 i128;
+typedef unsigned __int128 u128;
+constexpr int MS_QWORDS = 18;                            // per cluster: (lo, hi) of A00 A01 A02 A11 A12 A22 b0 b1 b2
+
+// dbl() of DESIGN.md section 4.2.3 (kernels_meshsmooth.hip's msm_dbl)
+__device__ __forceinline__ double ms_dbl(i128 n) {
+    const bool neg = n < 0;
+    const u128 m = neg ? (u128)0 - (u128)n : (u128)n;
+    const double d = (double)(u64)(m >> 64) * 18446744073709551616.0 + (double)(u64)m;
+    return neg ? -d : d;
+}
+
+// rec (lo, hi) += t (H4: one carry per wrap of the low word; a zero word is not added)
+__device__ __forceinline__ void ms_add128(u64 *rec, i128 t) {
+    const u64 lo = (u64)(u128)t;
+    u64 hi = (u64)((u128)t >> 64);
+    if (lo) {
+        const u64 old = atomicAdd(rec, lo);
+        hi += old + lo < old ? 1ull : 0ull;
+    }
+    if (hi) atomicAdd(rec + 1, hi);
+}
+
+// qacc[18 c ..] += the plane quadric of triangle t seen from each of its corners' cells; info[4] += corners skipped by the span
+// rule.  vert_map is final (the kernel before this one wrote it); every thread of the block reaches the wave sum at the end.
+__global__ __launch_bounds__(256) void ms_quadric_kernel(MsCell g, const float *__restrict__ xyz, const unsigned *__restrict__ tri,
+                                                         unsigned long long n_tri, const unsigned *__restrict__ vmap, u64 *qacc,
+                                                         u64 *__restrict__ info) {
+    const unsigned long long t = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    unsigned skipped = 0;
+    if (t < n_tri) {
+        int ci[3][3], h[3][3];                                         // cell index and 2^10-step coordinate of the corners
+        unsigned c[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const unsigned v = tri[3 * t + j];
+            c[j] = vmap[v];
+            double d[3], fi[3];
+            ms_cell_of(g, xyz + 3ull * v, d, fi);
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                const double r = d[a] - fi[a] * g.cell;
+                const long long q = (long long)rint((r / g.cell) * MS_Q);
+                ci[j][a] = (int)fi[a];
+                h[j][a] = (int)((q + 8192) >> 14);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            // corners of one cluster share the frame and the term: the first of them adds mult times, the others nothing
+            int mult = 1;
+            bool first = true;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                if (j < k && c[j] == c[k]) first = false;
+                if (j > k && c[j] == c[k]) ++mult;
+            }
+            bool in_span = true;
+            long long p[3][3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    const int di = ci[j][a] - ci[k][a];
+                    in_span = in_span && di >= -3 && di <= 3;
+                    p[j][a] = (long long)di * 1024 + h[j][a];
+                }
+            if (!in_span) {
+                ++skipped;
+                continue;
+            }
+            if (!first) continue;
+            long long e1[3], e2[3], N[3];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) { e1[a] = p[1][a] - p[0][a]; e2[a] = p[2][a] - p[0][a]; }
+            N[0] = e1[1] * e2[2] - e1[2] * e2[1];
+            N[1] = e1[2] * e2[0] - e1[0] * e2[2];
+            N[2] = e1[0] * e2[1] - e1[1] * e2[0];
+            if (N[0] == 0 && N[1] == 0 && N[2] == 0) continue;         // zero area, or a vertex named twice: zeros
+            const long long d = -(N[0] * p[0][0] + N[1] * p[0][1] + N[2] * p[0][2]);
+            u64 *rec = qacc + (unsigned long long)MS_QWORDS * c[k];
+            ms_add128(rec + 0, (i128)(mult * N[0] * N[0]));
+            ms_add128(rec + 2, (i128)(mult * N[0] * N[1]));
+            ms_add128(rec + 4, (i128)(mult * N[0] * N[2]));
+            ms_add128(rec + 6, (i128)(mult * N[1] * N[1]));
+            ms_add128(rec + 8, (i128)(mult * N[1] * N[2]));
+            ms_add128(rec + 10, (i128)(mult * N[2] * N[2]));
+#pragma unroll
+            for (int a = 0; a < 3; ++a) ms_add128(rec + 12 + 2 * a, (i128)(mult * d) * (i128)N[a]);
+        }
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) skipped += __shfl_xor(skipped, s);
+    if ((threadIdx.x & 63) == 0 && skipped) atomicAdd(info + 4, (u64)skipped);
+}
+
+__device__ __forceinline__ i128 ms_load128(const u64 *__restrict__ rec) { return (i128)(((u128)rec[1] << 64) | (u128)rec[0]); }
+
+// x of (M + reg I) x = reg m - g in 2^10 steps per cell, clamped to the cell; false when the diagonal sums are all zero (mean rule)
+__device__ __forceinline__ bool ms_quadric_solve(const u64 *__restrict__ rec, const double m[3], double reg, double x[3], bool &clamped) {
+    const i128 A00 = ms_load128(rec), A11 = ms_load128(rec + 6), A22 = ms_load128(rec + 10);
+    if (A00 == 0 && A11 == 0 && A22 == 0) return false;
+    const double T = (ms_dbl(A00) + ms_dbl(A11)) + ms_dbl(A22);
+    const double K00 = ms_dbl(A00) / T + reg, K01 = ms_dbl(ms_load128(rec + 2)) / T, K02 = ms_dbl(ms_load128(rec + 4)) / T;
+    const double K11 = ms_dbl(A11) / T + reg, K12 = ms_dbl(ms_load128(rec + 8)) / T, K22 = ms_dbl(A22) / T + reg;
+    double r[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) r[a] = reg * m[a] - ms_dbl(ms_load128(rec + 12 + 2 * a)) / T;
+    const double c00 = K11 * K22 - K12 * K12, c01 = K02 * K12 - K01 * K22, c02 = K01 * K12 - K02 * K11;
+    const double c11 = K00 * K22 - K02 * K02, c12 = K01 * K02 - K00 * K12, c22 = K00 * K11 - K01 * K01;
+    const double det = (K00 * c00 + K01 * c01) + K02 * c02;
+    x[0] = ((c00 * r[0] + c01 * r[1]) + c02 * r[2]) / det;
+    x[1] = ((c01 * r[0] + c11 * r[1]) + c12 * r[2]) / det;
+    x[2] = ((c02 * r[0] + c12 * r[1]) + c22 * r[2]) / det;
+    // one step of refinement with the same adjugate: at rank 1 and 2 the cofactors and det cancel, and the first x carries it
+    const double p0 = r[0] - ((K00 * x[0] + K01 * x[1]) + K02 * x[2]);
+    const double p1 = r[1] - ((K01 * x[0] + K11 * x[1]) + K12 * x[2]);
+    const double p2 = r[2] - ((K02 * x[0] + K12 * x[1]) + K22 * x[2]);
+    x[0] = x[0] + ((c00 * p0 + c01 * p1) + c02 * p2) / det;
+    x[1] = x[1] + ((c01 * p0 + c11 * p1) + c12 * p2) / det;
+    x[2] = x[2] + ((c02 * p0 + c12 * p1) + c22 * p2) / det;
+    clamped = false;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        if (!(x[a] >= 0.0)) { x[a] = 0.0; clamped = true; }            // (also what is no number)
+        else if (x[a] > 1024.0) { x[a] = 1024.0; clamped = true; }
+    }
+    return true;
+}
+
+// ms_vert_write_kernel with the position from the cluster's quadric; info[5] += clusters placed by it, info[6] += clusters
+// clamped: one add per block and word (nearly every wave holds a leader, and an add per wave on one address is what the launch
+// then takes).  out_xyz == nullptr counts only (the capacity error still reports).  Every thread reaches the block sum.
+__global__ __launch_bounds__(256) void ms_vert_write_quadric_kernel(MsCell g, double reg, const float *__restrict__ xyz, bool colours, unsigned n,
+                                                                    const unsigned *__restrict__ slot, const unsigned *__restrict__ leader,
+                                                                    const unsigned *__restrict__ vmap, const u64 *__restrict__ acc,
+                                                                    const u64 *__restrict__ qacc, float *__restrict__ out_xyz,
+                                                                    uint8_t *__restrict__ out_rgb, unsigned long long cap, u64 *__restrict__ info) {
+    const unsigned v = blockIdx.x * 256u + threadIdx.x;
+    bool placed = false, clamped = false;
+    if (v < n && leader[slot[v]] == v) {
+        const unsigned c = vmap[v];
+        double d[3], fi[3], m[3], x[3];
+        ms_cell_of(g, xyz + 3ull * v, d, fi);
+        const u64 *a = acc + 7ull * c;
+        const u64 cnt = a[0];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) m[k] = (double)(long long)a[1 + k] / ((double)cnt * 16384.0);
+        placed = ms_quadric_solve(qacc + (unsigned long long)MS_QWORDS * c, m, reg, x, clamped);
+        if (out_xyz && c < cap) {
+            const double den = (double)cnt * MS_Q;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const double f = placed ? x[k] / 1024.0 : (double)(long long)a[1 + k] / den;
+                const double w = (fi[k] + f) * g.cell;
+                out_xyz[3ull * c + k] = (float)(g.o[k] + w);
+            }
+            if (colours) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) out_rgb[3ull * c + k] = (uint8_t)((2ull * a[4 + k] + cnt) / (2ull * cnt));
+            }
+        }
+    }
+    __shared__ unsigned sm[4];
+    const unsigned both = block_sum((placed ? 1u : 0u) | (placed && clamped ? 1u << 16 : 0u), sm);      // (256 threads: two 16-bit counts)
+    if (threadIdx.x == 0) {
+        if (both & 0xFFFFu) atomicAdd(info + 5, (u64)(both & 0xFFFFu));
+        if (both >> 16) atomicAdd(info + 6, (u64)(both >> 16));
     }
 }
 
@@ -289,6 +489,16 @@ int launch_ms_cluster(hipStream_t s, double cell, const double o[3], const float
     return TL3D_OK;
 }
 
+// qacc (zeroed, 18 words per vertex) += the corner quadrics of every triangle, info[4] += corners skipped; behind launch_ms_cluster
+int launch_ms_quadrics(hipStream_t s, double cell, const double o[3], const float *xyz, const unsigned *tri, long long n_tri,
+                       const unsigned *vmap, unsigned long long *qacc, unsigned long long *info) {
+    if (n_tri <= 0) return TL3D_OK;
+    hipLaunchKernelGGL(ms_quadric_kernel, dim3(blocks_of((unsigned long long)n_tri, 256)), dim3(256), 0, s, ms_cell(cell, o), xyz, tri,
+                       (unsigned long long)n_tri, vmap, qacc, info);
+    TL3D_HIP(hipGetLastError());
+    return TL3D_OK;
+}
+
 // Triangles through vert_map into the table (filled with 0xFF), then flag[t], survivors per chunk (tcounts) and their scan,
 // info[2] / info[3] = degenerate / duplicate
 int launch_ms_triangles(hipStream_t s, const unsigned *tri, long long n_tri, const unsigned *vmap, unsigned *ttab, unsigned long long tcap,
@@ -305,11 +515,17 @@ int launch_ms_triangles(hipStream_t s, const unsigned *tri, long long n_tri, con
     return launch_scan(s, tcounts, toffsets, (int)tchunks, toffsets + tchunks);         // (no triangle: the total is 0)
 }
 
+// qacc: the quadric sums (nullptr: mean placement); with them info[5] / info[6] += clusters placed by their quadric / clamped,
+// and out_xyz == nullptr writes nothing and counts all the same
 int launch_ms_write(hipStream_t s, double cell, const double o[3], const float *xyz, bool colours, long long n_vert, const unsigned *slot,
                     const unsigned *leader, const unsigned *vmap, const unsigned long long *acc, float *out_xyz, uint8_t *out_rgb,
                     unsigned long long vcap, const unsigned *tri, long long n_tri, const uint8_t *flag, const unsigned long long *toffsets,
-                    unsigned *out_tri, unsigned long long tcap) {
-    if (n_vert > 0 && vcap > 0) {
+                    unsigned *out_tri, unsigned long long tcap, const unsigned long long *qacc, double reg, unsigned long long *info) {
+    if (n_vert > 0 && qacc) {
+        hipLaunchKernelGGL(ms_vert_write_quadric_kernel, dim3(blocks_of((unsigned long long)n_vert, 256)), dim3(256), 0, s, ms_cell(cell, o), reg,
+                           xyz, colours, (unsigned)n_vert, slot, leader, vmap, acc, qacc, out_xyz, out_rgb, vcap, info);
+        TL3D_HIP(hipGetLastError());
+    } else if (n_vert > 0 && vcap > 0) {
         hipLaunchKernelGGL(ms_vert_write_kernel, dim3(blocks_of((unsigned long long)n_vert, 256)), dim3(256), 0, s, ms_cell(cell, o), xyz, colours,
                            (unsigned)n_vert, slot, leader, vmap, acc, out_xyz, out_rgb, vcap);
         TL3D_HIP(hipGetLastError());

@@ -399,6 +399,7 @@ static void release_grid(tl3d_ctx *ctx) {
     if (gs.ms_slot) (void)hipFree(gs.ms_slot);
     if (gs.ms_vmap) (void)hipFree(gs.ms_vmap);
     if (gs.ms_acc) (void)hipFree(gs.ms_acc);
+    if (gs.ms_qacc) (void)hipFree(gs.ms_qacc);
     if (gs.ms_ttab) (void)hipFree(gs.ms_ttab);
     if (gs.ms_flag) (void)hipFree(gs.ms_flag);
     if (gs.adj_cnt) (void)hipFree(gs.adj_cnt);
@@ -2935,54 +2936,93 @@ static int ms_grow(tl3d_ctx *ctx, int64_t n_tri, int64_t n_vert) {
     return rc;
 }
 
-int tl3d_mesh_simplify_clusters(tl3d_ctx *ctx, const float *xyz, const uint8_t *rgb, int64_t n_vert, const uint32_t *tri, int64_t n_tri,
-                                double cell, const double origin[3], float *out_xyz, uint8_t *out_rgb, int64_t vert_cap,
-                                uint32_t *out_tri, int64_t tri_cap, uint32_t *vert_map_out, int64_t *out_n_vert, int64_t *out_n_tri,
-                                int64_t *out_n_degenerate, int64_t *out_n_duplicate) {
+// Both placements.  quadric: the three extra counts (placed, clamped, corners skipped), or nullptr for mean placement, which
+// then launches, copies and waits exactly as it did before the quadric existed.
+static int ms_simplify(tl3d_ctx *ctx, const float *xyz, const uint8_t *rgb, int64_t n_vert, const uint32_t *tri, int64_t n_tri, double cell,
+                       const double origin[3], double reg, float *out_xyz, uint8_t *out_rgb, int64_t vert_cap, uint32_t *out_tri,
+                       int64_t tri_cap, uint32_t *vert_map_out, int64_t *const counts[4], int64_t *const quadric[3]) {
     MeshIO m{xyz, rgb, n_vert, tri, n_tri, out_xyz, out_rgb, vert_cap, out_tri, tri_cap};
-    int rc = m.check_sizes(out_n_vert && out_n_tri && out_n_degenerate && out_n_duplicate);
+    int rc = m.check_sizes(counts[0] && counts[1] && counts[2] && counts[3] && (!quadric || (quadric[0] && quadric[1] && quadric[2])));
     if (rc) return rc;
     REQUIRE(std::isfinite(cell) && cell > 0.0, TL3D_E_INVALID, "cell size %g: must be finite and > 0", cell);
     const double o[3] = {origin ? origin[0] : 0.0, origin ? origin[1] : 0.0, origin ? origin[2] : 0.0};
     REQUIRE(std::isfinite(o[0]) && std::isfinite(o[1]) && std::isfinite(o[2]), TL3D_E_INVALID, "origin (%g, %g, %g) is not finite", o[0], o[1], o[2]);
+    REQUIRE(!quadric || (std::isfinite(reg) && reg > 0.0 && reg <= 1.0), TL3D_E_INVALID, "reg %g: must lie in (0, 1]", reg);
     rc = m.check_arrays(vert_map_out, (size_t)n_vert * 4);
     if (rc) return rc;
     REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
-    *out_n_vert = *out_n_tri = *out_n_degenerate = *out_n_duplicate = 0;
+    for (int k = 0; k < 4; ++k) *counts[k] = 0;
+    for (int k = 0; quadric && k < 3; ++k) *quadric[k] = 0;
     if (n_vert == 0) return TL3D_OK;
     TL3D_HIP(hipSetDevice(ctx->device));
     rc = ms_grow(ctx, n_tri, n_vert);
+    if (!rc && quadric) rc = grow(&ctx->ms_qacc, &ctx->ms_qacc_n, 18 * (size_t)n_vert, "mesh simplification scratch");
     if (rc) return rc;
     Staging st(ctx);
     rc = m.stage_in(st);
     if (rc) return rc;
     // the validation passes: nothing is indexed, and no cell is computed for a table, before the host has seen their words
-    unsigned long long h[4] = {0, 0, 0, 0};
+    unsigned long long h[4] = {0, 0, 0, 0}, hq[3] = {0, 0, 0};
     rc = mio_validate(ctx, m.dtri, n_tri, n_vert, [&] { return launch_ms_validate(ctx->stream, cell, o, m.dxyz, n_vert, ctx->mio_info); }, &h[1]);
     if (rc) return rc;
     REQUIRE(h[1] == 0, TL3D_E_INVALID, "%llu vertices are not finite or lie 2^20 cells or more from the origin", h[1]);
     const size_t vslots = kt_slots((size_t)n_vert), tslots = kt_slots((size_t)n_tri);
     const ChunkHalves ch(ctx->mio_counts, ctx->mio_offsets, chunks_of(n_vert), chunks_of(n_tri));
     unsigned *leader = ctx->kt_vals;
+    unsigned long long *qacc = quadric ? ctx->ms_qacc : nullptr;
     TL3D_HIP(hipMemsetAsync(leader, 0xFF, vslots * sizeof(unsigned), ctx->stream));
     TL3D_HIP(hipMemsetAsync(ctx->ms_acc, 0, 7 * (size_t)n_vert * sizeof(unsigned long long), ctx->stream));
+    if (qacc) TL3D_HIP(hipMemsetAsync(qacc, 0, 18 * (size_t)n_vert * sizeof(unsigned long long), ctx->stream));
     if (n_tri) TL3D_HIP(hipMemsetAsync(ctx->ms_ttab, 0xFF, tslots * sizeof(unsigned), ctx->stream));
     rc = launch_ms_cluster(ctx->stream, cell, o, m.dxyz, m.drgb, n_vert, ctx->kt_keys, leader, vslots, ctx->ms_slot, ctx->ms_vmap,
                            ctx->ms_acc, ch.counts[0], ch.offs[0]);
+    if (!rc && qacc) rc = launch_ms_quadrics(ctx->stream, cell, o, m.dxyz, m.dtri, n_tri, ctx->ms_vmap, qacc, ctx->mio_info);
     if (!rc) rc = launch_ms_triangles(ctx->stream, m.dtri, n_tri, ctx->ms_vmap, ctx->ms_ttab, tslots, ctx->ms_flag, ch.counts[1], ch.offs[1], ctx->mio_info);
     unsigned long long tot[2] = {0, 0};
     if (!rc) rc = ch.totals(ctx->stream, tot, ctx->mio_info, h);
     if (rc) return rc;
-    *out_n_vert = (int64_t)tot[0];
-    *out_n_tri = (int64_t)tot[1];
-    *out_n_degenerate = (int64_t)h[2];
-    *out_n_duplicate = (int64_t)h[3];
+    *counts[0] = (int64_t)tot[0];
+    *counts[1] = (int64_t)tot[1];
+    *counts[2] = (int64_t)h[2];
+    *counts[3] = (int64_t)h[3];
     rc = m.stage_out(st, tot);
+    if (rc == TL3D_E_CAPACITY && quadric) {
+        // the solve counts what it places and clamps: run it without outputs, so that the refusal reports all seven counts
+        int rq = launch_ms_write(ctx->stream, cell, o, m.dxyz, false, n_vert, ctx->ms_slot, leader, ctx->ms_vmap, ctx->ms_acc, nullptr, nullptr, 0,
+                                 m.dtri, n_tri, ctx->ms_flag, ch.offs[1], nullptr, 0, qacc, reg, ctx->mio_info);
+        if (rq) return rq;
+        TL3D_HIP(hipMemcpyAsync(hq, ctx->mio_info + 4, sizeof(hq), hipMemcpyDeviceToHost, ctx->stream));
+        TL3D_HIP(hipStreamSynchronize(ctx->stream));
+        *quadric[0] = (int64_t)hq[1]; *quadric[1] = (int64_t)hq[2]; *quadric[2] = (int64_t)hq[0];
+    }
     if (rc) return rc;
     rc = launch_ms_write(ctx->stream, cell, o, m.dxyz, rgb != nullptr, n_vert, ctx->ms_slot, leader, ctx->ms_vmap, ctx->ms_acc, m.oxyz, m.orgb,
-                         tot[0], m.dtri, n_tri, ctx->ms_flag, ch.offs[1], m.otri, tot[1]);
+                         tot[0], m.dtri, n_tri, ctx->ms_flag, ch.offs[1], m.otri, tot[1], qacc, reg, ctx->mio_info);
     if (!rc && vert_map_out) TL3D_HIP(hipMemcpyAsync(vert_map_out, ctx->ms_vmap, (size_t)n_vert * 4, hipMemcpyDefault, ctx->stream));
-    return st.finish(rc, true);
+    if (!rc && quadric) TL3D_HIP(hipMemcpyAsync(hq, ctx->mio_info + 4, sizeof(hq), hipMemcpyDeviceToHost, ctx->stream));
+    rc = st.finish(rc, true);
+    if (!rc && quadric) { *quadric[0] = (int64_t)hq[1]; *quadric[1] = (int64_t)hq[2]; *quadric[2] = (int64_t)hq[0]; }
+    return rc;
+}
+
+int tl3d_mesh_simplify_clusters(tl3d_ctx *ctx, const float *xyz, const uint8_t *rgb, int64_t n_vert, const uint32_t *tri, int64_t n_tri,
+                                double cell, const double origin[3], float *out_xyz, uint8_t *out_rgb, int64_t vert_cap,
+                                uint32_t *out_tri, int64_t tri_cap, uint32_t *vert_map_out, int64_t *out_n_vert, int64_t *out_n_tri,
+                                int64_t *out_n_degenerate, int64_t *out_n_duplicate) {
+    int64_t *const counts[4] = {out_n_vert, out_n_tri, out_n_degenerate, out_n_duplicate};
+    return ms_simplify(ctx, xyz, rgb, n_vert, tri, n_tri, cell, origin, 0.0, out_xyz, out_rgb, vert_cap, out_tri, tri_cap, vert_map_out, counts,
+                       nullptr);
+}
+
+int tl3d_mesh_simplify_quadric(tl3d_ctx *ctx, const float *xyz, const uint8_t *rgb, int64_t n_vert, const uint32_t *tri, int64_t n_tri,
+                               double cell, const double origin[3], double reg, float *out_xyz, uint8_t *out_rgb, int64_t vert_cap,
+                               uint32_t *out_tri, int64_t tri_cap, uint32_t *vert_map_out, int64_t *out_n_vert, int64_t *out_n_tri,
+                               int64_t *out_n_degenerate, int64_t *out_n_duplicate, int64_t *out_n_quadric, int64_t *out_n_clamped,
+                               int64_t *out_n_skipped) {
+    int64_t *const counts[4] = {out_n_vert, out_n_tri, out_n_degenerate, out_n_duplicate};
+    int64_t *const quadric[3] = {out_n_quadric, out_n_clamped, out_n_skipped};
+    return ms_simplify(ctx, xyz, rgb, n_vert, tri, n_tri, cell, origin, reg, out_xyz, out_rgb, vert_cap, out_tri, tri_cap, vert_map_out, counts,
+                       quadric);
 }
 
 // ------------------------------------------------------------------------------------------- mesh smoothing, vertex normals

@@ -251,11 +251,14 @@ struct tl3d_grid_state {
     unsigned *kt_vals;
     size_t kt_val_slots;
     // tl3d_mesh_simplify_clusters: per vertex its slot in the key table and its cluster number, per cluster
-    // seven 64-bit sums (n, S, C), the triangle table (one index per slot, kt_slots(n_tri) slots), a class byte per triangle.
+    // seven 64-bit sums (n, S, C), the triangle table (one index per slot, kt_slots(n_tri) slots), a class byte per triangle;
+    // tl3d_mesh_simplify_quadric alone grows the nine 128-bit quadric sums per cluster beside them.
     // Grid-independent like the cc_ scratch, and here for the same reason.
     unsigned *ms_slot, *ms_vmap;
     unsigned long long *ms_acc;             // [7 per vertex]
     size_t ms_verts, ms_acc_n;              // capacity of ms_slot / ms_vmap in vertices, of ms_acc in words
+    unsigned long long *ms_qacc;            // tl3d_mesh_simplify_quadric only: [18 per vertex], nine 128-bit sums as (lo, hi)
+    size_t ms_qacc_n;                       // in words
     unsigned *ms_ttab;
     size_t ms_tslots;
     uint8_t *ms_flag;
@@ -287,7 +290,9 @@ struct tl3d_grid_state {
     //   [1]    components                                      vertices without a cell       vertices out of range
     //   [2]    key of the largest component (cc_roots_kernel)  degenerate triangles          unique edges
     //   [3]    kept components                                 duplicate triangles           a step left the range / zero normals
-    //   [4]                                                                                  a step left the range (steps take [3], [4] in turn)
+    //   [4]                                                    corners skipped (quadric)     a step left the range (steps take [3], [4] in turn)
+    //   [5]                                                    clusters placed by a quadric
+    //   [6]                                                    clusters clamped
     // tl3d_mesh_weld_keyed: [0] indices out of range, [1] keys out of range, [2] the largest offending (part << 32 | index),
     // [3] vertices owned twice, [4] unowned corners
     unsigned *mio_counts;                   // [vertex chunks + 1][triangle chunks + 1]
@@ -624,12 +629,15 @@ int launch_ms_validate(hipStream_t s, double cell, const double o[3], const floa
 int launch_ms_cluster(hipStream_t s, double cell, const double o[3], const float *xyz, const uint8_t *rgb, long long n_vert,
                       unsigned long long *keys, unsigned *leader, unsigned long long vcap, unsigned *slot, unsigned *vmap,
                       unsigned long long *acc, unsigned *vcounts, unsigned long long *voffsets);
+int launch_ms_quadrics(hipStream_t s, double cell, const double o[3], const float *xyz, const unsigned *tri, long long n_tri,
+                       const unsigned *vmap, unsigned long long *qacc, unsigned long long *info);
 int launch_ms_triangles(hipStream_t s, const unsigned *tri, long long n_tri, const unsigned *vmap, unsigned *ttab, unsigned long long tcap,
                         uint8_t *flag, unsigned *tcounts, unsigned long long *toffsets, unsigned long long *info);
 int launch_ms_write(hipStream_t s, double cell, const double o[3], const float *xyz, bool colours, long long n_vert, const unsigned *slot,
                     const unsigned *leader, const unsigned *vmap, const unsigned long long *acc, float *out_xyz, uint8_t *out_rgb,
                     unsigned long long vcap, const unsigned *tri, long long n_tri, const uint8_t *flag, const unsigned long long *toffsets,
-                    unsigned *out_tri, unsigned long long tcap);
+                    unsigned *out_tri, unsigned long long tcap, const unsigned long long *qacc = nullptr, double reg = 0.0,
+                    unsigned long long *info = nullptr);
 int sor_mean_distance(tl3d_ctx *ctx, const float *xyz_dev, long long n, int k, double cell, double *mean_dev);
 int sor_run(tl3d_ctx *ctx, const float *xyz_dev, long long n, int k, double std_ratio, double cell, uint8_t *keep_dev, long long *kept);
 

@@ -744,14 +744,21 @@ class FusionContext:
                     keep_vert=keep.astype(bool) if isinstance(keep, np.ndarray) else keep.bool())
         return oxyz[:kv.value], (orgb[:kv.value] if orgb is not None else None), otri[:kt.value], info
 
-    def simplify_mesh(self, xyz, rgb, tris, cell: float, origin=None):
+    def simplify_mesh(self, xyz, rgb, tris, cell: float, origin=None, placement: str = "mean", reg: float = 2.0 ** -10):
         """Vertex-clustering simplification of a mesh (needs no grid): the vertices of one cell of
         size `cell` (metres, on a lattice through `origin`, default (0, 0, 0)) become one vertex at their mean position and
         colour, numbered in the order of each cell's first vertex; triangles are mapped, the ones that collapse and the repeats
         of an earlier triangle go, the rest keep their order and winding.  Every cell becomes a vertex, also one no surviving
         triangle names (filter_mesh(min_triangles=1) drops those).  Same bytes in every run.  rgb may be None.  Returns
         (xyz, rgb, tris, info); info: clusters, vertices_in, triangles_in, degenerate_dropped, duplicates_dropped and
-        vert_map (u32 [V]: the output vertex of every input vertex)."""
+        vert_map (u32 [V]: the output vertex of every input vertex).
+        placement="quadric" (tl3d_mesh_simplify_quadric) changes only the positions: a merged vertex goes where the planes of the
+        triangles around its cell meet (Lindstrom's quadric clustering, regularised towards the mean by `reg` in (0, 1]), clamped
+        to its cell.  That keeps creases and corners of piecewise planar meshes; on smooth surfaces it gains nothing.  info then
+        also has quadric_placed (clusters with a quadric; the others sit at the mean), clamped and corners_skipped (triangle
+        corners whose triangle spans more than 3 cells)."""
+        if placement not in ("mean", "quadric"):
+            raise ValueError(f"placement = {placement!r}: must be 'mean' or 'quadric'")
         xyz, rgb, tris, empty = self._mesh_arrays(xyz, rgb, tris)
         nv, nt = len(xyz), len(tris)
         oxyz, otri = empty((nv, 3), np.float32), empty((nt, 3), np.uint32)
@@ -762,10 +769,18 @@ class FusionContext:
 
         def p(a):
             return abi.ptr(a) if a is not None and len(a) else None
-        abi.check(self._lib.tl3d_mesh_simplify_clusters(self._h, p(xyz), p(rgb), nv, p(tris), nt, float(cell), o, p(oxyz), p(orgb), nv,
-                                                        p(otri), nt, p(vmap), C.byref(kv), C.byref(kt), C.byref(ng), C.byref(nd)))
+        if placement == "quadric":
+            nq, nc, ns = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+            abi.check(self._lib.tl3d_mesh_simplify_quadric(self._h, p(xyz), p(rgb), nv, p(tris), nt, float(cell), o, float(reg), p(oxyz),
+                                                           p(orgb), nv, p(otri), nt, p(vmap), C.byref(kv), C.byref(kt), C.byref(ng),
+                                                           C.byref(nd), C.byref(nq), C.byref(nc), C.byref(ns)))
+        else:
+            abi.check(self._lib.tl3d_mesh_simplify_clusters(self._h, p(xyz), p(rgb), nv, p(tris), nt, float(cell), o, p(oxyz), p(orgb), nv,
+                                                            p(otri), nt, p(vmap), C.byref(kv), C.byref(kt), C.byref(ng), C.byref(nd)))
         info = dict(clusters=kv.value, vertices_in=nv, triangles_in=nt, degenerate_dropped=ng.value, duplicates_dropped=nd.value,
                     vert_map=vmap)
+        if placement == "quadric":
+            info.update(quadric_placed=nq.value, clamped=nc.value, corners_skipped=ns.value)
         return oxyz[:kv.value], (orgb[:kv.value] if orgb is not None else None), otri[:kt.value], info
 
     def smooth_mesh(self, xyz, tris, iterations: int, lam: float = 0.5, mu: float = -0.53):

@@ -939,6 +939,11 @@ class DepthToReconstructionPipeline:
             raise ValueError(f"mesh_simplify_cell = {cell}: must be a finite size in metres, or 0 for none")
         if cell > 0.0 and not self.config.extract_mesh:
             raise ValueError("mesh_simplify_cell simplifies the mesh: it needs extract_mesh = True")
+        placement = getattr(self.config, "mesh_simplify_placement", "mean")
+        if placement not in ("mean", "quadric"):
+            raise ValueError(f"mesh_simplify_placement = {placement!r}: must be 'mean' or 'quadric'")
+        if placement == "quadric" and not cell > 0.0:
+            raise ValueError("mesh_simplify_placement = 'quadric' places the simplified mesh's vertices: it needs mesh_simplify_cell > 0")
 
         it = getattr(self.config, "mesh_smooth_iterations", 0)
         lam, mu = float(getattr(self.config, "mesh_smooth_lambda", 0.5)), float(getattr(self.config, "mesh_smooth_mu", -0.53))
@@ -982,13 +987,18 @@ class DepthToReconstructionPipeline:
     def _simplify_mesh(self, ctx: FusionContext, mesh):
         """The mesh with the vertices of every cell of config.mesh_simplify_cell merged (FusionContext.simplify_mesh, DESIGN.md
         section 4.2.2).  The cell lattice goes through (0, 0, 0), so the result does not depend on where grids or blocks were
-        placed; stats["mesh_simplify"] says what was merged and dropped."""
+        placed; stats["mesh_simplify"] says what was merged and dropped.  config.mesh_simplify_placement = "quadric" puts every
+        merged vertex where its triangles' planes meet instead of at the mean (reg = 2^-10), and adds the placement and its three
+        counts to the stats."""
         cell = float(self.config.mesh_simplify_cell)
-        xyz, rgb, tris, info = ctx.simplify_mesh(*mesh, cell=cell, origin=(0.0, 0.0, 0.0))
+        placement = getattr(self.config, "mesh_simplify_placement", "mean")
+        xyz, rgb, tris, info = ctx.simplify_mesh(*mesh, cell=cell, origin=(0.0, 0.0, 0.0), placement=placement)
         info.pop("vert_map")
-        self.stats["mesh_simplify"] = dict(info, cell=cell)
+        self.stats["mesh_simplify"] = dict(info, cell=cell, **({"placement": placement} if placement != "mean" else {}))
+        quadric = (f"; quadric placement: {info['quadric_placed']} vertices, {info['clamped']} clamped, {info['corners_skipped']} corners "
+                   f"skipped" if placement == "quadric" else "")
         print(f"  Mesh simplify: cell {cell:g} m, {info['vertices_in']} -> {info['clusters']} vertices, {info['triangles_in']} -> {len(tris)} "
-              f"triangles ({info['degenerate_dropped']} degenerate, {info['duplicates_dropped']} duplicate)")
+              f"triangles ({info['degenerate_dropped']} degenerate, {info['duplicates_dropped']} duplicate){quadric}")
         return xyz, rgb, tris
 
     def _filter_mesh(self, ctx: FusionContext, mesh):

@@ -5,9 +5,10 @@ the mesh into device buffers, then times, with device events after two warm-ups,
 buffers in, device buffers out, origin (0, 0, 0)) at cells of --cells voxels, median of --reps calls each, and one complete
 tl3d_mesh_filter_components of the same mesh for scale.  Prints vertices and triangles in and out and the ms per cell size, beside
 the extraction figure of DESIGN.md section 7.7, and whether the result equals the numpy restatement of the rules
-(tests/mesh_simplify_reference.py) on the host.
+(tests/mesh_simplify_reference.py) on the host.  --placement quadric times tl3d_mesh_simplify_quadric (reg 2^-10) instead, against
+tests/mesh_simplify_quadric_reference.py; --placement both times the two calls of one build side by side, cell by cell.
 
-    python tools/bench_mesh_simplify.py [--reps 20] [--frames 512] [--cells 2,4,8]
+    python tools/bench_mesh_simplify.py [--reps 20] [--frames 512] [--cells 2,4,8] [--placement mean|quadric|both] [--no-check]
 """
 import argparse
 import ctypes as C
@@ -28,6 +29,8 @@ def main():
     ap.add_argument("--group", type=int, default=64, help="frames resident at once")
     ap.add_argument("--cells", type=str, default="2,4,8", help="cell sizes in voxels")
     ap.add_argument("--min-triangles", type=int, default=100, help="threshold of the component filter timed for scale")
+    ap.add_argument("--placement", choices=("mean", "quadric", "both"), default="mean", help="which call(s) to time")
+    ap.add_argument("--no-check", action="store_true", help="skip the comparison with the restatement on the host")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -35,6 +38,7 @@ def main():
     from tl3d import _cabi as abi
     from tl3d import synth
     sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import mesh_simplify_quadric_reference as mqr
     import mesh_simplify_reference as msr
 
     hl = synth.HEADLINE
@@ -62,7 +66,7 @@ def main():
         mxyz, mrgb, mtri = (torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).to(dev) for a in ctx.extract_mesh())
         nv, nt = len(mxyz), len(mtri)
         oxyz, orgb, otri = torch.empty_like(mxyz), torch.empty_like(mrgb), torch.empty_like(mtri)
-        cnt = [C.c_int64(0) for _ in range(4)]
+        cnt = [C.c_int64(0) for _ in range(7)]
 
         def timed(fn):
             ms = []
@@ -79,7 +83,7 @@ def main():
 
         def run_filter():
             abi.check(lib.tl3d_mesh_filter_components(ctx._h, abi.ptr(mxyz), abi.ptr(mrgb), nv, abi.ptr(mtri), nt, args.min_triangles, 0,
-                                                      abi.ptr(oxyz), abi.ptr(orgb), nv, abi.ptr(otri), nt, None, *[C.byref(c) for c in cnt]))
+                                                      abi.ptr(oxyz), abi.ptr(orgb), nv, abi.ptr(otri), nt, None, *[C.byref(c) for c in cnt[:4]]))
         t_filter = timed(run_filter)
         host = [a.cpu().numpy() for a in (mxyz, mrgb, mtri)]
         host[2] = host[2].view(np.uint32)
@@ -87,20 +91,36 @@ def main():
         for vox in [float(v) for v in args.cells.split(",")]:
             cell = vox * hl["voxel"]
 
-            def run_simplify():
+            def run_mean():
                 abi.check(lib.tl3d_mesh_simplify_clusters(ctx._h, abi.ptr(mxyz), abi.ptr(mrgb), nv, abi.ptr(mtri), nt, cell, None, abi.ptr(oxyz),
-                                                          abi.ptr(orgb), nv, abi.ptr(otri), nt, None, *[C.byref(c) for c in cnt]))
-            t = timed(run_simplify)
-            kv, kt = cnt[0].value, cnt[1].value
-            t0 = time.perf_counter()
-            want = msr.simplify(*host, cell)
-            t_host = time.perf_counter() - t0
-            equal = (kv == len(want[0]) and kt == len(want[2]) and np.array_equal(oxyz[:kv].cpu().numpy(), want[0])
-                     and np.array_equal(orgb[:kv].cpu().numpy(), want[1]) and np.array_equal(otri[:kt].cpu().numpy().view(np.uint32), want[2]))
-            rows.append(dict(cell_voxels=vox, cell_m=cell, vertices_out=kv, triangles_out=kt, degenerate_dropped=cnt[2].value,
-                             duplicates_dropped=cnt[3].value, simplify_ms_median=round(t[0], 3), simplify_ms_min=round(t[1], 3),
-                             simplify_over_mesh_extract=round(t[0] / MESH_EXTRACT_MS, 3), host_reference_ms=round(1e3 * t_host, 1),
-                             equals_host_reference=bool(equal)))
+                                                          abi.ptr(orgb), nv, abi.ptr(otri), nt, None, *[C.byref(c) for c in cnt[:4]]))
+
+            def run_quadric():
+                abi.check(lib.tl3d_mesh_simplify_quadric(ctx._h, abi.ptr(mxyz), abi.ptr(mrgb), nv, abi.ptr(mtri), nt, cell, None, mqr.REG,
+                                                         abi.ptr(oxyz), abi.ptr(orgb), nv, abi.ptr(otri), nt, None, *[C.byref(c) for c in cnt]))
+            mean = None
+            for placement in ("mean", "quadric"):
+                if args.placement not in (placement, "both"):
+                    continue
+                t = timed(run_mean if placement == "mean" else run_quadric)
+                kv, kt = cnt[0].value, cnt[1].value
+                row = dict(cell_voxels=vox, cell_m=cell, placement=placement, vertices_out=kv, triangles_out=kt, degenerate_dropped=cnt[2].value,
+                           duplicates_dropped=cnt[3].value, simplify_ms_median=round(t[0], 3), simplify_ms_min=round(t[1], 3),
+                           simplify_over_mesh_extract=round(t[0] / MESH_EXTRACT_MS, 3))
+                if placement == "quadric":
+                    row.update(quadric_placed=cnt[4].value, clamped=cnt[5].value, corners_skipped=cnt[6].value)
+                if not args.no_check:
+                    t0 = time.perf_counter()
+                    mean = mean if mean is not None else msr.simplify(*host, cell)
+                    want = mean if placement == "mean" else mqr.simplify(*host, cell, mean=mean)
+                    t_host = time.perf_counter() - t0
+                    equal = (kv == len(want[0]) and kt == len(want[2]) and np.array_equal(oxyz[:kv].cpu().numpy(), want[0])
+                             and np.array_equal(orgb[:kv].cpu().numpy(), want[1])
+                             and np.array_equal(otri[:kt].cpu().numpy().view(np.uint32), want[2])
+                             and (placement == "mean" or [c.value for c in cnt[4:]] == [want[3][k] for k in ("quadric_placed", "clamped",
+                                                                                                            "corners_skipped")]))
+                    row.update(host_reference_ms=round(1e3 * t_host, 1), equals_host_reference=bool(equal))
+                rows.append(row)
     print(json.dumps(dict(grid=spec.dims, voxel=spec.voxel_size, frames=args.frames, vertices_in=nv, triangles_in=nt, reps=args.reps,
                           mesh_extract_ms_design_7_7=MESH_EXTRACT_MS, filter_components_ms_median=round(t_filter[0], 3),
                           filter_components_ms_min=round(t_filter[1], 3), cells=rows)))
