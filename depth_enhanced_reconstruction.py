@@ -42,9 +42,18 @@ def main(argv=None):
                         help="find revisits among the registered poses, register them too and optimise every pose over the resulting graph before fusing")
     parser.add_argument("--model-tracking", action="store_true",
                         help="after the registration, register every kept frame against the TSDF fused from the frames before it and fuse at those poses")
+    parser.add_argument("--compare-to", type=str, default=None, metavar="REF.ply",
+                        help="score the fused cloud against the vertices of this PLY on the GPU: prints "
+                             "one line with the mean Chamfer distance and precision / recall / F-score at the thresholds")
+    parser.add_argument("--compare-threshold", type=float, action="append", default=None, metavar="M",
+                        help="a distance threshold of --compare-to, in metres (repeatable, at most 8; default 0.005 0.01 0.02)")
+    parser.add_argument("--compare-max-dist", type=float, default=None, metavar="M",
+                        help="points with no neighbour within this distance count as unmatched (default: no limit)")
     parser.add_argument("--device", type=int, default=0)
     args = parser.parse_args(argv)
 
+    if args.compare_threshold and len(args.compare_threshold) > 8:
+        parser.error("--compare-threshold: at most 8 thresholds")
     from tl3d import fileio
     from tl3d.config import ReconstructionConfig
     from tl3d.pipeline import DepthToReconstructionPipeline
@@ -61,6 +70,8 @@ def main(argv=None):
     config = ReconstructionConfig(fx=args.fx, fy=args.fy, cx=args.cx, cy=args.cy, min_depth=0.1, max_depth=100.0,
                                   voxel_size=0.005, subsample_factor=4, grid_dim=args.grid, device=args.device,
                                   depth_scale=args.depth_scale, loop_closure=args.loop_closure, model_tracking=args.model_tracking,
+                                  compare_to=args.compare_to, compare_max_dist=args.compare_max_dist,
+                                  compare_thresholds=tuple(args.compare_threshold) if args.compare_threshold else (0.005, 0.01, 0.02),
                                   outlier_filter=False)                   # DER's merge_pointclouds has no outlier filter (DER:615-645)
     pipeline = DepthToReconstructionPipeline(config)
     if args.depth_model:

@@ -98,6 +98,13 @@ def main(argv=None):
     parser.add_argument("--model-tracking", action="store_true",
                         help="after the registration, register every kept frame against the TSDF fused from the frames before it "
                              "(point-to-SDF) and fuse at those poses (one GPU only; not with --estimate-scale)")
+    parser.add_argument("--compare-to", type=str, default=None, metavar="REF.ply",
+                        help="score the fused cloud (and the mesh, with --mesh-output) against the vertices of this PLY on the GPU: prints "
+                             "one line with the mean Chamfer distance and precision / recall / F-score at the thresholds")
+    parser.add_argument("--compare-threshold", type=float, action="append", default=None, metavar="M",
+                        help="a distance threshold of --compare-to, in metres (repeatable, at most 8; default 0.005 0.01 0.02)")
+    parser.add_argument("--compare-max-dist", type=float, default=None, metavar="M",
+                        help="points with no neighbour within this distance count as unmatched (default: no limit)")
     parser.add_argument("--device", type=int, default=0)
     parser.add_argument("--stream", dest="stream", action="store_true", default=True,
                         help="(default) decode on worker threads into pinned buffers with asynchronous uploads; host RAM never holds the sequence")
@@ -121,6 +128,8 @@ def main(argv=None):
         parser.error("--mesh-smooth / --mesh-normals work on the mesh: they need --mesh-output")
     if args.mesh_weld != "host" and not args.mesh_output:
         parser.error("--mesh-weld device welds the mesh: it needs --mesh-output")
+    if args.compare_threshold and len(args.compare_threshold) > 8:
+        parser.error("--compare-threshold: at most 8 thresholds")
     if args.loop_closure and (args.gpus > 1 or world > 1):
         parser.error("--loop-closure needs a single GPU: every kept frame must be resident where the revisits are registered")
     if args.loop_closure and args.estimate_scale:
@@ -147,7 +156,9 @@ def main(argv=None):
                                   model_tracking=args.model_tracking, mesh_min_component_triangles=max(0, args.mesh_min_component),
                                   mesh_largest_component=args.mesh_largest_component, mesh_simplify_cell=args.mesh_simplify_cell,
                                   mesh_simplify_placement=args.mesh_simplify_placement,
-                                  mesh_smooth_iterations=args.mesh_smooth, mesh_normals=args.mesh_normals, mesh_weld=args.mesh_weld)
+                                  mesh_smooth_iterations=args.mesh_smooth, mesh_normals=args.mesh_normals, mesh_weld=args.mesh_weld,
+                                  compare_to=args.compare_to, compare_max_dist=args.compare_max_dist,
+                                  compare_thresholds=tuple(args.compare_threshold) if args.compare_threshold else (0.005, 0.01, 0.02))
     pipeline = DepthToReconstructionPipeline(config)
     # a rank decodes every frame on its host (pose chain and scale rule run over the whole sequence) and uploads its share
     streaming = args.stream and dist is None

@@ -611,6 +611,56 @@ int tl3d_statistical_outlier(tl3d_ctx *ctx, const float *xyz_hd, int64_t n, int 
  * search grid (doubled until it has at most 2^27 cells); the result does not depend on it. */
 int tl3d_knn_mean_distance(tl3d_ctx *ctx, const float *xyz_hd, int64_t n, int nb_neighbors, double cell_size, double *mean_out_hd);
 
+/* Exact nearest neighbours from one set to ANOTHER (no reference code: the reference never scores a cloud -- the
+ * definition is Open3D's compute_point_cloud_distance).  Per query point q: dist_out[q] = the fp64 distance to the nearest target
+ * point (differences of the f32 coordinates, squares and their sum in fp64, one correctly rounded root) and index_out[q] = its index;
+ * the winner is the minimum over the pair (d^2, index), so an exact tie goes to the smaller index and nothing depends on the order
+ * the search meets the points in.  Host or device pointers throughout; either output may be NULL; no grid is needed.
+ * cell_size only sets the search grid over the target's box (doubled until it has at most 2^27 cells) and never changes a result;
+ * cell_size <= 0: (V / (4 n_target))^(1/k) with V the product of the box's k non-zero extents (1 for a box without extent).
+ * max_dist <= 0: unlimited; otherwise a query with nothing at distance <= max_dist gets +inf and -1.  An empty target gives +inf / -1
+ * for every query and TL3D_OK; n_query == 0 is TL3D_OK.  Queries may lie anywhere, far outside the target's box included.
+ * TL3D_E_INVALID before any device work: a null ctx, negative sizes, n_target >= 2^31, an output that overlaps an input (or the
+ * other output); and from a device pass in front of the search, with nothing written: a non-finite coordinate in either set.
+ * Tests (tests/test_gpu_nearest.py): distances within 1e-12 relative of an fp64 brute force and exactly 0 where it is 0, the index
+ * the smallest-index minimiser on exact ties, the same bytes for every cell size, for host and device arrays and in every run. */
+int tl3d_nearest_points(tl3d_ctx *ctx, const float *query_hd, int64_t n_query,
+                        const float *target_hd, int64_t n_target, double cell_size, double max_dist,
+                        double *dist_out_hd, int32_t *index_out_hd);
+
+/* The same against an indexed triangle list: dist_out[q] = the fp64 distance from q to the nearest point of the nearest CLOSED
+ * triangle (the plane distance where the foot of the perpendicular lies inside, else the minimum over the three closed edges),
+ * tri_out[q] = that triangle, the smaller index on an exact tie.  Triangles with collinear or repeated corners are segments or
+ * points and measure as such (never NaN).  A triangle is listed in every cell its box overlaps; the cell doubles until that list
+ * has at most min(16 n_tri + 2^20, 2^31) entries, so one triangle across the whole box beside thousands of small ones costs memory
+ * in proportion to n_tri.  cell_size <= 0: the mean over the triangles of their box's largest extent.  Everything else as
+ * tl3d_nearest_points, with n_vert and n_tri < 2^31 and, from the device pass, TL3D_E_INVALID for a triangle index >= n_vert
+ * (compared before it is used) and for a non-finite vertex.  Unreferenced vertices only widen the search grid.
+ * Tests: within 16 eps_tri x the box diagonal of an fp64 reference held against a long-double second formulation. */
+int tl3d_nearest_triangles(tl3d_ctx *ctx, const float *query_hd, int64_t n_query,
+                           const float *xyz_hd, int64_t n_vert, const uint32_t *tri_hd, int64_t n_tri,
+                           double cell_size, double max_dist, double *dist_out_hd, int32_t *tri_out_hd);
+
+/* Summary of a distance array (host or device): n, the finite entries, their sum, sum of squares and maximum (0 without one), and
+ * per threshold t_j (at most 8) the entries <= t_j.  Fixed reduction shape (1024 block partials added in block order): the same
+ * input gives the same bytes in every run; the counts and the maximum are exact.  +inf entries (queries beyond max_dist) are no
+ * finite entries and lie under no finite threshold.  TL3D_E_INVALID: null ctx / out, n < 0, more than 8 thresholds.
+ * The struct is tl3d_distance_stats: C has one name space for typedefs and functions. */
+typedef struct tl3d_distance_stats {
+    int64_t n;
+    int64_t n_finite;
+    double  sum;
+    double  sum_sq;
+    double  max;
+    int64_t below[8];
+} tl3d_distance_stats;
+int tl3d_distance_summary(tl3d_ctx *ctx, const double *dist_hd, int64_t n,
+                          const double *thresholds, int n_thresholds, tl3d_distance_stats *out);
+
+/* Queries of the two searches run bucketed by the target grid's cell, so that the lanes of a wave read the same few cells, and
+ * scatter their results back by original index (default).  cell_order = 0: in input order.  The results are the same bytes. */
+int tl3d_set_nearest_query_order(tl3d_ctx *ctx, int cell_order);
+
 /* measurement */
 int tl3d_set_profile(tl3d_ctx *ctx, int count_records, int time_kernels);
 /* Noise-robust registration: normal maps built after this call come from the depth averaged over a (2 radius + 1)^2 window

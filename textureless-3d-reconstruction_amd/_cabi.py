@@ -27,6 +27,7 @@ SYMBOLS = [
     "tl3d_accumulate_points", "tl3d_points_bounds", "tl3d_integrate", "tl3d_build_normals",
     "tl3d_download_normals", "tl3d_icp_p2plane", "tl3d_icp_enqueue", "tl3d_icp_collect", "tl3d_icp_batch_enqueue", "tl3d_icp_batch_collect", "tl3d_icp_evaluate_pairs", "tl3d_host_pack_bgr_rows", "tl3d_host_copy_rows", "tl3d_build_normals_many", "tl3d_fuse_frames", "tl3d_grid_reset", "tl3d_grid_device_ptr",
     "tl3d_grid_download", "tl3d_grid_upload", "tl3d_grid_add", "tl3d_grid_touched_bricks", "tl3d_grid_pack_bricks", "tl3d_grid_unpack_bricks", "tl3d_rccl_unique_id", "tl3d_rccl_init", "tl3d_allreduce_grid", "tl3d_extract", "tl3d_extract_mesh", "tl3d_extract_mesh_keyed", "tl3d_mesh_components", "tl3d_mesh_filter_components", "tl3d_mesh_simplify_clusters", "tl3d_mesh_simplify_quadric", "tl3d_mesh_smooth_taubin", "tl3d_mesh_vertex_normals", "tl3d_mesh_weld_keyed", "tl3d_raycast", "tl3d_track_evaluate", "tl3d_track_frame", "tl3d_statistical_outlier", "tl3d_knn_mean_distance",
+    "tl3d_nearest_points", "tl3d_nearest_triangles", "tl3d_distance_summary", "tl3d_set_nearest_query_order",
     "tl3d_set_profile", "tl3d_set_normal_smoothing", "tl3d_set_tsdf_pairing", "tl3d_get_stats", "tl3d_reset_stats", "tl3d_event_record", "tl3d_event_elapsed_ms",
 ]
 
@@ -71,6 +72,11 @@ class IcpEval(C.Structure):
 class MeshPart(C.Structure):
     _fields_ = [("xyz_hd", C.c_void_p), ("rgb_hd", C.c_void_p), ("key_hd", C.c_void_p), ("n_vert", C.c_int64),
                 ("tri_hd", C.c_void_p), ("n_tri", C.c_int64), ("core_lo", C.c_int64 * 3), ("core_hi", C.c_int64 * 3)]
+
+
+class DistanceStats(C.Structure):
+    _fields_ = [("n", C.c_int64), ("n_finite", C.c_int64), ("sum", C.c_double), ("sum_sq", C.c_double), ("max", C.c_double),
+                ("below", C.c_int64 * 8)]
 
 
 ICP_MAX_LEVELS = 4
@@ -232,6 +238,10 @@ def load():
         "tl3d_track_frame": [vp, i32, dbl, vp, vp, i32, C.POINTER(IcpParams), i32, C.POINTER(IcpResult)],
         "tl3d_statistical_outlier": [vp, vp, i64, i32, dbl, dbl, vp, C.POINTER(i64)],
         "tl3d_knn_mean_distance": [vp, vp, i64, i32, dbl, vp],
+        "tl3d_nearest_points": [vp, vp, i64, vp, i64, dbl, dbl, vp, vp],
+        "tl3d_nearest_triangles": [vp, vp, i64, vp, i64, vp, i64, dbl, dbl, vp, vp],
+        "tl3d_distance_summary": [vp, vp, i64, vp, i32, C.POINTER(DistanceStats)],
+        "tl3d_set_nearest_query_order": [vp, i32],
         "tl3d_set_profile": [vp, i32, i32],
         "tl3d_set_tsdf_pairing": [vp, i32],
         "tl3d_get_stats": [vp, C.POINTER(Stats)],

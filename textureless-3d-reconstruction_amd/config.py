@@ -95,6 +95,13 @@ class ReconstructionConfig:
     track_min_weight: int = 1           # a voxel takes part once this many frames saw it
     track_min_fitness: float = 0.5      # below it (or with status 2) a frame is lost: it keeps the chain-relative pose
     track_levels: Optional[tuple] = None   # ((iterations, stride, gate in metres), ...) coarse to fine; None: the chain's levels
+    # score the result against a reference scan: a PLY file whose vertices are the reference cloud.  After
+    # reconstruct() stats["compare"] holds metrics.compare_clouds(fused cloud, reference) -- Chamfer, precision / recall / F-score at
+    # the thresholds (metres) -- and, with extract_mesh, metrics.compare_cloud_to_mesh(reference, final mesh) under "mesh".
+    # compare_max_dist: points with no neighbour within it count as unmatched.  None: nothing changes.
+    compare_to: Optional[str] = None
+    compare_thresholds: tuple = (0.005, 0.01, 0.02)
+    compare_max_dist: Optional[float] = None
 
     @property
     def K(self) -> np.ndarray:

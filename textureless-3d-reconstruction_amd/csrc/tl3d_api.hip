@@ -414,6 +414,8 @@ static void release_grid(tl3d_ctx *ctx) {
     if (gs.mio_counts) (void)hipFree(gs.mio_counts);
     if (gs.mio_offsets) (void)hipFree(gs.mio_offsets);
     if (gs.mio_info) (void)hipFree(gs.mio_info);
+    if (gs.nn_slab) (void)hipFree(gs.nn_slab);
+    if (gs.nn_buf) (void)hipFree(gs.nn_buf);
     for (int h = 0; h < TSDF_SCRATCHES; ++h)
         if (gs.ev_upd[h]) (void)hipEventDestroy(gs.ev_upd[h]);      // (build_grid creates them anew)
     memset(&gs, 0, sizeof(gs));
@@ -2783,6 +2785,92 @@ static int mio_validate(tl3d_ctx *ctx, const uint32_t *dtri, int64_t n_tri, int6
     TL3D_HIP(hipStreamSynchronize(ctx->stream));
     REQUIRE(n_tri == 0 || (int64_t)h[0] < n_vert, TL3D_E_INVALID, "triangle index %llu out of range [0, %lld)", h[0], (long long)n_vert);
     if (word1) *word1 = h[1];
+    return TL3D_OK;
+}
+
+// ------------------------------------------------------------------------------------------- nearest neighbours, distance summary
+// what both searches check before any device work
+static int nn_check(tl3d_ctx *ctx, const float *query, int64_t n_query, const void *const *ins, const size_t *in_bytes, int n_ins,
+                    double *dist_out, int32_t *index_out) {
+    REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
+    REQUIRE(n_query >= 0 && (n_query == 0 || query), TL3D_E_INVALID, "bad query list");
+    const void *outs[2] = {dist_out, index_out};
+    const size_t out_b[2] = {(size_t)n_query * sizeof(double), (size_t)n_query * sizeof(int32_t)};
+    for (int o = 0; o < 2; ++o) {
+        REQUIRE(!ranges_overlap(outs[o], out_b[o], query, (size_t)n_query * 12), TL3D_E_INVALID, "an output aliases an input");
+        for (int i = 0; i < n_ins; ++i)
+            REQUIRE(!ranges_overlap(outs[o], out_b[o], ins[i], in_bytes[i]), TL3D_E_INVALID, "an output aliases an input");
+    }
+    REQUIRE(!ranges_overlap(dist_out, out_b[0], index_out, out_b[1]), TL3D_E_INVALID, "the outputs alias each other");
+    return TL3D_OK;
+}
+
+int tl3d_nearest_points(tl3d_ctx *ctx, const float *query, int64_t n_query, const float *target, int64_t n_target, double cell_size,
+                        double max_dist, double *dist_out, int32_t *index_out) {
+    REQUIRE(n_target >= 0 && (n_target == 0 || target), TL3D_E_INVALID, "bad target list");
+    REQUIRE(n_target < (1ll << 31), TL3D_E_INVALID, "n_target %lld: indices need fewer than 2^31 points", (long long)n_target);
+    const void *ins[1] = {target};
+    const size_t in_b[1] = {(size_t)n_target * 12};
+    int rc = nn_check(ctx, query, n_query, ins, in_b, 1, dist_out, index_out);
+    if (rc) return rc;
+    if (n_query == 0) return TL3D_OK;
+    TL3D_HIP(hipSetDevice(ctx->device));
+    Staging st(ctx);
+    const float *dq, *dt = nullptr;
+    double *dd = nullptr;
+    int32_t *di = nullptr;
+    rc = st.in(query, (size_t)n_query * 12, &dq);
+    if (!rc && n_target) rc = st.in(target, (size_t)n_target * 12, &dt);
+    if (!rc && dist_out) rc = st.out(dist_out, (size_t)n_query * sizeof(double), &dd);
+    if (!rc && index_out) rc = st.out(index_out, (size_t)n_query * sizeof(int32_t), &di);
+    if (rc) return rc;
+    return st.finish(nearest_points_run(ctx, dq, n_query, dt, n_target, cell_size, max_dist, dd, di), true);
+}
+
+int tl3d_nearest_triangles(tl3d_ctx *ctx, const float *query, int64_t n_query, const float *xyz, int64_t n_vert, const uint32_t *tri,
+                           int64_t n_tri, double cell_size, double max_dist, double *dist_out, int32_t *tri_out) {
+    REQUIRE(n_tri >= 0 && n_vert >= 0, TL3D_E_INVALID, "negative size (n_tri %lld, n_vert %lld)", (long long)n_tri, (long long)n_vert);
+    REQUIRE(n_vert < (1ll << 31) && n_tri < (1ll << 31), TL3D_E_INVALID, "n_vert %lld, n_tri %lld: indices need fewer than 2^31 of each",
+            (long long)n_vert, (long long)n_tri);
+    REQUIRE((n_tri == 0 || tri) && (n_vert == 0 || xyz), TL3D_E_INVALID, "null mesh array");
+    const void *ins[2] = {xyz, tri};
+    const size_t in_b[2] = {(size_t)n_vert * 12, (size_t)n_tri * 12};
+    int rc = nn_check(ctx, query, n_query, ins, in_b, 2, dist_out, tri_out);
+    if (rc) return rc;
+    if (n_query == 0) return TL3D_OK;
+    TL3D_HIP(hipSetDevice(ctx->device));
+    Staging st(ctx);
+    const float *dq, *dx = nullptr;
+    const uint32_t *dt = nullptr;
+    double *dd = nullptr;
+    int32_t *di = nullptr;
+    rc = st.in(query, (size_t)n_query * 12, &dq);
+    if (!rc && n_vert) rc = st.in(xyz, (size_t)n_vert * 12, &dx);
+    if (!rc && n_tri) rc = st.in(tri, (size_t)n_tri * 12, &dt);
+    if (!rc && dist_out) rc = st.out(dist_out, (size_t)n_query * sizeof(double), &dd);
+    if (!rc && tri_out) rc = st.out(tri_out, (size_t)n_query * sizeof(int32_t), &di);
+    if (rc) return rc;
+    return st.finish(nearest_triangles_run(ctx, dq, n_query, dx, n_vert, dt, n_tri, cell_size, max_dist, dd, di), true);
+}
+
+int tl3d_distance_summary(tl3d_ctx *ctx, const double *dist, int64_t n, const double *thresholds, int n_thresholds, tl3d_distance_stats *out) {
+    REQUIRE(ctx && out, TL3D_E_INVALID, "null argument");
+    REQUIRE(n >= 0 && (n == 0 || dist), TL3D_E_INVALID, "bad distance list");
+    REQUIRE(n_thresholds >= 0 && n_thresholds <= 8 && (n_thresholds == 0 || thresholds), TL3D_E_INVALID, "n_thresholds %d outside [0, 8]", n_thresholds);
+    memset(out, 0, sizeof(*out));
+    out->n = n;
+    if (n == 0) return TL3D_OK;
+    TL3D_HIP(hipSetDevice(ctx->device));
+    Staging st(ctx);
+    const double *dd;
+    int rc = st.in(dist, (size_t)n * sizeof(double), &dd);
+    if (rc) return rc;
+    return st.finish(distance_summary_run(ctx, dd, n, thresholds, n_thresholds, out), true);
+}
+
+int tl3d_set_nearest_query_order(tl3d_ctx *ctx, int cell_order) {
+    REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
+    ctx->nn_input_order = cell_order == 0;
     return TL3D_OK;
 }
 

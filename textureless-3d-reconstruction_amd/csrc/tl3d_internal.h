@@ -299,6 +299,11 @@ struct tl3d_grid_state {
     unsigned long long *mio_offsets;
     size_t mio_chunks;                      // capacity of both, in entries
     unsigned long long *mio_info;           // [8]
+    // tl3d_nearest_points / tl3d_nearest_triangles / tl3d_distance_summary: the block partials of their
+    // reductions (fixed size) and ONE buffer the calls carve their cell tables, sorted target and query order from.
+    // Grid-independent like the cc_ scratch, and here for the same reason.
+    void *nn_slab, *nn_buf;
+    size_t nn_bytes;                        // capacity of nn_buf
     // tl3d_set_block_core: the grid is one block of a lattice of lat[] voxels and emits only what its core (grid.clo / chi) owns
     bool has_core;
     long long lat[3];
@@ -405,6 +410,7 @@ struct tl3d_ctx : tl3d_grid_state {
         double *slab;            // [track_members][TRACK_SUMS]
     } track;
     float *bounds_slab;
+    bool nn_input_order;         // tl3d_set_nearest_query_order(ctx, 0): nearest-neighbour queries run in input order, not bucketed by cell
     // stats / profiling
     tl3d_stats stats;
     bool count_records, time_kernels;
@@ -640,6 +646,13 @@ int launch_ms_write(hipStream_t s, double cell, const double o[3], const float *
                     unsigned long long *info = nullptr);
 int sor_mean_distance(tl3d_ctx *ctx, const float *xyz_dev, long long n, int k, double cell, double *mean_dev);
 int sor_run(tl3d_ctx *ctx, const float *xyz_dev, long long n, int k, double std_ratio, double cell, uint8_t *keep_dev, long long *kept);
+
+// nearest neighbours from one set to another and the distance summary (kernels_nearest.hip); device pointers, outputs may be null
+int nearest_points_run(tl3d_ctx *ctx, const float *query, long long nq, const float *target, long long nt, double cell, double max_dist,
+                       double *dist, int *index);
+int nearest_triangles_run(tl3d_ctx *ctx, const float *query, long long nq, const float *xyz, long long nv, const unsigned *tri, long long n_tri,
+                          double cell, double max_dist, double *dist, int *index);
+int distance_summary_run(tl3d_ctx *ctx, const double *dist, long long n, const double *thresholds, int nthr, tl3d_distance_stats *out);
 
 // mesh smoothing and vertex normals (kernels_meshsmooth.hip)
 int launch_msm_validate(hipStream_t s, const float *xyz, long long n_vert, unsigned long long *info);

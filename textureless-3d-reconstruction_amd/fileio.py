@@ -602,3 +602,56 @@ def save_reconstruction(points, colors, output_path, ascii: bool = False) -> boo
         write_ply_binary(filepath, points, colors)
     print(f"Saved to {filepath}")
     return True
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
+              "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def read_ply_points(path) -> np.ndarray:
+    """The vertex positions of a PLY file as float32 [n, 3]: `format ascii 1.0` and `binary_little_endian 1.0`, x / y / z of type
+    float or double (a double is rounded to float32), every other vertex property and every element behind the vertices (faces)
+    skipped.  Reads what write_ply_ascii, write_ply_binary and write_ply_mesh write and what the reference writes (D2R:673-703).
+    ValueError for anything else (big-endian files, a list property inside the vertex element, no x / y / z)."""
+    with open(str(path), "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header")
+    if not data.startswith(b"ply") or end < 0:
+        raise ValueError(f"{path}: not a PLY file")
+    body = data.find(b"\n", end) + 1
+    fmt, n_vert, props, element, first = None, None, [], None, None
+    for line in data[:end].decode("ascii", "replace").splitlines():
+        w = line.split()
+        if not w:
+            continue
+        if w[0] == "format":
+            fmt = w[1]
+        elif w[0] == "element":
+            element = w[1]
+            if first is None:
+                first = element
+            if element == "vertex":
+                n_vert = int(w[2])
+        elif w[0] == "property" and element == "vertex":
+            if w[1] == "list" or w[1] not in _PLY_TYPES:
+                raise ValueError(f"{path}: vertex property `{line.strip()}` is not a scalar")
+            props.append((w[2], _PLY_TYPES[w[1]]))
+    names = [p[0] for p in props]
+    if n_vert is None or first != "vertex" or not all(a in names for a in "xyz"):
+        raise ValueError(f"{path}: the first element must be `vertex` with x, y, z")
+    if fmt == "binary_little_endian":
+        rec = np.dtype([(nm, "<" + t) for nm, t in props])
+        if len(data) - body < n_vert * rec.itemsize:
+            raise ValueError(f"{path}: truncated vertex data")
+        v = np.frombuffer(data, rec, count=n_vert, offset=body)
+        return np.stack([v["x"], v["y"], v["z"]], axis=1).astype(np.float32) if n_vert else np.zeros((0, 3), np.float32)
+    if fmt == "ascii":
+        if n_vert == 0:
+            return np.zeros((0, 3), np.float32)
+        rows = data[body:].split(b"\n", n_vert)[:n_vert]
+        tab = np.array([r.split() for r in rows])
+        if tab.ndim != 2 or tab.shape != (n_vert, len(props)):
+            raise ValueError(f"{path}: malformed vertex rows")
+        cols = [names.index(a) for a in "xyz"]
+        return tab[:, cols].astype(np.float64).astype(np.float32)
+    raise ValueError(f"{path}: PLY format `{fmt}` is not supported")

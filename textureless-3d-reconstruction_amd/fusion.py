@@ -903,6 +903,76 @@ class FusionContext:
         abi.check(self._lib.tl3d_knn_mean_distance(self._h, abi.ptr(xyz), len(xyz), int(nb_neighbors), cell, abi.ptr(mean)))
         return mean
 
+    # ---- distances between sets (none of it needs a grid) -----------
+    @staticmethod
+    def _points(a):
+        """A point list as the library wants it: numpy -> float32 [n,3] on the host, a torch tensor stays where it is."""
+        if hasattr(a, "data_ptr"):
+            import torch
+            return a.to(dtype=torch.float32).reshape(-1, 3).contiguous()
+        return np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 3)
+
+    @staticmethod
+    def _nearest_outputs(query):
+        if hasattr(query, "data_ptr"):
+            import torch
+            return (torch.empty(len(query), dtype=torch.float64, device=query.device),
+                    torch.empty(len(query), dtype=torch.int32, device=query.device))
+        return np.empty(len(query), np.float64), np.empty(len(query), np.int32)
+
+    def nearest_points(self, query, target, max_dist=None, cell_size=None):
+        """(dist float64 [n], index int32 [n]): for every query point the exact fp64 distance to its nearest target point and that
+        point's index (the smallest index on an exact tie).  max_dist: a query with nothing within it gets +inf / -1 (so does every
+        query of an empty target).  cell_size sets the search grid only (default: from the target's box and count); the result does
+        not depend on it.  numpy in, numpy out; torch device tensors in, device tensors out."""
+        query, target = self._points(query), self._points(target)
+        dist, index = self._nearest_outputs(query)
+
+        def p(a):
+            return abi.ptr(a) if len(a) else None
+        abi.check(self._lib.tl3d_nearest_points(self._h, p(query), len(query), p(target), len(target),
+                                                float(cell_size) if cell_size is not None else 0.0,
+                                                float(max_dist) if max_dist is not None else 0.0, p(dist), p(index)))
+        return dist, index
+
+    def nearest_triangles(self, query, xyz, tris, max_dist=None, cell_size=None):
+        """(dist float64 [n], tri int32 [n]): for every query point the exact fp64 distance to the nearest point of the closed
+        triangles of the mesh (xyz, tris) and the triangle it lies on (the smallest index on an exact tie); degenerate triangles
+        measure as the segments or points they are.  max_dist, cell_size (default: the mean triangle box) and array kinds as
+        nearest_points."""
+        query = self._points(query)
+        xyz, _, tris, _ = self._mesh_arrays(xyz, None, tris)
+        dist, index = self._nearest_outputs(query)
+
+        def p(a):
+            return abi.ptr(a) if len(a) else None
+        abi.check(self._lib.tl3d_nearest_triangles(self._h, p(query), len(query), p(xyz), len(xyz), p(tris), len(tris),
+                                                   float(cell_size) if cell_size is not None else 0.0,
+                                                   float(max_dist) if max_dist is not None else 0.0, p(dist), p(index)))
+        return dist, index
+
+    def distance_summary(self, dist, thresholds=()):
+        """Summary of a float64 distance array (numpy or device tensor), reduced in a fixed shape on the GPU (the same bytes in every
+        run): n, within (the finite entries), sum, sum_sq and max over those, mean and rms (nan without a finite entry), and below:
+        per threshold (at most 8) the number of entries <= it."""
+        if hasattr(dist, "data_ptr"):
+            import torch
+            dist = dist.to(dtype=torch.float64).reshape(-1).contiguous()
+        else:
+            dist = np.ascontiguousarray(dist, dtype=np.float64).reshape(-1)
+        thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+        out = abi.DistanceStats()
+        abi.check(self._lib.tl3d_distance_summary(self._h, abi.ptr(dist) if len(dist) else None, len(dist),
+                                                  abi.ptr(thr) if len(thr) else None, len(thr), C.byref(out)))
+        m = out.n_finite
+        return dict(n=out.n, within=m, sum=out.sum, sum_sq=out.sum_sq, max=out.max,
+                    mean=out.sum / m if m else float("nan"), rms=(out.sum_sq / m) ** 0.5 if m else float("nan"),
+                    below=[int(out.below[j]) for j in range(len(thr))])
+
+    def set_nearest_query_order(self, cell_order: bool):
+        """nearest_points / nearest_triangles run their queries bucketed by cell (default) or, off, in input order: same bytes."""
+        abi.check(self._lib.tl3d_set_nearest_query_order(self._h, 1 if cell_order else 0))
+
     # ---- measurement -----------------------------------------------------------------------
     def set_profile(self, count_records=False, time_kernels=False):
         abi.check(self._lib.tl3d_set_profile(self._h, int(count_records), int(time_kernels)))

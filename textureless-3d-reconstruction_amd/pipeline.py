@@ -555,6 +555,21 @@ class DepthToReconstructionPipeline:
             ctx.close()
         return xyz.astype(np.float64), rgb, self.camera_poses
 
+    def _compare(self, ctx: FusionContext, xyz):
+        """config.compare_to: the fused cloud against the reference scan's points (metrics.compare_clouds; a = the fused cloud, so
+        precision is its accuracy and recall its completeness), and under "mesh" the reference against the final mesh
+        (metrics.compare_cloud_to_mesh) when there is one.  Reads the results only: nothing the run computes changes."""
+        from . import metrics
+        cfg = self.config
+        ref = fileio.read_ply_points(cfg.compare_to)
+        thr = tuple(float(t) for t in (cfg.compare_thresholds or ()))
+        out = metrics.compare_clouds(ctx, np.ascontiguousarray(xyz, dtype=np.float32), ref, thresholds=thr, max_dist=cfg.compare_max_dist)
+        out["reference"], out["reference_points"] = str(cfg.compare_to), len(ref)
+        if self.mesh is not None:
+            out["mesh"] = metrics.compare_cloud_to_mesh(ctx, ref, self.mesh[0], self.mesh[2], thresholds=thr, max_dist=cfg.compare_max_dist)
+        print("  " + metrics.format_line(out))
+        return out
+
     def _extract_points(self, ctx: FusionContext):
         cfg = self.config
         return ctx.extract(abi.EXTRACT_CENTROID, min_count=1, min_weight=cfg.tsdf_min_weight, max_abs_tsdf=cfg.tsdf_max_abs)
@@ -693,6 +708,10 @@ class DepthToReconstructionPipeline:
             t0 = clock()
             self._render_views(ctx)
             stage["render"] = clock() - t0
+        if cfg.compare_to:
+            t0 = clock()
+            self.stats["compare"] = self._compare(ctx, xyz)
+            stage["compare"] = clock() - t0
         self.timings = {name + "_s": round(t1 - t0, 4) for (name, t1), (_, t0) in zip(marks[1:], marks[:-1])}
         self.timings.update({k + "_s": round(v, 4) for k, v in stage.items()})
         if not one:
@@ -891,6 +910,10 @@ class DepthToReconstructionPipeline:
                         t0 = time.perf_counter()
                         self.mesh_normals = ctx.mesh_normals(self.mesh[0], self.mesh[2])
                         self.timings["mesh_normals_s"] = round(time.perf_counter() - t0, 4)
+                if cfg.compare_to:
+                    t0 = time.perf_counter()
+                    self.stats["compare"] = self._compare(ctx, xyz)
+                    self.timings["compare_s"] = round(time.perf_counter() - t0, 4)
                 say(f"\nFinal reconstruction: {len(xyz)} points, {len(self.camera_poses)} cameras")
                 xyz = xyz.astype(np.float64)
         finally:
