@@ -239,7 +239,10 @@ int tl3d_accumulate_centroid(tl3d_ctx *ctx, int slot, const double R[9], const d
                              uint32_t flags, int subsample, double min_depth, double max_depth);
 /* same, from an explicit point list (merge_pointclouds' call shape, D2R:386-420) */
 int tl3d_accumulate_points(tl3d_ctx *ctx, const float *xyz_hd, const uint8_t *rgb_hd, int64_t n);
-/* min/max bound of a point list (Open3D's voxel origin = min_bound - voxel/2) */
+/* min/max bound of a point list (Open3D's voxel origin = min_bound - voxel/2).  Per axis, fminf / fmaxf over the f32 coordinates:
+ * a NaN coordinate is ignored (the bounds are those of the axis' other values; numpy's p.min(0) would give NaN), an axis that holds
+ * nothing but NaN keeps the empty extent out_min = +inf, out_max = -inf; infinities count as values; denormals are kept as they
+ * are; the sign of a bound that is zero is not specified (tests/test_gpu_centroid_accumulate.py pins all of this). */
 int tl3d_points_bounds(tl3d_ctx *ctx, const float *xyz_hd, int64_t n, double out_min[3], double out_max[3]);
 
 /* a11: TSDF integration of one frame (no reference code; convention in DESIGN.md).
