@@ -1,6 +1,6 @@
 // kernels_compact.hip -- the scan between the count pass and the write pass of the order-preserving compaction (compact.h): the
 // per-chunk counts of one launch -> 64-bit offsets and the grand total.  One block: its callers (point and mesh extraction, the
-// two mesh clean-up calls, the outlier filter) have at most a few thousand chunks.
+// two mesh clean-up calls) have at most a few thousand chunks, the cell index (kernels_cellgrid.hip) at most 2^17 chunk sums.
 #include "tl3d_internal.h"
 
 namespace tl3d {

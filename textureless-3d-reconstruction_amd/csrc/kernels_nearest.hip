@@ -4,8 +4,8 @@
 // the reference never scores a cloud; the definitions are those of Open3D's compute_point_cloud_distance and of the Chamfer / F-score
 // literature.
 //
-// The target is counting-sorted into a uniform cell grid over its own box (count, scan, fill, as the outlier filter does; the
-// original index rides beside each sorted point; a triangle goes into every cell its box overlaps).  A query scans the cells around
+// The target is counting-sorted into the uniform cell index of cellgrid.h over its own box (the original index rides beside each
+// sorted point; a triangle goes into every cell its box overlaps: nn_tri_bin_kernel).  A query scans the cells around
 // its CLAMPED cell in shells of growing Chebyshev radius.  Two things differ from the filter's k-NN:
 //   * the winner is the minimum over the PAIR (d2, index), so neither the fill order inside a cell (atomics) nor the order in which
 //     cells are met shows in the result, and an exact tie goes to the smaller index;
@@ -15,35 +15,22 @@
 //     plane) and, being in the grid, at least box_b and box_c away along the other two (query's distance to the grid's extent on that
 //     axis; 0 inside).  bound2 = min over open faces of gap_a^2 + box_b^2 + box_c^2; the search ends when no face is open, when
 //     best2 < bound2 (strictly: a tie further out may have the smaller index), or when bound2 > max_dist^2.
-// All of it in cell units u = (x - origin) * inv_cell, evaluated by ONE expression (nn_u) for targets, triangle corners and queries:
-// that expression is monotone in x, so "binned beyond the face" implies u beyond the face exactly; turning cell units back into
+// All of it in cell units u = (x - origin) * inv_cell, evaluated by ONE expression (cell_u, cellgrid.h) for targets, triangle corners
+// and queries: it is monotone in x, so "binned beyond the face" implies u beyond the face exactly; turning cell units back into
 // metres costs at most 4 roundings (2^-53 each, relative to the larger |u|), which NN_SLACK = 1e-15 (4.5 of them) pays for: every
 // bound is shrunk by it, which can only make a search look one shell further.
 #include <math.h>
 
 #include <vector>
 
-#include "tl3d_internal.h"
+#include "cellgrid.h"
 
 namespace tl3d {
 
-struct NnGrid {
-    double ox, oy, oz, cell, inv_cell;
-    int nx, ny, nz;
-};
-
 constexpr double NN_SLACK = 1e-15;
 constexpr int NN_RED = 1024;            // blocks of the reductions (fixed: the partial sums do not depend on the device)
+static_assert((size_t)NN_RED * 128 <= CELL_SLAB_BYTES, "the block partials of every reduction here fit the slab");
 constexpr int NN_LEVELS = 16;           // candidate cell sizes one triangle-pair count pass looks at (cell * 2^j)
-
-__device__ __forceinline__ double nn_u(double x, double o, double inv_cell) { return (x - o) * inv_cell; }
-__device__ __forceinline__ int nn_clampi(double u, int n) { return (int)fmin(fmax(floor(u), 0.0), (double)(n - 1)); }
-__device__ __forceinline__ long long nn_cell_of(const NnGrid &g, const float *__restrict__ p) {
-    const int cx = nn_clampi(nn_u((double)p[0], g.ox, g.inv_cell), g.nx);
-    const int cy = nn_clampi(nn_u((double)p[1], g.oy, g.inv_cell), g.ny);
-    const int cz = nn_clampi(nn_u((double)p[2], g.oz, g.inv_cell), g.nz);
-    return ((long long)cz * g.ny + cy) * g.nx + cx;
-}
 
 // ---- validation and bounds -----------------------------------------------------------------------------------------------------
 // per block: min[3], max[3] over the finite points (f32), and the number of points with a non-finite coordinate (its bits in [6])
@@ -114,87 +101,21 @@ __global__ __launch_bounds__(256) void nn_tri_stats_kernel(const float *__restri
     }
 }
 
-// ---- counting sort -------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void nn_count_kernel(NnGrid g, const float *__restrict__ xyz, long long n, unsigned *__restrict__ cnt) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    atomicAdd(cnt + nn_cell_of(g, xyz + 3 * i), 1u);
-}
-
-__global__ __launch_bounds__(256) void nn_chunk_sum_kernel(const unsigned *__restrict__ v, long long n, unsigned *__restrict__ sums) {
-    __shared__ unsigned sm[4];
-    const long long base = (long long)blockIdx.x * 1024;
-    unsigned s = 0;
-    for (int k = 0; k < 4; ++k) {
-        const long long i = base + k * 256 + threadIdx.x;
-        if (i < n) s += v[i];
-    }
-    for (int d = 32; d > 0; d >>= 1) s += __shfl_down(s, d);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) sums[blockIdx.x] = sm[0] + sm[1] + sm[2] + sm[3];
-}
-
-// exclusive scan inside each 1024-element chunk, offset by the scanned chunk sums; start[n] = the total
-__global__ __launch_bounds__(256) void nn_chunk_scan_kernel(const unsigned *__restrict__ v, long long n,
-                                                            const unsigned long long *__restrict__ chunk_off, int nchunks,
-                                                            unsigned *__restrict__ start) {
-    __shared__ unsigned sm[4];
-    const long long i0 = (long long)blockIdx.x * 1024 + (long long)threadIdx.x * 4;
-    unsigned a[4], s = 0;
-    for (int k = 0; k < 4; ++k) { a[k] = (i0 + k < n) ? v[i0 + k] : 0u; s += a[k]; }
-    unsigned inc = s;
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned t = __shfl_up(inc, d);
-        if (lane >= d) inc += t;
-    }
-    if (lane == 63) sm[wid] = inc;
-    __syncthreads();
-    unsigned run = (unsigned)chunk_off[blockIdx.x] + inc - s;
-    for (int w = 0; w < wid; ++w) run += sm[w];
-    for (int k = 0; k < 4; ++k) {
-        if (i0 + k < n) start[i0 + k] = run;
-        run += a[k];
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) start[n] = (unsigned)chunk_off[nchunks];
-}
-
-// cnt holds the cell counts and is counted DOWN to zero: the slot order inside a cell is whatever the atomics give
-__global__ __launch_bounds__(256) void nn_fill_points_kernel(NnGrid g, const float *__restrict__ xyz, long long n,
-                                                             const unsigned *__restrict__ start, unsigned *__restrict__ cnt,
-                                                             float4 *__restrict__ sorted) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const long long c = nn_cell_of(g, xyz + 3 * i);
-    const unsigned pos = start[c] + atomicSub(cnt + c, 1u) - 1u;
-    sorted[pos] = make_float4(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], __int_as_float((int)i));
-}
-
-__global__ __launch_bounds__(256) void nn_fill_order_kernel(NnGrid g, const float *__restrict__ xyz, long long n,
-                                                            const unsigned *__restrict__ start, unsigned *__restrict__ cnt,
-                                                            unsigned *__restrict__ order) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const long long c = nn_cell_of(g, xyz + 3 * i);
-    order[start[c] + atomicSub(cnt + c, 1u) - 1u] = (unsigned)i;
-}
-
 // ---- triangles into cells ------------------------------------------------------------------------------------------------------
 struct NnBox { int lo[3], hi[3]; };
-__device__ __forceinline__ NnBox nn_tri_box(const NnGrid &g, const float *__restrict__ xyz, const unsigned *__restrict__ tri, long long t) {
+__device__ __forceinline__ NnBox nn_tri_box(const CellGrid &g, const float *__restrict__ xyz, const unsigned *__restrict__ tri, long long t) {
     const float *a = xyz + 3 * (size_t)tri[3 * t], *b = xyz + 3 * (size_t)tri[3 * t + 1], *c = xyz + 3 * (size_t)tri[3 * t + 2];
     const double o[3] = {g.ox, g.oy, g.oz};
     const int n[3] = {g.nx, g.ny, g.nz};
     NnBox bx;
     for (int k = 0; k < 3; ++k) {
-        bx.lo[k] = nn_clampi(nn_u((double)fminf(a[k], fminf(b[k], c[k])), o[k], g.inv_cell), n[k]);
-        bx.hi[k] = nn_clampi(nn_u((double)fmaxf(a[k], fmaxf(b[k], c[k])), o[k], g.inv_cell), n[k]);
+        bx.lo[k] = cell_clampi(cell_u((double)fminf(a[k], fminf(b[k], c[k])), o[k], g.inv_cell), n[k]);
+        bx.hi[k] = cell_clampi(cell_u((double)fmaxf(a[k], fmaxf(b[k], c[k])), o[k], g.inv_cell), n[k]);
     }
     return bx;
 }
 
-struct NnLevels { NnGrid g[NN_LEVELS]; };
+struct NnLevels { CellGrid g[NN_LEVELS]; };
 // total[j] = (triangle, cell) pairs of the grid g[j] (integer adds: the same in every run)
 __global__ __launch_bounds__(256) void nn_tri_pairs_kernel(NnLevels lv, const float *__restrict__ xyz, const unsigned *__restrict__ tri,
                                                            long long n_tri, unsigned long long *__restrict__ total) {
@@ -210,8 +131,8 @@ __global__ __launch_bounds__(256) void nn_tri_pairs_kernel(NnLevels lv, const fl
     }
 }
 
-// fill == nullptr: count the triangle into every cell of its box; else write its index there (cnt counted down, as the points)
-__global__ __launch_bounds__(256) void nn_tri_bin_kernel(NnGrid g, const float *__restrict__ xyz, const unsigned *__restrict__ tri, long long n_tri,
+// fill == nullptr: count the triangle into every cell of its box; else write its index there (cnt counted down, as cell_fill_kernel does)
+__global__ __launch_bounds__(256) void nn_tri_bin_kernel(CellGrid g, const float *__restrict__ xyz, const unsigned *__restrict__ tri, long long n_tri,
                                                          const unsigned *__restrict__ start, unsigned *__restrict__ cnt, unsigned *__restrict__ fill) {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= n_tri) return;
@@ -310,7 +231,7 @@ __device__ __forceinline__ double nn_lower(double v, double um, double cell) {
 
 // order == nullptr: thread i serves query i; else query order[i] (queries bucketed by cell: a wave's lanes walk the same cells)
 template <class Eval>
-__global__ __launch_bounds__(256) void nn_search_kernel(NnGrid g, const float *__restrict__ query, long long nq, const unsigned *__restrict__ order,
+__global__ __launch_bounds__(256) void nn_search_kernel(CellGrid g, const float *__restrict__ query, long long nq, const unsigned *__restrict__ order,
                                                         const unsigned *__restrict__ start, Eval eval, double max_dist,
                                                         double *__restrict__ dist_out, int *__restrict__ index_out) {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -318,12 +239,12 @@ __global__ __launch_bounds__(256) void nn_search_kernel(NnGrid g, const float *_
     const long long qi = order ? (long long)order[t] : t;
     const double p[3] = {(double)query[3 * qi], (double)query[3 * qi + 1], (double)query[3 * qi + 2]};
     const int n[3] = {g.nx, g.ny, g.nz};
-    const double u[3] = {nn_u(p[0], g.ox, g.inv_cell), nn_u(p[1], g.oy, g.inv_cell), nn_u(p[2], g.oz, g.inv_cell)};
+    const double u[3] = {cell_u(p[0], g.ox, g.inv_cell), cell_u(p[1], g.oy, g.inv_cell), cell_u(p[2], g.oz, g.inv_cell)};
     int c[3];
     double box2[3];                                        // squared distance to the grid's extent, per axis (a lower bound)
     const double nmax = (double)max(g.nx, max(g.ny, g.nz)) + 1.0;
     for (int a = 0; a < 3; ++a) {
-        c[a] = nn_clampi(u[a], n[a]);
+        c[a] = cell_clampi(u[a], n[a]);
         const double b = nn_lower(fmax(0.0, fmax(-u[a], u[a] - (double)n[a])), nmax + fabs(u[a]), g.cell);
         box2[a] = b * b;
     }
@@ -423,61 +344,7 @@ __global__ __launch_bounds__(256) void nn_summary_kernel(const double *__restric
         if (e__ != hipSuccess) return set_err(TL3D_E_HIP, "%s failed: %s", #x, hipGetErrorString(e__)); \
     } while (0)
 
-// the call's scratch: one buffer of the context, grown on demand (release_grid frees it), carved at 256-B steps
-static int nn_reserve(tl3d_ctx *ctx, size_t bytes) {
-    if (bytes <= ctx->nn_bytes) return TL3D_OK;
-    if (ctx->nn_buf) (void)hipFree(ctx->nn_buf);
-    ctx->nn_buf = nullptr;
-    ctx->nn_bytes = 0;
-    if (hipMalloc(&ctx->nn_buf, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        ctx->nn_buf = nullptr;
-        return set_err(TL3D_E_NOMEM, "nearest-neighbour scratch alloc (%zu B) failed", bytes);
-    }
-    ctx->nn_bytes = bytes;
-    return TL3D_OK;
-}
-struct NnCarve {
-    size_t off = 0;
-    template <class T> size_t take(size_t n) {
-        const size_t at = off;
-        off += (n * sizeof(T) + 255) & ~(size_t)255;
-        return at;
-    }
-};
-
-static int nn_slab(tl3d_ctx *ctx) {
-    if (ctx->nn_slab) return TL3D_OK;
-    if (hipMalloc(&ctx->nn_slab, (size_t)NN_RED * 128) != hipSuccess) {
-        (void)hipGetLastError();
-        ctx->nn_slab = nullptr;
-        return set_err(TL3D_E_NOMEM, "nearest-neighbour slab alloc failed");
-    }
-    return TL3D_OK;
-}
-
 static unsigned nn_red_blocks(long long n) { return (unsigned)std::max(1ll, std::min((long long)NN_RED, (n + 255) / 256)); }
-
-// the grid of `cell` over [mn, mx]; false when it has more than 2^27 cells
-static bool nn_grid(const double mn[3], const double mx[3], double cell, NnGrid *g) {
-    g->cell = cell;
-    g->inv_cell = 1.0 / cell;
-    g->ox = mn[0]; g->oy = mn[1]; g->oz = mn[2];
-    const double ex = floor((mx[0] - mn[0]) / cell) + 1, ey = floor((mx[1] - mn[1]) / cell) + 1, ez = floor((mx[2] - mn[2]) / cell) + 1;
-    if (!(ex * ey * ez <= 134217728.0)) return false;
-    g->nx = (int)ex; g->ny = (int)ey; g->nz = (int)ez;
-    return true;
-}
-
-static int nn_scan(hipStream_t s, const unsigned *cnt, long long ncell, unsigned *chunk_sums, unsigned long long *chunk_off, unsigned *start) {
-    const int nchunks = (int)((ncell + 1023) / 1024);
-    hipLaunchKernelGGL(nn_chunk_sum_kernel, dim3(nchunks), dim3(256), 0, s, cnt, ncell, chunk_sums);
-    const int rc = launch_scan(s, chunk_sums, chunk_off, nchunks, chunk_off + nchunks);
-    if (rc) return rc;
-    hipLaunchKernelGGL(nn_chunk_scan_kernel, dim3(nchunks), dim3(256), 0, s, cnt, ncell, chunk_off, nchunks, start);
-    NN_HIP(hipGetLastError());
-    return TL3D_OK;
-}
 
 // bounds of a point list and the number of its non-finite points: one launch; the caller reads the slab
 static void nn_bounds_launch(hipStream_t s, const float *xyz, long long n, float *slab) {
@@ -511,23 +378,43 @@ static double nn_default_cell_points(const double mn[3], const double mx[3], lon
     return (c > 0.0 && isfinite(c)) ? c : 1.0;
 }
 
-// the queries bucketed into the target's grid (unless the context runs them in input order), then the search; cnt: all zero
-template <class Eval>
-static int nn_search(tl3d_ctx *ctx, const NnGrid &g, const float *query, long long nq, const unsigned *start, unsigned *cnt, unsigned *q_start,
-                     unsigned *chunk_sums, unsigned long long *chunk_off, unsigned *order, const Eval &eval, double max_dist, double *dist,
-                     int *index) {
+// A search's scratch, carved from the context's buffer: the cell tables of the target and of the queries (one cnt serves both, see
+// cellgrid.h), the scan's chunk sums and offsets, the target's payload behind the cells (P: float4 points, or triangle indices)
+// and the query order.
+template <class P> struct NnScratch {
+    unsigned *cnt, *t_start, *q_start, *chunk_sums;
+    unsigned long long *chunk_off;
+    P *payload;
+    unsigned *order;
+};
+template <class P> static int nn_scratch(tl3d_ctx *ctx, long long ncell, size_t n_payload, long long nq, NnScratch<P> *sc) {
+    const size_t nchunks = cell_chunks(ncell);
+    const size_t bytes[7] = {(size_t)ncell * sizeof(unsigned), (size_t)(ncell + 1) * sizeof(unsigned), (size_t)(ncell + 1) * sizeof(unsigned),
+                             nchunks * sizeof(unsigned), (nchunks + 1) * sizeof(unsigned long long), n_payload * sizeof(P),
+                             (size_t)nq * sizeof(unsigned)};
+    void *p[7];
+    const int rc = cell_carve(ctx, bytes, 7, p);
+    if (rc) return rc;
+    *sc = {(unsigned *)p[0], (unsigned *)p[1], (unsigned *)p[2], (unsigned *)p[3], (unsigned long long *)p[4], (P *)p[5], (unsigned *)p[6]};
+    return TL3D_OK;
+}
+
+// the queries bucketed into the target's grid (unless the context runs them in input order), then the search; sc.cnt: all zero
+template <class P, class Eval>
+static int nn_search(tl3d_ctx *ctx, const CellGrid &g, const float *query, long long nq, const NnScratch<P> &sc, const Eval &eval, double max_dist,
+                     double *dist, int *index) {
     hipStream_t s = ctx->stream;
     const unsigned nb = (unsigned)((nq + 255) / 256);
     const long long ncell = (long long)g.nx * g.ny * g.nz;
     const unsigned *ord = nullptr;
     if (!ctx->nn_input_order) {            // (the target's fill counted cnt down to zero again)
-        hipLaunchKernelGGL(nn_count_kernel, dim3(nb), dim3(256), 0, s, g, query, nq, cnt);
-        const int rc = nn_scan(s, cnt, ncell, chunk_sums, chunk_off, q_start);
+        launch_cell_count(s, g, query, nq, sc.cnt);
+        const int rc = launch_cell_scan(s, sc.cnt, ncell, sc.chunk_sums, sc.chunk_off, sc.q_start);
         if (rc) return rc;
-        hipLaunchKernelGGL(nn_fill_order_kernel, dim3(nb), dim3(256), 0, s, g, query, nq, q_start, cnt, order);
-        ord = order;
+        launch_cell_fill(s, g, query, nq, sc.q_start, sc.cnt, EmitIndex{sc.order});
+        ord = sc.order;
     }
-    hipLaunchKernelGGL(nn_search_kernel<Eval>, dim3(nb), dim3(256), 0, s, g, query, nq, ord, start, eval, max_dist, dist, index);
+    hipLaunchKernelGGL(nn_search_kernel<Eval>, dim3(nb), dim3(256), 0, s, g, query, nq, ord, sc.t_start, eval, max_dist, dist, index);
     NN_HIP(hipGetLastError());
     return TL3D_OK;
 }
@@ -542,9 +429,9 @@ static int nn_fill_none(tl3d_ctx *ctx, long long nq, double *dist, int *index) {
 int nearest_points_run(tl3d_ctx *ctx, const float *query, long long nq, const float *target, long long nt, double cell, double max_dist,
                        double *dist, int *index) {
     hipStream_t s = ctx->stream;
-    int rc = nn_slab(ctx);
+    int rc = cell_slab(ctx);
     if (rc) return rc;
-    float *slab = (float *)ctx->nn_slab;
+    float *slab = (float *)ctx->cg_slab;
     std::vector<float> h((size_t)NN_RED * 16);
     nn_bounds_launch(s, query, nq, slab);
     if (nt) nn_bounds_launch(s, target, nt, slab + (size_t)NN_RED * 8);
@@ -558,29 +445,19 @@ int nearest_points_run(tl3d_ctx *ctx, const float *query, long long nq, const fl
     bad = nn_bounds_fold(h.data() + (size_t)NN_RED * 8, nt, mn, mx);
     if (bad) return set_err(TL3D_E_INVALID, "%llu target points have a non-finite coordinate", bad);
     if (!(cell > 0.0)) cell = nn_default_cell_points(mn, mx, nt);
-    NnGrid g;
-    while (!nn_grid(mn, mx, cell, &g)) cell *= 2.0;
+    CellGrid g;
+    cell_grid_fit(mn, mx, cell, &g);
     const long long ncell = (long long)g.nx * g.ny * g.nz;
-    const size_t nchunks = (size_t)((ncell + 1023) / 1024);
-    NnCarve cv;
-    const size_t o_cnt = cv.take<unsigned>(ncell), o_ts = cv.take<unsigned>(ncell + 1), o_qs = cv.take<unsigned>(ncell + 1);
-    const size_t o_cs = cv.take<unsigned>(nchunks), o_co = cv.take<unsigned long long>(nchunks + 1);
-    const size_t o_sorted = cv.take<float4>(nt), o_order = cv.take<unsigned>(nq);
-    rc = nn_reserve(ctx, cv.off);
+    NnScratch<float4> sc;
+    rc = nn_scratch(ctx, ncell, (size_t)nt, nq, &sc);
     if (rc) return rc;
-    char *b = (char *)ctx->nn_buf;
-    unsigned *cnt = (unsigned *)(b + o_cnt), *t_start = (unsigned *)(b + o_ts), *q_start = (unsigned *)(b + o_qs);
-    unsigned *chunk_sums = (unsigned *)(b + o_cs), *order = (unsigned *)(b + o_order);
-    unsigned long long *chunk_off = (unsigned long long *)(b + o_co);
-    float4 *sorted = (float4 *)(b + o_sorted);
-    const unsigned ntb = (unsigned)((nt + 255) / 256);
-    NN_HIP(hipMemsetAsync(cnt, 0, ncell * sizeof(unsigned), s));
-    hipLaunchKernelGGL(nn_count_kernel, dim3(ntb), dim3(256), 0, s, g, target, nt, cnt);
-    rc = nn_scan(s, cnt, ncell, chunk_sums, chunk_off, t_start);
+    NN_HIP(hipMemsetAsync(sc.cnt, 0, ncell * sizeof(unsigned), s));
+    launch_cell_count(s, g, target, nt, sc.cnt);
+    rc = launch_cell_scan(s, sc.cnt, ncell, sc.chunk_sums, sc.chunk_off, sc.t_start);
     if (rc) return rc;
-    hipLaunchKernelGGL(nn_fill_points_kernel, dim3(ntb), dim3(256), 0, s, g, target, nt, t_start, cnt, sorted);
-    const NnPointEval pe = {sorted};
-    return nn_search(ctx, g, query, nq, t_start, cnt, q_start, chunk_sums, chunk_off, order, pe, max_dist, dist, index);
+    launch_cell_fill(s, g, target, nt, sc.t_start, sc.cnt, EmitPointIndex{sc.payload});
+    const NnPointEval pe = {sc.payload};
+    return nn_search(ctx, g, query, nq, sc, pe, max_dist, dist, index);
 }
 
 // The (triangle, cell) pair list is bounded: the cell doubles until the list has at most NN_PAIR_CAP(n_tri) = min(16 n_tri + 2^20, 2^31)
@@ -591,9 +468,9 @@ static unsigned long long nn_pair_cap(long long n_tri) { return std::min(16ull *
 int nearest_triangles_run(tl3d_ctx *ctx, const float *query, long long nq, const float *xyz, long long nv, const unsigned *tri, long long n_tri,
                           double cell, double max_dist, double *dist, int *index) {
     hipStream_t s = ctx->stream;
-    int rc = nn_slab(ctx);
+    int rc = cell_slab(ctx);
     if (rc) return rc;
-    float *slab = (float *)ctx->nn_slab;
+    float *slab = (float *)ctx->cg_slab;
     double *tslab = (double *)(slab + (size_t)NN_RED * 16);
     unsigned long long *totals = (unsigned long long *)(tslab + (size_t)NN_RED * 2);       // [NN_LEVELS]
     std::vector<float> h((size_t)NN_RED * 16);
@@ -622,7 +499,7 @@ int nearest_triangles_run(tl3d_ctx *ctx, const float *query, long long nq, const
         cell = ext / (double)n_tri;
         if (!(cell > 0.0) || !isfinite(cell)) cell = 1.0;
     }
-    NnGrid g;
+    CellGrid g;
     const unsigned long long cap = nn_pair_cap(n_tri);
     const unsigned ntb = (unsigned)((n_tri + 255) / 256);
     unsigned long long npairs = 0;
@@ -630,7 +507,7 @@ int nearest_triangles_run(tl3d_ctx *ctx, const float *query, long long nq, const
         NnLevels lv;
         bool ok[NN_LEVELS];
         for (int j = 0; j < NN_LEVELS; ++j) {
-            ok[j] = nn_grid(mn, mx, ldexp(cell, j), &lv.g[j]);
+            ok[j] = cell_grid_make(mn, mx, ldexp(cell, j), &lv.g[j]);
             if (!ok[j]) lv.g[j].nx = lv.g[j].ny = lv.g[j].nz = 1;       // not a candidate: counted as one cell, never chosen
         }
         unsigned long long got[NN_LEVELS];
@@ -644,32 +521,24 @@ int nearest_triangles_run(tl3d_ctx *ctx, const float *query, long long nq, const
         cell = ldexp(cell, NN_LEVELS);
     }
     const long long ncell = (long long)g.nx * g.ny * g.nz;
-    const size_t nchunks = (size_t)((ncell + 1023) / 1024);
-    NnCarve cv;
-    const size_t o_cnt = cv.take<unsigned>(ncell), o_ts = cv.take<unsigned>(ncell + 1), o_qs = cv.take<unsigned>(ncell + 1);
-    const size_t o_cs = cv.take<unsigned>(nchunks), o_co = cv.take<unsigned long long>(nchunks + 1);
-    const size_t o_pairs = cv.take<unsigned>(npairs), o_order = cv.take<unsigned>(nq);
-    rc = nn_reserve(ctx, cv.off);
+    NnScratch<unsigned> sc;
+    rc = nn_scratch(ctx, ncell, (size_t)npairs, nq, &sc);
     if (rc) return rc;
-    char *b = (char *)ctx->nn_buf;
-    unsigned *cnt = (unsigned *)(b + o_cnt), *t_start = (unsigned *)(b + o_ts), *q_start = (unsigned *)(b + o_qs);
-    unsigned *chunk_sums = (unsigned *)(b + o_cs), *order = (unsigned *)(b + o_order), *pairs = (unsigned *)(b + o_pairs);
-    unsigned long long *chunk_off = (unsigned long long *)(b + o_co);
-    NN_HIP(hipMemsetAsync(cnt, 0, ncell * sizeof(unsigned), s));
-    hipLaunchKernelGGL(nn_tri_bin_kernel, dim3(ntb), dim3(256), 0, s, g, xyz, tri, n_tri, (const unsigned *)nullptr, cnt, (unsigned *)nullptr);
-    rc = nn_scan(s, cnt, ncell, chunk_sums, chunk_off, t_start);
+    NN_HIP(hipMemsetAsync(sc.cnt, 0, ncell * sizeof(unsigned), s));
+    hipLaunchKernelGGL(nn_tri_bin_kernel, dim3(ntb), dim3(256), 0, s, g, xyz, tri, n_tri, (const unsigned *)nullptr, sc.cnt, (unsigned *)nullptr);
+    rc = launch_cell_scan(s, sc.cnt, ncell, sc.chunk_sums, sc.chunk_off, sc.t_start);
     if (rc) return rc;
-    hipLaunchKernelGGL(nn_tri_bin_kernel, dim3(ntb), dim3(256), 0, s, g, xyz, tri, n_tri, (const unsigned *)t_start, cnt, pairs);
-    const NnTriEval te = {pairs, xyz, tri};
-    return nn_search(ctx, g, query, nq, t_start, cnt, q_start, chunk_sums, chunk_off, order, te, max_dist, dist, index);
+    hipLaunchKernelGGL(nn_tri_bin_kernel, dim3(ntb), dim3(256), 0, s, g, xyz, tri, n_tri, (const unsigned *)sc.t_start, sc.cnt, sc.payload);
+    const NnTriEval te = {sc.payload, xyz, tri};
+    return nn_search(ctx, g, query, nq, sc, te, max_dist, dist, index);
 }
 
 // dist: device memory.  The block partials are added in block order on the host: the same input gives the same bytes.
 int distance_summary_run(tl3d_ctx *ctx, const double *dist, long long n, const double *thresholds, int nthr, tl3d_distance_stats *out) {
     hipStream_t s = ctx->stream;
-    int rc = nn_slab(ctx);
+    int rc = cell_slab(ctx);
     if (rc) return rc;
-    unsigned long long *slab = (unsigned long long *)ctx->nn_slab;          // [NN_RED][16]
+    unsigned long long *slab = (unsigned long long *)ctx->cg_slab;          // [NN_RED][16]
     NnThr thr;
     for (int j = 0; j < 8; ++j) thr.t[j] = j < nthr ? thresholds[j] : 0.0;
     const unsigned nb = nn_red_blocks(n);

@@ -414,8 +414,8 @@ static void release_grid(tl3d_ctx *ctx) {
     if (gs.mio_counts) (void)hipFree(gs.mio_counts);
     if (gs.mio_offsets) (void)hipFree(gs.mio_offsets);
     if (gs.mio_info) (void)hipFree(gs.mio_info);
-    if (gs.nn_slab) (void)hipFree(gs.nn_slab);
-    if (gs.nn_buf) (void)hipFree(gs.nn_buf);
+    if (gs.cg_slab) (void)hipFree(gs.cg_slab);
+    if (gs.cg_buf) (void)hipFree(gs.cg_buf);
     for (int h = 0; h < TSDF_SCRATCHES; ++h)
         if (gs.ev_upd[h]) (void)hipEventDestroy(gs.ev_upd[h]);      // (build_grid creates them anew)
     memset(&gs, 0, sizeof(gs));
@@ -2721,7 +2721,7 @@ int tl3d_knn_mean_distance(tl3d_ctx *ctx, const float *xyz, int64_t n, int nb_ne
     int rc = st.in(xyz, (size_t)n * 12, &dx);
     if (!rc) rc = st.out(mean_out, (size_t)n * sizeof(double), &dm);
     if (rc) return rc;
-    return st.finish(sor_mean_distance(ctx, dx, n, nb_neighbors, cell_size, dm), true);
+    return st.finish(sor_mean_distance(ctx, dx, n, nb_neighbors, cell_size, &dm), true);
 }
 
 // ------------------------------------------------------------------------------------------- mesh components

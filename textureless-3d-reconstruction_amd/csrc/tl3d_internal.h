@@ -299,11 +299,12 @@ struct tl3d_grid_state {
     unsigned long long *mio_offsets;
     size_t mio_chunks;                      // capacity of both, in entries
     unsigned long long *mio_info;           // [8]
-    // tl3d_nearest_points / tl3d_nearest_triangles / tl3d_distance_summary: the block partials of their
-    // reductions (fixed size) and ONE buffer the calls carve their cell tables, sorted target and query order from.
+    // The calls on the uniform cell index (cellgrid.h) -- tl3d_statistical_outlier / tl3d_knn_mean_distance,
+    // tl3d_nearest_points / tl3d_nearest_triangles -- and tl3d_distance_summary: the block partials of their reductions (fixed size)
+    // and ONE buffer each call carves its cell tables and sorted points from (cell_carve), nothing in it live across calls.
     // Grid-independent like the cc_ scratch, and here for the same reason.
-    void *nn_slab, *nn_buf;
-    size_t nn_bytes;                        // capacity of nn_buf
+    void *cg_slab, *cg_buf;
+    size_t cg_bytes;                        // capacity of cg_buf
     // tl3d_set_block_core: the grid is one block of a lattice of lat[] voxels and emits only what its core (grid.clo / chi) owns
     bool has_core;
     long long lat[3];
@@ -619,7 +620,7 @@ int launch_iota(hipStream_t s, unsigned *t, unsigned n);
 int probe_hw_queues(int n_streams, double spin_ms, double *elapsed_ms);
 int launch_add_i32(hipStream_t s, int *dst, const int *src, size_t n);
 int launch_add_u64(hipStream_t s, unsigned long long *dst, const unsigned long long *src, size_t n);
-// outlier filter: the k-NN mean-distance stage alone (mean_dev: n doubles), and the whole filter, which thresholds it
+// mesh components (kernels_meshcc.hip)
 int launch_cc_validate(hipStream_t s, const unsigned *tri, long long n_tri, unsigned long long *info);
 int launch_cc_label(hipStream_t s, const unsigned *tri, long long n_tri, long long n_vert, unsigned *parent, unsigned *count,
                     unsigned long long *info);
@@ -644,7 +645,19 @@ int launch_ms_write(hipStream_t s, double cell, const double o[3], const float *
                     unsigned long long vcap, const unsigned *tri, long long n_tri, const uint8_t *flag, const unsigned long long *toffsets,
                     unsigned *out_tri, unsigned long long tcap, const unsigned long long *qacc = nullptr, double reg = 0.0,
                     unsigned long long *info = nullptr);
-int sor_mean_distance(tl3d_ctx *ctx, const float *xyz_dev, long long n, int k, double cell, double *mean_dev);
+// the uniform cell index (kernels_cellgrid.hip; the device half is cellgrid.h)
+struct CellGrid;
+constexpr size_t CELL_SLAB_BYTES = 128 << 10;
+inline size_t cell_chunks(long long ncell) { return (size_t)((ncell + 1023) / 1024); }
+bool cell_grid_make(const double mn[3], const double mx[3], double cell, CellGrid *g);
+void cell_grid_fit(const double mn[3], const double mx[3], double cell, CellGrid *g);
+void launch_cell_count(hipStream_t s, const CellGrid &g, const float *xyz, long long n, unsigned *cnt);
+int launch_cell_scan(hipStream_t s, const unsigned *cnt, long long ncell, unsigned *chunk_sums, unsigned long long *chunk_off, unsigned *start);
+int cell_slab(tl3d_ctx *ctx);
+int cell_carve(tl3d_ctx *ctx, const size_t *bytes, int n, void **out);
+// outlier filter (kernels_sor.hip): the k-NN mean-distance stage alone (*mean_dev: n doubles, or null: carved with the call's scratch
+// and returned), and the whole filter, which thresholds it
+int sor_mean_distance(tl3d_ctx *ctx, const float *xyz_dev, long long n, int k, double cell, double **mean_dev);
 int sor_run(tl3d_ctx *ctx, const float *xyz_dev, long long n, int k, double std_ratio, double cell, uint8_t *keep_dev, long long *kept);
 
 // nearest neighbours from one set to another and the distance summary (kernels_nearest.hip); device pointers, outputs may be null
