@@ -237,7 +237,8 @@ def icp_sums(g: Geometry, depth_src, nmap_tgt, T, stride=4, max_dist=0.05, scale
         ty = ((vt.astype(F32) - g.cy) / g.fy) * dt
         dx, dy, dz = qx - tx, qy - ty, qz - dt
         dist2 = fma32(dx, dx, fma32(dy, dy, dz * dz))
-        ok &= dist2 <= F32(max_dist * max_dist)
+        md = F32(max_dist)
+        ok &= dist2 <= md * md                                             # the f32 gate squared in f32 (tl3d.h; not the double's square)
         nx, ny, nz = nm[..., 0], nm[..., 1], nm[..., 2]
         res = fma32(dx, nx, fma32(dy, ny, dz * nz))
         J = [fma32(qy, nz, -(qz * ny)), fma32(qz, nx, -(qx * nz)), fma32(qx, ny, -(qy * nx)), nx, ny, nz]
