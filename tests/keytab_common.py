@@ -20,7 +20,7 @@ def kt_mix(keys):
 
 
 def kt_slots(max_keys):
-    """kt_slots of tl3d_api.hip: the smallest power of two >= 1024 and >= 2 * max_keys"""
+    """kt_slots of api_mesh.hip: the smallest power of two >= 1024 and >= 2 * max_keys"""
     cap = MIN_SLOTS
     while cap < 2 * int(max_keys):
         cap <<= 1

@@ -94,28 +94,4 @@ int cell_slab(tl3d_ctx *ctx) {
     return TL3D_OK;
 }
 
-// A call's scratch: n arrays of bytes[i] bytes, carved at 256-B steps from ONE buffer of the context that grows on demand
-// (release_grid frees it).  What an earlier call left in it is garbage to the next.
-int cell_carve(tl3d_ctx *ctx, const size_t *bytes, int n, void **out) {
-    size_t total = 0;
-    for (int i = 0; i < n; ++i) total += (bytes[i] + 255) & ~(size_t)255;
-    if (total > ctx->cg_bytes) {
-        if (ctx->cg_buf) (void)hipFree(ctx->cg_buf);
-        ctx->cg_buf = nullptr;
-        ctx->cg_bytes = 0;
-        if (hipMalloc(&ctx->cg_buf, total) != hipSuccess) {
-            (void)hipGetLastError();
-            ctx->cg_buf = nullptr;
-            return set_err(TL3D_E_NOMEM, "nearest-neighbour scratch alloc (%zu B) failed", total);
-        }
-        ctx->cg_bytes = total;
-    }
-    size_t off = 0;
-    for (int i = 0; i < n; ++i) {
-        out[i] = (char *)ctx->cg_buf + off;
-        off += (bytes[i] + 255) & ~(size_t)255;
-    }
-    return TL3D_OK;
-}
-
 }  // namespace tl3d

@@ -23,6 +23,7 @@
 
 #include <vector>
 
+#include "api_host.h"
 #include "cellgrid.h"
 
 namespace tl3d {
@@ -393,7 +394,7 @@ template <class P> static int nn_scratch(tl3d_ctx *ctx, long long ncell, size_t 
                              nchunks * sizeof(unsigned), (nchunks + 1) * sizeof(unsigned long long), n_payload * sizeof(P),
                              (size_t)nq * sizeof(unsigned)};
     void *p[7];
-    const int rc = cell_carve(ctx, bytes, 7, p);
+    const int rc = scratch_carve(ctx, 0, bytes, 7, p, "nearest-neighbour scratch");
     if (rc) return rc;
     *sc = {(unsigned *)p[0], (unsigned *)p[1], (unsigned *)p[2], (unsigned *)p[3], (unsigned long long *)p[4], (P *)p[5], (unsigned *)p[6]};
     return TL3D_OK;

@@ -11,6 +11,7 @@
 
 #include <vector>
 
+#include "api_host.h"
 #include "cellgrid.h"
 
 namespace tl3d {
@@ -117,7 +118,7 @@ int sor_mean_distance(tl3d_ctx *ctx, const float *xyz, long long n, int k, doubl
     const size_t bytes[6] = {(size_t)ncell * sizeof(unsigned), (size_t)(ncell + 1) * sizeof(unsigned), nchunks * sizeof(unsigned),
                              (nchunks + 1) * sizeof(unsigned long long), (size_t)n * 3 * sizeof(float), *mean_d ? 0 : (size_t)n * sizeof(double)};
     void *p[6];
-    rc = cell_carve(ctx, bytes, 6, p);
+    rc = scratch_carve(ctx, 0, bytes, 6, p, "nearest-neighbour scratch");
     if (rc) return rc;
     unsigned *cnt = (unsigned *)p[0], *start = (unsigned *)p[1], *chunk_sums = (unsigned *)p[2];
     unsigned long long *chunk_off = (unsigned long long *)p[3];

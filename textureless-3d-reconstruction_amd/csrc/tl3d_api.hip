@@ -1,15 +1,14 @@
-// tl3d_api.hip -- the extern "C" surface declared in include/tl3d.h: context, frame slots, launch glue.
+// tl3d_api.hip -- the extern "C" surface declared in include/tl3d.h: context, frame slots, launch glue (the mesh calls: api_mesh.hip).
 #include <dlfcn.h>
 #include <stdarg.h>
 #include <stdlib.h>
 #include <math.h>
 
-#include <functional>
 #include <mutex>
 #include <new>
 #include <vector>
 
-#include "tl3d_internal.h"
+#include "api_host.h"
 
 using namespace tl3d;
 
@@ -36,11 +35,6 @@ static int env_int(const char *name, int dflt) {
     return dflt;
 #endif
 }
-
-#define REQUIRE(cond, code, ...)                           \
-    do {                                                   \
-        if (!(cond)) return set_err((code), __VA_ARGS__);  \
-    } while (0)
 
 // The five RCCL entry points the merge needs, resolved at run time; enum values from rccl.h (ncclInt32 = 2, ncclInt64 = 4,
 // ncclUint64 = 5, ncclSum = 0).
@@ -92,80 +86,6 @@ static hipError_t device_malloc_big(void **p, size_t bytes) {
     return e;
 }
 
-static bool is_device_ptr(const void *p) {
-    if (!p) return false;
-    hipPointerAttribute_t at;
-    memset(&at, 0, sizeof(at));
-    hipError_t e = hipPointerGetAttributes(&at, p);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
-}
-
-// Per-call device staging of caller arrays that may live in host or in device memory.  A device pointer is used as it is; a host
-// input gets a temporary and an upload on the context's stream, a host output a temporary that finish() copies back; scratch() is
-// a temporary of the call's own.  The destructor waits for the stream before it frees, on every way out of the call, so nothing
-// in flight loses its memory; a call that staged nothing never waits here.
-namespace {
-class Staging {
-  public:
-    explicit Staging(tl3d_ctx *ctx) : ctx_(ctx) {}
-    Staging(const Staging &) = delete;
-    Staging &operator=(const Staging &) = delete;
-    ~Staging() {
-        if (n_) (void)hipStreamSynchronize(ctx_->stream);
-        for (int i = 0; i < n_; ++i) (void)hipFree(tmp_[i].dev);
-    }
-    template <class T> int in(const T *p, size_t bytes, const T **dev) {
-        *dev = p;
-        if (is_device_ptr(p)) return TL3D_OK;
-        void *d = nullptr;
-        const int rc = take(bytes, nullptr, &d);
-        if (rc) return rc;
-        *dev = (const T *)d;
-        if (hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, ctx_->stream) != hipSuccess) return set_err(TL3D_E_HIP, "staging upload (%zu B) failed", bytes);
-        return TL3D_OK;
-    }
-    template <class T> int out(T *p, size_t bytes, T **dev) {
-        *dev = p;
-        if (is_device_ptr(p) || bytes == 0) return TL3D_OK;
-        return take(bytes, p, (void **)dev);
-    }
-    template <class T> int scratch(size_t bytes, T **dev) { return take(bytes, nullptr, (void **)dev); }
-    // rc: what the launchers returned; it wins.  Otherwise the host outputs are copied back, and the stream is waited for when
-    // anything was staged (or `wait`: the call promises finished device outputs too)
-    int finish(int rc, bool wait = false) {
-        if (rc) return rc;
-        hipError_t e = hipSuccess;
-        for (int i = 0; i < n_ && e == hipSuccess; ++i)
-            if (tmp_[i].host_out) e = hipMemcpyAsync(tmp_[i].host_out, tmp_[i].dev, tmp_[i].bytes, hipMemcpyDeviceToHost, ctx_->stream);
-        if (e == hipSuccess && (n_ || wait)) e = hipStreamSynchronize(ctx_->stream);
-        if (e != hipSuccess) return set_err(TL3D_E_HIP, "staging copy / sync failed: %s", hipGetErrorString(e));
-        return TL3D_OK;
-    }
-
-  private:
-    int take(size_t bytes, void *host_out, void **dev) {
-        *dev = nullptr;
-        if (n_ == MAX) return set_err(TL3D_E_STATE, "more than %d staged arrays in one call", MAX);
-        if (hipMalloc(dev, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            *dev = nullptr;
-            return set_err(TL3D_E_NOMEM, "staging alloc (%zu B) failed", bytes);
-        }
-        tmp_[n_++] = {*dev, host_out, bytes};
-        return TL3D_OK;
-    }
-    static constexpr int MAX = 8;
-    struct Tmp { void *dev, *host_out; size_t bytes; };
-    tl3d_ctx *ctx_;
-    Tmp tmp_[MAX];
-    int n_ = 0;
-};
-}  // namespace
-
 // grow-on-demand device scratch of `need` elements: on failure the buffer is gone and its capacity 0
 template <class T> static int grow(T **p, size_t *cap, size_t need, const char *what) {
     if (need <= *cap) return TL3D_OK;
@@ -188,23 +108,20 @@ template <class A, class B> static int grow_pair(A **a, B **b, size_t *cap, size
     return rc;
 }
 
-// A counts / offsets pair of the compaction (compact.h), cut into its halves: [n[0] chunks + 1] for the vertices (or the points),
-// then [n[1] chunks + 1] for the triangles; the entry behind a half's chunks takes its total.  One half when n1 < 0.
-struct ChunkHalves {
-    int n[2];
-    unsigned *counts[2];
-    unsigned long long *offs[2];
-    ChunkHalves(unsigned *c, unsigned long long *o, int n0, int n1 = -1) : n{n0, n1}, counts{c, c + n0 + 1}, offs{o, o + n0 + 1} {}
-    int scan(hipStream_t s, int h) const { return launch_scan(s, counts[h], offs[h], n[h], offs[h] + n[h]); }
-    // behind the caller's launches: the totals of the halves and, with `info`, its first four report words; one wait for all
-    int totals(hipStream_t s, unsigned long long *tot, const unsigned long long *info = nullptr, unsigned long long *h_info = nullptr) const {
-        for (int h = 0; h < (n[1] < 0 ? 1 : 2); ++h)
-            TL3D_HIP(hipMemcpyAsync(&tot[h], offs[h] + n[h], sizeof(tot[h]), hipMemcpyDeviceToHost, s));
-        if (info) TL3D_HIP(hipMemcpyAsync(h_info, info, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-        TL3D_HIP(hipStreamSynchronize(s));
-        return TL3D_OK;
+namespace tl3d {
+int scratch_carve(tl3d_ctx *ctx, int stage, const size_t *bytes, int n, void **out, const char *what) {
+    size_t total = 0;
+    for (int i = 0; i < n; ++i) total += (bytes[i] + 255) & ~(size_t)255;
+    const int rc = grow(&ctx->scratch[stage], &ctx->scratch_bytes[stage], total, what);
+    if (rc) return rc;
+    size_t off = 0;
+    for (int i = 0; i < n; ++i) {
+        out[i] = ctx->scratch[stage] + off;
+        off += (bytes[i] + 255) & ~(size_t)255;
     }
-};
+    return TL3D_OK;
+}
+}  // namespace tl3d
 
 static PoseF make_pose_f(const double R[9], const double t[3]) {
     PoseF p;
@@ -391,31 +308,9 @@ static void release_grid(tl3d_ctx *ctx) {
     if (gs.mesh_counts) (void)hipFree(gs.mesh_counts);
     if (gs.mesh_offsets) (void)hipFree(gs.mesh_offsets);
     if (gs.mesh_first) (void)hipFree(gs.mesh_first);
-    if (gs.cc_parent) (void)hipFree(gs.cc_parent);
-    if (gs.cc_count) (void)hipFree(gs.cc_count);
-    if (gs.cc_remap) (void)hipFree(gs.cc_remap);
-    if (gs.kt_keys) (void)hipFree(gs.kt_keys);
-    if (gs.kt_vals) (void)hipFree(gs.kt_vals);
-    if (gs.ms_slot) (void)hipFree(gs.ms_slot);
-    if (gs.ms_vmap) (void)hipFree(gs.ms_vmap);
-    if (gs.ms_acc) (void)hipFree(gs.ms_acc);
-    if (gs.ms_qacc) (void)hipFree(gs.ms_qacc);
-    if (gs.ms_ttab) (void)hipFree(gs.ms_ttab);
-    if (gs.ms_flag) (void)hipFree(gs.ms_flag);
-    if (gs.adj_cnt) (void)hipFree(gs.adj_cnt);
-    if (gs.adj_cursor) (void)hipFree(gs.adj_cursor);
-    if (gs.adj_row) (void)hipFree(gs.adj_row);
-    if (gs.adj_list) (void)hipFree(gs.adj_list);
-    if (gs.adj_xyz) (void)hipFree(gs.adj_xyz);
-    if (gs.adj_ccounts) (void)hipFree(gs.adj_ccounts);
-    if (gs.adj_coffs) (void)hipFree(gs.adj_coffs);
-    if (gs.wm_vmap) (void)hipFree(gs.wm_vmap);
-    if (gs.wm_parts) (void)hipFree(gs.wm_parts);
-    if (gs.mio_counts) (void)hipFree(gs.mio_counts);
-    if (gs.mio_offsets) (void)hipFree(gs.mio_offsets);
-    if (gs.mio_info) (void)hipFree(gs.mio_info);
+    if (gs.scratch[0]) (void)hipFree(gs.scratch[0]);
+    if (gs.scratch[1]) (void)hipFree(gs.scratch[1]);
     if (gs.cg_slab) (void)hipFree(gs.cg_slab);
-    if (gs.cg_buf) (void)hipFree(gs.cg_buf);
     for (int h = 0; h < TSDF_SCRATCHES; ++h)
         if (gs.ev_upd[h]) (void)hipEventDestroy(gs.ev_upd[h]);      // (build_grid creates them anew)
     memset(&gs, 0, sizeof(gs));
@@ -2724,70 +2619,6 @@ int tl3d_knn_mean_distance(tl3d_ctx *ctx, const float *xyz, int64_t n, int nb_ne
     return st.finish(sor_mean_distance(ctx, dx, n, nb_neighbors, cell_size, &dm), true);
 }
 
-// ------------------------------------------------------------------------------------------- mesh components
-// [a, a + na) and [b, b + nb) share a byte (host and device pointers live in one address space)
-static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
-    if (!a || !b || !na || !nb) return false;
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
-
-// the argument checks both calls share; none of them needs a device
-static int cc_check_mesh(const uint32_t *tri, int64_t n_tri, int64_t n_vert, const char *tri_reason = "the component key needs") {
-    REQUIRE(n_tri >= 0 && n_vert >= 0, TL3D_E_INVALID, "negative size (n_tri %lld, n_vert %lld)", (long long)n_tri, (long long)n_vert);
-    REQUIRE(n_vert < (1ll << 31), TL3D_E_INVALID, "n_vert %lld: indices need fewer than 2^31 vertices", (long long)n_vert);
-    REQUIRE(n_tri < (1ll << 32), TL3D_E_INVALID, "n_tri %lld: %s fewer than 2^32 triangles", (long long)n_tri, tri_reason);
-    REQUIRE(n_tri == 0 || tri, TL3D_E_INVALID, "null triangle list");
-    return TL3D_OK;
-}
-
-// the chunk counts / offsets and the report words of the mesh-in / mesh-out calls (tl3d_internal.h: mio_*)
-static int mio_grow(tl3d_ctx *ctx, int64_t n_tri, int64_t n_vert, const char *what) {
-    int rc = grow_pair(&ctx->mio_counts, &ctx->mio_offsets, &ctx->mio_chunks, (size_t)chunks_of(n_vert) + (size_t)chunks_of(n_tri) + 2, what);
-    if (rc) return rc;
-    if (!ctx->mio_info && hipMalloc(&ctx->mio_info, 8 * sizeof(unsigned long long)) != hipSuccess) {
-        (void)hipGetLastError();
-        ctx->mio_info = nullptr;
-        return set_err(TL3D_E_NOMEM, "%s alloc failed", what);
-    }
-    return TL3D_OK;
-}
-
-// slots of a table that takes max_keys entries at most (keytab.h H3): the smallest power of two >= 1024 and >= 2 * max_keys
-static size_t kt_slots(size_t max_keys) {
-    size_t cap = 1024;
-    while (cap < 2 * max_keys) cap <<= 1;                  // load <= 0.5
-    return cap;
-}
-
-// The context's key table (tl3d_internal.h: kt_*) with `slots` slots, every key EMPTY behind what the stream holds already; vals: the
-// caller keeps a 32-bit word beside each key (what it holds, and its fill if it needs one, are the caller's)
-static int kt_reserve(tl3d_ctx *ctx, size_t slots, bool vals, const char *what) {
-    int rc = grow(&ctx->kt_keys, &ctx->kt_key_slots, slots, what);
-    if (!rc && vals) rc = grow(&ctx->kt_vals, &ctx->kt_val_slots, slots, what);
-    if (rc) return rc;
-    TL3D_HIP(hipMemsetAsync(ctx->kt_keys, 0xFF, slots * sizeof(unsigned long long), ctx->stream));
-    return TL3D_OK;
-}
-
-// The validation sequence of the calls that take one indexed mesh: the report words zeroed, the largest triangle index
-// (cc_validate_kernel) into word 0, the caller's own validator (`second`, if it has one) into word 1, one wait, and the refusal of
-// an index beyond n_vert.  *word1 = what `second` counted: the caller refuses it in its own words.  Nothing of the call indexes by
-// a triangle, or takes a coordinate apart, before this has returned TL3D_OK.
-static int mio_validate(tl3d_ctx *ctx, const uint32_t *dtri, int64_t n_tri, int64_t n_vert, const std::function<int()> &second = nullptr,
-                        unsigned long long *word1 = nullptr) {
-    unsigned long long h[2] = {0, 0};
-    TL3D_HIP(hipMemsetAsync(ctx->mio_info, 0, 8 * sizeof(unsigned long long), ctx->stream));
-    int rc = launch_cc_validate(ctx->stream, dtri, n_tri, ctx->mio_info);
-    if (!rc && second) rc = second();
-    if (rc) return rc;
-    TL3D_HIP(hipMemcpyAsync(h, ctx->mio_info, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-    TL3D_HIP(hipStreamSynchronize(ctx->stream));
-    REQUIRE(n_tri == 0 || (int64_t)h[0] < n_vert, TL3D_E_INVALID, "triangle index %llu out of range [0, %lld)", h[0], (long long)n_vert);
-    if (word1) *word1 = h[1];
-    return TL3D_OK;
-}
-
 // ------------------------------------------------------------------------------------------- nearest neighbours, distance summary
 // what both searches check before any device work
 static int nn_check(tl3d_ctx *ctx, const float *query, int64_t n_query, const void *const *ins, const size_t *in_bytes, int n_ins,
@@ -2871,541 +2702,6 @@ int tl3d_distance_summary(tl3d_ctx *ctx, const double *dist, int64_t n, const do
 int tl3d_set_nearest_query_order(tl3d_ctx *ctx, int cell_order) {
     REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
     ctx->nn_input_order = cell_order == 0;
-    return TL3D_OK;
-}
-
-static int cc_grow(tl3d_ctx *ctx, int64_t n_tri, int64_t n_vert) {
-    size_t cap2 = ctx->cc_verts, cap3 = ctx->cc_verts;
-    int rc = grow(&ctx->cc_parent, &ctx->cc_verts, (size_t)n_vert, "mesh component scratch");
-    if (!rc) rc = grow(&ctx->cc_count, &cap2, (size_t)n_vert, "mesh component scratch");
-    if (!rc) rc = grow(&ctx->cc_remap, &cap3, (size_t)n_vert, "mesh component scratch");
-    if (rc) {
-        ctx->cc_verts = 0;
-        return rc;
-    }
-    return mio_grow(ctx, n_tri, n_vert, "mesh component scratch");
-}
-
-// What a call that takes an indexed mesh and returns one does with its arrays, whichever kernels run in between: the argument
-// checks (their order, codes and texts are part of the interface), staging the three inputs, the capacity error, staging the
-// three outputs.  The call's fourth output (one entry per input vertex) differs in size and stays with the call.
-struct MeshIO {
-    const float *xyz; const uint8_t *rgb; int64_t n_vert; const uint32_t *tri; int64_t n_tri;
-    float *out_xyz; uint8_t *out_rgb; int64_t vert_cap; uint32_t *out_tri; int64_t tri_cap;
-    const float *dxyz = nullptr; const uint8_t *drgb = nullptr; const uint32_t *dtri = nullptr;     // stage_in
-    float *oxyz = nullptr; uint8_t *orgb = nullptr; uint32_t *otri = nullptr;                       // stage_out
-
-    // sizes, capacities, and the call's count outputs (counts_given: none of them is null)
-    int check_sizes(bool counts_given) const {
-        const int rc = cc_check_mesh(tri, n_tri, n_vert);
-        if (rc) return rc;
-        REQUIRE(vert_cap >= 0 && tri_cap >= 0, TL3D_E_INVALID, "negative capacity");
-        REQUIRE(counts_given, TL3D_E_INVALID, "null argument");
-        return TL3D_OK;
-    }
-    // the arrays; extra_out: the call's fourth output, extra_bytes long
-    int check_arrays(const void *extra_out, size_t extra_bytes) const {
-        REQUIRE(n_vert == 0 || xyz, TL3D_E_INVALID, "null vertex list");
-        REQUIRE((vert_cap == 0 || (out_xyz && (out_rgb || !rgb))) && (tri_cap == 0 || out_tri), TL3D_E_INVALID, "null output with a capacity");
-        const void *ins[3] = {xyz, rgb, tri};
-        const size_t in_b[3] = {(size_t)n_vert * 12, (size_t)n_vert * 3, (size_t)n_tri * 12};
-        const void *outs[4] = {out_xyz, rgb ? out_rgb : nullptr, out_tri, extra_out};
-        const size_t out_b[4] = {(size_t)vert_cap * 12, (size_t)vert_cap * 3, (size_t)tri_cap * 12, extra_bytes};
-        for (int o = 0; o < 4; ++o)
-            for (int i = 0; i < 3; ++i)
-                REQUIRE(!ranges_overlap(outs[o], out_b[o], ins[i], in_b[i]), TL3D_E_INVALID, "an output aliases an input");
-        return TL3D_OK;
-    }
-    int stage_in(Staging &st) {
-        int rc = st.in(xyz, (size_t)n_vert * 12, &dxyz);
-        if (!rc && rgb) rc = st.in(rgb, (size_t)n_vert * 3, &drgb);
-        if (!rc && n_tri) rc = st.in(tri, (size_t)n_tri * 12, &dtri);
-        return rc;
-    }
-    // tot: the vertices and triangles the result has
-    int stage_out(Staging &st, const unsigned long long tot[2]) {
-        if ((int64_t)tot[0] > vert_cap || (int64_t)tot[1] > tri_cap)
-            return set_err(TL3D_E_CAPACITY, "need %llu vertices / %llu triangles, capacities %lld / %lld", tot[0], tot[1], (long long)vert_cap,
-                           (long long)tri_cap);
-        int rc = st.out(out_xyz, (size_t)tot[0] * 12, &oxyz);
-        if (!rc && rgb) rc = st.out(out_rgb, (size_t)tot[0] * 3, &orgb);
-        if (!rc) rc = st.out(out_tri, (size_t)tot[1] * 12, &otri);
-        return rc;
-    }
-};
-
-// The validation pass and, only when every index is below n_vert, the labelling: cc_parent = labels, cc_count = triangles per
-// label, the report words: largest index, components, key of the largest component.  Waits for the stream once.
-static int cc_label(tl3d_ctx *ctx, const uint32_t *dtri, int64_t n_tri, int64_t n_vert) {
-    const int rc = mio_validate(ctx, dtri, n_tri, n_vert);
-    return rc ? rc : launch_cc_label(ctx->stream, dtri, n_tri, n_vert, ctx->cc_parent, ctx->cc_count, ctx->mio_info);
-}
-
-int tl3d_mesh_components(tl3d_ctx *ctx, const uint32_t *tri, int64_t n_tri, int64_t n_vert, uint32_t *label_out, uint32_t *tri_count_out,
-                         int64_t *out_n_components) {
-    int rc = cc_check_mesh(tri, n_tri, n_vert);
-    if (rc) return rc;
-    REQUIRE(out_n_components != nullptr && (n_vert == 0 || label_out), TL3D_E_INVALID, "null argument");
-    const size_t tb = (size_t)n_tri * 12, vb = (size_t)n_vert * 4;
-    REQUIRE(!ranges_overlap(label_out, vb, tri, tb) && !ranges_overlap(tri_count_out, vb, tri, tb) && !ranges_overlap(label_out, vb, tri_count_out, vb),
-            TL3D_E_INVALID, "an output aliases an input (or the other output)");
-    REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
-    *out_n_components = 0;
-    if (n_vert == 0) return TL3D_OK;
-    TL3D_HIP(hipSetDevice(ctx->device));
-    rc = cc_grow(ctx, n_tri, n_vert);
-    if (rc) return rc;
-    Staging st(ctx);
-    const uint32_t *dtri = nullptr;
-    if (n_tri) rc = st.in(tri, tb, &dtri);
-    if (rc) return rc;
-    unsigned long long h[4] = {0, 0, 0, 0};
-    rc = cc_label(ctx, dtri, n_tri, n_vert);
-    if (rc) return rc;
-    TL3D_HIP(hipMemcpyAsync(label_out, ctx->cc_parent, vb, hipMemcpyDefault, ctx->stream));
-    if (tri_count_out) TL3D_HIP(hipMemcpyAsync(tri_count_out, ctx->cc_count, vb, hipMemcpyDefault, ctx->stream));
-    TL3D_HIP(hipMemcpyAsync(h, ctx->mio_info, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-    TL3D_HIP(hipStreamSynchronize(ctx->stream));
-    *out_n_components = (int64_t)h[1];
-    return TL3D_OK;
-}
-
-int tl3d_mesh_filter_components(tl3d_ctx *ctx, const float *xyz, const uint8_t *rgb, int64_t n_vert, const uint32_t *tri, int64_t n_tri,
-                                int64_t min_triangles, int largest_only, float *out_xyz, uint8_t *out_rgb, int64_t vert_cap,
-                                uint32_t *out_tri, int64_t tri_cap, uint8_t *keep_vert_out, int64_t *out_n_vert, int64_t *out_n_tri,
-                                int64_t *out_n_components, int64_t *out_n_kept) {
-    MeshIO m{xyz, rgb, n_vert, tri, n_tri, out_xyz, out_rgb, vert_cap, out_tri, tri_cap};
-    int rc = m.check_sizes(out_n_vert && out_n_tri && out_n_components && out_n_kept);
-    if (!rc) rc = m.check_arrays(keep_vert_out, (size_t)n_vert);
-    if (rc) return rc;
-    REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
-    *out_n_vert = *out_n_tri = *out_n_components = *out_n_kept = 0;
-    if (n_vert == 0) return TL3D_OK;
-    TL3D_HIP(hipSetDevice(ctx->device));
-    rc = cc_grow(ctx, n_tri, n_vert);
-    if (rc) return rc;
-    Staging st(ctx);
-    uint8_t *dkeep = nullptr;
-    rc = m.stage_in(st);
-    if (!rc && keep_vert_out) rc = st.out(keep_vert_out, (size_t)n_vert, &dkeep);
-    if (rc) return rc;
-    unsigned long long h[4] = {0, 0, 0, 0};
-    rc = cc_label(ctx, m.dtri, n_tri, n_vert);
-    if (rc) return rc;
-    const ChunkHalves ch(ctx->mio_counts, ctx->mio_offsets, chunks_of(n_vert), chunks_of(n_tri));
-    rc = launch_cc_keep_count(ctx->stream, (long long)min_triangles, largest_only != 0, m.dtri, n_tri, n_vert, ctx->cc_parent, ctx->cc_count,
-                              ch.counts[0], ch.counts[1], dkeep, ctx->mio_info);
-    if (!rc) rc = ch.scan(ctx->stream, 0);
-    if (!rc) rc = ch.scan(ctx->stream, 1);                                                   // (no triangle: the total is 0)
-    unsigned long long tot[2] = {0, 0};
-    if (!rc) rc = ch.totals(ctx->stream, tot, ctx->mio_info, h);
-    if (rc) return rc;
-    *out_n_vert = (int64_t)tot[0];
-    *out_n_tri = (int64_t)tot[1];
-    *out_n_components = (int64_t)h[1];
-    *out_n_kept = (int64_t)h[3];
-    rc = m.stage_out(st, tot);
-    if (rc) return rc;
-    rc = launch_cc_compact(ctx->stream, (long long)min_triangles, largest_only != 0, m.dtri, n_tri, n_vert, ctx->cc_parent, ctx->cc_count,
-                           ch.offs[0], ch.offs[1], m.dxyz, m.drgb, m.oxyz, m.orgb, tot[0], m.otri, tot[1], ctx->cc_remap, ctx->mio_info);
-    return st.finish(rc, true);
-}
-
-// ------------------------------------------------------------------------------------------- mesh simplification
-// the vertex table: a key per slot and, in the word beside it, the cluster's leader
-static int ms_grow(tl3d_ctx *ctx, int64_t n_tri, int64_t n_vert) {
-    const char *what = "mesh simplification scratch";
-    int rc = kt_reserve(ctx, kt_slots((size_t)n_vert), true, what);
-    if (!rc) rc = grow_pair(&ctx->ms_slot, &ctx->ms_vmap, &ctx->ms_verts, (size_t)n_vert, what);
-    if (!rc) rc = grow(&ctx->ms_acc, &ctx->ms_acc_n, 7 * (size_t)n_vert, what);
-    if (!rc && n_tri) rc = grow(&ctx->ms_ttab, &ctx->ms_tslots, kt_slots((size_t)n_tri), what);
-    if (!rc && n_tri) rc = grow(&ctx->ms_flag, &ctx->ms_tris, (size_t)n_tri, what);
-    if (!rc) rc = mio_grow(ctx, n_tri, n_vert, what);
-    return rc;
-}
-
-// Both placements.  quadric: the three extra counts (placed, clamped, corners skipped), or nullptr for mean placement, which
-// then launches, copies and waits exactly as it did before the quadric existed.
-static int ms_simplify(tl3d_ctx *ctx, const float *xyz, const uint8_t *rgb, int64_t n_vert, const uint32_t *tri, int64_t n_tri, double cell,
-                       const double origin[3], double reg, float *out_xyz, uint8_t *out_rgb, int64_t vert_cap, uint32_t *out_tri,
-                       int64_t tri_cap, uint32_t *vert_map_out, int64_t *const counts[4], int64_t *const quadric[3]) {
-    MeshIO m{xyz, rgb, n_vert, tri, n_tri, out_xyz, out_rgb, vert_cap, out_tri, tri_cap};
-    int rc = m.check_sizes(counts[0] && counts[1] && counts[2] && counts[3] && (!quadric || (quadric[0] && quadric[1] && quadric[2])));
-    if (rc) return rc;
-    REQUIRE(std::isfinite(cell) && cell > 0.0, TL3D_E_INVALID, "cell size %g: must be finite and > 0", cell);
-    const double o[3] = {origin ? origin[0] : 0.0, origin ? origin[1] : 0.0, origin ? origin[2] : 0.0};
-    REQUIRE(std::isfinite(o[0]) && std::isfinite(o[1]) && std::isfinite(o[2]), TL3D_E_INVALID, "origin (%g, %g, %g) is not finite", o[0], o[1], o[2]);
-    REQUIRE(!quadric || (std::isfinite(reg) && reg > 0.0 && reg <= 1.0), TL3D_E_INVALID, "reg %g: must lie in (0, 1]", reg);
-    rc = m.check_arrays(vert_map_out, (size_t)n_vert * 4);
-    if (rc) return rc;
-    REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
-    for (int k = 0; k < 4; ++k) *counts[k] = 0;
-    for (int k = 0; quadric && k < 3; ++k) *quadric[k] = 0;
-    if (n_vert == 0) return TL3D_OK;
-    TL3D_HIP(hipSetDevice(ctx->device));
-    rc = ms_grow(ctx, n_tri, n_vert);
-    if (!rc && quadric) rc = grow(&ctx->ms_qacc, &ctx->ms_qacc_n, 18 * (size_t)n_vert, "mesh simplification scratch");
-    if (rc) return rc;
-    Staging st(ctx);
-    rc = m.stage_in(st);
-    if (rc) return rc;
-    // the validation passes: nothing is indexed, and no cell is computed for a table, before the host has seen their words
-    unsigned long long h[4] = {0, 0, 0, 0}, hq[3] = {0, 0, 0};
-    rc = mio_validate(ctx, m.dtri, n_tri, n_vert, [&] { return launch_ms_validate(ctx->stream, cell, o, m.dxyz, n_vert, ctx->mio_info); }, &h[1]);
-    if (rc) return rc;
-    REQUIRE(h[1] == 0, TL3D_E_INVALID, "%llu vertices are not finite or lie 2^20 cells or more from the origin", h[1]);
-    const size_t vslots = kt_slots((size_t)n_vert), tslots = kt_slots((size_t)n_tri);
-    const ChunkHalves ch(ctx->mio_counts, ctx->mio_offsets, chunks_of(n_vert), chunks_of(n_tri));
-    unsigned *leader = ctx->kt_vals;
-    unsigned long long *qacc = quadric ? ctx->ms_qacc : nullptr;
-    TL3D_HIP(hipMemsetAsync(leader, 0xFF, vslots * sizeof(unsigned), ctx->stream));
-    TL3D_HIP(hipMemsetAsync(ctx->ms_acc, 0, 7 * (size_t)n_vert * sizeof(unsigned long long), ctx->stream));
-    if (qacc) TL3D_HIP(hipMemsetAsync(qacc, 0, 18 * (size_t)n_vert * sizeof(unsigned long long), ctx->stream));
-    if (n_tri) TL3D_HIP(hipMemsetAsync(ctx->ms_ttab, 0xFF, tslots * sizeof(unsigned), ctx->stream));
-    rc = launch_ms_cluster(ctx->stream, cell, o, m.dxyz, m.drgb, n_vert, ctx->kt_keys, leader, vslots, ctx->ms_slot, ctx->ms_vmap,
-                           ctx->ms_acc, ch.counts[0], ch.offs[0]);
-    if (!rc && qacc) rc = launch_ms_quadrics(ctx->stream, cell, o, m.dxyz, m.dtri, n_tri, ctx->ms_vmap, qacc, ctx->mio_info);
-    if (!rc) rc = launch_ms_triangles(ctx->stream, m.dtri, n_tri, ctx->ms_vmap, ctx->ms_ttab, tslots, ctx->ms_flag, ch.counts[1], ch.offs[1], ctx->mio_info);
-    unsigned long long tot[2] = {0, 0};
-    if (!rc) rc = ch.totals(ctx->stream, tot, ctx->mio_info, h);
-    if (rc) return rc;
-    *counts[0] = (int64_t)tot[0];
-    *counts[1] = (int64_t)tot[1];
-    *counts[2] = (int64_t)h[2];
-    *counts[3] = (int64_t)h[3];
-    rc = m.stage_out(st, tot);
-    if (rc == TL3D_E_CAPACITY && quadric) {
-        // the solve counts what it places and clamps: run it without outputs, so that the refusal reports all seven counts
-        int rq = launch_ms_write(ctx->stream, cell, o, m.dxyz, false, n_vert, ctx->ms_slot, leader, ctx->ms_vmap, ctx->ms_acc, nullptr, nullptr, 0,
-                                 m.dtri, n_tri, ctx->ms_flag, ch.offs[1], nullptr, 0, qacc, reg, ctx->mio_info);
-        if (rq) return rq;
-        TL3D_HIP(hipMemcpyAsync(hq, ctx->mio_info + 4, sizeof(hq), hipMemcpyDeviceToHost, ctx->stream));
-        TL3D_HIP(hipStreamSynchronize(ctx->stream));
-        *quadric[0] = (int64_t)hq[1]; *quadric[1] = (int64_t)hq[2]; *quadric[2] = (int64_t)hq[0];
-    }
-    if (rc) return rc;
-    rc = launch_ms_write(ctx->stream, cell, o, m.dxyz, rgb != nullptr, n_vert, ctx->ms_slot, leader, ctx->ms_vmap, ctx->ms_acc, m.oxyz, m.orgb,
-                         tot[0], m.dtri, n_tri, ctx->ms_flag, ch.offs[1], m.otri, tot[1], qacc, reg, ctx->mio_info);
-    if (!rc && vert_map_out) TL3D_HIP(hipMemcpyAsync(vert_map_out, ctx->ms_vmap, (size_t)n_vert * 4, hipMemcpyDefault, ctx->stream));
-    if (!rc && quadric) TL3D_HIP(hipMemcpyAsync(hq, ctx->mio_info + 4, sizeof(hq), hipMemcpyDeviceToHost, ctx->stream));
-    rc = st.finish(rc, true);
-    if (!rc && quadric) { *quadric[0] = (int64_t)hq[1]; *quadric[1] = (int64_t)hq[2]; *quadric[2] = (int64_t)hq[0]; }
-    return rc;
-}
-
-int tl3d_mesh_simplify_clusters(tl3d_ctx *ctx, const float *xyz, const uint8_t *rgb, int64_t n_vert, const uint32_t *tri, int64_t n_tri,
-                                double cell, const double origin[3], float *out_xyz, uint8_t *out_rgb, int64_t vert_cap,
-                                uint32_t *out_tri, int64_t tri_cap, uint32_t *vert_map_out, int64_t *out_n_vert, int64_t *out_n_tri,
-                                int64_t *out_n_degenerate, int64_t *out_n_duplicate) {
-    int64_t *const counts[4] = {out_n_vert, out_n_tri, out_n_degenerate, out_n_duplicate};
-    return ms_simplify(ctx, xyz, rgb, n_vert, tri, n_tri, cell, origin, 0.0, out_xyz, out_rgb, vert_cap, out_tri, tri_cap, vert_map_out, counts,
-                       nullptr);
-}
-
-int tl3d_mesh_simplify_quadric(tl3d_ctx *ctx, const float *xyz, const uint8_t *rgb, int64_t n_vert, const uint32_t *tri, int64_t n_tri,
-                               double cell, const double origin[3], double reg, float *out_xyz, uint8_t *out_rgb, int64_t vert_cap,
-                               uint32_t *out_tri, int64_t tri_cap, uint32_t *vert_map_out, int64_t *out_n_vert, int64_t *out_n_tri,
-                               int64_t *out_n_degenerate, int64_t *out_n_duplicate, int64_t *out_n_quadric, int64_t *out_n_clamped,
-                               int64_t *out_n_skipped) {
-    int64_t *const counts[4] = {out_n_vert, out_n_tri, out_n_degenerate, out_n_duplicate};
-    int64_t *const quadric[3] = {out_n_quadric, out_n_clamped, out_n_skipped};
-    return ms_simplify(ctx, xyz, rgb, n_vert, tri, n_tri, cell, origin, reg, out_xyz, out_rgb, vert_cap, out_tri, tri_cap, vert_map_out, counts,
-                       quadric);
-}
-
-// ------------------------------------------------------------------------------------------- mesh smoothing, vertex normals
-// what both calls need per vertex and per chunk; the edge table, the rows and the second position buffer grow where they are used
-static int adj_grow(tl3d_ctx *ctx, int64_t n_tri, int64_t n_vert, const char *what) {
-    int rc = grow_pair(&ctx->adj_cnt, &ctx->adj_cursor, &ctx->adj_verts, (size_t)n_vert, what);
-    if (!rc) rc = grow(&ctx->adj_row, &ctx->adj_rows, (size_t)n_vert, what);
-    if (!rc) rc = grow_pair(&ctx->adj_ccounts, &ctx->adj_coffs, &ctx->adj_chunks, (size_t)chunks_of(n_vert) + 1, what);
-    if (!rc) rc = mio_grow(ctx, n_tri, n_vert, what);
-    return rc;
-}
-
-// the two validation passes and the host's look at their words: nothing is indexed, and no coordinate is quantised, before it
-static int adj_validate(tl3d_ctx *ctx, const float *dxyz, int64_t n_vert, const uint32_t *dtri, int64_t n_tri) {
-    unsigned long long bad = 0;
-    const int rc = mio_validate(ctx, dtri, n_tri, n_vert, [&] { return launch_msm_validate(ctx->stream, dxyz, n_vert, ctx->mio_info); }, &bad);
-    if (rc) return rc;
-    REQUIRE(bad == 0, TL3D_E_INVALID, "%llu vertices are not finite or lie beyond 2^20 m", bad);
-    return TL3D_OK;
-}
-
-int tl3d_mesh_smooth_taubin(tl3d_ctx *ctx, const float *xyz, int64_t n_vert, const uint32_t *tri, int64_t n_tri, int iterations, double lambda,
-                            double mu, float *out_xyz, uint32_t *valence_out, int64_t *out_n_edges) {
-    const char *what = "mesh smoothing scratch";
-    int rc = cc_check_mesh(tri, n_tri, n_vert, "the triangle and corner counts need");
-    if (rc) return rc;
-    REQUIRE(out_n_edges != nullptr && (n_vert == 0 || (xyz && out_xyz)), TL3D_E_INVALID, "null argument");
-    REQUIRE(iterations >= 0 && iterations <= 1000, TL3D_E_INVALID, "iterations %d out of range [0, 1000]", iterations);
-    REQUIRE(lambda > 0.0 && lambda <= 1.0, TL3D_E_INVALID, "lambda %g out of range (0, 1]", lambda);             // (false for NaN)
-    REQUIRE(mu >= -2.0 && mu <= 0.0, TL3D_E_INVALID, "mu %g out of range [-2, 0]", mu);
-    const size_t xb = (size_t)n_vert * 12, tb = (size_t)n_tri * 12, vb = (size_t)n_vert * 4;
-    REQUIRE(!ranges_overlap(out_xyz, xb, xyz, xb) && !ranges_overlap(out_xyz, xb, tri, tb) && !ranges_overlap(valence_out, vb, xyz, xb) &&
-                !ranges_overlap(valence_out, vb, tri, tb) && !ranges_overlap(valence_out, vb, out_xyz, xb),
-            TL3D_E_INVALID, "an output aliases an input (or the other output)");
-    REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
-    *out_n_edges = 0;
-    if (n_vert == 0) return TL3D_OK;
-    TL3D_HIP(hipSetDevice(ctx->device));
-    rc = adj_grow(ctx, n_tri, n_vert, what);
-    const size_t slots = kt_slots(3 * (size_t)n_tri);      // the edge table: a triangle brings at most three keys
-    if (!rc && n_tri) rc = kt_reserve(ctx, slots, false, what);
-    if (!rc && n_tri && iterations) rc = grow(&ctx->adj_xyz, &ctx->adj_xyz_n, 3 * (size_t)n_vert, what);
-    if (rc) return rc;
-    Staging st(ctx);
-    const float *dxyz = nullptr;
-    const uint32_t *dtri = nullptr;
-    float *oxyz = nullptr;
-    uint32_t *oval = nullptr;
-    rc = st.in(xyz, xb, &dxyz);
-    if (!rc && n_tri) rc = st.in(tri, tb, &dtri);
-    if (!rc) rc = st.out(out_xyz, xb, &oxyz);
-    if (!rc && valence_out) rc = st.out(valence_out, vb, &oval);
-    if (!rc) rc = adj_validate(ctx, dxyz, n_vert, dtri, n_tri);
-    if (rc) return rc;
-    hipStream_t s = ctx->stream;
-    TL3D_HIP(hipMemsetAsync(ctx->adj_cnt, 0, vb, s));
-    unsigned long long h[5] = {0, 0, 0, 0, 0};
-    if (n_tri) {
-        rc = launch_msm_edges(s, dtri, n_tri, ctx->kt_keys, slots, ctx->adj_cnt, ctx->mio_info);
-        if (rc) return rc;
-        TL3D_HIP(hipMemcpyAsync(h, ctx->mio_info, sizeof(h), hipMemcpyDeviceToHost, s));
-        TL3D_HIP(hipStreamSynchronize(s));
-    }
-    *out_n_edges = (int64_t)h[2];
-    if (oval) TL3D_HIP(hipMemcpyAsync(oval, ctx->adj_cnt, vb, hipMemcpyDeviceToDevice, s));
-    if (h[2] == 0 || iterations == 0) {                    // nothing moves
-        TL3D_HIP(hipMemcpyAsync(oxyz, dxyz, xb, hipMemcpyDeviceToDevice, s));
-        return st.finish(TL3D_OK, true);
-    }
-    rc = grow(&ctx->adj_list, &ctx->adj_list_n, 2 * (size_t)h[2], what);
-    if (!rc) rc = launch_msm_rows(s, ctx->adj_cnt, n_vert, ctx->adj_ccounts, ctx->adj_coffs, ctx->adj_row, ctx->adj_cursor);
-    if (!rc) rc = launch_msm_edge_fill(s, ctx->kt_keys, slots, ctx->adj_cnt, ctx->adj_row, ctx->adj_cursor, ctx->adj_list);
-    // 2 * iterations steps between the scratch buffer and the output: in -> scratch -> out -> scratch -> out ...
-    const float *src = dxyz;
-    for (int i = 0; i < 2 * iterations && !rc; ++i) {
-        float *dst = (i & 1) ? oxyz : ctx->adj_xyz;
-        // the divergence flag: step i reports through word 3 + (i & 1) and reads the word of the step before it (both zero at first)
-        rc = launch_msm_step(s, src, dst, n_vert, ctx->adj_cnt, ctx->adj_row, ctx->adj_list, (i & 1) ? mu : lambda,
-                             ctx->mio_info + 4 - (i & 1), ctx->mio_info + 3 + (i & 1));
-        src = dst;
-    }
-    if (rc) return rc;
-    TL3D_HIP(hipMemcpyAsync(h, ctx->mio_info, sizeof(h), hipMemcpyDeviceToHost, s));
-    rc = st.finish(TL3D_OK, true);
-    if (rc) return rc;
-    REQUIRE((h[3] | h[4]) == 0, TL3D_E_INVALID,
-            "smoothing diverged: a step gave a coordinate that is not finite or lies beyond 2^20 m (lambda %g, mu %g)", lambda, mu);
-    return TL3D_OK;
-}
-
-int tl3d_mesh_vertex_normals(tl3d_ctx *ctx, const float *xyz, int64_t n_vert, const uint32_t *tri, int64_t n_tri, float *out_normal,
-                             int64_t *out_n_zero) {
-    const char *what = "mesh normal scratch";
-    int rc = cc_check_mesh(tri, n_tri, n_vert, "the triangle ids of the rows need");
-    if (rc) return rc;
-    REQUIRE(out_n_zero != nullptr && (n_vert == 0 || (xyz && out_normal)), TL3D_E_INVALID, "null argument");
-    const size_t xb = (size_t)n_vert * 12, tb = (size_t)n_tri * 12;
-    REQUIRE(!ranges_overlap(out_normal, xb, xyz, xb) && !ranges_overlap(out_normal, xb, tri, tb), TL3D_E_INVALID, "an output aliases an input");
-    REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
-    *out_n_zero = 0;
-    if (n_vert == 0) return TL3D_OK;
-    TL3D_HIP(hipSetDevice(ctx->device));
-    rc = adj_grow(ctx, n_tri, n_vert, what);
-    if (!rc && n_tri) rc = grow(&ctx->adj_list, &ctx->adj_list_n, 3 * (size_t)n_tri, what);
-    if (rc) return rc;
-    Staging st(ctx);
-    const float *dxyz = nullptr;
-    const uint32_t *dtri = nullptr;
-    float *onrm = nullptr;
-    rc = st.in(xyz, xb, &dxyz);
-    if (!rc && n_tri) rc = st.in(tri, tb, &dtri);
-    if (!rc) rc = st.out(out_normal, xb, &onrm);
-    if (!rc) rc = adj_validate(ctx, dxyz, n_vert, dtri, n_tri);
-    if (rc) return rc;
-    hipStream_t s = ctx->stream;
-    if (n_tri == 0) {
-        TL3D_HIP(hipMemsetAsync(onrm, 0, xb, s));
-        *out_n_zero = n_vert;
-        return st.finish(TL3D_OK, true);
-    }
-    TL3D_HIP(hipMemsetAsync(ctx->adj_cnt, 0, (size_t)n_vert * 4, s));
-    rc = launch_msm_corners(s, dtri, n_tri, n_vert, ctx->adj_cnt, ctx->adj_ccounts, ctx->adj_coffs, ctx->adj_row, ctx->adj_cursor, ctx->adj_list);
-    if (!rc) rc = launch_msm_normals(s, dxyz, dtri, n_vert, ctx->adj_cnt, ctx->adj_row, ctx->adj_list, onrm, ctx->mio_info);
-    if (rc) return rc;
-    unsigned long long h[4] = {0, 0, 0, 0};
-    TL3D_HIP(hipMemcpyAsync(h, ctx->mio_info, sizeof(h), hipMemcpyDeviceToHost, s));
-    rc = st.finish(TL3D_OK, true);
-    if (rc) return rc;
-    *out_n_zero = (int64_t)h[3];
-    return TL3D_OK;
-}
-
-// ------------------------------------------------------------------------------------------- mesh weld
-// Waits for the stream three times, however many parts there are: behind the validation pass, behind the scan (the number kept sizes
-// the table and is compared with the capacity), and at the end.
-int tl3d_mesh_weld_keyed(tl3d_ctx *ctx, const tl3d_mesh_part *parts, int n_parts, const int64_t lattice_dims[3], float *out_xyz,
-                         uint8_t *out_rgb, int64_t *out_key, int64_t vert_cap, uint32_t *out_tri, int64_t tri_cap, int64_t *out_n_vert,
-                         int64_t *out_n_tri, int64_t *out_n_twice, int64_t *out_n_unowned) {
-    const char *what = "mesh weld scratch";
-    REQUIRE(lattice_dims && out_n_vert && out_n_tri && out_n_twice && out_n_unowned && (n_parts <= 0 || parts), TL3D_E_INVALID, "null argument");
-    REQUIRE(n_parts >= 0, TL3D_E_INVALID, "n_parts %d is negative", n_parts);
-    REQUIRE(vert_cap >= 0 && tri_cap >= 0, TL3D_E_INVALID, "negative capacity");
-    int64_t nv_tot = 0, nt_tot = 0;
-    int with_rgb = 0, with_verts = 0;
-    for (int p = 0; p < n_parts; ++p) {
-        const tl3d_mesh_part &m = parts[p];
-        REQUIRE(m.n_vert >= 0 && m.n_tri >= 0, TL3D_E_INVALID, "part %d: negative size (n_vert %lld, n_tri %lld)", p, (long long)m.n_vert,
-                (long long)m.n_tri);
-        REQUIRE(m.n_vert < (1ll << 31), TL3D_E_INVALID, "part %d: n_vert %lld: indices need fewer than 2^31 vertices", p, (long long)m.n_vert);
-        REQUIRE(m.n_tri < (1ll << 32), TL3D_E_INVALID, "part %d: n_tri %lld: needs fewer than 2^32 triangles", p, (long long)m.n_tri);
-        REQUIRE((m.n_vert == 0 || (m.xyz_hd && m.key_hd)) && (m.n_tri == 0 || m.tri_hd), TL3D_E_INVALID, "null argument (part %d)", p);
-        nv_tot += m.n_vert;
-        nt_tot += m.n_tri;
-        with_verts += m.n_vert > 0;
-        with_rgb += m.n_vert > 0 && m.rgb_hd;
-    }
-    REQUIRE(nt_tot < (1ll << 32), TL3D_E_INVALID, "%lld triangles in all: the welded mesh needs fewer than 2^32 triangles", (long long)nt_tot);
-    REQUIRE(nv_tot < (1ll << 40), TL3D_E_INVALID, "%lld vertices in all: the weld needs fewer than 2^40 input vertices", (long long)nv_tot);
-    unsigned __int128 nlat = 1;
-    for (int a = 0; a < 3; ++a) {
-        REQUIRE(lattice_dims[a] > 0, TL3D_E_INVALID, "lattice of %lld voxels on axis %d", (long long)lattice_dims[a], a);
-        nlat *= (unsigned __int128)lattice_dims[a];
-        REQUIRE(nlat < ((unsigned __int128)1 << 61), TL3D_E_INVALID, "lattice of 2^61 voxels or more: mesh keys would overflow");
-    }
-    for (int p = 0; p < n_parts; ++p)
-        for (int a = 0; a < 3; ++a)
-            REQUIRE(parts[p].core_lo[a] >= 0 && parts[p].core_lo[a] <= parts[p].core_hi[a] && parts[p].core_hi[a] <= lattice_dims[a], TL3D_E_INVALID,
-                    "part %d: core [%lld, %lld) on axis %d must be a range within the lattice's %lld voxels", p, (long long)parts[p].core_lo[a],
-                    (long long)parts[p].core_hi[a], a, (long long)lattice_dims[a]);
-    REQUIRE(with_rgb == 0 || with_rgb == with_verts, TL3D_E_INVALID, "rgb given in some parts only (%d of %d)", with_rgb, with_verts);
-    const bool rgb = with_rgb > 0;
-    REQUIRE((vert_cap == 0 || (out_xyz && (out_rgb || !rgb))) && (tri_cap == 0 || out_tri), TL3D_E_INVALID, "null output with a capacity");
-    {
-        const void *outs[4] = {out_xyz, rgb ? out_rgb : nullptr, out_key, out_tri};
-        const size_t out_b[4] = {(size_t)vert_cap * 12, (size_t)vert_cap * 3, (size_t)vert_cap * 8, (size_t)tri_cap * 12};
-        for (int p = 0; p < n_parts; ++p) {
-            const tl3d_mesh_part &m = parts[p];
-            const void *ins[4] = {m.xyz_hd, m.rgb_hd, m.key_hd, m.tri_hd};
-            const size_t in_b[4] = {(size_t)m.n_vert * 12, (size_t)m.n_vert * 3, (size_t)m.n_vert * 8, (size_t)m.n_tri * 12};
-            for (int o = 0; o < 4; ++o)
-                for (int i = 0; i < 4; ++i)
-                    REQUIRE(!ranges_overlap(outs[o], out_b[o], ins[i], in_b[i]), TL3D_E_INVALID, "an output aliases an input (part %d)", p);
-        }
-    }
-    REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
-    *out_n_vert = *out_n_tri = *out_n_twice = *out_n_unowned = 0;
-    if (n_parts == 0 || nv_tot == 0) return TL3D_OK;
-    TL3D_HIP(hipSetDevice(ctx->device));
-    int rc = mio_grow(ctx, 0, nv_tot, what);
-    if (!rc) rc = grow(&ctx->wm_vmap, &ctx->wm_verts, (size_t)nv_tot, what);
-    if (!rc) rc = grow(&ctx->wm_parts, &ctx->wm_parts_n, (size_t)n_parts + 1, what);
-    if (rc) return rc;
-    hipStream_t s = ctx->stream;
-    // the inputs: a device array is read where it is; the host arrays of a kind are uploaded into one temporary, part behind part
-    // (desc is declared in front of st: it is uploaded asynchronously, and st's destructor is what waits for the stream on every
-    // way out.  st holds at most 4 input temporaries and 4 output temporaries: exactly Staging's MAX.)
-    std::vector<WeldPart> desc((size_t)n_parts + 1);
-    Staging st(ctx);
-    {
-        const size_t unit[4] = {12, 3, 8, 12};
-        size_t host_b[4] = {0, 0, 0, 0};
-        std::vector<uint8_t> on_host((size_t)n_parts * 4, 0);
-        for (int p = 0; p < n_parts; ++p) {
-            const tl3d_mesh_part &m = parts[p];
-            const void *ins[4] = {m.xyz_hd, rgb ? m.rgb_hd : nullptr, m.key_hd, m.tri_hd};
-            const size_t in_b[4] = {(size_t)m.n_vert * 12, (size_t)m.n_vert * 3, (size_t)m.n_vert * 8, (size_t)m.n_tri * 12};
-            for (int k = 0; k < 4; ++k)
-                if (ins[k] && in_b[k] && !is_device_ptr(ins[k])) {
-                    on_host[(size_t)p * 4 + k] = 1;
-                    host_b[k] += in_b[k];
-                }
-        }
-        uint8_t *slab[4] = {nullptr, nullptr, nullptr, nullptr};
-        for (int k = 0; k < 4 && !rc; ++k)
-            if (host_b[k]) rc = st.scratch(host_b[k], &slab[k]);
-        if (rc) return rc;
-        size_t used[4] = {0, 0, 0, 0};
-        unsigned long long v0 = 0, t0 = 0;
-        for (int p = 0; p < n_parts; ++p) {
-            const tl3d_mesh_part &m = parts[p];
-            const void *ins[4] = {m.xyz_hd, rgb ? m.rgb_hd : nullptr, m.key_hd, m.tri_hd};
-            const size_t cnt[4] = {(size_t)m.n_vert, (size_t)m.n_vert, (size_t)m.n_vert, (size_t)m.n_tri};
-            for (int k = 0; k < 4; ++k)
-                if (on_host[(size_t)p * 4 + k]) {
-                    void *d = slab[k] + used[k];
-                    TL3D_HIP(hipMemcpyAsync(d, ins[k], cnt[k] * unit[k], hipMemcpyHostToDevice, s));
-                    used[k] += cnt[k] * unit[k];
-                    ins[k] = d;
-                }
-            WeldPart &w = desc[(size_t)p];
-            w.xyz = (const float *)ins[0];
-            w.rgb = (const uint8_t *)ins[1];
-            w.key = (const long long *)ins[2];
-            w.tri = (const unsigned *)ins[3];
-            w.v0 = v0;
-            w.t0 = t0;
-            for (int a = 0; a < 3; ++a) {
-                w.lo[a] = (long long)m.core_lo[a];
-                w.hi[a] = (long long)m.core_hi[a];
-            }
-            v0 += (unsigned long long)m.n_vert;
-            t0 += (unsigned long long)m.n_tri;
-        }
-        memset(&desc[(size_t)n_parts], 0, sizeof(WeldPart));
-        desc[(size_t)n_parts].v0 = v0;
-        desc[(size_t)n_parts].t0 = t0;
-        TL3D_HIP(hipMemcpyAsync(ctx->wm_parts, desc.data(), desc.size() * sizeof(WeldPart), hipMemcpyHostToDevice, s));
-    }
-    const long long lat[3] = {(long long)lattice_dims[0], (long long)lattice_dims[1], (long long)lattice_dims[2]};
-    const unsigned long long nv = (unsigned long long)nv_tot, nt = (unsigned long long)nt_tot;
-    // the validation pass: nothing is indexed, and no key is taken apart, before the host has seen its words
-    unsigned long long h[5] = {0, 0, 0, 0, 0};
-    TL3D_HIP(hipMemsetAsync(ctx->mio_info, 0, 8 * sizeof(unsigned long long), s));
-    rc = launch_wm_validate(s, ctx->wm_parts, n_parts, nv, nt, 3ull * (unsigned long long)nlat, ctx->mio_info);
-    if (rc) return rc;
-    TL3D_HIP(hipMemcpyAsync(h, ctx->mio_info, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    TL3D_HIP(hipStreamSynchronize(s));
-    REQUIRE(h[0] == 0, TL3D_E_INVALID, "%llu triangle indices out of range (the largest: %llu in part %llu, which has %lld vertices)", h[0],
-            h[2] & 0xffffffffull, h[2] >> 32, (long long)parts[h[2] >> 32].n_vert);
-    REQUIRE(h[1] == 0, TL3D_E_INVALID, "%llu keys outside [0, 3 * %llu lattice voxels)", h[1], (unsigned long long)nlat);
-    // the kept vertices
-    const int chunks = chunks_of(nv);
-    unsigned long long kept = 0;
-    rc = launch_wm_own_count(s, ctx->wm_parts, n_parts, nv, lat, ctx->mio_counts, ctx->mio_offsets);
-    if (rc) return rc;
-    TL3D_HIP(hipMemcpyAsync(&kept, ctx->mio_offsets + chunks, sizeof(kept), hipMemcpyDeviceToHost, s));
-    TL3D_HIP(hipStreamSynchronize(s));
-    *out_n_vert = (int64_t)kept;
-    *out_n_tri = nt_tot;
-    REQUIRE(kept < (1ull << 31), TL3D_E_CAPACITY, "%llu kept vertices: triangle indices need fewer than 2^31", kept);
-    if ((int64_t)kept > vert_cap || nt_tot > tri_cap)
-        return set_err(TL3D_E_CAPACITY, "need %llu vertices / %lld triangles, capacities %lld / %lld", kept, (long long)nt_tot, (long long)vert_cap,
-                       (long long)tri_cap);
-    float *oxyz = nullptr;
-    uint8_t *orgb = nullptr;
-    int64_t *okey = nullptr;
-    uint32_t *otri = nullptr;
-    rc = st.out(out_xyz, (size_t)kept * 12, &oxyz);
-    if (!rc && rgb) rc = st.out(out_rgb, (size_t)kept * 3, &orgb);
-    if (!rc && out_key) rc = st.out(out_key, (size_t)kept * 8, &okey);
-    if (!rc) rc = st.out(out_tri, (size_t)nt * 12, &otri);
-    const size_t slots = kt_slots((size_t)kept);           // the key table: a key per slot and, in the word beside it, the kept vertex's output index
-    if (!rc) rc = kt_reserve(ctx, slots, true, what);
-    if (rc) return rc;
-    rc = launch_wm_own_write(s, ctx->wm_parts, n_parts, nv, lat, ctx->mio_offsets, oxyz, orgb, (long long *)okey, kept, ctx->wm_vmap, ctx->kt_keys,
-                             ctx->kt_vals, slots, ctx->mio_info);
-    if (!rc) rc = launch_wm_resolve(s, ctx->wm_parts, n_parts, nt, ctx->wm_vmap, ctx->kt_keys, ctx->kt_vals, slots, otri, ctx->mio_info);
-    if (rc) return rc;
-    TL3D_HIP(hipMemcpyAsync(h, ctx->mio_info, sizeof(h), hipMemcpyDeviceToHost, s));
-    rc = st.finish(TL3D_OK, true);
-    if (rc) return rc;
-    *out_n_twice = (int64_t)h[3];
-    *out_n_unowned = (int64_t)h[4];
-    REQUIRE(h[3] == 0, TL3D_E_INVALID, "a vertex is owned by two block cores (%llu kept vertices repeat a key: the cores overlap)", h[3]);
-    REQUIRE(h[4] == 0, TL3D_E_INVALID, "a triangle references a vertex no block core owns (%llu corners: a halo is missing)", h[4]);
     return TL3D_OK;
 }
 

@@ -235,56 +235,14 @@ struct tl3d_grid_state {
     size_t mesh_blocks;                     // capacity of both, in entries (two per block)
     unsigned *mesh_first;
     size_t mesh_first_n;
-    // tl3d_mesh_components / tl3d_mesh_filter_components: union-find parents (= labels), triangles per label and new vertex ids
-    // (12 B per vertex).  None of it depends on the grid (the calls work without one); it lives here so that release_grid stays
-    // the one place that frees device scratch grown on demand.
-    unsigned *cc_parent, *cc_count, *cc_remap;
-    size_t cc_verts;                        // capacity of each, in vertices
-    // The 64-bit key table of the mesh calls (keytab.h): a key per slot and, for the callers that keep one,
-    // a 32-bit word beside it -- tl3d_mesh_simplify_clusters: cell keys of kt_slots(n_vert) slots, the word = the cluster's leader;
-    // tl3d_mesh_smooth_taubin: edge keys of kt_slots(3 n_tri) slots, no word; tl3d_mesh_weld_keyed: vertex keys of kt_slots(kept)
-    // slots, the word = the kept vertex's output index.  ONE table serves all three: every call fills the keys with 0xFF on the
-    // context's stream before its first insert (kt_reserve, tl3d_api.hip) and writes a word before it reads it, so no call reads
-    // what another left behind, and calls on one context run one behind the other.  Grid-independent like the cc_ scratch.
-    unsigned long long *kt_keys;
-    size_t kt_key_slots;                    // capacity, in slots
-    unsigned *kt_vals;
-    size_t kt_val_slots;
-    // tl3d_mesh_simplify_clusters: per vertex its slot in the key table and its cluster number, per cluster
-    // seven 64-bit sums (n, S, C), the triangle table (one index per slot, kt_slots(n_tri) slots), a class byte per triangle;
-    // tl3d_mesh_simplify_quadric alone grows the nine 128-bit quadric sums per cluster beside them.
-    // Grid-independent like the cc_ scratch, and here for the same reason.
-    unsigned *ms_slot, *ms_vmap;
-    unsigned long long *ms_acc;             // [7 per vertex]
-    size_t ms_verts, ms_acc_n;              // capacity of ms_slot / ms_vmap in vertices, of ms_acc in words
-    unsigned long long *ms_qacc;            // tl3d_mesh_simplify_quadric only: [18 per vertex], nine 128-bit sums as (lo, hi)
-    size_t ms_qacc_n;                       // in words
-    unsigned *ms_ttab;
-    size_t ms_tslots;
-    uint8_t *ms_flag;
-    size_t ms_tris;
-    // tl3d_mesh_smooth_taubin / tl3d_mesh_vertex_normals: per vertex a count (valence, or incident
-    // corners) and a fill cursor, the 64-bit row offsets, the rows themselves (2 E neighbours, or 3 n_tri triangle ids), the second
-    // position buffer of the steps, and the 64-bit chunk sums and offsets of the row scan.  Grid-independent like the cc_ scratch,
-    // and here for the same reason.
-    unsigned *adj_cnt, *adj_cursor;
-    size_t adj_verts;                       // capacity of both, in vertices
-    unsigned long long *adj_row;
-    size_t adj_rows;
-    unsigned *adj_list;
-    size_t adj_list_n;
-    float *adj_xyz;
-    size_t adj_xyz_n;                       // in floats
-    unsigned long long *adj_ccounts, *adj_coffs;
-    size_t adj_chunks;                      // capacity of both, in entries
-    // tl3d_mesh_weld_keyed: per input vertex its output index or NONE, the part descriptors.
-    // Grid-independent like the cc_ scratch, and here for the same reason.
-    unsigned *wm_vmap;
-    size_t wm_verts;
-    tl3d::WeldPart *wm_parts;
-    size_t wm_parts_n;
-    // What the mesh-in / mesh-out calls above share, none of it live across calls: counts and offsets per chunk of vertices /
-    // triangles, and the eight words their kernels report through, zeroed by each call before use:
+    // The device scratch of the mesh calls (api_mesh.hip) and of the calls on the uniform cell index (kernels_sor.hip,
+    // kernels_nearest.hip): the two grow-on-demand buffers every call carves its arrays from (scratch_carve, api_host.h; nothing
+    // in them is live across calls) and the fixed slab (CELL_SLAB_BYTES) of the cell-index calls' block partials.  None of it
+    // depends on the grid (the calls work without one): it lives here so that tl3d_detach_grid gives the memory back.
+    char *scratch[2];
+    size_t scratch_bytes[2];                // capacities
+    void *cg_slab;
+    // The eight report words of a mesh call's carve, zeroed by the call before its first kernel:
     //   word   tl3d_mesh_components / _filter_components       tl3d_mesh_simplify_clusters   tl3d_mesh_smooth_taubin / _vertex_normals
     //   [0]    largest triangle index (its low u32 word)       the same                      the same
     //   [1]    components                                      vertices without a cell       vertices out of range
@@ -295,16 +253,6 @@ struct tl3d_grid_state {
     //   [6]                                                    clusters clamped
     // tl3d_mesh_weld_keyed: [0] indices out of range, [1] keys out of range, [2] the largest offending (part << 32 | index),
     // [3] vertices owned twice, [4] unowned corners
-    unsigned *mio_counts;                   // [vertex chunks + 1][triangle chunks + 1]
-    unsigned long long *mio_offsets;
-    size_t mio_chunks;                      // capacity of both, in entries
-    unsigned long long *mio_info;           // [8]
-    // The calls on the uniform cell index (cellgrid.h) -- tl3d_statistical_outlier / tl3d_knn_mean_distance,
-    // tl3d_nearest_points / tl3d_nearest_triangles -- and tl3d_distance_summary: the block partials of their reductions (fixed size)
-    // and ONE buffer each call carves its cell tables and sorted points from (cell_carve), nothing in it live across calls.
-    // Grid-independent like the cc_ scratch, and here for the same reason.
-    void *cg_slab, *cg_buf;
-    size_t cg_bytes;                        // capacity of cg_buf
     // tl3d_set_block_core: the grid is one block of a lattice of lat[] voxels and emits only what its core (grid.clo / chi) owns
     bool has_core;
     long long lat[3];
@@ -654,7 +602,6 @@ void cell_grid_fit(const double mn[3], const double mx[3], double cell, CellGrid
 void launch_cell_count(hipStream_t s, const CellGrid &g, const float *xyz, long long n, unsigned *cnt);
 int launch_cell_scan(hipStream_t s, const unsigned *cnt, long long ncell, unsigned *chunk_sums, unsigned long long *chunk_off, unsigned *start);
 int cell_slab(tl3d_ctx *ctx);
-int cell_carve(tl3d_ctx *ctx, const size_t *bytes, int n, void **out);
 // outlier filter (kernels_sor.hip): the k-NN mean-distance stage alone (*mean_dev: n doubles, or null: carved with the call's scratch
 // and returned), and the whole filter, which thresholds it
 int sor_mean_distance(tl3d_ctx *ctx, const float *xyz_dev, long long n, int k, double cell, double **mean_dev);
