@@ -678,6 +678,14 @@ int tl3d_set_normal_smoothing(tl3d_ctx *ctx, int radius);
 /* tl3d_integrate collects up to 32 frames per update launch (the bricks they see are read and written once for all of them;
  * the grid is the same bit for bit).  on = 0: one frame per launch.  Default: on. */
 int tl3d_set_tsdf_pairing(tl3d_ctx *ctx, int on);
+/* The TSDF prep keeps what it derives from a frame's depth image alone (depth tiles, their pyramid, one valid pixel: functions
+ * of the image, the scale and the depth limits) with the frame's slot, and builds it again only after a new frame went into
+ * the slot or when one of those parameters differs: a frame fused a second time (another scan, another block of a blocked
+ * grid, tl3d_count_bricks followed by the fusion) skips that pass.  builds: per-frame builds so far; hits: look-ups that
+ * found the slot's tiles usable; bytes: device memory the tiles hold (about 0.95 MB per 1080 x 1920 slot, taken on first
+ * use).  Any of the three may be null; the pending batch is issued first (look-ups happen then).  With TL3D_TILE_CACHE=0 in the environment when the context is created every look-up
+ * is a miss (the tiles are built once per batch, as before the cache existed). */
+int tl3d_tile_cache_info(tl3d_ctx *ctx, uint64_t *builds, uint64_t *hits, uint64_t *bytes);
 int tl3d_get_stats(tl3d_ctx *ctx, tl3d_stats *out);
 int tl3d_reset_stats(tl3d_ctx *ctx);
 int tl3d_event_record(tl3d_ctx *ctx, int which /* 0 or 1 */);

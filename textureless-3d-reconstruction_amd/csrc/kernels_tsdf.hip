@@ -3,13 +3,16 @@
 // (oracle/tl3d_oracle.c: orc_tsdf_integrate) and both sides evaluate the same f32 sequence, so the integer
 // grid {sum of rint(tsdf*32767), weight} is bit-identical.
 //
-// tl3d_integrate collects frames into BATCHES of up to 32 (TL3D_TSDF_MAXBATCH).  Per batch, five launches; the per-frame
-// arguments (pose, depth image, scratch pointers) of all its frames sit in one descriptor array in device memory and
-// blockIdx.y / a bit index picks the frame:
+// tl3d_integrate collects frames into BATCHES of up to 32 (TL3D_TSDF_MAXBATCH).  The per-frame arguments (pose, depth image,
+// tile and scratch pointers) of all its frames sit in one descriptor array in device memory and blockIdx.y / a bit index picks
+// the frame.  Kernels 1 and 2 depend on the depth image, the scale and the depth limits only: their output is kept with the
+// frame's slot and they run only over the frames of the batch whose slot has none for these parameters (no launch if none):
 //   1. depth_tiles_kernel     (min, max, all-valid) of the valid scaled depth over 8x8-, 16x16- and 32x32-pixel tiles
-//                             (pyramid levels 0-2) of every frame, 4 B/pixel read; the 8x8 level once more as 8-B records
+//                             (pyramid levels 0-2) of a stale frame, 4 B/pixel read; the 8x8 level once more as 8-B records
 //                             for the update kernel's per-voxel test
-//   2. tile_pyramid_kernel    1 workgroup per frame: 2x2 reductions of level 2 up to a single tile; one valid pixel of the frame
+//   2. tile_pyramid_kernel    1 workgroup per stale frame: 2x2 reductions of level 2 up to a single tile; one valid pixel of the frame
+//  2b. batch_begin_kernel     1 workgroup per frame, every batch: the batch's resets (list cursors, ticket counters, histogram
+//                             bins), the frame's list of cells in view (pose-dependent), its valid pixel from the slot
 //   3. brick_cull_kernel      per frame, one lane per 8^3 brick (one wave per 4x4x4-brick cell) classifies it from <= 16
 //                             pyramid lookups:
 //        SKIP   outside the view, no valid depth under it, or more than trunc behind every surface it can see
@@ -78,7 +81,7 @@ static_assert(sizeof(FrameDesc) == 128, "FrameDesc: 16 of them travel as one ker
 // what all frames of a batch share
 struct BatchBufs {
     const FrameDesc *frames;             // [n_frames]
-    unsigned *hdr;                       // [0] length of the batch list (reset by the tiles kernel)
+    unsigned *hdr;                       // [0] length of the batch list (reset by batch_begin_kernel)
     unsigned *list;                      // bricks that at least one frame of the batch lists, in order of first listing
     unsigned *order;                     // the same bricks, dearest first (by the number of frames that list them): what the update walks
     unsigned *framemask;                 // [nbricks] bit f: frame f lists the brick; all zero between batches (the update re-arms it)
@@ -139,19 +142,17 @@ __device__ __forceinline__ void ld_depth4(const uint16_t *__restrict__ p, size_t
 // reduction of its own, 19 steps; the kernel's 33 M vector instructions per 32 frames were a sixth of the batch's -- and the batch is
 // bound by exactly those)  min / max over the VALID pixels: an invalid one enters as NaN, which v_min_f32 / v_max_f32
 // pass over.  No LDS, no workgroup barrier.
+// The tiles, the pyramid and the valid pixel are functions of the depth image, the scale and the depth limits alone: they live with
+// the frame's SLOT (Slot::tiles, tl3d_internal.h) and are built only for the frames of a batch whose slot holds none for these
+// parameters -- the STALE frames, by their index in the batch (blockIdx.y picks an entry of the list).
+struct StaleList { unsigned char idx[TL3D_TSDF_MAXBATCH]; };
 template <typename DT>
-__global__ __launch_bounds__(256) void depth_tiles_kernel(Cam cam, BatchBufs B, Pyramid py, int nrx, int nry) {
-    const DescPtr F = const_descs(B) + blockIdx.y;
+__global__ __launch_bounds__(256) void depth_tiles_kernel(Cam cam, BatchBufs B, Pyramid py, int nrx, int nry, StaleList stale) {
+    const DescPtr F = const_descs(B) + stale.idx[blockIdx.y];
     const TsdfConst c = desc_const(F);
     const DT *__restrict__ depth = static_cast<const DT *>(F->depth);
     float4 *__restrict__ tiles = F->tiles;
     float2 *__restrict__ vtile = F->vtile;
-    if (blockIdx.x == 0 && threadIdx.x < 2) F->counts[threadIdx.x] = 0u;        // reset the frame's list cursors
-    if (blockIdx.x == 0 && blockIdx.y == 0) {                                    // and the batch list's, the update's ticket counters, the ordering pass's bins
-        if (threadIdx.x == 2) B.hdr[0] = 0u;
-        if (threadIdx.x >= 64 && threadIdx.x < 64 + TICKET_GROUPS) B.hdr[HDR_TICKETS + 16u * (threadIdx.x - 64)] = 0u;
-        if (threadIdx.x >= 128) B.hdr[HDR_HIST + (threadIdx.x - 128)] = 0u;
-    }
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int q4 = lane & 7, rq = lane >> 3;
     const bool vec = (cam.W & 3) == 0;                              // rows are 16-B aligned
@@ -239,25 +240,34 @@ __global__ __launch_bounds__(256) void depth_tiles_kernel(Cam cam, BatchBufs B, 
     }
 }
 
-// ---- 2. pyramid: levels 3 .. from level 2 ------------------------------------------------------------------
-// Also finds ONE PIXEL OF THE FRAME THAT IS VALID (the top-left pixel of an all-valid tile; counts[VALID_PIXEL]): where the update
-// kernel sends the lanes whose depth value cannot matter (below).
-constexpr int VALID_PIXEL = 32;          // word of a frame's counts block
+constexpr int VALID_PIXEL = 32;          // word of a frame's counts block: ONE PIXEL OF THE FRAME THAT IS VALID (tile_pyramid_kernel)
 constexpr int CELL_COUNT = 48;           // word of a frame's counts block: length of the frame's cell list
 __device__ __forceinline__ bool sphere_in_view(const Frustum &fr, float x, float y, float z, float rad) {
     return (z + rad > 0.0f) && (fr.lx * x + fr.lz * z >= -rad) && (fr.rx * x + fr.rz * z >= -rad) &&
            (fr.ty * y + fr.tz * z >= -rad) && (fr.by * y + fr.bz * z >= -rad);
 }
 
-// ... and the frame's CELL LIST: the 4x4x4-brick cells whose bounding sphere meets the view (one in five on the headline orbit), so
-// that the brick classification starts waves only for those.
-__global__ __launch_bounds__(256) void tile_pyramid_kernel(Cam cam, Grid g, Frustum fr, Pyramid py, BatchBufs B) {
-    float4 *__restrict__ tiles = const_descs(B)[blockIdx.x].tiles;
-    __shared__ unsigned s_found, s_ncell;
-    if (threadIdx.x == 0) { s_found = 0xffffffffu; s_ncell = 0u; }
+// The valid pixel is kept in the first word of the float4 behind the pyramid's last level (the slot's buffer has that one more).
+__device__ __forceinline__ int pyramid_total(const Pyramid &py) { return py.off[py.nlev - 1] + py.ntx[py.nlev - 1] * py.nty[py.nlev - 1]; }
+
+// ---- 2b. what every batch does for every frame, cached tiles or not: 1 workgroup per frame --------------------------------------
+// The RESETS of the batch (the frame's list cursors; in workgroup 0 the batch list's length, the update's ticket counters and the
+// ordering pass's bins): ahead of the brick classification in stream order, whether or not a tile build ran.  The frame's CELL
+// LIST: the 4x4x4-brick cells whose bounding sphere meets the view (one in five on the headline orbit), so that the brick
+// classification starts waves only for those -- it depends on the pose.  And the slot's valid pixel, copied to where the update
+// kernel reads it.
+__global__ __launch_bounds__(256) void batch_begin_kernel(Grid g, Frustum fr, Pyramid py, BatchBufs B) {
+    __shared__ unsigned s_ncell;
+    const DescPtr F = const_descs(B) + blockIdx.x;
+    if (threadIdx.x < 2) F->counts[threadIdx.x] = 0u;                            // reset the frame's list cursors
+    if (blockIdx.x == 0) {                                                       // and the batch list's, the update's ticket counters, the ordering pass's bins
+        if (threadIdx.x == 2) B.hdr[0] = 0u;
+        if (threadIdx.x >= 64 && threadIdx.x < 64 + TICKET_GROUPS) B.hdr[HDR_TICKETS + 16u * (threadIdx.x - 64)] = 0u;
+        if (threadIdx.x >= 128) B.hdr[HDR_HIST + (threadIdx.x - 128)] = 0u;
+    }
+    if (threadIdx.x == 0) s_ncell = 0u;
     __syncthreads();
     {
-        const DescPtr F = const_descs(B) + blockIdx.x;
         const PoseF pose = desc_pose(F);
         unsigned *__restrict__ cells = F->cells;
         const int ncx = (g.nbx + 3) >> 2, ncy = (g.nby + 3) >> 2, ncz = (g.nbz + 3) >> 2;
@@ -281,8 +291,23 @@ __global__ __launch_bounds__(256) void tile_pyramid_kernel(Cam cam, Grid g, Frus
             if (in) cells[base + __popcll(m & ((1ull << (threadIdx.x & 63)) - 1ull))] = (unsigned)cell;
         }
         __syncthreads();
-        if (threadIdx.x == 0) F->counts[CELL_COUNT] = s_ncell;
+        if (threadIdx.x == 0) {
+            F->counts[CELL_COUNT] = s_ncell;
+            const unsigned vp = *reinterpret_cast<const unsigned *>(F->tiles + pyramid_total(py));
+            F->counts[VALID_PIXEL] = vp;
+            const_cast<FrameDesc *>(B.frames)[blockIdx.x].valid_pix = vp;      // (the update kernel of this batch reads it as a scalar)
+        }
     }
+}
+
+// ---- 2. pyramid: levels 3 .. from level 2; 1 workgroup per STALE frame ----------------------------------------------------------
+// Also finds ONE PIXEL OF THE FRAME THAT IS VALID (the top-left pixel of an all-valid tile): where the update kernel sends the
+// lanes whose depth value cannot matter (below).
+__global__ __launch_bounds__(256) void tile_pyramid_kernel(Cam cam, Pyramid py, BatchBufs B, StaleList stale) {
+    float4 *__restrict__ tiles = const_descs(B)[stale.idx[blockIdx.x]].tiles;
+    __shared__ unsigned s_found;
+    if (threadIdx.x == 0) s_found = 0xffffffffu;
+    __syncthreads();
     for (int L = min(2, py.nlev - 1); L >= 0; L -= 2) {           // 32-pixel tiles first; only a frame full of holes needs the 8-pixel ones
         const int n = py.ntx[L] * py.nty[L];
         for (int i = threadIdx.x; i < n; i += 256)
@@ -297,8 +322,7 @@ __global__ __launch_bounds__(256) void tile_pyramid_kernel(Cam cam, Grid g, Frus
     }
     if (threadIdx.x == 0) {
         const unsigned vp = s_found == 0xffffffffu ? 0u : s_found;
-        const_descs(B)[blockIdx.x].counts[VALID_PIXEL] = vp;
-        const_cast<FrameDesc *>(B.frames)[blockIdx.x].valid_pix = vp;      // (the update kernel of this batch reads it as a scalar)
+        *reinterpret_cast<unsigned *>(tiles + pyramid_total(py)) = vp;     // with the slot: batch_begin_kernel hands it to each batch
     }
     for (int L = 3; L < py.nlev; ++L) {
         const int n = py.ntx[L] * py.nty[L];
@@ -1238,12 +1262,12 @@ static size_t pyramid_tiles(const Pyramid &p) { return (size_t)p.off[p.nlev - 1]
 static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // Scratch of ONE batch in flight (the context keeps two and alternates):
-//   [descriptors (max_frames)] [header 256 B] [batch list] [frame masks] then per frame [counts 256 B] [tile pyramid] [list] [sub-brick masks] [8-B level-0 tiles]
+//   [descriptors (max_frames)] [header 256 B] [batch list] [frame masks] then per frame [counts 256 B] [list] [sub-brick masks] [cell list]
+// (the tile pyramid and the 8-B level-0 tiles of a frame live with its slot: tsdf_tile_cache_bytes)
 struct BatchLayout {
-    size_t off_desc, off_hdr, off_list, off_order, off_mask, off_frames, per_frame, f_counts, f_tiles, f_list, f_sub, f_vt, f_cells, total;
+    size_t off_desc, off_hdr, off_list, off_order, off_mask, off_frames, per_frame, f_counts, f_list, f_sub, f_cells, total;
 };
 static BatchLayout batch_layout(const Cam &cam, const Grid &g, int max_frames) {
-    const Pyramid p = make_pyramid(cam);
     const size_t nbricks = (size_t)g.nbx * g.nby * g.nbz;
     BatchLayout L;
     L.off_desc = 0;
@@ -1253,11 +1277,9 @@ static BatchLayout batch_layout(const Cam &cam, const Grid &g, int max_frames) {
     L.off_mask = L.off_order + up256((nbricks + 64) * sizeof(unsigned));
     L.off_frames = L.off_mask + up256(nbricks * sizeof(unsigned));
     L.f_counts = 0;
-    L.f_tiles = 256;
-    L.f_list = L.f_tiles + up256(pyramid_tiles(p) * sizeof(float4));
+    L.f_list = 256;
     L.f_sub = L.f_list + up256((nbricks + 64) * sizeof(unsigned));
-    L.f_vt = L.f_sub + up256(nbricks * sizeof(unsigned short));
-    L.f_cells = L.f_vt + up256((size_t)p.ntx[0] * p.nty[0] * sizeof(float2));
+    L.f_cells = L.f_sub + up256(nbricks * sizeof(unsigned short));
     const size_t ncells = (size_t)((g.nbx + 3) / 4) * ((g.nby + 3) / 4) * ((g.nbz + 3) / 4);
     L.per_frame = L.f_cells + up256((ncells + 4) * sizeof(unsigned));
     L.total = L.off_frames + L.per_frame * (size_t)max_frames;
@@ -1265,6 +1287,15 @@ static BatchLayout batch_layout(const Cam &cam, const Grid &g, int max_frames) {
 }
 
 size_t tsdf_batch_scratch_bytes(const Cam &cam, const Grid &g, int max_frames) { return batch_layout(cam, g, max_frames).total; }
+
+// One slot's tile buffer: [tile pyramid, float4 per tile, + one float4 whose first word is the valid pixel] [8-B level-0 tiles at *vtile_off]
+size_t tsdf_tile_cache_bytes(const Cam &cam, size_t *vtile_off, size_t *vpix_off) {
+    const Pyramid p = make_pyramid(cam);
+    const size_t off = up256((pyramid_tiles(p) + 1) * sizeof(float4));
+    if (vtile_off) *vtile_off = off;
+    if (vpix_off) *vpix_off = pyramid_tiles(p) * sizeof(float4);
+    return off + up256((size_t)p.ntx[0] * p.nty[0] * sizeof(float2));
+}
 
 // bytes of a batch scratch that must be zero before its first use (the frame masks; the update kernel re-arms them)
 void tsdf_batch_scratch_zero_range(const Cam &cam, const Grid &g, int max_frames, size_t *off, size_t *bytes) {
@@ -1295,12 +1326,17 @@ static BatchBufs batch_bufs(const BatchLayout &L, void *scratch, int n) {
     return B;
 }
 
-// The whole prep of a batch of n frames (one depth kind) on stream s: descriptor upload, depth tiles, pyramid, brick
-// classification, sub-brick masks.  `scratch` is a batch scratch of at least n frames (tsdf_batch_scratch_bytes).
+// The whole prep of a batch of n frames (one depth kind) on stream s: descriptor upload, depth tiles and pyramid of the n_stale
+// frames stale[] (indices into the batch; the others' slots hold them already), resets + cell lists, brick classification,
+// sub-brick masks.  tiles[i]: frame i's slot buffer (tsdf_tile_cache_bytes; frames of one slot share it and at most one of them is
+// stale).  `scratch` is a batch scratch of at least n frames (tsdf_batch_scratch_bytes).
 int launch_tsdf_prepare(hipStream_t s, const Cam &cam, const Grid &g, int n, int max_frames, const PoseF *p, const Frustum &fr,
                         const void *const *depth, bool depth_u16, const float *scale, float mind, float maxd, void *scratch, unsigned *free_cnt,
-                        bool classify_only) {
+                        void *const *tiles, const unsigned char *stale, int n_stale, bool classify_only) {
     if (n < 1 || n > max_frames || n > TL3D_TSDF_MAXBATCH) return set_err(TL3D_E_INVALID, "bad batch size %d", n);
+    if (n_stale < 0 || n_stale > n) return set_err(TL3D_E_INVALID, "bad stale count %d", n_stale);
+    size_t vt_off = 0;
+    (void)tsdf_tile_cache_bytes(cam, &vt_off, nullptr);
     const BatchLayout L = batch_layout(cam, g, max_frames);
     const Pyramid py = make_pyramid(cam);
     char *base = static_cast<char *>(scratch);
@@ -1312,10 +1348,10 @@ int launch_tsdf_prepare(hipStream_t s, const Cam &cam, const Grid &g, int n, int
         d[i].c = make_const(cam, scale[i], mind, maxd);
         d[i].depth = depth[i];
         d[i].counts = reinterpret_cast<unsigned *>(fb + L.f_counts);
-        d[i].tiles = reinterpret_cast<float4 *>(fb + L.f_tiles);
+        d[i].tiles = reinterpret_cast<float4 *>(tiles[i]);
         d[i].list = reinterpret_cast<unsigned *>(fb + L.f_list);
         d[i].sub = reinterpret_cast<unsigned short *>(fb + L.f_sub);
-        d[i].vtile = reinterpret_cast<float2 *>(fb + L.f_vt);
+        d[i].vtile = reinterpret_cast<float2 *>(static_cast<char *>(tiles[i]) + vt_off);
         d[i].cells = reinterpret_cast<unsigned *>(fb + L.f_cells);
     }
     for (int i0 = 0; i0 < n; i0 += 16) {
@@ -1329,12 +1365,22 @@ int launch_tsdf_prepare(hipStream_t s, const Cam &cam, const Grid &g, int n, int
     const BatchBufs B = batch_bufs(L, scratch, n);
     const int nrx = (cam.W + REGION - 1) / REGION, nry = (cam.H + REGION - 1) / REGION;
     const int nreg = nrx * nry;
-    if (depth_u16)
-        hipLaunchKernelGGL(depth_tiles_kernel<uint16_t>, dim3((nreg + 3) / 4 < 512 ? (nreg + 3) / 4 : 512, n), dim3(256), 0, s, cam, B, py, nrx, nry);
-    else
-        hipLaunchKernelGGL(depth_tiles_kernel<float>, dim3((nreg + 3) / 4 < 512 ? (nreg + 3) / 4 : 512, n), dim3(256), 0, s, cam, B, py, nrx, nry);
-    TL3D_HIP(hipGetLastError());
-    hipLaunchKernelGGL(tile_pyramid_kernel, dim3(n), dim3(256), 0, s, cam, g, fr, py, B);
+    if (n_stale > 0) {                                   // the build: only over the frames whose slot has no tiles for these parameters
+        StaleList sl;
+        memset(&sl, 0, sizeof(sl));
+        for (int i = 0; i < n_stale; ++i) {
+            if (stale[i] >= n) return set_err(TL3D_E_INVALID, "bad stale index %d", (int)stale[i]);
+            sl.idx[i] = stale[i];
+        }
+        if (depth_u16)
+            hipLaunchKernelGGL(depth_tiles_kernel<uint16_t>, dim3((nreg + 3) / 4 < 512 ? (nreg + 3) / 4 : 512, n_stale), dim3(256), 0, s, cam, B, py, nrx, nry, sl);
+        else
+            hipLaunchKernelGGL(depth_tiles_kernel<float>, dim3((nreg + 3) / 4 < 512 ? (nreg + 3) / 4 : 512, n_stale), dim3(256), 0, s, cam, B, py, nrx, nry, sl);
+        TL3D_HIP(hipGetLastError());
+        hipLaunchKernelGGL(tile_pyramid_kernel, dim3(n_stale), dim3(256), 0, s, cam, py, B, sl);
+        TL3D_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(batch_begin_kernel, dim3(n), dim3(256), 0, s, g, fr, py, B);      // (always: resets, cell lists, valid pixels)
     TL3D_HIP(hipGetLastError());
     const int ncells = ((g.nbx + 3) / 4) * ((g.nby + 3) / 4) * ((g.nbz + 3) / 4);
     const int nquad = (ncells + 3) / 4;                 // the cells in view are known only on the device: a fixed grid strides over each frame's list

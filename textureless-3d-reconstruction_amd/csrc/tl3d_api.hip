@@ -314,6 +314,7 @@ static void release_grid(tl3d_ctx *ctx) {
     for (int h = 0; h < TSDF_SCRATCHES; ++h)
         if (gs.ev_upd[h]) (void)hipEventDestroy(gs.ev_upd[h]);      // (build_grid creates them anew)
     memset(&gs, 0, sizeof(gs));
+    ctx->tc_done_before = ctx->tsdf_batch_no;           // (the caller has waited: no batch still reads a slot's tiles)
     ctx->grid_epoch++;
     ctx->cfg.channels = 0;
     for (int i = 0; i < 3; ++i) ctx->cfg.voxel_offset[i] = 0;
@@ -498,14 +499,22 @@ int tl3d_create(const tl3d_config *cfg, int device, tl3d_ctx **out) {
     memset(ctx, 0, sizeof(*ctx));
     ctx->cfg = *cfg;
     ctx->device = device;
+    {   // the per-slot TSDF tile cache is a product feature with an off switch for A/B runs (every look-up a miss): read here, once
+        const char *v = getenv("TL3D_TILE_CACHE");
+        ctx->tile_cache = !(v && atoi(v) == 0);
+    }
     ctx->slots = new (std::nothrow) Slot[cfg->n_slots];
     if (!ctx->slots) { delete ctx; return set_err(TL3D_E_NOMEM, "host allocation failed"); }
     {
         const size_t npx = (size_t)cfg->width * cfg->height;
         const size_t npm = pm_pixels(cfg->width, cfg->height);      // normal maps and averaged depth: phase-major rows of 4 * ceil(W / 4) entries
-        const size_t bytes[5] = {npx * sizeof(float), npx * sizeof(uint16_t), npx * 3, npm * sizeof(float4), npm * sizeof(float)};
-        FramePool *pools[5] = {&ctx->pool_depth, &ctx->pool_u16, &ctx->pool_bgr, &ctx->pool_nmap, &ctx->pool_sdepth};
-        for (int k = 0; k < 5; ++k) {
+        Cam tc;
+        memset(&tc, 0, sizeof(tc));
+        tc.W = cfg->width; tc.H = cfg->height;
+        const size_t bytes[6] = {npx * sizeof(float), npx * sizeof(uint16_t), npx * 3, npm * sizeof(float4), npm * sizeof(float),
+                                 tsdf_tile_cache_bytes(tc, nullptr, nullptr)};      // (the TSDF tile cache: Slot::tiles)
+        FramePool *pools[6] = {&ctx->pool_depth, &ctx->pool_u16, &ctx->pool_bgr, &ctx->pool_nmap, &ctx->pool_sdepth, &ctx->pool_tiles};
+        for (int k = 0; k < 6; ++k) {
             FramePool &fp = *pools[k];
             fp.block = (bytes[k] + 16 + 255) & ~(size_t)255;      // 16 B of slack: a pixel's 3 colour bytes are read as one 4-byte word
             fp.remaining = cfg->n_slots;
@@ -671,6 +680,7 @@ int tl3d_destroy(tl3d_ctx *ctx) {
     pool_release(ctx->pool_bgr);
     pool_release(ctx->pool_nmap);
     pool_release(ctx->pool_sdepth);
+    pool_release(ctx->pool_tiles);
     for (int q = 0; q < 4; ++q)
         if (ctx->prep_stream[q]) (void)hipStreamSynchronize(ctx->prep_stream[q]);
     release_grid(ctx);
@@ -729,6 +739,7 @@ int tl3d_sync(tl3d_ctx *ctx) {
         if (ctx->icp_lanes[l].stream) TL3D_HIP(hipStreamSynchronize(ctx->icp_lanes[l].stream));
     if (ctx->icp_batch.stream) TL3D_HIP(hipStreamSynchronize(ctx->icp_batch.stream));
     TL3D_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->tc_done_before = ctx->tsdf_batch_no;
     if (ctx->bp_async_pending && ctx->bp_state) {
         ctx->bp_async_pending = false;
         unsigned long long err = 0;
@@ -786,6 +797,7 @@ static int upload_impl(tl3d_ctx *ctx, int slot, const void *depth_hd, int depth_
     s.loaded = true;
     s.has_normals = false;
     s.smooth_radius = 0;                                 // (the averaged depth belongs to the previous frame of this slot)
+    s.tc_built = s.tc_read = false;                      // (so do the TSDF tiles; their readers are ahead of this upload on the main stream)
     if (!s.ev_upload) TL3D_HIP(hipEventCreateWithFlags(&s.ev_upload, hipEventDisableTiming));
     TL3D_HIP(hipEventRecord(s.ev_upload, ctx->stream));       // the prep stream waits on this, not on the whole main stream
     // pageable host sources are consumed before hipMemcpyAsync returns only for small copies; make the hand-over explicit
@@ -1062,6 +1074,74 @@ int tl3d_frame_bounds(tl3d_ctx *ctx, int slot, const double R[9], const double t
     return tl3d_frames_bounds(ctx, 1, &s, R, t, &scale, flags, subsample, min_depth, max_depth, out_min, out_max);
 }
 
+// ------------------------------------------------------------------------------------------- TSDF tile cache
+// every batch numbered b or lower has left the device: the host has waited since (tc_done_before), or the batch that is being
+// issued waits for the scratch of batch (its number - TSDF_SCRATCHES) and every update before that one is ahead of it
+static bool batch_known_complete(const tl3d_ctx *ctx, unsigned b) {
+    return (int)(b - ctx->tc_done_before) < 0 || ctx->tsdf_batch_no - b >= (unsigned)TSDF_SCRATCHES;
+}
+
+// The tile buffers of the n frames of one prep chain that is about to be issued on stream ps as batch number `batch`, and which of
+// the frames must build theirs (stale[]: indices into the chain, one per slot).  A slot's tiles serve when the cache is on,
+// they are built and their key (scale bits, depth limits) is the chain's; frames of one slot share one build (the caller has
+// cut the chain where a slot would need two keys).  Orders ps behind what it must not overtake (the table beside
+// flush_updates); ps == the main stream needs nothing: every update is on it and has waited for its own prep chain.
+static int tile_cache_lookup(tl3d_ctx *ctx, hipStream_t ps, unsigned batch, int n, const int *slot_ids, const float *scales, float mind, float maxd,
+                             void **tiles, unsigned char *stale, int *n_stale) {
+    const bool side = ps != ctx->stream;
+    unsigned waited_prep = 0, waited_upd = 0;            // bit h: ps already waits for ev_prep[h] / ev_upd[h]
+    size_t vt_off = 0, vp_off = 0;
+    (void)tsdf_tile_cache_bytes(ctx->cam, &vt_off, &vp_off);
+    *n_stale = 0;
+    for (int i = 0; i < n; ++i) {
+        Slot &s = ctx->slots[slot_ids[i]];
+        if (!s.tiles) {
+            char *p = (char *)pool_take(ctx->pool_tiles);
+            if (!p) return set_err(TL3D_E_NOMEM, "tile cache alloc failed");
+            s.tiles = (float4 *)p;
+            s.vtile = (float2 *)(p + vt_off);
+            s.vpix = (unsigned *)(p + vp_off);            // first word of the float4 behind the pyramid's last level
+            s.tc_built = s.tc_read = false;
+        }
+        tiles[i] = s.tiles;
+        bool shared = false;
+        for (int j = 0; j < i && !shared; ++j) shared = slot_ids[j] == slot_ids[i];
+        if (shared) { ctx->tc_hits++; continue; }
+        uint32_t bits;
+        memcpy(&bits, &scales[i], sizeof(bits));
+        if (ctx->tile_cache && s.tc_built && s.tc_scale_bits == bits && s.tc_mind == mind && s.tc_maxd == maxd) {
+            ctx->tc_hits++;
+            // built by a batch on another prep stream that may still be at it: behind that chain
+            if (side && !batch_known_complete(ctx, s.tc_build_batch) && ctx->prep_stream[s.tc_build_batch % (unsigned)ctx->n_prep_streams] != ps) {
+                const unsigned h = s.tc_build_batch % (unsigned)TSDF_SCRATCHES;
+                if (!((waited_prep >> h) & 1u)) TL3D_HIP(hipStreamWaitEvent(ps, ctx->ev_prep[h], 0));
+                waited_prep |= 1u << h;
+            }
+        } else {
+            // a rebuild overwrites what the chain and the update of the last reader may still read: behind that batch's update
+            // (an upload since then is ordered already: it sits behind every update, and ps waits for it)
+            if (side && s.tc_read && !batch_known_complete(ctx, s.tc_reader_batch)) {
+                const unsigned h = s.tc_reader_batch % (unsigned)TSDF_SCRATCHES;
+                if (ctx->upd_recorded[h] && !((waited_upd >> h) & 1u)) TL3D_HIP(hipStreamWaitEvent(ps, ctx->ev_upd[h], 0));
+                waited_upd |= 1u << h;
+            }
+            stale[(*n_stale)++] = (unsigned char)i;
+            s.tc_built = true;
+            s.tc_scale_bits = bits; s.tc_mind = mind; s.tc_maxd = maxd;
+            s.tc_build_batch = batch;
+            ctx->tc_builds++;
+        }
+        s.tc_read = true;
+        s.tc_reader_batch = batch;
+    }
+    return TL3D_OK;
+}
+// a chain that was not issued (or not completely): its builds did not happen
+static void tile_cache_forget(tl3d_ctx *ctx, int n, const int *slot_ids, const unsigned char *stale, int n_stale) {
+    (void)n;
+    for (int k = 0; k < n_stale; ++k) ctx->slots[slot_ids[stale[k]]].tc_built = false;
+}
+
 // ------------------------------------------------------------------------------------------- occupancy of a planned grid
 // Which bricks of a grid (geometry only: no records, no pools) a fusion of these frames WOULD give records to: the TSDF
 // classification of every frame (tiles, pyramid, brick classes: the update's own prep chain, sub-brick masks and update left out)
@@ -1105,19 +1185,36 @@ int tl3d_count_bricks(tl3d_ctx *ctx, const tl3d_config *cfg, int n_frames, const
         tsdf_batch_scratch_zero_range(ctx->cam, g, batch, &zoff, &zbytes);
         TL3D_HIP(hipMemsetAsync(free_cnt, 0, nbr * sizeof(unsigned), ctx->stream));
         const Frustum fr = make_frustum(ctx->cam);
-        for (int i0 = 0; i0 < n_frames; i0 += batch) {
-            const int m = n_frames - i0 < batch ? n_frames - i0 : batch;
+        // The chains run on the main stream, behind every update issued so far: the tiles they find are complete, the ones they
+        // build overwrite nothing a batch still reads, and the call ends with a wait for the stream -- numbered as the last issued
+        // batch they count as complete from then on.
+        for (int i0 = 0, m = 0; i0 < n_frames; i0 += m) {
             PoseF poses[TL3D_TSDF_MAXBATCH];
             const void *depths[TL3D_TSDF_MAXBATCH];
             float sc[TL3D_TSDF_MAXBATCH];
-            for (int j = 0; j < m; ++j) {
-                poses[j] = make_pose_f(R + (size_t)9 * (i0 + j), t + (size_t)3 * (i0 + j));
-                depths[j] = ctx->slots[slots[i0 + j]].depth;
-                sc[j] = (float)(scales ? scales[i0 + j] : 1.0);
+            int ids[TL3D_TSDF_MAXBATCH];
+            for (m = 0; m < batch && i0 + m < n_frames; ++m) {
+                const float scj = (float)(scales ? scales[i0 + m] : 1.0);
+                bool cut = false;                            // one slot at two scales: two sets of tiles, two chains
+                for (int j = 0; j < m && !cut; ++j) cut = ids[j] == slots[i0 + m] && memcmp(&sc[j], &scj, sizeof(float)) != 0;
+                if (cut) break;
+                poses[m] = make_pose_f(R + (size_t)9 * (i0 + m), t + (size_t)3 * (i0 + m));
+                depths[m] = ctx->slots[slots[i0 + m]].depth;
+                sc[m] = scj;
+                ids[m] = slots[i0 + m];
             }
-            TL3D_HIP(hipMemsetAsync((char *)scratch + zoff, 0, zbytes, ctx->stream));    // (no update re-arms the frame masks)
-            rc = launch_tsdf_prepare(ctx->stream, ctx->cam, g, m, batch, poses, fr, depths, false, sc, mind, maxd, scratch, free_cnt, true);
-            if (rc) return rc;
+            void *tiles[TL3D_TSDF_MAXBATCH];
+            unsigned char stale[TL3D_TSDF_MAXBATCH];
+            int n_stale = 0;
+            rc = tile_cache_lookup(ctx, ctx->stream, ctx->tsdf_batch_no - 1u, m, ids, sc, mind, maxd, tiles, stale, &n_stale);
+            if (!rc && hipMemsetAsync((char *)scratch + zoff, 0, zbytes, ctx->stream) != hipSuccess) rc = set_err(TL3D_E_HIP, "memset failed");    // (no update re-arms the frame masks)
+            if (!rc) rc = launch_tsdf_prepare(ctx->stream, ctx->cam, g, m, batch, poses, fr, depths, false, sc, mind, maxd, scratch, free_cnt, tiles, stale, n_stale, true);
+            if (rc) {
+                tile_cache_forget(ctx, m, ids, stale, n_stale);
+                (void)hipStreamSynchronize(ctx->stream);
+                ctx->tc_done_before = ctx->tsdf_batch_no;
+                return rc;
+            }
         }
     }
     if ((cfg->channels & TL3D_CH_CENTROID) && centroid_subsample >= 1) {
@@ -1133,6 +1230,7 @@ int tl3d_count_bricks(tl3d_ctx *ctx, const tl3d_config *cfg, int n_frames, const
     unsigned cur[4] = {0, 0, 0, 0};
     TL3D_HIP(hipMemcpyAsync(cur, g.cursors, sizeof(cur), hipMemcpyDeviceToHost, ctx->stream));
     TL3D_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->tc_done_before = ctx->tsdf_batch_no;
     *bricks_tsdf = (int64_t)(cur[0] < nbr ? cur[0] : nbr);
     *bricks_centroid = (int64_t)(cur[2] < nbr ? cur[2] : nbr);
     return TL3D_OK;
@@ -1255,6 +1353,20 @@ static int flush_centroid(tl3d_ctx *ctx) {
     return TL3D_OK;
 }
 
+// Who waits for whom around a slot's TSDF tiles (Slot::tiles; b = this batch's number, h = b % TSDF_SCRATCHES, ps = its prep stream):
+//   producer                                   event                      consumer
+//   upload / ray cast into the slot (main;     Slot::ev_upload            the build of batch b on ps (as the depth image itself)
+//     behind every earlier update, so behind
+//     every earlier reader of the tiles)
+//   update of batch b - TSDF_SCRATCHES (main;  ev_upd[h]                  everything of batch b on ps: covers every reader and
+//     it waited for that batch's chain)          (the scratch-reuse wait)   builder numbered b - TSDF_SCRATCHES or lower
+//   update of reader batch r, b - 3 <= r < b   ev_upd[r % TSDF_SCRATCHES] a REBUILD without an upload (key change, cache off) on ps;
+//     (last batch to read the slot's tiles)                                 never the latest update unless it is that reader
+//   build in batch r, b - 3 <= r < b, on       ev_prep[r % TSDF_SCRATCHES] a batch on ps that finds those tiles (hit); none if
+//     another prep stream                                                   the host has waited since (tc_done_before)
+//   chain of batch b (ps)                      ev_prep[h]                 update of batch b (main)
+//   tl3d_count_bricks: chains on the main stream, then a wait for it       every later batch (counted complete: tc_done_before)
+// A slot twice in one batch with one key: one build, shared.  With two keys the batch is cut in front of the second (tl3d_integrate).
 static int flush_updates(tl3d_ctx *ctx) {
     {
         const int crc = flush_centroid(ctx);
@@ -1273,6 +1385,7 @@ static int flush_updates(tl3d_ctx *ctx) {
     PoseF poses[TL3D_TSDF_MAXBATCH];
     const void *depths[TL3D_TSDF_MAXBATCH];
     float scales[TL3D_TSDF_MAXBATCH];
+    int ids[TL3D_TSDF_MAXBATCH];
     for (int i = 0; i < n; ++i) {
         const tl3d_ctx::PendingUpdate &w = ctx->pend[i];
         const Slot &ws = ctx->slots[w.slot];
@@ -1280,13 +1393,22 @@ static int flush_updates(tl3d_ctx *ctx) {
         poses[i] = w.pose;
         depths[i] = u16 ? (const void *)ws.depth_u16 : (const void *)ws.depth;
         scales[i] = w.scale;
+        ids[i] = w.slot;
     }
     if (ps != ctx->stream) {
         if (ctx->upd_recorded[half]) TL3D_HIP(hipStreamWaitEvent(ps, ctx->ev_upd[half], 0));
         if (ctx->ev_free_recorded) TL3D_HIP(hipStreamWaitEvent(ps, ctx->ev_free, 0));      // clears / folds of the free-space counters
     }
-    int rc = launch_tsdf_prepare(ps, ctx->cam, ctx->grid, n, ctx->tsdf_batch, poses, fr, depths, u16, scales, mind, maxd, ctx->tsdf_scratch[half], ctx->free_cnt);
-    if (rc) return rc;
+    void *tiles[TL3D_TSDF_MAXBATCH];
+    unsigned char stale[TL3D_TSDF_MAXBATCH];
+    int n_stale = 0;
+    int rc = tile_cache_lookup(ctx, ps, ctx->tsdf_batch_no, n, ids, scales, mind, maxd, tiles, stale, &n_stale);
+    if (!rc) rc = launch_tsdf_prepare(ps, ctx->cam, ctx->grid, n, ctx->tsdf_batch, poses, fr, depths, u16, scales, mind, maxd, ctx->tsdf_scratch[half], ctx->free_cnt,
+                                      tiles, stale, n_stale);
+    if (rc) {
+        tile_cache_forget(ctx, n, ids, stale, n_stale);
+        return rc;
+    }
     if (ps != ctx->stream) {
         TL3D_HIP(hipEventRecord(ctx->ev_prep[half], ps));
         TL3D_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_prep[half], 0));
@@ -1332,10 +1454,25 @@ int tl3d_integrate(tl3d_ctx *ctx, int slot, const double R[9], const double t[3]
     // The frame joins the pending batch (one depth kind per batch); the batch goes out when it is full, or when any call needs
     // the grid, a slot, a sync or a time stamp (flush_updates).
     if (ctx->n_pend > 0 && ctx->pend_u16 != u16) FLUSH_UPDATES(ctx);
+    {   // ... and one set of tiles per slot: the same slot at another scale starts a new batch
+        const float scf = (float)scale;
+        bool cut = false;
+        for (int i = 0; i < ctx->n_pend && !cut; ++i) cut = ctx->pend[i].slot == slot && memcmp(&ctx->pend[i].scale, &scf, sizeof(float)) != 0;
+        if (cut) FLUSH_UPDATES(ctx);
+    }
     ctx->pend_u16 = u16;
     tl3d_ctx::PendingUpdate &u = ctx->pend[ctx->n_pend++];
     u.slot = slot; u.pose = p; u.scale = (float)scale;
     if (ctx->n_pend >= (ctx->tsdf_pairing ? ctx->tsdf_batch : 1)) return flush_updates(ctx);
+    return TL3D_OK;
+}
+
+int tl3d_tile_cache_info(tl3d_ctx *ctx, uint64_t *builds, uint64_t *hits, uint64_t *bytes) {
+    REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
+    FLUSH_UPDATES(ctx);                                 // (look-ups happen when a batch is issued)
+    if (builds) *builds = ctx->tc_builds;
+    if (hits) *hits = ctx->tc_hits;
+    if (bytes) *bytes = (uint64_t)(ctx->cfg.n_slots - ctx->pool_tiles.remaining) * ctx->pool_tiles.block;
     return TL3D_OK;
 }
 
@@ -2460,6 +2597,7 @@ int tl3d_raycast(tl3d_ctx *ctx, const double R[9], const double t[3], int min_we
         s.loaded = true;
         s.has_normals = false;
         s.smooth_radius = 0;
+        s.tc_built = s.tc_read = false;
         if (!s.ev_upload) TL3D_HIP(hipEventCreateWithFlags(&s.ev_upload, hipEventDisableTiming));
         TL3D_HIP(hipEventRecord(s.ev_upload, ctx->stream));
     }

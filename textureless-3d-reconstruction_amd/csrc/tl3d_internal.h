@@ -174,6 +174,18 @@ struct Slot {
     bool has_color = false;
     bool loaded = false;
     bool has_normals = false;
+    // TSDF tile cache: what the TSDF prep derives from the depth image, the scale and the depth limits alone (kernels_tsdf.hip:
+    // depth_tiles_kernel, tile_pyramid_kernel).  One lazily allocated block (tl3d_ctx::pool_tiles, tsdf_tile_cache_bytes) and the
+    // key it was built with; every writer of `depth` clears tc_built.  The u16 and f32 images give the same tiles (mm_to_m is
+    // the conversion the f32 copy was made with, no contraction, no fast math), so the depth kind is not part of the key.
+    float4 *tiles = nullptr;     // pyramid, all levels; the float4 behind the last level holds ...
+    unsigned *vpix = nullptr;    // ... the frame's valid pixel (device word)
+    float2 *vtile = nullptr;     // level-0 tiles as 8-B records
+    uint32_t tc_scale_bits = 0;  // key: bits of the f32 scale, the depth limits
+    float tc_mind = 0, tc_maxd = 0;
+    bool tc_built = false;
+    bool tc_read = false;        // some batch since the last upload has read or built the tiles: tc_reader_batch is its number
+    unsigned tc_build_batch = 0, tc_reader_batch = 0;   // tl3d_ctx::tsdf_batch_no of the batch that built them / read them last
 };
 
 // One part of a mesh weld (kernels_meshweld.hip) as the kernels see it: the part's arrays in device memory and the vertices and
@@ -275,7 +287,7 @@ struct tl3d_ctx : tl3d_grid_state {
     bool own_stream;
     tl3d::Cam cam;
     tl3d::Slot *slots;
-    tl3d::FramePool pool_depth, pool_u16, pool_bgr, pool_nmap, pool_sdepth;
+    tl3d::FramePool pool_depth, pool_u16, pool_bgr, pool_nmap, pool_sdepth, pool_tiles;
     int normal_radius;           // tl3d_set_normal_smoothing: window radius of the next normal maps (0: none)
     // scratch
     // TSDF integration: the prep chain of a batch (tiles, pyramid, cull, brick classes) runs on a prep stream while the update
@@ -288,6 +300,12 @@ struct tl3d_ctx : tl3d_grid_state {
     bool tsdf_use_u16;                    // gather from the millimetre image when the slot has one (env TL3D_U16_GATHER=0: never)
     int tsdf_batch;                       // frames per batch (env TL3D_TSDF_BATCH, default 32; 1 = no deferral)
     unsigned tsdf_seq, tsdf_batch_no;
+    // TSDF tile cache (Slot::tiles): off = every look-up is a miss (env TL3D_TILE_CACHE=0, read when the context is created);
+    // every batch numbered below tc_done_before is known complete on the device (the host has waited since); per-frame builds
+    // and look-ups that found tiles (tl3d_tile_cache_info)
+    bool tile_cache;
+    unsigned tc_done_before;
+    unsigned long long tc_builds, tc_hits;
     struct PendingUpdate { int slot; tl3d::PoseF pose; float scale; } pend[TL3D_TSDF_MAXBATCH];
     tl3d::CenFrame cen_pend[tl3d::TL3D_CEN_MAXBATCH];   // voxel-centroid accumulations not yet launched (one stride per batch)
     int n_cen_pend = 0;
@@ -519,7 +537,8 @@ size_t tsdf_batch_scratch_bytes(const Cam &cam, const Grid &g, int max_frames);
 void tsdf_batch_scratch_zero_range(const Cam &cam, const Grid &g, int max_frames, size_t *off, size_t *bytes);
 int launch_tsdf_prepare(hipStream_t s, const Cam &cam, const Grid &g, int n, int max_frames, const PoseF *p, const Frustum &fr,
                         const void *const *depth, bool depth_u16, const float *scale, float mind, float maxd, void *scratch, unsigned *free_cnt,
-                        bool classify_only = false);
+                        void *const *tiles, const unsigned char *stale, int n_stale, bool classify_only = false);
+size_t tsdf_tile_cache_bytes(const Cam &cam, size_t *vtile_off, size_t *vpix_off);
 int launch_centroid_mark(hipStream_t s, const Cam &cam, const Grid &g, const BpArgs &a, const PoseD &p, const float *depth, const double *xf, const double *yf);
 #ifdef TL3D_EXPERIMENTS
 void tsdf_debug_print_spans(int nwaves);

@@ -413,6 +413,12 @@ class FusionContext:
                                               mn_d, mx_d, C.byref(nt), C.byref(nc)))
         return int(nt.value), int(nc.value)
 
+    def tile_cache_info(self):
+        """(builds, hits, bytes) of the per-slot TSDF tile cache (tl3d.h: tl3d_tile_cache_info)."""
+        b, h, m = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        abi.check(self._lib.tl3d_tile_cache_info(self._h, C.byref(b), C.byref(h), C.byref(m)))
+        return int(b.value), int(h.value), int(m.value)
+
     # ---- fusion ----------------------------------------------------------------------------
     def accumulate_centroid(self, slot: int, pose=None, scale=1.0, subsample: int = 1, min_depth=None, max_depth=None,
                             scale_f64: bool = False):
