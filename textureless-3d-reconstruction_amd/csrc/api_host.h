@@ -1,5 +1,5 @@
-// api_host.h -- host helpers the translation units of the extern "C" surface share (tl3d_api.hip, api_mesh.hip), and the one
-// scratch mechanism of the calls that need device memory of their own (scratch_carve).  Host code only.
+// api_host.h -- host helpers the translation units of the extern "C" surface share (tl3d_api.hip, api_mesh.hip, api_register.hip),
+// and the one scratch mechanism of the calls that need device memory of their own (scratch_carve).  Host code only.
 #pragma once
 #include "tl3d_internal.h"
 
@@ -114,5 +114,47 @@ struct ChunkHalves {
 // the one array a call can size only after the host has seen a count (growing stage 0 then would lose what the call has in it).
 // hipFree's implicit wait keeps work in flight from losing its memory.  Defined in tl3d_api.hip.
 int scratch_carve(tl3d_ctx *ctx, int stage, const size_t *bytes, int n, void **out, const char *what);
+
+// grow-on-demand device scratch of `need` elements: on failure the buffer is gone and its capacity 0
+template <class T> int grow(T **p, size_t *cap, size_t need, const char *what) {
+    if (need <= *cap) return TL3D_OK;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    if (hipMalloc(p, need * sizeof(T)) != hipSuccess) {
+        (void)hipGetLastError();
+        return set_err(TL3D_E_NOMEM, "%s alloc (%zu B) failed", what, need * sizeof(T));
+    }
+    *cap = need;
+    return TL3D_OK;
+}
+// two buffers that share one capacity (*cap counts elements of each)
+template <class A, class B> int grow_pair(A **a, B **b, size_t *cap, size_t need, const char *what) {
+    size_t cap_b = *cap;
+    int rc = grow(a, cap, need, what);
+    if (!rc) rc = grow(b, &cap_b, need, what);
+    if (rc) *cap = 0;
+    return rc;
+}
+
+// what api_register.hip shares with tl3d_api.hip, where each is defined and described
+int check_slot(tl3d_ctx *ctx, int slot, bool need_loaded);
+int order_after_lanes(tl3d_ctx *ctx, int slot, bool rewrites_depth, bool rewrites_nmap);
+void *pool_take(FramePool &fp);
+int flush_updates(tl3d_ctx *ctx);
+int fold_free(tl3d_ctx *ctx);
+// every call that reads or writes the TSDF grid, re-uses a frame slot, synchronises or time-stamps first issues the deferred updates
+#define FLUSH_UPDATES(ctx_)                          \
+    do {                                             \
+        const int rc_ = tl3d::flush_updates(ctx_);   \
+        if (rc_) return rc_;                         \
+    } while (0)
+#define FLUSH_AND_FOLD(ctx_)                         \
+    do {                                             \
+        FLUSH_UPDATES(ctx_);                         \
+        const int frc_ = tl3d::fold_free(ctx_);      \
+        if (frc_) return frc_;                       \
+    } while (0)
+void registration_release(tl3d_ctx *ctx);   // tl3d_destroy's: everything registration owns in a context (defined in api_register.hip)
 
 }  // namespace tl3d

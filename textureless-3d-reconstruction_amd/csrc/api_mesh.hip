@@ -1,4 +1,5 @@
-// api_mesh.hip -- the mesh-in / mesh-out calls of the extern "C" surface (include/tl3d.h): host code only, no call needs a grid.
+// api_mesh.hip -- the mesh-in / mesh-out calls of the extern "C" surface (include/tl3d.h; the registration calls: api_register.hip,
+// everything else: tl3d_api.hip): host code only, no call needs a grid.
 // Each call carves its device scratch from the context's buffers (scratch_carve, api_host.h) by ONE size list at its top; the
 // comment on the list names, array by array, the memset or kernel that writes it first -- nothing is read before.
 #include <math.h>

@@ -89,6 +89,7 @@ struct IcpState {                // lives in device memory for the whole ICP run
     int iters_run;
     int over;                    // batched runs: no further level follows (last level done, failed, or < 8 correspondences)
 };
+constexpr int ICP_SUM_E = 27, ICP_SUM_CORR = 28, ICP_SUM_SRC = 29;   // e, cnt and nsrc of IcpState::sums, for the host's read-outs (api_register.hip)
 
 struct IcpRun {                  // per-run arguments of the ICP kernels, read from device memory so that a lane's
     const float *depth_src;      // kernel chain has constant launch arguments and can be replayed as a hipGraph
@@ -330,7 +331,7 @@ struct tl3d_ctx : tl3d_grid_state {
     int *d_maxw;
     unsigned long long *d_counters;   // device counters [16]
     unsigned long long *d_cen_counters;   // centroid statistics, sharded: [256 lines][8] (points kept, points dropped)
-    struct IcpLane {             // one in-flight ICP run: own stream, device state, partial-sum slab, pinned read-back
+    struct IcpLane {             // one in-flight ICP run: own stream, device state, partial-sum slab, pinned read-back (api_register.hip, as the next three)
         hipStream_t stream;
         double *slab;            // [ICP_MAX_BLOCKS][ICP_SLAB]
         unsigned *ticket;        // arrival counter of the iteration kernel (64-B block of its own; 0 between launches)
