@@ -686,6 +686,18 @@ int tl3d_set_tsdf_pairing(tl3d_ctx *ctx, int on);
  * use).  Any of the three may be null; the pending batch is issued first (look-ups happen then).  With TL3D_TILE_CACHE=0 in the environment when the context is created every look-up
  * is a miss (the tiles are built once per batch, as before the cache existed). */
 int tl3d_tile_cache_info(tl3d_ctx *ctx, uint64_t *builds, uint64_t *hits, uint64_t *bytes);
+/* Beside the tiles a slot keeps the RESULT of the TSDF prep's brick and sub-brick classification for the last (pose, scale, depth
+ * limits, grid geometry) it was fused or counted with: the bricks near a surface with their sub-brick masks and the free-space
+ * bricks.  A batch that meets the slot again with exactly that key (compared bit for bit, the pose as the twelve f32 words the
+ * kernels get) replays the lists instead of classifying: another scan over resident frames with fixed poses, a fusion after
+ * tl3d_grid_reset, tl3d_count_bricks followed by the fusion.  One entry per slot; a new image, a ray cast into the slot or
+ * another key replaces it.  The grid is the same bit for bit either way.  classified / replayed: frames that went through the
+ * classification kernels / whose entry was replayed; overflowed: of the classified, those whose bricks did not fit the slot's
+ * buffer (never replayed); bytes: device memory the entries hold (288 KB per slot by default, taken on first use).  Any of the
+ * four may be null; the pending batch is issued first and the call waits for the device.  Environment, read when the context is
+ * created: TL3D_CLASS_CACHE=0 every frame is classified; TL3D_CLASS_CACHE_ENTRIES=n bricks per slot buffer (default 49152, 6 B
+ * each); TL3D_TILE_CACHE=0 switches this cache off too. */
+int tl3d_class_cache_info(tl3d_ctx *ctx, uint64_t *classified, uint64_t *replayed, uint64_t *overflowed, uint64_t *bytes);
 int tl3d_get_stats(tl3d_ctx *ctx, tl3d_stats *out);
 int tl3d_reset_stats(tl3d_ctx *ctx);
 int tl3d_event_record(tl3d_ctx *ctx, int which /* 0 or 1 */);

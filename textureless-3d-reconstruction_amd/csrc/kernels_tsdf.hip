@@ -24,6 +24,10 @@
 //   4. subbrick_classify_kernel  per frame, one wave per listed brick: its eight 4x4x4 SUB-BRICKS by the same three rules
 //        (8 lanes per sub-brick: one extreme voxel centre each, <= 8 pyramid lookups) -> a (mixed, free) bit mask.  On the
 //        headline sequence 3.4 of the 8 sub-bricks of a listed brick stay MIXED.
+//        Kernels 3 and 4 depend on the pose, the scale, the depth limits, the slot's tiles and the grid's geometry only: their
+//        result is kept with the slot as well (the classification cache, below) and a frame that meets its slot with the same
+//        key again is REPLAYED from it by class_replay_kernel, which runs in front of kernel 3; kernels 3 and 4 return at once
+//        for such a frame.
 //   5. tsdf_update_kernel     ONE launch per batch, one 64-lane wave per brick of the batch list: for every frame that lists
 //        the brick (frame mask), the voxels of its MIXED sub-bricks are projected; the 8x8-pixel tile under a voxel's pixel
 //        decides most of them (free / behind everything), the rest gather their depth value; FREE sub-bricks add (32767, 1);
@@ -363,14 +367,84 @@ __device__ __forceinline__ int classify_box(const Grid &g, float4 a, float zmin,
     return 1;
 }
 
-__global__ __launch_bounds__(256) void brick_cull_kernel(Cam cam, Grid g, BatchBufs B, Frustum fr, Pyramid py,
-                                                         unsigned *__restrict__ free_cnt) {
+// ---- the classification cache ------------------------------------------------------------------------------------------
+// What the cull and the sub-brick classification find for a frame depends on its pose, scale and depth limits, the camera, the
+// slot's tiles and the grid's geometry -- not on the grid's records, nor on any earlier batch.  A slot keeps the result of the
+// last classification made for it (Slot::cls; the host holds the key, tl3d_api.hip: class_cache_lookup) and a batch that meets
+// the slot again with the same key REPLAYS it: class_replay_kernel walks the cached lists through the very tail the cull ends
+// with.  Buffer: [header: CC_HDR_WORDS] [entries: cap words, the MIXED bricks from the front as F->list gets them, the FREE
+// bricks from the back] [cap 16-bit sub-brick masks, one per MIXED entry, as F->sub[brick] holds them].  Only the device knows
+// how many bricks a frame lists: class_finish_kernel marks the header complete only if MIXED + FREE <= cap, a frame that did
+// not fit is classified every time, and each kernel takes its path for a frame from the mode and that header alone (uniform
+// over the frame's workgroups; no host wait).  Level 1 = lists and counts, level 2 = + masks: a classify-only chain
+// (tl3d_count_bricks) fills level 1, and the fusion that follows replays it, runs the sub-brick classification over the
+// cached list and leaves level 2.
+__device__ __forceinline__ bool class_replays(const ClassPlan &P, int f) {
+    return class_mode(P, f) == CC_REPLAY && P.cache[f][3] == 1u;
+}
+
+// The TAIL of a brick's classification for frame `frame`, shared by the cull and the replay: one lane per (brick, class), the
+// whole workgroup calls it.  MIXED (cls 1): the brick's bit in the frame mask; the first frame of the batch to set a bit takes
+// the brick's pool slot and puts it on the batch list; the frame's own list.  FREE (cls 2): one add to the brick's free-space
+// counter.  The four waves pool their survivors so that the list cursors see one atomic per workgroup, not per wave.
+// save: the frame's cache buffer if this classification is to be recorded, else null.
+struct ClassTailLds { unsigned cnt[4][3], base[3]; };
+__device__ __forceinline__ void class_tail(const Grid &g, const BatchBufs &B, DescPtr F, unsigned *__restrict__ free_cnt, unsigned frame, int cls, unsigned brick,
+                                           unsigned *__restrict__ save, unsigned cap, ClassTailLds &S) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    unsigned *__restrict__ list = F->list;
+    // MIXED: the brick's bit in the frame mask; the first frame of the batch to set a bit also puts the brick on the batch list
+    bool first = false;
+    if (cls == 1) {
+        first = atomicOr(B.framemask + brick, 1u << frame) == 0u;
+        if (first) (void)brick_slot_ensure(g.tsdf_tab, g.cursors, g.tsdf_cap, brick);     // sparse grid: records on first touch
+    }
+    // Free space: every voxel of the brick gets exactly (+32767, +1).  That is ONE integer add here instead of a 4 KB read +
+    // 4 KB write by the update kernel; the counters are folded into the records before anything reads them (fold_free_kernel).
+    if (cls == 2) atomicAdd(free_cnt + brick, 1u);
+    const unsigned long long mm = __ballot(cls == 1), mf = __ballot(cls == 2), m1 = __ballot(first);
+    if (lane == 0) { S.cnt[wid][0] = (unsigned)__popcll(mm); S.cnt[wid][1] = (unsigned)__popcll(mf); S.cnt[wid][2] = (unsigned)__popcll(m1); }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const unsigned tot = S.cnt[0][threadIdx.x] + S.cnt[1][threadIdx.x] + S.cnt[2][threadIdx.x] + S.cnt[3][threadIdx.x];
+        unsigned *cur = threadIdx.x < 2 ? F->counts + threadIdx.x : B.hdr;      // [1]: free-space bricks, counted (listed only in the cache)
+        S.base[threadIdx.x] = tot ? atomicAdd(cur, tot) : 0u;
+    }
+    __syncthreads();
+    unsigned bm = S.base[0], b1 = S.base[2];
+    for (int w = 0; w < wid; ++w) { bm += S.cnt[w][0]; b1 += S.cnt[w][2]; }
+    const unsigned long long below = (1ull << lane) - 1ull;
+    if (cls == 1) list[bm + __popcll(mm & below)] = brick;
+    if (first) B.list[b1 + __popcll(m1 & below)] = brick;
+    if (save) {                                                    // (uniform) the same entry, and the FREE bricks, into the slot's buffer
+        unsigned bf = S.base[1];
+        for (int w = 0; w < wid; ++w) bf += S.cnt[w][1];
+        const unsigned pm = bm + (unsigned)__popcll(mm & below), pf = bf + (unsigned)__popcll(mf & below);
+        if (cls == 1 && pm < cap) save[CC_HDR_WORDS + pm] = brick;
+        if (cls == 2 && pf < cap) save[CC_HDR_WORDS + (cap - 1u - pf)] = brick;
+    }
+    __syncthreads();                                               // S is reused by the next trip
+}
+
+// CACHE = false: for chains none of whose frames uses the cache (ClassPlan::modes == 0: the cache is off) -- the kernel as it was
+// before the cache existed, without the plan among its arguments (brick_cull_kernel; brick_cull_cached_kernel is the other).
+template <bool CACHE>
+__device__ __forceinline__ void brick_cull(const Cam &cam, const Grid &g, const BatchBufs &B, const Frustum &fr, const Pyramid &py,
+                                           unsigned *__restrict__ free_cnt, const ClassPlan &P) {
+    unsigned *__restrict__ save = nullptr;
+    if (CACHE) {
+        if (class_replays(P, blockIdx.y)) return;                   // (class_replay_kernel has listed this frame's bricks)
+        const unsigned mode = class_mode(P, blockIdx.y);
+        if (mode == CC_SAVE) save = P.cache[blockIdx.y];
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            atomicAdd(P.stats + 0, 1ull);
+            if (mode == CC_REPLAY) atomicAdd(P.stats + 2, 1ull);    // its entry did not fit: classified every time
+        }
+    }
     const DescPtr F = const_descs(B) + blockIdx.y;
     const PoseF pose = desc_pose(F);
     const float4 *__restrict__ tiles = F->tiles;
-    unsigned *__restrict__ list = F->list;
-    __shared__ unsigned s_cnt[4][3];
-    __shared__ unsigned s_base[3];
+    __shared__ ClassTailLds S;
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int ncx = (g.nbx + 3) >> 2, ncy = (g.nby + 3) >> 2, ncz = (g.nbz + 3) >> 2;
     // the frame's cell list (tile_pyramid_kernel): four cells per workgroup and trip
@@ -454,31 +528,11 @@ __global__ __launch_bounds__(256) void brick_cull_kernel(Cam cam, Grid g, BatchB
             }
         }
     }
-    // MIXED: the brick's bit in the frame mask; the first frame of the batch to set a bit also puts the brick on the batch list
-    bool first = false;
-    if (cls == 1) {
-        first = atomicOr(B.framemask + brick, 1u << blockIdx.y) == 0u;
-        if (first) (void)brick_slot_ensure(g.tsdf_tab, g.cursors, g.tsdf_cap, (unsigned)brick);     // sparse grid: records on first touch
+    class_tail(g, B, F, free_cnt, blockIdx.y, cls, (unsigned)brick, save, CACHE ? P.cap : 0u, S);
     }
-    // Free space: every voxel of the brick gets exactly (+32767, +1).  That is ONE integer add here instead of a 4 KB read +
-    // 4 KB write by the update kernel; the counters are folded into the records before anything reads them (fold_free_kernel).
-    if (cls == 2) atomicAdd(free_cnt + brick, 1u);
-    const unsigned long long mm = __ballot(cls == 1), mf = __ballot(cls == 2), m1 = __ballot(first);
-    if (lane == 0) { s_cnt[wid][0] = (unsigned)__popcll(mm); s_cnt[wid][1] = (unsigned)__popcll(mf); s_cnt[wid][2] = (unsigned)__popcll(m1); }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const unsigned tot = s_cnt[0][threadIdx.x] + s_cnt[1][threadIdx.x] + s_cnt[2][threadIdx.x] + s_cnt[3][threadIdx.x];
-        unsigned *cur = threadIdx.x < 2 ? F->counts + threadIdx.x : B.hdr;      // [1]: free-space bricks, counted only
-        s_base[threadIdx.x] = tot ? atomicAdd(cur, tot) : 0u;
-    }
-    __syncthreads();
-    unsigned bm = s_base[0], b1 = s_base[2];
-    for (int w = 0; w < wid; ++w) { bm += s_cnt[w][0]; b1 += s_cnt[w][2]; }
-    const unsigned long long below = (1ull << lane) - 1ull;
-    if (cls == 1) list[bm + __popcll(mm & below)] = (unsigned)brick;
-    if (first) B.list[b1 + __popcll(m1 & below)] = (unsigned)brick;
-    __syncthreads();                                               // s_cnt / s_base are reused by the next trip
-    }
+}
+__global__ __launch_bounds__(256) void brick_cull_kernel(Cam cam, Grid g, BatchBufs B, Frustum fr, Pyramid py, unsigned *__restrict__ free_cnt) {
+    brick_cull<false>(cam, g, B, fr, py, free_cnt, ClassPlan());
 }
 
 // records += count x (32767, 1) for every brick with a pending free-space count; the count returns to zero (exchanged, so a
@@ -621,14 +675,27 @@ __device__ __forceinline__ int classify_subbrick(const Cam &cam, const Grid &g, 
 }
 
 // Prep kernel 4: sub-brick masks of the listed bricks of every frame; one lane per sub-brick, 8 bricks per wave.
-__global__ __launch_bounds__(256) void subbrick_classify_kernel(Cam cam, Grid g, Pyramid py, BatchBufs B) {
+// A frame that was replayed at level 2 has its masks already; one replayed at level 1 is classified over the CACHED list (the
+// same bricks as F->list, in the order the masks are kept in); a frame that is being saved keeps a copy of each mask.
+template <bool CACHE>
+__device__ __forceinline__ void subbrick_classify(const Cam &cam, const Grid &g, const Pyramid &py, const BatchBufs &B, const ClassPlan &P) {
     const DescPtr F = const_descs(B) + blockIdx.y;
     const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const unsigned nbricks = (unsigned)(g.nbx * g.nby * g.nbz);
-    const unsigned n = min(F->counts[0], nbricks);
+    unsigned n = min(F->counts[0], nbricks);
+    const unsigned *__restrict__ list = F->list;
+    unsigned short *__restrict__ csub = nullptr;                    // the masks' copy in the slot's buffer, by list index
+    if (CACHE) {
+        const bool replayed = class_replays(P, blockIdx.y);
+        if (replayed) {
+            if (P.cache[blockIdx.y][2] >= 2u) return;
+            list = P.cache[blockIdx.y] + CC_HDR_WORDS;
+            n = min(n, P.cap);
+        }
+        if (replayed || class_mode(P, blockIdx.y) == CC_SAVE) csub = reinterpret_cast<unsigned short *>(P.cache[blockIdx.y] + CC_HDR_WORDS + P.cap);
+    }
     const PoseF pose = desc_pose(F);
     const float4 *__restrict__ tiles = F->tiles;
-    const unsigned *__restrict__ list = F->list;
     unsigned short *__restrict__ sub = F->sub;
     const int j = lane >> 3, sb = lane & 7;
     for (unsigned base = (blockIdx.x * 4u + (unsigned)wid) * 8u; base < n; base += gridDim.x * 32u) {
@@ -641,8 +708,15 @@ __global__ __launch_bounds__(256) void subbrick_classify_kernel(Cam cam, Grid g,
             cls = classify_subbrick(cam, g, py, pose, tiles, bx * 8 + (sb & 1) * 4, by * 8 + ((sb >> 1) & 1) * 4, bz * 8 + (sb >> 2) * 4);
         }
         const unsigned long long mm = __ballot(cls == 1), mf = __ballot(cls == 2);
-        if (sb == 0 && t < n) sub[brick] = (unsigned short)(((mm >> (8 * j)) & 0xffull) | (((mf >> (8 * j)) & 0xffull) << 8));
+        if (sb == 0 && t < n) {
+            const unsigned short m = (unsigned short)(((mm >> (8 * j)) & 0xffull) | (((mf >> (8 * j)) & 0xffull) << 8));
+            sub[brick] = m;
+            if (CACHE && csub && t < P.cap) csub[t] = m;
+        }
     }
+}
+__global__ __launch_bounds__(256) void subbrick_classify_kernel(Cam cam, Grid g, Pyramid py, BatchBufs B) {
+    subbrick_classify<false>(cam, g, py, B, ClassPlan());
 }
 
 // ---- 4b. the batch list, dearest bricks first -------------------------------------------------------------------------------
@@ -1241,6 +1315,60 @@ __global__ __launch_bounds__(256, UPD_WAVES) void tsdf_update_pairs_kernel(Cam c
     }
 }
 
+// ---- the kernels of the classification cache ------------------------------------------------------------------------------
+// The entry points that take a ClassPlan (the bodies they share with the plain kernels are above), the replay and the finish.
+__global__ __launch_bounds__(256) void brick_cull_cached_kernel(Cam cam, Grid g, BatchBufs B, Frustum fr, Pyramid py, unsigned *__restrict__ free_cnt,
+                                                                ClassPlan P) {
+    brick_cull<true>(cam, g, B, fr, py, free_cnt, P);
+}
+__global__ __launch_bounds__(256) void subbrick_classify_cached_kernel(Cam cam, Grid g, Pyramid py, BatchBufs B, ClassPlan P) {
+    subbrick_classify<true>(cam, g, py, B, P);
+}
+// The replay of a frame whose slot holds its classification: every cached entry through class_tail, 256 per workgroup and trip,
+// and at level 2 the sub-brick masks.  Indices read from the buffer are clamped as list entries are everywhere.
+__global__ __launch_bounds__(256) void class_replay_kernel(Grid g, BatchBufs B, unsigned *__restrict__ free_cnt, ClassPlan P) {
+    if (!class_replays(P, blockIdx.y)) return;
+    const unsigned *__restrict__ C = P.cache[blockIdx.y];
+    const DescPtr F = const_descs(B) + blockIdx.y;
+    __shared__ ClassTailLds S;
+    const unsigned nbricks = (unsigned)(g.nbx * g.nby * g.nbz), cap = P.cap;
+    const unsigned nm = min(C[0], cap), nf = min(C[1], cap - nm);
+    const bool masks = !P.classify_only && C[2] >= 2u;
+    const unsigned short *__restrict__ cm = reinterpret_cast<const unsigned short *>(C + CC_HDR_WORDS + cap);
+    unsigned short *__restrict__ sub = F->sub;
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(P.stats + 1, 1ull);
+    for (unsigned i0 = blockIdx.x * 256u; i0 < nm + nf; i0 += gridDim.x * 256u) {
+        const unsigned i = i0 + threadIdx.x;
+        int cls = 0;
+        unsigned brick = 0;
+        if (i < nm) {
+            brick = min(C[CC_HDR_WORDS + i], nbricks - 1u);
+            cls = 1;
+            if (masks) sub[brick] = cm[i];
+        } else if (i < nm + nf) {
+            brick = min(C[CC_HDR_WORDS + (cap - 1u - (i - nm))], nbricks - 1u);
+            cls = 2;
+        }
+        class_tail(g, B, F, free_cnt, blockIdx.y, cls, brick, nullptr, cap, S);
+    }
+}
+
+// The last kernel of a chain that wrote cache entries, one workgroup per frame: the header of a saved frame (complete only if
+// the frame fit), and level 2 for an entry that was replayed at level 1 and got its masks from this chain.
+__global__ __launch_bounds__(64) void class_finish_kernel(BatchBufs B, ClassPlan P) {
+    if (threadIdx.x != 0) return;
+    const DescPtr F = const_descs(B) + blockIdx.x;
+    unsigned *C = P.cache[blockIdx.x];
+    if (class_mode(P, blockIdx.x) == CC_SAVE) {
+        const unsigned nm = F->counts[0], nf = F->counts[1];
+        const bool fit = nm <= P.cap && nf <= P.cap - nm;
+        C[0] = nm; C[1] = nf; C[2] = P.classify_only ? 1u : 2u; C[3] = fit ? 1u : 0u;
+        if (!fit) atomicAdd(P.stats + 2, 1ull);
+    } else if (class_replays(P, blockIdx.x) && C[2] < 2u && !P.classify_only) {
+        C[2] = 2u;
+    }
+}
+
 static Pyramid make_pyramid(const Cam &cam) {
     Pyramid p;
     memset(&p, 0, sizeof(p));
@@ -1288,6 +1416,9 @@ static BatchLayout batch_layout(const Cam &cam, const Grid &g, int max_frames) {
 
 size_t tsdf_batch_scratch_bytes(const Cam &cam, const Grid &g, int max_frames) { return batch_layout(cam, g, max_frames).total; }
 
+// One slot's classification buffer for `entries` bricks: header, entries, 16-bit masks (6 B per entry)
+size_t tsdf_class_cache_bytes(unsigned entries) { return up256(CC_HDR_WORDS * sizeof(unsigned) + (size_t)entries * (sizeof(unsigned) + sizeof(unsigned short))); }
+
 // One slot's tile buffer: [tile pyramid, float4 per tile, + one float4 whose first word is the valid pixel] [8-B level-0 tiles at *vtile_off]
 size_t tsdf_tile_cache_bytes(const Cam &cam, size_t *vtile_off, size_t *vpix_off) {
     const Pyramid p = make_pyramid(cam);
@@ -1328,11 +1459,12 @@ static BatchBufs batch_bufs(const BatchLayout &L, void *scratch, int n) {
 
 // The whole prep of a batch of n frames (one depth kind) on stream s: descriptor upload, depth tiles and pyramid of the n_stale
 // frames stale[] (indices into the batch; the others' slots hold them already), resets + cell lists, brick classification,
-// sub-brick masks.  tiles[i]: frame i's slot buffer (tsdf_tile_cache_bytes; frames of one slot share it and at most one of them is
+// sub-brick masks -- or, for the frames plan marks CC_REPLAY and whose buffer is complete, the replay of both; class_writes: the
+// chain writes cache entries (class_finish_kernel closes it).  tiles[i]: frame i's slot buffer (tsdf_tile_cache_bytes; frames of one slot share it and at most one of them is
 // stale).  `scratch` is a batch scratch of at least n frames (tsdf_batch_scratch_bytes).
 int launch_tsdf_prepare(hipStream_t s, const Cam &cam, const Grid &g, int n, int max_frames, const PoseF *p, const Frustum &fr,
                         const void *const *depth, bool depth_u16, const float *scale, float mind, float maxd, void *scratch, unsigned *free_cnt,
-                        void *const *tiles, const unsigned char *stale, int n_stale, bool classify_only) {
+                        void *const *tiles, const unsigned char *stale, int n_stale, const ClassPlan &plan, bool class_writes, bool classify_only) {
     if (n < 1 || n > max_frames || n > TL3D_TSDF_MAXBATCH) return set_err(TL3D_E_INVALID, "bad batch size %d", n);
     if (n_stale < 0 || n_stale > n) return set_err(TL3D_E_INVALID, "bad stale count %d", n_stale);
     size_t vt_off = 0;
@@ -1384,9 +1516,36 @@ int launch_tsdf_prepare(hipStream_t s, const Cam &cam, const Grid &g, int n, int
     TL3D_HIP(hipGetLastError());
     const int ncells = ((g.nbx + 3) / 4) * ((g.nby + 3) / 4) * ((g.nbz + 3) / 4);
     const int nquad = (ncells + 3) / 4;                 // the cells in view are known only on the device: a fixed grid strides over each frame's list
-    hipLaunchKernelGGL(brick_cull_kernel, dim3(nquad < 256 ? nquad : 256, n), dim3(256), 0, s, cam, g, B, fr, py, free_cnt);
+    // The classification cache (plan: the host's look-up): frames whose slot holds their classification are replayed, the cull
+    // and the sub-brick classification return at once for them -- and the other way round.
+    const int nbricks = g.nbx * g.nby * g.nbz;
+    ClassPlan P = plan;
+    P.cap = plan.cap < (unsigned)nbricks ? plan.cap : (unsigned)nbricks;
+    P.classify_only = classify_only ? 1 : 0;
+    bool any_replay = false;
+    for (int i = 0; i < n; ++i) {
+        if (class_mode(P, i) != CC_CLASSIFY && (!P.cache[i] || P.cap == 0u)) return set_err(TL3D_E_INVALID, "frame %d: no classification buffer", i);
+        any_replay = any_replay || class_mode(P, i) == CC_REPLAY;
+    }
+    if (n < TL3D_TSDF_MAXBATCH) P.modes &= (1ull << (2 * n)) - 1ull;
+    const bool cached = P.modes != 0ull;                 // (else the kernels as they were without the cache; the caller counts the frames as classified)
+    if (any_replay) {
+        const unsigned trips = (P.cap + 255u) / 256u;
+        hipLaunchKernelGGL(class_replay_kernel, dim3(trips < 16u ? trips : 16u, n), dim3(256), 0, s, g, B, free_cnt, P);
+        TL3D_HIP(hipGetLastError());
+    }
+    if (cached)
+        hipLaunchKernelGGL(brick_cull_cached_kernel, dim3(nquad < 256 ? nquad : 256, n), dim3(256), 0, s, cam, g, B, fr, py, free_cnt, P);
+    else
+        hipLaunchKernelGGL(brick_cull_kernel, dim3(nquad < 256 ? nquad : 256, n), dim3(256), 0, s, cam, g, B, fr, py, free_cnt);
     TL3D_HIP(hipGetLastError());
-    if (classify_only) return TL3D_OK;                    // (tl3d_count_bricks: which bricks WOULD get records is all that is asked)
+    if (classify_only) {                                  // (tl3d_count_bricks: which bricks WOULD get records is all that is asked)
+        if (class_writes) {
+            hipLaunchKernelGGL(class_finish_kernel, dim3(n), dim3(64), 0, s, B, P);
+            TL3D_HIP(hipGetLastError());
+        }
+        return TL3D_OK;
+    }
     // The batch list ordered by cost, dearest bricks first (a one-frame batch: every brick costs the same; the update walks the list).
     // A brick's cost is the number of frames that list it -- the frame masks, which the cull has just finished -- so the two small
     // kernels go BEFORE the sub-brick classification, not behind it: beside an update kernel the classification stretches over the
@@ -1399,12 +1558,18 @@ int launch_tsdf_prepare(hipStream_t s, const Cam &cam, const Grid &g, int n, int
         TL3D_HIP(hipGetLastError());
     }
     // sub-brick masks of the listed bricks (their number is known only on the device: a fixed grid strides over each list)
-    const int nbricks = g.nbx * g.nby * g.nbz;
     int ncb = (nbricks + 31) / 32;                       // 8 bricks per wave, 4 waves per workgroup
     const int cap = n >= 8 ? 128 : 512;
     if (ncb > cap) ncb = cap;
-    hipLaunchKernelGGL(subbrick_classify_kernel, dim3(ncb, n), dim3(256), 0, s, cam, g, py, B);
+    if (cached)
+        hipLaunchKernelGGL(subbrick_classify_cached_kernel, dim3(ncb, n), dim3(256), 0, s, cam, g, py, B, P);
+    else
+        hipLaunchKernelGGL(subbrick_classify_kernel, dim3(ncb, n), dim3(256), 0, s, cam, g, py, B);
     TL3D_HIP(hipGetLastError());
+    if (class_writes) {
+        hipLaunchKernelGGL(class_finish_kernel, dim3(n), dim3(64), 0, s, B, P);
+        TL3D_HIP(hipGetLastError());
+    }
     return TL3D_OK;
 }
 

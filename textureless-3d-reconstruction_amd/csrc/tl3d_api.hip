@@ -466,6 +466,14 @@ int tl3d_create(const tl3d_config *cfg, int device, tl3d_ctx **out) {
     {   // the per-slot TSDF tile cache is a product feature with an off switch for A/B runs (every look-up a miss): read here, once
         const char *v = getenv("TL3D_TILE_CACHE");
         ctx->tile_cache = !(v && atoi(v) == 0);
+        // ... and so is the classification cache beside it (Slot::cls): its switch, and the entries (MIXED + FREE bricks of one
+        // frame) a slot's buffer holds.  Default 49 152 = 288 KB per slot: a headline frame (512^3 voxels at 5 mm, 1080 x 1920)
+        // lists ~15.4 k MIXED + ~10.2 k FREE bricks, a little over half of that.
+        v = getenv("TL3D_CLASS_CACHE");
+        ctx->class_cache = !(v && atoi(v) == 0);
+        v = getenv("TL3D_CLASS_CACHE_ENTRIES");
+        const long long e = v ? atoll(v) : 49152;
+        ctx->cc_entries = (unsigned)(e < 1 ? 1 : e > (1ll << 26) ? (1ll << 26) : e);
     }
     ctx->slots = new (std::nothrow) Slot[cfg->n_slots];
     if (!ctx->slots) { delete ctx; return set_err(TL3D_E_NOMEM, "host allocation failed"); }
@@ -475,8 +483,11 @@ int tl3d_create(const tl3d_config *cfg, int device, tl3d_ctx **out) {
         Cam tc;
         memset(&tc, 0, sizeof(tc));
         tc.W = cfg->width; tc.H = cfg->height;
-        const size_t bytes[6] = {npx * sizeof(float), npx * sizeof(uint16_t), npx * 3, npm * sizeof(float4), npm * sizeof(float),
-                                 tsdf_tile_cache_bytes(tc, nullptr, nullptr)};      // (the TSDF tile cache: Slot::tiles)
+        // The TSDF tile cache (Slot::tiles) and, behind it in the same block, the classification cache (Slot::cls): one pool, so
+        // that a slot's first fusion costs one slab allocation per 64 slots, as before the second cache.
+        ctx->tc_bytes = (tsdf_tile_cache_bytes(tc, nullptr, nullptr) + 16 + 255) & ~(size_t)255;
+        ctx->cc_bytes = ctx->class_cache && ctx->tile_cache ? tsdf_class_cache_bytes(ctx->cc_entries) : 0;
+        const size_t bytes[6] = {npx * sizeof(float), npx * sizeof(uint16_t), npx * 3, npm * sizeof(float4), npm * sizeof(float), ctx->tc_bytes + ctx->cc_bytes - 16};
         FramePool *pools[6] = {&ctx->pool_depth, &ctx->pool_u16, &ctx->pool_bgr, &ctx->pool_nmap, &ctx->pool_sdepth, &ctx->pool_tiles};
         for (int k = 0; k < 6; ++k) {
             FramePool &fp = *pools[k];
@@ -510,8 +521,10 @@ int tl3d_create(const tl3d_config *cfg, int device, tl3d_ctx **out) {
         const int grc = alloc_grid(ctx, cfg);
         if (grc) return fail(grc);
     }
-    if (hipMalloc(&ctx->d_counters, 16 * sizeof(unsigned long long)) != hipSuccess) return fail(set_err(TL3D_E_NOMEM, "alloc failed"));
-    if (hipMemsetAsync(ctx->d_counters, 0, 16 * sizeof(unsigned long long), ctx->stream) != hipSuccess) return fail(set_err(TL3D_E_HIP, "memset failed"));
+    // (16 counters of the update kernel, then the 4 of the classification cache: ClassPlan::stats)
+    if (hipMalloc(&ctx->d_counters, 20 * sizeof(unsigned long long)) != hipSuccess) return fail(set_err(TL3D_E_NOMEM, "alloc failed"));
+    if (hipMemsetAsync(ctx->d_counters, 0, 20 * sizeof(unsigned long long), ctx->stream) != hipSuccess) return fail(set_err(TL3D_E_HIP, "memset failed"));
+    ctx->d_cc_stats = ctx->d_counters + 16;
     if (hipMalloc(&ctx->d_cen_counters, 256 * 8 * sizeof(unsigned long long)) != hipSuccess) return fail(set_err(TL3D_E_NOMEM, "alloc failed"));
     if (hipMemsetAsync(ctx->d_cen_counters, 0, 256 * 8 * sizeof(unsigned long long), ctx->stream) != hipSuccess) return fail(set_err(TL3D_E_HIP, "memset failed"));
     if (hipMalloc(&ctx->bounds_slab, 1024 * 6 * sizeof(float)) != hipSuccess) return fail(set_err(TL3D_E_NOMEM, "alloc failed"));
@@ -1079,6 +1092,8 @@ static int tile_cache_lookup(tl3d_ctx *ctx, hipStream_t ps, unsigned batch, int 
             s.vtile = (float2 *)(p + vt_off);
             s.vpix = (unsigned *)(p + vp_off);            // first word of the float4 behind the pyramid's last level
             s.tc_built = s.tc_read = false;
+            s.cls = ctx->cc_bytes ? (unsigned *)(p + ctx->tc_bytes) : nullptr;
+            s.cc_valid = s.cc_touched = false;
         }
         tiles[i] = s.tiles;
         bool shared = false;
@@ -1103,6 +1118,7 @@ static int tile_cache_lookup(tl3d_ctx *ctx, hipStream_t ps, unsigned batch, int 
                 waited_upd |= 1u << h;
             }
             stale[(*n_stale)++] = (unsigned char)i;
+            s.cc_valid = false;                          // the slot's classification was made from the tiles this build replaces
             s.tc_built = true;
             s.tc_scale_bits = bits; s.tc_mind = mind; s.tc_maxd = maxd;
             s.tc_build_batch = batch;
@@ -1117,6 +1133,85 @@ static int tile_cache_lookup(tl3d_ctx *ctx, hipStream_t ps, unsigned batch, int 
 static void tile_cache_forget(tl3d_ctx *ctx, int n, const int *slot_ids, const unsigned char *stale, int n_stale) {
     (void)n;
     for (int k = 0; k < n_stale; ++k) ctx->slots[slot_ids[stale[k]]].tc_built = false;
+}
+
+// ------------------------------------------------------------------------------------------- TSDF classification cache
+static ClassKey class_key(const PoseF &p, float scale, float mind, float maxd, const Grid &g) {
+    ClassKey k;
+    const float f[20] = {p.r[0], p.r[1], p.r[2], p.r[3], p.r[4], p.r[5], p.r[6], p.r[7], p.r[8], p.t[0], p.t[1], p.t[2], scale, mind, maxd,
+                         g.ox, g.oy, g.oz, g.vs, g.trunc};
+    memcpy(k.w, f, sizeof(f));
+    const int gi[6] = {g.nbx, g.nby, g.nbz, g.vox, g.voy, g.voz};
+    memcpy(k.w + 20, gi, sizeof(gi));
+    return k;
+}
+
+// How the classification kernels of the chain that tile_cache_lookup has just prepared treat each of its n frames (plan), and
+// whether the chain writes any slot's entry (*writes: bit i = frame i's; class_finish_kernel must run, class_cache_forget
+// undoes it).  A slot's entry serves when the cache is on, the entry is valid -- no tile rebuild since it was made, this
+// chain's included -- and its key is the frame's, bit for bit: the frame is REPLAYED (if it fit: the device knows).  Otherwise
+// the frame is classified and SAVED under its key.  A classify-only chain asks for level 1; a fusion that finds level 1 replays
+// it, classifies the sub-bricks and leaves level 2, which counts as a write.  One slot twice in a chain: the second use is a
+// replay if the first is one that writes nothing and the keys are equal, else it is classified without the cache.
+// Orders ps behind what it must not overtake (the table beside flush_updates); nothing to do on the main stream.
+static int class_cache_lookup(tl3d_ctx *ctx, hipStream_t ps, unsigned batch, int n, const int *slot_ids, const PoseF *poses, const float *scales, float mind,
+                              float maxd, const Grid &g, bool classify_only, ClassPlan *plan, unsigned *writes) {
+    memset(plan, 0, sizeof(*plan));
+    plan->cap = ctx->cc_entries;
+    plan->stats = ctx->d_cc_stats;
+    *writes = 0u;
+    if (!ctx->class_cache || !ctx->tile_cache) return TL3D_OK;      // every frame: CC_CLASSIFY
+    const bool side = ps != ctx->stream;
+    unsigned waited_prep = 0, waited_upd = 0;            // bit h: ps already waits for ev_prep[h] / ev_upd[h]
+    for (int i = 0; i < n; ++i) {
+        Slot &s = ctx->slots[slot_ids[i]];
+        const ClassKey key = class_key(poses[i], scales[i], mind, maxd, g);
+        int first = -1;
+        for (int j = 0; j < i && first < 0; ++j)
+            if (slot_ids[j] == slot_ids[i]) first = j;
+        if (first >= 0) {
+            if (class_mode(*plan, first) == CC_REPLAY && !((*writes >> first) & 1u) && memcmp(&key, &s.cc_key, sizeof(key)) == 0) {
+                class_set_mode(*plan, i, CC_REPLAY);
+                plan->cache[i] = s.cls;
+            }
+            continue;
+        }
+        if (!s.cls) return set_err(TL3D_E_STATE, "slot %d has no classification buffer", slot_ids[i]);      // (it comes with the tiles: tile_cache_lookup)
+        plan->cache[i] = s.cls;
+        const bool hit = s.cc_valid && memcmp(&key, &s.cc_key, sizeof(key)) == 0;
+        if (hit && (classify_only || s.cc_level >= 2)) {
+            class_set_mode(*plan, i, CC_REPLAY);
+            // saved by a batch on another prep stream that may still be at it: behind that chain
+            if (side && !batch_known_complete(ctx, s.cc_save_batch) && ctx->prep_stream[s.cc_save_batch % (unsigned)ctx->n_prep_streams] != ps) {
+                const unsigned h = s.cc_save_batch % (unsigned)TSDF_SCRATCHES;
+                if (!((waited_prep >> h) & 1u)) TL3D_HIP(hipStreamWaitEvent(ps, ctx->ev_prep[h], 0));
+                waited_prep |= 1u << h;
+            }
+        } else {
+            // a write (save under a new key, or level 1 -> 2) changes what the chains of up to three earlier batches may still
+            // read or write on other prep streams: behind the UPDATE of the last batch that used the entry -- it waited for that
+            // batch's chain, and the updates before it for theirs
+            if (side && s.cc_touched && !batch_known_complete(ctx, s.cc_touch_batch)) {
+                const unsigned h = s.cc_touch_batch % (unsigned)TSDF_SCRATCHES;
+                if (ctx->upd_recorded[h] && !((waited_upd >> h) & 1u)) TL3D_HIP(hipStreamWaitEvent(ps, ctx->ev_upd[h], 0));
+                waited_upd |= 1u << h;
+            }
+            class_set_mode(*plan, i, hit ? CC_REPLAY : CC_SAVE);
+            *writes |= 1u << i;
+            s.cc_valid = true;
+            s.cc_key = key;
+            s.cc_level = classify_only ? 1 : 2;
+            s.cc_save_batch = batch;
+        }
+        s.cc_touched = true;
+        s.cc_touch_batch = batch;
+    }
+    return TL3D_OK;
+}
+// a chain that was not issued (or not completely): what it was to write is not there
+static void class_cache_forget(tl3d_ctx *ctx, int n, const int *slot_ids, unsigned writes) {
+    for (int i = 0; i < n; ++i)
+        if ((writes >> i) & 1u) ctx->slots[slot_ids[i]].cc_valid = false;
 }
 
 // ------------------------------------------------------------------------------------------- occupancy of a planned grid
@@ -1183,11 +1278,17 @@ int tl3d_count_bricks(tl3d_ctx *ctx, const tl3d_config *cfg, int n_frames, const
             void *tiles[TL3D_TSDF_MAXBATCH];
             unsigned char stale[TL3D_TSDF_MAXBATCH];
             int n_stale = 0;
+            ClassPlan plan;
+            unsigned cwrites = 0;
             rc = tile_cache_lookup(ctx, ctx->stream, ctx->tsdf_batch_no - 1u, m, ids, sc, mind, maxd, tiles, stale, &n_stale);
+            if (!rc) rc = class_cache_lookup(ctx, ctx->stream, ctx->tsdf_batch_no - 1u, m, ids, poses, sc, mind, maxd, g, true, &plan, &cwrites);
             if (!rc && hipMemsetAsync((char *)scratch + zoff, 0, zbytes, ctx->stream) != hipSuccess) rc = set_err(TL3D_E_HIP, "memset failed");    // (no update re-arms the frame masks)
-            if (!rc) rc = launch_tsdf_prepare(ctx->stream, ctx->cam, g, m, batch, poses, fr, depths, false, sc, mind, maxd, scratch, free_cnt, tiles, stale, n_stale, true);
+            if (!rc) rc = launch_tsdf_prepare(ctx->stream, ctx->cam, g, m, batch, poses, fr, depths, false, sc, mind, maxd, scratch, free_cnt, tiles, stale, n_stale,
+                                              plan, cwrites != 0u, true);
+            if (!rc && plan.modes == 0ull) ctx->cc_classified_host += (unsigned long long)m;
             if (rc) {
                 tile_cache_forget(ctx, m, ids, stale, n_stale);
+                class_cache_forget(ctx, m, ids, cwrites);
                 (void)hipStreamSynchronize(ctx->stream);
                 ctx->tc_done_before = ctx->tsdf_batch_no;
                 return rc;
@@ -1344,6 +1445,15 @@ static int flush_centroid(tl3d_ctx *ctx) {
 //   chain of batch b (ps)                      ev_prep[h]                 update of batch b (main)
 //   tl3d_count_bricks: chains on the main stream, then a wait for it       every later batch (counted complete: tc_done_before)
 // A slot twice in one batch with one key: one build, shared.  With two keys the batch is cut in front of the second (tl3d_integrate).
+// ... and around its classification (Slot::cls; only prep chains touch it, the update never does):
+//   chain of batch r, b - 3 <= r < b, that    ev_prep[r % TSDF_SCRATCHES] a batch on ps that REPLAYS the entry; none if r's chain
+//     wrote the entry, on another prep stream                               ran on ps or the host has waited since
+//   update of batch r, b - 3 <= r < b, the    ev_upd[r % TSDF_SCRATCHES]  a chain on ps that WRITES the entry (new key, or masks
+//     last batch whose chain used the entry                                 added to a level-1 entry): it waited for r's chain, and
+//     (replay or write)                                                     the updates before it for the chains of earlier users
+//   a rebuild of the slot's tiles (above)     --                          drops the entry: the next look-up writes it anew
+//   tl3d_count_bricks: as for the tiles
+// A slot twice in one batch: one key and a complete entry, both replay it; otherwise the second use is classified without the cache.
 extern "C++" int tl3d::flush_updates(tl3d_ctx *ctx) {
     {
         const int crc = flush_centroid(ctx);
@@ -1379,11 +1489,16 @@ extern "C++" int tl3d::flush_updates(tl3d_ctx *ctx) {
     void *tiles[TL3D_TSDF_MAXBATCH];
     unsigned char stale[TL3D_TSDF_MAXBATCH];
     int n_stale = 0;
+    ClassPlan plan;
+    unsigned cwrites = 0;
     int rc = tile_cache_lookup(ctx, ps, ctx->tsdf_batch_no, n, ids, scales, mind, maxd, tiles, stale, &n_stale);
+    if (!rc) rc = class_cache_lookup(ctx, ps, ctx->tsdf_batch_no, n, ids, poses, scales, mind, maxd, ctx->grid, false, &plan, &cwrites);
     if (!rc) rc = launch_tsdf_prepare(ps, ctx->cam, ctx->grid, n, ctx->tsdf_batch, poses, fr, depths, u16, scales, mind, maxd, ctx->tsdf_scratch[half], ctx->free_cnt,
-                                      tiles, stale, n_stale);
+                                      tiles, stale, n_stale, plan, cwrites != 0u);
+    if (!rc && plan.modes == 0ull) ctx->cc_classified_host += (unsigned long long)n;     // (such a chain's kernels do not count)
     if (rc) {
         tile_cache_forget(ctx, n, ids, stale, n_stale);
+        class_cache_forget(ctx, n, ids, cwrites);
         return rc;
     }
     if (ps != ctx->stream) {
@@ -1449,7 +1564,23 @@ int tl3d_tile_cache_info(tl3d_ctx *ctx, uint64_t *builds, uint64_t *hits, uint64
     FLUSH_UPDATES(ctx);                                 // (look-ups happen when a batch is issued)
     if (builds) *builds = ctx->tc_builds;
     if (hits) *hits = ctx->tc_hits;
-    if (bytes) *bytes = (uint64_t)(ctx->cfg.n_slots - ctx->pool_tiles.remaining) * ctx->pool_tiles.block;
+    if (bytes) *bytes = (uint64_t)(ctx->cfg.n_slots - ctx->pool_tiles.remaining) * ctx->tc_bytes;
+    return TL3D_OK;
+}
+
+int tl3d_class_cache_info(tl3d_ctx *ctx, uint64_t *classified, uint64_t *replayed, uint64_t *overflowed, uint64_t *bytes) {
+    REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
+    FLUSH_UPDATES(ctx);                                 // (look-ups happen when a batch is issued)
+    TL3D_HIP(hipSetDevice(ctx->device));
+    // which path a frame took is the device's decision (only it knows whether the frame fit): its counters, behind every update
+    // issued so far and so behind every chain
+    unsigned long long h[4] = {0, 0, 0, 0};
+    TL3D_HIP(hipMemcpyAsync(h, ctx->d_cc_stats, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    TL3D_HIP(hipStreamSynchronize(ctx->stream));
+    if (classified) *classified = h[0] + ctx->cc_classified_host;
+    if (replayed) *replayed = h[1];
+    if (overflowed) *overflowed = h[2];
+    if (bytes) *bytes = (uint64_t)(ctx->cfg.n_slots - ctx->pool_tiles.remaining) * ctx->cc_bytes;
     return TL3D_OK;
 }
 

@@ -148,6 +148,27 @@ struct TrackArgs {
 };
 constexpr int TRACK_SUMS = 32;   // doubles per partial: the head of IcpState::sums
 
+// Everything the TSDF brick and sub-brick classification of a frame depends on besides the slot's tiles and the camera, as the
+// kernels get it (f32 words after the double -> float conversions); compared bitwise.
+struct ClassKey {
+    uint32_t w[26] = {};         // pose r[9] t[3], scale, min / max depth, nbx nby nbz, vox voy voz, ox oy oz vs, trunc
+};
+// How the classification kernels of one prep chain treat each frame (a kernel argument, indexed by the frame number).
+constexpr unsigned char CC_CLASSIFY = 0;    // classify, as without the cache
+constexpr unsigned char CC_SAVE = 1;        // classify and record the result in cache[f]
+constexpr unsigned char CC_REPLAY = 2;      // replay cache[f] if its header says the frame fit (the device knows), else classify
+constexpr int CC_HDR_WORDS = 16;            // header of a buffer: [0] MIXED entries, [1] FREE entries, [2] level, [3] 1 = complete
+struct ClassPlan {
+    unsigned *cache[32];         // [TL3D_TSDF_MAXBATCH] the slot's buffer: header, entries[cap] (MIXED from the front, FREE from the back), u16 masks[cap]
+    unsigned long long modes;    // two bits per frame (class_mode): a shift and a mask on the scalar unit; 0 = no frame of the chain uses the cache
+    unsigned cap;               // entries a buffer holds for this grid: min(configured entries, bricks of the grid)
+    int classify_only;
+    unsigned long long *stats;   // device counters: [0] frames classified, [1] replayed, [2] of the classified: did not fit (tl3d_class_cache_info)
+};
+__host__ __device__ __forceinline__ unsigned class_mode(const ClassPlan &P, int f) { return (unsigned)(P.modes >> (2 * f)) & 3u; }
+inline void class_set_mode(ClassPlan &P, int f, unsigned mode) { P.modes = (P.modes & ~(3ull << (2 * f))) | ((unsigned long long)mode << (2 * f)); }
+static_assert(sizeof(ClassPlan) <= 320, "ClassPlan travels as a kernel argument beside Grid, Cam and Pyramid (4 KB in all)");
+
 // Frame buffers come from slabs, not one hipMalloc per buffer: a 1000-frame context used to make (and, slower, free) 4000
 // allocations.  One pool per buffer kind (equal-sized blocks); a slab holds up to 64 blocks and lives until tl3d_destroy.
 constexpr int FRAME_SLAB_BLOCKS = 64;
@@ -187,6 +208,17 @@ struct Slot {
     bool tc_built = false;
     bool tc_read = false;        // some batch since the last upload has read or built the tiles: tc_reader_batch is its number
     unsigned tc_build_batch = 0, tc_reader_batch = 0;   // tl3d_ctx::tsdf_batch_no of the batch that built them / read them last
+    // TSDF classification cache: the brick cull's and the sub-brick classification's result for ONE key (ClassKey: pose, scale,
+    // depth limits, grid geometry), replayed when a batch meets the slot again with that key (kernels_tsdf.hip:
+    // class_replay_kernel).  It lives behind the tiles in the slot's block of tl3d_ctx::pool_tiles (tsdf_class_cache_bytes).  It is made from the
+    // slot's tiles: every rebuild of those drops it (tile_cache_lookup).  cc_level: 1 = lists and counts (what a classify-only
+    // chain can fill), 2 = + sub-brick masks.  Whether the frame FIT is known to the device alone (the buffer's header).
+    unsigned *cls = nullptr;
+    ClassKey cc_key;
+    bool cc_valid = false;
+    int cc_level = 0;
+    bool cc_touched = false;     // some chain has read or written the entry: cc_touch_batch is the last one's batch number
+    unsigned cc_save_batch = 0, cc_touch_batch = 0;     // batch whose chain wrote the entry last / used it last
 };
 
 // One part of a mesh weld (kernels_meshweld.hip) as the kernels see it: the part's arrays in device memory and the vertices and
@@ -307,6 +339,13 @@ struct tl3d_ctx : tl3d_grid_state {
     bool tile_cache;
     unsigned tc_done_before;
     unsigned long long tc_builds, tc_hits;
+    // TSDF classification cache (Slot::cls): off = every look-up classifies (env TL3D_CLASS_CACHE=0, or the tile cache off);
+    // entries per slot buffer (env TL3D_CLASS_CACHE_ENTRIES); both read when the context is created
+    bool class_cache;
+    unsigned cc_entries;
+    size_t tc_bytes, cc_bytes;            // of a slot's block in pool_tiles: the tiles' part, the classification buffer behind it (0: cache off)
+    unsigned long long *d_cc_stats;       // ClassPlan::stats (the four words behind d_counters' sixteen)
+    unsigned long long cc_classified_host;  // frames of chains in which no frame used the cache: their kernels are the plain ones and do not count
     struct PendingUpdate { int slot; tl3d::PoseF pose; float scale; } pend[TL3D_TSDF_MAXBATCH];
     tl3d::CenFrame cen_pend[tl3d::TL3D_CEN_MAXBATCH];   // voxel-centroid accumulations not yet launched (one stride per batch)
     int n_cen_pend = 0;
@@ -538,8 +577,9 @@ size_t tsdf_batch_scratch_bytes(const Cam &cam, const Grid &g, int max_frames);
 void tsdf_batch_scratch_zero_range(const Cam &cam, const Grid &g, int max_frames, size_t *off, size_t *bytes);
 int launch_tsdf_prepare(hipStream_t s, const Cam &cam, const Grid &g, int n, int max_frames, const PoseF *p, const Frustum &fr,
                         const void *const *depth, bool depth_u16, const float *scale, float mind, float maxd, void *scratch, unsigned *free_cnt,
-                        void *const *tiles, const unsigned char *stale, int n_stale, bool classify_only = false);
+                        void *const *tiles, const unsigned char *stale, int n_stale, const ClassPlan &plan, bool class_writes, bool classify_only = false);
 size_t tsdf_tile_cache_bytes(const Cam &cam, size_t *vtile_off, size_t *vpix_off);
+size_t tsdf_class_cache_bytes(unsigned entries);
 int launch_centroid_mark(hipStream_t s, const Cam &cam, const Grid &g, const BpArgs &a, const PoseD &p, const float *depth, const double *xf, const double *yf);
 #ifdef TL3D_EXPERIMENTS
 void tsdf_debug_print_spans(int nwaves);

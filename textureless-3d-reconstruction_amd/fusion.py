@@ -419,6 +419,12 @@ class FusionContext:
         abi.check(self._lib.tl3d_tile_cache_info(self._h, C.byref(b), C.byref(h), C.byref(m)))
         return int(b.value), int(h.value), int(m.value)
 
+    def class_cache_info(self):
+        """(classified, replayed, overflowed, bytes) of the per-slot TSDF classification cache, counts per frame (tl3d.h: tl3d_class_cache_info)."""
+        c, r, o, m = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        abi.check(self._lib.tl3d_class_cache_info(self._h, C.byref(c), C.byref(r), C.byref(o), C.byref(m)))
+        return int(c.value), int(r.value), int(o.value), int(m.value)
+
     # ---- fusion ----------------------------------------------------------------------------
     def accumulate_centroid(self, slot: int, pose=None, scale=1.0, subsample: int = 1, min_depth=None, max_depth=None,
                             scale_f64: bool = False):
