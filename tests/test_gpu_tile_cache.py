@@ -265,6 +265,30 @@ def test_count_then_fuse(wh):
     assert counts[True] == counts[False] and counts[True][0] > 0
 
 
+@pytest.mark.parametrize("wh", SIZES)
+def test_count_cuts_the_chain_at_a_second_scale(wh):
+    """One count of slots [0, 0, 1] at scales [1.0, 1.25, 1.0]: slot 0 needs two sets of tiles, so the call issues two chains and
+    builds three times (an uncut chain would share slot 0's build: two).  The counts are those of a context with the cache off and
+    of one where the second use has a slot of its own."""
+    w, h = wh
+    poses, frames = _frames(w, h)
+    scales = [1.0, 1.25, 1.0]
+    with _ctx(w, h) as ctx:
+        _upload_all(ctx, w, h)
+        cut = ctx.count_bricks(_spec(), [0, 0, 1], [poses[0], poses[0], poses[1]], scales, centroid_subsample=0)
+        builds = ctx.tile_cache_info()[0]
+    with _ctx(w, h, cache=False) as ctx:
+        _upload_all(ctx, w, h)
+        off = ctx.count_bricks(_spec(), [0, 0, 1], [poses[0], poses[0], poses[1]], scales, centroid_subsample=0)
+    with _ctx(w, h) as ctx:
+        _upload_all(ctx, w, h)
+        ctx.upload(2, frames[0])
+        own = ctx.count_bricks(_spec(), [0, 2, 1], [poses[0], poses[0], poses[1]], scales, centroid_subsample=0)
+    print("counts: cut", cut, "cache off", off, "own slot", own, "builds", builds)
+    assert cut[0] > 0 and cut == off and cut == own
+    assert builds == 3
+
+
 def _flight_plan(order):
     """70 integrates cycling over three slots; the scale alternates with every integrate (a slot meets both scales in turn: the
     batches are cut every three frames, a dozen in flight over the prep streams) or with every 32 (three full batches, each

@@ -1,4 +1,4 @@
-// api_host.h -- host helpers the translation units of the extern "C" surface share (tl3d_api.hip, api_mesh.hip, api_register.hip),
+// api_host.h -- host helpers the translation units of the extern "C" surface share (tl3d_api.hip, api_fuse.hip, api_mesh.hip, api_register.hip),
 // and the one scratch mechanism of the calls that need device memory of their own (scratch_carve).  Host code only.
 #pragma once
 #include "tl3d_internal.h"
@@ -137,12 +137,17 @@ template <class A, class B> int grow_pair(A **a, B **b, size_t *cap, size_t need
     return rc;
 }
 
-// what api_register.hip shares with tl3d_api.hip, where each is defined and described
+// what api_register.hip and api_fuse.hip share with tl3d_api.hip, where each is defined and described (flush_updates: api_fuse.hip)
 int check_slot(tl3d_ctx *ctx, int slot, bool need_loaded);
 int order_after_lanes(tl3d_ctx *ctx, int slot, bool rewrites_depth, bool rewrites_nmap);
 void *pool_take(FramePool &fp);
 int flush_updates(tl3d_ctx *ctx);
 int fold_free(tl3d_ctx *ctx);
+PoseD make_pose_d(const double R[9], const double t[3], bool no_pose);
+int make_bp_args(tl3d_ctx *ctx, double scale, uint32_t flags, int subsample, double min_d, double max_d, BpArgs *a);
+int validate_grid(const tl3d_config *cfg);
+void grid_geometry(Grid &g, const tl3d_config *cfg);
+int measure_max_weight(tl3d_ctx *ctx, const int2 *grid, long long *out);
 // every call that reads or writes the TSDF grid, re-uses a frame slot, synchronises or time-stamps first issues the deferred updates
 #define FLUSH_UPDATES(ctx_)                          \
     do {                                             \

@@ -370,7 +370,7 @@ __device__ __forceinline__ int classify_box(const Grid &g, float4 a, float zmin,
 // ---- the classification cache ------------------------------------------------------------------------------------------
 // What the cull and the sub-brick classification find for a frame depends on its pose, scale and depth limits, the camera, the
 // slot's tiles and the grid's geometry -- not on the grid's records, nor on any earlier batch.  A slot keeps the result of the
-// last classification made for it (Slot::cls; the host holds the key, tl3d_api.hip: class_cache_lookup) and a batch that meets
+// last classification made for it (Slot::cls; the host holds the key, api_fuse.hip: class_cache_lookup) and a batch that meets
 // the slot again with the same key REPLAYS it: class_replay_kernel walks the cached lists through the very tail the cull ends
 // with.  Buffer: [header: CC_HDR_WORDS] [entries: cap words, the MIXED bricks from the front as F->list gets them, the FREE
 // bricks from the back] [cap 16-bit sub-brick masks, one per MIXED entry, as F->sub[brick] holds them].  Only the device knows
@@ -1457,14 +1457,14 @@ static BatchBufs batch_bufs(const BatchLayout &L, void *scratch, int n) {
     return B;
 }
 
-// The whole prep of a batch of n frames (one depth kind) on stream s: descriptor upload, depth tiles and pyramid of the n_stale
-// frames stale[] (indices into the batch; the others' slots hold them already), resets + cell lists, brick classification,
-// sub-brick masks -- or, for the frames plan marks CC_REPLAY and whose buffer is complete, the replay of both; class_writes: the
-// chain writes cache entries (class_finish_kernel closes it).  tiles[i]: frame i's slot buffer (tsdf_tile_cache_bytes; frames of one slot share it and at most one of them is
-// stale).  `scratch` is a batch scratch of at least n frames (tsdf_batch_scratch_bytes).
-int launch_tsdf_prepare(hipStream_t s, const Cam &cam, const Grid &g, int n, int max_frames, const PoseF *p, const Frustum &fr,
-                        const void *const *depth, bool depth_u16, const float *scale, float mind, float maxd, void *scratch, unsigned *free_cnt,
-                        void *const *tiles, const unsigned char *stale, int n_stale, const ClassPlan &plan, bool class_writes, bool classify_only) {
+// The whole prep of the chain c (c.n frames, one depth kind) on stream s: descriptor upload, depth tiles and pyramid of the
+// c.n_stale frames c.stale[] (the others' slots hold them already), resets + cell lists, brick classification, sub-brick masks --
+// or, for the frames c.plan marks CC_REPLAY and whose buffer is complete, the replay of both; c.class_writes != 0: the chain writes
+// cache entries (class_finish_kernel closes it).  `scratch` is a batch scratch of at least c.n frames (tsdf_batch_scratch_bytes).
+int launch_tsdf_prepare(hipStream_t s, const Cam &cam, const Grid &g, const Frustum &fr, const PrepChain &c, int max_frames, void *scratch,
+                        unsigned *free_cnt, bool classify_only) {
+    const int n = c.n, n_stale = c.n_stale;
+    const bool class_writes = c.class_writes != 0u;
     if (n < 1 || n > max_frames || n > TL3D_TSDF_MAXBATCH) return set_err(TL3D_E_INVALID, "bad batch size %d", n);
     if (n_stale < 0 || n_stale > n) return set_err(TL3D_E_INVALID, "bad stale count %d", n_stale);
     size_t vt_off = 0;
@@ -1476,14 +1476,14 @@ int launch_tsdf_prepare(hipStream_t s, const Cam &cam, const Grid &g, int n, int
     memset(d, 0, sizeof(d));
     for (int i = 0; i < n; ++i) {
         char *fb = base + L.off_frames + L.per_frame * (size_t)i;
-        d[i].pose = p[i];
-        d[i].c = make_const(cam, scale[i], mind, maxd);
-        d[i].depth = depth[i];
+        d[i].pose = c.pose[i];
+        d[i].c = make_const(cam, c.scale[i], c.mind, c.maxd);
+        d[i].depth = c.depth[i];
         d[i].counts = reinterpret_cast<unsigned *>(fb + L.f_counts);
-        d[i].tiles = reinterpret_cast<float4 *>(tiles[i]);
+        d[i].tiles = reinterpret_cast<float4 *>(c.tiles[i]);
         d[i].list = reinterpret_cast<unsigned *>(fb + L.f_list);
         d[i].sub = reinterpret_cast<unsigned short *>(fb + L.f_sub);
-        d[i].vtile = reinterpret_cast<float2 *>(static_cast<char *>(tiles[i]) + vt_off);
+        d[i].vtile = reinterpret_cast<float2 *>(static_cast<char *>(c.tiles[i]) + vt_off);
         d[i].cells = reinterpret_cast<unsigned *>(fb + L.f_cells);
     }
     for (int i0 = 0; i0 < n; i0 += 16) {
@@ -1501,10 +1501,10 @@ int launch_tsdf_prepare(hipStream_t s, const Cam &cam, const Grid &g, int n, int
         StaleList sl;
         memset(&sl, 0, sizeof(sl));
         for (int i = 0; i < n_stale; ++i) {
-            if (stale[i] >= n) return set_err(TL3D_E_INVALID, "bad stale index %d", (int)stale[i]);
-            sl.idx[i] = stale[i];
+            if (c.stale[i] >= n) return set_err(TL3D_E_INVALID, "bad stale index %d", (int)c.stale[i]);
+            sl.idx[i] = c.stale[i];
         }
-        if (depth_u16)
+        if (c.depth_u16)
             hipLaunchKernelGGL(depth_tiles_kernel<uint16_t>, dim3((nreg + 3) / 4 < 512 ? (nreg + 3) / 4 : 512, n_stale), dim3(256), 0, s, cam, B, py, nrx, nry, sl);
         else
             hipLaunchKernelGGL(depth_tiles_kernel<float>, dim3((nreg + 3) / 4 < 512 ? (nreg + 3) / 4 : 512, n_stale), dim3(256), 0, s, cam, B, py, nrx, nry, sl);
@@ -1519,8 +1519,8 @@ int launch_tsdf_prepare(hipStream_t s, const Cam &cam, const Grid &g, int n, int
     // The classification cache (plan: the host's look-up): frames whose slot holds their classification are replayed, the cull
     // and the sub-brick classification return at once for them -- and the other way round.
     const int nbricks = g.nbx * g.nby * g.nbz;
-    ClassPlan P = plan;
-    P.cap = plan.cap < (unsigned)nbricks ? plan.cap : (unsigned)nbricks;
+    ClassPlan P = c.plan;
+    P.cap = P.cap < (unsigned)nbricks ? P.cap : (unsigned)nbricks;
     P.classify_only = classify_only ? 1 : 0;
     bool any_replay = false;
     for (int i = 0; i < n; ++i) {

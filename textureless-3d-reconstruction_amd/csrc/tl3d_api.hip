@@ -1,5 +1,5 @@
-// tl3d_api.hip -- the extern "C" surface declared in include/tl3d.h: context, frame slots, launch glue (the mesh calls: api_mesh.hip;
-// normal maps, ICP and tracking: api_register.hip), and the definitions of the host helpers api_host.h declares.
+// tl3d_api.hip -- the extern "C" surface declared in include/tl3d.h: context, frame slots, grids, launch glue (the mesh calls: api_mesh.hip;
+// normal maps, ICP and tracking: api_register.hip; fusion and brick counts: api_fuse.hip), and most of the host helpers api_host.h declares.
 #include <dlfcn.h>
 #include <stdarg.h>
 #include <stdlib.h>
@@ -102,14 +102,7 @@ int scratch_carve(tl3d_ctx *ctx, int stage, const size_t *bytes, int n, void **o
 }
 }  // namespace tl3d
 
-static PoseF make_pose_f(const double R[9], const double t[3]) {
-    PoseF p;
-    for (int i = 0; i < 9; ++i) p.r[i] = (float)R[i];
-    for (int i = 0; i < 3; ++i) p.t[i] = (float)t[i];
-    return p;
-}
-
-static PoseD make_pose_d(const double R[9], const double t[3], bool no_pose) {
+PoseD tl3d::make_pose_d(const double R[9], const double t[3], bool no_pose) {
     PoseD p;
     memset(&p, 0, sizeof(p));
     if (no_pose) {
@@ -121,19 +114,6 @@ static PoseD make_pose_d(const double R[9], const double t[3], bool no_pose) {
     return p;
 }
 
-static Frustum make_frustum(const Cam &c) {
-    // inside: aL <= x/z <= aR, aT <= y/z <= aB, widened by one pixel on every side
-    const double aL = (-1.5 - c.cxd) / c.fxd, aR = ((double)c.W + 0.5 - c.cxd) / c.fxd;
-    const double aT = (-1.5 - c.cyd) / c.fyd, aB = ((double)c.H + 0.5 - c.cyd) / c.fyd;
-    Frustum f;
-    double n;
-    n = sqrt(1.0 + aL * aL); f.lx = (float)(1.0 / n);  f.lz = (float)(-aL / n);
-    n = sqrt(1.0 + aR * aR); f.rx = (float)(-1.0 / n); f.rz = (float)(aR / n);
-    n = sqrt(1.0 + aT * aT); f.ty = (float)(1.0 / n);  f.tz = (float)(-aT / n);
-    n = sqrt(1.0 + aB * aB); f.by = (float)(-1.0 / n); f.bz = (float)(aB / n);
-    return f;
-}
-
 int tl3d::check_slot(tl3d_ctx *ctx, int slot, bool need_loaded) {
     REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
     REQUIRE(slot >= 0 && slot < ctx->cfg.n_slots, TL3D_E_INVALID, "slot %d out of range [0,%d)", slot, ctx->cfg.n_slots);
@@ -143,7 +123,6 @@ int tl3d::check_slot(tl3d_ctx *ctx, int slot, bool need_loaded) {
 
 static int upload_impl(tl3d_ctx *ctx, int slot, const void *depth_hd, int depth_kind, const uint8_t *bgr_hd, bool wait);
 static int bp_check_error(tl3d_ctx *ctx, unsigned long long err);
-static int flush_centroid(tl3d_ctx *ctx);
 
 // ICP lanes read slots[src].depth and slots[tgt].nmap on their own streams.  A call that rewrites one of those buffers on
 // the main stream (a new upload into the slot, a rebuilt normal map) is ordered behind every uncollected run that reads it.
@@ -160,7 +139,7 @@ int tl3d::order_after_lanes(tl3d_ctx *ctx, int slot, bool rewrites_depth, bool r
 }
 
 // exact largest voxel weight of the TSDF channel (blocks; the deferred updates must have been issued)
-static int measure_max_weight(tl3d_ctx *ctx, const int2 *grid, long long *out) {
+int tl3d::measure_max_weight(tl3d_ctx *ctx, const int2 *grid, long long *out) {
     if (!ctx->d_maxw && hipMalloc(&ctx->d_maxw, sizeof(int)) != hipSuccess) return set_err(TL3D_E_NOMEM, "alloc failed");
     // the context's own channel: the pool slots in use + the counts of bricks without records; anything else: a dense array
     int rc = grid == ctx->tsdf ? launch_max_weight(ctx->stream, ctx->grid, ctx->tsdf, ctx->d_maxw)
@@ -193,7 +172,7 @@ int tl3d::fold_free(tl3d_ctx *ctx) {
     return mark_free_cnt_write(ctx);
 }
 
-static int validate_grid(const tl3d_config *cfg) {
+int tl3d::validate_grid(const tl3d_config *cfg) {
     REQUIRE((cfg->channels & ~(TL3D_CH_TSDF | TL3D_CH_CENTROID)) == 0 && cfg->channels != 0, TL3D_E_INVALID, "bad channel bits 0x%x", cfg->channels);
     REQUIRE(cfg->nx > 0 && cfg->ny > 0 && cfg->nz > 0 && cfg->nx % TL3D_BRICK == 0 && cfg->ny % TL3D_BRICK == 0 &&
                 cfg->nz % TL3D_BRICK == 0,
@@ -243,7 +222,7 @@ static int reset_brick_tables(tl3d_ctx *ctx) {
     return TL3D_OK;
 }
 
-static void grid_geometry(Grid &g, const tl3d_config *cfg) {
+void tl3d::grid_geometry(Grid &g, const tl3d_config *cfg) {
     g.nx = cfg->nx; g.ny = cfg->ny; g.nz = cfg->nz;
     g.nbx = cfg->nx / 8; g.nby = cfg->ny / 8; g.nbz = cfg->nz / 8;
     g.oxd = cfg->origin[0]; g.oyd = cfg->origin[1]; g.ozd = cfg->origin[2]; g.vsd = cfg->voxel_size;
@@ -507,7 +486,6 @@ int tl3d_create(const tl3d_config *cfg, int device, tl3d_ctx **out) {
     c.fx = (float)cfg->fx; c.fy = (float)cfg->fy; c.cx = (float)cfg->cx; c.cy = (float)cfg->cy;
     Grid &g = ctx->grid;
     memset(&g, 0, sizeof(g));
-    int rc = TL3D_OK;
     auto fail = [&](int code) { tl3d_destroy(ctx); return code; };
 
     if (cfg->stream) {
@@ -538,7 +516,6 @@ int tl3d_create(const tl3d_config *cfg, int device, tl3d_ctx **out) {
     }
     for (int i = 0; i < 2; ++i)
         if (hipEventCreate(&ctx->ev[i]) != hipSuccess) return fail(set_err(TL3D_E_HIP, "event create failed"));
-    (void)rc;
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail(set_err(TL3D_E_HIP, "sync failed"));
     *out = ctx;
     return TL3D_OK;
@@ -753,6 +730,21 @@ int tl3d_host_copy_rows(uint8_t *dst, const uint8_t *const *rows, int height, si
 
 }  // extern "C"
 
+// The slot's depth image was rewritten on the main stream (an upload, a ray cast into the slot).  What was derived from the previous
+// frame is void: the normal map, the averaged depth, the TSDF tiles (their users are ahead of the writer on the main stream; the
+// classification goes when the tiles are rebuilt).  The prep streams wait on ev_upload, not on the whole main stream.
+static int slot_rewritten(tl3d_ctx *ctx, Slot &s, bool has_u16, bool has_color) {
+    s.has_u16 = has_u16;
+    s.has_color = has_color;
+    s.loaded = true;
+    s.has_normals = false;
+    s.smooth_radius = 0;
+    s.tc.valid = s.tc.used = false;
+    if (!s.ev_upload) TL3D_HIP(hipEventCreateWithFlags(&s.ev_upload, hipEventDisableTiming));
+    TL3D_HIP(hipEventRecord(s.ev_upload, ctx->stream));
+    return TL3D_OK;
+}
+
 static int upload_impl(tl3d_ctx *ctx, int slot, const void *depth_hd, int depth_kind, const uint8_t *bgr_hd, bool wait) {
     int rc = check_slot(ctx, slot, false);
     if (rc) return rc;
@@ -767,7 +759,6 @@ static int upload_impl(tl3d_ctx *ctx, int slot, const void *depth_hd, int depth_
     if (!s.depth && !(s.depth = (float *)pool_take(ctx->pool_depth))) return set_err(TL3D_E_NOMEM, "frame alloc failed");
     if (depth_kind == TL3D_DEPTH_F32_M) {
         TL3D_HIP(hipMemcpyAsync(s.depth, depth_hd, npx * sizeof(float), hipMemcpyDefault, ctx->stream));
-        s.has_u16 = false;
     } else {
         // the millimetre image stays beside its f32 conversion: the TSDF kernels gather from it (half the cache lines
         // under a brick's footprint) and convert with the same IEEE division, every other kernel reads the f32 copy
@@ -775,21 +766,13 @@ static int upload_impl(tl3d_ctx *ctx, int slot, const void *depth_hd, int depth_
         TL3D_HIP(hipMemcpyAsync(s.depth_u16, depth_hd, npx * sizeof(uint16_t), hipMemcpyDefault, ctx->stream));
         rc = launch_u16_to_f32(ctx->stream, s.depth_u16, s.depth, npx);
         if (rc) return rc;
-        s.has_u16 = true;
     }
     if (bgr_hd) {
         if (!s.bgr && !(s.bgr = (uint8_t *)pool_take(ctx->pool_bgr))) return set_err(TL3D_E_NOMEM, "frame alloc failed");
         TL3D_HIP(hipMemcpyAsync(s.bgr, bgr_hd, npx * 3, hipMemcpyDefault, ctx->stream));
-        s.has_color = true;
-    } else {
-        s.has_color = false;
     }
-    s.loaded = true;
-    s.has_normals = false;
-    s.smooth_radius = 0;                                 // (the averaged depth belongs to the previous frame of this slot)
-    s.tc_built = s.tc_read = false;                      // (so do the TSDF tiles; their readers are ahead of this upload on the main stream)
-    if (!s.ev_upload) TL3D_HIP(hipEventCreateWithFlags(&s.ev_upload, hipEventDisableTiming));
-    TL3D_HIP(hipEventRecord(s.ev_upload, ctx->stream));       // the prep stream waits on this, not on the whole main stream
+    rc = slot_rewritten(ctx, s, depth_kind == TL3D_DEPTH_U16_MM, bgr_hd != nullptr);
+    if (rc) return rc;
     // pageable host sources are consumed before hipMemcpyAsync returns only for small copies; make the hand-over explicit
     if (wait && (!is_device_ptr(depth_hd) || (bgr_hd && !is_device_ptr(bgr_hd)))) TL3D_HIP(hipStreamSynchronize(ctx->stream));
     return TL3D_OK;
@@ -889,7 +872,7 @@ int tl3d_download_depth(tl3d_ctx *ctx, int slot, float *out) {
 }
 
 // ------------------------------------------------------------------------------------------- back-projection
-static int make_bp_args(tl3d_ctx *ctx, double scale, uint32_t flags, int subsample, double min_d, double max_d, BpArgs *a) {
+extern "C++" int tl3d::make_bp_args(tl3d_ctx *ctx, double scale, uint32_t flags, int subsample, double min_d, double max_d, BpArgs *a) {
     REQUIRE(subsample >= 1, TL3D_E_INVALID, "subsample must be >= 1");
     REQUIRE((flags & ~(TL3D_F_SCALE_F64 | TL3D_F_NO_POSE)) == 0, TL3D_E_INVALID, "unknown flags 0x%x", flags);
     a->sub = subsample;
@@ -1064,301 +1047,6 @@ int tl3d_frame_bounds(tl3d_ctx *ctx, int slot, const double R[9], const double t
     return tl3d_frames_bounds(ctx, 1, &s, R, t, &scale, flags, subsample, min_depth, max_depth, out_min, out_max);
 }
 
-// ------------------------------------------------------------------------------------------- TSDF tile cache
-// every batch numbered b or lower has left the device: the host has waited since (tc_done_before), or the batch that is being
-// issued waits for the scratch of batch (its number - TSDF_SCRATCHES) and every update before that one is ahead of it
-static bool batch_known_complete(const tl3d_ctx *ctx, unsigned b) {
-    return (int)(b - ctx->tc_done_before) < 0 || ctx->tsdf_batch_no - b >= (unsigned)TSDF_SCRATCHES;
-}
-
-// The tile buffers of the n frames of one prep chain that is about to be issued on stream ps as batch number `batch`, and which of
-// the frames must build theirs (stale[]: indices into the chain, one per slot).  A slot's tiles serve when the cache is on,
-// they are built and their key (scale bits, depth limits) is the chain's; frames of one slot share one build (the caller has
-// cut the chain where a slot would need two keys).  Orders ps behind what it must not overtake (the table beside
-// flush_updates); ps == the main stream needs nothing: every update is on it and has waited for its own prep chain.
-static int tile_cache_lookup(tl3d_ctx *ctx, hipStream_t ps, unsigned batch, int n, const int *slot_ids, const float *scales, float mind, float maxd,
-                             void **tiles, unsigned char *stale, int *n_stale) {
-    const bool side = ps != ctx->stream;
-    unsigned waited_prep = 0, waited_upd = 0;            // bit h: ps already waits for ev_prep[h] / ev_upd[h]
-    size_t vt_off = 0, vp_off = 0;
-    (void)tsdf_tile_cache_bytes(ctx->cam, &vt_off, &vp_off);
-    *n_stale = 0;
-    for (int i = 0; i < n; ++i) {
-        Slot &s = ctx->slots[slot_ids[i]];
-        if (!s.tiles) {
-            char *p = (char *)pool_take(ctx->pool_tiles);
-            if (!p) return set_err(TL3D_E_NOMEM, "tile cache alloc failed");
-            s.tiles = (float4 *)p;
-            s.vtile = (float2 *)(p + vt_off);
-            s.vpix = (unsigned *)(p + vp_off);            // first word of the float4 behind the pyramid's last level
-            s.tc_built = s.tc_read = false;
-            s.cls = ctx->cc_bytes ? (unsigned *)(p + ctx->tc_bytes) : nullptr;
-            s.cc_valid = s.cc_touched = false;
-        }
-        tiles[i] = s.tiles;
-        bool shared = false;
-        for (int j = 0; j < i && !shared; ++j) shared = slot_ids[j] == slot_ids[i];
-        if (shared) { ctx->tc_hits++; continue; }
-        uint32_t bits;
-        memcpy(&bits, &scales[i], sizeof(bits));
-        if (ctx->tile_cache && s.tc_built && s.tc_scale_bits == bits && s.tc_mind == mind && s.tc_maxd == maxd) {
-            ctx->tc_hits++;
-            // built by a batch on another prep stream that may still be at it: behind that chain
-            if (side && !batch_known_complete(ctx, s.tc_build_batch) && ctx->prep_stream[s.tc_build_batch % (unsigned)ctx->n_prep_streams] != ps) {
-                const unsigned h = s.tc_build_batch % (unsigned)TSDF_SCRATCHES;
-                if (!((waited_prep >> h) & 1u)) TL3D_HIP(hipStreamWaitEvent(ps, ctx->ev_prep[h], 0));
-                waited_prep |= 1u << h;
-            }
-        } else {
-            // a rebuild overwrites what the chain and the update of the last reader may still read: behind that batch's update
-            // (an upload since then is ordered already: it sits behind every update, and ps waits for it)
-            if (side && s.tc_read && !batch_known_complete(ctx, s.tc_reader_batch)) {
-                const unsigned h = s.tc_reader_batch % (unsigned)TSDF_SCRATCHES;
-                if (ctx->upd_recorded[h] && !((waited_upd >> h) & 1u)) TL3D_HIP(hipStreamWaitEvent(ps, ctx->ev_upd[h], 0));
-                waited_upd |= 1u << h;
-            }
-            stale[(*n_stale)++] = (unsigned char)i;
-            s.cc_valid = false;                          // the slot's classification was made from the tiles this build replaces
-            s.tc_built = true;
-            s.tc_scale_bits = bits; s.tc_mind = mind; s.tc_maxd = maxd;
-            s.tc_build_batch = batch;
-            ctx->tc_builds++;
-        }
-        s.tc_read = true;
-        s.tc_reader_batch = batch;
-    }
-    return TL3D_OK;
-}
-// a chain that was not issued (or not completely): its builds did not happen
-static void tile_cache_forget(tl3d_ctx *ctx, int n, const int *slot_ids, const unsigned char *stale, int n_stale) {
-    (void)n;
-    for (int k = 0; k < n_stale; ++k) ctx->slots[slot_ids[stale[k]]].tc_built = false;
-}
-
-// ------------------------------------------------------------------------------------------- TSDF classification cache
-static ClassKey class_key(const PoseF &p, float scale, float mind, float maxd, const Grid &g) {
-    ClassKey k;
-    const float f[20] = {p.r[0], p.r[1], p.r[2], p.r[3], p.r[4], p.r[5], p.r[6], p.r[7], p.r[8], p.t[0], p.t[1], p.t[2], scale, mind, maxd,
-                         g.ox, g.oy, g.oz, g.vs, g.trunc};
-    memcpy(k.w, f, sizeof(f));
-    const int gi[6] = {g.nbx, g.nby, g.nbz, g.vox, g.voy, g.voz};
-    memcpy(k.w + 20, gi, sizeof(gi));
-    return k;
-}
-
-// How the classification kernels of the chain that tile_cache_lookup has just prepared treat each of its n frames (plan), and
-// whether the chain writes any slot's entry (*writes: bit i = frame i's; class_finish_kernel must run, class_cache_forget
-// undoes it).  A slot's entry serves when the cache is on, the entry is valid -- no tile rebuild since it was made, this
-// chain's included -- and its key is the frame's, bit for bit: the frame is REPLAYED (if it fit: the device knows).  Otherwise
-// the frame is classified and SAVED under its key.  A classify-only chain asks for level 1; a fusion that finds level 1 replays
-// it, classifies the sub-bricks and leaves level 2, which counts as a write.  One slot twice in a chain: the second use is a
-// replay if the first is one that writes nothing and the keys are equal, else it is classified without the cache.
-// Orders ps behind what it must not overtake (the table beside flush_updates); nothing to do on the main stream.
-static int class_cache_lookup(tl3d_ctx *ctx, hipStream_t ps, unsigned batch, int n, const int *slot_ids, const PoseF *poses, const float *scales, float mind,
-                              float maxd, const Grid &g, bool classify_only, ClassPlan *plan, unsigned *writes) {
-    memset(plan, 0, sizeof(*plan));
-    plan->cap = ctx->cc_entries;
-    plan->stats = ctx->d_cc_stats;
-    *writes = 0u;
-    if (!ctx->class_cache || !ctx->tile_cache) return TL3D_OK;      // every frame: CC_CLASSIFY
-    const bool side = ps != ctx->stream;
-    unsigned waited_prep = 0, waited_upd = 0;            // bit h: ps already waits for ev_prep[h] / ev_upd[h]
-    for (int i = 0; i < n; ++i) {
-        Slot &s = ctx->slots[slot_ids[i]];
-        const ClassKey key = class_key(poses[i], scales[i], mind, maxd, g);
-        int first = -1;
-        for (int j = 0; j < i && first < 0; ++j)
-            if (slot_ids[j] == slot_ids[i]) first = j;
-        if (first >= 0) {
-            if (class_mode(*plan, first) == CC_REPLAY && !((*writes >> first) & 1u) && memcmp(&key, &s.cc_key, sizeof(key)) == 0) {
-                class_set_mode(*plan, i, CC_REPLAY);
-                plan->cache[i] = s.cls;
-            }
-            continue;
-        }
-        if (!s.cls) return set_err(TL3D_E_STATE, "slot %d has no classification buffer", slot_ids[i]);      // (it comes with the tiles: tile_cache_lookup)
-        plan->cache[i] = s.cls;
-        const bool hit = s.cc_valid && memcmp(&key, &s.cc_key, sizeof(key)) == 0;
-        if (hit && (classify_only || s.cc_level >= 2)) {
-            class_set_mode(*plan, i, CC_REPLAY);
-            // saved by a batch on another prep stream that may still be at it: behind that chain
-            if (side && !batch_known_complete(ctx, s.cc_save_batch) && ctx->prep_stream[s.cc_save_batch % (unsigned)ctx->n_prep_streams] != ps) {
-                const unsigned h = s.cc_save_batch % (unsigned)TSDF_SCRATCHES;
-                if (!((waited_prep >> h) & 1u)) TL3D_HIP(hipStreamWaitEvent(ps, ctx->ev_prep[h], 0));
-                waited_prep |= 1u << h;
-            }
-        } else {
-            // a write (save under a new key, or level 1 -> 2) changes what the chains of up to three earlier batches may still
-            // read or write on other prep streams: behind the UPDATE of the last batch that used the entry -- it waited for that
-            // batch's chain, and the updates before it for theirs
-            if (side && s.cc_touched && !batch_known_complete(ctx, s.cc_touch_batch)) {
-                const unsigned h = s.cc_touch_batch % (unsigned)TSDF_SCRATCHES;
-                if (ctx->upd_recorded[h] && !((waited_upd >> h) & 1u)) TL3D_HIP(hipStreamWaitEvent(ps, ctx->ev_upd[h], 0));
-                waited_upd |= 1u << h;
-            }
-            class_set_mode(*plan, i, hit ? CC_REPLAY : CC_SAVE);
-            *writes |= 1u << i;
-            s.cc_valid = true;
-            s.cc_key = key;
-            s.cc_level = classify_only ? 1 : 2;
-            s.cc_save_batch = batch;
-        }
-        s.cc_touched = true;
-        s.cc_touch_batch = batch;
-    }
-    return TL3D_OK;
-}
-// a chain that was not issued (or not completely): what it was to write is not there
-static void class_cache_forget(tl3d_ctx *ctx, int n, const int *slot_ids, unsigned writes) {
-    for (int i = 0; i < n; ++i)
-        if ((writes >> i) & 1u) ctx->slots[slot_ids[i]].cc_valid = false;
-}
-
-// ------------------------------------------------------------------------------------------- occupancy of a planned grid
-// Which bricks of a grid (geometry only: no records, no pools) a fusion of these frames WOULD give records to: the TSDF
-// classification of every frame (tiles, pyramid, brick classes: the update's own prep chain, sub-brick masks and update left out)
-// and the bricks the frames' samples fall into, against scratch brick tables whose cursors count the distinct bricks.  What a
-// sparse grid's pools must hold (tl3d_config.pool_bricks_*): the reference's hash-map merge sizes itself (D2R:404-410); a pool is
-// allocated up front, and this is how to know how large -- a few microseconds per frame instead of a guess.
-int tl3d_count_bricks(tl3d_ctx *ctx, const tl3d_config *cfg, int n_frames, const int32_t *slots, const double *R, const double *t,
-                      const double *scales, int centroid_subsample, double min_depth, double max_depth, int64_t *bricks_tsdf,
-                      int64_t *bricks_centroid) {
-    REQUIRE(ctx && cfg && slots && R && t && bricks_tsdf && bricks_centroid, TL3D_E_INVALID, "null argument");
-    REQUIRE(n_frames >= 1, TL3D_E_INVALID, "n_frames must be positive");
-    int rc = validate_grid(cfg);
-    if (rc) return rc;
-    for (int i = 0; i < n_frames; ++i) {
-        rc = check_slot(ctx, slots[i], true);
-        if (rc) return rc;
-    }
-    FLUSH_UPDATES(ctx);
-    TL3D_HIP(hipSetDevice(ctx->device));
-    Grid g;
-    memset(&g, 0, sizeof(g));
-    grid_geometry(g, cfg);
-    const size_t nbr = ((size_t)g.nx * g.ny * g.nz) >> 9;
-    Staging st(ctx);                                    // the temporaries below go when the call returns, behind the stream
-    unsigned *tabs, *free_cnt = nullptr;
-    void *scratch = nullptr;
-    rc = st.scratch((2 * nbr + 64) * sizeof(unsigned), &tabs);
-    if (rc) return rc;
-    TL3D_HIP(hipMemsetAsync(tabs, 0xff, 2 * nbr * sizeof(unsigned), ctx->stream));
-    TL3D_HIP(hipMemsetAsync(tabs + 2 * nbr, 0, 64 * sizeof(unsigned), ctx->stream));
-    g.tsdf_tab = tabs; g.cen_tab = tabs + nbr; g.cursors = tabs + 2 * nbr;
-    g.tsdf_cap = g.cen_cap = (unsigned)nbr;
-    const float mind = (float)min_depth, maxd = (float)max_depth;
-    if (cfg->channels & TL3D_CH_TSDF) {
-        const int batch = TL3D_TSDF_MAXBATCH;
-        const size_t sb = tsdf_batch_scratch_bytes(ctx->cam, g, batch);
-        rc = st.scratch(nbr * sizeof(unsigned), &free_cnt);
-        if (!rc) rc = st.scratch(sb, &scratch);
-        if (rc) return rc;
-        size_t zoff = 0, zbytes = 0;
-        tsdf_batch_scratch_zero_range(ctx->cam, g, batch, &zoff, &zbytes);
-        TL3D_HIP(hipMemsetAsync(free_cnt, 0, nbr * sizeof(unsigned), ctx->stream));
-        const Frustum fr = make_frustum(ctx->cam);
-        // The chains run on the main stream, behind every update issued so far: the tiles they find are complete, the ones they
-        // build overwrite nothing a batch still reads, and the call ends with a wait for the stream -- numbered as the last issued
-        // batch they count as complete from then on.
-        for (int i0 = 0, m = 0; i0 < n_frames; i0 += m) {
-            PoseF poses[TL3D_TSDF_MAXBATCH];
-            const void *depths[TL3D_TSDF_MAXBATCH];
-            float sc[TL3D_TSDF_MAXBATCH];
-            int ids[TL3D_TSDF_MAXBATCH];
-            for (m = 0; m < batch && i0 + m < n_frames; ++m) {
-                const float scj = (float)(scales ? scales[i0 + m] : 1.0);
-                bool cut = false;                            // one slot at two scales: two sets of tiles, two chains
-                for (int j = 0; j < m && !cut; ++j) cut = ids[j] == slots[i0 + m] && memcmp(&sc[j], &scj, sizeof(float)) != 0;
-                if (cut) break;
-                poses[m] = make_pose_f(R + (size_t)9 * (i0 + m), t + (size_t)3 * (i0 + m));
-                depths[m] = ctx->slots[slots[i0 + m]].depth;
-                sc[m] = scj;
-                ids[m] = slots[i0 + m];
-            }
-            void *tiles[TL3D_TSDF_MAXBATCH];
-            unsigned char stale[TL3D_TSDF_MAXBATCH];
-            int n_stale = 0;
-            ClassPlan plan;
-            unsigned cwrites = 0;
-            rc = tile_cache_lookup(ctx, ctx->stream, ctx->tsdf_batch_no - 1u, m, ids, sc, mind, maxd, tiles, stale, &n_stale);
-            if (!rc) rc = class_cache_lookup(ctx, ctx->stream, ctx->tsdf_batch_no - 1u, m, ids, poses, sc, mind, maxd, g, true, &plan, &cwrites);
-            if (!rc && hipMemsetAsync((char *)scratch + zoff, 0, zbytes, ctx->stream) != hipSuccess) rc = set_err(TL3D_E_HIP, "memset failed");    // (no update re-arms the frame masks)
-            if (!rc) rc = launch_tsdf_prepare(ctx->stream, ctx->cam, g, m, batch, poses, fr, depths, false, sc, mind, maxd, scratch, free_cnt, tiles, stale, n_stale,
-                                              plan, cwrites != 0u, true);
-            if (!rc && plan.modes == 0ull) ctx->cc_classified_host += (unsigned long long)m;
-            if (rc) {
-                tile_cache_forget(ctx, m, ids, stale, n_stale);
-                class_cache_forget(ctx, m, ids, cwrites);
-                (void)hipStreamSynchronize(ctx->stream);
-                ctx->tc_done_before = ctx->tsdf_batch_no;
-                return rc;
-            }
-        }
-    }
-    if ((cfg->channels & TL3D_CH_CENTROID) && centroid_subsample >= 1) {
-        for (int i = 0; i < n_frames; ++i) {
-            BpArgs a;
-            rc = make_bp_args(ctx, scales ? scales[i] : 1.0, 0, centroid_subsample, min_depth, max_depth, &a);
-            if (rc) return rc;
-            const PoseD p = make_pose_d(R + (size_t)9 * i, t + (size_t)3 * i, false);
-            rc = launch_centroid_mark(ctx->stream, ctx->cam, g, a, p, ctx->slots[slots[i]].depth, ctx->bp_factors, ctx->bp_factors + ctx->cam.W);
-            if (rc) return rc;
-        }
-    }
-    unsigned cur[4] = {0, 0, 0, 0};
-    TL3D_HIP(hipMemcpyAsync(cur, g.cursors, sizeof(cur), hipMemcpyDeviceToHost, ctx->stream));
-    TL3D_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->tc_done_before = ctx->tsdf_batch_no;
-    *bricks_tsdf = (int64_t)(cur[0] < nbr ? cur[0] : nbr);
-    *bricks_centroid = (int64_t)(cur[2] < nbr ? cur[2] : nbr);
-    return TL3D_OK;
-}
-
-// ------------------------------------------------------------------------------------------- centroid accumulation
-int tl3d_accumulate_centroid(tl3d_ctx *ctx, int slot, const double R[9], const double t[3], double scale, uint32_t flags,
-                             int subsample, double min_depth, double max_depth) {
-    int rc = check_slot(ctx, slot, true);
-    if (rc) return rc;
-    REQUIRE(ctx->centroid != nullptr, TL3D_E_STATE, "centroid channel not enabled");
-    REQUIRE((flags & TL3D_F_NO_POSE) || (R && t), TL3D_E_INVALID, "pose required unless TL3D_F_NO_POSE");
-    BpArgs a;
-    rc = make_bp_args(ctx, scale, flags, subsample, min_depth, max_depth, &a);
-    if (rc) return rc;
-    const Slot &s = ctx->slots[slot];
-    // The frame joins the pending batch (one stride per batch); the batch goes out when it is full, or when any call needs the grid,
-    // a slot, a sync or a time stamp (flush_updates).  Integer sums: the grid does not depend on where the batches are cut.
-    if (ctx->n_cen_pend > 0 && ctx->cen_pend[0].a.sub != a.sub) {
-        rc = flush_centroid(ctx);
-        if (rc) return rc;
-    }
-    CenFrame &f = ctx->cen_pend[ctx->n_cen_pend++];
-    f.p = make_pose_d(R, t, (flags & TL3D_F_NO_POSE) != 0);
-    f.a = a;
-    f.depth = s.depth;
-    f.bgr = s.has_color ? s.bgr : nullptr;
-    if (ctx->n_cen_pend >= TL3D_CEN_MAXBATCH) return flush_centroid(ctx);
-    return TL3D_OK;
-}
-
-int tl3d_accumulate_points(tl3d_ctx *ctx, const float *xyz, const uint8_t *rgb, int64_t n) {
-    REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
-    REQUIRE(ctx->centroid != nullptr, TL3D_E_STATE, "centroid channel not enabled");
-    REQUIRE(n >= 0 && (n == 0 || (xyz && rgb)), TL3D_E_INVALID, "bad point list");
-    if (n == 0) return TL3D_OK;
-    TL3D_HIP(hipSetDevice(ctx->device));
-    Staging st(ctx);
-    const float *dxyz;
-    const uint8_t *drgb;
-    int rc = st.in(xyz, (size_t)n * 12, &dxyz);
-    if (!rc) rc = st.in(rgb, (size_t)n * 3, &drgb);
-    if (rc) return rc;
-    ctx->grid_epoch++;
-    rc = st.finish(launch_centroid_points(ctx->stream, ctx->grid, dxyz, drgb, n, ctx->centroid, ctx->d_cen_counters));
-    if (rc) return rc;
-    ctx->stats.centroid_launches++;
-    return TL3D_OK;
-}
-
 int tl3d_points_bounds(tl3d_ctx *ctx, const float *xyz, int64_t n, double out_min[3], double out_max[3]) {
     REQUIRE(ctx && xyz && out_min && out_max, TL3D_E_INVALID, "null argument");
     REQUIRE(n > 0, TL3D_E_INVALID, "empty point list has no bounds");
@@ -1380,225 +1068,6 @@ int tl3d_points_bounds(tl3d_ctx *ctx, const float *xyz, int64_t n, double out_mi
             out_min[a] = fmin(out_min[a], (double)h[(size_t)b * 6 + a]);
             out_max[a] = fmax(out_max[a], (double)h[(size_t)b * 6 + 3 + a]);
         }
-    return TL3D_OK;
-}
-
-// ------------------------------------------------------------------------------------------- TSDF
-static int ktimer_begin(tl3d_ctx *ctx) {
-    if (!ctx->time_kernels) return -1;
-    if (!ctx->ktimers) {
-        ctx->n_ktimers = 1024;
-        ctx->ktimers = new (std::nothrow) tl3d_ctx::KTimer[ctx->n_ktimers];
-        if (!ctx->ktimers) return -1;
-        for (int i = 0; i < ctx->n_ktimers; ++i) {
-            (void)hipEventCreate(&ctx->ktimers[i].a);
-            (void)hipEventCreate(&ctx->ktimers[i].b);
-        }
-        ctx->ktimers_used = 0;
-    }
-    if (ctx->ktimers_used == ctx->n_ktimers) {          // drain
-        (void)hipStreamSynchronize(ctx->stream);
-        for (int i = 0; i < ctx->ktimers_used; ++i) {
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, ctx->ktimers[i].a, ctx->ktimers[i].b) == hipSuccess) {
-                ctx->stats.tsdf_kernel_ms += ms;
-                ctx->stats.tsdf_kernel_timed += (uint64_t)ctx->ktimers[i].launches;
-            }
-        }
-        ctx->ktimers_used = 0;
-    }
-    const int id = ctx->ktimers_used++;
-    (void)hipEventRecord(ctx->ktimers[id].a, ctx->stream);
-    return id;
-}
-
-// Issues the pending batch: its prep chain on a side stream (it needs the frames' uploads, the batch scratch whose previous
-// user -- three batches ago -- has been updated, and the last clear / fold of the free-space counters), then ONE update launch on
-// the main stream behind it.  Results never depend on where the batch boundaries fall (integer sums).
-// the pending voxel-centroid accumulations: one launch for all of them (they share a stride)
-static int flush_centroid(tl3d_ctx *ctx) {
-    if (ctx->n_cen_pend == 0) return TL3D_OK;
-    const int n = ctx->n_cen_pend;
-    ctx->n_cen_pend = 0;                                // whatever happens below, the batch is consumed
-    TL3D_HIP(hipSetDevice(ctx->device));
-    if (!ctx->d_cen_frames && hipMalloc(&ctx->d_cen_frames, sizeof(CenFrame) * TL3D_CEN_MAXBATCH) != hipSuccess)
-        return set_err(TL3D_E_NOMEM, "centroid descriptor alloc failed");
-    ctx->grid_epoch++;
-    const int rc = launch_centroid_batch(ctx->stream, ctx->cam, ctx->grid, n, ctx->cen_pend, ctx->d_cen_frames, ctx->bp_factors, ctx->bp_factors + ctx->cam.W,
-                                         ctx->centroid, ctx->d_cen_counters);
-    if (rc) return rc;
-    ctx->stats.centroid_launches++;
-    return TL3D_OK;
-}
-
-// Who waits for whom around a slot's TSDF tiles (Slot::tiles; b = this batch's number, h = b % TSDF_SCRATCHES, ps = its prep stream):
-//   producer                                   event                      consumer
-//   upload / ray cast into the slot (main;     Slot::ev_upload            the build of batch b on ps (as the depth image itself)
-//     behind every earlier update, so behind
-//     every earlier reader of the tiles)
-//   update of batch b - TSDF_SCRATCHES (main;  ev_upd[h]                  everything of batch b on ps: covers every reader and
-//     it waited for that batch's chain)          (the scratch-reuse wait)   builder numbered b - TSDF_SCRATCHES or lower
-//   update of reader batch r, b - 3 <= r < b   ev_upd[r % TSDF_SCRATCHES] a REBUILD without an upload (key change, cache off) on ps;
-//     (last batch to read the slot's tiles)                                 never the latest update unless it is that reader
-//   build in batch r, b - 3 <= r < b, on       ev_prep[r % TSDF_SCRATCHES] a batch on ps that finds those tiles (hit); none if
-//     another prep stream                                                   the host has waited since (tc_done_before)
-//   chain of batch b (ps)                      ev_prep[h]                 update of batch b (main)
-//   tl3d_count_bricks: chains on the main stream, then a wait for it       every later batch (counted complete: tc_done_before)
-// A slot twice in one batch with one key: one build, shared.  With two keys the batch is cut in front of the second (tl3d_integrate).
-// ... and around its classification (Slot::cls; only prep chains touch it, the update never does):
-//   chain of batch r, b - 3 <= r < b, that    ev_prep[r % TSDF_SCRATCHES] a batch on ps that REPLAYS the entry; none if r's chain
-//     wrote the entry, on another prep stream                               ran on ps or the host has waited since
-//   update of batch r, b - 3 <= r < b, the    ev_upd[r % TSDF_SCRATCHES]  a chain on ps that WRITES the entry (new key, or masks
-//     last batch whose chain used the entry                                 added to a level-1 entry): it waited for r's chain, and
-//     (replay or write)                                                     the updates before it for the chains of earlier users
-//   a rebuild of the slot's tiles (above)     --                          drops the entry: the next look-up writes it anew
-//   tl3d_count_bricks: as for the tiles
-// A slot twice in one batch: one key and a complete entry, both replay it; otherwise the second use is classified without the cache.
-extern "C++" int tl3d::flush_updates(tl3d_ctx *ctx) {
-    {
-        const int crc = flush_centroid(ctx);
-        if (crc) return crc;
-    }
-    if (ctx->n_pend == 0) return TL3D_OK;
-    ctx->grid_epoch++;
-    TL3D_HIP(hipSetDevice(ctx->device));
-    const float mind = (float)ctx->cfg.min_depth, maxd = (float)ctx->cfg.max_depth;
-    const Frustum fr = make_frustum(ctx->cam);
-    const int n = ctx->n_pend;
-    ctx->n_pend = 0;                                    // whatever happens below, the batch is consumed
-    const int half = (int)(ctx->tsdf_batch_no % (unsigned)TSDF_SCRATCHES);
-    const bool u16 = ctx->pend_u16;
-    hipStream_t ps = ctx->tsdf_single_stream ? ctx->stream : ctx->prep_stream[ctx->tsdf_batch_no % (unsigned)ctx->n_prep_streams];
-    PoseF poses[TL3D_TSDF_MAXBATCH];
-    const void *depths[TL3D_TSDF_MAXBATCH];
-    float scales[TL3D_TSDF_MAXBATCH];
-    int ids[TL3D_TSDF_MAXBATCH];
-    for (int i = 0; i < n; ++i) {
-        const tl3d_ctx::PendingUpdate &w = ctx->pend[i];
-        const Slot &ws = ctx->slots[w.slot];
-        if (ps != ctx->stream && ws.ev_upload) TL3D_HIP(hipStreamWaitEvent(ps, ws.ev_upload, 0));
-        poses[i] = w.pose;
-        depths[i] = u16 ? (const void *)ws.depth_u16 : (const void *)ws.depth;
-        scales[i] = w.scale;
-        ids[i] = w.slot;
-    }
-    if (ps != ctx->stream) {
-        if (ctx->upd_recorded[half]) TL3D_HIP(hipStreamWaitEvent(ps, ctx->ev_upd[half], 0));
-        if (ctx->ev_free_recorded) TL3D_HIP(hipStreamWaitEvent(ps, ctx->ev_free, 0));      // clears / folds of the free-space counters
-    }
-    void *tiles[TL3D_TSDF_MAXBATCH];
-    unsigned char stale[TL3D_TSDF_MAXBATCH];
-    int n_stale = 0;
-    ClassPlan plan;
-    unsigned cwrites = 0;
-    int rc = tile_cache_lookup(ctx, ps, ctx->tsdf_batch_no, n, ids, scales, mind, maxd, tiles, stale, &n_stale);
-    if (!rc) rc = class_cache_lookup(ctx, ps, ctx->tsdf_batch_no, n, ids, poses, scales, mind, maxd, ctx->grid, false, &plan, &cwrites);
-    if (!rc) rc = launch_tsdf_prepare(ps, ctx->cam, ctx->grid, n, ctx->tsdf_batch, poses, fr, depths, u16, scales, mind, maxd, ctx->tsdf_scratch[half], ctx->free_cnt,
-                                      tiles, stale, n_stale, plan, cwrites != 0u);
-    if (!rc && plan.modes == 0ull) ctx->cc_classified_host += (unsigned long long)n;     // (such a chain's kernels do not count)
-    if (rc) {
-        tile_cache_forget(ctx, n, ids, stale, n_stale);
-        class_cache_forget(ctx, n, ids, cwrites);
-        return rc;
-    }
-    if (ps != ctx->stream) {
-        TL3D_HIP(hipEventRecord(ctx->ev_prep[half], ps));
-        TL3D_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_prep[half], 0));
-    }
-    // profiling mode: one event pair around the update kernel
-    const int kt = ktimer_begin(ctx);
-    rc = launch_tsdf_update(ctx->stream, ctx->cam, ctx->grid, n, ctx->tsdf_batch, u16, mind, maxd, ctx->tsdf, ctx->tsdf_scratch[half], ctx->d_counters,
-                            ctx->count_records, ctx->tsdf_max_blocks, ctx->tsdf_xcd_group);
-    if (rc == TL3D_OK) ctx->stats.tsdf_launches++;
-    if (kt >= 0) {
-        ctx->ktimers[kt].launches = rc == TL3D_OK ? 1 : 0;
-        (void)hipEventRecord(ctx->ktimers[kt].b, ctx->stream);
-    }
-    ctx->tsdf_batch_no++;
-    TL3D_HIP(hipEventRecord(ctx->ev_upd[half], ctx->stream));
-    ctx->upd_recorded[half] = true;
-    return rc;
-}
-
-int tl3d_integrate(tl3d_ctx *ctx, int slot, const double R[9], const double t[3], double scale) {
-    int rc = check_slot(ctx, slot, true);
-    if (rc) return rc;
-    REQUIRE(ctx->tsdf != nullptr, TL3D_E_STATE, "TSDF channel not enabled");
-    REQUIRE(R && t, TL3D_E_INVALID, "null pose");
-    TL3D_HIP(hipSetDevice(ctx->device));
-    const PoseF p = make_pose_f(R, t);
-    // int32 headroom: one more observation must keep every |sum_q| <= weight * 32767 below 2^31
-    if (ctx->tsdf_w_unknown || ctx->tsdf_w_upper + 1 > TL3D_TSDF_MAX_WEIGHT) {
-        FLUSH_AND_FOLD(ctx);
-        long long w = 0;
-        rc = measure_max_weight(ctx, ctx->tsdf, &w);
-        if (rc) return rc;
-        ctx->tsdf_w_upper = w;
-        ctx->tsdf_w_unknown = false;
-        REQUIRE(w + 1 <= TL3D_TSDF_MAX_WEIGHT, TL3D_E_STATE,
-                "a voxel already holds %lld observations: one more could overflow its int32 TSDF sum (limit %d); extract or reset the grid",
-                w, TL3D_TSDF_MAX_WEIGHT);
-    }
-    ctx->tsdf_w_upper++;
-    ctx->free_dirty = true;
-    const Slot &sl = ctx->slots[slot];
-    const bool u16 = sl.has_u16 && ctx->tsdf_use_u16;
-    // The frame joins the pending batch (one depth kind per batch); the batch goes out when it is full, or when any call needs
-    // the grid, a slot, a sync or a time stamp (flush_updates).
-    if (ctx->n_pend > 0 && ctx->pend_u16 != u16) FLUSH_UPDATES(ctx);
-    {   // ... and one set of tiles per slot: the same slot at another scale starts a new batch
-        const float scf = (float)scale;
-        bool cut = false;
-        for (int i = 0; i < ctx->n_pend && !cut; ++i) cut = ctx->pend[i].slot == slot && memcmp(&ctx->pend[i].scale, &scf, sizeof(float)) != 0;
-        if (cut) FLUSH_UPDATES(ctx);
-    }
-    ctx->pend_u16 = u16;
-    tl3d_ctx::PendingUpdate &u = ctx->pend[ctx->n_pend++];
-    u.slot = slot; u.pose = p; u.scale = (float)scale;
-    if (ctx->n_pend >= (ctx->tsdf_pairing ? ctx->tsdf_batch : 1)) return flush_updates(ctx);
-    return TL3D_OK;
-}
-
-int tl3d_tile_cache_info(tl3d_ctx *ctx, uint64_t *builds, uint64_t *hits, uint64_t *bytes) {
-    REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
-    FLUSH_UPDATES(ctx);                                 // (look-ups happen when a batch is issued)
-    if (builds) *builds = ctx->tc_builds;
-    if (hits) *hits = ctx->tc_hits;
-    if (bytes) *bytes = (uint64_t)(ctx->cfg.n_slots - ctx->pool_tiles.remaining) * ctx->tc_bytes;
-    return TL3D_OK;
-}
-
-int tl3d_class_cache_info(tl3d_ctx *ctx, uint64_t *classified, uint64_t *replayed, uint64_t *overflowed, uint64_t *bytes) {
-    REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
-    FLUSH_UPDATES(ctx);                                 // (look-ups happen when a batch is issued)
-    TL3D_HIP(hipSetDevice(ctx->device));
-    // which path a frame took is the device's decision (only it knows whether the frame fit): its counters, behind every update
-    // issued so far and so behind every chain
-    unsigned long long h[4] = {0, 0, 0, 0};
-    TL3D_HIP(hipMemcpyAsync(h, ctx->d_cc_stats, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-    TL3D_HIP(hipStreamSynchronize(ctx->stream));
-    if (classified) *classified = h[0] + ctx->cc_classified_host;
-    if (replayed) *replayed = h[1];
-    if (overflowed) *overflowed = h[2];
-    if (bytes) *bytes = (uint64_t)(ctx->cfg.n_slots - ctx->pool_tiles.remaining) * ctx->cc_bytes;
-    return TL3D_OK;
-}
-
-int tl3d_fuse_frames(tl3d_ctx *ctx, int n, const int32_t *slots, const double *R, const double *t, const double *scales,
-                     uint32_t flags, int centroid_subsample, double min_depth, double max_depth) {
-    REQUIRE(ctx && slots && R && t, TL3D_E_INVALID, "null argument");
-    REQUIRE(n >= 0, TL3D_E_INVALID, "n must not be negative");
-    for (int i = 0; i < n; ++i) {
-        const double sc = scales ? scales[i] : 1.0;
-        if (ctx->tsdf) {
-            const int rc = tl3d_integrate(ctx, slots[i], R + (size_t)9 * i, t + (size_t)3 * i, sc);
-            if (rc) return rc;
-        }
-        if (ctx->centroid && centroid_subsample >= 1) {
-            const int rc = tl3d_accumulate_centroid(ctx, slots[i], R + (size_t)9 * i, t + (size_t)3 * i, sc, flags, centroid_subsample, min_depth, max_depth);
-            if (rc) return rc;
-        }
-    }
     return TL3D_OK;
 }
 
@@ -2125,15 +1594,8 @@ int tl3d_raycast(tl3d_ctx *ctx, const double R[9], const double t[3], int min_we
                         (float *)dn, (uint8_t *)dc, sc);
     if (rc) return rc;
     if (slot >= 0) {                                     // the slot now holds an f32 frame, as after an upload
-        Slot &s = ctx->slots[slot];
-        s.has_u16 = false;
-        s.has_color = s.bgr != nullptr;
-        s.loaded = true;
-        s.has_normals = false;
-        s.smooth_radius = 0;
-        s.tc_built = s.tc_read = false;
-        if (!s.ev_upload) TL3D_HIP(hipEventCreateWithFlags(&s.ev_upload, hipEventDisableTiming));
-        TL3D_HIP(hipEventRecord(s.ev_upload, ctx->stream));
+        rc = slot_rewritten(ctx, ctx->slots[slot], false, sc != nullptr);
+        if (rc) return rc;
     }
     if (depth_out && dd != depth_out) TL3D_HIP(hipMemcpyAsync(depth_out, dd, npx * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     if (normal_out && dn != normal_out) TL3D_HIP(hipMemcpyAsync(normal_out, dn, npx * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));

@@ -169,6 +169,30 @@ __host__ __device__ __forceinline__ unsigned class_mode(const ClassPlan &P, int 
 inline void class_set_mode(ClassPlan &P, int f, unsigned mode) { P.modes = (P.modes & ~(3ull << (2 * f))) | ((unsigned long long)mode << (2 * f)); }
 static_assert(sizeof(ClassPlan) <= 320, "ClassPlan travels as a kernel argument beside Grid, Cam and Pyramid (4 KB in all)");
 
+// A product kept in a slot's cache block (Slot::tc: the tiles, Slot::cc: the classification), beside its key: who wrote it and who
+// used it last.  What a prep chain waits for before it reads or overwrites the product follows from these four (api_fuse.hip: ChainOrder).
+struct Cached {
+    bool valid = false;          // the product is there, made under the key beside it
+    bool used = false;           // some chain has read or written it (the tiles: since the slot's last upload): use_batch is the last one's number
+    unsigned write_batch = 0, use_batch = 0;    // tl3d_ctx::tsdf_batch_no of the batch whose chain wrote it last / used it last
+};
+
+// The frames of one prep chain and what the cache look-ups decided for them (api_fuse.hip: issue_prep_chain, launch_tsdf_prepare)
+struct PrepChain {
+    int n;                       // frames
+    bool depth_u16;              // depth[] are millimetre images (one depth kind and one pair of limits per chain)
+    float mind, maxd;
+    int slot[32];                // [TL3D_TSDF_MAXBATCH], as the next five
+    PoseF pose[32];
+    float scale[32];
+    const void *depth[32];
+    void *tiles[32];             // the slot's tile buffer (tsdf_tile_cache_bytes); frames of one slot share it and at most one of them is stale
+    unsigned char stale[32];     // the n_stale frames (indices into the chain, one per slot) that build their tiles
+    int n_stale;
+    ClassPlan plan;
+    unsigned class_writes;       // bit i: the chain writes frame i's classification entry (class_finish_kernel closes it)
+};
+
 // Frame buffers come from slabs, not one hipMalloc per buffer: a 1000-frame context used to make (and, slower, free) 4000
 // allocations.  One pool per buffer kind (equal-sized blocks); a slab holds up to 64 blocks and lives until tl3d_destroy.
 constexpr int FRAME_SLAB_BLOCKS = 64;
@@ -198,27 +222,23 @@ struct Slot {
     bool has_normals = false;
     // TSDF tile cache: what the TSDF prep derives from the depth image, the scale and the depth limits alone (kernels_tsdf.hip:
     // depth_tiles_kernel, tile_pyramid_kernel).  One lazily allocated block (tl3d_ctx::pool_tiles, tsdf_tile_cache_bytes) and the
-    // key it was built with; every writer of `depth` clears tc_built.  The u16 and f32 images give the same tiles (mm_to_m is
-    // the conversion the f32 copy was made with, no contraction, no fast math), so the depth kind is not part of the key.
+    // key it was built with; every writer of `depth` calls slot_rewritten (tl3d_api.hip), which clears tc.  The u16 and f32 images give
+    // the same tiles (mm_to_m is the conversion the f32 copy was made with, no contraction, no fast math): the depth kind is no part of the key.
     float4 *tiles = nullptr;     // pyramid, all levels; the float4 behind the last level holds ...
     unsigned *vpix = nullptr;    // ... the frame's valid pixel (device word)
     float2 *vtile = nullptr;     // level-0 tiles as 8-B records
     uint32_t tc_scale_bits = 0;  // key: bits of the f32 scale, the depth limits
     float tc_mind = 0, tc_maxd = 0;
-    bool tc_built = false;
-    bool tc_read = false;        // some batch since the last upload has read or built the tiles: tc_reader_batch is its number
-    unsigned tc_build_batch = 0, tc_reader_batch = 0;   // tl3d_ctx::tsdf_batch_no of the batch that built them / read them last
+    Cached tc;
     // TSDF classification cache: the brick cull's and the sub-brick classification's result for ONE key (ClassKey: pose, scale,
     // depth limits, grid geometry), replayed when a batch meets the slot again with that key (kernels_tsdf.hip:
     // class_replay_kernel).  It lives behind the tiles in the slot's block of tl3d_ctx::pool_tiles (tsdf_class_cache_bytes).  It is made from the
-    // slot's tiles: every rebuild of those drops it (tile_cache_lookup).  cc_level: 1 = lists and counts (what a classify-only
-    // chain can fill), 2 = + sub-brick masks.  Whether the frame FIT is known to the device alone (the buffer's header).
+    // slot's tiles: every rebuild of those drops it (api_fuse.hip: tile_cache_lookup).  cc_level: 1 = lists and counts (what a
+    // classify-only chain can fill), 2 = + sub-brick masks.  Whether the frame FIT is known to the device alone (the buffer's header).
     unsigned *cls = nullptr;
-    ClassKey cc_key;
-    bool cc_valid = false;
+    ClassKey cc_key;             // key, with cc_level
     int cc_level = 0;
-    bool cc_touched = false;     // some chain has read or written the entry: cc_touch_batch is the last one's batch number
-    unsigned cc_save_batch = 0, cc_touch_batch = 0;     // batch whose chain wrote the entry last / used it last
+    Cached cc;
 };
 
 // One part of a mesh weld (kernels_meshweld.hip) as the kernels see it: the part's arrays in device memory and the vertices and
@@ -328,11 +348,10 @@ struct tl3d_ctx : tl3d_grid_state {
     hipStream_t prep_stream[4];  // consecutive BATCHES take them in turn (three by default: one per batch scratch)
     int n_prep_streams;
     bool tsdf_pairing;                    // frames of a batch share ONE update launch (tl3d_set_tsdf_pairing(ctx, 0): one frame per launch)
-    bool pend_u16;                        // depth kind of the pending batch (a batch holds one kind)
     hipEvent_t ev_prep[TSDF_SCRATCHES];                // prep of the batch using scratch h is done (recorded on its prep stream)
     bool tsdf_use_u16;                    // gather from the millimetre image when the slot has one (env TL3D_U16_GATHER=0: never)
     int tsdf_batch;                       // frames per batch (env TL3D_TSDF_BATCH, default 32; 1 = no deferral)
-    unsigned tsdf_seq, tsdf_batch_no;
+    unsigned tsdf_batch_no;
     // TSDF tile cache (Slot::tiles): off = every look-up is a miss (env TL3D_TILE_CACHE=0, read when the context is created);
     // every batch numbered below tc_done_before is known complete on the device (the host has waited since); per-frame builds
     // and look-ups that found tiles (tl3d_tile_cache_info)
@@ -346,7 +365,7 @@ struct tl3d_ctx : tl3d_grid_state {
     size_t tc_bytes, cc_bytes;            // of a slot's block in pool_tiles: the tiles' part, the classification buffer behind it (0: cache off)
     unsigned long long *d_cc_stats;       // ClassPlan::stats (the four words behind d_counters' sixteen)
     unsigned long long cc_classified_host;  // frames of chains in which no frame used the cache: their kernels are the plain ones and do not count
-    struct PendingUpdate { int slot; tl3d::PoseF pose; float scale; } pend[TL3D_TSDF_MAXBATCH];
+    tl3d::PrepChain pend;                 // the batch being collected (tl3d_integrate fills slot, pose, scale, depth and depth_u16; the rest is flush_updates')
     tl3d::CenFrame cen_pend[tl3d::TL3D_CEN_MAXBATCH];   // voxel-centroid accumulations not yet launched (one stride per batch)
     int n_cen_pend = 0;
     tl3d::CenFrame *d_cen_frames = nullptr;              // their descriptors on the device
@@ -422,7 +441,6 @@ struct tl3d_ctx : tl3d_grid_state {
     tl3d_stats stats;
     bool count_records, time_kernels;
     hipEvent_t ev[2];
-    hipEvent_t kev0, kev1;
     struct KTimer { hipEvent_t a, b; int launches; };   // one event pair around `launches` back-to-back update kernels
     KTimer *ktimers;
     int n_ktimers, ktimers_used;
@@ -575,9 +593,8 @@ int launch_bounds(hipStream_t s, const float *xyz, long long n, float *slab, int
 // tsdf
 size_t tsdf_batch_scratch_bytes(const Cam &cam, const Grid &g, int max_frames);
 void tsdf_batch_scratch_zero_range(const Cam &cam, const Grid &g, int max_frames, size_t *off, size_t *bytes);
-int launch_tsdf_prepare(hipStream_t s, const Cam &cam, const Grid &g, int n, int max_frames, const PoseF *p, const Frustum &fr,
-                        const void *const *depth, bool depth_u16, const float *scale, float mind, float maxd, void *scratch, unsigned *free_cnt,
-                        void *const *tiles, const unsigned char *stale, int n_stale, const ClassPlan &plan, bool class_writes, bool classify_only = false);
+int launch_tsdf_prepare(hipStream_t s, const Cam &cam, const Grid &g, const Frustum &fr, const PrepChain &c, int max_frames, void *scratch,
+                        unsigned *free_cnt, bool classify_only);
 size_t tsdf_tile_cache_bytes(const Cam &cam, size_t *vtile_off, size_t *vpix_off);
 size_t tsdf_class_cache_bytes(unsigned entries);
 int launch_centroid_mark(hipStream_t s, const Cam &cam, const Grid &g, const BpArgs &a, const PoseD &p, const float *depth, const double *xf, const double *yf);
