@@ -49,9 +49,22 @@ def main(argv=None):
                         help="a distance threshold of --compare-to, in metres (repeatable, at most 8; default 0.005 0.01 0.02)")
     parser.add_argument("--compare-max-dist", type=float, default=None, metavar="M",
                         help="points with no neighbour within this distance count as unmatched (default: no limit)")
+    parser.add_argument("--cloud-normals", action="store_true",
+                        help="give the fused cloud per-point normals on the GPU (PCA over the nearest neighbours, turned towards the "
+                             "nearest camera) and write them as nx ny nz")
+    parser.add_argument("--cloud-normals-neighbors", type=int, default=30, metavar="K",
+                        help="neighbours of --cloud-normals, the point itself included (3..64; default 30)")
+    parser.add_argument("--cloud-normals-radius", type=float, default=0.0, metavar="M",
+                        help="neighbours further than this many metres are left out (default 0: no limit)")
+    parser.add_argument("--cloud-curvature", action="store_true",
+                        help="with --cloud-normals: also write the surface variation l0 / (l0 + l1 + l2) as `curvature`")
     parser.add_argument("--device", type=int, default=0)
     args = parser.parse_args(argv)
 
+    if args.cloud_curvature and not args.cloud_normals:
+        parser.error("--cloud-curvature comes out of the normal estimation: it needs --cloud-normals")
+    if not 3 <= args.cloud_normals_neighbors <= 64:
+        parser.error("--cloud-normals-neighbors must lie in [3, 64]")
     if args.compare_threshold and len(args.compare_threshold) > 8:
         parser.error("--compare-threshold: at most 8 thresholds")
     from tl3d import fileio
@@ -70,6 +83,8 @@ def main(argv=None):
     config = ReconstructionConfig(fx=args.fx, fy=args.fy, cx=args.cx, cy=args.cy, min_depth=0.1, max_depth=100.0,
                                   voxel_size=0.005, subsample_factor=4, grid_dim=args.grid, device=args.device,
                                   depth_scale=args.depth_scale, loop_closure=args.loop_closure, model_tracking=args.model_tracking,
+                                  cloud_normals=args.cloud_normals, cloud_normals_neighbors=args.cloud_normals_neighbors,
+                                  cloud_normals_radius=args.cloud_normals_radius, cloud_curvature=args.cloud_curvature,
                                   compare_to=args.compare_to, compare_max_dist=args.compare_max_dist,
                                   compare_thresholds=tuple(args.compare_threshold) if args.compare_threshold else (0.005, 0.01, 0.02),
                                   outlier_filter=False)                   # DER's merge_pointclouds has no outlier filter (DER:615-645)
@@ -124,7 +139,8 @@ def main(argv=None):
         return 0
     points, colors, poses = result
     out_dir.mkdir(parents=True, exist_ok=True)
-    fileio.save_reconstruction(points, colors, out_dir / "reconstruction.ply")
+    fileio.save_reconstruction(points, colors, out_dir / "reconstruction.ply", normals=pipeline.cloud_normals,
+                               curvature=pipeline.cloud_curvature)
     print(f"Saved {len(points)} points to {out_dir / 'reconstruction.ply'}")
     return 0
 

@@ -105,6 +105,15 @@ def main(argv=None):
                         help="a distance threshold of --compare-to, in metres (repeatable, at most 8; default 0.005 0.01 0.02)")
     parser.add_argument("--compare-max-dist", type=float, default=None, metavar="M",
                         help="points with no neighbour within this distance count as unmatched (default: no limit)")
+    parser.add_argument("--cloud-normals", action="store_true",
+                        help="give the fused cloud per-point normals on the GPU (PCA over the nearest neighbours, turned towards the "
+                             "nearest camera) and write them as nx ny nz")
+    parser.add_argument("--cloud-normals-neighbors", type=int, default=30, metavar="K",
+                        help="neighbours of --cloud-normals, the point itself included (3..64; default 30)")
+    parser.add_argument("--cloud-normals-radius", type=float, default=0.0, metavar="M",
+                        help="neighbours further than this many metres are left out (default 0: no limit)")
+    parser.add_argument("--cloud-curvature", action="store_true",
+                        help="with --cloud-normals: also write the surface variation l0 / (l0 + l1 + l2) as `curvature`")
     parser.add_argument("--device", type=int, default=0)
     parser.add_argument("--stream", dest="stream", action="store_true", default=True,
                         help="(default) decode on worker threads into pinned buffers with asynchronous uploads; host RAM never holds the sequence")
@@ -128,6 +137,10 @@ def main(argv=None):
         parser.error("--mesh-smooth / --mesh-normals work on the mesh: they need --mesh-output")
     if args.mesh_weld != "host" and not args.mesh_output:
         parser.error("--mesh-weld device welds the mesh: it needs --mesh-output")
+    if args.cloud_curvature and not args.cloud_normals:
+        parser.error("--cloud-curvature comes out of the normal estimation: it needs --cloud-normals")
+    if not 3 <= args.cloud_normals_neighbors <= 64:
+        parser.error("--cloud-normals-neighbors must lie in [3, 64]")
     if args.compare_threshold and len(args.compare_threshold) > 8:
         parser.error("--compare-threshold: at most 8 thresholds")
     if args.loop_closure and (args.gpus > 1 or world > 1):
@@ -157,6 +170,8 @@ def main(argv=None):
                                   mesh_largest_component=args.mesh_largest_component, mesh_simplify_cell=args.mesh_simplify_cell,
                                   mesh_simplify_placement=args.mesh_simplify_placement,
                                   mesh_smooth_iterations=args.mesh_smooth, mesh_normals=args.mesh_normals, mesh_weld=args.mesh_weld,
+                                  cloud_normals=args.cloud_normals, cloud_normals_neighbors=args.cloud_normals_neighbors,
+                                  cloud_normals_radius=args.cloud_normals_radius, cloud_curvature=args.cloud_curvature,
                                   compare_to=args.compare_to, compare_max_dist=args.compare_max_dist,
                                   compare_thresholds=tuple(args.compare_threshold) if args.compare_threshold else (0.005, 0.01, 0.02))
     pipeline = DepthToReconstructionPipeline(config)
@@ -189,7 +204,8 @@ def main(argv=None):
     else:
         points, colors, poses = pipeline.reconstruct(anchors=anchors, estimate_scale=args.estimate_scale)
     if points is not None and len(points) > 0:
-        pipeline.save_reconstruction(points, colors, args.output, ascii=args.ascii)
+        pipeline.save_reconstruction(points, colors, args.output, ascii=args.ascii, normals=pipeline.cloud_normals,
+                                     curvature=pipeline.cloud_curvature)
         if args.mesh_output:
             pipeline.save_mesh(args.mesh_output, ascii=args.ascii)
         if not args.no_vis:

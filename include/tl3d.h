@@ -614,6 +614,36 @@ int tl3d_statistical_outlier(tl3d_ctx *ctx, const float *xyz_hd, int64_t n, int 
  * search grid (doubled until it has at most 2^27 cells); the result does not depend on it. */
 int tl3d_knn_mean_distance(tl3d_ctx *ctx, const float *xyz_hd, int64_t n, int nb_neighbors, double cell_size, double *mean_out_hd);
 
+/* Normals and surface variation of a point list by PCA over each point's k nearest neighbours (no reference
+ * code: the reference's cloud carries positions and colours only -- the definition is Open3D's estimate_normals followed by
+ * orient_normals_towards_camera_location, and PCL's surface variation).  Host or device pointers for xyz, normal_out [n][3] and
+ * curvature_out [n] (may be NULL); viewpoints is a HOST array [m][3] (may be NULL with m = 0); out_degenerate may be NULL; no grid
+ * is needed.
+ * Neighbourhood of point i: the min(nb_neighbors, n) points that are smallest under the order (d^2, index), d^2 the fp64 sum of
+ * squares of the fp64 differences of the f32 coordinates; the point itself is one of them and an exact tie goes to the smaller
+ * index (the rule of tl3d_nearest_points).  max_radius > 0 then drops every member with d^2 > max_radius * max_radius (one fp64
+ * product; a point exactly on the radius stays); max_radius <= 0: no limit.
+ * Covariance, all in fp64, the k' members summed in their (d^2, index) order: e_j = p_j - p_i (exact), m = (sum e_j) / k',
+ * C = sum (e_j - m)(e_j - m)^T (two passes, no division: scale does not matter).  That order is why the result is the same bytes
+ * for every cell_size and in every run.
+ * normal_out[i] = the unit eigenvector of C's smallest eigenvalue l0 (l0 <= l1 <= l2; cyclic Jacobi in fp64, accurate when two
+ * eigenvalues are close), rounded to f32 at the end; curvature_out[i] = l0 / (l0 + l1 + l2) as f32, 0 when the sum is 0.
+ * Degenerate: fewer than 3 members left, or l2 == 0 (all members coincide, C is exactly 0): normal (0,0,0), curvature 0, counted in
+ * *out_degenerate.  A collinear neighbourhood is not degenerate: it gets some unit vector perpendicular to the line.
+ * Orientation: with n_viewpoints > 0 point i looks at its nearest viewpoint c (nearest by (d^2, index) in fp64 over all of them);
+ * the fp64 normal is negated before rounding when n . (c - p_i) < 0, and left as the unoriented call gives it when that is
+ * exactly 0.  Without viewpoints the sign is unspecified, but the same in every run.
+ * nb_neighbors in [3, 64]; cell_size > 0 only sets the search grid (doubled until it has at most 2^27 cells) and never changes a
+ * result; n == 0 is TL3D_OK.  TL3D_E_INVALID before any device work, with nothing written: a null ctx, xyz or normal_out, n < 0 or
+ * n >= 2^31, n_viewpoints < 0 (or > 0 with a null pointer), a non-finite viewpoint, an output that overlaps the input or the other
+ * output; and from the device pass in front of the search, with nothing written: a non-finite coordinate.
+ * Tests (tests/test_gpu_cloud_normals.py): sin(angle to an fp64 reference) <= 2^-22 + 1024 * 2^-52 * l2 / (l1 - l0) per point,
+ * exact answers on lattices with ties, the same bytes for every cell size, for host and device arrays and in every run. */
+int tl3d_estimate_normals(tl3d_ctx *ctx, const float *xyz_hd, int64_t n,
+                          int nb_neighbors, double max_radius, double cell_size,
+                          const double *viewpoints_h, int64_t n_viewpoints,
+                          float *normal_out_hd, float *curvature_out_hd, int64_t *out_degenerate);
+
 /* Exact nearest neighbours from one set to ANOTHER (no reference code: the reference never scores a cloud -- the
  * definition is Open3D's compute_point_cloud_distance).  Per query point q: dist_out[q] = the fp64 distance to the nearest target
  * point (differences of the f32 coordinates, squares and their sum in fp64, one correctly rounded root) and index_out[q] = its index;

@@ -102,6 +102,14 @@ class ReconstructionConfig:
     compare_to: Optional[str] = None
     compare_thresholds: tuple = (0.005, 0.01, 0.02)
     compare_max_dist: Optional[float] = None
+    # normals (and surface variation) of the fused cloud: PCA over each point's cloud_normals_neighbors
+    # nearest neighbours (Open3D's max_nn), none further than cloud_normals_radius metres (0: no limit), turned towards the nearest
+    # kept camera; once over the whole cloud, after the outlier filter.  DepthToReconstructionPipeline.cloud_normals /
+    # .cloud_curvature, written by save_reconstruction as nx ny nz / curvature.  cloud_curvature needs cloud_normals.  Off: nothing changes.
+    cloud_normals: bool = False
+    cloud_normals_neighbors: int = 30
+    cloud_normals_radius: float = 0.0
+    cloud_curvature: bool = False
 
     @property
     def K(self) -> np.ndarray:

@@ -366,6 +366,22 @@ static unsigned long long nn_bounds_fold(const float *h, long long n, double mn[
     return bad;
 }
 
+// the same pass for a caller outside this file (kernels_normals.hip): the box of the finite points of a device list and the number
+// of points with a non-finite coordinate
+int points_bounds_finite(tl3d_ctx *ctx, const float *xyz, long long n, double mn[3], double mx[3], unsigned long long *bad) {
+    hipStream_t s = ctx->stream;
+    const int rc = cell_slab(ctx);
+    if (rc) return rc;
+    float *slab = (float *)ctx->cg_slab;
+    std::vector<float> h((size_t)NN_RED * 8);
+    nn_bounds_launch(s, xyz, n, slab);
+    NN_HIP(hipGetLastError());
+    NN_HIP(hipMemcpyAsync(h.data(), slab, h.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+    NN_HIP(hipStreamSynchronize(s));
+    *bad = nn_bounds_fold(h.data(), n, mn, mx);
+    return TL3D_OK;
+}
+
 // Default cell of a point target: the box has V = the product of its non-zero extents (k of them) and n points; cell = (V / (4 n))^(1/k),
 // i.e. four cells per point if the points filled the box -- surface clouds fill a thin sheet of it, and end near ten points per
 // occupied cell.  A box without extent is one cell.

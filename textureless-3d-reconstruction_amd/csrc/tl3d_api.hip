@@ -1643,6 +1643,37 @@ int tl3d_knn_mean_distance(tl3d_ctx *ctx, const float *xyz, int64_t n, int nb_ne
     return st.finish(sor_mean_distance(ctx, dx, n, nb_neighbors, cell_size, &dm), true);
 }
 
+// ------------------------------------------------------------------------------------------- cloud normals
+int tl3d_estimate_normals(tl3d_ctx *ctx, const float *xyz, int64_t n, int nb_neighbors, double max_radius, double cell_size,
+                          const double *viewpoints, int64_t n_viewpoints, float *normal_out, float *curvature_out, int64_t *out_degenerate) {
+    REQUIRE(ctx && xyz && normal_out, TL3D_E_INVALID, "null argument");
+    REQUIRE(n >= 0 && n < (1ll << 31), TL3D_E_INVALID, "n %lld: indices need 0 <= n < 2^31", (long long)n);
+    REQUIRE(nb_neighbors >= 3 && nb_neighbors <= 64, TL3D_E_INVALID, "nb_neighbors must be in [3,64]");
+    REQUIRE(cell_size > 0, TL3D_E_INVALID, "cell_size must be positive");
+    REQUIRE(n_viewpoints >= 0 && n_viewpoints < (1ll << 31) && (n_viewpoints == 0 || viewpoints), TL3D_E_INVALID, "bad viewpoint list");
+    for (int64_t i = 0; i < 3 * n_viewpoints; ++i) REQUIRE(isfinite(viewpoints[i]), TL3D_E_INVALID, "viewpoint %lld is not finite", (long long)(i / 3));
+    const size_t nb_x = (size_t)n * 12, nb_c = (size_t)n * 4;
+    REQUIRE(!ranges_overlap(normal_out, nb_x, xyz, nb_x) && !ranges_overlap(curvature_out, nb_c, xyz, nb_x), TL3D_E_INVALID, "an output aliases the input");
+    REQUIRE(!ranges_overlap(normal_out, nb_x, curvature_out, nb_c), TL3D_E_INVALID, "the outputs alias each other");
+    if (n == 0) {
+        if (out_degenerate) *out_degenerate = 0;
+        return TL3D_OK;
+    }
+    TL3D_HIP(hipSetDevice(ctx->device));
+    Staging st(ctx);
+    const float *dx;
+    float *dn, *dc = nullptr;
+    int rc = st.in(xyz, nb_x, &dx);
+    if (!rc) rc = st.out(normal_out, nb_x, &dn);
+    if (!rc && curvature_out) rc = st.out(curvature_out, nb_c, &dc);
+    if (rc) return rc;
+    long long deg = 0;
+    rc = st.finish(normals_run(ctx, dx, n, nb_neighbors, max_radius, cell_size, viewpoints, n_viewpoints, dn, dc, &deg), true);
+    if (rc) return rc;
+    if (out_degenerate) *out_degenerate = deg;
+    return TL3D_OK;
+}
+
 // ------------------------------------------------------------------------------------------- nearest neighbours, distance summary
 // what both searches check before any device work
 static int nn_check(tl3d_ctx *ctx, const float *query, int64_t n_query, const void *const *ins, const size_t *in_bytes, int n_ins,

@@ -690,6 +690,12 @@ int nearest_points_run(tl3d_ctx *ctx, const float *query, long long nq, const fl
 int nearest_triangles_run(tl3d_ctx *ctx, const float *query, long long nq, const float *xyz, long long nv, const unsigned *tri, long long n_tri,
                           double cell, double max_dist, double *dist, int *index);
 int distance_summary_run(tl3d_ctx *ctx, const double *dist, long long n, const double *thresholds, int nthr, tl3d_distance_stats *out);
+// the searches' validation pass alone: the box of a device list's finite points and the number of non-finite ones (waits for the stream)
+int points_bounds_finite(tl3d_ctx *ctx, const float *xyz_dev, long long n, double mn[3], double mx[3], unsigned long long *bad);
+
+// normals and surface variation by k-NN PCA (kernels_normals.hip); device pointers but the viewpoints (host), curvature may be null
+int normals_run(tl3d_ctx *ctx, const float *xyz, long long n, int k, double max_radius, double cell, const double *vp_host, long long n_vp,
+                float *normal, float *curvature, long long *degenerate);
 
 // mesh smoothing and vertex normals (kernels_meshsmooth.hip)
 int launch_msm_validate(hipStream_t s, const float *xyz, long long n_vert, unsigned long long *info);

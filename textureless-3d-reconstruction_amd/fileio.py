@@ -513,31 +513,62 @@ def save_depth_like_processor(depth_m: np.ndarray, out_dir, frame_id: str):
 _HEADER_TAIL = ["property uchar red", "property uchar green", "property uchar blue", "end_header"]
 
 
-def write_ply_ascii(path, points, colors):
+def _cloud_attributes(n, normals, curvature):
+    """normals f32 [n,3] / curvature f32 [n] of a cloud of n points as the writers take them (either may be None)."""
+    if normals is not None:
+        normals = np.asarray(normals, dtype=np.float32).reshape(-1, 3)
+        assert len(normals) == n, "one normal per point"
+    if curvature is not None:
+        curvature = np.asarray(curvature, dtype=np.float32).reshape(-1)
+        assert len(curvature) == n, "one curvature per point"
+    return normals, curvature
+
+
+def write_ply_ascii(path, points, colors, normals=None, curvature=None):
     """The reference's fallback writer byte for byte (D2R:689-701): `float` xyz printed with Python's str() of the
-    numpy scalar, colours as integers."""
+    numpy scalar, colours as integers.  normals (f32 [n,3]): the record becomes `x y z nx ny nz red green blue`, the order
+    Open3D and MeshLab read (write_ply_mesh's); curvature (f32 [n]): a `float curvature` last.  Without both: the reference's bytes."""
+    normals, curvature = _cloud_attributes(len(points), normals, curvature)
     with open(path, "w") as f:
         f.write("ply\nformat ascii 1.0\n")
         f.write(f"element vertex {len(points)}\n")
         f.write("property float x\nproperty float y\nproperty float z\n")
-        f.write("\n".join(_HEADER_TAIL) + "\n")
-        for p, c in zip(points, colors):
-            f.write(f"{p[0]} {p[1]} {p[2]} {int(c[0])} {int(c[1])} {int(c[2])}\n")
+        if normals is not None:
+            f.write("property float nx\nproperty float ny\nproperty float nz\n")
+        f.write("\n".join(_HEADER_TAIL[:3] + (["property float curvature"] if curvature is not None else []) + _HEADER_TAIL[3:]) + "\n")
+        if normals is None and curvature is None:
+            for p, c in zip(points, colors):
+                f.write(f"{p[0]} {p[1]} {p[2]} {int(c[0])} {int(c[1])} {int(c[2])}\n")
+            return
+        for i, (p, c) in enumerate(zip(points, colors)):
+            n = "" if normals is None else f"{normals[i, 0]} {normals[i, 1]} {normals[i, 2]} "
+            k = "" if curvature is None else f" {curvature[i]}"
+            f.write(f"{p[0]} {p[1]} {p[2]} {n}{int(c[0])} {int(c[1])} {int(c[2])}{k}\n")
 
 
-def write_ply_binary(path, points, colors, double_xyz: bool = True):
+def write_ply_binary(path, points, colors, double_xyz: bool = True, normals=None, curvature=None):
     """binary_little_endian PLY, vertices only.  double_xyz=True is the layout Open3D's write_point_cloud emits for
     the reference (D2R:684-687: points are Vector3dVector, i.e. fp64) -- from Open3D's source as remembered, not
-    verifiable in this image."""
+    verifiable in this image.  normals (f32 [n,3]): `nx ny nz` of the type of x y z between the position and the colour (the order
+    Open3D and MeshLab read); curvature (f32 [n]): a `float curvature` last.  Without both every byte is as ever."""
     pts = np.asarray(points)
     col = np.asarray(colors, dtype=np.uint8)
+    normals, curvature = _cloud_attributes(len(pts), normals, curvature)
     ft, fname = ("<f8", "double") if double_xyz else ("<f4", "float")
-    rec = np.empty(len(pts), dtype=[("x", ft), ("y", ft), ("z", ft), ("r", "u1"), ("g", "u1"), ("b", "u1")])
+    nfields = [] if normals is None else [("nx", ft), ("ny", ft), ("nz", ft)]
+    cfields = [] if curvature is None else [("curvature", "<f4")]
+    rec = np.empty(len(pts), dtype=[("x", ft), ("y", ft), ("z", ft), *nfields, ("r", "u1"), ("g", "u1"), ("b", "u1"), *cfields])
     if len(pts):
         rec["x"], rec["y"], rec["z"] = pts[:, 0], pts[:, 1], pts[:, 2]
         rec["r"], rec["g"], rec["b"] = col[:, 0], col[:, 1], col[:, 2]
+        if normals is not None:
+            rec["nx"], rec["ny"], rec["nz"] = normals[:, 0], normals[:, 1], normals[:, 2]
+        if curvature is not None:
+            rec["curvature"] = curvature
     header = "\n".join(["ply", "format binary_little_endian 1.0", f"element vertex {len(pts)}",
-                        f"property {fname} x", f"property {fname} y", f"property {fname} z"] + _HEADER_TAIL) + "\n"
+                        f"property {fname} x", f"property {fname} y", f"property {fname} z"]
+                       + [f"property {fname} {a}" for a, _ in nfields] + _HEADER_TAIL[:3]
+                       + ["property float curvature" for _ in cfields] + _HEADER_TAIL[3:]) + "\n"
     with open(path, "wb") as f:
         f.write(header.encode("ascii"))
         f.write(rec.tobytes())
@@ -588,18 +619,19 @@ def write_ply_mesh(path, xyz, rgb, tris, ascii: bool = False, normals=None):
         f.write(frec.tobytes())
 
 
-def save_reconstruction(points, colors, output_path, ascii: bool = False) -> bool:
+def save_reconstruction(points, colors, output_path, ascii: bool = False, normals=None, curvature=None) -> bool:
     """DepthToReconstructionPipeline.save_reconstruction (D2R:673-703): empty input prints `No points to save` and
-    writes nothing; parent directories are created; prints `Saved to <path>`."""
+    writes nothing; parent directories are created; prints `Saved to <path>`.  normals / curvature: per-point attributes the
+    writers add to the vertex record (write_ply_binary, write_ply_ascii); without them the file is the reference's."""
     if len(points) == 0:
         print("No points to save")
         return False
     filepath = Path(output_path)
     filepath.parent.mkdir(parents=True, exist_ok=True)
     if ascii:
-        write_ply_ascii(filepath, points, colors)
+        write_ply_ascii(filepath, points, colors, normals=normals, curvature=curvature)
     else:
-        write_ply_binary(filepath, points, colors)
+        write_ply_binary(filepath, points, colors, normals=normals, curvature=curvature)
     print(f"Saved to {filepath}")
     return True
 

@@ -258,6 +258,7 @@ class FusionContext:
         self.grid = grid
         self.device = int(device)
         self.n_slots = int(n_slots)
+        self.last_normals_degenerate = 0           # degenerate neighbourhoods of the last estimate_normals()
 
     # ---- lifetime --------------------------------------------------------------------------
     def close(self):
@@ -914,6 +915,36 @@ class FusionContext:
         cell = float(cell_size if cell_size is not None else (self.grid.voxel_size * 2 if self.grid else 0.01))
         abi.check(self._lib.tl3d_knn_mean_distance(self._h, abi.ptr(xyz), len(xyz), int(nb_neighbors), cell, abi.ptr(mean)))
         return mean
+
+    def estimate_normals(self, xyz, nb_neighbors=30, max_radius=0.0, viewpoints=None, cell_size=None, curvature=False):
+        """normals float32 [n,3], or (normals, curvature float32 [n]) with curvature=True: per point the unit eigenvector of the
+        smallest eigenvalue of the covariance of its nb_neighbors nearest neighbours (itself included, k clamped to n, an exact tie
+        to the smaller index; max_radius > 0 drops neighbours beyond it), and the surface variation l0 / (l0 + l1 + l2) (DESIGN.md
+        section 4.5).  viewpoints [m,3]: every normal is turned towards the viewpoint nearest its point; without them the sign is
+        arbitrary but fixed.  Points with fewer than 3 neighbours left, or whose neighbours all coincide, get (0,0,0) and 0;
+        last_normals_degenerate counts them.  cell_size sets the search grid only; the result does not depend on it.
+        numpy in, numpy out; a torch device tensor in, device tensors out."""
+        xyz = self._points(xyz)
+        n = len(xyz)
+        if hasattr(xyz, "data_ptr"):
+            import torch
+            normals = torch.empty((n, 3), dtype=torch.float32, device=xyz.device)
+            curv = torch.empty((n,), dtype=torch.float32, device=xyz.device) if curvature else None
+        else:
+            normals = np.empty((n, 3), np.float32)
+            curv = np.empty((n,), np.float32) if curvature else None
+        vp = None
+        if viewpoints is not None:
+            vp = np.ascontiguousarray(viewpoints, dtype=np.float64).reshape(-1, 3)
+        cell = float(cell_size if cell_size is not None else (self.grid.voxel_size * 2 if self.grid else 0.01))
+        deg = C.c_int64(0)
+        self.last_normals_degenerate = 0
+        if n:
+            abi.check(self._lib.tl3d_estimate_normals(self._h, abi.ptr(xyz), n, int(nb_neighbors), float(max_radius), cell,
+                                                      abi.ptr(vp) if vp is not None and len(vp) else None, len(vp) if vp is not None else 0,
+                                                      abi.ptr(normals), abi.ptr(curv) if curvature else None, C.byref(deg)))
+        self.last_normals_degenerate = int(deg.value)
+        return (normals, curv) if curvature else normals
 
     # ---- distances between sets (DESIGN.md section 4.4; none of it needs a grid) -----------
     @staticmethod

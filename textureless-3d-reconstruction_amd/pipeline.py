@@ -157,6 +157,8 @@ class DepthToReconstructionPipeline:
         self.blocks: List[GridSpec] = []          # the grids it was fused in (one, or the blocks of a lattice beyond one grid)
         self.mesh_normals = None                  # f32 [V,3] of that mesh when config.mesh_normals, else None
         self.mesh = None                          # (xyz f32 [V,3], rgb u8 [V,3], tris u32 [T,3]) of the last reconstruct(), config.extract_mesh
+        self.cloud_normals = None                 # f32 [N,3] of the returned points when config.cloud_normals, else None
+        self.cloud_curvature = None               # f32 [N] of the returned points when config.cloud_curvature, else None
 
     # ---- a2 --------------------------------------------------------------------------------------
     def load_data(self, rgb_folder: str, depth_folder: str) -> int:
@@ -462,9 +464,11 @@ class DepthToReconstructionPipeline:
         """
         self.mesh = None
         self.mesh_normals = None
+        self.cloud_normals = self.cloud_curvature = None
         cfg = self.config
         self._check_mesh_filter_config()
         self._check_mesh_weld_config()
+        self._check_cloud_normals_config()
         loop = bool(getattr(cfg, "loop_closure", False)) and poses is None      # with poses given nothing is registered: the option is ignored
         if loop and estimate_scale:
             raise ValueError("loop_closure does not go with estimate_scale: the pose graph's edges carry no scale")
@@ -585,6 +589,22 @@ class DepthToReconstructionPipeline:
             xyz, rgb = xyz[keep], rgb[keep]
         return xyz, rgb, dict(voxels=n_vox, after_outlier_filter=len(xyz))
 
+    def _estimate_cloud_normals(self, ctx: FusionContext, xyz, voxel_size) -> float:
+        """config.cloud_normals: normals (and curvature) of the cleaned cloud, every normal turned towards the nearest kept camera's
+        centre -R^T t; once over the whole cloud, so a blocked run shows no seam.  Leaves cloud_normals /
+        cloud_curvature (rows match xyz) and stats["cloud_normals"]; returns the seconds it took."""
+        cfg = self.config
+        t0 = time.perf_counter()
+        k, radius = int(cfg.cloud_normals_neighbors), float(cfg.cloud_normals_radius)
+        centres = np.array([-np.asarray(R, np.float64).T @ np.asarray(t, np.float64).reshape(3) for R, t in self.camera_poses],
+                           np.float64).reshape(-1, 3)
+        out = ctx.estimate_normals(xyz, k, max_radius=radius, viewpoints=centres, cell_size=2.0 * voxel_size,
+                                   curvature=bool(cfg.cloud_curvature))
+        self.cloud_normals, self.cloud_curvature = out if cfg.cloud_curvature else (out, None)
+        self.stats["cloud_normals"] = dict(neighbors=k, radius=radius, viewpoints=len(centres), degenerate=ctx.last_normals_degenerate)
+        print(f"  Cloud normals: {len(xyz)} points, {k} neighbours, {len(centres)} viewpoints, {ctx.last_normals_degenerate} degenerate")
+        return time.perf_counter() - t0
+
     def _fuse_blocks(self, ctx: FusionContext, lattice: GridSpec, blocks: List[Block], marks=None, layout_given: bool = False):
         """The fusion of reconstruct(), for a lattice planned as one block as for many.  Per block, in the one context whose frames
         stay resident: the block's layout (from its own brick count), attach its grid, set its core, fuse every kept frame (the cull
@@ -668,6 +688,8 @@ class DepthToReconstructionPipeline:
         stage["extract_and_filter"] += clock() - t0
         self.stats = dict(points_accumulated=core_points, points_dropped=valid_points - core_points, **counts,
                           sparse=any(g.sparse for g in done), **sums, blocks=len(done))
+        if cfg.cloud_normals:
+            stage["cloud_normals"] = self._estimate_cloud_normals(ctx, xyz, lattice.voxel_size)
         if one and done[0].sparse:
             print(f"  Sparse volume: {sums['bricks_tsdf']} TSDF bricks and {sums['bricks_centroid']} centroid bricks hold records "
                   f"(of {done[0].nvox // 512}); {done[0].device_bytes() / 2**30:.2f} GiB")
@@ -765,9 +787,11 @@ class DepthToReconstructionPipeline:
         if getattr(self.config, "model_tracking", False) and poses is None:
             raise ValueError("model_tracking needs a single GPU: every kept frame is registered against one model, in order")
         self._check_mesh_filter_config()
+        self._check_cloud_normals_config()
         world, rank = dist.get_world_size(), dist.get_rank()
         self.mesh = None
         self.mesh_normals = None
+        self.cloud_normals = self.cloud_curvature = None
         if len(self.images) < 2:
             print("Need at least 2 images")
             return None, None, None
@@ -888,6 +912,8 @@ class DepthToReconstructionPipeline:
                 say("\n--- Step 5: Extract and clean point cloud ---")
                 xyz, rgb, counts = self._clean_cloud(ctx, [self._extract_points(ctx)], grid.voxel_size)
                 self.stats = dict(points_accumulated=tot[0], points_dropped=tot[1], **counts)
+                if cfg.cloud_normals:
+                    self.timings["cloud_normals_s"] = round(self._estimate_cloud_normals(ctx, xyz, grid.voxel_size), 4)
                 if cfg.extract_mesh:
                     t0 = time.perf_counter()
                     self.mesh = self._extract_mesh(ctx)
@@ -979,6 +1005,18 @@ class DepthToReconstructionPipeline:
         if (int(it) > 0 or bool(getattr(self.config, "mesh_normals", False))) and not self.config.extract_mesh:
             raise ValueError("mesh_smooth_iterations / mesh_normals work on the mesh: they need extract_mesh = True")
 
+    def _check_cloud_normals_config(self):
+        cfg = self.config
+        on = bool(getattr(cfg, "cloud_normals", False))
+        if bool(getattr(cfg, "cloud_curvature", False)) and not on:
+            raise ValueError("cloud_curvature comes out of the normal estimation: it needs cloud_normals = True")
+        if on:
+            k, radius = cfg.cloud_normals_neighbors, float(cfg.cloud_normals_radius)
+            if isinstance(k, bool) or int(k) != k or not 3 <= int(k) <= 64:
+                raise ValueError(f"cloud_normals_neighbors = {k}: must be a whole number in [3, 64]")
+            if not np.isfinite(radius) or radius < 0.0:
+                raise ValueError(f"cloud_normals_radius = {radius}: must be a finite distance in metres, or 0 for no limit")
+
     def _check_mesh_weld_config(self):
         mode = getattr(self.config, "mesh_weld", "host")
         if mode not in ("host", "device"):
@@ -1065,5 +1103,5 @@ class DepthToReconstructionPipeline:
         fileio.write_ply_mesh(path, *self.mesh, ascii=ascii, normals=self.mesh_normals)
         print(f"Saved mesh to {path}")
 
-    def save_reconstruction(self, points, colors, output_path: str, ascii: bool = False):
-        fileio.save_reconstruction(points, colors, output_path, ascii=ascii)
+    def save_reconstruction(self, points, colors, output_path: str, ascii: bool = False, normals=None, curvature=None):
+        fileio.save_reconstruction(points, colors, output_path, ascii=ascii, normals=normals, curvature=curvature)
