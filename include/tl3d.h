@@ -728,6 +728,17 @@ int tl3d_tile_cache_info(tl3d_ctx *ctx, uint64_t *builds, uint64_t *hits, uint64
  * created: TL3D_CLASS_CACHE=0 every frame is classified; TL3D_CLASS_CACHE_ENTRIES=n bricks per slot buffer (default 49152, 6 B
  * each); TL3D_TILE_CACHE=0 switches this cache off too. */
 int tl3d_class_cache_info(tl3d_ctx *ctx, uint64_t *classified, uint64_t *replayed, uint64_t *overflowed, uint64_t *bytes);
+/* The first fusion batch that replays a slot's entry (and holds the slot once; at most 8 entries per batch, the others at their
+ * next replay) REFINES its sub-brick masks: every sub-brick the
+ * entry lists as near a surface is put through the update's own per-voxel test against the 8x8-pixel depth tiles, once, and the
+ * ones that test decides for all 64 voxels leave the update's work for good -- all behind every surface: dropped; all in free
+ * space in front of every surface: counted as free space.  Later replays of the entry use the refined masks.  A frame that is
+ * fused once pays nothing; the grid is the same bit for bit.  Counts of (frame, sub-brick) pairs over the context's life:
+ * seen: put through the test; dropped / freed: decided as above; decided: every voxel decided, some one way and some the other
+ * (kept: a mask bit cannot say which voxel is which); overflowed: always 0 (reserved for per-voxel masks that did not fit).
+ * Any of the five may be null; the pending batch is issued first and the call waits for the device.  Environment, read when the
+ * context is created: TL3D_CLASS_REFINE=0 nothing is refined; so with TL3D_CLASS_CACHE=0 or TL3D_TILE_CACHE=0. */
+int tl3d_class_refine_info(tl3d_ctx *ctx, uint64_t *seen, uint64_t *dropped, uint64_t *freed, uint64_t *decided, uint64_t *overflowed);
 int tl3d_get_stats(tl3d_ctx *ctx, tl3d_stats *out);
 int tl3d_reset_stats(tl3d_ctx *ctx);
 int tl3d_event_record(tl3d_ctx *ctx, int which /* 0 or 1 */);

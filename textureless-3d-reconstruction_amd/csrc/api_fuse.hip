@@ -1,5 +1,5 @@
 // api_fuse.hip -- the fusion calls of the extern "C" surface (tl3d_integrate, tl3d_fuse_frames, tl3d_accumulate_centroid,
-// tl3d_accumulate_points, tl3d_count_bricks, the two cache read-outs) and the one path every TSDF prep chain takes to the device:
+// tl3d_accumulate_points, tl3d_count_bricks, the cache read-outs) and the one path every TSDF prep chain takes to the device:
 // the per-slot caches' look-ups, the ordering rule around them (ChainOrder), issue_prep_chain, flush_updates.  Host code only.
 #include <math.h>
 
@@ -48,7 +48,8 @@ static bool batch_known_complete(const tl3d_ctx *ctx, unsigned b) {
 //     b - 3 <= w < b, on another prep stream     (before_read)                replay); none if the host has waited since (tc_done_before)
 //   update of batch u = X.use_batch,           ev_upd[u % TSDF_SCRATCHES]   a chain on ps that OVERWRITES X (tiles: a rebuild without an
 //     b - 3 <= u < b, the last batch whose       (before_overwrite)           upload -- key change, cache off; classification: a new key,
-//     chain read or wrote X                                                   or masks added to a level-1 entry).  u's update waited for
+//     chain read or wrote X                                                   masks added to a level-1 entry, or the masks of a level-2
+//                                                                             entry refined: level 3).  u's update waited for
 //                                                                             u's chain, and the updates before it for the chains of
 //                                                                             earlier users; none if X.used is clear or the host has waited
 //   chain of batch b (ps)                      ev_prep[h]                   update of batch b (main; flush_updates)
@@ -146,14 +147,23 @@ static ClassKey class_key(const PoseF &p, float scale, float mind, float maxd, c
 // undoes it).  A slot's entry serves when the cache is on, the entry is valid -- no tile rebuild since it was made, this
 // chain's included -- and its key is the frame's, bit for bit: the frame is REPLAYED (if it fit: the device knows).  Otherwise
 // the frame is classified and SAVED under its key.  A classify-only chain asks for level 1; a fusion that finds level 1 replays
-// it, classifies the sub-bricks and leaves level 2, which counts as a write.  One slot twice in a chain: the second use is a
-// replay if the first is one that writes nothing and the keys are equal, else it is classified without the cache.
+// it, classifies the sub-bricks and leaves level 2, which counts as a write.  A fusion that finds level 2 replays it and -- if
+// refinement is on (TL3D_CLASS_REFINE), the chain holds the slot once and has not reached CLASS_REFINES_PER_CHAIN -- refines the
+// masks and leaves level 3 (plan.refine; a write of the same kind: before_overwrite, class_writes, wrote).  Lazy on purpose: a
+// frame that is fused once, and count-then-fuse, pay nothing.  Level 3 serves every chain as level 2 does.  One slot twice in a
+// chain: the second use is a replay if the first is one that writes nothing and the keys are equal, else it is classified
+// without the cache; such a chain refines nothing of that slot.
+// A chain refines at most this many of its frames' entries; the others stay at level 2 until the next chain that replays them.  The
+// refinement of 32 frames is as much work as their update, and what does not fit beside the update on the prep streams delays it:
+// plain bench.py, whose first timed steps refine, ran 1.1 % under the parent with 16 per chain, 1.2-1.3 % over it with 8 or 4.
+constexpr int CLASS_REFINES_PER_CHAIN = 8;
 static int class_cache_lookup(tl3d_ctx *ctx, ChainOrder &ord, PrepChain &c, const Grid &g, bool classify_only) {
     ClassPlan &plan = c.plan;
     memset(&plan, 0, sizeof(plan));
     plan.cap = ctx->cc_entries;
     plan.stats = ctx->d_cc_stats;
     if (!ctx->class_cache || !ctx->tile_cache) return TL3D_OK;      // every frame: CC_CLASSIFY
+    int n_refines = 0;
     for (int i = 0; i < c.n; ++i) {
         Slot &s = ctx->slots[c.slot[i]];
         const ClassKey key = class_key(c.pose[i], c.scale[i], c.mind, c.maxd, g);
@@ -170,7 +180,11 @@ static int class_cache_lookup(tl3d_ctx *ctx, ChainOrder &ord, PrepChain &c, cons
         if (!s.cls) return set_err(TL3D_E_STATE, "slot %d has no classification buffer", c.slot[i]);      // (it comes with the tiles: tile_cache_lookup)
         plan.cache[i] = s.cls;
         const bool hit = s.cc.valid && memcmp(&key, &s.cc_key, sizeof(key)) == 0;
-        const bool reads = hit && (classify_only || s.cc_level >= 2);    // else a write: a save under a new key, or level 1 -> 2
+        // the first fusion chain that replays a level-2 entry refines its masks (class_refine_kernel) -- if it holds the slot once:
+        // a second use in the chain would read the masks while they change
+        bool refines = hit && !classify_only && s.cc_level == 2 && ctx->class_refine && n_refines < CLASS_REFINES_PER_CHAIN;
+        for (int j = i + 1; j < c.n && refines; ++j) refines = c.slot[j] != c.slot[i];
+        const bool reads = hit && (classify_only || s.cc_level >= 2) && !refines;    // else a write: a save under a new key, level 1 -> 2, or 2 -> 3
         const int rc = reads ? ord.before_read(s.cc) : ord.before_overwrite(s.cc);
         if (rc) return rc;
         if (reads) {
@@ -178,8 +192,9 @@ static int class_cache_lookup(tl3d_ctx *ctx, ChainOrder &ord, PrepChain &c, cons
         } else {
             class_set_mode(plan, i, hit ? CC_REPLAY : CC_SAVE);
             c.class_writes |= 1u << i;
+            if (refines) { plan.refine |= 1u << i; ++n_refines; }
             s.cc_key = key;
-            s.cc_level = classify_only ? 1 : 2;
+            s.cc_level = classify_only ? 1 : refines ? 3 : 2;
             ord.wrote(s.cc);
         }
         ord.used(s.cc);
@@ -492,6 +507,22 @@ int tl3d_class_cache_info(tl3d_ctx *ctx, uint64_t *classified, uint64_t *replaye
     if (replayed) *replayed = h[1];
     if (overflowed) *overflowed = h[2];
     if (bytes) *bytes = (uint64_t)(ctx->cfg.n_slots - ctx->pool_tiles.remaining) * ctx->cc_bytes;
+    return TL3D_OK;
+}
+
+int tl3d_class_refine_info(tl3d_ctx *ctx, uint64_t *seen, uint64_t *dropped, uint64_t *freed, uint64_t *decided, uint64_t *overflowed) {
+    REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
+    FLUSH_UPDATES(ctx);                                 // (look-ups happen when a batch is issued)
+    TL3D_HIP(hipSetDevice(ctx->device));
+    // the refinement's own counters (class_refine_kernel), behind every update issued so far and so behind every chain
+    unsigned long long h[5] = {0, 0, 0, 0, 0};
+    TL3D_HIP(hipMemcpyAsync(h, ctx->d_cc_stats + 4, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    TL3D_HIP(hipStreamSynchronize(ctx->stream));
+    if (seen) *seen = h[0];
+    if (dropped) *dropped = h[1];
+    if (freed) *freed = h[2];
+    if (decided) *decided = h[3];
+    if (overflowed) *overflowed = h[4];
     return TL3D_OK;
 }
 

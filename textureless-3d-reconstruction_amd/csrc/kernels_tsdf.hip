@@ -27,7 +27,8 @@
 //        Kernels 3 and 4 depend on the pose, the scale, the depth limits, the slot's tiles and the grid's geometry only: their
 //        result is kept with the slot as well (the classification cache, below) and a frame that meets its slot with the same
 //        key again is REPLAYED from it by class_replay_kernel, which runs in front of kernel 3; kernels 3 and 4 return at once
-//        for such a frame.
+//        for such a frame.  The first fusion chain that replays an entry also REFINES its masks (class_refine_kernel): the
+//        sub-bricks the update's own per-voxel tile test decides for all 64 voxels leave the MIXED masks for good.
 //   5. tsdf_update_kernel     ONE launch per batch, one 64-lane wave per brick of the batch list: for every frame that lists
 //        the brick (frame mask), the voxels of its MIXED sub-bricks are projected; the 8x8-pixel tile under a voxel's pixel
 //        decides most of them (free / behind everything), the rest gather their depth value; FREE sub-bricks add (32767, 1);
@@ -246,6 +247,7 @@ __global__ __launch_bounds__(256) void depth_tiles_kernel(Cam cam, BatchBufs B, 
 
 constexpr int VALID_PIXEL = 32;          // word of a frame's counts block: ONE PIXEL OF THE FRAME THAT IS VALID (tile_pyramid_kernel)
 constexpr int CELL_COUNT = 48;           // word of a frame's counts block: length of the frame's cell list
+constexpr int REFINE_COUNTS = 8;         // words 8-11 of a frame's counts block: what class_refine_kernel decided for the frame's pairs (reset with the list cursors)
 __device__ __forceinline__ bool sphere_in_view(const Frustum &fr, float x, float y, float z, float rad) {
     return (z + rad > 0.0f) && (fr.lx * x + fr.lz * z >= -rad) && (fr.rx * x + fr.rz * z >= -rad) &&
            (fr.ty * y + fr.tz * z >= -rad) && (fr.by * y + fr.bz * z >= -rad);
@@ -264,6 +266,7 @@ __global__ __launch_bounds__(256) void batch_begin_kernel(Grid g, Frustum fr, Py
     __shared__ unsigned s_ncell;
     const DescPtr F = const_descs(B) + blockIdx.x;
     if (threadIdx.x < 2) F->counts[threadIdx.x] = 0u;                            // reset the frame's list cursors
+    if (threadIdx.x >= REFINE_COUNTS && threadIdx.x < REFINE_COUNTS + 4) F->counts[threadIdx.x] = 0u;      // and its refinement counts
     if (blockIdx.x == 0) {                                                       // and the batch list's, the update's ticket counters, the ordering pass's bins
         if (threadIdx.x == 2) B.hdr[0] = 0u;
         if (threadIdx.x >= 64 && threadIdx.x < 64 + TICKET_GROUPS) B.hdr[HDR_TICKETS + 16u * (threadIdx.x - 64)] = 0u;
@@ -378,7 +381,8 @@ __device__ __forceinline__ int classify_box(const Grid &g, float4 a, float zmin,
 // not fit is classified every time, and each kernel takes its path for a frame from the mode and that header alone (uniform
 // over the frame's workgroups; no host wait).  Level 1 = lists and counts, level 2 = + masks: a classify-only chain
 // (tl3d_count_bricks) fills level 1, and the fusion that follows replays it, runs the sub-brick classification over the
-// cached list and leaves level 2.
+// cached list and leaves level 2.  Level 3 = masks refined by class_refine_kernel (below, with the cache's other kernels); it
+// serves every chain as level 2 does.
 __device__ __forceinline__ bool class_replays(const ClassPlan &P, int f) {
     return class_mode(P, f) == CC_REPLAY && P.cache[f][3] == 1u;
 }
@@ -1074,8 +1078,42 @@ __device__ __forceinline__ unsigned keep_scalar(unsigned x) {             // x, 
     return x;
 }
 
+// Stage A of a pair and rule (4), ONE spelling for the update kernel and for class_refine_kernel: whether the 8x8-pixel tile
+// under a voxel's pixel decides it must come out the same in both, bit for bit -- a sub-brick that the refinement takes off a
+// frame's MIXED mask is sound for exactly that reason and for no other.
+// pair_project: the voxel centre (wxs, wys, wzs) through the pose (r0..r8, t0..t2) -> byte offsets of its pixel (pix) and of the
+// 8-B record of the tile that holds it (tix; always legal addresses); returns zc, or +inf for a voxel that is not in front of
+// zmin or whose pixel lies outside the image ("behind everything": no update).
+__device__ __forceinline__ float pair_project(const Cam &cam, float r0, float r1, float r2, float r3, float r4, float r5, float r6, float r7, float r8,
+                                              float t0, float t1, float t2, float wxs, float wys, float wzs, float zmin, unsigned row_bytes,
+                                              unsigned pix_bytes, int ntx0, unsigned &pix, unsigned &tix) {
+    const float xc = fmaf(r0, wxs, fmaf(r1, wys, fmaf(r2, wzs, t0)));
+    const float yc = fmaf(r3, wxs, fmaf(r4, wys, fmaf(r5, wzs, t1)));
+    const float zc = fmaf(r6, wxs, fmaf(r7, wys, fmaf(r8, wzs, t2)));
+    float inv = __builtin_amdgcn_rcpf(zc);                     // + one Newton step == the IEEE quotient (tsdf_project)
+    inv = fmaf(fmaf(-zc, inv, 1.0f), inv, inv);
+    if (__builtin_expect(!(zc >= 1.17549435e-38f && zc < 8.5e37f), 0)) inv = 1.0f / zc;
+    const float uf = fmaf(cam.fx * xc, inv, cam.cx);
+    const float vf = fmaf(cam.fy * yc, inv, cam.cy);
+    // nearest pixel floor(uf + 0.5) in ONE conversion (v_cvt_flr_i32_f32 == v_floor_f32 + v_cvt_i32_f32 on every bit
+    // pattern), and the window  -0.5 <= uf < W - 0.5  as ONE unsigned compare of it  (the same decision for every float
+    // and every width: tools/ubench_flr.hip, exhaustive)
+    const int ui = cvt_flr_i32(uf + 0.5f), vi = cvt_flr_i32(vf + 0.5f);
+    const bool ok = (zc > zmin) & ((unsigned)ui <= (unsigned)(cam.W - 1)) & ((unsigned)vi <= (unsigned)(cam.H - 1));
+    const int u = clamp_i32(ui, cam.W - 1), v = clamp_i32(vi, cam.H - 1);
+    pix = mad_u24((unsigned)v, row_bytes, (unsigned)u * pix_bytes);
+    tix = mad_u24((unsigned)v >> TILE0_SHIFT, (unsigned)ntx0 << 3, (unsigned)u & ~7u);
+    return ok ? zc : INFINITY;
+}
+// pair_tile_test: tl = the tile's record (lowest depth if all 64 pixels are valid else -inf, highest valid depth), zc as
+// pair_project returns it.  fre: tsdf == 1 exactly whatever the pixel says; skp: no update whatever the pixel says.
+__device__ __forceinline__ void pair_tile_test(float2 tl, float zc, float trunc_free, float trunc, bool &fre, bool &skp) {
+    fre = tl.x - zc >= trunc_free;
+    skp = !(tl.y - zc >= -trunc);
+}
+
 #ifdef TL3D_EXPERIMENTS
-__device__ unsigned long long g_upd_span[16384][2];        // experiments: start / end (100 MHz real-time clock) of every wave of the last stamped launch
+__device__ unsigned long long g_upd_span[16384][2];       // experiments: start / end (100 MHz real-time clock) of every wave of the last stamped launch
 #endif
 constexpr int UPD_WAVES = 8;             // waves per SIMD the pair kernel is built for (64 vector registers)
 
@@ -1193,23 +1231,9 @@ __global__ __launch_bounds__(256, UPD_WAVES) void tsdf_update_pairs_kernel(Cam c
                 m &= m - 1u;                                                   // (0 stays 0)
                 {
                     const float wxs = (s & 1u) ? wx1 : wx0, wys = (s & 2u) ? wy1 : wy0, wzs = (s & 4u) ? wz1 : wz0;
-                    const float xc = fmaf(r0, wxs, fmaf(r1, wys, fmaf(r2, wzs, t0)));
-                    const float yc = fmaf(r3, wxs, fmaf(r4, wys, fmaf(r5, wzs, t1)));
-                    const float zc = fmaf(r6, wxs, fmaf(r7, wys, fmaf(r8, wzs, t2)));
-                    float inv = __builtin_amdgcn_rcpf(zc);                     // + one Newton step == the IEEE quotient (tsdf_project)
-                    inv = fmaf(fmaf(-zc, inv, 1.0f), inv, inv);
-                    if (__builtin_expect(!(zc >= 1.17549435e-38f && zc < 8.5e37f), 0)) inv = 1.0f / zc;
-                    const float uf = fmaf(cam.fx * xc, inv, cam.cx);
-                    const float vf = fmaf(cam.fy * yc, inv, cam.cy);
-                    // nearest pixel floor(uf + 0.5) in ONE conversion (v_cvt_flr_i32_f32 == v_floor_f32 + v_cvt_i32_f32 on every bit
-                    // pattern), and the window  -0.5 <= uf < W - 0.5  as ONE unsigned compare of it  (the same decision for every float
-                    // and every width: tools/ubench_flr.hip, exhaustive)
-                    const int ui = cvt_flr_i32(uf + 0.5f), vi = cvt_flr_i32(vf + 0.5f);
-                    const bool ok = (zc > zmin) & ((unsigned)ui <= (unsigned)(cam.W - 1)) & ((unsigned)vi <= (unsigned)(cam.H - 1));
-                    const int u = clamp_i32(ui, cam.W - 1), v = clamp_i32(vi, cam.H - 1);
-                    pixA[par] = mad_u24((unsigned)v, row_bytes, (unsigned)u * (unsigned)sizeof(DT));
-                    const unsigned tix = mad_u24((unsigned)v >> TILE0_SHIFT, (unsigned)ntx0 << 3, (unsigned)u & ~7u);
-                    zcA[par] = ok ? zc : INFINITY;
+                    unsigned tix;
+                    zcA[par] = pair_project(cam, r0, r1, r2, r3, r4, r5, r6, r7, r8, t0, t1, t2, wxs, wys, wzs, zmin, row_bytes, (unsigned)sizeof(DT), ntx0,
+                                            pixA[par], tix);
                     tlA[par] = *reinterpret_cast<const float2 *>(a_vt + ((EXP & 1) ? (unsigned)lane * 8u : tix));
                 }
                 // the scalars pair k hands down the pipeline, then -- its frame used up -- the next frame's (the loads have stages C
@@ -1240,8 +1264,8 @@ __global__ __launch_bounds__(256, UPD_WAVES) void tsdf_update_pairs_kernel(Cam c
                 bool open1;
                 {
                     const float zc = zcA[par ^ 1];
-                    const bool fre = tlA[par ^ 1].x - zc >= trunc_free;
-                    const bool skp = !(tlA[par ^ 1].y - zc >= -g.trunc);
+                    bool fre, skp;
+                    pair_tile_test(tlA[par ^ 1], zc, trunc_free, g.trunc, fre, skp);
                     zcB[par ^ 1] = fre ? -INFINITY : (skp ? INFINITY : zc);
                     const unsigned pix = ((EXP & 2) || fre || skp) ? b_vp : pixA[par ^ 1];
                     dvB[par ^ 1] = PixLoad<DT>::load(b_img, pix);
@@ -1353,8 +1377,96 @@ __global__ __launch_bounds__(256) void class_replay_kernel(Grid g, BatchBufs B, 
     }
 }
 
+// The REFINEMENT of a replayed level-2 entry (ClassPlan::refine: the host's choice -- a fusion chain that holds the slot once;
+// the header's: the entry fit and is at level 2), behind the replay and in front of everything that reads the masks.  A MIXED
+// sub-brick is a PAIR of the update: 64 lanes = its 64 voxels, through the update's own stage A and tile test (pair_project,
+// pair_tile_test: the same decision per lane, bit for bit).  A pair whose every lane the tiles decide needs no depth pixel, and
+// what the update would add for it is fixed by the key the entry was made under:
+//   every lane "behind everything"     the pair adds nothing: its MIXED bit goes;
+//   every lane "in front of everything" every voxel gets exactly (32767, 1), what a FREE sub-brick gets: MIXED bit -> FREE bit
+//                                       (the update counts it with a ballot: no pipeline step);
+//   both kinds, no open lane            counted only (stats[7]): no mask bit can say which lane is which.
+// The new mask goes to the frame's sub[] of this batch and to the entry; class_finish_kernel marks the entry level 3.  Brick
+// lists, free-space counts and pool slots are not touched: a brick whose pairs all vanish stays listed.
+// stats[4..8]: pairs seen, dropped, turned FREE, decided with both kinds of lane, (masks that did not fit: none are kept);
+// counted per frame here and folded into the context's words by class_finish_kernel.
+__global__ __launch_bounds__(256) void class_refine_kernel(Cam cam, Grid g, BatchBufs B, ClassPlan P) {
+    const int f = blockIdx.y;
+    if (!((P.refine >> f) & 1u) || !class_replays(P, f)) return;
+    unsigned *__restrict__ C = P.cache[f];
+    if (C[2] != 2u) return;
+    const DescPtr F = const_descs(B) + f;
+    __shared__ unsigned s_cnt[4];
+    if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0u;
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const unsigned nbricks = (unsigned)(g.nbx * g.nby * g.nbz), cap = P.cap;
+    const unsigned nm = min(C[0], cap);
+    unsigned short *__restrict__ cm = reinterpret_cast<unsigned short *>(C + CC_HDR_WORDS + cap);
+    unsigned short *__restrict__ sub = F->sub;
+    const float r0 = F->pose.r[0], r1 = F->pose.r[1], r2 = F->pose.r[2], r3 = F->pose.r[3], r4 = F->pose.r[4], r5 = F->pose.r[5];
+    const float r6 = F->pose.r[6], r7 = F->pose.r[7], r8 = F->pose.r[8], t0 = F->pose.t[0], t1 = F->pose.t[1], t2 = F->pose.t[2];
+    const char *vt = reinterpret_cast<const char *>(F->vtile);
+    const int ntx0 = (cam.W + TILE0 - 1) >> TILE0_SHIFT;
+    const float trunc_free = g.trunc * 1.001f;
+    unsigned seen = 0, dropped = 0, freed = 0, both = 0;
+    for (unsigned i = blockIdx.x * 4u + (unsigned)wid; i < nm; i += gridDim.x * 4u) {
+        const unsigned brick = min((unsigned)__builtin_amdgcn_readfirstlane((int)C[CC_HDR_WORDS + i]), nbricks - 1u);
+        const unsigned m0 = (unsigned)__builtin_amdgcn_readfirstlane((int)cm[i]);
+        if ((m0 & 0xffu) == 0u) continue;
+        const int bx = (int)(brick % (unsigned)g.nbx), by = (int)((brick / (unsigned)g.nbx) % (unsigned)g.nby), bz = (int)(brick / (unsigned)(g.nbx * g.nby));
+        // the lane's voxel centres, exactly as the update kernel forms them
+        const int lx = g.vox + bx * 8, ly = g.voy + by * 8, lz = g.voz + bz * 8;
+        const float wx0 = fmaf((float)(lx | (lane & 3)) + 0.5f, g.vs, g.ox), wx1 = fmaf((float)(lx | 4 | (lane & 3)) + 0.5f, g.vs, g.ox);
+        const float wy0 = fmaf((float)(ly | ((lane >> 2) & 3)) + 0.5f, g.vs, g.oy), wy1 = fmaf((float)(ly | 4 | ((lane >> 2) & 3)) + 0.5f, g.vs, g.oy);
+        const float wz0 = fmaf((float)(lz | (lane >> 4)) + 0.5f, g.vs, g.oz), wz1 = fmaf((float)(lz | 4 | (lane >> 4)) + 0.5f, g.vs, g.oz);
+        // all tile records of the brick's pairs are asked for before the first is looked at
+        float zc[8];
+        float2 tl[8];
+#pragma unroll
+        for (unsigned s = 0; s < 8u; ++s) {
+            zc[s] = INFINITY;
+            tl[s] = make_float2(0.0f, 0.0f);
+            if ((m0 >> s) & 1u) {
+                const float wxs = (s & 1u) ? wx1 : wx0, wys = (s & 2u) ? wy1 : wy0, wzs = (s & 4u) ? wz1 : wz0;
+                unsigned pix, tix;
+                zc[s] = pair_project(cam, r0, r1, r2, r3, r4, r5, r6, r7, r8, t0, t1, t2, wxs, wys, wzs, 0.0f, (unsigned)cam.W * 4u, 4u, ntx0, pix, tix);
+                tl[s] = *reinterpret_cast<const float2 *>(vt + tix);
+            }
+        }
+        unsigned m = m0;
+#pragma unroll
+        for (unsigned s = 0; s < 8u; ++s)
+            if ((m0 >> s) & 1u) {
+                bool fre, skp;
+                pair_tile_test(tl[s], zc[s], trunc_free, g.trunc, fre, skp);
+                const unsigned long long bfre = __ballot(fre), bskp = __ballot(skp);
+                seen += 1u;
+                if (bskp == ~0ull) { m &= ~(1u << s); dropped += 1u; }
+                else if (bfre == ~0ull) { m = (m & ~(1u << s)) | (1u << (8u + s)); freed += 1u; }
+                else if ((bfre | bskp) == ~0ull) both += 1u;
+            }
+        if (m != m0 && lane == 0) {
+            cm[i] = (unsigned short)m;
+            sub[brick] = (unsigned short)m;
+        }
+    }
+    // the counts: pooled per workgroup, then into the FRAME's counts block (one address per frame and kind: adds to one address
+    // retire one after the other, and 32 k waves adding to the context's four words took longer than the kernel's work);
+    // class_finish_kernel folds them into the context's
+    if (lane == 0 && seen) {
+        atomicAdd(&s_cnt[0], seen);
+        if (dropped) atomicAdd(&s_cnt[1], dropped);
+        if (freed) atomicAdd(&s_cnt[2], freed);
+        if (both) atomicAdd(&s_cnt[3], both);
+    }
+    __syncthreads();
+    if (threadIdx.x < 4 && s_cnt[threadIdx.x]) atomicAdd(F->counts + REFINE_COUNTS + threadIdx.x, s_cnt[threadIdx.x]);
+}
+
 // The last kernel of a chain that wrote cache entries, one workgroup per frame: the header of a saved frame (complete only if
-// the frame fit), and level 2 for an entry that was replayed at level 1 and got its masks from this chain.
+// the frame fit), level 2 for an entry that was replayed at level 1 and got its masks from this chain, level 3 for one that this
+// chain refined.
 __global__ __launch_bounds__(64) void class_finish_kernel(BatchBufs B, ClassPlan P) {
     if (threadIdx.x != 0) return;
     const DescPtr F = const_descs(B) + blockIdx.x;
@@ -1364,8 +1476,13 @@ __global__ __launch_bounds__(64) void class_finish_kernel(BatchBufs B, ClassPlan
         const bool fit = nm <= P.cap && nf <= P.cap - nm;
         C[0] = nm; C[1] = nf; C[2] = P.classify_only ? 1u : 2u; C[3] = fit ? 1u : 0u;
         if (!fit) atomicAdd(P.stats + 2, 1ull);
-    } else if (class_replays(P, blockIdx.x) && C[2] < 2u && !P.classify_only) {
-        C[2] = 2u;
+    } else if (class_replays(P, blockIdx.x) && !P.classify_only) {
+        if (C[2] < 2u) C[2] = 2u;
+        else if (C[2] == 2u && ((P.refine >> blockIdx.x) & 1u)) {
+            C[2] = 3u;
+            for (int k = 0; k < 4; ++k)
+                if (F->counts[REFINE_COUNTS + k]) atomicAdd(P.stats + 4 + k, (unsigned long long)F->counts[REFINE_COUNTS + k]);
+        }
     }
 }
 
@@ -1459,8 +1576,8 @@ static BatchBufs batch_bufs(const BatchLayout &L, void *scratch, int n) {
 
 // The whole prep of the chain c (c.n frames, one depth kind) on stream s: descriptor upload, depth tiles and pyramid of the
 // c.n_stale frames c.stale[] (the others' slots hold them already), resets + cell lists, brick classification, sub-brick masks --
-// or, for the frames c.plan marks CC_REPLAY and whose buffer is complete, the replay of both; c.class_writes != 0: the chain writes
-// cache entries (class_finish_kernel closes it).  `scratch` is a batch scratch of at least c.n frames (tsdf_batch_scratch_bytes).
+// or, for the frames c.plan marks CC_REPLAY and whose buffer is complete, the replay of both, and for those of c.plan.refine the
+// refinement of the replayed masks; c.class_writes != 0: the chain writes cache entries (class_finish_kernel closes it).  `scratch` is a batch scratch of at least c.n frames (tsdf_batch_scratch_bytes).
 int launch_tsdf_prepare(hipStream_t s, const Cam &cam, const Grid &g, const Frustum &fr, const PrepChain &c, int max_frames, void *scratch,
                         unsigned *free_cnt, bool classify_only) {
     const int n = c.n, n_stale = c.n_stale;
@@ -1533,6 +1650,12 @@ int launch_tsdf_prepare(hipStream_t s, const Cam &cam, const Grid &g, const Frus
         const unsigned trips = (P.cap + 255u) / 256u;
         hipLaunchKernelGGL(class_replay_kernel, dim3(trips < 16u ? trips : 16u, n), dim3(256), 0, s, g, B, free_cnt, P);
         TL3D_HIP(hipGetLastError());
+        if (n < TL3D_TSDF_MAXBATCH) P.refine &= (1u << n) - 1u;
+        if (P.refine != 0u && !classify_only) {          // (one wave per cached MIXED brick, a fixed grid strides over each list)
+            const unsigned quads = (P.cap + 3u) / 4u;
+            hipLaunchKernelGGL(class_refine_kernel, dim3(quads < 256u ? quads : 256u, n), dim3(256), 0, s, cam, g, B, P);
+            TL3D_HIP(hipGetLastError());
+        }
     }
     if (cached)
         hipLaunchKernelGGL(brick_cull_cached_kernel, dim3(nquad < 256 ? nquad : 256, n), dim3(256), 0, s, cam, g, B, fr, py, free_cnt, P);

@@ -450,6 +450,8 @@ int tl3d_create(const tl3d_config *cfg, int device, tl3d_ctx **out) {
         // lists ~15.4 k MIXED + ~10.2 k FREE bricks, a little over half of that.
         v = getenv("TL3D_CLASS_CACHE");
         ctx->class_cache = !(v && atoi(v) == 0);
+        v = getenv("TL3D_CLASS_REFINE");                 // 0: replayed entries stay at level 2 (class_refine_kernel never runs)
+        ctx->class_refine = !(v && atoi(v) == 0);
         v = getenv("TL3D_CLASS_CACHE_ENTRIES");
         const long long e = v ? atoll(v) : 49152;
         ctx->cc_entries = (unsigned)(e < 1 ? 1 : e > (1ll << 26) ? (1ll << 26) : e);
@@ -499,9 +501,9 @@ int tl3d_create(const tl3d_config *cfg, int device, tl3d_ctx **out) {
         const int grc = alloc_grid(ctx, cfg);
         if (grc) return fail(grc);
     }
-    // (16 counters of the update kernel, then the 4 of the classification cache: ClassPlan::stats)
-    if (hipMalloc(&ctx->d_counters, 20 * sizeof(unsigned long long)) != hipSuccess) return fail(set_err(TL3D_E_NOMEM, "alloc failed"));
-    if (hipMemsetAsync(ctx->d_counters, 0, 20 * sizeof(unsigned long long), ctx->stream) != hipSuccess) return fail(set_err(TL3D_E_HIP, "memset failed"));
+    // (16 counters of the update kernel, then ClassPlan::stats: the 4 of the classification cache and the 5 of its refinement)
+    if (hipMalloc(&ctx->d_counters, 32 * sizeof(unsigned long long)) != hipSuccess) return fail(set_err(TL3D_E_NOMEM, "alloc failed"));
+    if (hipMemsetAsync(ctx->d_counters, 0, 32 * sizeof(unsigned long long), ctx->stream) != hipSuccess) return fail(set_err(TL3D_E_HIP, "memset failed"));
     ctx->d_cc_stats = ctx->d_counters + 16;
     if (hipMalloc(&ctx->d_cen_counters, 256 * 8 * sizeof(unsigned long long)) != hipSuccess) return fail(set_err(TL3D_E_NOMEM, "alloc failed"));
     if (hipMemsetAsync(ctx->d_cen_counters, 0, 256 * 8 * sizeof(unsigned long long), ctx->stream) != hipSuccess) return fail(set_err(TL3D_E_HIP, "memset failed"));

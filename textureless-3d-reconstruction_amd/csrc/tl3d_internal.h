@@ -163,7 +163,9 @@ struct ClassPlan {
     unsigned long long modes;    // two bits per frame (class_mode): a shift and a mask on the scalar unit; 0 = no frame of the chain uses the cache
     unsigned cap;               // entries a buffer holds for this grid: min(configured entries, bricks of the grid)
     int classify_only;
-    unsigned long long *stats;   // device counters: [0] frames classified, [1] replayed, [2] of the classified: did not fit (tl3d_class_cache_info)
+    unsigned refine;             // bit f: the chain refines frame f's replayed level-2 entry and leaves level 3 (class_refine_kernel)
+    unsigned long long *stats;   // device counters: [0] frames classified, [1] replayed, [2] of the classified: did not fit (tl3d_class_cache_info);
+                                 // [4..8] of the refinement: pairs seen, dropped, turned FREE, decided with both kinds of lane, masks that did not fit (tl3d_class_refine_info)
 };
 __host__ __device__ __forceinline__ unsigned class_mode(const ClassPlan &P, int f) { return (unsigned)(P.modes >> (2 * f)) & 3u; }
 inline void class_set_mode(ClassPlan &P, int f, unsigned mode) { P.modes = (P.modes & ~(3ull << (2 * f))) | ((unsigned long long)mode << (2 * f)); }
@@ -234,7 +236,8 @@ struct Slot {
     // depth limits, grid geometry), replayed when a batch meets the slot again with that key (kernels_tsdf.hip:
     // class_replay_kernel).  It lives behind the tiles in the slot's block of tl3d_ctx::pool_tiles (tsdf_class_cache_bytes).  It is made from the
     // slot's tiles: every rebuild of those drops it (api_fuse.hip: tile_cache_lookup).  cc_level: 1 = lists and counts (what a
-    // classify-only chain can fill), 2 = + sub-brick masks.  Whether the frame FIT is known to the device alone (the buffer's header).
+    // classify-only chain can fill), 2 = + sub-brick masks, 3 = masks refined by the per-voxel tile test (class_refine_kernel: the first
+    // fusion chain that replays a level-2 entry and holds the slot once).  Whether the frame FIT is known to the device alone (the buffer's header).
     unsigned *cls = nullptr;
     ClassKey cc_key;             // key, with cc_level
     int cc_level = 0;
@@ -361,9 +364,10 @@ struct tl3d_ctx : tl3d_grid_state {
     // TSDF classification cache (Slot::cls): off = every look-up classifies (env TL3D_CLASS_CACHE=0, or the tile cache off);
     // entries per slot buffer (env TL3D_CLASS_CACHE_ENTRIES); both read when the context is created
     bool class_cache;
+    bool class_refine;                    // a replayed level-2 entry is refined to level 3 (env TL3D_CLASS_REFINE=0: never), read like its siblings
     unsigned cc_entries;
     size_t tc_bytes, cc_bytes;            // of a slot's block in pool_tiles: the tiles' part, the classification buffer behind it (0: cache off)
-    unsigned long long *d_cc_stats;       // ClassPlan::stats (the four words behind d_counters' sixteen)
+    unsigned long long *d_cc_stats;       // ClassPlan::stats (the sixteen words behind d_counters' sixteen: four of the cache, five of the refinement)
     unsigned long long cc_classified_host;  // frames of chains in which no frame used the cache: their kernels are the plain ones and do not count
     tl3d::PrepChain pend;                 // the batch being collected (tl3d_integrate fills slot, pose, scale, depth and depth_u16; the rest is flush_updates')
     tl3d::CenFrame cen_pend[tl3d::TL3D_CEN_MAXBATCH];   // voxel-centroid accumulations not yet launched (one stride per batch)

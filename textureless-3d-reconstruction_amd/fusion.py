@@ -426,6 +426,13 @@ class FusionContext:
         abi.check(self._lib.tl3d_class_cache_info(self._h, C.byref(c), C.byref(r), C.byref(o), C.byref(m)))
         return int(c.value), int(r.value), int(o.value), int(m.value)
 
+    def class_refine_info(self):
+        """(seen, dropped, freed, decided, overflowed): (frame, sub-brick) pairs the refinement of replayed classification entries
+        tested and what it decided for them (tl3d.h: tl3d_class_refine_info)."""
+        v = [C.c_uint64(0) for _ in range(5)]
+        abi.check(self._lib.tl3d_class_refine_info(self._h, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
     # ---- fusion ----------------------------------------------------------------------------
     def accumulate_centroid(self, slot: int, pose=None, scale=1.0, subsample: int = 1, min_depth=None, max_depth=None,
                             scale_f64: bool = False):
