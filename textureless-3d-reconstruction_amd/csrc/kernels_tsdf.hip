@@ -1112,6 +1112,20 @@ __device__ __forceinline__ void pair_tile_test(float2 tl, float zc, float trunc_
     skp = !(tl.y - zc >= -trunc);
 }
 
+// A record is read, added to and written ONCE per launch: nothing in the launch asks for it again, so its 2 x 8 B per voxel go
+// through the caches as non-temporal traffic.  Measured: the kernel 8 us of 325 shorter, 2 % fewer requests to the
+// fabric; that the depth lines neighbours share stay cached longer for it is supposed, the counters do not show it.
+typedef int rec_v2i __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ int2 rec_load_nt(const int2 *p) {
+    const rec_v2i v = __builtin_nontemporal_load(reinterpret_cast<const rec_v2i *>(p));
+    return make_int2(v.x, v.y);
+}
+__device__ __forceinline__ void rec_store_nt(int2 *p, int2 r) {
+    rec_v2i v;
+    v.x = r.x; v.y = r.y;
+    __builtin_nontemporal_store(v, reinterpret_cast<rec_v2i *>(p));
+}
+
 #ifdef TL3D_EXPERIMENTS
 __device__ unsigned long long g_upd_span[16384][2];       // experiments: start / end (100 MHz real-time clock) of every wave of the last stamped launch
 #endif
@@ -1290,14 +1304,14 @@ __global__ __launch_bounds__(256, UPD_WAVES) void tsdf_update_pairs_kernel(Cam c
         int2 rec[8];
 #pragma unroll
         for (int s = 0; s < 8; ++s)
-            if (a[s] >> 21) rec[s] = recs[s * 64 + lane];
+            if (a[s] >> 21) rec[s] = rec_load_nt(recs + s * 64 + lane);
 #pragma unroll
         for (int s = 0; s < 8; ++s)
             if (a[s] >> 21) {
                 const int w = (int)(a[s] >> 21);
                 rec[s].x += (int)(a[s] & 0x1fffffu) - 32768 * w;
                 rec[s].y += w;
-                recs[s * 64 + lane] = rec[s];
+                rec_store_nt(recs + s * 64 + lane, rec[s]);
                 if (COUNT) { nread += 1; nwritten += 1; }
             }
         if (EXP & 16) { const unsigned long long now = __builtin_readcyclecounter(); pf_rmw += now - pf_a; pf_a = now; }
