@@ -1042,13 +1042,19 @@ __global__ __launch_bounds__(256, TL3D_UPD_WAVES) void tsdf_update_kernel(Cam ca
 //     need eight predicated adds);  FREE sub-bricks are counted per sub-brick over the frames with ballots and enter the sums
 //     once per brick;
 //   * three stages as before -- A project + tile record, B tile test + depth gather, C quantise + add -- software-pipelined
-//     over the pairs: step k runs A(k), C(k-2), B(k-1); a tile record has a full step, a depth value two thirds of one, before
-//     anything waits for it (and seven other waves of the SIMD have work meanwhile).  P pairs take P + 2 steps; the empty slots at either end run with zc = +inf ("behind
+//     over the pairs: step k runs A(k), C(k-1-LAT), B(k-1); a tile record has a full step before anything waits for it, a depth
+//     value LAT - 1 steps and a third (and seven other waves of the SIMD have work meanwhile).  LAT = 2 in the kernels without
+//     counters: the wait in front of stage C is vmcnt(3), it leaves the two newer steps' loads in flight (at LAT = 1 it was
+//     vmcnt(1), and the kernel 3 % slower: DESIGN.md 7.5).  Loads return in order, so stage B's wait for its tile record also
+//     waits for every depth value older than two steps: LAT = 3 needs no wait of its own in stage C, buys a fraction of a
+//     step, and does not fit the scalar registers.  P pairs take P + 1 + LAT steps, rounded up to whole loop bodies (6 steps at
+//     LAT = 2: the parity of A -> B and the three-entry rings of B -> C both come round); the empty slots at either end run
+//     with zc = +inf ("behind
 //     everything": no update) and legal addresses, so the steady loop has no branch but its back edge and the frame switch
 //     (stages skipped by wave-uniform branches at either end instead: the compiler's wait counts at the joins turn conservative and
 //     the launch takes a quarter longer: 61 k against 76 k frames/s);
 //   * every load of a stage is a scalar base + a 32-bit per-lane offset.
-// About 45 vector registers: eight waves per SIMD hide what the three of the form above could not.
+// 62 vector registers at LAT = 2 (56 at LAT = 1), no scratch: eight waves per SIMD hide what the three of the form above could not.
 // The arithmetic of a voxel is tsdf_project / tsdf_finish, as above: the grid is the oracle's bit for bit.
 __device__ __forceinline__ int clamp_i32(int x, int hi_uniform) {        // min(max(x, 0), hi): one instruction (hi >= 0)
     int r;
@@ -1072,6 +1078,10 @@ __device__ __forceinline__ int cvt_flr_i32(float x) {                    // (int
     int r;
     asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(r) : "v"(x));
     return r;
+}
+__device__ __forceinline__ float keep_vector(float x) {                   // x, wave-uniform, lives in a VECTOR register from here on
+    asm volatile("" : "+v"(x));
+    return x;
 }
 __device__ __forceinline__ unsigned keep_scalar(unsigned x) {             // x, wave-uniform, is computed HERE and lives in one scalar register
     asm volatile("" : "+s"(x));
@@ -1130,12 +1140,20 @@ __device__ __forceinline__ void rec_store_nt(int2 *p, int2 r) {
 __device__ unsigned long long g_upd_span[16384][2];       // experiments: start / end (100 MHz real-time clock) of every wave of the last stamped launch
 #endif
 constexpr int UPD_WAVES = 8;             // waves per SIMD the pair kernel is built for (64 vector registers)
+// the depth-gather latency (LAT below) the library ships: 2 for both depth formats (f32 +3.0 %, 16-bit +2.4 % frames/s against 1:
+// profiles/update_depth_latency_ab.txt); the counting instantiations, not on a timed path, would need 66 vector registers at 2
+template <bool COUNT, typename DT> struct PairsLat { static constexpr int value = 1; };
+template <typename DT> struct PairsLat<false, DT> { static constexpr int value = 2; };
 
 // EXP (experiments flavour only, results incomplete): bit 0 tile records read at lane * 8 (coalesced), bit 1 every lane reads the frame's
 // valid pixel (no scattered depth reads), bit 2 no LDS add, bit 3 no record accesses
-template <bool COUNT, typename DT, int EXP = 0>
+// LAT: the steps between stage B of a pair (depth gather issued) and its stage C (depth value used)
+template <bool COUNT, typename DT, int EXP = 0, int LAT = PairsLat<COUNT, DT>::value>
 __global__ __launch_bounds__(256, UPD_WAVES) void tsdf_update_pairs_kernel(Cam cam, Grid g, BatchBufs B, float mind, float maxd,
                                                                            int2 *__restrict__ grid, unsigned long long *__restrict__ counters) {
+    static_assert(LAT >= 1 && LAT <= 3, "the step is unrolled for LAT 1..3");
+    constexpr int RING = LAT + 1;                                 // entries of the B -> C rings
+    constexpr int UNROLL = (RING % 2) ? 2 * RING : RING;          // steps per loop body: the A -> B parity and the rings both come round
     __shared__ unsigned s_acc[4 * 512];                           // per wave: [8 sub-bricks][64 lanes] packed running sums
     const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     unsigned *const acc = s_acc + wid * 512 + lane;               // + 64 s
@@ -1150,8 +1168,12 @@ __global__ __launch_bounds__(256, UPD_WAVES) void tsdf_update_pairs_kernel(Cam c
     auto entry_of = [&](unsigned k) -> unsigned { return k >= 0x2000000u ? 0xffffffffu : k * ngrp + grp; };
     const DescPtr frames = const_descs(B);
     const int ntx0 = (cam.W + TILE0 - 1) >> TILE0_SHIFT;
-    const float trunc_free = g.trunc * 1.001f;
     const unsigned row_bytes = (unsigned)cam.W * (unsigned)sizeof(DT);
+    // the longer rings take scalar registers (80 a wave at this occupancy, all in use): constants that only the vector arithmetic
+    // of stages B and C reads move to vector registers, where there is room
+    const float c_mind = LAT > 1 ? keep_vector(mind) : mind, c_maxd = LAT > 1 ? keep_vector(maxd) : maxd;
+    const float c_inv_trunc = LAT > 1 ? keep_vector(g.inv_trunc) : g.inv_trunc;
+    const float trunc_free = LAT > 1 ? keep_vector(g.trunc * 1.001f) : g.trunc * 1.001f;
 
     auto fetch = [&](unsigned t, unsigned &brick, unsigned &fm, unsigned &subv, unsigned &slot) {
         brick = min((unsigned)__builtin_amdgcn_readfirstlane((int)B.order[t]), nbricks - 1u);
@@ -1208,7 +1230,7 @@ __global__ __launch_bounds__(256, UPD_WAVES) void tsdf_update_pairs_kernel(Cam c
         unsigned rest = (unsigned)__ballot((subv & 0xffu) != 0u);              // frames with at least one MIXED sub-brick (lanes 0..31)
         if (EXP & 16) { pf_b = __builtin_readcyclecounter(); pf_setup += pf_b - pf_a; pf_bricks += 1; pf_steps += npairs; }
         if (npairs) {
-            // ---- scalars of the frame stage A works in, of the pair stage B works on, of the three pairs on their way to stage C
+            // ---- scalars of the frame stage A works in, of the pair stage B works on, of the LAT + 1 pairs on their way to stage C
             float r0 = 0, r1 = 0, r2 = 0, r3 = 0, r4 = 0, r5 = 0, r6 = 0, r7 = 0, r8 = 0, t0 = 0, t1 = 0, t2 = 0, a_sc = 0;
             unsigned a_vp = 0, m = 0;
             const char *a_vt = nullptr, *a_img = nullptr;
@@ -1227,16 +1249,24 @@ __global__ __launch_bounds__(256, UPD_WAVES) void tsdf_update_pairs_kernel(Cam c
             switch_frame();
             const char *b_img = a_img;
             unsigned b_vp = a_vp;
-            float c_sc1 = a_sc, c_sc2 = a_sc;
-            unsigned c_s1 = 0, c_s2 = 0;
-            bool c_open2 = false;                                              // pair k - 2 left some voxel to its depth pixel (wave-uniform)
-            // ---- pipeline registers, by the parity of the pair: A -> B (zc or +inf, pixel offset, tile record), B -> C (zc / +-inf, depth)
-            float zcA[2] = {INFINITY, INFINITY}, zcB[2] = {INFINITY, INFINITY};
+            // ---- the hand-down from B to C, rings of LAT + 1 entries indexed by the pair number mod (LAT + 1): wave-uniform
+            // (sub-brick, the frame's depth scale, "some voxel of the pair is left to its depth pixel") and per lane (zc / +-inf,
+            // depth).  All indices are compile-time constants of the unrolled step: named registers, no moves
+            float c_sc[RING];
+            unsigned c_s[RING];
+            bool c_open[RING];
+            float zcB[RING];
+            typename PixLoad<DT>::raw dvB[RING];
+#pragma unroll
+            for (int i = 0; i < RING; ++i) { c_sc[i] = a_sc; c_s[i] = 0u; c_open[i] = false; zcB[i] = INFINITY; dvB[i] = 0; }
+            // ---- A -> B, by the parity of the pair: zc or +inf, pixel offset, tile record
+            float zcA[2] = {INFINITY, INFINITY};
             unsigned pixA[2] = {0u, 0u};
             float2 tlA[2] = {make_float2(0.f, 0.f), make_float2(0.f, 0.f)};
-            typename PixLoad<DT>::raw dvB[2] = {0, 0};
-            const unsigned nsteps = npairs + 2u;
-            auto step = [&](unsigned k, const int par) {
+            const unsigned nsteps = npairs + 1u + (unsigned)LAT;
+            if (EXP & 16) pf_steps += (unsigned long long)((nsteps + UNROLL - 1u) / UNROLL * UNROLL) << 32;   // steps run, above the pairs
+            auto step = [&](unsigned k, const int j) {                          // j = k mod UNROLL, a literal at every call
+                const int par = j & 1, rc = j % RING, rb = (j + LAT) % RING;   // rings: pair k's and pair k-1-LAT's slot; pair k-1's
                 // ---- A(k): the lane's voxel of sub-brick s in the current frame -> pixel, tile record.  An empty slot (k >= npairs)
                 // runs with the camera plane at infinity: nothing lies in front of it
                 const bool have = k < npairs;
@@ -1256,23 +1286,23 @@ __global__ __launch_bounds__(256, UPD_WAVES) void tsdf_update_pairs_kernel(Cam c
                 const unsigned n_vp = a_vp, n_s = s;
                 const float n_sc = a_sc;
                 if (m == 0u && rest != 0u) switch_frame();
-                // ---- C(k - 2): depth value -> increment of the running sum.  A pair whose every voxel the tiles decided (two in five)
+                // ---- C(k - 1 - LAT): depth value -> increment of the running sum.  A pair whose every voxel the tiles decided (two in five)
                 // has only "in front of everything" lanes (zc = -inf: tsdf = 1 exactly, and the pixel they read is valid) and "behind
                 // everything" lanes: no arithmetic
                 {
-                    const float zc = zcB[par];
+                    const float zc = zcB[rc];
                     unsigned inc;
-                    if (c_open2) {
-                        const float d = PixLoad<DT>::value(dvB[par]) * c_sc2;
+                    if (c_open[rc]) {
+                        const float d = PixLoad<DT>::value(dvB[rc]) * c_sc[rc];
                         const float sdf = d - zc;
-                        const bool ok = (d > mind && d < maxd) && (sdf >= -g.trunc);
-                        const float tsdf = fminf(1.0f, sdf * g.inv_trunc);
+                        const bool ok = (d > c_mind && d < c_maxd) && (sdf >= -g.trunc);
+                        const float tsdf = fminf(1.0f, sdf * c_inv_trunc);
                         const int q = (int)rintf(tsdf * 32767.0f);
                         inc = ok ? (unsigned)(q + 32768) + (1u << 21) : 0u;
                     } else {
                         inc = (zc < 0.0f) ? 65535u + (1u << 21) : 0u;
                     }
-                    if (!(EXP & 4) || inc == 0x12345u) (void)__hip_atomic_fetch_add(acc + 64u * c_s2, inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                    if (!(EXP & 4) || inc == 0x12345u) (void)__hip_atomic_fetch_add(acc + 64u * c_s[rc], inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
                 }
                 // ---- B(k - 1): what the tile leaves open gathers its pixel; the decided lanes read the frame's valid pixel
                 bool open1;
@@ -1280,17 +1310,19 @@ __global__ __launch_bounds__(256, UPD_WAVES) void tsdf_update_pairs_kernel(Cam c
                     const float zc = zcA[par ^ 1];
                     bool fre, skp;
                     pair_tile_test(tlA[par ^ 1], zc, trunc_free, g.trunc, fre, skp);
-                    zcB[par ^ 1] = fre ? -INFINITY : (skp ? INFINITY : zc);
+                    zcB[rb] = fre ? -INFINITY : (skp ? INFINITY : zc);
                     const unsigned pix = ((EXP & 2) || fre || skp) ? b_vp : pixA[par ^ 1];
-                    dvB[par ^ 1] = PixLoad<DT>::load(b_img, pix);
+                    dvB[rb] = PixLoad<DT>::load(b_img, pix);
                     open1 = __ballot(!(fre || skp)) != 0ull;
                 }
                 b_img = n_img; b_vp = n_vp;
-                c_sc2 = c_sc1; c_s2 = c_s1; c_open2 = open1; c_sc1 = n_sc; c_s1 = n_s;
+                c_open[rb] = open1; c_sc[rc] = n_sc; c_s[rc] = n_s;             // (C of this step has read slot rc)
             };
-            for (unsigned k = 0; k < nsteps; k += 2u) {                         // (an odd count: one more empty step)
+            for (unsigned k = 0; (int)k - (1 + LAT) < (int)npairs; k += (unsigned)UNROLL) {           // (no multiple of UNROLL: empty steps up to one)
                 step(k, 0);
                 step(k + 1u, 1);
+                if constexpr (UNROLL > 2) { step(k + 2u, 2); step(k + 3u, 3); }
+                if constexpr (UNROLL > 4) { step(k + 4u, 4); step(k + 5u, 5); }
             }
         }
         if (EXP & 16) { pf_a = __builtin_readcyclecounter(); pf_loop += pf_a - pf_b; }
@@ -1761,23 +1793,46 @@ int launch_tsdf_update(hipStream_t s, const Cam &cam, const Grid &g, int n, int 
     (void)xcd_group;
 #ifdef TL3D_EXPERIMENTS
     static const int pexp = getenv("TL3D_PAIRS_EXP") ? atoi(getenv("TL3D_PAIRS_EXP")) : 0;
-#define TL3D_LAUNCH_PEXP(E_) \
-    hipLaunchKernelGGL((tsdf_update_pairs_kernel<false, float, E_>), dim3(nblk), dim3(256), 0, s, cam, g, B, mind, maxd, grid, counters)
+    static const int plat = getenv("TL3D_PAIRS_LAT") ? atoi(getenv("TL3D_PAIRS_LAT")) : 0;       // A/B on one box: 1..3, else what ships
+#define TL3D_LAUNCH_PEXP_L(E_, L_) \
+    hipLaunchKernelGGL((tsdf_update_pairs_kernel<false, float, E_, L_>), dim3(nblk), dim3(256), 0, s, cam, g, B, mind, maxd, grid, counters)
+#define TL3D_LAUNCH_PEXP(E_) TL3D_LAUNCH_PEXP_L(E_, (PairsLat<false, float>::value))
+#define TL3D_LAUNCH_PEXP_BY_LAT(E_) /* the modes that are run per LAT: no depth gathers, stamps */ \
+    do {                                                                                           \
+        if (plat == 1) TL3D_LAUNCH_PEXP_L(E_, 1); else if (plat == 2) TL3D_LAUNCH_PEXP_L(E_, 2);   \
+        else if (plat == 3) TL3D_LAUNCH_PEXP_L(E_, 3); else TL3D_LAUNCH_PEXP(E_);                  \
+    } while (0)
     if (pexp && !count && !depth_u16) {
         switch (pexp) {
             case 1: TL3D_LAUNCH_PEXP(1); break;
-            case 2: TL3D_LAUNCH_PEXP(2); break;
+            case 2: TL3D_LAUNCH_PEXP_BY_LAT(2); break;
             case 3: TL3D_LAUNCH_PEXP(3); break;
             case 4: TL3D_LAUNCH_PEXP(4); break;
             case 7: TL3D_LAUNCH_PEXP(7); break;
             case 8: TL3D_LAUNCH_PEXP(8); break;
-            case 16: TL3D_LAUNCH_PEXP(16); break;
+            case 16: TL3D_LAUNCH_PEXP_BY_LAT(16); break;
             case 32: TL3D_LAUNCH_PEXP(32); break;
             default: TL3D_LAUNCH_PEXP(15); break;
         }
         TL3D_HIP(hipGetLastError());
         return TL3D_OK;
     }
+#undef TL3D_LAUNCH_PEXP_BY_LAT
+#undef TL3D_LAUNCH_PEXP
+#undef TL3D_LAUNCH_PEXP_L
+#define TL3D_LAUNCH_PLAT(L_)                                                                                                                       \
+    do {                                                                                                                                           \
+        if (depth_u16) hipLaunchKernelGGL((tsdf_update_pairs_kernel<false, uint16_t, 0, L_>), dim3(nblk), dim3(256), 0, s, cam, g, B, mind, maxd,  \
+                                          grid, counters);                                                                                         \
+        else hipLaunchKernelGGL((tsdf_update_pairs_kernel<false, float, 0, L_>), dim3(nblk), dim3(256), 0, s, cam, g, B, mind, maxd, grid,         \
+                                counters);                                                                                                         \
+    } while (0)
+    if (plat >= 1 && plat <= 3 && !count) {
+        if (plat == 1) TL3D_LAUNCH_PLAT(1); else if (plat == 2) TL3D_LAUNCH_PLAT(2); else TL3D_LAUNCH_PLAT(3);
+        TL3D_HIP(hipGetLastError());
+        return TL3D_OK;
+    }
+#undef TL3D_LAUNCH_PLAT
 #endif
 #define TL3D_LAUNCH_PAIRS(C_, T_) \
     hipLaunchKernelGGL((tsdf_update_pairs_kernel<C_, T_>), dim3(nblk), dim3(256), 0, s, cam, g, B, mind, maxd, grid, counters)

@@ -1815,8 +1815,10 @@ int tl3d_get_stats(tl3d_ctx *ctx, tl3d_stats *out) {
     ctx->stats.tsdf_bricks_free_counted = h[6];
     ctx->stats.tsdf_batch_bricks = h[7];
 #ifdef TL3D_EXPERIMENTS
-    if (h[14]) fprintf(stderr, "[tl3d exp] update kernel, per wave (s_memtime ticks): setup %.0f  pair loop %.0f  record update %.0f  lifetime %.0f;  bricks per wave %.2f, pairs per brick %.1f, waves %llu; longest wave %.0f x launches\n",
-                       (double)h[8] / h[14], (double)h[9] / h[14], (double)h[10] / h[14], (double)h[11] / h[14], (double)h[12] / h[14], h[12] ? (double)h[13] / h[12] : 0.0, h[14], (double)h[15]);
+    if (h[14]) fprintf(stderr, "[tl3d exp] update kernel, per wave (s_memtime ticks): setup %.0f  pair loop %.0f  record update %.0f  lifetime %.0f;  bricks per wave %.2f, pairs per brick %.1f, steps per pair %.3f, waves %llu; longest wave %.0f x launches\n",
+                       (double)h[8] / h[14], (double)h[9] / h[14], (double)h[10] / h[14], (double)h[11] / h[14], (double)h[12] / h[14],
+                       h[12] ? (double)(h[13] & 0xffffffffull) / h[12] : 0.0, (h[13] & 0xffffffffull) ? (double)(h[13] >> 32) / (double)(h[13] & 0xffffffffull) : 0.0,
+                       h[14], (double)h[15]);
     if (h[14]) tsdf_debug_print_spans(ctx->tsdf_max_blocks * 4 > 16384 ? 16384 : ctx->tsdf_max_blocks * 4);
 #endif
     if (ctx->brick_tabs) {
