@@ -1,4 +1,4 @@
-"""A plain numpy model of the TSDF prep chain (kernels_tsdf.hip): the tile pyramid, the brick class, the sub-brick class, and the
+"""A plain numpy model of the TSDF prep chain (kernels_tsdf_prep.hip): the tile pyramid, the brick class, the sub-brick class, and the
 per-voxel truth the classes must be conservative against.  TEST REFERENCE ONLY.
 
 It restates the rule from the kernels' comments and code in f32 scalars, one brick at a time.  It is NOT kept bit-equal with the

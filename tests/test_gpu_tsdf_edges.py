@@ -98,7 +98,7 @@ def attach_exact_pool(ctx, cases, slot_of):
     """Give the grid-less context a SPARSE grid whose pool holds exactly the bricks this fusion gives records to.  That is the
     library's own count (count_bricks: the fusion's classification without records), not the number of bricks the oracle
     touches: the classification is conservative, so a brick on the image border or beside a hole is listed -- and takes a slot --
-    although no voxel of it is updated in the end (kernels_tsdf.hip, brick_cull_kernel), while a brick that is free space in
+    although no voxel of it is updated in the end (kernels_tsdf_prep.hip, brick_cull_kernel), while a brick that is free space in
     every frame is touched by the oracle and keeps a 4-byte count instead of records.  What the oracle's grid does bound: every
     brick holding a record that is not pure free space was listed, so it needs a slot."""
     geom = tl3d.GridSpec(cases[0].dims, cases[0].origin, ec.VOXEL, ec.TRUNC, tl3d.CH_TSDF)

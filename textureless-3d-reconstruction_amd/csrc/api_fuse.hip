@@ -310,7 +310,7 @@ int tl3d::flush_updates(tl3d_ctx *ctx) {
     // profiling mode: one event pair around the update kernel
     const int kt = ktimer_begin(ctx);
     rc = launch_tsdf_update(ctx->stream, ctx->cam, ctx->grid, c.n, ctx->tsdf_batch, c.depth_u16, c.mind, c.maxd, ctx->tsdf, ctx->tsdf_scratch[half],
-                            ctx->d_counters, ctx->count_records, ctx->tsdf_max_blocks, ctx->tsdf_xcd_group);
+                            ctx->d_counters, ctx->count_records, ctx->tsdf_max_blocks);
     if (rc == TL3D_OK) ctx->stats.tsdf_launches++;
     if (kt >= 0) {
         ctx->ktimers[kt].launches = rc == TL3D_OK ? 1 : 0;

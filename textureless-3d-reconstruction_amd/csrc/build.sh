@@ -16,9 +16,13 @@ fi
 OBJS=()
 PIDS=()
 mkdir -p "${BUILD}"
-for f in tl3d_api api_fuse api_mesh api_register kernels_backproject kernels_centroid kernels_tsdf kernels_icp kernels_icp_eval kernels_compact kernels_extract kernels_mesh kernels_meshcc kernels_meshsimplify kernels_meshsmooth kernels_meshweld kernels_raycast kernels_track kernels_cellgrid kernels_sor kernels_nearest kernels_normals kernels_grid; do
+for f in tl3d_api api_fuse api_mesh api_register kernels_backproject kernels_centroid kernels_tsdf_prep kernels_tsdf kernels_icp kernels_icp_eval kernels_compact kernels_extract kernels_mesh kernels_meshcc kernels_meshsimplify kernels_meshsmooth kernels_meshweld kernels_raycast kernels_track kernels_cellgrid kernels_sor kernels_nearest kernels_normals kernels_grid; do
   src="${HERE}/${f}.hip"; obj="${BUILD}/${f}.o"
-  if [[ ! -f "$obj" || "$src" -nt "$obj" || "${HERE}/tl3d_internal.h" -nt "$obj" || "${HERE}/api_host.h" -nt "$obj" || "${HERE}/bp_device.h" -nt "$obj" || "${HERE}/icp_sample.h" -nt "$obj" || "${HERE}/tsdf_cell.h" -nt "$obj" || "${HERE}/mc_tables.h" -nt "$obj" || "${HERE}/compact.h" -nt "$obj" || "${HERE}/keytab.h" -nt "$obj" || "${HERE}/cellgrid.h" -nt "$obj" || "${HERE}/sym3_eigen.h" -nt "$obj" || "${HERE}/../../include/tl3d.h" -nt "$obj" ]]; then
+  stale=0                                          # no object yet, or the source or ANY header is newer than it
+  for dep in "$src" "${HERE}"/*.h "${HERE}/../../include/tl3d.h"; do
+    if [[ ! -f "$obj" || "$dep" -nt "$obj" ]]; then stale=1; break; fi
+  done
+  if [[ "$stale" == 1 ]]; then
     rm -f "$obj"                                   # a failed compile must not leave a stale object to link
     "$HIPCC" "${FLAGS[@]}" ${TL3D_EXTRA_FLAGS:-} -c "$src" -o "$obj" &
     PIDS+=($!)

@@ -340,7 +340,6 @@ static int build_grid(tl3d_ctx *ctx, const tl3d_config *cfg) {
             ctx->tsdf_max_blocks = env_int("TL3D_UPDATE_BLOCKS", 12 * cus);
         }
         if (ctx->tsdf_max_blocks < 8) ctx->tsdf_max_blocks = 8;
-        ctx->tsdf_xcd_group = env_int("TL3D_XCD_GROUP", 1);       // consecutive list entries per ticket chunk (1: best balance; 16: 41.8k against 43.8k frames/s)
         ctx->tsdf_single_stream = env_int("TL3D_SINGLE_STREAM", 0) != 0;
         {   // the scratch of the batches in flight (TSDF_SCRATCHES): one allocation; the frame masks start out zero (the update re-arms them)
             const size_t each = (tsdf_batch_scratch_bytes(ctx->cam, g, ctx->tsdf_batch) + 255) & ~(size_t)255;

@@ -222,7 +222,7 @@ struct Slot {
     bool has_color = false;
     bool loaded = false;
     bool has_normals = false;
-    // TSDF tile cache: what the TSDF prep derives from the depth image, the scale and the depth limits alone (kernels_tsdf.hip:
+    // TSDF tile cache: what the TSDF prep derives from the depth image, the scale and the depth limits alone (kernels_tsdf_prep.hip:
     // depth_tiles_kernel, tile_pyramid_kernel).  One lazily allocated block (tl3d_ctx::pool_tiles, tsdf_tile_cache_bytes) and the
     // key it was built with; every writer of `depth` calls slot_rewritten (tl3d_api.hip), which clears tc.  The u16 and f32 images give
     // the same tiles (mm_to_m is the conversion the f32 copy was made with, no contraction, no fast math): the depth kind is no part of the key.
@@ -233,7 +233,7 @@ struct Slot {
     float tc_mind = 0, tc_maxd = 0;
     Cached tc;
     // TSDF classification cache: the brick cull's and the sub-brick classification's result for ONE key (ClassKey: pose, scale,
-    // depth limits, grid geometry), replayed when a batch meets the slot again with that key (kernels_tsdf.hip:
+    // depth limits, grid geometry), replayed when a batch meets the slot again with that key (kernels_tsdf_prep.hip:
     // class_replay_kernel).  It lives behind the tiles in the slot's block of tl3d_ctx::pool_tiles (tsdf_class_cache_bytes).  It is made from the
     // slot's tiles: every rebuild of those drops it (api_fuse.hip: tile_cache_lookup).  cc_level: 1 = lists and counts (what a
     // classify-only chain can fill), 2 = + sub-brick masks, 3 = masks refined by the per-voxel tile test (class_refine_kernel: the first
@@ -386,7 +386,7 @@ struct tl3d_ctx : tl3d_grid_state {
     double *bp_factors;                  // projection factors (D2R:287-295): [0, W) xf[u] = (u - cx) / fx, [W, W + H) yf[v] = (v - cy) / fy
     hipEvent_t ev_free;                   // recorded on the main stream behind its last write to free_cnt (clear, fold); prep chains wait for it
     bool ev_free_recorded;
-    int tsdf_max_blocks, tsdf_xcd_group;  // launch geometry of the update kernel (12 workgroups per CU, XCD-grouped lists)
+    int tsdf_max_blocks;                  // launch geometry of the update kernel (12 workgroups per CU)
     bool tsdf_single_stream;
     void *rccl_comm;             // ncclComm_t of tl3d_rccl_init (RCCL is dlopen'ed: tl3d_api.hip)
     int rccl_world;
@@ -606,7 +606,7 @@ int launch_centroid_mark(hipStream_t s, const Cam &cam, const Grid &g, const BpA
 void tsdf_debug_print_spans(int nwaves);
 #endif
 int launch_tsdf_update(hipStream_t s, const Cam &cam, const Grid &g, int n, int max_frames, bool depth_u16, float mind, float maxd, int2 *grid,
-                       void *scratch, unsigned long long *counters, bool count, int max_blocks, int xcd_group);
+                       void *scratch, unsigned long long *counters, bool count, int max_blocks);
 int launch_fold_free(hipStream_t s, const Grid &g, int2 *grid, unsigned *free_cnt);
 // normals + icp
 int launch_nmap_rowmajor(hipStream_t s, const Cam &cam, const float4 *nmap, float4 *out);

@@ -1,4 +1,4 @@
-# usage (GPU box): bash tools/pmc_chunk.sh "VAR=val ..." ...   -- FETCH_SIZE per frame and L2 hit rate of tsdf_update_kernel per setting (experiments flavour); appends to gpurun_out/r03_pmc_chunk.txt
+# usage (GPU box): bash tools/pmc_chunk.sh "VAR=val ..." ...   -- FETCH_SIZE per frame and L2 hit rate of tsdf_update_pairs_kernel per setting (experiments flavour); appends to the r03_pmc_chunk.txt that the loop below names
 set -uo pipefail
 export TMPDIR=/tmp
 cd "$(dirname "${BASH_SOURCE[0]}")/.."
@@ -15,7 +15,7 @@ from collections import defaultdict
 a = defaultdict(list)
 for f in glob.glob("/tmp/pmcc/**/*counter_collection.csv", recursive=True):
     for r in csv.DictReader(open(f)):
-        if "tsdf_update_kernel<false" in r["Kernel_Name"]:
+        if "tsdf_update_pairs_kernel<false" in r["Kernel_Name"]:
             a[r["Counter_Name"]].append(float(r["Counter_Value"]))
 m = {k: sum(v) / len(v) for k, v in a.items()}
 import json

@@ -1,7 +1,7 @@
 #!/usr/bin/env bash
 # usage (GPU box, repo root): bash tools/pmc_quick.sh <tag> [extra env assignments for the experiments flavour]
 # Separate rocprofv3 --pmc passes (never combined with tracing) over ONE step of 64 frames of the headline bench; prints the
-# per-dispatch mean of every counter for tsdf_update_kernel.
+# per-dispatch mean of every counter for the update kernel.
 set -uo pipefail
 TAG="${1:-pmc}"; shift || true
 export TMPDIR=/tmp

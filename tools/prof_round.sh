@@ -1,7 +1,7 @@
 #!/usr/bin/env bash
 # usage (GPU box, repo root):  bash tools/prof_round.sh r03
 # 1. rocprofv3 --kernel-trace --stats of (a) the timed loop alone (`bench.py --no-cpu-baseline --no-rows --no-single`: every
-#    tsdf_update_kernel dispatch is a 32-frame launch of the headline workload, so its average duration must agree with
+#    dispatch of the update kernel is a 32-frame launch of the headline workload, so its average duration must agree with
 #    roofline.ms_per_launch) and (b) the DEFAULT command (all rows; the update kernel's dispatches split by the phase of bench.py they belong to);
 # 2. separate --pmc passes (never combined with tracing; FETCH_SIZE and WRITE_SIZE cannot share a pass on gfx950) over ONE step of
 #    64 frames (two update launches of 32 frames) of the same workload -> per-dispatch means for every tl3d kernel, pmc_traffic.json;
