@@ -58,6 +58,17 @@ def main(argv=None):
                         help="neighbours further than this many metres are left out (default 0: no limit)")
     parser.add_argument("--cloud-curvature", action="store_true",
                         help="with --cloud-normals: also write the surface variation l0 / (l0 + l1 + l2) as `curvature`")
+    parser.add_argument("--cloud-planes", action="store_true",
+                        help="with --cloud-normals: segment the fused cloud into planar regions on the GPU (walls, floors, ceilings) and "
+                             "write each point's plane number as `plane` (-1: none)")
+    parser.add_argument("--cloud-planes-angle", type=float, default=10.0, metavar="DEG",
+                        help="largest angle between the normals of two linked points (default 10)")
+    parser.add_argument("--cloud-planes-min-points", type=int, default=200, metavar="N",
+                        help="smallest region that can be a plane (default 200)")
+    parser.add_argument("--cloud-planes-max-curvature", type=float, default=0.05, metavar="C",
+                        help="points with a surface variation above this take no part (creases; 0: no bound; default 0.05)")
+    parser.add_argument("--cloud-planes-report", default=None, metavar="FILE.json",
+                        help="with --cloud-planes: write the plane table (normal, d, centroid, rms, count) as JSON")
     parser.add_argument("--device", type=int, default=0)
     args = parser.parse_args(argv)
 
@@ -65,6 +76,10 @@ def main(argv=None):
         parser.error("--cloud-curvature comes out of the normal estimation: it needs --cloud-normals")
     if not 3 <= args.cloud_normals_neighbors <= 64:
         parser.error("--cloud-normals-neighbors must lie in [3, 64]")
+    if (args.cloud_planes or args.cloud_planes_report) and not (args.cloud_planes and args.cloud_normals):
+        parser.error("--cloud-planes segments the cloud by its normals: it needs --cloud-normals (and --cloud-planes-report needs --cloud-planes)")
+    if args.cloud_planes_min_points < 3:
+        parser.error("--cloud-planes-min-points must be 3 at the least")
     if args.compare_threshold and len(args.compare_threshold) > 8:
         parser.error("--compare-threshold: at most 8 thresholds")
     from tl3d import fileio
@@ -83,6 +98,8 @@ def main(argv=None):
     config = ReconstructionConfig(fx=args.fx, fy=args.fy, cx=args.cx, cy=args.cy, min_depth=0.1, max_depth=100.0,
                                   voxel_size=0.005, subsample_factor=4, grid_dim=args.grid, device=args.device,
                                   depth_scale=args.depth_scale, loop_closure=args.loop_closure, model_tracking=args.model_tracking,
+                                  cloud_planes=args.cloud_planes, cloud_planes_angle_deg=args.cloud_planes_angle,
+                                  cloud_planes_min_points=args.cloud_planes_min_points, cloud_planes_max_curvature=args.cloud_planes_max_curvature,
                                   cloud_normals=args.cloud_normals, cloud_normals_neighbors=args.cloud_normals_neighbors,
                                   cloud_normals_radius=args.cloud_normals_radius, cloud_curvature=args.cloud_curvature,
                                   compare_to=args.compare_to, compare_max_dist=args.compare_max_dist,
@@ -140,7 +157,9 @@ def main(argv=None):
     points, colors, poses = result
     out_dir.mkdir(parents=True, exist_ok=True)
     fileio.save_reconstruction(points, colors, out_dir / "reconstruction.ply", normals=pipeline.cloud_normals,
-                               curvature=pipeline.cloud_curvature)
+                               curvature=pipeline.cloud_curvature, planes=pipeline.cloud_plane_ids)
+    if args.cloud_planes_report:
+        fileio.write_plane_report(args.cloud_planes_report, pipeline.cloud_planes)
     print(f"Saved {len(points)} points to {out_dir / 'reconstruction.ply'}")
     return 0
 

@@ -114,6 +114,17 @@ def main(argv=None):
                         help="neighbours further than this many metres are left out (default 0: no limit)")
     parser.add_argument("--cloud-curvature", action="store_true",
                         help="with --cloud-normals: also write the surface variation l0 / (l0 + l1 + l2) as `curvature`")
+    parser.add_argument("--cloud-planes", action="store_true",
+                        help="with --cloud-normals: segment the fused cloud into planar regions on the GPU (walls, floors, ceilings) and "
+                             "write each point's plane number as `plane` (-1: none)")
+    parser.add_argument("--cloud-planes-angle", type=float, default=10.0, metavar="DEG",
+                        help="largest angle between the normals of two linked points (default 10)")
+    parser.add_argument("--cloud-planes-min-points", type=int, default=200, metavar="N",
+                        help="smallest region that can be a plane (default 200)")
+    parser.add_argument("--cloud-planes-max-curvature", type=float, default=0.05, metavar="C",
+                        help="points with a surface variation above this take no part (creases; 0: no bound; default 0.05)")
+    parser.add_argument("--cloud-planes-report", default=None, metavar="FILE.json",
+                        help="with --cloud-planes: write the plane table (normal, d, centroid, rms, count) as JSON")
     parser.add_argument("--device", type=int, default=0)
     parser.add_argument("--stream", dest="stream", action="store_true", default=True,
                         help="(default) decode on worker threads into pinned buffers with asynchronous uploads; host RAM never holds the sequence")
@@ -141,6 +152,10 @@ def main(argv=None):
         parser.error("--cloud-curvature comes out of the normal estimation: it needs --cloud-normals")
     if not 3 <= args.cloud_normals_neighbors <= 64:
         parser.error("--cloud-normals-neighbors must lie in [3, 64]")
+    if (args.cloud_planes or args.cloud_planes_report) and not (args.cloud_planes and args.cloud_normals):
+        parser.error("--cloud-planes segments the cloud by its normals: it needs --cloud-normals (and --cloud-planes-report needs --cloud-planes)")
+    if args.cloud_planes_min_points < 3:
+        parser.error("--cloud-planes-min-points must be 3 at the least")
     if args.compare_threshold and len(args.compare_threshold) > 8:
         parser.error("--compare-threshold: at most 8 thresholds")
     if args.loop_closure and (args.gpus > 1 or world > 1):
@@ -170,6 +185,8 @@ def main(argv=None):
                                   mesh_largest_component=args.mesh_largest_component, mesh_simplify_cell=args.mesh_simplify_cell,
                                   mesh_simplify_placement=args.mesh_simplify_placement,
                                   mesh_smooth_iterations=args.mesh_smooth, mesh_normals=args.mesh_normals, mesh_weld=args.mesh_weld,
+                                  cloud_planes=args.cloud_planes, cloud_planes_angle_deg=args.cloud_planes_angle,
+                                  cloud_planes_min_points=args.cloud_planes_min_points, cloud_planes_max_curvature=args.cloud_planes_max_curvature,
                                   cloud_normals=args.cloud_normals, cloud_normals_neighbors=args.cloud_normals_neighbors,
                                   cloud_normals_radius=args.cloud_normals_radius, cloud_curvature=args.cloud_curvature,
                                   compare_to=args.compare_to, compare_max_dist=args.compare_max_dist,
@@ -205,7 +222,10 @@ def main(argv=None):
         points, colors, poses = pipeline.reconstruct(anchors=anchors, estimate_scale=args.estimate_scale)
     if points is not None and len(points) > 0:
         pipeline.save_reconstruction(points, colors, args.output, ascii=args.ascii, normals=pipeline.cloud_normals,
-                                     curvature=pipeline.cloud_curvature)
+                                     curvature=pipeline.cloud_curvature, planes=pipeline.cloud_plane_ids)
+        if args.cloud_planes_report:
+            from tl3d import fileio
+            fileio.write_plane_report(args.cloud_planes_report, pipeline.cloud_planes)
         if args.mesh_output:
             pipeline.save_mesh(args.mesh_output, ascii=args.ascii)
         if not args.no_vis:

@@ -644,6 +644,58 @@ int tl3d_estimate_normals(tl3d_ctx *ctx, const float *xyz_hd, int64_t n,
                           const double *viewpoints_h, int64_t n_viewpoints,
                           float *normal_out_hd, float *curvature_out_hd, int64_t *out_degenerate);
 
+/* Planar regions of a point list with normals (no reference code: the reference never segments its cloud -- the
+ * rules are ours: smoothness-constrained region growing as in PCL's RegionGrowing with a planarity test behind it, the question
+ * Open3D's detect_planar_patches answers).  Host or device pointers for xyz [n][3], normal [n][3], curvature [n] (may be NULL),
+ * plane_id_out [n] and planes_out [plane_cap] (may be NULL with plane_cap 0); params and out_counts [4] are host memory; no grid
+ * is needed.  All arithmetic is fp64 on the f32 inputs converted exactly, plain products and sums in x, y, z order.
+ * Eligible point: the squared length of its normal is finite and > 0; with a curvature array and max_curvature > 0 also
+ * curvature <= max_curvature (a NaN compares false: not eligible).
+ * Link between eligible i != j (symmetric), when all of: d^2 = dx dx + dy dy + dz dz <= radius * radius (one product; a pair exactly
+ * on the radius is linked); s = n_i . n_j, |s| unless signed_normals, s >= min_cos; |n_i . (p_j - p_i)| <= max_offset and
+ * |n_j . (p_i - p_j)| <= max_offset.
+ * Region: a connected component of the link graph over the eligible points; its label is its smallest point index (its seed).  The
+ * partition is a function of the point SET; only the numbering follows the input order.
+ * Moments of a region with count >= min_points, about its seed: Q(x) = llrint(x * 2^20), e = Q(p) - Q(p_seed); the sums count,
+ * sum e (3), sum e_a e_b (6, 128-bit) and sum N with N = llrint(n * 2^20) (3; a normal component beyond +-2^11 is clamped to it)
+ * are exact integers, so their order is free and every run gives the same sums.  (sum e and sum N are kept in 64 bits; the call
+ * refuses a cloud where sum e might not fit: n * (E * 2^20 + 1) must stay below 2^62, E the largest extent of the points' box in
+ * metres -- 2^31 points over 2 km, 2^20 points over 4 000 km.)
+ * Plane of a region, one fixed fp64 sequence on those sums: m = sum e / count, C_ab = sum e_a e_b - sum e_a * sum e_b / count;
+ * l0 <= l1 <= l2 and the unit eigenvector of l0 by cyclic Jacobi; the normal is negated when normal . sum N < 0 and left as it is
+ * when that is 0; centroid = (Q(p_seed) + m) * 2^-20, d = normal . centroid, rms = sqrt(max(l0, 0) / count) * 2^-20.
+ * Accepted as a plane: count >= min_points, l2 > 0 and (max_rms <= 0 or rms <= max_rms).  Accepted planes are numbered 0 .. P-1 in
+ * ascending label; plane_id_out[i] = the number of i's accepted plane, else -1 (ineligible points, small regions, rejected regions).
+ * out_counts = {eligible points, regions, regions with count >= min_points, planes}.  plane_cap < planes: TL3D_E_CAPACITY with the
+ * four counts stored and plane_id_out written, but no plane record.  cell_size > 0 only sets the search grid (doubled until it has
+ * at most 2^27 cells) and never changes a result; n == 0 is TL3D_OK.  A gently curved surface grows into ONE region, which max_rms
+ * then rejects; planes that meet at a crease are kept apart by max_curvature on the crease's blended normals.
+ * TL3D_E_INVALID before any device work, with nothing written: a null ctx, xyz, normal, params, plane_id_out or out_counts (or
+ * planes_out with plane_cap > 0), n < 0 or n >= 2^31, plane_cap < 0, radius not finite or <= 0, min_cos outside [0, 1] or NaN, a
+ * negative or NaN max_offset, min_points < 3, cell_size not > 0, reserved != 0, an output that overlaps an input or the other
+ * output; and from the device pass in front of the index, with nothing written: a non-finite coordinate, |x| >= 2^22 m, or
+ * n * (E * 2^20 + 1) >= 2^62.
+ * Tests (tests/test_gpu_plane_segments.py): plane_id, the counts and every plane's count and seed equal two numpy / scipy
+ * formulations exactly on crafted clouds, decision edges one f32 ulp apart and union-find topologies; the same bytes for every cell
+ * size, for host and device arrays and in every run; the plane parameters within a derived bar of the exact sums' answer. */
+typedef struct tl3d_plane_params {
+    double radius, min_cos, max_offset, max_curvature, max_rms;
+    int64_t min_points;
+    int32_t signed_normals;
+    int32_t reserved;
+} tl3d_plane_params;
+typedef struct tl3d_plane {
+    double normal[3];
+    double d;
+    double centroid[3];
+    double rms;
+    int64_t count;
+    int64_t seed;
+} tl3d_plane;
+int tl3d_segment_planes(tl3d_ctx *ctx, const float *xyz_hd, const float *normal_hd, const float *curvature_hd, int64_t n,
+                        const tl3d_plane_params *params, double cell_size,
+                        int32_t *plane_id_out_hd, tl3d_plane *planes_out_hd, int64_t plane_cap, int64_t *out_counts /* [4] */);
+
 /* Exact nearest neighbours from one set to ANOTHER (no reference code: the reference never scores a cloud -- the
  * definition is Open3D's compute_point_cloud_distance).  Per query point q: dist_out[q] = the fp64 distance to the nearest target
  * point (differences of the f32 coordinates, squares and their sum in fp64, one correctly rounded root) and index_out[q] = its index;

@@ -26,7 +26,7 @@ SYMBOLS = [
     "tl3d_slot_wait", "tl3d_attach_grid", "tl3d_detach_grid", "tl3d_set_block_core", "tl3d_backproject", "tl3d_backproject_device", "tl3d_frame_bounds", "tl3d_frames_bounds", "tl3d_count_bricks", "tl3d_accumulate_centroid",
     "tl3d_accumulate_points", "tl3d_points_bounds", "tl3d_integrate", "tl3d_build_normals",
     "tl3d_download_normals", "tl3d_icp_p2plane", "tl3d_icp_enqueue", "tl3d_icp_collect", "tl3d_icp_batch_enqueue", "tl3d_icp_batch_collect", "tl3d_icp_evaluate_pairs", "tl3d_host_pack_bgr_rows", "tl3d_host_copy_rows", "tl3d_build_normals_many", "tl3d_fuse_frames", "tl3d_grid_reset", "tl3d_grid_device_ptr",
-    "tl3d_grid_download", "tl3d_grid_upload", "tl3d_grid_add", "tl3d_grid_touched_bricks", "tl3d_grid_pack_bricks", "tl3d_grid_unpack_bricks", "tl3d_rccl_unique_id", "tl3d_rccl_init", "tl3d_allreduce_grid", "tl3d_extract", "tl3d_extract_mesh", "tl3d_extract_mesh_keyed", "tl3d_mesh_components", "tl3d_mesh_filter_components", "tl3d_mesh_simplify_clusters", "tl3d_mesh_simplify_quadric", "tl3d_mesh_smooth_taubin", "tl3d_mesh_vertex_normals", "tl3d_mesh_weld_keyed", "tl3d_raycast", "tl3d_track_evaluate", "tl3d_track_frame", "tl3d_statistical_outlier", "tl3d_knn_mean_distance", "tl3d_estimate_normals",
+    "tl3d_grid_download", "tl3d_grid_upload", "tl3d_grid_add", "tl3d_grid_touched_bricks", "tl3d_grid_pack_bricks", "tl3d_grid_unpack_bricks", "tl3d_rccl_unique_id", "tl3d_rccl_init", "tl3d_allreduce_grid", "tl3d_extract", "tl3d_extract_mesh", "tl3d_extract_mesh_keyed", "tl3d_mesh_components", "tl3d_mesh_filter_components", "tl3d_mesh_simplify_clusters", "tl3d_mesh_simplify_quadric", "tl3d_mesh_smooth_taubin", "tl3d_mesh_vertex_normals", "tl3d_mesh_weld_keyed", "tl3d_raycast", "tl3d_track_evaluate", "tl3d_track_frame", "tl3d_statistical_outlier", "tl3d_knn_mean_distance", "tl3d_estimate_normals", "tl3d_segment_planes",
     "tl3d_nearest_points", "tl3d_nearest_triangles", "tl3d_distance_summary", "tl3d_set_nearest_query_order",
     "tl3d_set_profile", "tl3d_set_normal_smoothing", "tl3d_set_tsdf_pairing", "tl3d_tile_cache_info", "tl3d_class_cache_info", "tl3d_class_refine_info", "tl3d_get_stats", "tl3d_reset_stats", "tl3d_event_record", "tl3d_event_elapsed_ms",
 ]
@@ -77,6 +77,16 @@ class MeshPart(C.Structure):
 class DistanceStats(C.Structure):
     _fields_ = [("n", C.c_int64), ("n_finite", C.c_int64), ("sum", C.c_double), ("sum_sq", C.c_double), ("max", C.c_double),
                 ("below", C.c_int64 * 8)]
+
+
+class PlaneParams(C.Structure):
+    _fields_ = [("radius", C.c_double), ("min_cos", C.c_double), ("max_offset", C.c_double), ("max_curvature", C.c_double),
+                ("max_rms", C.c_double), ("min_points", C.c_int64), ("signed_normals", C.c_int32), ("reserved", C.c_int32)]
+
+
+# tl3d_plane as a numpy record (80 bytes, no padding)
+PLANE_DTYPE = np.dtype([("normal", np.float64, (3,)), ("d", np.float64), ("centroid", np.float64, (3,)), ("rms", np.float64),
+                        ("count", np.int64), ("seed", np.int64)])
 
 
 ICP_MAX_LEVELS = 4
@@ -242,6 +252,7 @@ def load():
         "tl3d_statistical_outlier": [vp, vp, i64, i32, dbl, dbl, vp, C.POINTER(i64)],
         "tl3d_knn_mean_distance": [vp, vp, i64, i32, dbl, vp],
         "tl3d_estimate_normals": [vp, vp, i64, i32, dbl, dbl, vp, i64, vp, vp, C.POINTER(i64)],
+        "tl3d_segment_planes": [vp, vp, vp, vp, i64, C.POINTER(PlaneParams), dbl, vp, vp, i64, C.POINTER(i64)],
         "tl3d_nearest_points": [vp, vp, i64, vp, i64, dbl, dbl, vp, vp],
         "tl3d_nearest_triangles": [vp, vp, i64, vp, i64, vp, i64, dbl, dbl, vp, vp],
         "tl3d_distance_summary": [vp, vp, i64, vp, i32, C.POINTER(DistanceStats)],

@@ -110,6 +110,19 @@ class ReconstructionConfig:
     cloud_normals_neighbors: int = 30
     cloud_normals_radius: float = 0.0
     cloud_curvature: bool = False
+    # planar regions of the cloud with normals: points are linked within cloud_planes_radius when their normals
+    # lie within cloud_planes_angle_deg and each within cloud_planes_offset of the other's tangent plane; points with a surface
+    # variation above cloud_planes_max_curvature (0: no bound) take no part; a region of at least cloud_planes_min_points points whose
+    # plane fits with rms <= cloud_planes_max_rms is a plane.  A length of 0 means 2.5 voxels (radius), 1 voxel (offset), 0.5 voxel (rms).
+    # DepthToReconstructionPipeline.cloud_plane_ids / .cloud_planes, written by save_reconstruction as `plane`.  Needs cloud_normals.
+    # Off: nothing changes.
+    cloud_planes: bool = False
+    cloud_planes_radius: float = 0.0
+    cloud_planes_angle_deg: float = 10.0
+    cloud_planes_offset: float = 0.0
+    cloud_planes_max_curvature: float = 0.05
+    cloud_planes_min_points: int = 200
+    cloud_planes_max_rms: float = 0.0
 
     @property
     def K(self) -> np.ndarray:

@@ -1675,6 +1675,47 @@ int tl3d_estimate_normals(tl3d_ctx *ctx, const float *xyz, int64_t n, int nb_nei
     return TL3D_OK;
 }
 
+// ------------------------------------------------------------------------------------------- planar regions of a cloud
+int tl3d_segment_planes(tl3d_ctx *ctx, const float *xyz, const float *normal, const float *curvature, int64_t n, const tl3d_plane_params *params,
+                        double cell_size, int32_t *plane_id_out, tl3d_plane *planes_out, int64_t plane_cap, int64_t *out_counts) {
+    REQUIRE(ctx && xyz && normal && params && plane_id_out && out_counts, TL3D_E_INVALID, "null argument");
+    REQUIRE(n >= 0 && n < (1ll << 31), TL3D_E_INVALID, "n %lld: indices need 0 <= n < 2^31", (long long)n);
+    REQUIRE(plane_cap >= 0 && (plane_cap == 0 || planes_out), TL3D_E_INVALID, "bad plane capacity");
+    REQUIRE(isfinite(params->radius) && params->radius > 0, TL3D_E_INVALID, "radius must be finite and positive");
+    REQUIRE(params->min_cos >= 0 && params->min_cos <= 1, TL3D_E_INVALID, "min_cos must be in [0,1]");
+    REQUIRE(params->max_offset >= 0, TL3D_E_INVALID, "max_offset must not be negative");
+    REQUIRE(params->min_points >= 3, TL3D_E_INVALID, "min_points must be at least 3");
+    REQUIRE(params->reserved == 0, TL3D_E_INVALID, "reserved must be 0");
+    REQUIRE(cell_size > 0, TL3D_E_INVALID, "cell_size must be positive");
+    const size_t nb_x = (size_t)n * 12, nb_c = (size_t)n * 4, nb_p = (size_t)plane_cap * sizeof(tl3d_plane);
+    const void *ins[3] = {xyz, normal, curvature};
+    const size_t in_b[3] = {nb_x, nb_x, nb_c};
+    for (int i = 0; i < 3; ++i)
+        REQUIRE(!ranges_overlap(plane_id_out, nb_c, ins[i], in_b[i]) && !ranges_overlap(planes_out, nb_p, ins[i], in_b[i]), TL3D_E_INVALID,
+                "an output aliases an input");
+    REQUIRE(!ranges_overlap(plane_id_out, nb_c, planes_out, nb_p), TL3D_E_INVALID, "the outputs alias each other");
+    if (n == 0) {
+        out_counts[0] = out_counts[1] = out_counts[2] = out_counts[3] = 0;
+        return TL3D_OK;
+    }
+    TL3D_HIP(hipSetDevice(ctx->device));
+    Staging st(ctx);
+    const float *dx, *dn, *dc = nullptr;
+    int32_t *did;
+    int rc = st.in(xyz, nb_x, &dx);
+    if (!rc) rc = st.in(normal, nb_x, &dn);
+    if (!rc && curvature) rc = st.in(curvature, nb_c, &dc);
+    if (!rc) rc = st.out(plane_id_out, nb_c, &did);
+    if (rc) return rc;
+    long long counts[4] = {0, 0, 0, 0};
+    bool short_cap = false;
+    rc = st.finish(planes_run(ctx, dx, dn, dc, n, *params, cell_size, did, planes_out, plane_cap, counts, &short_cap), true);
+    if (rc) return rc;
+    for (int i = 0; i < 4; ++i) out_counts[i] = counts[i];
+    if (short_cap) return set_err(TL3D_E_CAPACITY, "need %lld planes, capacity %lld", counts[3], (long long)plane_cap);
+    return TL3D_OK;
+}
+
 // ------------------------------------------------------------------------------------------- nearest neighbours, distance summary
 // what both searches check before any device work
 static int nn_check(tl3d_ctx *ctx, const float *query, int64_t n_query, const void *const *ins, const size_t *in_bytes, int n_ins,

@@ -701,6 +701,10 @@ int points_bounds_finite(tl3d_ctx *ctx, const float *xyz_dev, long long n, doubl
 int normals_run(tl3d_ctx *ctx, const float *xyz, long long n, int k, double max_radius, double cell, const double *vp_host, long long n_vp,
                 float *normal, float *curvature, long long *degenerate);
 
+// planar regions of a cloud (kernels_planes.hip); device pointers but planes_hd (host or device) and counts (host); curvature may be null
+int planes_run(tl3d_ctx *ctx, const float *xyz, const float *nrm, const float *curv, long long n, const tl3d_plane_params &prm, double cell,
+               int *plane_id, tl3d_plane *planes_hd, long long plane_cap, long long counts[4], bool *short_cap);
+
 // mesh smoothing and vertex normals (kernels_meshsmooth.hip)
 int launch_msm_validate(hipStream_t s, const float *xyz, long long n_vert, unsigned long long *info);
 int launch_msm_edges(hipStream_t s, const unsigned *tri, long long n_tri, unsigned long long *keys, unsigned long long slots, unsigned *deg,

@@ -513,6 +513,14 @@ def save_depth_like_processor(depth_m: np.ndarray, out_dir, frame_id: str):
 _HEADER_TAIL = ["property uchar red", "property uchar green", "property uchar blue", "end_header"]
 
 
+def _cloud_planes(n, planes):
+    """plane numbers i32 [n] of a cloud of n points as the writers take them (may be None)"""
+    if planes is not None:
+        planes = np.asarray(planes, dtype=np.int32).reshape(-1)
+        assert len(planes) == n, "one plane number per point"
+    return planes
+
+
 def _cloud_attributes(n, normals, curvature):
     """normals f32 [n,3] / curvature f32 [n] of a cloud of n points as the writers take them (either may be None)."""
     if normals is not None:
@@ -524,39 +532,44 @@ def _cloud_attributes(n, normals, curvature):
     return normals, curvature
 
 
-def write_ply_ascii(path, points, colors, normals=None, curvature=None):
+def write_ply_ascii(path, points, colors, normals=None, curvature=None, planes=None):
     """The reference's fallback writer byte for byte (D2R:689-701): `float` xyz printed with Python's str() of the
     numpy scalar, colours as integers.  normals (f32 [n,3]): the record becomes `x y z nx ny nz red green blue`, the order
-    Open3D and MeshLab read (write_ply_mesh's); curvature (f32 [n]): a `float curvature` last.  Without both: the reference's bytes."""
+    Open3D and MeshLab read (write_ply_mesh's); curvature (f32 [n]): a `float curvature` behind the colour; planes (i32 [n]): an `int plane` last.  Without
+    all three: the reference's bytes."""
     normals, curvature = _cloud_attributes(len(points), normals, curvature)
+    planes = _cloud_planes(len(points), planes)
     with open(path, "w") as f:
         f.write("ply\nformat ascii 1.0\n")
         f.write(f"element vertex {len(points)}\n")
         f.write("property float x\nproperty float y\nproperty float z\n")
         if normals is not None:
             f.write("property float nx\nproperty float ny\nproperty float nz\n")
-        f.write("\n".join(_HEADER_TAIL[:3] + (["property float curvature"] if curvature is not None else []) + _HEADER_TAIL[3:]) + "\n")
-        if normals is None and curvature is None:
+        f.write("\n".join(_HEADER_TAIL[:3] + (["property float curvature"] if curvature is not None else [])
+                          + (["property int plane"] if planes is not None else []) + _HEADER_TAIL[3:]) + "\n")
+        if normals is None and curvature is None and planes is None:
             for p, c in zip(points, colors):
                 f.write(f"{p[0]} {p[1]} {p[2]} {int(c[0])} {int(c[1])} {int(c[2])}\n")
             return
         for i, (p, c) in enumerate(zip(points, colors)):
             n = "" if normals is None else f"{normals[i, 0]} {normals[i, 1]} {normals[i, 2]} "
-            k = "" if curvature is None else f" {curvature[i]}"
+            k = ("" if curvature is None else f" {curvature[i]}") + ("" if planes is None else f" {int(planes[i])}")
             f.write(f"{p[0]} {p[1]} {p[2]} {n}{int(c[0])} {int(c[1])} {int(c[2])}{k}\n")
 
 
-def write_ply_binary(path, points, colors, double_xyz: bool = True, normals=None, curvature=None):
+def write_ply_binary(path, points, colors, double_xyz: bool = True, normals=None, curvature=None, planes=None):
     """binary_little_endian PLY, vertices only.  double_xyz=True is the layout Open3D's write_point_cloud emits for
     the reference (D2R:684-687: points are Vector3dVector, i.e. fp64) -- from Open3D's source as remembered, not
     verifiable in this image.  normals (f32 [n,3]): `nx ny nz` of the type of x y z between the position and the colour (the order
-    Open3D and MeshLab read); curvature (f32 [n]): a `float curvature` last.  Without both every byte is as ever."""
+    Open3D and MeshLab read); curvature (f32 [n]): a `float curvature` behind the colour; planes (i32 [n]): an `int plane` last.
+    Without all three every byte is as ever."""
     pts = np.asarray(points)
     col = np.asarray(colors, dtype=np.uint8)
     normals, curvature = _cloud_attributes(len(pts), normals, curvature)
     ft, fname = ("<f8", "double") if double_xyz else ("<f4", "float")
     nfields = [] if normals is None else [("nx", ft), ("ny", ft), ("nz", ft)]
-    cfields = [] if curvature is None else [("curvature", "<f4")]
+    planes = _cloud_planes(len(pts), planes)
+    cfields = ([] if curvature is None else [("curvature", "<f4")]) + ([] if planes is None else [("plane", "<i4")])
     rec = np.empty(len(pts), dtype=[("x", ft), ("y", ft), ("z", ft), *nfields, ("r", "u1"), ("g", "u1"), ("b", "u1"), *cfields])
     if len(pts):
         rec["x"], rec["y"], rec["z"] = pts[:, 0], pts[:, 1], pts[:, 2]
@@ -565,10 +578,12 @@ def write_ply_binary(path, points, colors, double_xyz: bool = True, normals=None
             rec["nx"], rec["ny"], rec["nz"] = normals[:, 0], normals[:, 1], normals[:, 2]
         if curvature is not None:
             rec["curvature"] = curvature
+        if planes is not None:
+            rec["plane"] = planes
     header = "\n".join(["ply", "format binary_little_endian 1.0", f"element vertex {len(pts)}",
                         f"property {fname} x", f"property {fname} y", f"property {fname} z"]
                        + [f"property {fname} {a}" for a, _ in nfields] + _HEADER_TAIL[:3]
-                       + ["property float curvature" for _ in cfields] + _HEADER_TAIL[3:]) + "\n"
+                       + [f"property {'int' if a == 'plane' else 'float'} {a}" for a, _ in cfields] + _HEADER_TAIL[3:]) + "\n"
     with open(path, "wb") as f:
         f.write(header.encode("ascii"))
         f.write(rec.tobytes())
@@ -619,9 +634,9 @@ def write_ply_mesh(path, xyz, rgb, tris, ascii: bool = False, normals=None):
         f.write(frec.tobytes())
 
 
-def save_reconstruction(points, colors, output_path, ascii: bool = False, normals=None, curvature=None) -> bool:
+def save_reconstruction(points, colors, output_path, ascii: bool = False, normals=None, curvature=None, planes=None) -> bool:
     """DepthToReconstructionPipeline.save_reconstruction (D2R:673-703): empty input prints `No points to save` and
-    writes nothing; parent directories are created; prints `Saved to <path>`.  normals / curvature: per-point attributes the
+    writes nothing; parent directories are created; prints `Saved to <path>`.  normals / curvature / planes: per-point attributes the
     writers add to the vertex record (write_ply_binary, write_ply_ascii); without them the file is the reference's."""
     if len(points) == 0:
         print("No points to save")
@@ -629,11 +644,25 @@ def save_reconstruction(points, colors, output_path, ascii: bool = False, normal
     filepath = Path(output_path)
     filepath.parent.mkdir(parents=True, exist_ok=True)
     if ascii:
-        write_ply_ascii(filepath, points, colors, normals=normals, curvature=curvature)
+        write_ply_ascii(filepath, points, colors, normals=normals, curvature=curvature, planes=planes)
     else:
-        write_ply_binary(filepath, points, colors, normals=normals, curvature=curvature)
+        write_ply_binary(filepath, points, colors, normals=normals, curvature=curvature, planes=planes)
     print(f"Saved to {filepath}")
     return True
+
+
+def write_plane_report(path, planes) -> None:
+    """The plane table of a segmented cloud (DepthToReconstructionPipeline.cloud_planes) as JSON: {"planes": [{normal, d, centroid,
+    rms, count}, ..]} in the planes' numbering; parent directories are created."""
+    import json
+    filepath = Path(path)
+    filepath.parent.mkdir(parents=True, exist_ok=True)
+    rows = [dict(normal=[float(v) for v in p["normal"]], d=float(p["d"]), centroid=[float(v) for v in p["centroid"]], rms=float(p["rms"]),
+                 count=int(p["count"])) for p in (planes if planes is not None else [])]
+    with open(filepath, "w") as f:
+        json.dump(dict(planes=rows), f, indent=1)
+        f.write("\n")
+    print(f"Saved {len(rows)} planes to {filepath}")
 
 
 _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",

@@ -6,6 +6,7 @@ every method is one call into libtl3d.so.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -952,6 +953,45 @@ class FusionContext:
                                                       abi.ptr(normals), abi.ptr(curv) if curvature else None, C.byref(deg)))
         self.last_normals_degenerate = int(deg.value)
         return (normals, curv) if curvature else normals
+
+    def segment_planes(self, xyz, normals, curvature=None, radius=None, max_angle_deg=10.0, max_offset=None, max_curvature=0.0,
+                       min_points=200, max_rms=0.0, signed_normals=True, cell_size=None):
+        """(plane_id int32 [n], planes, counts): the planar regions of a cloud with normals.  Points with a
+        usable normal (and, with a curvature array and max_curvature > 0, curvature <= max_curvature) are linked when they lie
+        within radius, their normals within max_angle_deg (of parallel or anti-parallel with signed_normals=False) and each within
+        max_offset of the other's tangent plane; a connected region of at least min_points points whose fitted plane has
+        rms <= max_rms (max_rms <= 0: any) is a plane.  plane_id is the number of a point's plane or -1; planes is a numpy record
+        array (normal, d, centroid, rms, count, seed) in ascending seed; counts = dict(eligible, regions, candidates, planes).
+        radius / max_offset default to 2.5 / 1 voxel of the attached grid (0.025 / 0.01 m without one).  cell_size sets the search
+        grid only (default: radius); the result does not depend on it.  numpy in, numpy plane_id out; torch device tensors in, a
+        device plane_id out."""
+        xyz, normals = self._points(xyz), self._points(normals)
+        n = len(xyz)
+        assert len(normals) == n, f"{len(normals)} normals for {n} points"
+        voxel = self.grid.voxel_size if self.grid else 0.01
+        radius = float(radius) if radius is not None else 2.5 * voxel
+        max_offset = float(max_offset) if max_offset is not None else voxel
+        if hasattr(xyz, "data_ptr"):
+            import torch
+            plane_id = torch.empty((n,), dtype=torch.int32, device=xyz.device)
+            if curvature is not None:
+                curvature = curvature.to(dtype=torch.float32).reshape(-1).contiguous()
+        else:
+            plane_id = np.empty((n,), np.int32)
+            if curvature is not None:
+                curvature = np.ascontiguousarray(curvature, dtype=np.float32).reshape(-1)
+        assert curvature is None or len(curvature) == n, f"{len(curvature)} curvatures for {n} points"
+        prm = abi.PlaneParams(radius=radius, min_cos=math.cos(math.radians(float(max_angle_deg))), max_offset=max_offset,
+                              max_curvature=float(max_curvature), max_rms=float(max_rms), min_points=int(min_points),
+                              signed_normals=1 if signed_normals else 0, reserved=0)
+        cell = float(cell_size) if cell_size is not None else radius
+        cnt = (C.c_int64 * 4)()
+        cap = n // max(int(min_points), 1)                      # every candidate has min_points points of its own
+        planes = np.zeros((cap,), abi.PLANE_DTYPE)
+        abi.check(self._lib.tl3d_segment_planes(self._h, abi.ptr(xyz), abi.ptr(normals), abi.ptr(curvature), n, C.byref(prm), cell,
+                                                abi.ptr(plane_id), abi.ptr(planes) if cap else None, cap, cnt))
+        counts = dict(eligible=int(cnt[0]), regions=int(cnt[1]), candidates=int(cnt[2]), planes=int(cnt[3]))
+        return plane_id, planes[:counts["planes"]].copy(), counts
 
     # ---- distances between sets (DESIGN.md section 4.4; none of it needs a grid) -----------
     @staticmethod

@@ -140,6 +140,33 @@ def per_frame_scales(depths, anchors, default: float = 1.0, fetch=None):
     return tr.history[:n]
 
 
+def check_cloud_options(cfg):
+    """config.cloud_planes: what reconstruct() refuses before any work"""
+    if not bool(getattr(cfg, "cloud_planes", False)):
+        return
+    if not bool(getattr(cfg, "cloud_normals", False)):
+        raise ValueError("cloud_planes segments the cloud by its normals: it needs cloud_normals = True")
+    for name in ("cloud_planes_radius", "cloud_planes_offset", "cloud_planes_max_curvature", "cloud_planes_max_rms"):
+        v = float(getattr(cfg, name))
+        if not np.isfinite(v) or v < 0.0:
+            raise ValueError(f"{name} = {v}: must be finite and not negative (0: the default)")
+    angle = float(cfg.cloud_planes_angle_deg)
+    if not 0.0 <= angle <= 90.0:                        # (false for NaN)
+        raise ValueError(f"cloud_planes_angle_deg = {angle}: must lie in [0, 90]")
+    m = cfg.cloud_planes_min_points
+    if isinstance(m, bool) or int(m) != m or int(m) < 3:
+        raise ValueError(f"cloud_planes_min_points = {m}: must be a whole number, 3 at the least")
+
+
+def cloud_plane_parameters(cfg, voxel_size=None) -> dict:
+    """config.cloud_planes_* as FusionContext.segment_planes takes them, lengths in metres: a length of 0 is 2.5 voxels for the
+    radius, 1 voxel for the offset and 0.5 voxel for the rms"""
+    voxel = float(cfg.voxel_size if voxel_size is None else voxel_size)
+    return dict(radius=float(cfg.cloud_planes_radius) or 2.5 * voxel, max_angle_deg=float(cfg.cloud_planes_angle_deg),
+                max_offset=float(cfg.cloud_planes_offset) or voxel, max_curvature=float(cfg.cloud_planes_max_curvature),
+                min_points=int(cfg.cloud_planes_min_points), max_rms=float(cfg.cloud_planes_max_rms) or 0.5 * voxel)
+
+
 class DepthToReconstructionPipeline:
     def __init__(self, config: ReconstructionConfig = None):
         self.config = config or ReconstructionConfig()
@@ -159,6 +186,9 @@ class DepthToReconstructionPipeline:
         self.mesh = None                          # (xyz f32 [V,3], rgb u8 [V,3], tris u32 [T,3]) of the last reconstruct(), config.extract_mesh
         self.cloud_normals = None                 # f32 [N,3] of the returned points when config.cloud_normals, else None
         self.cloud_curvature = None               # f32 [N] of the returned points when config.cloud_curvature, else None
+        self.cloud_plane_ids = None               # i32 [N] of the returned points when config.cloud_planes: a plane's number or -1
+        self.cloud_planes = None                  # the planes' records (normal, d, centroid, rms, count, seed) when config.cloud_planes
+        self._plane_curvature = None              # the curvature on its way from the normals to the planes, between the two calls only
 
     # ---- a2 --------------------------------------------------------------------------------------
     def load_data(self, rgb_folder: str, depth_folder: str) -> int:
@@ -464,7 +494,7 @@ class DepthToReconstructionPipeline:
         """
         self.mesh = None
         self.mesh_normals = None
-        self.cloud_normals = self.cloud_curvature = None
+        self.cloud_normals = self.cloud_curvature = self.cloud_plane_ids = self.cloud_planes = self._plane_curvature = None
         cfg = self.config
         self._check_mesh_filter_config()
         self._check_mesh_weld_config()
@@ -598,11 +628,29 @@ class DepthToReconstructionPipeline:
         k, radius = int(cfg.cloud_normals_neighbors), float(cfg.cloud_normals_radius)
         centres = np.array([-np.asarray(R, np.float64).T @ np.asarray(t, np.float64).reshape(3) for R, t in self.camera_poses],
                            np.float64).reshape(-1, 3)
+        planes = bool(getattr(cfg, "cloud_planes", False))         # the segmentation wants the curvature, asked for or not
         out = ctx.estimate_normals(xyz, k, max_radius=radius, viewpoints=centres, cell_size=2.0 * voxel_size,
-                                   curvature=bool(cfg.cloud_curvature))
-        self.cloud_normals, self.cloud_curvature = out if cfg.cloud_curvature else (out, None)
+                                   curvature=bool(cfg.cloud_curvature) or planes)
+        self.cloud_normals, curvature = out if (cfg.cloud_curvature or planes) else (out, None)
+        self.cloud_curvature = curvature if cfg.cloud_curvature else None
         self.stats["cloud_normals"] = dict(neighbors=k, radius=radius, viewpoints=len(centres), degenerate=ctx.last_normals_degenerate)
         print(f"  Cloud normals: {len(xyz)} points, {k} neighbours, {len(centres)} viewpoints, {ctx.last_normals_degenerate} degenerate")
+        self._plane_curvature = curvature if planes else None
+        return time.perf_counter() - t0
+
+    def _segment_cloud_planes(self, ctx: FusionContext, xyz, voxel_size) -> float:
+        """config.cloud_planes: the planar regions of the cleaned cloud from its normals and curvature; once
+        over the whole cloud, right behind _estimate_cloud_normals.  Leaves cloud_plane_ids (rows match xyz), cloud_planes and
+        stats["cloud_planes"]; returns the seconds it took."""
+        t0 = time.perf_counter()
+        prm = cloud_plane_parameters(self.config, voxel_size)
+        ids, planes, counts = ctx.segment_planes(xyz, self.cloud_normals, self._plane_curvature, **prm)
+        self._plane_curvature = None
+        self.cloud_plane_ids, self.cloud_planes = ids, planes
+        largest = np.argsort(-planes["count"], kind="stable")[:10]
+        self.stats["cloud_planes"] = dict(**counts, **prm, largest=[dict(count=int(planes["count"][k]), rms=float(planes["rms"][k])) for k in largest])
+        print(f"  Cloud planes: {counts['planes']} planes hold {int((ids >= 0).sum())} of {len(xyz)} points "
+              f"({counts['eligible']} eligible, {counts['regions']} regions, {counts['candidates']} of {prm['min_points']} points or more)")
         return time.perf_counter() - t0
 
     def _fuse_blocks(self, ctx: FusionContext, lattice: GridSpec, blocks: List[Block], marks=None, layout_given: bool = False):
@@ -690,6 +738,8 @@ class DepthToReconstructionPipeline:
                           sparse=any(g.sparse for g in done), **sums, blocks=len(done))
         if cfg.cloud_normals:
             stage["cloud_normals"] = self._estimate_cloud_normals(ctx, xyz, lattice.voxel_size)
+        if getattr(cfg, "cloud_planes", False):
+            stage["cloud_planes"] = self._segment_cloud_planes(ctx, xyz, lattice.voxel_size)
         if one and done[0].sparse:
             print(f"  Sparse volume: {sums['bricks_tsdf']} TSDF bricks and {sums['bricks_centroid']} centroid bricks hold records "
                   f"(of {done[0].nvox // 512}); {done[0].device_bytes() / 2**30:.2f} GiB")
@@ -791,7 +841,7 @@ class DepthToReconstructionPipeline:
         world, rank = dist.get_world_size(), dist.get_rank()
         self.mesh = None
         self.mesh_normals = None
-        self.cloud_normals = self.cloud_curvature = None
+        self.cloud_normals = self.cloud_curvature = self.cloud_plane_ids = self.cloud_planes = self._plane_curvature = None
         if len(self.images) < 2:
             print("Need at least 2 images")
             return None, None, None
@@ -914,6 +964,8 @@ class DepthToReconstructionPipeline:
                 self.stats = dict(points_accumulated=tot[0], points_dropped=tot[1], **counts)
                 if cfg.cloud_normals:
                     self.timings["cloud_normals_s"] = round(self._estimate_cloud_normals(ctx, xyz, grid.voxel_size), 4)
+                if getattr(cfg, "cloud_planes", False):
+                    self.timings["cloud_planes_s"] = round(self._segment_cloud_planes(ctx, xyz, grid.voxel_size), 4)
                 if cfg.extract_mesh:
                     t0 = time.perf_counter()
                     self.mesh = self._extract_mesh(ctx)
@@ -1007,6 +1059,7 @@ class DepthToReconstructionPipeline:
 
     def _check_cloud_normals_config(self):
         cfg = self.config
+        check_cloud_options(cfg)
         on = bool(getattr(cfg, "cloud_normals", False))
         if bool(getattr(cfg, "cloud_curvature", False)) and not on:
             raise ValueError("cloud_curvature comes out of the normal estimation: it needs cloud_normals = True")
@@ -1103,5 +1156,5 @@ class DepthToReconstructionPipeline:
         fileio.write_ply_mesh(path, *self.mesh, ascii=ascii, normals=self.mesh_normals)
         print(f"Saved mesh to {path}")
 
-    def save_reconstruction(self, points, colors, output_path: str, ascii: bool = False, normals=None, curvature=None):
-        fileio.save_reconstruction(points, colors, output_path, ascii=ascii, normals=normals, curvature=curvature)
+    def save_reconstruction(self, points, colors, output_path: str, ascii: bool = False, normals=None, curvature=None, planes=None):
+        fileio.save_reconstruction(points, colors, output_path, ascii=ascii, normals=normals, curvature=curvature, planes=planes)
