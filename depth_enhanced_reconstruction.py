@@ -69,6 +69,17 @@ def main(argv=None):
                         help="points with a surface variation above this take no part (creases; 0: no bound; default 0.05)")
     parser.add_argument("--cloud-planes-report", default=None, metavar="FILE.json",
                         help="with --cloud-planes: write the plane table (normal, d, centroid, rms, count) as JSON")
+    parser.add_argument("--depth-filter", action="store_true",
+                        help="drop flying pixels and small regions from every depth frame on the GPU before anything reads it "
+                             "(registration, tracking, fusion); pixels are only ever invalidated, never altered")
+    parser.add_argument("--depth-filter-jump", type=float, default=0.05, metavar="REL",
+                        help="two pixels are linked when their depths differ by at most REL times the smaller one (default 0.05)")
+    parser.add_argument("--depth-filter-radius", type=int, default=1, metavar="R",
+                        help="the support window is (2R+1)^2 pixels (1..3; default 1)")
+    parser.add_argument("--depth-filter-min-support", type=int, default=4, metavar="N",
+                        help="a pixel with fewer than N linked pixels in its window goes (0..(2R+1)^2-1; default 4)")
+    parser.add_argument("--depth-filter-min-region", type=int, default=0, metavar="N",
+                        help="a 4-connected region of linked pixels smaller than N goes too (default 0: no such stage)")
     parser.add_argument("--device", type=int, default=0)
     args = parser.parse_args(argv)
 
@@ -80,6 +91,15 @@ def main(argv=None):
         parser.error("--cloud-planes segments the cloud by its normals: it needs --cloud-normals (and --cloud-planes-report needs --cloud-planes)")
     if args.cloud_planes_min_points < 3:
         parser.error("--cloud-planes-min-points must be 3 at the least")
+    if args.depth_filter:
+        from tl3d.pipeline import check_depth_filter_options
+        try:
+            check_depth_filter_options(argparse.Namespace(depth_filter=True, depth_filter_jump=args.depth_filter_jump,
+                                                          depth_filter_radius=args.depth_filter_radius,
+                                                          depth_filter_min_support=args.depth_filter_min_support,
+                                                          depth_filter_min_region=args.depth_filter_min_region))
+        except ValueError as e:
+            parser.error("--depth-filter: " + str(e))
     if args.compare_threshold and len(args.compare_threshold) > 8:
         parser.error("--compare-threshold: at most 8 thresholds")
     from tl3d import fileio
@@ -98,6 +118,9 @@ def main(argv=None):
     config = ReconstructionConfig(fx=args.fx, fy=args.fy, cx=args.cx, cy=args.cy, min_depth=0.1, max_depth=100.0,
                                   voxel_size=0.005, subsample_factor=4, grid_dim=args.grid, device=args.device,
                                   depth_scale=args.depth_scale, loop_closure=args.loop_closure, model_tracking=args.model_tracking,
+                                  depth_filter=args.depth_filter, depth_filter_jump=args.depth_filter_jump,
+                                  depth_filter_radius=args.depth_filter_radius, depth_filter_min_support=args.depth_filter_min_support,
+                                  depth_filter_min_region=args.depth_filter_min_region,
                                   cloud_planes=args.cloud_planes, cloud_planes_angle_deg=args.cloud_planes_angle,
                                   cloud_planes_min_points=args.cloud_planes_min_points, cloud_planes_max_curvature=args.cloud_planes_max_curvature,
                                   cloud_normals=args.cloud_normals, cloud_normals_neighbors=args.cloud_normals_neighbors,

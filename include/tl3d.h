@@ -195,6 +195,47 @@ int tl3d_pinned_free(void *p);
 int tl3d_upload_frame_async(tl3d_ctx *ctx, int slot, const void *depth_hd, int depth_kind, const uint8_t *bgr_hd);
 int tl3d_slot_wait(tl3d_ctx *ctx, int slot);
 
+/* Depth-frame filter: flying pixels and small regions (no reference code: the reference fuses its depth maps as
+ * they come -- the rules are ours, the question librealsense's and Open3D's depth clean-ups answer).  The filter only ever
+ * INVALIDATES pixels (writes 0); it never smooths or alters a value, and its result is an exact function of the image.
+ * The image is one depth image of the context's W x H, f32 or u16 millimetres.  All arithmetic is f32, on the f32 pixel itself or on
+ * the u16 value converted exactly to f32 -- never on the metres copy -- so the array call and the slot call agree bit for bit.
+ * valid p: d_p is finite and d_p > 0.  An invalid pixel is never changed, whatever its bytes are (NaN payloads, -0, inf, negatives).
+ * linked p, q: both valid and fabsf(d_q - d_p) <= jump * fminf(d_p, d_q), jump = jump_rel rounded once to f32: one rounded
+ * subtraction, one rounded product, one compare; nothing to contract, no fast math.  The test is relative: the depth scale and the
+ * choice of mm or m do not matter, and relative (unscaled) depth can be filtered.
+ * Stage A, flying pixels: S_p = the number of pixels q != p of the (2 radius + 1)^2 window, inside the image, linked to p on the
+ * INPUT image; a valid p with S_p < min_support becomes 0.  Pixels outside the image support nobody.
+ * Stage B, small regions, on stage A's result (min_region > 1): horizontally or vertically adjacent survivors are joined when
+ * linked; the regions are the transitive closure of the joins (a~b and b~c make one region even when a and c are not linked); a
+ * survivor whose region has fewer than min_region pixels becomes 0.
+ * counts, per image: {valid in, removed by A, regions after A, removed by B}; regions is 0 when stage B is off.
+ * Parameters: jump_rel > 0 and finite (default 0.05), radius 1..3 (1), min_support 0..(2 radius + 1)^2 - 1 (4), min_region >= 0
+ * (0; 0 or 1: stage B off), reserved 0.
+ * tl3d_filter_depth: a pure function of one image; depth_in / depth_out are host or device pointers of depth_kind (the output has
+ * the kind of the input), counts_out [4] is host memory; depth_out == depth_in is allowed, any other overlap is refused; needs no
+ * grid and touches no slot.
+ * tl3d_filter_depth_slots: filters the resident frames slots[0..n) in place, each as a new upload of the slot would be ordered
+ * (behind the deferred TSDF updates and every uncollected ICP run that reads the slot) and with what a new upload voids: the normal
+ * map, the averaged depth, the TSDF tile and classification caches.  A u16 slot is filtered on its millimetres, and both the
+ * millimetres and the f32 copy are zeroed; colour is untouched.  counts_out [n][4] (host) may be NULL.  n == 0 is TL3D_OK; a slot
+ * that holds no frame is TL3D_E_STATE.
+ * TL3D_E_INVALID before any device work, with nothing written: a null argument, a bad depth_kind, a parameter outside its range,
+ * reserved != 0, n < 0, a slot out of range or named twice, overlapping images.
+ * Tests (tests/test_gpu_depth_filter*.py): output bits and counts equal two numpy formulations on crafted images (tile seams,
+ * link decisions one f32 ulp apart, union-find topologies, invalid bit patterns); stale slot state; the pipeline option. */
+typedef struct tl3d_depth_filter_params {
+    double jump_rel;
+    int32_t radius;
+    int32_t min_support;
+    int64_t min_region;
+    int32_t reserved;
+} tl3d_depth_filter_params;
+int tl3d_filter_depth(tl3d_ctx *ctx, const void *depth_in_hd, int depth_kind, const tl3d_depth_filter_params *params,
+                      void *depth_out_hd, int64_t *counts_out /* [4] */);
+int tl3d_filter_depth_slots(tl3d_ctx *ctx, int n, const int32_t *slots, const tl3d_depth_filter_params *params,
+                            int64_t *counts_out /* [n][4] or NULL */);
+
 /* a3+a4/a5: DenseReconstructor.depth_to_pointcloud (depth_to_reconstruction.py:328-384) and
  * DensePointCloudGenerator.depth_to_pointcloud (depth_enhanced_reconstruction.py:554-613).
  * Writes the surviving points in row-major pixel order.  cap = capacity in points; on

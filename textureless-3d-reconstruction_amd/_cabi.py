@@ -23,7 +23,7 @@ TSDF_MAX_WEIGHT = 65536
 SYMBOLS = [
     "tl3d_last_error", "tl3d_version", "tl3d_device_count", "tl3d_runtime_info", "tl3d_probe_hw_queues", "tl3d_grid_max_weight", "tl3d_create", "tl3d_destroy", "tl3d_sync", "tl3d_get_stream", "tl3d_release_cached_memory",
     "tl3d_upload_frame", "tl3d_download_depth", "tl3d_pinned_alloc", "tl3d_pinned_free", "tl3d_upload_frame_async",
-    "tl3d_slot_wait", "tl3d_attach_grid", "tl3d_detach_grid", "tl3d_set_block_core", "tl3d_backproject", "tl3d_backproject_device", "tl3d_frame_bounds", "tl3d_frames_bounds", "tl3d_count_bricks", "tl3d_accumulate_centroid",
+    "tl3d_slot_wait", "tl3d_filter_depth", "tl3d_filter_depth_slots", "tl3d_attach_grid", "tl3d_detach_grid", "tl3d_set_block_core", "tl3d_backproject", "tl3d_backproject_device", "tl3d_frame_bounds", "tl3d_frames_bounds", "tl3d_count_bricks", "tl3d_accumulate_centroid",
     "tl3d_accumulate_points", "tl3d_points_bounds", "tl3d_integrate", "tl3d_build_normals",
     "tl3d_download_normals", "tl3d_icp_p2plane", "tl3d_icp_enqueue", "tl3d_icp_collect", "tl3d_icp_batch_enqueue", "tl3d_icp_batch_collect", "tl3d_icp_evaluate_pairs", "tl3d_host_pack_bgr_rows", "tl3d_host_copy_rows", "tl3d_build_normals_many", "tl3d_fuse_frames", "tl3d_grid_reset", "tl3d_grid_device_ptr",
     "tl3d_grid_download", "tl3d_grid_upload", "tl3d_grid_add", "tl3d_grid_touched_bricks", "tl3d_grid_pack_bricks", "tl3d_grid_unpack_bricks", "tl3d_rccl_unique_id", "tl3d_rccl_init", "tl3d_allreduce_grid", "tl3d_extract", "tl3d_extract_mesh", "tl3d_extract_mesh_keyed", "tl3d_mesh_components", "tl3d_mesh_filter_components", "tl3d_mesh_simplify_clusters", "tl3d_mesh_simplify_quadric", "tl3d_mesh_smooth_taubin", "tl3d_mesh_vertex_normals", "tl3d_mesh_weld_keyed", "tl3d_raycast", "tl3d_track_evaluate", "tl3d_track_frame", "tl3d_statistical_outlier", "tl3d_knn_mean_distance", "tl3d_estimate_normals", "tl3d_segment_planes",
@@ -77,6 +77,11 @@ class MeshPart(C.Structure):
 class DistanceStats(C.Structure):
     _fields_ = [("n", C.c_int64), ("n_finite", C.c_int64), ("sum", C.c_double), ("sum_sq", C.c_double), ("max", C.c_double),
                 ("below", C.c_int64 * 8)]
+
+
+class DepthFilterParams(C.Structure):
+    _fields_ = [("jump_rel", C.c_double), ("radius", C.c_int32), ("min_support", C.c_int32), ("min_region", C.c_int64),
+                ("reserved", C.c_int32)]
 
 
 class PlaneParams(C.Structure):
@@ -198,6 +203,8 @@ def load():
         "tl3d_pinned_free": [vp],
         "tl3d_upload_frame_async": [vp, i32, vp, i32, vp],
         "tl3d_slot_wait": [vp, i32],
+        "tl3d_filter_depth": [vp, vp, i32, C.POINTER(DepthFilterParams), vp, C.POINTER(i64)],
+        "tl3d_filter_depth_slots": [vp, i32, vp, C.POINTER(DepthFilterParams), vp],
         "tl3d_attach_grid": [vp, C.POINTER(Config)],
         "tl3d_detach_grid": [vp],
         "tl3d_set_block_core": [vp, vp, vp, vp],

@@ -123,6 +123,17 @@ class ReconstructionConfig:
     cloud_planes_max_curvature: float = 0.05
     cloud_planes_min_points: int = 200
     cloud_planes_max_rms: float = 0.0
+    # depth-frame filter: once over all resident frames, behind the upload and the per-frame scales and in
+    # front of the registration, so everything downstream reads the filtered frames.  Two valid pixels (finite, > 0) are linked when
+    # their depths differ by at most depth_filter_jump times the smaller one; a pixel with fewer than depth_filter_min_support
+    # linked pixels in its (2 depth_filter_radius + 1)^2 window is set to 0 (flying pixels), then every 4-connected region of
+    # linked survivors smaller than depth_filter_min_region (0: no such stage).  Pixels are only invalidated, never altered.
+    # stats["depth_filter"].  Not on a sharded run.  Off: nothing changes.
+    depth_filter: bool = False
+    depth_filter_jump: float = 0.05
+    depth_filter_radius: int = 1
+    depth_filter_min_support: int = 4
+    depth_filter_min_region: int = 0
 
     @property
     def K(self) -> np.ndarray:

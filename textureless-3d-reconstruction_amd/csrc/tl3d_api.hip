@@ -872,6 +872,81 @@ int tl3d_download_depth(tl3d_ctx *ctx, int slot, float *out) {
     return TL3D_OK;
 }
 
+// ------------------------------------------------------------------------------------------- depth-frame filter (kernels_depthfilter.hip)
+// what both calls check before any device work
+static int depth_filter_check(const tl3d_depth_filter_params *p) {
+    REQUIRE(isfinite(p->jump_rel) && p->jump_rel > 0, TL3D_E_INVALID, "jump_rel must be finite and positive");
+    REQUIRE(p->radius >= 1 && p->radius <= 3, TL3D_E_INVALID, "radius %d outside [1,3]", p->radius);
+    const int window = (2 * p->radius + 1) * (2 * p->radius + 1);
+    REQUIRE(p->min_support >= 0 && p->min_support <= window - 1, TL3D_E_INVALID, "min_support %d outside [0,%d]", p->min_support, window - 1);
+    REQUIRE(p->min_region >= 0, TL3D_E_INVALID, "min_region must not be negative");
+    REQUIRE(p->reserved == 0, TL3D_E_INVALID, "reserved must be 0");
+    return TL3D_OK;
+}
+
+int tl3d_filter_depth(tl3d_ctx *ctx, const void *depth_in, int depth_kind, const tl3d_depth_filter_params *params, void *depth_out,
+                      int64_t *counts_out) {
+    REQUIRE(ctx && depth_in && params && depth_out && counts_out, TL3D_E_INVALID, "null argument");
+    REQUIRE(depth_kind == TL3D_DEPTH_F32_M || depth_kind == TL3D_DEPTH_U16_MM, TL3D_E_INVALID, "bad depth_kind %d", depth_kind);
+    int rc = depth_filter_check(params);
+    if (rc) return rc;
+    const size_t bytes = (size_t)ctx->cam.W * ctx->cam.H * (depth_kind == TL3D_DEPTH_U16_MM ? sizeof(uint16_t) : sizeof(float));
+    REQUIRE(depth_out == depth_in || !ranges_overlap(depth_out, bytes, depth_in, bytes), TL3D_E_INVALID, "the output overlaps the input");
+    REQUIRE(!ranges_overlap(counts_out, 4 * sizeof(int64_t), depth_in, bytes) && !ranges_overlap(counts_out, 4 * sizeof(int64_t), depth_out, bytes),
+            TL3D_E_INVALID, "the counts overlap an image");
+    TL3D_HIP(hipSetDevice(ctx->device));
+    Staging st(ctx);
+    char *dout = nullptr;
+    rc = st.out((char *)depth_out, bytes, &dout);
+    if (rc) return rc;
+    // the kernels work in place on the output: it starts as the input's bytes (invalid pixels keep theirs)
+    if ((const void *)dout != depth_in) TL3D_HIP(hipMemcpyAsync(dout, depth_in, bytes, hipMemcpyDefault, ctx->stream));
+    void *img = dout;
+    long long counts[4] = {0, 0, 0, 0};
+    rc = st.finish(depth_filter_run(ctx, 1, &img, nullptr, &depth_kind, *params, counts), true);
+    if (rc) return rc;
+    for (int i = 0; i < 4; ++i) counts_out[i] = counts[i];
+    return TL3D_OK;
+}
+
+int tl3d_filter_depth_slots(tl3d_ctx *ctx, int n, const int32_t *slots, const tl3d_depth_filter_params *params, int64_t *counts_out) {
+    REQUIRE(ctx && params && n >= 0 && (slots || n == 0), TL3D_E_INVALID, "null argument or negative n");
+    int rc = depth_filter_check(params);
+    if (rc) return rc;
+    for (int i = 0; i < n; ++i) {
+        REQUIRE(slots[i] >= 0 && slots[i] < ctx->cfg.n_slots, TL3D_E_INVALID, "slot %d out of range [0,%d)", slots[i], ctx->cfg.n_slots);
+        for (int j = 0; j < i; ++j) REQUIRE(slots[j] != slots[i], TL3D_E_INVALID, "slot %d named twice", slots[i]);
+    }
+    for (int i = 0; i < n; ++i) REQUIRE(ctx->slots[slots[i]].loaded, TL3D_E_STATE, "slot %d holds no frame", slots[i]);
+    if (n == 0) return TL3D_OK;
+    // each slot as upload_impl treats a rewrite: behind the deferred updates and the lanes that read it, the kernels on the main
+    // stream, then slot_rewritten (normal map, averaged depth, tile and class caches void; ev_upload recorded)
+    FLUSH_UPDATES(ctx);
+    TL3D_HIP(hipSetDevice(ctx->device));
+    std::vector<void *> img(n);
+    std::vector<float *> f32(n);
+    std::vector<int> kinds(n);
+    std::vector<long long> counts(counts_out ? (size_t)n * 4 : 0);
+    for (int i = 0; i < n; ++i) {
+        rc = order_after_lanes(ctx, slots[i], true, true);
+        if (rc) return rc;
+        Slot &s = ctx->slots[slots[i]];
+        kinds[i] = s.has_u16 ? TL3D_DEPTH_U16_MM : TL3D_DEPTH_F32_M;
+        img[i] = s.has_u16 ? (void *)s.depth_u16 : (void *)s.depth;
+        f32[i] = s.has_u16 ? s.depth : nullptr;
+    }
+    rc = depth_filter_run(ctx, n, img.data(), f32.data(), kinds.data(), *params, counts_out ? counts.data() : nullptr);
+    // (after a failed launch too: some of the slots may have been written)
+    for (int i = 0; i < n; ++i) {
+        Slot &s = ctx->slots[slots[i]];
+        const int rrc = slot_rewritten(ctx, s, s.has_u16, s.has_color);
+        if (!rc) rc = rrc;
+    }
+    if (rc) return rc;
+    for (size_t i = 0; i < counts.size(); ++i) counts_out[i] = counts[i];
+    return TL3D_OK;
+}
+
 // ------------------------------------------------------------------------------------------- back-projection
 extern "C++" int tl3d::make_bp_args(tl3d_ctx *ctx, double scale, uint32_t flags, int subsample, double min_d, double max_d, BpArgs *a) {
     REQUIRE(subsample >= 1, TL3D_E_INVALID, "subsample must be >= 1");

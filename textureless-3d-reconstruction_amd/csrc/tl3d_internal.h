@@ -705,6 +705,12 @@ int normals_run(tl3d_ctx *ctx, const float *xyz, long long n, int k, double max_
 int planes_run(tl3d_ctx *ctx, const float *xyz, const float *nrm, const float *curv, long long n, const tl3d_plane_params &prm, double cell,
                int *plane_id, tl3d_plane *planes_hd, long long plane_cap, long long counts[4], bool *short_cap);
 
+// depth-image filter (kernels_depthfilter.hip): n images of the context's W x H, filtered in place on its stream; device pointers but
+// counts (host, [n][4], may be null: then the call does not wait); f32[i] is a u16 image's f32 copy to zero with it, or null
+constexpr int DF_MAXBATCH = 16;      // frames that may share a launch (blockIdx.z)
+int depth_filter_run(tl3d_ctx *ctx, int n, void *const *img, float *const *f32, const int *kinds, const tl3d_depth_filter_params &prm,
+                     long long *counts);
+
 // mesh smoothing and vertex normals (kernels_meshsmooth.hip)
 int launch_msm_validate(hipStream_t s, const float *xyz, long long n_vert, unsigned long long *info);
 int launch_msm_edges(hipStream_t s, const unsigned *tri, long long n_tri, unsigned long long *keys, unsigned long long slots, unsigned *deg,

@@ -351,6 +351,55 @@ class FusionContext:
         abi.check(self._lib.tl3d_download_depth(self._h, int(slot), abi.ptr(out)))
         return out
 
+    # ---- depth-frame filter (needs no grid) ---------------------------
+    DEPTH_FILTER_COUNTS = ("valid", "removed_flying", "regions", "removed_regions")
+
+    @staticmethod
+    def _depth_filter_params(jump_rel, radius, min_support, min_region) -> "abi.DepthFilterParams":
+        return abi.DepthFilterParams(jump_rel=float(jump_rel), radius=int(radius), min_support=int(min_support),
+                                     min_region=int(min_region), reserved=0)
+
+    def filter_depth(self, depth, jump_rel=0.05, radius=1, min_support=4, min_region=0, out=None):
+        """(filtered, counts): one depth image [H,W] (numpy or torch, host or device; float32, or uint16 millimetres) with its
+        flying pixels and small regions set to 0; every other pixel, an invalid one too, keeps its bits.  A valid pixel (finite,
+        > 0) is linked to a valid neighbour when |d_q - d_p| <= jump_rel * min(d_p, d_q) in f32; it goes when fewer than
+        min_support pixels of its (2 radius + 1)^2 window are linked to it, and then when its 4-connected region of linked
+        survivors has fewer than min_region pixels (0 or 1: no such stage).  counts = dict(valid, removed_flying, regions,
+        removed_regions).  out: an array like depth to write into (depth itself filters in place); default a new one."""
+        if isinstance(depth, np.ndarray):
+            if depth.dtype != np.uint16:
+                depth = np.ascontiguousarray(depth, dtype=np.float32)
+            depth = np.ascontiguousarray(depth)
+            kind = abi.DEPTH_U16_MM if depth.dtype == np.uint16 else abi.DEPTH_F32_M
+            if out is None:
+                out = np.empty_like(depth)
+        else:
+            import torch
+            kind = abi.DEPTH_U16_MM if depth.dtype in (torch.uint16, torch.int16) else abi.DEPTH_F32_M
+            if kind == abi.DEPTH_F32_M and depth.dtype != torch.float32:
+                depth = depth.to(torch.float32)
+            depth = depth.contiguous()
+            if out is None:
+                out = torch.empty_like(depth)
+        assert tuple(depth.shape) == (self.height, self.width), f"depth {tuple(depth.shape)} != {(self.height, self.width)}"
+        def item(a):
+            return a.itemsize if isinstance(a, np.ndarray) else a.element_size()
+        assert tuple(out.shape) == tuple(depth.shape) and item(out) == item(depth), "out must match depth in shape and element size"
+        prm = self._depth_filter_params(jump_rel, radius, min_support, min_region)
+        cnt = (C.c_int64 * 4)()
+        abi.check(self._lib.tl3d_filter_depth(self._h, abi.ptr(depth), kind, C.byref(prm), abi.ptr(out), cnt))
+        return out, dict(zip(self.DEPTH_FILTER_COUNTS, (int(c) for c in cnt)))
+
+    def filter_depth_slots(self, slots, jump_rel=0.05, radius=1, min_support=4, min_region=0, counts=True):
+        """Filters the resident frames `slots` in place by the rule of filter_depth (a uint16 frame on its millimetres), each as a
+        new upload of its slot: normal maps and everything cached from the old image are void.  Returns the counts as int64 [n, 4]
+        (valid, removed_flying, regions, removed_regions per slot), or None with counts=False (the call then does not wait)."""
+        sl = np.ascontiguousarray([int(s) for s in slots], np.int32)
+        prm = self._depth_filter_params(jump_rel, radius, min_support, min_region)
+        cnt = np.zeros((len(sl), 4), np.int64) if counts else None
+        abi.check(self._lib.tl3d_filter_depth_slots(self._h, len(sl), abi.ptr(sl) if len(sl) else None, C.byref(prm), abi.ptr(cnt)))
+        return cnt
+
     # ---- a4/a5 -----------------------------------------------------------------------------
     @staticmethod
     def _pose_args(pose, flags):

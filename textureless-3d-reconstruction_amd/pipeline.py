@@ -167,6 +167,35 @@ def cloud_plane_parameters(cfg, voxel_size=None) -> dict:
                 min_points=int(cfg.cloud_planes_min_points), max_rms=float(cfg.cloud_planes_max_rms) or 0.5 * voxel)
 
 
+def check_depth_filter_options(cfg):
+    """config.depth_filter: what reconstruct() refuses before any work (the ranges of tl3d_filter_depth_slots)"""
+    if not bool(getattr(cfg, "depth_filter", False)):
+        return
+    jump = float(cfg.depth_filter_jump)
+    if not (np.isfinite(jump) and jump > 0.0):
+        raise ValueError(f"depth_filter_jump = {jump}: must be finite and positive")
+    ints = {}
+    for name in ("depth_filter_radius", "depth_filter_min_support", "depth_filter_min_region"):
+        v = getattr(cfg, name)
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"{name} = {v}: must be a whole number")
+        ints[name] = int(v)
+    r = ints["depth_filter_radius"]
+    if not 1 <= r <= 3:
+        raise ValueError(f"depth_filter_radius = {r}: must lie in [1, 3]")
+    top = (2 * r + 1) ** 2 - 1
+    if not 0 <= ints["depth_filter_min_support"] <= top:
+        raise ValueError(f"depth_filter_min_support = {ints['depth_filter_min_support']}: must lie in [0, {top}] for radius {r}")
+    if ints["depth_filter_min_region"] < 0:
+        raise ValueError(f"depth_filter_min_region = {ints['depth_filter_min_region']}: must not be negative")
+
+
+def depth_filter_parameters(cfg) -> dict:
+    """config.depth_filter_* as FusionContext.filter_depth_slots takes them"""
+    return dict(jump_rel=float(cfg.depth_filter_jump), radius=int(cfg.depth_filter_radius),
+                min_support=int(cfg.depth_filter_min_support), min_region=int(cfg.depth_filter_min_region))
+
+
 class DepthToReconstructionPipeline:
     def __init__(self, config: ReconstructionConfig = None):
         self.config = config or ReconstructionConfig()
@@ -499,6 +528,7 @@ class DepthToReconstructionPipeline:
         self._check_mesh_filter_config()
         self._check_mesh_weld_config()
         self._check_cloud_normals_config()
+        check_depth_filter_options(cfg)
         loop = bool(getattr(cfg, "loop_closure", False)) and poses is None      # with poses given nothing is registered: the option is ignored
         if loop and estimate_scale:
             raise ValueError("loop_closure does not go with estimate_scale: the pose graph's edges carry no scale")
@@ -543,6 +573,10 @@ class DepthToReconstructionPipeline:
             host_depths = [d if isinstance(d, np.ndarray) else None for d in self.depths]
             self.scales = per_frame_scales(host_depths, anchors, default=scale, fetch=ctx.download_depth)
             marks.append(("upload", clock()))
+            depth_filter_stats = None
+            if getattr(cfg, "depth_filter", False):
+                depth_filter_stats = self._filter_depth_frames(ctx, n)
+                marks.append(("depth_filter", clock()))
             if poses is not None:
                 self.camera_poses, self.frame_index = list(poses), list(range(len(poses)))
             else:
@@ -581,6 +615,8 @@ class DepthToReconstructionPipeline:
                 grid = plan_lattice(mn, mx, cfg.voxel_size, cfg.grid_dim, trunc_voxels=cfg.sdf_trunc_voxels)
                 blocks = plan_blocks(grid, MAX_BLOCK_VOXELS)
             xyz, rgb = self._fuse_blocks(ctx, grid, blocks, marks, layout_given=given)
+            if depth_filter_stats is not None:
+                self.stats["depth_filter"] = depth_filter_stats
             if loop_stats is not None:
                 self.stats["loop_closure"] = loop_stats
             if track_stats is not None:
@@ -588,6 +624,18 @@ class DepthToReconstructionPipeline:
         finally:
             ctx.close()
         return xyz.astype(np.float64), rgb, self.camera_poses
+
+    def _filter_depth_frames(self, ctx: FusionContext, n: int) -> dict:
+        """config.depth_filter: flying pixels and small regions of all n resident frames set to 0, in one call, in front of everything
+        that reads a frame.  Returns what goes into stats["depth_filter"]: the totals of the four counts, the
+        frames and the parameters."""
+        prm = depth_filter_parameters(self.config)
+        counts = ctx.filter_depth_slots(list(range(n)), **prm)
+        tot = counts.sum(axis=0)
+        out = dict(frames=int(n), valid=int(tot[0]), removed_flying=int(tot[1]), regions=int(tot[2]), removed_regions=int(tot[3]), **prm)
+        print(f"  Depth filter: {out['removed_flying']} flying pixels and {out['removed_regions']} pixels of small regions "
+              f"removed from {out['valid']} valid pixels of {n} frames")
+        return out
 
     def _compare(self, ctx: FusionContext, xyz):
         """config.compare_to: the fused cloud against the reference scan's points (metrics.compare_clouds; a = the fused cloud, so
@@ -836,6 +884,8 @@ class DepthToReconstructionPipeline:
             raise ValueError("loop_closure needs a single GPU: every kept frame must be resident where the revisits are registered")
         if getattr(self.config, "model_tracking", False) and poses is None:
             raise ValueError("model_tracking needs a single GPU: every kept frame is registered against one model, in order")
+        if getattr(self.config, "depth_filter", False):
+            raise ValueError("depth_filter needs a single GPU: the shards upload their frames in several places, and the filter is not wired into them")
         self._check_mesh_filter_config()
         self._check_cloud_normals_config()
         world, rank = dist.get_world_size(), dist.get_rank()
