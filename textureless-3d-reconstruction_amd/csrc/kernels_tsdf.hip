@@ -19,6 +19,8 @@
 // brick + the depth images of the batch's frames.
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "tl3d_internal.h"
 #include "bp_device.h"
 #include "tsdf_batch.h"
@@ -53,13 +55,24 @@ namespace tl3d {
 //     LAT = 2 in the kernels without counters: the wait in front of stage C is vmcnt(3), it leaves the two newer steps' loads in
 //     flight (at LAT = 1 it was vmcnt(1), and the kernel 3 % slower: DESIGN.md 7.5).  Loads return in order, so stage B's wait
 //     for its tile record also waits for every depth value older than two steps: LAT = 3 needs no wait of its own in stage C,
-//     buys a fraction of a step, and does not fit the scalar registers.  P pairs take P + 1 + LAT steps, rounded up to whole
-//     loop bodies (6 steps at LAT = 2: the parity of A -> B and the three-entry rings of B -> C both come round); the empty
-//     slots at either end run with zc = +inf ("behind everything": no update) and legal addresses, so the steady loop has no
-//     branch but its back edge and the frame switch (stages skipped by wave-uniform branches at either end instead: the
-//     compiler's wait counts at the joins turn conservative and the launch takes a quarter longer: 61 k against 76 k frames/s);
+//     buys a fraction of a step, and does not fit the scalar registers.
+//   * P pairs take EXACTLY P + 1 + LAT steps.  The steady loop runs whole bodies of full steps and nothing else (6 steps at
+//     LAT = 2: the parity of A -> B and the three-entry rings of B -> C both come round), P div 6 of them, with no branch but its
+//     back edge and the frame switch.  Behind it, in straight-line code: the P mod 6 full steps that remain, each behind one
+//     forward branch, and the drain for the ring phase the last of them leaves (one drain per remainder) -- B of the last pair
+//     with C of pair P - 1 - LAT, then C of the LAT pairs still on their way: no projection, no tile record, one depth load.
+//     Which stages a step runs is a compile-time argument of the ONE spelling of the stages.  The first 1 + LAT steps of a brick
+//     still run their stages B and C on empty slots (zc = +inf, "behind everything": no update, legal addresses).
+//     What does NOT work, and why the ends look as they do: the remaining steps and the drains as NESTED if / else (no path
+//     rejoining) are linearised by the compiler's control-flow structuriser all the same -- every drain behind every join, the
+//     pipeline's state kept alive twice over: 64 vector registers and 15 spilled; the remaining steps IN FRONT of the loop
+//     (entering the body's sequence where P mod 6 steps are left of it, one drain) make the first step of every body wait for
+//     all loads unless every load of those steps is awaited first, and are no faster; stages skipped by wave-uniform branches
+//     INSIDE the loop body: the wait counts at the joins turn conservative and the launch takes a quarter longer (61 k
+//     against 76 k frames/s).  Until this shape a brick ran 6 ceil((P + 3) / 6) steps, every one a whole stage A and both
+//     loads: 5.5 empty steps per brick, 1.110 steps per pair where it is 1.06 now;
 //   * every load of a stage is a scalar base + a 32-bit per-lane offset.
-// 62 vector registers at LAT = 2 (56 at LAT = 1), no scratch: eight waves per SIMD.
+// 61 vector registers at LAT = 2 (56 at LAT = 1, 60 with counters), no scratch: eight waves per SIMD.
 // The arithmetic of a voxel is pair_project + stage C below, the oracle's sequence: the grid is the oracle's bit for bit.
 
 // loads from a wave-uniform base + a 32-bit per-lane byte offset (scalar base, vector offset: one address register per load)
@@ -298,29 +311,31 @@ __global__ __launch_bounds__(256, UPD_WAVES) void tsdf_update_pairs_kernel(Cam c
             float zcA[2] = {INFINITY, INFINITY};
             unsigned pixA[2] = {0u, 0u};
             float2 tlA[2] = {make_float2(0.f, 0.f), make_float2(0.f, 0.f)};
-            const unsigned nsteps = npairs + 1u + (unsigned)LAT;
-            if (EXP & 16) pf_steps += (unsigned long long)((nsteps + UNROLL - 1u) / UNROLL * UNROLL) << 32;   // steps run, above the pairs
-            auto step = [&](unsigned k, const int j) {                          // j = k mod UNROLL, a literal at every call
+            if (EXP & 16) pf_steps += (unsigned long long)(npairs + 1u + (unsigned)LAT) << 32;   // steps run, above the pairs
+            // ONE spelling of the stages.  A full step runs A(k), C(k - 1 - LAT), B(k - 1); the drain steps behind the brick's last
+            // pair run the stages that still have a pair: `stages` (bit 0 A, bit 1 B; C always) is a compile-time argument
+            auto step = [&](const int j, auto stages) {                         // j = the step's number mod UNROLL, a literal at every call
+                constexpr bool ST_A = (decltype(stages)::value & 1) != 0, ST_B = (decltype(stages)::value & 2) != 0;
                 const int par = j & 1, rc = j % RING, rb = (j + LAT) % RING;   // rings: pair k's and pair k-1-LAT's slot; pair k-1's
-                // ---- A(k): the lane's voxel of sub-brick s in the current frame -> pixel, tile record.  An empty slot (k >= npairs)
-                // runs with the camera plane at infinity: nothing lies in front of it
-                const bool have = k < npairs;
-                const unsigned s = have ? (unsigned)__builtin_ctz(m) : 0u;
-                const float zmin = have ? 0.0f : INFINITY;
-                m &= m - 1u;                                                   // (0 stays 0)
-                {
-                    const float wxs = (s & 1u) ? wx1 : wx0, wys = (s & 2u) ? wy1 : wy0, wzs = (s & 4u) ? wz1 : wz0;
-                    unsigned tix;
-                    zcA[par] = pair_project(cam, r0, r1, r2, r3, r4, r5, r6, r7, r8, t0, t1, t2, wxs, wys, wzs, zmin, row_bytes, (unsigned)sizeof(DT), ntx0,
-                                            pixA[par], tix);
-                    tlA[par] = *reinterpret_cast<const float2 *>(a_vt + ((EXP & 1) ? (unsigned)lane * 8u : tix));
-                }
-                // the scalars pair k hands down the pipeline, then -- its frame used up -- the next frame's (the loads have stages C
-                // and B to arrive in)
+                // ---- A(k): the lane's voxel of sub-brick s in the current frame -> pixel, tile record (k < npairs: the mask has a bit)
                 const char *n_img = a_img;
-                const unsigned n_vp = a_vp, n_s = s;
-                const float n_sc = a_sc;
-                if (m == 0u && rest != 0u) switch_frame();
+                unsigned n_vp = a_vp, n_s = 0u;
+                float n_sc = a_sc;
+                if constexpr (ST_A) {
+                    const unsigned s = (unsigned)__builtin_ctz(m);
+                    m &= m - 1u;
+                    {
+                        const float wxs = (s & 1u) ? wx1 : wx0, wys = (s & 2u) ? wy1 : wy0, wzs = (s & 4u) ? wz1 : wz0;
+                        unsigned tix;
+                        zcA[par] = pair_project(cam, r0, r1, r2, r3, r4, r5, r6, r7, r8, t0, t1, t2, wxs, wys, wzs, 0.0f, row_bytes, (unsigned)sizeof(DT), ntx0,
+                                                pixA[par], tix);
+                        tlA[par] = *reinterpret_cast<const float2 *>(a_vt + ((EXP & 1) ? (unsigned)lane * 8u : tix));
+                    }
+                    // the scalars pair k hands down the pipeline, then -- its frame used up -- the next frame's (the loads have stages C
+                    // and B to arrive in)
+                    n_s = s;
+                    if (m == 0u && rest != 0u) switch_frame();
+                }
                 // ---- C(k - 1 - LAT): depth value -> increment of the running sum.  A pair whose every voxel the tiles decided (two in five)
                 // has only "in front of everything" lanes (zc = -inf: tsdf = 1 exactly, and the pixel they read is valid) and "behind
                 // everything" lanes: no arithmetic
@@ -340,24 +355,57 @@ __global__ __launch_bounds__(256, UPD_WAVES) void tsdf_update_pairs_kernel(Cam c
                     if (!(EXP & 4) || inc == 0x12345u) (void)__hip_atomic_fetch_add(acc + 64u * c_s[rc], inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
                 }
                 // ---- B(k - 1): what the tile leaves open gathers its pixel; the decided lanes read the frame's valid pixel
-                bool open1;
-                {
+                if constexpr (ST_B) {
                     const float zc = zcA[par ^ 1];
                     bool fre, skp;
                     pair_tile_test(tlA[par ^ 1], zc, trunc_free, g.trunc, fre, skp);
                     zcB[rb] = fre ? -INFINITY : (skp ? INFINITY : zc);
                     const unsigned pix = ((EXP & 2) || fre || skp) ? b_vp : pixA[par ^ 1];
                     dvB[rb] = PixLoad<DT>::load(b_img, pix);
-                    open1 = __ballot(!(fre || skp)) != 0ull;
+                    c_open[rb] = __ballot(!(fre || skp)) != 0ull;
                 }
-                b_img = n_img; b_vp = n_vp;
-                c_open[rb] = open1; c_sc[rc] = n_sc; c_s[rc] = n_s;             // (C of this step has read slot rc)
+                if constexpr (ST_A) {
+                    b_img = n_img; b_vp = n_vp;
+                    c_sc[rc] = n_sc; c_s[rc] = n_s;                             // (C of this step has read slot rc)
+                }
             };
-            for (unsigned k = 0; (int)k - (1 + LAT) < (int)npairs; k += (unsigned)UNROLL) {           // (no multiple of UNROLL: empty steps up to one)
-                step(k, 0);
-                step(k + 1u, 1);
-                if constexpr (UNROLL > 2) { step(k + 2u, 2); step(k + 3u, 3); }
-                if constexpr (UNROLL > 4) { step(k + 4u, 4); step(k + 5u, 5); }
+            constexpr std::integral_constant<int, 7> FULL{};
+            constexpr std::integral_constant<int, 6> DRAIN_BC{};
+            constexpr std::integral_constant<int, 4> DRAIN_C{};
+            // P pairs take P + 1 + LAT steps: whole bodies of full steps in the steady loop and nothing else ...
+            const unsigned bodies = UNROLL == 6 ? (npairs * 43691u) >> 18 : npairs / (unsigned)UNROLL;   // (P <= 256; a shift at 2 and 4)
+            const unsigned left = npairs - bodies * (unsigned)UNROLL;
+            for (unsigned b = bodies; b != 0u; --b) {
+                step(0, FULL);
+                step(1, FULL);
+                if constexpr (UNROLL > 2) { step(2, FULL); step(3, FULL); }
+                if constexpr (UNROLL > 4) { step(4, FULL); step(5, FULL); }
+            }
+            // ... the full steps that are left, fewer than UNROLL, in straight-line code, each behind one forward branch ...
+            if (left > 0u) step(0, FULL);
+            if constexpr (UNROLL > 2) {
+                if (left > 1u) step(1, FULL);
+                if (left > 2u) step(2, FULL);
+            }
+            if constexpr (UNROLL > 4) {
+                if (left > 3u) step(3, FULL);
+                if (left > 4u) step(4, FULL);
+            }
+            // ... and the drain for the ring phase the last pair left: B of that pair with C of pair P - 1 - LAT, then C of the LAT
+            // pairs still on their way -- no projection, no tile record, one depth load.  The waits are the compiler's
+            auto drain = [&](const int j) {
+                step(j, DRAIN_BC);
+                step((j + 1) % UNROLL, DRAIN_C);
+                if constexpr (LAT > 1) step((j + 2) % UNROLL, DRAIN_C);
+                if constexpr (LAT > 2) step((j + 3) % UNROLL, DRAIN_C);
+            };
+            switch (left) {
+                case 0: drain(0); break;
+                case 1: drain(1); break;
+                case 2: if constexpr (UNROLL > 2) drain(2); break;
+                case 3: if constexpr (UNROLL > 2) drain(3); break;
+                case 4: if constexpr (UNROLL > 4) drain(4); break;
+                default: if constexpr (UNROLL > 4) drain(5); break;
             }
         }
         if (EXP & 16) { pf_a = __builtin_readcyclecounter(); pf_loop += pf_a - pf_b; }
