@@ -80,6 +80,16 @@ def main(argv=None):
                         help="a pixel with fewer than N linked pixels in its window goes (0..(2R+1)^2-1; default 4)")
     parser.add_argument("--depth-filter-min-region", type=int, default=0, metavar="N",
                         help="a 4-connected region of linked pixels smaller than N goes too (default 0: no such stage)")
+    parser.add_argument("--photometric", action="store_true",
+                        help="register with colour too: a photometric term beside the point-to-plane one observes the motion geometry "
+                             "cannot see (along a tunnel, across a wall)")
+    parser.add_argument("--photo-weight", type=float, default=0.1, metavar="W",
+                        help="weight of the photometric system beside the geometric one (default 0.1; too small a weight falls under "
+                             "the solver's eigenvalue cutoff)")
+    parser.add_argument("--photo-gate", type=float, default=0.2, metavar="G",
+                        help="largest intensity difference (0..1) of a photometric correspondence (default 0.2)")
+    parser.add_argument("--photo-smooth-radius", type=int, default=1, metavar="R",
+                        help="the intensity is averaged over (2R+1)^2 pixels on one side of depth edges (0..7; default 1)")
     parser.add_argument("--device", type=int, default=0)
     args = parser.parse_args(argv)
 
@@ -102,6 +112,14 @@ def main(argv=None):
             parser.error("--depth-filter: " + str(e))
     if args.compare_threshold and len(args.compare_threshold) > 8:
         parser.error("--compare-threshold: at most 8 thresholds")
+    if args.photometric:
+        from tl3d.pipeline import check_photometric_options
+        try:
+            check_photometric_options(argparse.Namespace(photometric=True, photo_weight=args.photo_weight, photo_gate=args.photo_gate,
+                                                         photo_smooth_radius=args.photo_smooth_radius, photo_depth_jump=0.05,
+                                                         loop_closure=args.loop_closure))
+        except ValueError as e:
+            parser.error("--photometric: " + str(e))
     from tl3d import fileio
     from tl3d.config import ReconstructionConfig
     from tl3d.pipeline import DepthToReconstructionPipeline
@@ -121,6 +139,8 @@ def main(argv=None):
                                   depth_filter=args.depth_filter, depth_filter_jump=args.depth_filter_jump,
                                   depth_filter_radius=args.depth_filter_radius, depth_filter_min_support=args.depth_filter_min_support,
                                   depth_filter_min_region=args.depth_filter_min_region,
+                                  photometric=args.photometric, photo_weight=args.photo_weight, photo_gate=args.photo_gate,
+                                  photo_smooth_radius=args.photo_smooth_radius,
                                   cloud_planes=args.cloud_planes, cloud_planes_angle_deg=args.cloud_planes_angle,
                                   cloud_planes_min_points=args.cloud_planes_min_points, cloud_planes_max_curvature=args.cloud_planes_max_curvature,
                                   cloud_normals=args.cloud_normals, cloud_normals_neighbors=args.cloud_normals_neighbors,

@@ -363,6 +363,59 @@ typedef struct tl3d_icp_eval {
 int tl3d_icp_evaluate_pairs(tl3d_ctx *ctx, const tl3d_icp_pair *pairs, int n_pairs, int stride, double max_dist,
                             tl3d_icp_eval *out /* [n_pairs] */);
 
+/* a10, with colour: joint point-to-plane + photometric registration (no reference code: the reference takes its
+ * poses from image features).  Beside the geometric residual of tl3d_icp_* a correspondence contributes the difference between the
+ * smoothed intensity of its source pixel and that of the target image at its projection, which observes the in-surface motion that
+ * point-to-plane cannot (a tube's axis, a wall's plane).
+ * tl3d_build_intensity_many: the intensity map of each of the n slots, from its colour image and its f32 depth: per pixel
+ * (S, Sx, Sy, flag) with y = 29 B + 150 G + 77 R, S = (float)sum y / (float)(count * 65280) over the pixels of the (2 radius + 1)^2
+ * window that are in the image, valid (depth finite and > 0) and linked to the centre (fabsf(a - b) <= depth_jump * fminf(a, b), the
+ * depth filter's rule), flag 0 for an invalid centre (the record is zero), 2 when all four axis neighbours are in the image, valid
+ * and linked to the centre, else 1; Sx, Sy the central differences of S where flag is 2, else 0.  Bit for bit a function of the two
+ * images.  Every rewrite of the slot (upload, tl3d_filter_depth_slots, a ray cast into it) voids the map.  TL3D_E_STATE for a slot
+ * without a frame or without colour; TL3D_E_INVALID for a slot out of range, radius outside 0..7, depth_jump not positive. */
+int tl3d_build_intensity_many(tl3d_ctx *ctx, int n, const int32_t *slots, int radius, double depth_jump);
+/* the slot's intensity map, row-major; host or device memory.  TL3D_E_STATE without a map. */
+int tl3d_download_intensity(tl3d_ctx *ctx, int slot, float *imap_out_hd /* [H][W][4] */);
+/* ONE pass of both systems for each pair at pairs[i].T_init, no update.  The geometric half is tl3d_icp_evaluate_pairs' (same
+ * samples, counts and terms).  A geometric correspondence (source pixel (u, v), target pixel (ut, vt), projection (uf, vf))
+ * QUALIFIES when the target record has flag 2 and the source record flag >= 1; it is a photometric correspondence when also
+ * |r_I| <= photo_gate, r_I = S_t + Sx_t (uf - ut) + Sy_t (vf - vt) - S_s; J_I = [q x g, g] with g the gradient of r_I with respect
+ * to the transformed point q.  f32 values, fp64 sums of fp64 products, the two systems apart; a pair's result is bit for bit the
+ * same in every run, whatever n_pairs and wherever the pair stands.  n_pairs >= 0; chunked like tl3d_icp_evaluate_pairs; blocks.
+ * TL3D_E_STATE while an ICP batch is uncollected, for a slot without a frame or without an intensity map, a target without a normal
+ * map; TL3D_E_INVALID for slots out of range, stride < 1, max_dist or photo_gate not positive. */
+typedef struct tl3d_rgbd_eval {
+    tl3d_icp_eval geo;          /* the point-to-plane system, as tl3d_icp_evaluate_pairs gives it  */
+    double A_p[21];             /* upper triangle of sum J_I J_I^T, row-major                      */
+    double b_p[6];              /* sum J_I r_I                                                     */
+    double e_p;                 /* sum r_I^2                                                       */
+    int64_t n_photo;            /* photometric correspondences                                     */
+    int64_t n_qualified;        /* geometric correspondences whose two records qualify             */
+} tl3d_rgbd_eval;
+int tl3d_rgbd_evaluate_pairs(tl3d_ctx *ctx, const tl3d_icp_pair *pairs, int n_pairs, int stride, double max_dist, double photo_gate,
+                             tl3d_rgbd_eval *out /* [n_pairs] */);
+/* The registration: every pair through all of `levels`, coarse to fine, every iteration on the device (two launches per iteration
+ * for the whole batch), then a final pass at the result.  An iteration solves (A_g + photo_weight A_p + lam I) x = -(b_g +
+ * photo_weight b_p) -- damping and the eigenvalue cutoff eig_rel act on the joint system, so a photo_weight too small leaves the
+ * photometric directions under the cutoff -- and applies T <- exp(x) T.  Stop, failure and level chaining as the batched ICP above
+ * (a pass with fewer than 6 geometric correspondences fails the run, a level that ends with fewer than 8 is the pair's last);
+ * photo_weight 0 is the point-to-plane registration.  out as the batched ICP fills it (fitness, rmse, n_corr, n_src geometric);
+ * info (may be NULL) adds the photometric statistics of the final pass.  Blocks.  Errors as tl3d_rgbd_evaluate_pairs, and
+ * TL3D_E_INVALID for n_levels outside 1..TL3D_ICP_MAX_LEVELS, a negative photo_weight, estimate_scale. */
+typedef struct tl3d_rgbd_level {
+    tl3d_icp_params icp;        /* iters, stride, max_dist, damping, eps, eig_rel; estimate_scale must be 0 */
+    double photo_weight;        /* lambda >= 0: weight of the photometric system                   */
+    double photo_gate;          /* |r_I| <= photo_gate, in units of S (0..1)                       */
+} tl3d_rgbd_level;
+typedef struct tl3d_rgbd_info {
+    double photo_rmse;          /* sqrt(e_p / n_photo) of the final pass, 0 without correspondences */
+    int64_t n_photo;            /* photometric correspondences of the final pass                   */
+    int64_t n_qualified;        /* geometric correspondences whose two records qualify             */
+} tl3d_rgbd_info;
+int tl3d_rgbd_register_pairs(tl3d_ctx *ctx, const tl3d_icp_pair *pairs, int n_pairs, const tl3d_rgbd_level *levels, int n_levels,
+                             tl3d_icp_result *out /* [n_pairs] */, tl3d_rgbd_info *info /* [n_pairs] or NULL */);
+
 /* grids */
 /* Give a context created with channels = 0 its grid later (geometry fields of cfg: channels, nx, ny, nz, origin,
  * voxel_size, sdf_trunc, ext_*): frames stay resident while poses and scene bounds are still being computed. */

@@ -27,6 +27,7 @@ SYMBOLS = [
     "tl3d_accumulate_points", "tl3d_points_bounds", "tl3d_integrate", "tl3d_build_normals",
     "tl3d_download_normals", "tl3d_icp_p2plane", "tl3d_icp_enqueue", "tl3d_icp_collect", "tl3d_icp_batch_enqueue", "tl3d_icp_batch_collect", "tl3d_icp_evaluate_pairs", "tl3d_host_pack_bgr_rows", "tl3d_host_copy_rows", "tl3d_build_normals_many", "tl3d_fuse_frames", "tl3d_grid_reset", "tl3d_grid_device_ptr",
     "tl3d_grid_download", "tl3d_grid_upload", "tl3d_grid_add", "tl3d_grid_touched_bricks", "tl3d_grid_pack_bricks", "tl3d_grid_unpack_bricks", "tl3d_rccl_unique_id", "tl3d_rccl_init", "tl3d_allreduce_grid", "tl3d_extract", "tl3d_extract_mesh", "tl3d_extract_mesh_keyed", "tl3d_mesh_components", "tl3d_mesh_filter_components", "tl3d_mesh_simplify_clusters", "tl3d_mesh_simplify_quadric", "tl3d_mesh_smooth_taubin", "tl3d_mesh_vertex_normals", "tl3d_mesh_weld_keyed", "tl3d_raycast", "tl3d_track_evaluate", "tl3d_track_frame", "tl3d_statistical_outlier", "tl3d_knn_mean_distance", "tl3d_estimate_normals", "tl3d_segment_planes",
+    "tl3d_build_intensity_many", "tl3d_download_intensity", "tl3d_rgbd_evaluate_pairs", "tl3d_rgbd_register_pairs",
     "tl3d_nearest_points", "tl3d_nearest_triangles", "tl3d_distance_summary", "tl3d_set_nearest_query_order",
     "tl3d_set_profile", "tl3d_set_normal_smoothing", "tl3d_set_tsdf_pairing", "tl3d_tile_cache_info", "tl3d_class_cache_info", "tl3d_class_refine_info", "tl3d_get_stats", "tl3d_reset_stats", "tl3d_event_record", "tl3d_event_elapsed_ms",
 ]
@@ -67,6 +68,19 @@ class IcpPair(C.Structure):
 
 class IcpEval(C.Structure):
     _fields_ = [("A", C.c_double * 21), ("b", C.c_double * 6), ("e", C.c_double), ("n_corr", C.c_int64), ("n_src", C.c_int64)]
+
+
+class RgbdEval(C.Structure):
+    _fields_ = [("geo", IcpEval), ("A_p", C.c_double * 21), ("b_p", C.c_double * 6), ("e_p", C.c_double), ("n_photo", C.c_int64),
+                ("n_qualified", C.c_int64)]
+
+
+class RgbdLevel(C.Structure):
+    _fields_ = [("icp", IcpParams), ("photo_weight", C.c_double), ("photo_gate", C.c_double)]
+
+
+class RgbdInfo(C.Structure):
+    _fields_ = [("photo_rmse", C.c_double), ("n_photo", C.c_int64), ("n_qualified", C.c_int64)]
 
 
 class MeshPart(C.Structure):
@@ -226,6 +240,10 @@ def load():
         "tl3d_icp_batch_collect": [vp, C.POINTER(IcpResult), i32],
         "tl3d_icp_evaluate_pairs": [vp, C.POINTER(IcpPair), i32, i32, dbl, C.POINTER(IcpEval)],
         "tl3d_build_normals_many": [vp, i32, vp, vp, dbl],
+        "tl3d_build_intensity_many": [vp, i32, vp, i32, dbl],
+        "tl3d_download_intensity": [vp, i32, vp],
+        "tl3d_rgbd_evaluate_pairs": [vp, C.POINTER(IcpPair), i32, i32, dbl, dbl, C.POINTER(RgbdEval)],
+        "tl3d_rgbd_register_pairs": [vp, C.POINTER(IcpPair), i32, C.POINTER(RgbdLevel), i32, C.POINTER(IcpResult), C.POINTER(RgbdInfo)],
         "tl3d_fuse_frames": [vp, i32, vp, vp, vp, vp, u32, i32, dbl, dbl],
         "tl3d_host_pack_bgr_rows": [vp, vp, i32, i32],
         "tl3d_host_copy_rows": [vp, vp, i32, C.c_size_t],

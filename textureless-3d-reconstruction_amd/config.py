@@ -134,6 +134,18 @@ class ReconstructionConfig:
     depth_filter_radius: int = 1
     depth_filter_min_support: int = 4
     depth_filter_min_region: int = 0
+    # photometric term in the frame-to-frame registration: beside the point-to-plane residual every
+    # correspondence contributes the difference of the smoothed intensities of its two pixels, which observes the in-surface motion
+    # geometry cannot (a tube's axis, a wall's plane).  The joint system is A_g + photo_weight A_p; a weight too small leaves the
+    # photometric directions under icp_eig_rel (0.01 does on the open tube).  photo_gate bounds |r_I| (intensities in 0..1);
+    # the intensity is averaged over a (2 photo_smooth_radius + 1)^2 window of pixels linked by photo_depth_jump (the depth filter's
+    # rule).  Needs colour with every frame; not with estimate_scale, loop_closure or a sharded run.  icp_log entries and
+    # stats["photometric"] carry n_photo and the photometric rmse.  Off: nothing changes.
+    photometric: bool = False
+    photo_weight: float = 0.1
+    photo_gate: float = 0.2
+    photo_smooth_radius: int = 1
+    photo_depth_jump: float = 0.05
 
     @property
     def K(self) -> np.ndarray:

@@ -29,6 +29,29 @@ template <class P> static void describe_pair(P *p, const Slot &ss, const Slot &s
     p->scale = (float)scale;
 }
 
+// A float4 map kept in phase-major rows (tl3d_internal.h: pm_index; normal maps, intensity maps) as the row-major [H][W][4] image a
+// caller gets, into host or device memory; waits for the stream.
+static int download_pm_map(tl3d_ctx *ctx, const float4 *map, float *out) {
+    TL3D_HIP(hipSetDevice(ctx->device));
+    if (is_device_ptr(out)) {
+        const int rc2 = launch_nmap_rowmajor(ctx->stream, ctx->cam, map, (float4 *)out);
+        if (rc2) return rc2;
+        TL3D_HIP(hipStreamSynchronize(ctx->stream));
+        return TL3D_OK;
+    }
+    const int W = ctx->cam.W, H = ctx->cam.H, w4 = pm_w4(W);
+    float4 *tmp = (float4 *)malloc(pm_pixels(W, H) * sizeof(float4));
+    REQUIRE(tmp != nullptr, TL3D_E_NOMEM, "host allocation failed");
+    hipError_t e = hipMemcpyAsync(tmp, map, pm_pixels(W, H) * sizeof(float4), hipMemcpyDefault, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { free(tmp); TL3D_HIP(e); }
+    float4 *o4 = (float4 *)out;
+    for (int v = 0; v < H; ++v)
+        for (int u = 0; u < W; ++u) o4[(size_t)v * W + u] = tmp[pm_index(u, v, w4)];
+    free(tmp);
+    return TL3D_OK;
+}
+
 // The checks of a level.  Every call refuses iters outside [0,1000], stride < 1 and a max_dist that is not positive (NaN included);
 // `refuse` adds what only some calls refuse: max_dist >= 1e18 (infinity included), estimate_scale.
 enum : unsigned { LV_FINITE_GATE = 1, LV_NO_SCALE = 2 };
@@ -120,6 +143,9 @@ void registration_release(tl3d_ctx *ctx) {
     if (ctx->icp_eval.slab) (void)hipFree(ctx->icp_eval.slab);
     if (ctx->icp_eval.sums) (void)hipFree(ctx->icp_eval.sums);
     track_free(ctx->track);
+    if (ctx->rgbd.pairs) (void)hipFree(ctx->rgbd.pairs);
+    if (ctx->rgbd.states) (void)hipFree(ctx->rgbd.states);
+    if (ctx->rgbd.slab) (void)hipFree(ctx->rgbd.slab);
 }
 }  // namespace tl3d
 
@@ -155,25 +181,7 @@ int tl3d_download_normals(tl3d_ctx *ctx, int slot, float *out) {
     if (rc) return rc;
     REQUIRE(out != nullptr, TL3D_E_INVALID, "null out");
     REQUIRE(ctx->slots[slot].has_normals, TL3D_E_STATE, "slot %d has no normal map (call tl3d_build_normals)", slot);
-    TL3D_HIP(hipSetDevice(ctx->device));
-    // the map lives in phase-major rows (tl3d_internal.h: pm_index); the caller gets it row-major
-    if (is_device_ptr(out)) {
-        const int rc2 = launch_nmap_rowmajor(ctx->stream, ctx->cam, ctx->slots[slot].nmap, (float4 *)out);
-        if (rc2) return rc2;
-        TL3D_HIP(hipStreamSynchronize(ctx->stream));
-        return TL3D_OK;
-    }
-    const int W = ctx->cam.W, H = ctx->cam.H, w4 = pm_w4(W);
-    float4 *tmp = (float4 *)malloc(pm_pixels(W, H) * sizeof(float4));
-    REQUIRE(tmp != nullptr, TL3D_E_NOMEM, "host allocation failed");
-    hipError_t e = hipMemcpyAsync(tmp, ctx->slots[slot].nmap, pm_pixels(W, H) * sizeof(float4), hipMemcpyDefault, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { free(tmp); TL3D_HIP(e); }
-    float4 *o4 = (float4 *)out;
-    for (int v = 0; v < H; ++v)
-        for (int u = 0; u < W; ++u) o4[(size_t)v * W + u] = tmp[pm_index(u, v, w4)];
-    free(tmp);
-    return TL3D_OK;
+    return download_pm_map(ctx, ctx->slots[slot].nmap, out);
 }
 
 int tl3d_build_normals_many(tl3d_ctx *ctx, int n, const int32_t *slots, const double *scales, double depth_jump) {
@@ -657,6 +665,176 @@ int tl3d_track_frame(tl3d_ctx *ctx, int slot, double scale, const double R_init[
     if (rc) return rc;
     read_result(*ctx->track.host, out);
     out->scale = scale;                                  // (tracking estimates none: the caller's)
+    return TL3D_OK;
+}
+
+// ------------------------------------------------------------------------------------------- joint point-to-plane + photometric
+int tl3d_build_intensity_many(tl3d_ctx *ctx, int n, const int32_t *slots, int radius, double depth_jump) {
+    REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
+    REQUIRE(n >= 0 && (slots || n == 0), TL3D_E_INVALID, "null argument or negative n");
+    REQUIRE(radius >= 0 && radius <= 7, TL3D_E_INVALID, "radius %d outside [0,7]", radius);
+    REQUIRE(depth_jump > 0, TL3D_E_INVALID, "depth_jump must be positive");
+    for (int i = 0; i < n; ++i) {
+        const int rc = check_slot(ctx, slots[i], true);
+        if (rc) return rc;
+        REQUIRE(ctx->slots[slots[i]].has_color, TL3D_E_STATE, "slot %d holds no colour image", slots[i]);
+    }
+    if (n == 0) return TL3D_OK;
+    TL3D_HIP(hipSetDevice(ctx->device));
+    for (int i = 0; i < n; ++i) {
+        Slot &s = ctx->slots[slots[i]];
+        if (!s.imap && !(s.imap = (float4 *)pool_take(ctx->pool_imap))) return set_err(TL3D_E_NOMEM, "intensity map alloc failed");
+        // the main stream: behind the slot's upload and behind every registration that read the previous map (they block)
+        const int rc = launch_intensity(ctx->stream, ctx->cam, s.depth, s.bgr, radius, (float)depth_jump, s.imap);
+        if (rc) return rc;
+        s.has_intensity = true;
+        if (!s.ev_intensity) TL3D_HIP(hipEventCreateWithFlags(&s.ev_intensity, hipEventDisableTiming));
+        TL3D_HIP(hipEventRecord(s.ev_intensity, ctx->stream));
+    }
+    return TL3D_OK;
+}
+
+int tl3d_download_intensity(tl3d_ctx *ctx, int slot, float *out) {
+    int rc = check_slot(ctx, slot, true);
+    if (rc) return rc;
+    REQUIRE(out != nullptr, TL3D_E_INVALID, "null out");
+    REQUIRE(ctx->slots[slot].has_intensity, TL3D_E_STATE, "slot %d has no intensity map (call tl3d_build_intensity_many)", slot);
+    return download_pm_map(ctx, ctx->slots[slot].imap, out);
+}
+
+// what both calls check of their pairs: check_pair, then colour and intensity maps on both sides
+static int rgbd_check_pairs(tl3d_ctx *ctx, const tl3d_icp_pair *pairs, int n_pairs) {
+    for (int i = 0; i < n_pairs; ++i) {
+        const int rc = check_pair(ctx, pairs[i].slot_src, pairs[i].slot_tgt, i);
+        if (rc) return rc;
+        const int sl[2] = {pairs[i].slot_src, pairs[i].slot_tgt};
+        for (int k = 0; k < 2; ++k) {
+            REQUIRE(ctx->slots[sl[k]].has_color, TL3D_E_STATE, "pair %d: slot %d holds no colour image", i, sl[k]);
+            REQUIRE(ctx->slots[sl[k]].has_intensity, TL3D_E_STATE, "pair %d: slot %d has no intensity map (call tl3d_build_intensity_many)", i, sl[k]);
+        }
+    }
+    return TL3D_OK;
+}
+
+static RgbdLevel rgbd_level(tl3d_ctx *ctx, const tl3d_icp_params &p, double photo_gate) {
+    const IcpLevel L = make_level(ctx->cam, p);
+    return RgbdLevel{L.md2, (float)photo_gate, (float)ctx->cfg.min_depth, (float)ctx->cfg.max_depth, L.stride, L.Ws, L.Hs, rgbd_members(L.Ws, L.Hs)};
+}
+
+// Every pair through `levels` in chunks the scratch holds: states up, every launch of every level, states down, one wait per chunk.
+// eval: one final pass at the initial poses and nothing else.  hs: the final states, [n_pairs].
+static int rgbd_run(tl3d_ctx *ctx, const tl3d_icp_pair *pairs, int n_pairs, const tl3d_rgbd_level *levels, int n_levels, bool eval,
+                    std::vector<RgbdState> &hs) {
+    std::vector<RgbdLevel> lv((size_t)n_levels);
+    int members_max = 1;
+    for (int l = 0; l < n_levels; ++l) {
+        lv[l] = rgbd_level(ctx, levels[l].icp, levels[l].photo_gate);
+        if (lv[l].members > members_max) members_max = lv[l].members;
+    }
+    size_t chunk = ICP_EVAL_SLAB_DOUBLES / ((size_t)members_max * RGBD_SUMS);
+    if (chunk < 1) chunk = 1;
+    if (chunk > 32768) chunk = 32768;                      // the pair is the launch's grid.y
+    if (chunk > (size_t)n_pairs) chunk = (size_t)n_pairs;
+    TL3D_HIP(hipSetDevice(ctx->device));
+    tl3d_ctx::Rgbd &b = ctx->rgbd;
+    int rc = chunk <= b.cap_pairs ? TL3D_OK : grow_pair(&b.pairs, &b.states, &b.cap_pairs, chunk < 64 ? 64 : chunk, "RGB-D registration");
+    if (!rc) rc = grow(&b.slab, &b.cap_slab, chunk * members_max * RGBD_SUMS, "RGB-D registration slab");
+    if (rc) return rc;
+    std::vector<RgbdPair> hp(chunk);
+    hs.assign((size_t)n_pairs, RgbdState());
+    // the main stream: behind every upload, normal map and intensity map issued so far
+    for (size_t i0 = 0; i0 < (size_t)n_pairs; i0 += chunk) {
+        const size_t m = (size_t)n_pairs - i0 < chunk ? (size_t)n_pairs - i0 : chunk;
+        for (size_t k = 0; k < m; ++k) {
+            const tl3d_icp_pair &p = pairs[i0 + k];
+            const Slot &ss = ctx->slots[p.slot_src], &st = ctx->slots[p.slot_tgt];
+            describe_pair(&hp[k], ss, st, p.scale_src);
+            hp[k].imap_src = ss.imap;
+            hp[k].imap_tgt = st.imap;
+            RgbdState &h = hs[i0 + k];
+            memset(&h, 0, sizeof(h));
+            memcpy(h.icp.T, p.T_init, sizeof(h.icp.T));
+            h.icp.scale = p.scale_src;
+        }
+        TL3D_HIP(hipMemcpyAsync(b.pairs, hp.data(), m * sizeof(RgbdPair), hipMemcpyHostToDevice, ctx->stream));
+        TL3D_HIP(hipMemcpyAsync(b.states, &hs[i0], m * sizeof(RgbdState), hipMemcpyHostToDevice, ctx->stream));
+        for (int l = 0; l < n_levels && !rc; ++l) {
+            const tl3d_icp_params &p = levels[l].icp;
+            const int last = eval || l == n_levels - 1 ? 2 : 1;
+            for (int it = 0; it <= (eval ? 0 : p.iters) && !rc; ++it) {
+                const int fin = it == (eval ? 0 : p.iters) ? last : 0;
+                rc = launch_rgbd_pass(ctx->stream, ctx->cam, b.pairs, (int)m, lv[l], b.states, fin, b.slab);
+                if (!rc) rc = launch_rgbd_step(ctx->stream, b.slab, (int)m, lv[l].members, b.states, levels[l].photo_weight, p.damping, p.eps, p.eig_rel, fin);
+            }
+        }
+        if (rc) return rc;
+        TL3D_HIP(hipMemcpyAsync(&hs[i0], b.states, m * sizeof(RgbdState), hipMemcpyDeviceToHost, ctx->stream));
+        TL3D_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return TL3D_OK;
+}
+
+int tl3d_rgbd_evaluate_pairs(tl3d_ctx *ctx, const tl3d_icp_pair *pairs, int n_pairs, int stride, double max_dist, double photo_gate,
+                             tl3d_rgbd_eval *out) {
+    REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
+    REQUIRE(n_pairs >= 0, TL3D_E_INVALID, "n_pairs %d is negative", n_pairs);
+    tl3d_rgbd_level lv;
+    memset(&lv, 0, sizeof(lv));
+    lv.icp.stride = stride;
+    lv.icp.max_dist = max_dist;
+    lv.photo_gate = photo_gate;
+    int rc = check_level(lv.icp, LV_FINITE_GATE);
+    if (rc) return rc;
+    REQUIRE(photo_gate > 0, TL3D_E_INVALID, "photo_gate must be positive");
+    REQUIRE(n_pairs == 0 || (pairs && out), TL3D_E_INVALID, "null argument");
+    REQUIRE(!ctx->icp_batch.busy, TL3D_E_STATE, "an ICP batch is still uncollected");
+    rc = rgbd_check_pairs(ctx, pairs, n_pairs);
+    if (rc) return rc;
+    if (n_pairs == 0) return TL3D_OK;
+    std::vector<RgbdState> hs;
+    rc = rgbd_run(ctx, pairs, n_pairs, &lv, 1, true, hs);
+    if (rc) return rc;
+    for (int i = 0; i < n_pairs; ++i) {
+        read_eval(hs[i].icp.sums, &out[i].geo);
+        memcpy(out[i].A_p, hs[i].photo, 21 * sizeof(double));
+        memcpy(out[i].b_p, hs[i].photo + 21, 6 * sizeof(double));
+        out[i].e_p = hs[i].photo[RGBD_SUM_E_P - 32];
+        out[i].n_photo = (int64_t)hs[i].photo[RGBD_SUM_PHOTO - 32];
+        out[i].n_qualified = (int64_t)hs[i].icp.sums[RGBD_SUM_ELIG];
+    }
+    return TL3D_OK;
+}
+
+int tl3d_rgbd_register_pairs(tl3d_ctx *ctx, const tl3d_icp_pair *pairs, int n_pairs, const tl3d_rgbd_level *levels, int n_levels,
+                             tl3d_icp_result *out, tl3d_rgbd_info *info) {
+    REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
+    REQUIRE(n_pairs >= 0, TL3D_E_INVALID, "n_pairs %d is negative", n_pairs);
+    REQUIRE(n_levels >= 1 && n_levels <= TL3D_ICP_MAX_LEVELS, TL3D_E_INVALID, "n_levels %d outside [1,%d]", n_levels, TL3D_ICP_MAX_LEVELS);
+    REQUIRE(levels != nullptr, TL3D_E_INVALID, "null argument");
+    for (int l = 0; l < n_levels; ++l) {
+        REQUIRE(!levels[l].icp.estimate_scale, TL3D_E_INVALID, "the joint registration does not estimate the scale (estimate_scale must be 0)");
+        const int rc = check_level(levels[l].icp, LV_FINITE_GATE);
+        if (rc) return rc;
+        REQUIRE(levels[l].photo_gate > 0, TL3D_E_INVALID, "photo_gate must be positive");
+        REQUIRE(levels[l].photo_weight >= 0, TL3D_E_INVALID, "photo_weight must not be negative");
+    }
+    REQUIRE(n_pairs == 0 || (pairs && out), TL3D_E_INVALID, "null argument");
+    REQUIRE(!ctx->icp_batch.busy, TL3D_E_STATE, "an ICP batch is still uncollected");
+    int rc = rgbd_check_pairs(ctx, pairs, n_pairs);
+    if (rc) return rc;
+    if (n_pairs == 0) return TL3D_OK;
+    std::vector<RgbdState> hs;
+    rc = rgbd_run(ctx, pairs, n_pairs, levels, n_levels, false, hs);
+    if (rc) return rc;
+    for (int i = 0; i < n_pairs; ++i) {
+        read_result(hs[i].icp, &out[i]);
+        if (info) {
+            const double e_p = hs[i].photo[RGBD_SUM_E_P - 32], n_photo = hs[i].photo[RGBD_SUM_PHOTO - 32];
+            info[i].photo_rmse = n_photo > 0 ? sqrt(e_p / n_photo) : 0.0;
+            info[i].n_photo = (int64_t)n_photo;
+            info[i].n_qualified = (int64_t)hs[i].icp.sums[RGBD_SUM_ELIG];
+        }
+    }
     return TL3D_OK;
 }
 

@@ -954,6 +954,70 @@ int launch_track_step(hipStream_t s, const double *slab, int members, IcpState *
     return TL3D_OK;
 }
 
+// Joint point-to-plane + photometric registration (kernels_rgbd.hip), the step behind a pass: ONE wave per pair adds the pair's
+// partials in member order (lane c owns sum c of the 64), keeps them in the pair's state and, unless this is a final pass, forms
+// A = A_g + weight * A_p and b = b_g + weight * b_p in fp64 (a product, then a sum), solves the damped system with the solvers above
+// -- damping and the eigenvalue cutoff act on the joint system -- and applies T <- exp(x) T as the ICP does.  The rules are the
+// batched ICP's: a pass with fewer than 6 geometric correspondences or an unsolvable system fails the run (status 2, T the last good
+// pose), |x|_max < eps ends the level (status 1); final_pass as track_step_kernel: 1 ends a level that another one follows (over when
+// it failed or ended with fewer than 8 geometric correspondences, else done / status / iters_run are re-armed), 2 ends the last one.
+__global__ __launch_bounds__(64) void rgbd_step_kernel(const double *__restrict__ slab, int members, RgbdState *states, double weight, double damping,
+                                                       double eps, double eig_rel, int final_pass) {
+    RgbdState *st = states + blockIdx.x;
+    IcpState *state = &st->icp;
+    if (state->over || (!final_pass && state->done)) return;
+    __shared__ double sums[RGBD_SUMS];
+    __shared__ double joint[27];
+    const int c = threadIdx.x;
+    {
+        const double *p = slab + (size_t)blockIdx.x * members * RGBD_SUMS + c;
+        double s = 0.0;
+        for (int m = 0; m < members; ++m) s += p[(size_t)m * RGBD_SUMS];
+        sums[c] = s;
+        if (c < 32) state->sums[c] = s;
+        else st->photo[c - 32] = s;
+    }
+    __syncthreads();
+    if (final_pass) {
+        if (c == 0) {
+            if (final_pass == 2 || state->status == 2 || sums[28] < 8.0) {
+                state->over = 1;
+            } else {
+                state->done = 0;
+                state->status = 0;
+                state->iters_run = 0;
+            }
+        }
+        return;
+    }
+    if (c < 27) joint[c] = sums[c] + weight * sums[32 + c];
+    __syncthreads();
+    double x[6];
+    const int fail = (sums[28] < 6.0) ? 1 : solve6_wave(joint, joint + 21, damping, eig_rel, x);      // wave-uniform
+    if (c != 0) return;
+    if (fail) {
+        state->done = 1;
+        state->status = 2;
+        return;
+    }
+    double mx = 0.0;
+    for (int i = 0; i < 6; ++i) mx = fmax(mx, fabs(x[i]));
+    se3_apply(x, state->T);
+    state->iters_run = state->iters_run + 1;
+    if (mx < eps) {
+        state->done = 1;
+        state->status = 1;
+    }
+}
+
+int launch_rgbd_step(hipStream_t s, const double *slab, int n_pairs, int members, RgbdState *states, double photo_weight, double damping,
+                     double eps, double eig_rel, int final_pass) {
+    if (n_pairs <= 0) return TL3D_OK;
+    hipLaunchKernelGGL(rgbd_step_kernel, dim3(n_pairs), dim3(64), 0, s, slab, members, states, photo_weight, damping, eps, eig_rel, final_pass);
+    TL3D_HIP(hipGetLastError());
+    return TL3D_OK;
+}
+
 // a normal map (phase-major rows) as the row-major [H][W] image the caller of tl3d_download_normals gets
 __global__ __launch_bounds__(256) void nmap_rowmajor_kernel(int W, int H, const float4 *__restrict__ nmap, float4 *__restrict__ out) {
     const int u = blockIdx.x * 64 + (threadIdx.x & 63);

@@ -467,9 +467,10 @@ int tl3d_create(const tl3d_config *cfg, int device, tl3d_ctx **out) {
         // that a slot's first fusion costs one slab allocation per 64 slots, as before the second cache.
         ctx->tc_bytes = (tsdf_tile_cache_bytes(tc, nullptr, nullptr) + 16 + 255) & ~(size_t)255;
         ctx->cc_bytes = ctx->class_cache && ctx->tile_cache ? tsdf_class_cache_bytes(ctx->cc_entries) : 0;
-        const size_t bytes[6] = {npx * sizeof(float), npx * sizeof(uint16_t), npx * 3, npm * sizeof(float4), npm * sizeof(float), ctx->tc_bytes + ctx->cc_bytes - 16};
-        FramePool *pools[6] = {&ctx->pool_depth, &ctx->pool_u16, &ctx->pool_bgr, &ctx->pool_nmap, &ctx->pool_sdepth, &ctx->pool_tiles};
-        for (int k = 0; k < 6; ++k) {
+        const size_t bytes[7] = {npx * sizeof(float), npx * sizeof(uint16_t), npx * 3, npm * sizeof(float4), npm * sizeof(float), ctx->tc_bytes + ctx->cc_bytes - 16,
+                                 npm * sizeof(float4)};
+        FramePool *pools[7] = {&ctx->pool_depth, &ctx->pool_u16, &ctx->pool_bgr, &ctx->pool_nmap, &ctx->pool_sdepth, &ctx->pool_tiles, &ctx->pool_imap};
+        for (int k = 0; k < 7; ++k) {
             FramePool &fp = *pools[k];
             fp.block = (bytes[k] + 16 + 255) & ~(size_t)255;      // 16 B of slack: a pixel's 3 colour bytes are read as one 4-byte word
             fp.remaining = cfg->n_slots;
@@ -627,6 +628,7 @@ int tl3d_destroy(tl3d_ctx *ctx) {
         for (int i = 0; i < ctx->cfg.n_slots; ++i) {
             if (ctx->slots[i].ev_upload) (void)hipEventDestroy(ctx->slots[i].ev_upload);
             if (ctx->slots[i].ev_normals) (void)hipEventDestroy(ctx->slots[i].ev_normals);
+            if (ctx->slots[i].ev_intensity) (void)hipEventDestroy(ctx->slots[i].ev_intensity);
         }
         delete[] ctx->slots;
     }
@@ -636,6 +638,7 @@ int tl3d_destroy(tl3d_ctx *ctx) {
     pool_release(ctx->pool_nmap);
     pool_release(ctx->pool_sdepth);
     pool_release(ctx->pool_tiles);
+    pool_release(ctx->pool_imap);
     for (int q = 0; q < 4; ++q)
         if (ctx->prep_stream[q]) (void)hipStreamSynchronize(ctx->prep_stream[q]);
     release_grid(ctx);
@@ -739,6 +742,7 @@ static int slot_rewritten(tl3d_ctx *ctx, Slot &s, bool has_u16, bool has_color) 
     s.has_color = has_color;
     s.loaded = true;
     s.has_normals = false;
+    s.has_intensity = false;
     s.smooth_radius = 0;
     s.tc.valid = s.tc.used = false;
     if (!s.ev_upload) TL3D_HIP(hipEventCreateWithFlags(&s.ev_upload, hipEventDisableTiming));

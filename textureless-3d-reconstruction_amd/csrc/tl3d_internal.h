@@ -148,6 +148,30 @@ struct TrackArgs {
 };
 constexpr int TRACK_SUMS = 32;   // doubles per partial: the head of IcpState::sums
 
+// Joint point-to-plane + photometric registration (kernels_rgbd.hip).  A partial and a pair's totals are 64
+// doubles: [0, 32) the geometric system laid out as the head of IcpState::sums (a[21] b[6] e n_corr n_src), [30] the geometric
+// correspondences whose two intensity records qualify (before the photometric gate); [32, 64) the photometric system a_p[21] b_p[6]
+// e_p n_photo 0 0 0.  The two systems stay apart until the step kernel forms a + weight * a_p.
+constexpr int RGBD_SUMS = 64;
+constexpr int RGBD_SUM_ELIG = 30, RGBD_SUM_E_P = 32 + 27, RGBD_SUM_PHOTO = 32 + 28;
+constexpr int RGBD_SAMPLES_PER_MEMBER = 4096;   // workgroups per pair: a function of the level geometry only (rgbd_members)
+constexpr int RGBD_MEMBERS_CAP = 64;
+struct RgbdPair {                // what the pass reads of a pair
+    const float *depth_src;      // as IcpBatchPair: the slot's depth, or its window-averaged one in phase-major rows (src_pm)
+    const float4 *nmap_tgt;      // phase-major rows
+    const float4 *imap_src, *imap_tgt;   // intensity maps (S, Sx, Sy, flag), phase-major rows
+    float scale;
+    int src_pm;
+};
+struct RgbdState {               // per pair, in device memory for the whole run
+    IcpState icp;                // pose, geometric sums (sums[30]: the qualifying correspondences), done / status / iters_run / over
+    double photo[32];            // a_p[21] b_p[6] e_p n_photo 0 0 0
+};
+struct RgbdLevel {               // one level as the pass takes it
+    float md2, photo_gate, mind, maxd;
+    int stride, Ws, Hs, members;
+};
+
 // Everything the TSDF brick and sub-brick classification of a frame depends on besides the slot's tiles and the camera, as the
 // kernels get it (f32 words after the double -> float conversions); compared bitwise.
 struct ClassKey {
@@ -222,6 +246,11 @@ struct Slot {
     bool has_color = false;
     bool loaded = false;
     bool has_normals = false;
+    // Intensity map of the colour image (kernels_rgbd.hip: S, Sx, Sy, flag per pixel, phase-major rows), lazily allocated from
+    // tl3d_ctx::pool_imap; it is made from the slot's depth AND colour: slot_rewritten voids it with the normal map.
+    float4 *imap = nullptr;
+    bool has_intensity = false;
+    hipEvent_t ev_intensity = nullptr;   // recorded on the main stream after the slot's intensity map was built
     // TSDF tile cache: what the TSDF prep derives from the depth image, the scale and the depth limits alone (kernels_tsdf_prep.hip:
     // depth_tiles_kernel, tile_pyramid_kernel).  One lazily allocated block (tl3d_ctx::pool_tiles, tsdf_tile_cache_bytes) and the
     // key it was built with; every writer of `depth` calls slot_rewritten (tl3d_api.hip), which clears tc.  The u16 and f32 images give
@@ -343,7 +372,7 @@ struct tl3d_ctx : tl3d_grid_state {
     bool own_stream;
     tl3d::Cam cam;
     tl3d::Slot *slots;
-    tl3d::FramePool pool_depth, pool_u16, pool_bgr, pool_nmap, pool_sdepth, pool_tiles;
+    tl3d::FramePool pool_depth, pool_u16, pool_bgr, pool_nmap, pool_sdepth, pool_tiles, pool_imap;
     int normal_radius;           // tl3d_set_normal_smoothing: window radius of the next normal maps (0: none)
     // scratch
     // TSDF integration: the prep chain of a batch (tiles, pyramid, cull, brick classes) runs on a prep stream while the update
@@ -439,6 +468,13 @@ struct tl3d_ctx : tl3d_grid_state {
         tl3d::IcpState *state, *host;
         double *slab;            // [track_members][TRACK_SUMS]
     } track;
+    struct Rgbd {                // tl3d_rgbd_*: device buffers of one chunk of pairs (main stream), grown on demand
+        tl3d::RgbdPair *pairs;
+        tl3d::RgbdState *states;
+        size_t cap_pairs;        // of pairs and states
+        double *slab;            // [pairs][members][RGBD_SUMS] partials of the current pass
+        size_t cap_slab;         // in doubles
+    } rgbd;
     float *bounds_slab;
     bool nn_input_order;         // tl3d_set_nearest_query_order(ctx, 0): nearest-neighbour queries run in input order, not bucketed by cell
     // stats / profiling
@@ -623,6 +659,13 @@ int track_members(int Ws, int Hs);
 int launch_track_pass(hipStream_t s, const Cam &cam, const Grid &g, const float *depth, float scale, float mind, float maxd, int min_weight,
                       int stride, double max_dist, const int2 *tsdf, const IcpState *state, int final_pass, double *slab);
 int launch_track_step(hipStream_t s, const double *slab, int members, IcpState *state, double damping, double eps, double eig_rel, int final_pass);
+// joint point-to-plane + photometric registration (kernels_rgbd.hip: the intensity maps and the pass; kernels_icp.hip: the step)
+int launch_intensity(hipStream_t s, const Cam &cam, const float *depth, const uint8_t *bgr, int radius, float jump, float4 *imap);
+int rgbd_members(int Ws, int Hs);
+int launch_rgbd_pass(hipStream_t s, const Cam &cam, const RgbdPair *pairs, int n_pairs, const RgbdLevel &L, const RgbdState *states,
+                     int final_pass, double *slab);
+int launch_rgbd_step(hipStream_t s, const double *slab, int n_pairs, int members, RgbdState *states, double photo_weight, double damping,
+                     double eps, double eig_rel, int final_pass);
 // extraction
 int launch_extract_count(hipStream_t s, const Grid &g, int mode, int min_count, int min_weight, double max_abs,
                          const int2 *tsdf, const unsigned long long *cen, unsigned *block_counts, int nblocks);

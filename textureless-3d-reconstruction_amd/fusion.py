@@ -147,6 +147,10 @@ _ICP_RESULT_DT = np.dtype([("T", "<f8", (16,)), ("fitness", "<f8"), ("rmse", "<f
 _ICP_EVAL_DT = np.dtype([("A", "<f8", (21,)), ("b", "<f8", (6,)), ("e", "<f8"), ("n_corr", "<i8"), ("n_src", "<i8")])
 assert _ICP_PAIR_DT.itemsize == C.sizeof(abi.IcpPair) and _ICP_RESULT_DT.itemsize == C.sizeof(abi.IcpResult)
 assert _ICP_EVAL_DT.itemsize == C.sizeof(abi.IcpEval)
+_RGBD_EVAL_DT = np.dtype([("geo", _ICP_EVAL_DT), ("A_p", "<f8", (21,)), ("b_p", "<f8", (6,)), ("e_p", "<f8"), ("n_photo", "<i8"),
+                          ("n_qualified", "<i8")])
+_RGBD_INFO_DT = np.dtype([("photo_rmse", "<f8"), ("n_photo", "<i8"), ("n_qualified", "<i8")])
+assert _RGBD_EVAL_DT.itemsize == C.sizeof(abi.RgbdEval) and _RGBD_INFO_DT.itemsize == C.sizeof(abi.RgbdInfo)
 _TRIU6 = np.triu_indices(6)
 
 
@@ -610,6 +614,58 @@ class FusionContext:
         abi.check(self._lib.tl3d_icp_evaluate_pairs(self._h, arr.ctypes.data_as(C.POINTER(abi.IcpPair)), n, int(stride), float(max_dist),
                                                     res.ctypes.data_as(C.POINTER(abi.IcpEval))))
         return _eval_dicts(res, n)
+
+    # ---- joint point-to-plane + photometric registration -------------
+    def build_intensity(self, slots, radius=1, depth_jump=0.05):
+        """The intensity maps of `slots` (one slot or a sequence), from each slot's colour image and depth
+        (tl3d_build_intensity_many): what rgbd_evaluate / rgbd_register read on both sides of a pair."""
+        sl = np.ascontiguousarray(np.atleast_1d(np.asarray(slots, np.int32)))
+        abi.check(self._lib.tl3d_build_intensity_many(self._h, len(sl), abi.ptr(sl), int(radius), float(depth_jump)))
+
+    def download_intensity(self, slot: int, out=None) -> np.ndarray:
+        """The slot's intensity map as a row-major [H][W][4] image (S, Sx, Sy, flag); out: a host array or a device tensor to fill."""
+        if out is None:
+            out = np.empty((self.height, self.width, 4), np.float32)
+        abi.check(self._lib.tl3d_download_intensity(self._h, int(slot), abi.ptr(out)))
+        return out
+
+    def rgbd_evaluate(self, pairs, T, stride=2, max_dist=0.05, photo_gate=0.2, scales=None):
+        """One pass of the geometric AND the photometric system for every (slot_src, slot_tgt) of `pairs` at the pose T[i], no update
+        (tl3d_rgbd_evaluate_pairs).  One dict per pair: icp_evaluate's keys for the geometric system (A, b, e, n_corr, n_src,
+        fitness, rmse) plus A_p (6 x 6), b_p, e_p, n_photo, n_qualified and photo_rmse = sqrt(e_p / n_photo)."""
+        n = len(pairs)
+        arr = _pair_records(pairs, T, scales)
+        res = np.zeros(max(1, n), _RGBD_EVAL_DT)
+        abi.check(self._lib.tl3d_rgbd_evaluate_pairs(self._h, arr.ctypes.data_as(C.POINTER(abi.IcpPair)), n, int(stride), float(max_dist),
+                                                     float(photo_gate), res.ctypes.data_as(C.POINTER(abi.RgbdEval))))
+        out = _eval_dicts(np.ascontiguousarray(res["geo"]), n)
+        for i, d in enumerate(out):
+            A_p = np.zeros((6, 6))
+            A_p[_TRIU6] = res["A_p"][i]
+            A_p = A_p + np.triu(A_p, 1).T
+            n_photo, e_p = int(res["n_photo"][i]), float(res["e_p"][i])
+            d.update(A_p=A_p, b_p=res["b_p"][i].copy(), e_p=e_p, n_photo=n_photo, n_qualified=int(res["n_qualified"][i]),
+                     photo_rmse=float(np.sqrt(e_p / n_photo)) if n_photo > 0 else 0.0)
+        return out
+
+    def rgbd_register(self, pairs, levels, T_init=None, scales=None):
+        """Register every (slot_src, slot_tgt) of `pairs` through `levels`, coarse to fine, with the photometric term beside the
+        point-to-plane one (tl3d_rgbd_register_pairs; blocks).  levels: dicts with icp()'s keywords (estimate_scale is refused) plus
+        photo_weight (default 0.1) and photo_gate (default 0.2).  One dict per pair like icp_batch's, plus photo_rmse, n_photo and
+        n_qualified of the final pass."""
+        n = len(pairs)
+        arr = _pair_records(pairs, T_init, scales)
+        lv = (abi.RgbdLevel * max(1, len(levels)))()
+        for i, kw in enumerate(levels):
+            lv[i] = abi.RgbdLevel(_icp_params(kw), float(kw.get("photo_weight", 0.1)), float(kw.get("photo_gate", 0.2)))
+        res = np.zeros(max(1, n), _ICP_RESULT_DT)
+        info = np.zeros(max(1, n), _RGBD_INFO_DT)
+        abi.check(self._lib.tl3d_rgbd_register_pairs(self._h, arr.ctypes.data_as(C.POINTER(abi.IcpPair)), n, lv, len(levels),
+                                                     res.ctypes.data_as(C.POINTER(abi.IcpResult)), info.ctypes.data_as(C.POINTER(abi.RgbdInfo))))
+        out = _icp_result_dicts(res, n)
+        for i, d in enumerate(out):
+            d.update(photo_rmse=float(info["photo_rmse"][i]), n_photo=int(info["n_photo"][i]), n_qualified=int(info["n_qualified"][i]))
+        return out
 
     def track_evaluate(self, slot: int, pose, stride=2, max_dist=0.05, min_weight: int = 1, scale=1.0):
         """One point-to-SDF pass of the frame in `slot` against the TSDF channel at pose = (R, t) (world->camera, as integrate), no

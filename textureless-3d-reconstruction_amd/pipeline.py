@@ -196,6 +196,31 @@ def depth_filter_parameters(cfg) -> dict:
                 min_support=int(cfg.depth_filter_min_support), min_region=int(cfg.depth_filter_min_region))
 
 
+def check_photometric_options(cfg, images=None, estimate_scale=False, sharded=False):
+    """config.photometric: what reconstruct() / reconstruct_sharded() refuse before any device work.
+    images: the loaded colour images (an entry None = a frame without colour)."""
+    if not bool(getattr(cfg, "photometric", False)):
+        return
+    if sharded:
+        raise ValueError("photometric needs a single GPU: the shards register on the ICP lanes, and the joint registration is not wired into them")
+    if estimate_scale:
+        raise ValueError("photometric does not go with estimate_scale: the joint registration estimates no scale")
+    if bool(getattr(cfg, "loop_closure", False)):
+        raise ValueError("photometric does not go with loop_closure: the pose graph's edge weights are geometric (a joint-weight graph is a later change)")
+    w, g, j = float(cfg.photo_weight), float(cfg.photo_gate), float(cfg.photo_depth_jump)
+    if not (np.isfinite(w) and w >= 0.0):
+        raise ValueError(f"photo_weight = {w}: must be finite and not negative")
+    if not (np.isfinite(g) and g > 0.0):
+        raise ValueError(f"photo_gate = {g}: must be finite and positive")
+    if not (np.isfinite(j) and j > 0.0):
+        raise ValueError(f"photo_depth_jump = {j}: must be finite and positive")
+    r = cfg.photo_smooth_radius
+    if isinstance(r, bool) or int(r) != r or not 0 <= int(r) <= 7:
+        raise ValueError(f"photo_smooth_radius = {r}: must be a whole number in [0, 7]")
+    if images is not None and any(im is None for im in images):
+        raise ValueError("photometric needs a colour image with every frame")
+
+
 class DepthToReconstructionPipeline:
     def __init__(self, config: ReconstructionConfig = None):
         self.config = config or ReconstructionConfig()
@@ -264,13 +289,27 @@ class DepthToReconstructionPipeline:
         if not isinstance(scales, (list, tuple)):
             scales = [float(scales)] * n
         level_list = self._icp_levels()
+        cfg = self.config
+        photo = bool(getattr(cfg, "photometric", False))
+        log_start = len(self.icp_log)
+        log_keys = ("fitness", "rmse", "n_corr", "iters_run", "status") + (("n_photo", "photo_rmse") if photo else ())
+        if photo:
+            level_list = [dict(lv, photo_weight=float(cfg.photo_weight), photo_gate=float(cfg.photo_gate)) for lv in level_list]
+
+        def register(pairs, T0s, pair_scales):
+            """the one way to the device: the joint registration with config.photometric, else the batched ICP"""
+            if photo:
+                return ctx.rgbd_register(pairs, level_list, T_init=T0s, scales=pair_scales)
+            return ctx.icp_batch(pairs, level_list, T_init=T0s, scales=pair_scales)
 
         def blocking(src, cur, T0):
-            return ctx.icp_batch([(src, cur)], level_list, T_init=[T0], scales=[scales[src]])[0]
+            return register([(src, cur)], [T0], [scales[src]])[0]
         poses = [(np.eye(3), np.zeros((3, 1)))]
         index = [0]
         prev = 0
         ctx.build_normals_many(list(range(n)), scales)
+        if photo:
+            ctx.build_intensity(list(range(n)), int(cfg.photo_smooth_radius), float(cfg.photo_depth_jump))
         T_guess = np.eye(4)
 
         def prior(a, b_):
@@ -283,14 +322,14 @@ class DepthToReconstructionPipeline:
             batch = list(range(i, min(n, i + (16 if i == 1 else 128))))
             srcs = [prev if cur == batch[0] else cur - 1 for cur in batch]
             T0s = [prior(src, cur) for src, cur in zip(srcs, batch)]
-            results = ctx.icp_batch(list(zip(srcs, batch)), level_list, T_init=T0s, scales=[scales[src] for src in srcs])
+            results = register(list(zip(srcs, batch)), T0s, [scales[src] for src in srcs])
             for lane, cur in enumerate(batch):
                 print(f"\nProcessing image {cur}...")
                 res = results[lane]
                 src = prev if cur == batch[0] else cur - 1
                 if src != prev:                       # the frame this run started from was dropped: redo against `prev`
                     res = blocking(prev, cur, prior(prev, cur))
-                self.icp_log.append(dict(frame=cur, against=prev, **{k: res[k] for k in ("fitness", "rmse", "n_corr", "iters_run", "status")}))
+                self.icp_log.append(dict(frame=cur, against=prev, **{k: res[k] for k in log_keys}))
                 if res["status"] == 2 or res["n_corr"] < 8:
                     print(f"  Skipping - registration failed (correspondences: {res['n_corr']})")
                     continue
@@ -302,6 +341,11 @@ class DepthToReconstructionPipeline:
                 T_guess = T                  # constant-velocity prior for the next batch
                 prev = cur
             i = batch[-1] + 1
+        if photo:
+            kept = [e for e in self.icp_log[log_start:] if e["frame"] in index[1:]]
+            self._photo_stats = dict(weight=float(cfg.photo_weight), gate=float(cfg.photo_gate), smooth_radius=int(cfg.photo_smooth_radius),
+                                     depth_jump=float(cfg.photo_depth_jump), frames=len(kept), n_photo=int(sum(e["n_photo"] for e in kept)),
+                                     mean_photo_rmse=float(np.mean([e["photo_rmse"] for e in kept])) if kept else 0.0)
         return poses, index
 
     def _close_loops(self, ctx: FusionContext):
@@ -529,6 +573,9 @@ class DepthToReconstructionPipeline:
         self._check_mesh_weld_config()
         self._check_cloud_normals_config()
         check_depth_filter_options(cfg)
+        self._photo_stats = None
+        if poses is None:                                                       # with poses given nothing is registered: the option is ignored
+            check_photometric_options(cfg, None if getattr(self, "_files", None) is not None else self.images, estimate_scale)
         loop = bool(getattr(cfg, "loop_closure", False)) and poses is None      # with poses given nothing is registered: the option is ignored
         if loop and estimate_scale:
             raise ValueError("loop_closure does not go with estimate_scale: the pose graph's edges carry no scale")
@@ -621,6 +668,8 @@ class DepthToReconstructionPipeline:
                 self.stats["loop_closure"] = loop_stats
             if track_stats is not None:
                 self.stats["model_tracking"] = track_stats
+            if self._photo_stats is not None:
+                self.stats["photometric"] = self._photo_stats
         finally:
             ctx.close()
         return xyz.astype(np.float64), rgb, self.camera_poses
@@ -886,6 +935,8 @@ class DepthToReconstructionPipeline:
             raise ValueError("model_tracking needs a single GPU: every kept frame is registered against one model, in order")
         if getattr(self.config, "depth_filter", False):
             raise ValueError("depth_filter needs a single GPU: the shards upload their frames in several places, and the filter is not wired into them")
+        if poses is None:
+            check_photometric_options(self.config, sharded=True)
         self._check_mesh_filter_config()
         self._check_cloud_normals_config()
         world, rank = dist.get_world_size(), dist.get_rank()
