@@ -1,12 +1,17 @@
 """The cases of the cell-index edge tests (tests/test_cellgrid_edges_reference_cpu.py, tests/test_gpu_cellgrid_edges.py): clouds
-that put the uniform cell index of csrc/cellgrid.h, which the outlier filter and the nearest searches share, at the edges of its
-count / scan / fill.  No GPU imports.  Not a test.
+that put the uniform cell index of csrc/cellgrid.h, which the outlier filter, the nearest searches, cloud normals and plane
+segmentation share, at the edges of its count / scan / fill and of its shell walk.  No GPU imports.  Not a test.
 
 Every coordinate is a small multiple of 1/64 and every cell size a power of two, so binning has no rounding to argue about: the grid
 has floor((max - min) / cell) + 1 cells per axis, the number each case states, and each case also states how many points its
 first and its last cell hold.  1024 is the scan's chunk (cell_chunks): the lines have one cell per point and put the cell count
 at one cell, one chunk minus one, exactly one, one over, and two chunks plus one.  The end of the last cell comes from
-start[ncell], the entry behind the last chunk's scan."""
+start[ncell], the entry behind the last chunk's scan.
+
+The thin case puts the shell walk (cell_shell_walk) at its edges: a grid of 1 x 2 x 8 cells, four points in the corner cell
+(0, 0, 0) and 22 in each of the two cells at z = 7, nothing between.  A walk from the corner with k > 4 finds shells 1 to 6 empty
+and its neighbours in shell 7; the one cell along x makes every row's run begin and end in the same cell and puts the end cells of
+every interior row outside the grid on both sides; along y one of the two neighbours is always outside."""
 import functools
 
 import numpy as np
@@ -42,6 +47,21 @@ def _plane():
     return np.concatenate([p, last])
 
 
+THIN_KS = (20, 33)               # of the filter's k-NN; every one needs shell 7 from the corner
+THIN_K_NORMALS = 5               # the corner cell holds 4
+
+
+def _thin():
+    r = np.random.default_rng(0)
+    far = []
+    for half in (0, 1):                                                                 # the cells (0, half, 7)
+        pts = set()
+        while len(pts) < 22:
+            pts.add((int(r.integers(0, 64)), int(r.integers(0, 64)) + 64 * half, int(r.integers(0, 64)) + 7 * 64))
+        far += sorted(pts)
+    return np.array([[0, 0, 0], [5, 3, 2], [2, 9, 4], [7, 1, 11]] + far) / 64.0
+
+
 def _box():
     g = np.stack(np.meshgrid(np.arange(8), np.arange(8), np.arange(8), indexing="ij"), -1).reshape(-1, 3) / 8.0
     return g[np.random.default_rng(3).permutation(len(g))[:30]]                         # 30 distinct points of [0, 1)^3
@@ -53,8 +73,10 @@ _CASES = {
     **{f"last_full_{n}": ((lambda n=n: _last_full(n)), 1.0, (n, 1, 1), 1, 40) for n in LAST_FULL_NS},
     "plane": (_plane, 1.0, (PLANE_NX, PLANE_NY, 1), 1, 2),
     "box": (_box, 64.0, (1, 1, 1), 30, 30),
+    "thin": (_thin, 1.0, (1, 2, 8), 4, 22),
 }
-CASES = tuple(_CASES)
+THIN = "thin"                                                         # has its own tests: not one of CASES
+CASES = tuple(c for c in _CASES if c != THIN)
 NEAREST_ORDER_CASES = tuple(c for c in CASES if c != "box")          # cases 1-3 of the query-order check
 
 
@@ -118,8 +140,18 @@ def queries(name):
 
 
 @functools.lru_cache(maxsize=None)
+def thin_queries():
+    """inside the box: the corner, the empty middle (the nearest target is three shells off, back for one query and on for the
+    other) and the far end; and one point outside the box beyond the thin axis, level with the corner"""
+    q = np.ascontiguousarray(np.float32([[0.25, 0.125, 0.5], [0.5, 1.5, 0.25], [0.125, 0.75, 3.5], [0.75, 1.25, 4.25], [0.5, 0.5, 7.5],
+                                         [3.0, 0.25, 0.125]]))
+    q.setflags(write=False)
+    return q
+
+
+@functools.lru_cache(maxsize=None)
 def point_ref(name):
-    return nr.nearest_points_ref(queries(name), points(name))
+    return nr.nearest_points_ref(thin_queries() if name == THIN else queries(name), points(name))
 
 
 @functools.lru_cache(maxsize=None)

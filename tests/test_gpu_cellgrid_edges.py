@@ -3,17 +3,22 @@ scan / fill (tests/cellgrid_edges_common.py; the cases and the references are he
 tests/test_cellgrid_edges_reference_cpu.py).  Public API only.
 
 Two edges carry the outlier filter: the end of the last cell comes from start[ncell], the entry behind the last chunk's scan, and
-the cell counts must be zero on entry in a scratch buffer that an earlier, larger call of another kind has left dirty.
+the cell counts must be zero on entry in a scratch buffer that an earlier, larger call of another kind has left dirty -- the
+filter, the searches, cloud normals and plane segmentation build their index by one routine (cell_index_build) and take turns on
+one context.  A third carries the shell walk they share (cell_shell_walk): the thin grid of cellgrid_edges_common.py, whose rows are
+one cell long and whose neighbours are seven shells off.
 
 The rules are those of the callers' own tests.  Means: test_gpu_sor.py's, 1e-12 relative and exactly 0 where the reference is 0
 (derived in that file's docstring).  Mask: the reference's, wherever no reference mean lies within 1e-9 of the threshold (asserted
 first; the triples where one does are dropped, at most one in four, and which they are is asserted on the CPU).  Nearest point:
 test_gpu_nearest.py's helper; every coordinate here is dyadic, so ties are exact and go to the smaller index.  Nearest triangle:
-that file's tolerance, 16 x EPS_TRI x the diagonal, a minimiser, and -- the case being dyadic -- exact zeros and the smallest index."""
+that file's tolerance, 16 x EPS_TRI x the diagonal, a minimiser, and -- the case being dyadic -- exact zeros and the smallest index.
+Normals: cloud_normals_common.check against its brute-force reference, whose neighbours are in (d^2, index) order."""
 import numpy as np
 import pytest
 
 import cellgrid_edges_common as cg
+import cloud_normals_common as cn
 import nearest_common as nc
 import sor_common as sc
 import tl3d
@@ -82,11 +87,18 @@ def _calls():
     """the reuse sequence: a large search that leaves the scratch dirty, then small calls of every kind"""
     dq, dt, dcell = cg.dirty_cloud()
     lf, pl = "last_full_1025", "plane"
+    up = np.tile(np.float32([0, 0, 1]), (len(cg.points(pl)), 1))
+
+    def planes(c):
+        ids, recs, counts = c.segment_planes(cg.points(pl), up, radius=1.5, max_offset=0.5, min_points=3, cell_size=cg.cell_size(pl))
+        return ids, np.frombuffer(recs.tobytes(), np.uint8), np.int64([counts[k] for k in ("eligible", "regions", "candidates", "planes")])
     return [
         ("dirty nearest_points", lambda c: c.nearest_points(dq, dt, cell_size=dcell)),
         ("last_full knn", lambda c: (c.knn_mean_distance(cg.points(lf), 20, cell_size=cg.cell_size(lf)),)),
+        ("line_1025 normals", lambda c: c.estimate_normals(cg.points("line_1025"), 20, cell_size=1.0, curvature=True)),
         ("plane nearest_triangles", lambda c: c.nearest_triangles(cg.queries(pl), cg.points(pl), cg.plane_triangles(), cell_size=cg.cell_size(pl))),
         ("line_1025 outlier", lambda c: (c.statistical_outlier(cg.points("line_1025"), 20, 2.0, cell_size=1.0),)),
+        ("plane planes", planes),
         ("last_full knn again", lambda c: (c.knn_mean_distance(cg.points(lf), 20, cell_size=cg.cell_size(lf)),)),
         # twice the cells of the call before it: its counts lie over the (non-zero) start table that call left behind
         ("line_2049 knn", lambda c: (c.knn_mean_distance(cg.points("line_2049"), 20, cell_size=1.0),)),
@@ -96,17 +108,41 @@ def _calls():
 def test_a_dirty_scratch_does_not_show():
     """every call of the sequence on ONE context gives, bit for bit, what the same call gives on a fresh context"""
     with _fresh() as one:
-        shared = [call(one) for _, call in _calls()]
-    for (what, call), got in zip(_calls(), shared):
+        shared = {what: call(one) for what, call in _calls()}
+    for what, call in _calls():
         with _fresh() as c:
             alone = call(c)
-        assert len(got) == len(alone)
-        for a, b in zip(got, alone):
-            assert a.dtype == b.dtype and np.array_equal(a, b), what
-    _assert_means(shared[1][0], cg.ref_means("last_full_1025", 20), "last_full_1025 behind the dirty call")
-    _assert_plane_triangles(shared[2], "plane behind the filter")
-    assert np.array_equal(shared[4][0], shared[1][0])
-    _assert_means(shared[5][0], cg.ref_means("line_2049", 20), "line_2049 over the last call's tables")
+        assert len(shared[what]) == len(alone)
+        for a, b in zip(shared[what], alone):
+            assert a.dtype == b.dtype and a.tobytes() == b.tobytes(), what
+    _assert_means(shared["last_full knn"][0], cg.ref_means("last_full_1025", 20), "last_full_1025 behind the dirty call")
+    _assert_plane_triangles(shared["plane nearest_triangles"], "plane behind the normals")
+    ids, _, counts = shared["plane planes"]
+    assert np.all(ids == 0) and list(counts) == [len(ids), 1, 1, 1]                    # the lattice is one region, and it is a plane
+    assert np.array_equal(shared["last_full knn again"][0], shared["last_full knn"][0])
+    _assert_means(shared["line_2049 knn"][0], cg.ref_means("line_2049", 20), "line_2049 over the last call's tables")
+
+
+# ---- the thin grid: 1 x 2 x 8 cells ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("k", cg.THIN_KS)
+def test_thin_grid_means_match_the_reference(ctx, k):
+    got = ctx.knn_mean_distance(cg.points(cg.THIN), k, cell_size=cg.cell_size(cg.THIN))
+    _assert_means(got, cg.ref_means(cg.THIN, k), f"thin k={k}")
+
+
+def test_thin_grid_normals_match_the_reference(ctx):
+    p, k = cg.points(cg.THIN), cg.THIN_K_NORMALS
+    r = cn.brute(p, k)
+    assert not r.degenerate.any() and not cn.excluded(r).any()             # on the reference first
+    n, c = ctx.estimate_normals(p, k, cell_size=cg.cell_size(cg.THIN), curvature=True)
+    assert ctx.last_normals_degenerate == 0
+    cn.check(n, c, r, False, f"thin k={k}")
+
+
+def test_thin_grid_nearest_points_match_the_reference(ctx):
+    q, t = cg.thin_queries(), cg.points(cg.THIN)
+    got = ctx.nearest_points(q, t, cell_size=cg.cell_size(cg.THIN))
+    _assert_points(q, t, got, cg.point_ref(cg.THIN), True, "thin")
 
 
 @pytest.mark.parametrize("name", cg.NEAREST_ORDER_CASES)

@@ -1,11 +1,93 @@
-// kernels_cellgrid.hip -- the host half of the uniform cell index (cellgrid.h): the grid of a cell size over a box, the count and
-// the two-level scan of the cell counts, and the scratch of the calls that use the index (the outlier filter, the nearest searches).
+// kernels_cellgrid.hip -- the host half of the uniform cell index (cellgrid.h): the finite bounds pass in front of every build, the
+// grid of a cell size over a box, the count and the two-level scan of the cell counts that cell_index_build launches, and the slab
+// of the calls that use the index (the outlier filter, the nearest searches, cloud normals, plane segmentation).
 #include <math.h>
+
+#include <algorithm>
+#include <vector>
 
 #include "cellgrid.h"
 
 namespace tl3d {
 
+static_assert((size_t)NN_RED * 128 <= CELL_SLAB_BYTES, "the block partials of every reduction of the index's callers fit the slab");
+
+// ---- validation and bounds -----------------------------------------------------------------------------------------------------
+// per block: min[3], max[3] over the finite points (f32), and the number of points with a non-finite coordinate (its bits in [6])
+__global__ __launch_bounds__(256) void nn_bounds_kernel(const float *__restrict__ xyz, long long n, float *__restrict__ slab) {
+    __shared__ float sm[4][7];
+    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    unsigned bad = 0;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
+        if (isfinite(x) && isfinite(y) && isfinite(z)) {
+            mn[0] = fminf(mn[0], x); mn[1] = fminf(mn[1], y); mn[2] = fminf(mn[2], z);
+            mx[0] = fmaxf(mx[0], x); mx[1] = fmaxf(mx[1], y); mx[2] = fmaxf(mx[2], z);
+        } else {
+            ++bad;
+        }
+    }
+    for (int d = 32; d > 0; d >>= 1) {
+        for (int a = 0; a < 3; ++a) {
+            mn[a] = fminf(mn[a], __shfl_down(mn[a], d));
+            mx[a] = fmaxf(mx[a], __shfl_down(mx[a], d));
+        }
+        bad += __shfl_down(bad, d);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        float *w = sm[threadIdx.x >> 6];
+        for (int a = 0; a < 3; ++a) { w[a] = mn[a]; w[3 + a] = mx[a]; }
+        w[6] = __uint_as_float(bad);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float *o = slab + 8 * (size_t)blockIdx.x;
+        unsigned b = 0;
+        for (int a = 0; a < 3; ++a) {
+            o[a] = fminf(fminf(sm[0][a], sm[1][a]), fminf(sm[2][a], sm[3][a]));
+            o[3 + a] = fmaxf(fmaxf(sm[0][3 + a], sm[1][3 + a]), fmaxf(sm[2][3 + a], sm[3][3 + a]));
+        }
+        for (int w = 0; w < 4; ++w) b += __float_as_uint(sm[w][6]);
+        o[6] = __uint_as_float(b);
+        o[7] = 0.0f;
+    }
+}
+
+unsigned nn_red_blocks(long long n) { return (unsigned)std::max(1ll, std::min((long long)NN_RED, (n + 255) / 256)); }
+
+void nn_bounds_launch(hipStream_t s, const float *xyz, long long n, float *slab) {
+    hipLaunchKernelGGL(nn_bounds_kernel, dim3(nn_red_blocks(n)), dim3(256), 0, s, xyz, n, slab);
+}
+unsigned long long nn_bounds_fold(const float *h, long long n, double mn[3], double mx[3]) {
+    unsigned long long bad = 0;
+    for (int a = 0; a < 3; ++a) { mn[a] = INFINITY; mx[a] = -INFINITY; }
+    for (unsigned b = 0; b < nn_red_blocks(n); ++b) {
+        for (int a = 0; a < 3; ++a) {
+            mn[a] = fmin(mn[a], (double)h[8 * b + a]);
+            mx[a] = fmax(mx[a], (double)h[8 * b + 3 + a]);
+        }
+        unsigned w;
+        memcpy(&w, h + 8 * b + 6, 4);
+        bad += w;
+    }
+    return bad;
+}
+
+int points_bounds_finite(tl3d_ctx *ctx, const float *xyz, long long n, double mn[3], double mx[3], unsigned long long *bad) {
+    hipStream_t s = ctx->stream;
+    const int rc = cell_slab(ctx);
+    if (rc) return rc;
+    float *slab = (float *)ctx->cg_slab;
+    std::vector<float> h((size_t)NN_RED * 8);
+    nn_bounds_launch(s, xyz, n, slab);
+    TL3D_HIP(hipGetLastError());
+    TL3D_HIP(hipMemcpyAsync(h.data(), slab, h.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+    TL3D_HIP(hipStreamSynchronize(s));
+    *bad = nn_bounds_fold(h.data(), n, mn, mx);
+    return TL3D_OK;
+}
+
+// ---- count and scan ------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void cell_count_kernel(CellGrid g, const float *__restrict__ xyz, long long n, unsigned *__restrict__ cnt) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;

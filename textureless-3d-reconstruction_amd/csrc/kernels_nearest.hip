@@ -4,21 +4,15 @@
 // the reference never scores a cloud; the definitions are those of Open3D's compute_point_cloud_distance and of the Chamfer / F-score
 // literature.
 //
-// The target is counting-sorted into the uniform cell index of cellgrid.h over its own box (the original index rides beside each
-// sorted point; a triangle goes into every cell its box overlaps: nn_tri_bin_kernel).  A query scans the cells around
-// its CLAMPED cell in shells of growing Chebyshev radius.  Two things differ from the filter's k-NN:
+// The target is counting-sorted into the uniform cell index of cellgrid.h over its own box (cell_index_build; the original index rides
+// beside each sorted point; a triangle goes into every cell its box overlaps: nn_tri_bin_kernel counts and fills in place of the
+// build's count and fill, over the same tables and scan).  A query walks the shells of growing Chebyshev radius around its CLAMPED
+// cell (cell_shell_walk).  Two things differ from the filter's k-NN:
 //   * the winner is the minimum over the PAIR (d2, index), so neither the fill order inside a cell (atomics) nor the order in which
 //     cells are met shows in the result, and an exact tie goes to the smaller index;
-//   * the stop rule.  A query may lie outside the grid (a millimetre or a hundred diagonals), so "r cells scanned = r * cell
-//     cleared" is false.  After shell r the unscanned cells lie beyond the OPEN faces of the scanned cube (faces with grid cells
-//     behind them).  Whatever lies beyond the open face of axis a is at least gap_a away along a (query's own coordinate to the face
-//     plane) and, being in the grid, at least box_b and box_c away along the other two (query's distance to the grid's extent on that
-//     axis; 0 inside).  bound2 = min over open faces of gap_a^2 + box_b^2 + box_c^2; the search ends when no face is open, when
-//     best2 < bound2 (strictly: a tie further out may have the smaller index), or when bound2 > max_dist^2.
-// All of it in cell units u = (x - origin) * inv_cell, evaluated by ONE expression (cell_u, cellgrid.h) for targets, triangle corners
-// and queries: it is monotone in x, so "binned beyond the face" implies u beyond the face exactly; turning cell units back into
-// metres costs at most 4 roundings (2^-53 each, relative to the larger |u|), which NN_SLACK = 1e-15 (4.5 of them) pays for: every
-// bound is shrunk by it, which can only make a search look one shell further.
+//   * the stop rule.  A query may lie outside the grid, so the search ends on the bound of cellgrid.h (cell_face_bound, derived
+//     there): when no face is open, when best2 < bound2 (strictly: a tie further out may have the smaller index), or when
+//     bound2 > max_dist^2.
 #include <math.h>
 
 #include <vector>
@@ -28,52 +22,9 @@
 
 namespace tl3d {
 
-constexpr double NN_SLACK = 1e-15;
-constexpr int NN_RED = 1024;            // blocks of the reductions (fixed: the partial sums do not depend on the device)
-static_assert((size_t)NN_RED * 128 <= CELL_SLAB_BYTES, "the block partials of every reduction here fit the slab");
 constexpr int NN_LEVELS = 16;           // candidate cell sizes one triangle-pair count pass looks at (cell * 2^j)
 
-// ---- validation and bounds -----------------------------------------------------------------------------------------------------
-// per block: min[3], max[3] over the finite points (f32), and the number of points with a non-finite coordinate (its bits in [6])
-__global__ __launch_bounds__(256) void nn_bounds_kernel(const float *__restrict__ xyz, long long n, float *__restrict__ slab) {
-    __shared__ float sm[4][7];
-    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    unsigned bad = 0;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
-        if (isfinite(x) && isfinite(y) && isfinite(z)) {
-            mn[0] = fminf(mn[0], x); mn[1] = fminf(mn[1], y); mn[2] = fminf(mn[2], z);
-            mx[0] = fmaxf(mx[0], x); mx[1] = fmaxf(mx[1], y); mx[2] = fmaxf(mx[2], z);
-        } else {
-            ++bad;
-        }
-    }
-    for (int d = 32; d > 0; d >>= 1) {
-        for (int a = 0; a < 3; ++a) {
-            mn[a] = fminf(mn[a], __shfl_down(mn[a], d));
-            mx[a] = fmaxf(mx[a], __shfl_down(mx[a], d));
-        }
-        bad += __shfl_down(bad, d);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        float *w = sm[threadIdx.x >> 6];
-        for (int a = 0; a < 3; ++a) { w[a] = mn[a]; w[3 + a] = mx[a]; }
-        w[6] = __uint_as_float(bad);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float *o = slab + 8 * (size_t)blockIdx.x;
-        unsigned b = 0;
-        for (int a = 0; a < 3; ++a) {
-            o[a] = fminf(fminf(sm[0][a], sm[1][a]), fminf(sm[2][a], sm[3][a]));
-            o[3 + a] = fmaxf(fmaxf(sm[0][3 + a], sm[1][3 + a]), fmaxf(sm[2][3 + a], sm[3][3 + a]));
-        }
-        for (int w = 0; w < 4; ++w) b += __float_as_uint(sm[w][6]);
-        o[6] = __uint_as_float(b);
-        o[7] = 0.0f;
-    }
-}
-
+// ---- validation -----------------------------------------------------------------------------------------------------------------
 // per block: [0] the sum of the triangles' largest box extents (what the default cell is taken from; only the cell depends on it),
 // [1] the number of triangles with an index >= n_vert.  An index is compared before it is used.
 __global__ __launch_bounds__(256) void nn_tri_stats_kernel(const float *__restrict__ xyz, long long n_vert, const unsigned *__restrict__ tri,
@@ -225,11 +176,6 @@ struct NnTriEval {
     }
 };
 
-// metres that v cell units are worth at least (see the head of the file); um: the largest |u| involved
-__device__ __forceinline__ double nn_lower(double v, double um, double cell) {
-    return fmax(0.0, v * cell * (1.0 - NN_SLACK) - NN_SLACK * cell * um);
-}
-
 // order == nullptr: thread i serves query i; else query order[i] (queries bucketed by cell: a wave's lanes walk the same cells)
 template <class Eval>
 __global__ __launch_bounds__(256) void nn_search_kernel(CellGrid g, const float *__restrict__ query, long long nq, const unsigned *__restrict__ order,
@@ -246,40 +192,18 @@ __global__ __launch_bounds__(256) void nn_search_kernel(CellGrid g, const float 
     const double nmax = (double)max(g.nx, max(g.ny, g.nz)) + 1.0;
     for (int a = 0; a < 3; ++a) {
         c[a] = cell_clampi(u[a], n[a]);
-        const double b = nn_lower(fmax(0.0, fmax(-u[a], u[a] - (double)n[a])), nmax + fabs(u[a]), g.cell);
+        const double b = cell_lower(fmax(0.0, fmax(-u[a], u[a] - (double)n[a])), nmax + fabs(u[a]), g.cell);
         box2[a] = b * b;
     }
     const double md2 = max_dist > 0.0 ? max_dist * max_dist : INFINITY;
     NnBest best = {INFINITY, 0x7fffffff};
     for (int r = 0;; ++r) {
-        const int x0 = max(0, c[0] - r), x1 = min(g.nx - 1, c[0] + r);
-        const int y0 = max(0, c[1] - r), y1 = min(g.ny - 1, c[1] + r);
-        const int z0 = max(0, c[2] - r), z1 = min(g.nz - 1, c[2] + r);
-        for (int z = z0; z <= z1; ++z)
-            for (int y = y0; y <= y1; ++y) {
-                const long long row = ((long long)z * g.ny + y) * g.nx;
-                if (z == c[2] - r || z == c[2] + r || y == c[1] - r || y == c[1] + r) {
-                    eval(start[row + x0], start[row + x1 + 1], p[0], p[1], p[2], best);      // a row's cells are one run of the sorted list
-                } else {                                                                      // interior rows: only the two end cells
-                    if (c[0] - r >= 0) eval(start[row + c[0] - r], start[row + c[0] - r + 1], p[0], p[1], p[2], best);
-                    if (c[0] + r < g.nx) eval(start[row + c[0] + r], start[row + c[0] + r + 1], p[0], p[1], p[2], best);
-                }
-            }
+        cell_shell_walk(g, start, c[0], c[1], c[2], r, [&](unsigned s, unsigned e) { eval(s, e, p[0], p[1], p[2], best); });
         double bound2 = INFINITY;
         bool open = false;
-        for (int a = 0; a < 3; ++a) {
-            const double other = box2[(a + 1) % 3] + box2[(a + 2) % 3];
-            if (c[a] - r > 0) {                            // cells below c - r: u < c - r
-                const double gap = nn_lower(u[a] - (double)(c[a] - r), nmax + fabs(u[a]), g.cell);
-                bound2 = fmin(bound2, gap * gap + other);
-                open = true;
-            }
-            if (c[a] + r < n[a] - 1) {                     // cells above c + r: u >= c + r + 1
-                const double gap = nn_lower((double)(c[a] + r + 1) - u[a], nmax + fabs(u[a]), g.cell);
-                bound2 = fmin(bound2, gap * gap + other);
-                open = true;
-            }
-        }
+        cell_face_bound(u[0], c[0], r, g.nx, nmax, g.cell, box2[1] + box2[2], bound2, open);
+        cell_face_bound(u[1], c[1], r, g.ny, nmax, g.cell, box2[2] + box2[0], bound2, open);
+        cell_face_bound(u[2], c[2], r, g.nz, nmax, g.cell, box2[0] + box2[1], bound2, open);
         if (!open || best.d2 < bound2 || bound2 > md2) break;
     }
     double d = sqrt(best.d2);
@@ -345,43 +269,6 @@ __global__ __launch_bounds__(256) void nn_summary_kernel(const double *__restric
         if (e__ != hipSuccess) return set_err(TL3D_E_HIP, "%s failed: %s", #x, hipGetErrorString(e__)); \
     } while (0)
 
-static unsigned nn_red_blocks(long long n) { return (unsigned)std::max(1ll, std::min((long long)NN_RED, (n + 255) / 256)); }
-
-// bounds of a point list and the number of its non-finite points: one launch; the caller reads the slab
-static void nn_bounds_launch(hipStream_t s, const float *xyz, long long n, float *slab) {
-    hipLaunchKernelGGL(nn_bounds_kernel, dim3(nn_red_blocks(n)), dim3(256), 0, s, xyz, n, slab);
-}
-static unsigned long long nn_bounds_fold(const float *h, long long n, double mn[3], double mx[3]) {
-    unsigned long long bad = 0;
-    for (int a = 0; a < 3; ++a) { mn[a] = INFINITY; mx[a] = -INFINITY; }
-    for (unsigned b = 0; b < nn_red_blocks(n); ++b) {
-        for (int a = 0; a < 3; ++a) {
-            mn[a] = fmin(mn[a], (double)h[8 * b + a]);
-            mx[a] = fmax(mx[a], (double)h[8 * b + 3 + a]);
-        }
-        unsigned w;
-        memcpy(&w, h + 8 * b + 6, 4);
-        bad += w;
-    }
-    return bad;
-}
-
-// the same pass for a caller outside this file (kernels_normals.hip): the box of the finite points of a device list and the number
-// of points with a non-finite coordinate
-int points_bounds_finite(tl3d_ctx *ctx, const float *xyz, long long n, double mn[3], double mx[3], unsigned long long *bad) {
-    hipStream_t s = ctx->stream;
-    const int rc = cell_slab(ctx);
-    if (rc) return rc;
-    float *slab = (float *)ctx->cg_slab;
-    std::vector<float> h((size_t)NN_RED * 8);
-    nn_bounds_launch(s, xyz, n, slab);
-    NN_HIP(hipGetLastError());
-    NN_HIP(hipMemcpyAsync(h.data(), slab, h.size() * sizeof(float), hipMemcpyDeviceToHost, s));
-    NN_HIP(hipStreamSynchronize(s));
-    *bad = nn_bounds_fold(h.data(), n, mn, mx);
-    return TL3D_OK;
-}
-
 // Default cell of a point target: the box has V = the product of its non-zero extents (k of them) and n points; cell = (V / (4 n))^(1/k),
 // i.e. four cells per point if the points filled the box -- surface clouds fill a thin sheet of it, and end near ten points per
 // occupied cell.  A box without extent is one cell.
@@ -395,43 +282,42 @@ static double nn_default_cell_points(const double mn[3], const double mx[3], lon
     return (c > 0.0 && isfinite(c)) ? c : 1.0;
 }
 
-// A search's scratch, carved from the context's buffer: the cell tables of the target and of the queries (one cnt serves both, see
-// cellgrid.h), the scan's chunk sums and offsets, the target's payload behind the cells (P: float4 points, or triangle indices)
-// and the query order.
+// A search's scratch, carved from the context's buffer: the target's cell tables, the queries' start table over the same cnt, the
+// target's payload behind the cells (P: float4 points, or triangle indices) and the query order.
 template <class P> struct NnScratch {
-    unsigned *cnt, *t_start, *q_start, *chunk_sums;
-    unsigned long long *chunk_off;
+    CellTables t;
+    unsigned *q_start;
     P *payload;
     unsigned *order;
 };
 template <class P> static int nn_scratch(tl3d_ctx *ctx, long long ncell, size_t n_payload, long long nq, NnScratch<P> *sc) {
-    const size_t nchunks = cell_chunks(ncell);
-    const size_t bytes[7] = {(size_t)ncell * sizeof(unsigned), (size_t)(ncell + 1) * sizeof(unsigned), (size_t)(ncell + 1) * sizeof(unsigned),
-                             nchunks * sizeof(unsigned), (nchunks + 1) * sizeof(unsigned long long), n_payload * sizeof(P),
-                             (size_t)nq * sizeof(unsigned)};
+    size_t bytes[7];
+    cell_table_bytes(ncell, bytes);
+    bytes[4] = (size_t)(ncell + 1) * sizeof(unsigned);
+    bytes[5] = n_payload * sizeof(P);
+    bytes[6] = (size_t)nq * sizeof(unsigned);
     void *p[7];
     const int rc = scratch_carve(ctx, 0, bytes, 7, p, "nearest-neighbour scratch");
     if (rc) return rc;
-    *sc = {(unsigned *)p[0], (unsigned *)p[1], (unsigned *)p[2], (unsigned *)p[3], (unsigned long long *)p[4], (P *)p[5], (unsigned *)p[6]};
+    *sc = {CellTables::at(p), (unsigned *)p[4], (P *)p[5], (unsigned *)p[6]};
     return TL3D_OK;
 }
 
-// the queries bucketed into the target's grid (unless the context runs them in input order), then the search; sc.cnt: all zero
+// the queries bucketed into the target's grid (unless the context runs them in input order), then the search
 template <class P, class Eval>
 static int nn_search(tl3d_ctx *ctx, const CellGrid &g, const float *query, long long nq, const NnScratch<P> &sc, const Eval &eval, double max_dist,
                      double *dist, int *index) {
     hipStream_t s = ctx->stream;
     const unsigned nb = (unsigned)((nq + 255) / 256);
-    const long long ncell = (long long)g.nx * g.ny * g.nz;
     const unsigned *ord = nullptr;
-    if (!ctx->nn_input_order) {            // (the target's fill counted cnt down to zero again)
-        launch_cell_count(s, g, query, nq, sc.cnt);
-        const int rc = launch_cell_scan(s, sc.cnt, ncell, sc.chunk_sums, sc.chunk_off, sc.q_start);
+    if (!ctx->nn_input_order) {            // a second build over the target's cnt, which its fill counted down to zero again
+        CellTables q = sc.t;
+        q.start = sc.q_start;
+        const int rc = cell_index_build(s, g, query, nq, q, false, EmitIndex{sc.order});
         if (rc) return rc;
-        launch_cell_fill(s, g, query, nq, sc.q_start, sc.cnt, EmitIndex{sc.order});
         ord = sc.order;
     }
-    hipLaunchKernelGGL(nn_search_kernel<Eval>, dim3(nb), dim3(256), 0, s, g, query, nq, ord, sc.t_start, eval, max_dist, dist, index);
+    hipLaunchKernelGGL(nn_search_kernel<Eval>, dim3(nb), dim3(256), 0, s, g, query, nq, ord, sc.t.start, eval, max_dist, dist, index);
     NN_HIP(hipGetLastError());
     return TL3D_OK;
 }
@@ -464,15 +350,11 @@ int nearest_points_run(tl3d_ctx *ctx, const float *query, long long nq, const fl
     if (!(cell > 0.0)) cell = nn_default_cell_points(mn, mx, nt);
     CellGrid g;
     cell_grid_fit(mn, mx, cell, &g);
-    const long long ncell = (long long)g.nx * g.ny * g.nz;
     NnScratch<float4> sc;
-    rc = nn_scratch(ctx, ncell, (size_t)nt, nq, &sc);
+    rc = nn_scratch(ctx, cell_grid_cells(g), (size_t)nt, nq, &sc);
     if (rc) return rc;
-    NN_HIP(hipMemsetAsync(sc.cnt, 0, ncell * sizeof(unsigned), s));
-    launch_cell_count(s, g, target, nt, sc.cnt);
-    rc = launch_cell_scan(s, sc.cnt, ncell, sc.chunk_sums, sc.chunk_off, sc.t_start);
+    rc = cell_index_build(s, g, target, nt, sc.t, true, EmitPointIndex{sc.payload});
     if (rc) return rc;
-    launch_cell_fill(s, g, target, nt, sc.t_start, sc.cnt, EmitPointIndex{sc.payload});
     const NnPointEval pe = {sc.payload};
     return nn_search(ctx, g, query, nq, sc, pe, max_dist, dist, index);
 }
@@ -537,15 +419,16 @@ int nearest_triangles_run(tl3d_ctx *ctx, const float *query, long long nq, const
             if (ok[j] && got[j] <= cap) { g = lv.g[j]; npairs = got[j]; found = true; }
         cell = ldexp(cell, NN_LEVELS);
     }
-    const long long ncell = (long long)g.nx * g.ny * g.nz;
+    const long long ncell = cell_grid_cells(g);
     NnScratch<unsigned> sc;
     rc = nn_scratch(ctx, ncell, (size_t)npairs, nq, &sc);
     if (rc) return rc;
-    NN_HIP(hipMemsetAsync(sc.cnt, 0, ncell * sizeof(unsigned), s));
-    hipLaunchKernelGGL(nn_tri_bin_kernel, dim3(ntb), dim3(256), 0, s, g, xyz, tri, n_tri, (const unsigned *)nullptr, sc.cnt, (unsigned *)nullptr);
-    rc = launch_cell_scan(s, sc.cnt, ncell, sc.chunk_sums, sc.chunk_off, sc.t_start);
+    // cell_index_build's sequence with nn_tri_bin_kernel as count and fill: a triangle goes into every cell of its box
+    NN_HIP(hipMemsetAsync(sc.t.cnt, 0, ncell * sizeof(unsigned), s));
+    hipLaunchKernelGGL(nn_tri_bin_kernel, dim3(ntb), dim3(256), 0, s, g, xyz, tri, n_tri, (const unsigned *)nullptr, sc.t.cnt, (unsigned *)nullptr);
+    rc = launch_cell_scan(s, sc.t.cnt, ncell, sc.t.chunk_sums, sc.t.chunk_off, sc.t.start);
     if (rc) return rc;
-    hipLaunchKernelGGL(nn_tri_bin_kernel, dim3(ntb), dim3(256), 0, s, g, xyz, tri, n_tri, (const unsigned *)sc.t_start, sc.cnt, sc.payload);
+    hipLaunchKernelGGL(nn_tri_bin_kernel, dim3(ntb), dim3(256), 0, s, g, xyz, tri, n_tri, (const unsigned *)sc.t.start, sc.t.cnt, sc.payload);
     const NnTriEval te = {sc.payload, xyz, tri};
     return nn_search(ctx, g, query, nq, sc, te, max_dist, dist, index);
 }

@@ -2,17 +2,16 @@
 // section 4.5; tl3d_estimate_normals in tl3d.h has the definition).  No reference code: the reference writes positions and colours
 // only; the definition is the one of Open3D's estimate_normals + orient_normals_towards_camera_location and of PCL's surface variation.
 //
-// The points are counting-sorted into the uniform cell index of cellgrid.h over their own box, as float4 with the original index
-// beside the point.  Thread t serves the point in slot t of that sorted list, so the lanes of a wave are neighbours in space and walk
-// the same few cells; the result is scattered back by the original index.  (The sorted list IS the cell order of the queries: the
-// second count / scan / fill that the searches of kernels_nearest.hip need for a foreign query set has nothing to add here.)
-//   search   shells of growing Chebyshev radius around the point's cell, a row of cells read as one run, as nn_search_kernel does.
-//            The k best (d2, index) pairs live in registers (ordered insert over static indices, as sor_knn_kernel's list); the order
-//            is the PAIR's, so neither the fill order inside a cell (atomics) nor the cell size shows in which points are kept or in
-//            the order they are summed in.  The search ends when no face of the scanned cube has cells behind it, when the k-th pair's
-//            d2 lies strictly under the bound of everything unscanned (a tie further out may have the smaller index), or when that
-//            bound exceeds max_radius^2.  The bound is nn_search_kernel's with the query inside the grid: the smallest distance, in
-//            cell units, from the point to an open face, turned into metres with NN_SLACK taken off.
+// The points are counting-sorted into the uniform cell index of cellgrid.h over their own box (cell_index_build), as float4 with the
+// original index beside the point.  Thread t serves the point in slot t of that sorted list, so the lanes of a wave are neighbours in
+// space and walk the same few cells; the result is scattered back by the original index.  (The sorted list IS the cell order of the
+// queries: the second build that the searches of kernels_nearest.hip need for a foreign query set has nothing to add here.)
+//   search   the shells of growing Chebyshev radius around the point's cell (cell_shell_walk).  The k best (d2, index) pairs live in
+//            registers (ordered insert over static indices, as sor_knn_kernel's list); the order is the PAIR's, so neither the fill
+//            order inside a cell (atomics) nor the cell size shows in which points are kept or in the order they are summed in.  The
+//            search ends when no face of the walked cube has cells behind it, when the k-th pair's d2 lies strictly under the bound
+//            of everything not yet walked (a tie further out may have the smaller index), or when that bound exceeds max_radius^2.
+//            The bound is cell_face_bound's (cellgrid.h) for a point inside the grid: the other axes add nothing.
 //   PCA      e_j = p_j - p_i fetched again by index (twice: mean, then centred products; the list cannot hold 64 points beside the
 //            pairs), all in fp64 in list order; sym3_eigen.h solves the 3x3.
 //   sign     the viewpoints pass through LDS in chunks of 256; nearest by (d2, index); n . (c - p) < 0 negates.
@@ -24,27 +23,7 @@
 
 namespace tl3d {
 
-constexpr double NRM_SLACK = 1e-15;     // NN_SLACK of kernels_nearest.hip: pays for turning cell units back into metres
 constexpr int NRM_VP_CHUNK = 256;       // viewpoints per LDS chunk (one per thread of the block: 6 KB)
-
-__device__ __forceinline__ double nrm_lower(double v, double um, double cell) {
-    return fmax(0.0, v * cell * (1.0 - NRM_SLACK) - NRM_SLACK * cell * um);
-}
-
-// One axis of the stop rule: what lies beyond the open faces of the scanned cube [c - r, c + r] on this axis is at least `gap` away
-// (u: the point's coordinate in cell units, n: cells on the axis).  Scalars, not arrays indexed by axis: those went to scratch.
-__device__ __forceinline__ void nrm_face_bound(double u, int c, int r, int n, double nmax, double cell, double &bound2, bool &open) {
-    if (c - r > 0) {                                       // cells below c - r: u < c - r
-        const double gap = nrm_lower(u - (double)(c - r), nmax + fabs(u), cell);
-        bound2 = fmin(bound2, gap * gap);
-        open = true;
-    }
-    if (c + r < n - 1) {                                   // cells above c + r: u >= c + r + 1
-        const double gap = nrm_lower((double)(c + r + 1) - u, nmax + fabs(u), cell);
-        bound2 = fmin(bound2, gap * gap);
-        open = true;
-    }
-}
 
 // (a, ai) < (b, bi) in the order (d2, index)
 __device__ __forceinline__ bool nrm_less(double a, int ai, double b, int bi) { return a < b || (a == b && ai < bi); }
@@ -71,48 +50,31 @@ __global__ __launch_bounds__(256) void normals_kernel(CellGrid g, const float *_
         const int c0 = cell_clampi(u0, g.nx), c1 = cell_clampi(u1, g.ny), c2 = cell_clampi(u2, g.nz);
         const double nmax = (double)max(g.nx, max(g.ny, g.nz)) + 1.0;
         for (int r = 0;; ++r) {
-            const int x0 = max(0, c0 - r), x1 = min(g.nx - 1, c0 + r);
-            const int y0 = max(0, c1 - r), y1 = min(g.ny - 1, c1 + r);
-            const int z0 = max(0, c2 - r), z1 = min(g.nz - 1, c2 + r);
-            for (int z = z0; z <= z1; ++z)
-                for (int y = y0; y <= y1; ++y) {
-                    const long long row = ((long long)z * g.ny + y) * g.nx;
-                    const bool face = z == c2 - r || z == c2 + r || y == c1 - r || y == c1 + r;
-                    // a face row: its cells are one run of the sorted list; an interior row: its two end cells, one after the other
-                    for (int part = 0; part < (face ? 1 : 2); ++part) {
-                        unsigned s, e;
-                        if (face) {
-                            s = start[row + x0]; e = start[row + x1 + 1];
-                        } else {
-                            const int x = part == 0 ? c0 - r : c0 + r;
-                            if (x < 0 || x >= g.nx) continue;
-                            s = start[row + x]; e = start[row + x + 1];
-                        }
-                        for (unsigned q = s; q < e; ++q) {
-                            const float4 p = sorted[q];
-                            const double dx = (double)p.x - px, dy = (double)p.y - py, dz = (double)p.z - pz;
-                            double v = dx * dx + dy * dy + dz * dz;
-                            int vi = __float_as_int(p.w);
-                            if (nrm_less(v, vi, bd[KMAX - 1], bi[KMAX - 1])) {
+            cell_shell_walk(g, start, c0, c1, c2, r, [&](unsigned s, unsigned e) {
+                for (unsigned q = s; q < e; ++q) {
+                    const float4 p = sorted[q];
+                    const double dx = (double)p.x - px, dy = (double)p.y - py, dz = (double)p.z - pz;
+                    double v = dx * dx + dy * dy + dz * dz;
+                    int vi = __float_as_int(p.w);
+                    if (nrm_less(v, vi, bd[KMAX - 1], bi[KMAX - 1])) {
 #pragma unroll
-                                for (int j = 0; j < KMAX; ++j) {       // ordered insert, static indices -> registers
-                                    const double b = bd[j];
-                                    const int ib = bi[j];
-                                    const bool sw = nrm_less(v, vi, b, ib);
-                                    bd[j] = sw ? v : b;
-                                    bi[j] = sw ? vi : ib;
-                                    v = sw ? b : v;
-                                    vi = sw ? ib : vi;
-                                }
-                            }
+                        for (int j = 0; j < KMAX; ++j) {               // ordered insert, static indices -> registers
+                            const double b = bd[j];
+                            const int ib = bi[j];
+                            const bool sw = nrm_less(v, vi, b, ib);
+                            bd[j] = sw ? v : b;
+                            bi[j] = sw ? vi : ib;
+                            v = sw ? b : v;
+                            vi = sw ? ib : vi;
                         }
                     }
                 }
+            });
             double bound2 = INFINITY;
             bool open = false;
-            nrm_face_bound(u0, c0, r, g.nx, nmax, g.cell, bound2, open);
-            nrm_face_bound(u1, c1, r, g.ny, nmax, g.cell, bound2, open);
-            nrm_face_bound(u2, c2, r, g.nz, nmax, g.cell, bound2, open);
+            cell_face_bound(u0, c0, r, g.nx, nmax, g.cell, 0.0, bound2, open);
+            cell_face_bound(u1, c1, r, g.ny, nmax, g.cell, 0.0, bound2, open);
+            cell_face_bound(u2, c2, r, g.nz, nmax, g.cell, 0.0, bound2, open);
             double kth = INFINITY;
 #pragma unroll
             for (int j = 0; j < KMAX; ++j)
@@ -201,25 +163,23 @@ int normals_run(tl3d_ctx *ctx, const float *xyz, long long n, int k, double max_
     if (bad) return set_err(TL3D_E_INVALID, "%llu points have a non-finite coordinate", bad);
     CellGrid g;
     cell_grid_fit(mn, mx, cell, &g);
-    const long long ncell = (long long)g.nx * g.ny * g.nz;
-    const size_t nchunks = cell_chunks(ncell);
-    const size_t bytes[7] = {(size_t)ncell * sizeof(unsigned), (size_t)(ncell + 1) * sizeof(unsigned), nchunks * sizeof(unsigned),
-                             (nchunks + 1) * sizeof(unsigned long long), (size_t)n * sizeof(float4), (size_t)n_vp * 3 * sizeof(double),
-                             sizeof(unsigned long long)};
+    size_t bytes[7];
+    cell_table_bytes(cell_grid_cells(g), bytes);
+    bytes[4] = (size_t)n * sizeof(float4);
+    bytes[5] = (size_t)n_vp * 3 * sizeof(double);
+    bytes[6] = sizeof(unsigned long long);
     void *p[7];
     rc = scratch_carve(ctx, 0, bytes, 7, p, "normal estimation scratch");
     if (rc) return rc;
-    unsigned *cnt = (unsigned *)p[0], *start = (unsigned *)p[1], *chunk_sums = (unsigned *)p[2];
-    unsigned long long *chunk_off = (unsigned long long *)p[3], *n_deg = (unsigned long long *)p[6];
+    const CellTables t = CellTables::at(p);
+    const unsigned *start = t.start;
     float4 *sorted = (float4 *)p[4];
     double *vp = (double *)p[5];
-    TL3D_HIP(hipMemsetAsync(cnt, 0, (size_t)ncell * sizeof(unsigned), s));
+    unsigned long long *n_deg = (unsigned long long *)p[6];
     TL3D_HIP(hipMemsetAsync(n_deg, 0, sizeof(unsigned long long), s));
     if (n_vp) TL3D_HIP(hipMemcpyAsync(vp, vp_host, (size_t)n_vp * 3 * sizeof(double), hipMemcpyHostToDevice, s));
-    launch_cell_count(s, g, xyz, n, cnt);
-    rc = launch_cell_scan(s, cnt, ncell, chunk_sums, chunk_off, start);
+    rc = cell_index_build(s, g, xyz, n, t, true, EmitPointIndex{sorted});
     if (rc) return rc;
-    launch_cell_fill(s, g, xyz, n, start, cnt, EmitPointIndex{sorted});
     const unsigned nb = (unsigned)((n + 255) / 256);
     const double md2 = max_radius > 0.0 ? max_radius * max_radius : INFINITY;
     if (k <= 32)

@@ -6,8 +6,8 @@
 // towards the smaller root, add) commute, the moments are exact integers, and the compactions write at scanned offsets.
 //
 // Passes, each its own launch on the context's stream (kernel boundaries are the ONLY ordering between them; I5 of unionfind.h):
-//   bounds      points_bounds_finite; the host refuses a non-finite coordinate, |x| >= 2^22, and a box too wide for the 64-bit sums
-//   index       the cell index of cellgrid.h over all points; the fill leaves in slot order the point with its original index and,
+//   bounds      points_bounds_finite (kernels_cellgrid.hip); the host refuses a non-finite coordinate, |x| >= 2^22, and a box too wide for the 64-bit sums
+//   index       the cell index of cellgrid.h over all points (cell_index_build); the fill leaves in slot order the point with its original index and,
 //               beside it, its normal with the eligibility flag in w (an ineligible point is indexed and skipped by its flag)
 //   init        parent[i] = i, count[i] = 0
 //   link        one thread per sorted slot (the lanes of a wave are neighbours in space and walk the same runs); the rows of cells
@@ -466,36 +466,32 @@ int planes_run(tl3d_ctx *ctx, const float *xyz, const float *nrm, const float *c
         return set_err(TL3D_E_INVALID, "%lld points over %g m: plane segmentation needs n * (extent * 2^20 + 1) < 2^62", n, ext);
     CellGrid g;
     cell_grid_fit(mn, mx, cell, &g);
-    const long long ncell = (long long)g.nx * g.ny * g.nz;
-    const size_t nchunks = cell_chunks(ncell);
     const size_t maxc = (size_t)(n / prm.min_points);                  // candidates have min_points points of their own each
     const size_t pchunks = (size_t)chunks_of((unsigned long long)n), cchunks = (size_t)chunks_of(maxc);
     const size_t outc = std::min((size_t)plane_cap, maxc);
-    const size_t bytes[20] = {(size_t)ncell * sizeof(unsigned),        // 0 cnt         memset; zero again behind the fill
-                              (size_t)(ncell + 1) * sizeof(unsigned),  // 1 start       the scan
-                              nchunks * sizeof(unsigned),              // 2 chunk sums  the scan
-                              (nchunks + 1) * sizeof(pl_u64),          // 3 chunk offs  the scan
-                              (size_t)n * sizeof(float4),              // 4 sorted      the fill, every slot
-                              (size_t)n * sizeof(float4),              // 5 snrm        the fill, every slot
-                              (size_t)n * sizeof(unsigned),            // 6 parent      init
-                              (size_t)n * sizeof(unsigned),            // 7 count       init
-                              (size_t)n * sizeof(unsigned),            // 8 cand_id     candidate roots only; read at candidate roots only
-                              (pchunks + 1) * sizeof(unsigned),        // 9 point chunk counts
-                              (pchunks + 1) * sizeof(pl_u64),          // 10 point chunk offsets and the total behind them
-                              maxc * sizeof(unsigned),                 // 11 cand_seed
-                              maxc * PL_REC * sizeof(pl_u64),          // 12 records    memset for the candidates there are
-                              maxc * sizeof(tl3d_plane),               // 13 tmp planes planes kernel, every candidate
-                              maxc * sizeof(unsigned),                 // 14 accept     planes kernel, every candidate
-                              maxc * sizeof(int),                      // 15 cand_plane accepted write, every candidate
-                              (cchunks + 1) * sizeof(unsigned),        // 16 candidate chunk counts
-                              (cchunks + 1) * sizeof(pl_u64),          // 17 candidate chunk offsets and the total
-                              outc * sizeof(tl3d_plane),               // 18 the records on their way out
-                              8 * sizeof(pl_u64)};                     // 19 info       memset
+    size_t bytes[20] = {0, 0, 0, 0,                              // 0-3 the index's tables (cell_table_bytes, below)
+                        (size_t)n * sizeof(float4),              // 4 sorted      the fill, every slot
+                        (size_t)n * sizeof(float4),              // 5 snrm        the fill, every slot
+                        (size_t)n * sizeof(unsigned),            // 6 parent      init
+                        (size_t)n * sizeof(unsigned),            // 7 count       init
+                        (size_t)n * sizeof(unsigned),            // 8 cand_id     candidate roots only; read at candidate roots only
+                        (pchunks + 1) * sizeof(unsigned),        // 9 point chunk counts
+                        (pchunks + 1) * sizeof(pl_u64),          // 10 point chunk offsets and the total behind them
+                        maxc * sizeof(unsigned),                 // 11 cand_seed
+                        maxc * PL_REC * sizeof(pl_u64),          // 12 records    memset for the candidates there are
+                        maxc * sizeof(tl3d_plane),               // 13 tmp planes planes kernel, every candidate
+                        maxc * sizeof(unsigned),                 // 14 accept     planes kernel, every candidate
+                        maxc * sizeof(int),                      // 15 cand_plane accepted write, every candidate
+                        (cchunks + 1) * sizeof(unsigned),        // 16 candidate chunk counts
+                        (cchunks + 1) * sizeof(pl_u64),          // 17 candidate chunk offsets and the total
+                        outc * sizeof(tl3d_plane),               // 18 the records on their way out
+                        8 * sizeof(pl_u64)};                     // 19 info       memset
+    cell_table_bytes(cell_grid_cells(g), bytes);
     void *p[20];
     rc = scratch_carve(ctx, 0, bytes, 20, p, "plane segmentation scratch");
     if (rc) return rc;
-    unsigned *cnt = (unsigned *)p[0], *start = (unsigned *)p[1], *chunk_sums = (unsigned *)p[2];
-    pl_u64 *chunk_off = (pl_u64 *)p[3];
+    const CellTables t = CellTables::at(p);
+    const unsigned *start = t.start;
     float4 *sorted = (float4 *)p[4], *snrm = (float4 *)p[5];
     unsigned *parent = (unsigned *)p[6], *count = (unsigned *)p[7], *cand_id = (unsigned *)p[8], *pcounts = (unsigned *)p[9];
     pl_u64 *poffs = (pl_u64 *)p[10];
@@ -521,13 +517,9 @@ int planes_run(tl3d_ctx *ctx, const float *xyz, const float *nrm, const float *c
 
     PlTrace trace(s);
     trace.mark("start");
-    TL3D_HIP(hipMemsetAsync(cnt, 0, (size_t)ncell * sizeof(unsigned), s));
     TL3D_HIP(hipMemsetAsync(info, 0, 8 * sizeof(pl_u64), s));
-    launch_cell_count(s, g, xyz, n, cnt);
-    TL3D_HIP(hipGetLastError());
-    rc = launch_cell_scan(s, cnt, ncell, chunk_sums, chunk_off, start);
+    rc = cell_index_build(s, g, xyz, n, t, true, EmitPointNormal{sorted, snrm, nrm, use_curv ? curv : nullptr, prm.max_curvature});
     if (rc) return rc;
-    launch_cell_fill(s, g, xyz, n, start, cnt, EmitPointNormal{sorted, snrm, nrm, use_curv ? curv : nullptr, prm.max_curvature});
     TL3D_HIP(hipGetLastError());
     const unsigned nb = (unsigned)((n + 255) / 256), un = (unsigned)n;
     trace.mark("index");

@@ -4,9 +4,13 @@
 // KNN search returns it), mu / sigma (Bessel-corrected) of those means, keep  0 < mean < mu + ratio*sigma.
 // Restated in oracle/ref_numpy.py: statistical_outlier_open3d (Open3D itself: parity unpinned).
 //
-// Exact k-NN without a tree: points are counting-sorted into the uniform cell index of cellgrid.h (cell ~ 2 voxels); each
-// point scans the cells around it in growing cubes and stops once its k-th best distance is inside the scanned radius.
-// Distances in fp64 (Open3D works on double points); the k-best list lives in registers (static indexing).
+// Exact k-NN without a tree: points are counting-sorted into the uniform cell index of cellgrid.h (cell_index_build; cell ~ 2
+// voxels); each point walks the shells around its cell (cell_shell_walk) and stops once its k-th best distance is inside the
+// walked radius.  That rule is simpler than the bound of cellgrid.h (cell_face_bound) and valid here because every point lies
+// inside the box it was binned over: it is IN its cell, so whatever lies outside the walked cube [c - r, c + r]^3 is at least r
+// whole cells away along some axis.  (A search's query may lie outside the grid, where its clamped cell says nothing of the kind.)
+// The list holds the k smallest squared distances, kept sorted by a strict <: its content does not depend on the order in which
+// the walk meets the points.  Distances in fp64 (Open3D works on double points); the list lives in registers (static indexing).
 #include <math.h>
 
 #include <vector>
@@ -30,38 +34,23 @@ __global__ __launch_bounds__(256) void sor_knn_kernel(CellGrid cg, const float *
     for (int j = 0; j < KMAX; ++j) best[j] = 1e300;
     const int rmax = max(cg.nx, max(cg.ny, cg.nz));
     for (int r = 0; r <= rmax; ++r) {
-        // shell of Chebyshev radius r around (cx,cy,cz)
-        for (int dz = -r; dz <= r; ++dz) {
-            const int z = cz + dz;
-            if (z < 0 || z >= cg.nz) continue;
-            for (int dy = -r; dy <= r; ++dy) {
-                const int y = cy + dy;
-                if (y < 0 || y >= cg.ny) continue;
-                const bool face = (abs(dz) == r) || (abs(dy) == r);
-                const int step = face ? 1 : max(1, 2 * r);            // interior rows: only the two end cells
-                for (int dx = -r; dx <= r; dx += step) {
-                    const int x = cx + dx;
-                    if (x < 0 || x >= cg.nx) continue;
-                    const int c = (z * cg.ny + y) * cg.nx + x;
-                    const unsigned s = cell_start[c], e = cell_start[c + 1];
-                    for (unsigned q = s; q < e; ++q) {
-                        const double ddx = (double)sorted_xyz[3 * (size_t)q] - px, ddy = (double)sorted_xyz[3 * (size_t)q + 1] - py;
-                        const double ddz = (double)sorted_xyz[3 * (size_t)q + 2] - pz;
-                        double v = ddx * ddx + ddy * ddy + ddz * ddz;
-                        if (v < best[KMAX - 1]) {
+        cell_shell_walk(cg, cell_start, cx, cy, cz, r, [&](unsigned s, unsigned e) {
+            for (unsigned q = s; q < e; ++q) {
+                const double ddx = (double)sorted_xyz[3 * (size_t)q] - px, ddy = (double)sorted_xyz[3 * (size_t)q + 1] - py;
+                const double ddz = (double)sorted_xyz[3 * (size_t)q + 2] - pz;
+                double v = ddx * ddx + ddy * ddy + ddz * ddz;
+                if (v < best[KMAX - 1]) {
 #pragma unroll
-                            for (int j = 0; j < KMAX; ++j) {           // ordered insert, static indices -> registers
-                                const double b = best[j];
-                                const bool sw = v < b;
-                                best[j] = sw ? v : b;
-                                v = sw ? b : v;
-                            }
-                        }
+                    for (int j = 0; j < KMAX; ++j) {                   // ordered insert, static indices -> registers
+                        const double b = best[j];
+                        const bool sw = v < b;
+                        best[j] = sw ? v : b;
+                        v = sw ? b : v;
                     }
                 }
             }
-        }
-        // everything outside the scanned cube is at least r*cell away
+        });
+        // everything outside the walked cube is at least r*cell away (the head of the file)
         const double reach = (double)r * cg.cell;
         double kth = 1e300;
 #pragma unroll
@@ -113,22 +102,19 @@ int sor_mean_distance(tl3d_ctx *ctx, const float *xyz, long long n, int k, doubl
     if (rc) return rc;
     CellGrid cg;
     cell_grid_fit(mn, mx, cell, &cg);
-    const long long ncell = (long long)cg.nx * cg.ny * cg.nz;
-    const size_t nchunks = cell_chunks(ncell);
-    const size_t bytes[6] = {(size_t)ncell * sizeof(unsigned), (size_t)(ncell + 1) * sizeof(unsigned), nchunks * sizeof(unsigned),
-                             (nchunks + 1) * sizeof(unsigned long long), (size_t)n * 3 * sizeof(float), *mean_d ? 0 : (size_t)n * sizeof(double)};
+    size_t bytes[6];
+    cell_table_bytes(cell_grid_cells(cg), bytes);
+    bytes[4] = (size_t)n * 3 * sizeof(float);
+    bytes[5] = *mean_d ? 0 : (size_t)n * sizeof(double);
     void *p[6];
     rc = scratch_carve(ctx, 0, bytes, 6, p, "nearest-neighbour scratch");
     if (rc) return rc;
-    unsigned *cnt = (unsigned *)p[0], *start = (unsigned *)p[1], *chunk_sums = (unsigned *)p[2];
-    unsigned long long *chunk_off = (unsigned long long *)p[3];
+    const CellTables t = CellTables::at(p);
+    const unsigned *start = t.start;
     float *sorted = (float *)p[4];
     if (!*mean_d) *mean_d = (double *)p[5];
-    TL3D_HIP(hipMemsetAsync(cnt, 0, (size_t)ncell * sizeof(unsigned), s));
-    launch_cell_count(s, cg, xyz, n, cnt);
-    rc = launch_cell_scan(s, cnt, ncell, chunk_sums, chunk_off, start);
+    rc = cell_index_build(s, cg, xyz, n, t, true, EmitXyz{sorted});
     if (rc) return rc;
-    launch_cell_fill(s, cg, xyz, n, start, cnt, EmitXyz{sorted});
     const unsigned nb = (unsigned)((n + 255) / 256);
     if (k <= 32)
         hipLaunchKernelGGL(sor_knn_kernel<32>, dim3(nb), dim3(256), 0, s, cg, xyz, n, k, start, sorted, *mean_d);

@@ -333,8 +333,8 @@ struct tl3d_grid_state {
     unsigned *mesh_first;
     size_t mesh_first_n;
     // The device scratch of the mesh calls (api_mesh.hip) and of the calls on the uniform cell index (kernels_sor.hip,
-    // kernels_nearest.hip): the two grow-on-demand buffers every call carves its arrays from (scratch_carve, api_host.h; nothing
-    // in them is live across calls) and the fixed slab (CELL_SLAB_BYTES) of the cell-index calls' block partials.  None of it
+    // kernels_nearest.hip, kernels_normals.hip, kernels_planes.hip): the two grow-on-demand buffers every call carves its arrays
+    // from (scratch_carve, api_host.h; nothing in them is live across calls) and the fixed slab (CELL_SLAB_BYTES) of the cell-index calls' block partials.  None of it
     // depends on the grid (the calls work without one): it lives here so that tl3d_detach_grid gives the memory back.
     char *scratch[2];
     size_t scratch_bytes[2];                // capacities
@@ -726,6 +726,27 @@ void cell_grid_fit(const double mn[3], const double mx[3], double cell, CellGrid
 void launch_cell_count(hipStream_t s, const CellGrid &g, const float *xyz, long long n, unsigned *cnt);
 int launch_cell_scan(hipStream_t s, const unsigned *cnt, long long ncell, unsigned *chunk_sums, unsigned long long *chunk_off, unsigned *start);
 int cell_slab(tl3d_ctx *ctx);
+// The four tables of one index (cell_index_build, cellgrid.h), in the order a caller appends their sizes to its own carve list:
+// cnt[ncell] (zero in front of a count and again behind the fill), start[ncell + 1], and the scan's chunk sums and offsets.
+struct CellTables {
+    unsigned *cnt, *start, *chunk_sums;
+    unsigned long long *chunk_off;
+    static CellTables at(void *const p[4]) { return {(unsigned *)p[0], (unsigned *)p[1], (unsigned *)p[2], (unsigned long long *)p[3]}; }
+};
+inline void cell_table_bytes(long long ncell, size_t bytes[4]) {
+    bytes[0] = (size_t)ncell * sizeof(unsigned);
+    bytes[1] = (size_t)(ncell + 1) * sizeof(unsigned);
+    bytes[2] = cell_chunks(ncell) * sizeof(unsigned);
+    bytes[3] = (cell_chunks(ncell) + 1) * sizeof(unsigned long long);
+}
+// The first step of every build: the box of a device list's finite points and the number of points with a non-finite coordinate.
+// points_bounds_finite is the whole pass (waits for the stream).  The searches run it for two lists under one wait: nn_bounds_launch
+// leaves a list's block partials (nn_red_blocks(n) x 8 floats) in the slab, nn_bounds_fold folds their host copy and returns the count.
+constexpr int NN_RED = 1024;            // blocks of the reductions (fixed: the partial sums do not depend on the device)
+unsigned nn_red_blocks(long long n);
+void nn_bounds_launch(hipStream_t s, const float *xyz_dev, long long n, float *slab);
+unsigned long long nn_bounds_fold(const float *h, long long n, double mn[3], double mx[3]);
+int points_bounds_finite(tl3d_ctx *ctx, const float *xyz_dev, long long n, double mn[3], double mx[3], unsigned long long *bad);
 // outlier filter (kernels_sor.hip): the k-NN mean-distance stage alone (*mean_dev: n doubles, or null: carved with the call's scratch
 // and returned), and the whole filter, which thresholds it
 int sor_mean_distance(tl3d_ctx *ctx, const float *xyz_dev, long long n, int k, double cell, double **mean_dev);
@@ -737,8 +758,6 @@ int nearest_points_run(tl3d_ctx *ctx, const float *query, long long nq, const fl
 int nearest_triangles_run(tl3d_ctx *ctx, const float *query, long long nq, const float *xyz, long long nv, const unsigned *tri, long long n_tri,
                           double cell, double max_dist, double *dist, int *index);
 int distance_summary_run(tl3d_ctx *ctx, const double *dist, long long n, const double *thresholds, int nthr, tl3d_distance_stats *out);
-// the searches' validation pass alone: the box of a device list's finite points and the number of non-finite ones (waits for the stream)
-int points_bounds_finite(tl3d_ctx *ctx, const float *xyz_dev, long long n, double mn[3], double mx[3], unsigned long long *bad);
 
 // normals and surface variation by k-NN PCA (kernels_normals.hip); device pointers but the viewpoints (host), curvature may be null
 int normals_run(tl3d_ctx *ctx, const float *xyz, long long n, int k, double max_radius, double cell, const double *vp_host, long long n_vp,
