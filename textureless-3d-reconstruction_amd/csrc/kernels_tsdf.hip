@@ -178,7 +178,8 @@ __device__ __forceinline__ void rec_store_nt(int2 *p, int2 r) {
 }
 
 #ifdef TL3D_EXPERIMENTS
-__device__ unsigned long long g_upd_span[16384][2];       // experiments: start / end (100 MHz real-time clock) of every wave of the last stamped launch
+constexpr unsigned UPD_SPAN_WAVES = 65536;
+__device__ unsigned long long g_upd_span[UPD_SPAN_WAVES][2];   // experiments: start / end (100 MHz real-time clock) of every wave of the last stamped launch
 #endif
 constexpr int UPD_WAVES = 8;             // waves per SIMD the pair kernel is built for (64 vector registers)
 // the depth-gather latency (LAT below) the library ships: 2 for both depth formats (f32 +3.0 %, 16-bit +2.4 % frames/s against 1:
@@ -207,8 +208,13 @@ __global__ __launch_bounds__(256, UPD_WAVES) void tsdf_update_pairs_kernel(Cam c
     // list leaves waves idle for a third of the launch.  Tasks are handed out by TICKET instead: the workgroups form up to 64
     // groups (blockIdx % groups), group g owns list entries g, g + groups, g + 2 groups, ... (every group sees the same mix of
     // cheap and dear bricks) and a ticket counter of its own (64-B apart; a few hundred returning atomics per counter and
-    // launch, handed out two tasks ahead of their use, so nobody waits for one).  A wave's first task needs no ticket.  A
-    // ticket far beyond the list saturates (entry_of): it must not wrap into it.
+    // launch, handed out two tasks ahead of their use, so nobody waits for one).  A wave's first task needs no ticket: entry
+    // bi * 4 + wid of its group, dearest first.  The launch has four times the workgroups the chip holds at once (tl3d_api.hip),
+    // so most first tasks wait with a workgroup that has not started: the dispatcher starts it in the very slot a wave retires
+    // from, which hands those bricks out one at a time and later than any ticket is committed (a wave holds its tickets two
+    // tasks ahead).  At the headline shape the launch has a wave for four of every five list entries; tickets carry the rest,
+    // the cheapest bricks, and whatever a longer list leaves.  Measured, not assumed: late workgroups that take their first task by ticket instead
+    // make the kernel 7 % slower.  A ticket far beyond the list saturates (entry_of): it must not wrap into it.
     const unsigned ngrp = min((unsigned)TICKET_GROUPS, gridDim.x);
     const unsigned grp = blockIdx.x % ngrp, bi = blockIdx.x / ngrp;
     const unsigned waves_in_group = ((gridDim.x - grp + ngrp - 1u) / ngrp) * 4u;
@@ -434,7 +440,7 @@ __global__ __launch_bounds__(256, UPD_WAVES) void tsdf_update_pairs_kernel(Cam c
 #ifdef TL3D_EXPERIMENTS
     if ((EXP & 32) && lane == 0) {
         const unsigned wv = blockIdx.x * 4u + (unsigned)wid;
-        if (wv < 16384u) { g_upd_span[wv][0] = pf_rt0; g_upd_span[wv][1] = __builtin_amdgcn_s_memrealtime(); }
+        if (wv < UPD_SPAN_WAVES) { g_upd_span[wv][0] = pf_rt0; g_upd_span[wv][1] = __builtin_amdgcn_s_memrealtime(); }
         if (wv == 0) atomicAdd(counters + 14, 1ull);
     }
 #endif
@@ -635,20 +641,35 @@ int launch_tsdf_update(hipStream_t s, const Cam &cam, const Grid &g, int n, int 
 }
 
 #ifdef TL3D_EXPERIMENTS
-// when the waves of the last stamped launch ended (TL3D_PAIRS_EXP=32)
-void tsdf_debug_print_spans(int nwaves) {
-    static unsigned long long h[16384][2];
-    if (nwaves > 16384) nwaves = 16384;
+// when the waves of the last stamped launch started and ended (TL3D_PAIRS_EXP=32), and how the waves of the workgroups at or
+// above `late_from` (8 x CUs: those the chip cannot hold from the start) fared
+void tsdf_debug_print_spans(int nwaves, int late_from) {
+    static unsigned long long h[UPD_SPAN_WAVES][2];
+    if (nwaves > (int)UPD_SPAN_WAVES) nwaves = (int)UPD_SPAN_WAVES;
     if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_upd_span), sizeof(h)) != hipSuccess) return;
     unsigned long long t0 = ~0ull, t1 = 0;
     for (int i = 0; i < nwaves; ++i) if (h[i][0]) { if (h[i][0] < t0) t0 = h[i][0]; if (h[i][1] > t1) t1 = h[i][1]; }
     if (t1 <= t0) return;
     const double span = (double)(t1 - t0);
-    int he[10] = {0};
-    for (int i = 0; i < nwaves; ++i) if (h[i][0]) { int b = (int)(10.0 * (double)(h[i][1] - t0) / span); he[b > 9 ? 9 : b]++; }
-    fprintf(stderr, "[tl3d exp] launch %.1f us; waves ENDING in each tenth of it:", span * 0.01);
+    int hs[10] = {0}, he[10] = {0}, nlate = 0, nfirst = 0, nidle = 0;
+    double late_start = 0, late_life = 0, first_life = 0;
+    for (int i = 0; i < nwaves; ++i)
+        if (h[i][0]) {
+            const int bs = (int)(10.0 * (double)(h[i][0] - t0) / span), be = (int)(10.0 * (double)(h[i][1] - t0) / span);
+            const double life = (double)(h[i][1] - h[i][0]);
+            hs[bs > 9 ? 9 : bs]++;
+            he[be > 9 ? 9 : be]++;
+            if (i / 4 < late_from) { nfirst++; first_life += life; }
+            else if (life < 100.0) nidle++;                                   // under 1 us: a wave that found the list used up
+            else { nlate++; late_start += (double)(h[i][0] - t0); late_life += life; }
+        }
+    fprintf(stderr, "[tl3d exp] launch %.1f us; waves STARTING in each tenth of it:", span * 0.01);
+    for (int i = 0; i < 10; ++i) fprintf(stderr, " %d", hs[i]);
+    fprintf(stderr, "; ENDING:");
     for (int i = 0; i < 10; ++i) fprintf(stderr, " %d", he[i]);
-    fprintf(stderr, "\n");
+    fprintf(stderr, "\n[tl3d exp] waves of workgroups < %d: %d, mean lifetime %.1f us;  >= %d: %d with work, mean start %.1f us, mean lifetime %.1f us, and %d that found none\n",
+            late_from, nfirst, nfirst ? first_life * 0.01 / nfirst : 0.0, late_from, nlate, nlate ? late_start * 0.01 / nlate : 0.0,
+            nlate ? late_life * 0.01 / nlate : 0.0, nidle);
 }
 #endif
 

@@ -332,12 +332,20 @@ static int build_grid(tl3d_ctx *ctx, const tl3d_config *cfg) {
         ctx->tsdf_batch = env_int("TL3D_TSDF_BATCH", 32);
         if (ctx->tsdf_batch < 1) ctx->tsdf_batch = 1;
         if (ctx->tsdf_batch > TL3D_TSDF_MAXBATCH) ctx->tsdf_batch = TL3D_TSDF_MAXBATCH;
-        {   // Workgroups of the update kernel (the pair form: ~56 vector registers, eight waves per SIMD, tasks by ticket): 12 per CU.
-            // Round 4, same box, interleaved: 1536 / 2048 / 3072 workgroups 74.8 / 76.5 / 77.8 k frames/s; 4096 and 6144 inside
-            // the spread of 3072 (77.9 / 78.2 k against 77.5 k).  (Round 3's frame-major kernel, 128 registers, wanted three per CU.)
+        {   // Workgroups of the update kernel (61 vector registers, eight waves per SIMD: a CU holds 8 of them): at most 32 per CU,
+            // four times what the chip holds.  The ones that do not fit start one by one as waves retire, each wave on the static
+            // first task of its place in the launch (dearest bricks first): the dispatcher hands the dear bricks out better than
+            // the tickets do.  Same box, interleaved, three runs each, frames/s by workgroups per CU (profiles/update_residency_ab.txt):
+            //            8        12       16       24       32       48       64
+            //   plain    100.3 k  106.1 k  108.6 k  111.5 k  112.7 k  112.6 k  112.3 k   (lowest run)
+            //   warm     --       110.3 k  --       120.6 k  123.0 k  123.2 k  --        16-bit frames: 117.0 / 122.1 / 122.7 / 122.4 k
+            // and a first scan (prep kernels beside every update) the same at 12 to 48: 65.7 to 68.0 k.  Late workgroups that take
+            // their first task by ticket instead, so that none waits with an unstarted workgroup: 100.7 k against 107.7 k, not kept.
+            // (Round 4 had kept 12 after 77.5 to 78.2 k at 12, 16 and 24 -- with three big prep kernels beside every update, which
+            // the caches have since taken out of the steady state.)
             int cus = 0;
             if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || cus < 1) cus = 256;
-            ctx->tsdf_max_blocks = env_int("TL3D_UPDATE_BLOCKS", 12 * cus);
+            ctx->tsdf_max_blocks = env_int("TL3D_UPDATE_BLOCKS", 32 * cus);
         }
         if (ctx->tsdf_max_blocks < 8) ctx->tsdf_max_blocks = 8;
         ctx->tsdf_single_stream = env_int("TL3D_SINGLE_STREAM", 0) != 0;
@@ -1938,7 +1946,11 @@ int tl3d_get_stats(tl3d_ctx *ctx, tl3d_stats *out) {
                        (double)h[8] / h[14], (double)h[9] / h[14], (double)h[10] / h[14], (double)h[11] / h[14], (double)h[12] / h[14],
                        h[12] ? (double)(h[13] & 0xffffffffull) / h[12] : 0.0, (h[13] & 0xffffffffull) ? (double)(h[13] >> 32) / (double)(h[13] & 0xffffffffull) : 0.0,
                        h[14], (double)h[15]);
-    if (h[14]) tsdf_debug_print_spans(ctx->tsdf_max_blocks * 4 > 16384 ? 16384 : ctx->tsdf_max_blocks * 4);
+    if (h[14]) {
+        int cus = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || cus < 1) cus = 256;
+        tsdf_debug_print_spans(ctx->tsdf_max_blocks * 4, 8 * cus);
+    }
 #endif
     if (ctx->brick_tabs) {
         unsigned cur[4] = {0, 0, 0, 0};

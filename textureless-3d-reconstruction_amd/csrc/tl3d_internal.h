@@ -415,7 +415,7 @@ struct tl3d_ctx : tl3d_grid_state {
     double *bp_factors;                  // projection factors (D2R:287-295): [0, W) xf[u] = (u - cx) / fx, [W, W + H) yf[v] = (v - cy) / fy
     hipEvent_t ev_free;                   // recorded on the main stream behind its last write to free_cnt (clear, fold); prep chains wait for it
     bool ev_free_recorded;
-    int tsdf_max_blocks;                  // launch geometry of the update kernel (12 workgroups per CU)
+    int tsdf_max_blocks;                  // launch geometry of the update kernel (32 workgroups per CU)
     bool tsdf_single_stream;
     void *rccl_comm;             // ncclComm_t of tl3d_rccl_init (RCCL is dlopen'ed: tl3d_api.hip)
     int rccl_world;
@@ -639,7 +639,7 @@ size_t tsdf_tile_cache_bytes(const Cam &cam, size_t *vtile_off, size_t *vpix_off
 size_t tsdf_class_cache_bytes(unsigned entries);
 int launch_centroid_mark(hipStream_t s, const Cam &cam, const Grid &g, const BpArgs &a, const PoseD &p, const float *depth, const double *xf, const double *yf);
 #ifdef TL3D_EXPERIMENTS
-void tsdf_debug_print_spans(int nwaves);
+void tsdf_debug_print_spans(int nwaves, int late_from);
 #endif
 int launch_tsdf_update(hipStream_t s, const Cam &cam, const Grid &g, int n, int max_frames, bool depth_u16, float mind, float maxd, int2 *grid,
                        void *scratch, unsigned long long *counters, bool count, int max_blocks);
