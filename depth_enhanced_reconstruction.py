@@ -49,6 +49,15 @@ def main(argv=None):
                         help="a distance threshold of --compare-to, in metres (repeatable, at most 8; default 0.005 0.01 0.02)")
     parser.add_argument("--compare-max-dist", type=float, default=None, metavar="M",
                         help="points with no neighbour within this distance count as unmatched (default: no limit)")
+    parser.add_argument("--compare-align", action="store_true",
+                        help="register the fused cloud onto the --compare-to scan on the GPU first (point-to-plane ICP) and score it "
+                             "in the scan's frame; the written files are not moved.  A local method: a scan more than 20 cm away "
+                             "needs --compare-align-init")
+    parser.add_argument("--compare-align-scale", action="store_true",
+                        help="with --compare-align: estimate the scale too (needs a closed or bounded scene: open geometry observes "
+                             "the scale weakly)")
+    parser.add_argument("--compare-align-init", type=str, default=None, metavar="FILE",
+                        help="with --compare-align: a 4x4 matrix (.npy or text) mapping reconstruction to scan, where the registration starts")
     parser.add_argument("--cloud-normals", action="store_true",
                         help="give the fused cloud per-point normals on the GPU (PCA over the nearest neighbours, turned towards the "
                              "nearest camera) and write them as nx ny nz")
@@ -112,6 +121,13 @@ def main(argv=None):
             parser.error("--depth-filter: " + str(e))
     if args.compare_threshold and len(args.compare_threshold) > 8:
         parser.error("--compare-threshold: at most 8 thresholds")
+    if args.compare_align or args.compare_align_scale or args.compare_align_init:
+        from tl3d.pipeline import check_compare_options
+        try:
+            check_compare_options(argparse.Namespace(compare_to=args.compare_to, compare_align=args.compare_align,
+                                                     compare_align_scale=args.compare_align_scale, compare_align_init=args.compare_align_init))
+        except ValueError as e:
+            parser.error("--compare-align: " + str(e))
     if args.photometric:
         from tl3d.pipeline import check_photometric_options
         try:
@@ -147,6 +163,8 @@ def main(argv=None):
                                   cloud_normals_radius=args.cloud_normals_radius, cloud_curvature=args.cloud_curvature,
                                   compare_to=args.compare_to, compare_max_dist=args.compare_max_dist,
                                   compare_thresholds=tuple(args.compare_threshold) if args.compare_threshold else (0.005, 0.01, 0.02),
+                                  compare_align=args.compare_align, compare_align_scale=args.compare_align_scale,
+                                  compare_align_init=args.compare_align_init,
                                   outlier_filter=False)                   # DER's merge_pointclouds has no outlier filter (DER:615-645)
     pipeline = DepthToReconstructionPipeline(config)
     if args.depth_model:

@@ -840,6 +840,45 @@ int tl3d_distance_summary(tl3d_ctx *ctx, const double *dist_hd, int64_t n,
  * scatter their results back by original index (default).  cell_order = 0: in input order.  The results are the same bytes. */
 int tl3d_set_nearest_query_order(tl3d_ctx *ctx, int cell_order);
 
+/* ---- registration of two unorganised point clouds: ICP over the cell index, optionally with scale ------
+ * One pass at the pose (T, scale), every operation fp64 and rounded once, in this order (tests/cloud_register_reference.py
+ * restates it bit for bit).  For every sampled source point p (index i with i % stride == 0; f32 -> fp64):
+ *   m = R p, m_x = (R00 px + R01 py) + R02 pz ...;  w = scale * m;  q = w + t              (q is never rounded to f32)
+ *   y = the target point minimising (d2, index), d = y - q, d2 = dx dx + dy dy + dz dz      (tl3d_nearest_points' rule: an exact
+ *       tie goes to the smaller index); the pair is kept iff sqrt(d2) <= max_dist (max_dist <= 0: unlimited)
+ *   point-to-plane (target normals given): n = the normal of y; a correspondence whose normal is exactly (0, 0, 0) is dropped and
+ *       counted in n_no_normal; r = (n_x e_x + n_y e_y) + n_z e_z with e = q - y; J = [q x n, n, n . w] (the last with scale only)
+ *   point-to-point (normals NULL): three rows per correspondence, n = e_x, e_y, e_z in that order, the same expressions
+ *   A += J_i J_j (upper triangle), b += J_i r, e += r r; n_corr counts correspondences, n_src the sampled points.
+ * The sums have a fixed shape that depends on n_src alone: they, and the pose of tl3d_cloud_register, are the same bytes in every
+ * run, for every cell_size and under either setting of tl3d_set_nearest_query_order.  index_out[i] = the index of y, or -1 where
+ * the pair was gated, the target is empty or the point was not sampled.  cell_size as tl3d_nearest_points (the target's grid). */
+typedef struct tl3d_cloud_eval {
+    double  A[28];              /* upper triangle of the 7 x 7 matrix, row-major; without with_scale row and column 6 are 0 */
+    double  b[7];
+    double  e;
+    int64_t n_corr;
+    int64_t n_src;
+    int64_t n_no_normal;
+} tl3d_cloud_eval;
+/* TL3D_E_INVALID before any device work: null ctx / source / target (with points) / T / out, negative sizes, n_tgt or n_src >= 2^31,
+ * stride < 1, a non-finite T or scale; from the bounds pass, with nothing written: a non-finite coordinate.  TL3D_E_STATE while an
+ * ICP batch is uncollected.  n_src == 0 or n_tgt == 0: zero sums (n_src still counts the sampled points), every index -1. */
+int tl3d_cloud_evaluate(tl3d_ctx *ctx, const float *src_hd, int64_t n_src, const float *tgt_hd, int64_t n_tgt,
+                        const float *tgt_normals_hd /* NULL: point-to-point */, const double T[16], double scale, int stride,
+                        double max_dist, double cell_size, int with_scale, tl3d_cloud_eval *out,
+                        int32_t *index_out_hd /* may be NULL, [n_src] */);
+/* Gauss-Newton over such passes: per iteration solve (A + damping tr(A)/k I) x = -b under the relative eigenvalue cutoff (k = 6,
+ * or 7 with estimate_scale), T <- exp(x) T, scale <- scale exp(x[6]).  A pass with fewer than 6 correspondences or an unsolvable
+ * system fails the run (status 2, T the last good pose); |x|_max < eps ends a level (status 1); a level that failed or ended with
+ * fewer than 8 correspondences ends the run.  The target's index is built once; every level and iteration is enqueued without a
+ * host round trip and the state is read once.  out->T maps source to target and holds the rigid part, out->scale is sigma, n_src
+ * the sampled points of the last level.  Empty source or target: status 2, T = T_init.  Refusals as tl3d_cloud_evaluate, and
+ * n_levels outside 1..TL3D_ICP_MAX_LEVELS, iters outside [0, 1000], a max_dist that is not positive. */
+int tl3d_cloud_register(tl3d_ctx *ctx, const float *src_hd, int64_t n_src, const float *tgt_hd, int64_t n_tgt,
+                        const float *tgt_normals_hd, const double T_init[16], double scale_init,
+                        const tl3d_icp_params *levels, int n_levels, double cell_size, tl3d_icp_result *out);
+
 /* measurement */
 int tl3d_set_profile(tl3d_ctx *ctx, int count_records, int time_kernels);
 /* Noise-robust registration: normal maps built after this call come from the depth averaged over a (2 radius + 1)^2 window

@@ -29,6 +29,7 @@ SYMBOLS = [
     "tl3d_grid_download", "tl3d_grid_upload", "tl3d_grid_add", "tl3d_grid_touched_bricks", "tl3d_grid_pack_bricks", "tl3d_grid_unpack_bricks", "tl3d_rccl_unique_id", "tl3d_rccl_init", "tl3d_allreduce_grid", "tl3d_extract", "tl3d_extract_mesh", "tl3d_extract_mesh_keyed", "tl3d_mesh_components", "tl3d_mesh_filter_components", "tl3d_mesh_simplify_clusters", "tl3d_mesh_simplify_quadric", "tl3d_mesh_smooth_taubin", "tl3d_mesh_vertex_normals", "tl3d_mesh_weld_keyed", "tl3d_raycast", "tl3d_track_evaluate", "tl3d_track_frame", "tl3d_statistical_outlier", "tl3d_knn_mean_distance", "tl3d_estimate_normals", "tl3d_segment_planes",
     "tl3d_build_intensity_many", "tl3d_download_intensity", "tl3d_rgbd_evaluate_pairs", "tl3d_rgbd_register_pairs",
     "tl3d_nearest_points", "tl3d_nearest_triangles", "tl3d_distance_summary", "tl3d_set_nearest_query_order",
+    "tl3d_cloud_evaluate", "tl3d_cloud_register",
     "tl3d_set_profile", "tl3d_set_normal_smoothing", "tl3d_set_tsdf_pairing", "tl3d_tile_cache_info", "tl3d_class_cache_info", "tl3d_class_refine_info", "tl3d_get_stats", "tl3d_reset_stats", "tl3d_event_record", "tl3d_event_elapsed_ms",
 ]
 
@@ -91,6 +92,11 @@ class MeshPart(C.Structure):
 class DistanceStats(C.Structure):
     _fields_ = [("n", C.c_int64), ("n_finite", C.c_int64), ("sum", C.c_double), ("sum_sq", C.c_double), ("max", C.c_double),
                 ("below", C.c_int64 * 8)]
+
+
+class CloudEval(C.Structure):
+    _fields_ = [("A", C.c_double * 28), ("b", C.c_double * 7), ("e", C.c_double), ("n_corr", C.c_int64), ("n_src", C.c_int64),
+                ("n_no_normal", C.c_int64)]
 
 
 class DepthFilterParams(C.Structure):
@@ -282,6 +288,8 @@ def load():
         "tl3d_nearest_triangles": [vp, vp, i64, vp, i64, vp, i64, dbl, dbl, vp, vp],
         "tl3d_distance_summary": [vp, vp, i64, vp, i32, C.POINTER(DistanceStats)],
         "tl3d_set_nearest_query_order": [vp, i32],
+        "tl3d_cloud_evaluate": [vp, vp, i64, vp, i64, vp, vp, dbl, i32, dbl, dbl, i32, C.POINTER(CloudEval), vp],
+        "tl3d_cloud_register": [vp, vp, i64, vp, i64, vp, vp, dbl, C.POINTER(IcpParams), i32, dbl, C.POINTER(IcpResult)],
         "tl3d_set_profile": [vp, i32, i32],
         "tl3d_set_tsdf_pairing": [vp, i32],
         "tl3d_get_stats": [vp, C.POINTER(Stats)],

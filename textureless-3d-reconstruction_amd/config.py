@@ -102,6 +102,17 @@ class ReconstructionConfig:
     compare_to: Optional[str] = None
     compare_thresholds: tuple = (0.005, 0.01, 0.02)
     compare_max_dist: Optional[float] = None
+    # compare_align: a reference scan is never in the reconstruction's frame (the first camera's), so the
+    # fused cloud is first registered onto it on the GPU (FusionContext.register_clouds: point-to-plane ICP against the scan's
+    # unoriented normals, the frame ICP's gate schedule) and the cloud, and the mesh's vertices for the mesh comparison, are moved by
+    # the result before they are scored; the written files are not moved.  stats["compare"]["alignment"] = {T, scale, fitness, rmse,
+    # n_corr, iters_run, status}.  A local method: a scan further than a gate (20 cm) away needs compare_align_init, a 4 x 4
+    # matrix (or a .npy / text file of one) mapping reconstruction to scan.  compare_align_scale also estimates the scale (a
+    # reconstruction from relative depth is not in the scan's units); it needs a closed or bounded scene -- open geometry (a wall, a
+    # corner) observes the scale weakly and the estimate can collapse.  Needs compare_to.  Off: nothing changes.
+    compare_align: bool = False
+    compare_align_scale: bool = False
+    compare_align_init: Optional[object] = None
     # normals (and surface variation) of the fused cloud: PCA over each point's cloud_normals_neighbors
     # nearest neighbours (Open3D's max_nn), none further than cloud_normals_radius metres (0: no limit), turned towards the nearest
     # kept camera; once over the whole cloud, after the outlier filter.  DepthToReconstructionPipeline.cloud_normals /

@@ -130,8 +130,15 @@ static void track_free(tl3d_ctx::Track &tr) {
     memset(&tr, 0, sizeof(tr));
 }
 
+static void cloud_free(tl3d_ctx::Cloud &cl) {
+    if (cl.state) (void)hipFree(cl.state);
+    if (cl.host) (void)hipHostFree(cl.host);
+    memset(&cl, 0, sizeof(cl));
+}
+
 namespace tl3d {
 void registration_release(tl3d_ctx *ctx) {
+    cloud_free(ctx->cloud);
     for (int l = 0; l < TL3D_ICP_LANES; ++l) {
         tl3d_ctx::IcpLane &ln = ctx->icp_lanes[l];
         if (ln.stream) (void)hipStreamSynchronize(ln.stream);
@@ -835,6 +842,133 @@ int tl3d_rgbd_register_pairs(tl3d_ctx *ctx, const tl3d_icp_pair *pairs, int n_pa
             info[i].n_qualified = (int64_t)hs[i].icp.sums[RGBD_SUM_ELIG];
         }
     }
+    return TL3D_OK;
+}
+
+// ------------------------------------------------------------------------------------------- registration of two point clouds
+// what both cloud calls check before any device work
+static int cloud_check(tl3d_ctx *ctx, const float *src, int64_t n_src, const float *tgt, int64_t n_tgt, const double T[16], double scale) {
+    REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
+    REQUIRE(n_src >= 0 && (n_src == 0 || src), TL3D_E_INVALID, "bad source list");
+    REQUIRE(n_tgt >= 0 && (n_tgt == 0 || tgt), TL3D_E_INVALID, "bad target list");
+    REQUIRE(n_tgt < (1ll << 31) && n_src < (1ll << 31), TL3D_E_INVALID, "n_src %lld, n_tgt %lld: indices need fewer than 2^31 points of each",
+            (long long)n_src, (long long)n_tgt);
+    REQUIRE(T != nullptr, TL3D_E_INVALID, "null pose");
+    for (int i = 0; i < 16; ++i) REQUIRE(isfinite(T[i]), TL3D_E_INVALID, "the pose has a non-finite entry");
+    REQUIRE(isfinite(scale), TL3D_E_INVALID, "the scale is not finite");
+    return TL3D_OK;
+}
+
+// the buffers, the initial state on its way to the device, the staged arrays, the run and the one read-back: *ctx->cloud.host holds the result
+static int cloud_run(tl3d_ctx *ctx, const float *src, int64_t n_src, const float *tgt, int64_t n_tgt, const float *nrm, const double T[16],
+                     double scale, const tl3d_icp_params *levels, int n_levels, bool evaluate, double cell, int32_t *index_out) {
+    REQUIRE(!ctx->icp_batch.busy, TL3D_E_STATE, "an ICP batch is still uncollected");
+    TL3D_HIP(hipSetDevice(ctx->device));
+    tl3d_ctx::Cloud &cl = ctx->cloud;
+    if (!cl.state) {                                        // all or nothing, as icp_lane_init
+        bool ok = hipMalloc(&cl.state, sizeof(IcpState)) == hipSuccess;
+        ok = ok && hipHostMalloc(&cl.host, sizeof(IcpState), hipHostMallocDefault) == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            cloud_free(cl);
+            return set_err(TL3D_E_NOMEM, "cloud registration: buffer allocation failed");
+        }
+    }
+    IcpState *h = cl.host;
+    memset(h, 0, sizeof(*h));
+    memcpy(h->T, T, sizeof(h->T));
+    h->T[12] = h->T[13] = h->T[14] = 0.0;
+    h->T[15] = 1.0;
+    h->scale = scale;
+    Staging st(ctx);
+    const float *ds, *dt, *dn = nullptr;
+    int32_t *di = nullptr;
+    int rc = st.in(src, (size_t)n_src * 12, &ds);
+    if (!rc) rc = st.in(tgt, (size_t)n_tgt * 12, &dt);
+    if (!rc && nrm) rc = st.in(nrm, (size_t)n_tgt * 12, &dn);
+    if (!rc && index_out) rc = st.out(index_out, (size_t)n_src * sizeof(int32_t), &di);
+    if (rc) return rc;
+    TL3D_HIP(hipMemcpyAsync(cl.state, h, sizeof(IcpState), hipMemcpyHostToDevice, ctx->stream));
+    rc = cloud_icp_run(ctx, ds, n_src, dt, n_tgt, dn, levels, n_levels, evaluate, cell, cl.state, di);
+    if (!rc && hipMemcpyAsync(h, cl.state, sizeof(IcpState), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+        rc = set_err(TL3D_E_HIP, "cloud registration: state read-back failed");
+    return st.finish(rc, true);
+}
+
+int tl3d_cloud_evaluate(tl3d_ctx *ctx, const float *src, int64_t n_src, const float *tgt, int64_t n_tgt, const float *tgt_normals,
+                        const double T[16], double scale, int stride, double max_dist, double cell_size, int with_scale,
+                        tl3d_cloud_eval *out, int32_t *index_out) {
+    int rc = cloud_check(ctx, src, n_src, tgt, n_tgt, T, scale);
+    if (rc) return rc;
+    REQUIRE(out != nullptr, TL3D_E_INVALID, "null argument");
+    REQUIRE(stride >= 1, TL3D_E_INVALID, "stride must be >= 1");
+    REQUIRE(!(max_dist != max_dist), TL3D_E_INVALID, "max_dist is not a number");
+    REQUIRE(!ranges_overlap(index_out, (size_t)n_src * 4, src, (size_t)n_src * 12) && !ranges_overlap(index_out, (size_t)n_src * 4, tgt, (size_t)n_tgt * 12) &&
+                !ranges_overlap(index_out, (size_t)n_src * 4, tgt_normals, (size_t)n_tgt * 12),
+            TL3D_E_INVALID, "the output aliases an input");
+    tl3d_icp_params lv;
+    memset(&lv, 0, sizeof(lv));
+    lv.stride = stride;
+    lv.max_dist = max_dist;
+    lv.estimate_scale = with_scale ? 1 : 0;
+    if (n_src == 0 || n_tgt == 0) {                         // nothing to search: zero sums, every index -1
+        REQUIRE(!ctx->icp_batch.busy, TL3D_E_STATE, "an ICP batch is still uncollected");
+        if (index_out && n_src) {
+            TL3D_HIP(hipSetDevice(ctx->device));
+            Staging st(ctx);
+            int32_t *di = nullptr;
+            rc = st.out(index_out, (size_t)n_src * sizeof(int32_t), &di);
+            if (rc) return rc;
+            TL3D_HIP(hipMemsetAsync(di, 0xff, (size_t)n_src * sizeof(int32_t), ctx->stream));
+            rc = st.finish(TL3D_OK, true);
+            if (rc) return rc;
+        }
+        memset(out, 0, sizeof(*out));
+        out->n_src = (n_src + stride - 1) / stride;
+        return TL3D_OK;
+    }
+    rc = cloud_run(ctx, src, n_src, tgt, n_tgt, tgt_normals, T, scale, &lv, 1, true, cell_size, index_out);
+    if (rc) return rc;
+    const double *s = ctx->cloud.host->sums;
+    int m = 0, k = 0;
+    for (int i = 0; i < 6; ++i) {
+        for (int j = i; j < 6; ++j) out->A[k++] = s[m++];
+        out->A[k++] = s[32 + i];
+    }
+    out->A[k] = s[38];
+    memcpy(out->b, s + 21, 6 * sizeof(double));
+    out->b[6] = s[39];
+    out->e = s[ICP_SUM_E];
+    out->n_corr = (int64_t)s[ICP_SUM_CORR];
+    out->n_src = (int64_t)s[ICP_SUM_SRC];
+    out->n_no_normal = (int64_t)s[CLOUD_SUM_NO_NORMAL];
+    return TL3D_OK;
+}
+
+int tl3d_cloud_register(tl3d_ctx *ctx, const float *src, int64_t n_src, const float *tgt, int64_t n_tgt, const float *tgt_normals,
+                        const double T_init[16], double scale_init, const tl3d_icp_params *levels, int n_levels, double cell_size,
+                        tl3d_icp_result *out) {
+    int rc = cloud_check(ctx, src, n_src, tgt, n_tgt, T_init, scale_init);
+    if (rc) return rc;
+    REQUIRE(out != nullptr, TL3D_E_INVALID, "null argument");
+    REQUIRE(n_levels >= 1 && n_levels <= TL3D_ICP_MAX_LEVELS, TL3D_E_INVALID, "n_levels %d outside [1,%d]", n_levels, TL3D_ICP_MAX_LEVELS);
+    REQUIRE(levels != nullptr, TL3D_E_INVALID, "null argument");
+    for (int l = 0; l < n_levels && !rc; ++l) rc = check_level(levels[l], 0);
+    if (rc) return rc;
+    if (n_src == 0 || n_tgt == 0) {                         // nothing to register: the run fails at its first pass
+        REQUIRE(!ctx->icp_batch.busy, TL3D_E_STATE, "an ICP batch is still uncollected");
+        memset(out, 0, sizeof(*out));
+        memcpy(out->T, T_init, sizeof(out->T));
+        out->T[12] = out->T[13] = out->T[14] = 0.0;
+        out->T[15] = 1.0;
+        out->scale = scale_init;
+        out->n_src = (n_src + levels[0].stride - 1) / levels[0].stride;
+        out->status = 2;
+        return TL3D_OK;
+    }
+    rc = cloud_run(ctx, src, n_src, tgt, n_tgt, tgt_normals, T_init, scale_init, levels, n_levels, false, cell_size, nullptr);
+    if (rc) return rc;
+    read_result(*ctx->cloud.host, out);
     return TL3D_OK;
 }
 

@@ -143,4 +143,26 @@ __device__ __forceinline__ void cell_face_bound(double u, int c, int r, int n, d
     }
 }
 
+// ---- the nearest-point candidate ---------------------------------------------------------------------------------------------------
+// what a nearest search keeps (kernels_nearest.hip, kernels_cloudicp.hip): the minimum over the pair (d2, index), and the evaluation
+// of a run of a point target's sorted list against a query in fp64
+struct NnBest {
+    double d2;
+    int idx;
+    __device__ __forceinline__ void take(double v, int i) {
+        if (v < d2 || (v == d2 && i < idx)) { d2 = v; idx = i; }
+    }
+};
+
+struct NnPointEval {
+    const float4 *__restrict__ sorted;
+    __device__ __forceinline__ void operator()(unsigned s, unsigned e, double px, double py, double pz, NnBest &best) const {
+        for (unsigned q = s; q < e; ++q) {
+            const float4 t = sorted[q];
+            const double dx = (double)t.x - px, dy = (double)t.y - py, dz = (double)t.z - pz;
+            best.take(dx * dx + dy * dy + dz * dz, __float_as_int(t.w));
+        }
+    }
+};
+
 }  // namespace tl3d

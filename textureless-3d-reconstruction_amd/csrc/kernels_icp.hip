@@ -1018,6 +1018,68 @@ int launch_rgbd_step(hipStream_t s, const double *slab, int n_pairs, int members
     return TL3D_OK;
 }
 
+// Registration of two point clouds (kernels_cloudicp.hip), the step behind a pass: ONE wave adds the pass's partials in member order
+// (lane c owns sum c of the 40) and keeps them in state->sums; unless this is a final pass it solves the damped 6 x 6 system on the
+// wave, or with est_scale the 7 x 7 one on one lane, and applies T <- exp(x) T, scale <- scale exp(x[6]) (the pass's J is the Jacobian
+// for moving the SOURCE point by exp(x), and T maps source to target: no sign change).  The rules are rgbd_step_kernel's: fewer than 6
+// correspondences or an unsolvable system fail the run (status 2, T the last good pose), |x|_max < eps ends the level (status 1);
+// final_pass as track_step_kernel.
+__global__ __launch_bounds__(64) void cloud_step_kernel(const double *__restrict__ slab, int members, IcpState *state, int est_scale, double damping,
+                                                        double eps, double eig_rel, int final_pass) {
+    if (state->over || (!final_pass && state->done)) return;
+    __shared__ double sums[CLOUD_SUMS];
+    const int c = threadIdx.x;
+    if (c < CLOUD_SUMS) {
+        double s = 0.0;
+        for (int m = 0; m < members; ++m) s += slab[(size_t)m * CLOUD_SUMS + c];
+        sums[c] = s;
+        state->sums[c] = s;
+    }
+    __syncthreads();
+    if (final_pass) {
+        if (c == 0) {
+            if (final_pass == 2 || state->status == 2 || sums[28] < 8.0) {
+                state->over = 1;
+            } else {
+                state->done = 0;
+                state->status = 0;
+                state->iters_run = 0;
+            }
+        }
+        return;
+    }
+    double x[7];
+    x[6] = 0.0;
+    int fail = 0;
+    if (est_scale) {                                       // the 7 x 7 system, on one lane (wave-uniform branch)
+        if (c == 0) fail = (sums[28] < 6.0) ? 1 : solve7_serial(sums, damping, eig_rel, x);
+    } else {
+        fail = (sums[28] < 6.0) ? 1 : solve6_wave(sums, sums + 21, damping, eig_rel, x);
+    }
+    if (c != 0) return;
+    if (fail) {
+        state->done = 1;
+        state->status = 2;
+        return;
+    }
+    double mx = 0.0;
+    for (int i = 0; i < (est_scale ? 7 : 6); ++i) mx = fmax(mx, fabs(x[i]));
+    se3_apply(x, state->T);
+    if (est_scale) state->scale = state->scale * exp(x[6]);
+    state->iters_run = state->iters_run + 1;
+    if (mx < eps) {
+        state->done = 1;
+        state->status = 1;
+    }
+}
+
+int launch_cloud_step(hipStream_t s, const double *slab, int members, IcpState *state, int est_scale, double damping, double eps, double eig_rel,
+                      int final_pass) {
+    hipLaunchKernelGGL(cloud_step_kernel, dim3(1), dim3(64), 0, s, slab, members, state, est_scale, damping, eps, eig_rel, final_pass);
+    TL3D_HIP(hipGetLastError());
+    return TL3D_OK;
+}
+
 // a normal map (phase-major rows) as the row-major [H][W] image the caller of tl3d_download_normals gets
 __global__ __launch_bounds__(256) void nmap_rowmajor_kernel(int W, int H, const float4 *__restrict__ nmap, float4 *__restrict__ out) {
     const int u = blockIdx.x * 64 + (threadIdx.x & 63);

@@ -99,25 +99,7 @@ __global__ __launch_bounds__(256) void nn_tri_bin_kernel(CellGrid g, const float
 }
 
 // ---- the search ----------------------------------------------------------------------------------------------------------------
-struct NnBest {
-    double d2;
-    int idx;
-    __device__ __forceinline__ void take(double v, int i) {
-        if (v < d2 || (v == d2 && i < idx)) { d2 = v; idx = i; }
-    }
-};
-
-struct NnPointEval {
-    const float4 *__restrict__ sorted;
-    __device__ __forceinline__ void operator()(unsigned s, unsigned e, double px, double py, double pz, NnBest &best) const {
-        for (unsigned q = s; q < e; ++q) {
-            const float4 t = sorted[q];
-            const double dx = (double)t.x - px, dy = (double)t.y - py, dz = (double)t.z - pz;
-            best.take(dx * dx + dy * dy + dz * dz, __float_as_int(t.w));
-        }
-    }
-};
-
+// (NnBest and NnPointEval: cellgrid.h, shared with kernels_cloudicp.hip)
 // squared distance from the origin to the segment [p, q]
 __device__ __forceinline__ double nn_seg_d2(const double p[3], const double q[3]) {
     const double e[3] = {q[0] - p[0], q[1] - p[1], q[2] - p[2]};
@@ -272,7 +254,7 @@ __global__ __launch_bounds__(256) void nn_summary_kernel(const double *__restric
 // Default cell of a point target: the box has V = the product of its non-zero extents (k of them) and n points; cell = (V / (4 n))^(1/k),
 // i.e. four cells per point if the points filled the box -- surface clouds fill a thin sheet of it, and end near ten points per
 // occupied cell.  A box without extent is one cell.
-static double nn_default_cell_points(const double mn[3], const double mx[3], long long n) {
+double nn_default_cell_points(const double mn[3], const double mx[3], long long n) {
     double v = 1.0;
     int k = 0;
     for (int a = 0; a < 3; ++a)

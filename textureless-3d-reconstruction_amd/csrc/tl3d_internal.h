@@ -475,6 +475,9 @@ struct tl3d_ctx : tl3d_grid_state {
         double *slab;            // [pairs][members][RGBD_SUMS] partials of the current pass
         size_t cap_slab;         // in doubles
     } rgbd;
+    struct Cloud {               // tl3d_cloud_*: device state and its pinned copy for the way in and out (main stream)
+        tl3d::IcpState *state, *host;
+    } cloud;
     float *bounds_slab;
     bool nn_input_order;         // tl3d_set_nearest_query_order(ctx, 0): nearest-neighbour queries run in input order, not bucketed by cell
     // stats / profiling
@@ -758,6 +761,17 @@ int nearest_points_run(tl3d_ctx *ctx, const float *query, long long nq, const fl
 int nearest_triangles_run(tl3d_ctx *ctx, const float *query, long long nq, const float *xyz, long long nv, const unsigned *tri, long long n_tri,
                           double cell, double max_dist, double *dist, int *index);
 int distance_summary_run(tl3d_ctx *ctx, const double *dist, long long n, const double *thresholds, int nthr, tl3d_distance_stats *out);
+double nn_default_cell_points(const double mn[3], const double mx[3], long long n);
+
+// registration of two point clouds (kernels_cloudicp.hip; the step kernel is kernels_icp.hip's): device pointers; the run starts at
+// the pose in *state (device memory) and leaves its result there, enqueued on the context's stream behind one wait for the bounds
+constexpr int CLOUD_SUMS = 40;           // doubles per block partial: IcpState::sums, [30] the correspondences dropped for a zero normal
+constexpr int CLOUD_SUM_NO_NORMAL = 30;
+int cloud_members(long long n_src);
+int cloud_icp_run(tl3d_ctx *ctx, const float *src, long long n_src, const float *tgt, long long n_tgt, const float *tgt_normals,
+                  const tl3d_icp_params *levels, int n_levels, bool evaluate, double cell, IcpState *state, int *index_out);
+int launch_cloud_step(hipStream_t s, const double *slab, int members, IcpState *state, int est_scale, double damping, double eps,
+                      double eig_rel, int final_pass);
 
 // normals and surface variation by k-NN PCA (kernels_normals.hip); device pointers but the viewpoints (host), curvature may be null
 int normals_run(tl3d_ctx *ctx, const float *xyz, long long n, int k, double max_radius, double cell, const double *vp_host, long long n_vp,

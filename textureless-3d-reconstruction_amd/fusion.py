@@ -1168,6 +1168,71 @@ class FusionContext:
         """nearest_points / nearest_triangles run their queries bucketed by cell (default) or, off, in input order: same bytes."""
         abi.check(self._lib.tl3d_set_nearest_query_order(self._h, 1 if cell_order else 0))
 
+    # ---- registration of two point clouds (DESIGN.md section 14; needs no grid) -------------
+    #: register_clouds' default levels: the frame ICP's gate schedule (DESIGN.md section 10), every 4th source point, then all
+    CLOUD_LEVELS = (dict(iters=10, stride=4, max_dist=0.20), dict(iters=15, stride=1, max_dist=0.05))
+
+    def _cloud_arrays(self, source, target, target_normals):
+        source, target = self._points(source), self._points(target)
+        if target_normals is not None:
+            target_normals = self._points(target_normals)
+            assert len(target_normals) == len(target), f"{len(target_normals)} normals for {len(target)} target points"
+        return source, target, target_normals
+
+    def cloud_evaluate(self, source, target, target_normals=None, T=None, scale=1.0, stride=1, max_dist=0.05, with_scale=False,
+                       cell_size=None, indices=False):
+        """One pass of the cloud registration at the pose (T, scale), no update (tl3d_cloud_evaluate): every `stride`-th source point
+        p goes to q = scale * R p + t, meets its nearest target point y (the smaller index on a tie; kept within max_dist, None or
+        <= 0: unlimited) and gives the point-to-plane row of y's normal, or without normals the three point-to-point rows.  A dict:
+        A (7 x 7, sum J J^T with J = [q x n, n, n . w]; row and column 6 are zero without with_scale), b, e, n_corr, n_src,
+        n_no_normal (correspondences dropped for a (0, 0, 0) normal), fitness, rmse; with indices=True also index (int32 per source
+        point, -1: gated or not sampled; a device tensor for device input)."""
+        source, target, target_normals = self._cloud_arrays(source, target, target_normals)
+        T0 = np.ascontiguousarray(np.eye(4) if T is None else np.asarray(T, np.float64).reshape(4, 4))
+        index = self._nearest_outputs(source)[1] if indices else None
+
+        def p(a):
+            return abi.ptr(a) if a is not None and len(a) else None
+        res = abi.CloudEval()
+        abi.check(self._lib.tl3d_cloud_evaluate(self._h, p(source), len(source), p(target), len(target),
+                                                p(target_normals) if len(target) else None, abi.ptr(T0), float(scale), int(stride),
+                                                float(max_dist) if max_dist is not None else 0.0,
+                                                float(cell_size) if cell_size is not None else 0.0, 1 if with_scale else 0,
+                                                C.byref(res), p(index)))
+        A = np.zeros((7, 7))
+        A[np.triu_indices(7)] = np.frombuffer(res, np.float64, 28)
+        A = A + np.triu(A, 1).T
+        out = dict(A=A, b=np.array(res.b[:]), e=res.e, n_corr=res.n_corr, n_src=res.n_src, n_no_normal=res.n_no_normal,
+                   fitness=res.n_corr / res.n_src if res.n_src else 0.0, rmse=(res.e / res.n_corr) ** 0.5 if res.n_corr else 0.0,
+                   raw=bytes(res))
+        if indices:
+            out["index"] = index
+        return out
+
+    def register_clouds(self, source, target, target_normals=None, T_init=None, scale_init=1.0, levels=None, estimate_scale=False,
+                        cell_size=None):
+        """Register one unorganised cloud onto another (tl3d_cloud_register): ICP over the target's cell index, point-to-plane with
+        target_normals (unoriented ones are fine) and point-to-point without, through `levels` coarse to fine (dicts with icp()'s
+        keywords; stride counts source points; default CLOUD_LEVELS), all on the device.  estimate_scale makes the scale a 7th
+        unknown in every level that does not say otherwise -- it needs a closed or bounded scene: open geometry observes the scale
+        weakly.  The dict icp() returns: T maps source to target (rigid part), scale is sigma: x_target = scale * R x + t.  A local
+        method: the clouds must start within a gate of each other (T_init)."""
+        source, target, target_normals = self._cloud_arrays(source, target, target_normals)
+        T0 = np.ascontiguousarray(np.eye(4) if T_init is None else np.asarray(T_init, np.float64).reshape(4, 4))
+        levels = [dict(lv) for lv in (self.CLOUD_LEVELS if levels is None else levels)]
+        for lv in levels:
+            lv.setdefault("stride", 1)
+            lv.setdefault("estimate_scale", bool(estimate_scale))
+        lv = _icp_levels(levels)
+
+        def p(a):
+            return abi.ptr(a) if a is not None and len(a) else None
+        res = abi.IcpResult()
+        abi.check(self._lib.tl3d_cloud_register(self._h, p(source), len(source), p(target), len(target),
+                                                p(target_normals) if len(target) else None, abi.ptr(T0), float(scale_init), lv, len(levels),
+                                                float(cell_size) if cell_size is not None else 0.0, C.byref(res)))
+        return _icp_result_dicts(res)[0]
+
     # ---- measurement -----------------------------------------------------------------------
     def set_profile(self, count_records=False, time_kernels=False):
         abi.check(self._lib.tl3d_set_profile(self._h, int(count_records), int(time_kernels)))

@@ -42,6 +42,31 @@ def compare_cloud_to_mesh(ctx, points, xyz, tris, thresholds=(), max_dist=None) 
     return dict(points_to_surface=ps, vertices_to_points=vp, at=_rates(vp, ps, thresholds))
 
 
+def move_points(points, T, scale=1.0):
+    """scale * R p + t for every point, on the host in fp64, rounded to float32 once."""
+    import numpy as np
+    T = np.asarray(T, np.float64).reshape(4, 4)
+    p = np.asarray(points, np.float32).astype(np.float64).reshape(-1, 3)
+    return (float(scale) * (p @ T[:3, :3].T) + T[:3, 3]).astype(np.float32)
+
+
+def align_clouds(ctx, a, b, b_normals=None, **kw):
+    """Register cloud a onto cloud b (FusionContext.register_clouds; kw: T_init, scale_init, levels, estimate_scale, cell_size) and
+    return (the result, a moved into b's frame: scale * R a + t, float32 on the host).  A local method: a must start within a gate
+    of b (T_init); estimate_scale needs a closed or bounded scene."""
+    res = ctx.register_clouds(a, b, b_normals, **kw)
+    if hasattr(a, "data_ptr"):
+        a = a.detach().cpu().numpy()
+    return res, move_points(a, res["T"], res["scale"])
+
+
+def format_alignment(al: dict) -> str:
+    """One line for the drivers, beside format_line."""
+    t = al["T"][:3, 3] if hasattr(al["T"], "shape") else [row[3] for row in al["T"][:3]]
+    return (f"Align: status {al['status']}, {al['iters_run']} iterations, fitness {al['fitness']:.4f}, rmse {al['rmse']:.6g} m, "
+            f"scale {al['scale']:.6g}, t ({t[0]:.4f}, {t[1]:.4f}, {t[2]:.4f})")
+
+
 def format_line(cmp: dict) -> str:
     """One line for the drivers: Chamfer and the F-scores."""
     parts = [f"chamfer {cmp['chamfer_mean']:.6g} m"]

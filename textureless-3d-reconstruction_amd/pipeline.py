@@ -15,6 +15,7 @@ from __future__ import annotations
 from collections import defaultdict
 from typing import List, Optional, Tuple
 
+import os
 import time
 
 import numpy as np
@@ -165,6 +166,34 @@ def cloud_plane_parameters(cfg, voxel_size=None) -> dict:
     return dict(radius=float(cfg.cloud_planes_radius) or 2.5 * voxel, max_angle_deg=float(cfg.cloud_planes_angle_deg),
                 max_offset=float(cfg.cloud_planes_offset) or voxel, max_curvature=float(cfg.cloud_planes_max_curvature),
                 min_points=int(cfg.cloud_planes_min_points), max_rms=float(cfg.cloud_planes_max_rms) or 0.5 * voxel)
+
+
+def load_alignment_matrix(init):
+    """compare_align_init as a finite 4 x 4 float64 matrix: an array, or the path of a .npy or text file holding one."""
+    if isinstance(init, (str, os.PathLike)):
+        path = os.fspath(init)
+        try:
+            init = np.load(path) if path.lower().endswith(".npy") else np.loadtxt(path)
+        except (OSError, ValueError) as e:
+            raise ValueError(f"compare_align_init: cannot read a matrix from {path!r} ({e})") from e
+    T = np.asarray(init, dtype=np.float64)
+    if T.shape != (4, 4) or not np.all(np.isfinite(T)):
+        raise ValueError(f"compare_align_init: a finite 4 x 4 matrix is needed, got shape {T.shape}")
+    return np.ascontiguousarray(T)
+
+
+def check_compare_options(cfg):
+    """The configuration's compare_align settings: refused with a message before any work.  Returns the initial matrix (or None)."""
+    align = bool(getattr(cfg, "compare_align", False))
+    scale = bool(getattr(cfg, "compare_align_scale", False))
+    init = getattr(cfg, "compare_align_init", None)
+    if (scale or init is not None) and not align:
+        raise ValueError("compare_align_scale / compare_align_init set how compare_align registers: they need compare_align = True")
+    if not align:
+        return None
+    if not getattr(cfg, "compare_to", None):
+        raise ValueError("compare_align registers the result onto the reference scan: it needs compare_to")
+    return None if init is None else load_alignment_matrix(init)
 
 
 def check_depth_filter_options(cfg):
@@ -572,6 +601,7 @@ class DepthToReconstructionPipeline:
         self._check_mesh_filter_config()
         self._check_mesh_weld_config()
         self._check_cloud_normals_config()
+        check_compare_options(cfg)
         check_depth_filter_options(cfg)
         self._photo_stats = None
         if poses is None:                                                       # with poses given nothing is registered: the option is ignored
@@ -694,10 +724,26 @@ class DepthToReconstructionPipeline:
         cfg = self.config
         ref = fileio.read_ply_points(cfg.compare_to)
         thr = tuple(float(t) for t in (cfg.compare_thresholds or ()))
-        out = metrics.compare_clouds(ctx, np.ascontiguousarray(xyz, dtype=np.float32), ref, thresholds=thr, max_dist=cfg.compare_max_dist)
+        cloud = np.ascontiguousarray(xyz, dtype=np.float32)
+        mesh_xyz = self.mesh[0] if self.mesh is not None else None
+        alignment = None
+        if getattr(cfg, "compare_align", False):
+            # the scan's normals stay unoriented (the sign of a normal does not reach a point-to-plane row); the cloud and the mesh's
+            # vertices are moved on the host, in copies: what the run computed and writes stays in its own frame
+            init = check_compare_options(cfg)
+            normals = ctx.estimate_normals(ref)
+            res, cloud = metrics.align_clouds(ctx, cloud, ref, normals, T_init=init, estimate_scale=bool(cfg.compare_align_scale))
+            alignment = dict(T=res["T"].tolist(), scale=res["scale"], fitness=res["fitness"], rmse=res["rmse"], n_corr=res["n_corr"],
+                             iters_run=res["iters_run"], status=res["status"])
+            if mesh_xyz is not None:
+                mesh_xyz = metrics.move_points(mesh_xyz, res["T"], res["scale"])
+        out = metrics.compare_clouds(ctx, cloud, ref, thresholds=thr, max_dist=cfg.compare_max_dist)
         out["reference"], out["reference_points"] = str(cfg.compare_to), len(ref)
         if self.mesh is not None:
-            out["mesh"] = metrics.compare_cloud_to_mesh(ctx, ref, self.mesh[0], self.mesh[2], thresholds=thr, max_dist=cfg.compare_max_dist)
+            out["mesh"] = metrics.compare_cloud_to_mesh(ctx, ref, mesh_xyz, self.mesh[2], thresholds=thr, max_dist=cfg.compare_max_dist)
+        if alignment is not None:
+            out["alignment"] = alignment
+            print("  " + metrics.format_alignment(alignment))
         print("  " + metrics.format_line(out))
         return out
 
@@ -939,6 +985,7 @@ class DepthToReconstructionPipeline:
             check_photometric_options(self.config, sharded=True)
         self._check_mesh_filter_config()
         self._check_cloud_normals_config()
+        check_compare_options(self.config)
         world, rank = dist.get_world_size(), dist.get_rank()
         self.mesh = None
         self.mesh_normals = None
