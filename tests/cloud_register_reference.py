@@ -133,7 +133,7 @@ def solve(A28, b7, k, damping, eig_rel):
 
 
 def se3_apply(x, T):
-    """T <- exp(x) T as kernels_icp.hip's se3_apply has it: x = (w, v), the rotation is Rodrigues' exp([w]x) and v is ADDED to the
+    """T <- exp(x) T as reg_solve.h's se3_apply has it: x = (w, v), the rotation is Rodrigues' exp([w]x) and v is ADDED to the
     rotated translation (the update is dR T + [0 v], not the screw motion of the se(3) exponential)."""
     wx, wy, wz = x[0], x[1], x[2]
     th2 = wx * wx + wy * wy + wz * wz

@@ -2,7 +2,7 @@
 unobserved, one start pose per case, the fp64 reference of ONE update step, and the bound a correct device step must keep to it.
 Not a test.
 
-The solve of every registration (kernels_icp.hip: solve6_wave / solve_n_serial) is x = -(M + lam I)^+ b over
+The solve of every registration (reg_solve.h: solve6_wave / solve_n_serial) is x = -(M + lam I)^+ b over
 the eigen-directions of M + lam I whose eigenvalue exceeds eig_rel * the largest.  The reference here is that sentence in numpy
 (track_reference.solve for 6 unknowns, solve_n below for Sim(3)'s 7), fed with sums that never come from the device: the C oracle's
 icp_sums / icp_sums_scale for the pairwise paths, track_reference.sums for tracking.

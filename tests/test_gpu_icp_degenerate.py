@@ -1,5 +1,5 @@
 """GPU: the solve at the end of every registration -- solve6_direct, the cross-lane Jacobi solve6_wave, the one-lane Sim(3) solve
-(kernels_icp.hip), reached through icp, icp_batch and track -- on geometry that leaves some motion unobserved: planes, a sphere,
+(reg_solve.h), reached through icp, icp_batch and track -- on geometry that leaves some motion unobserved: planes, a sphere,
 a cylinder, an open tube, a corridor, six pixels.  Single update steps against the fp64 reference of
 tests/icp_degenerate_common.py within the bound derived there (tests/test_icp_degenerate_reference_cpu.py checks, with the
 references alone, the conditions under which that bound means something); unobserved directions; a few iterations against the

@@ -624,14 +624,14 @@ static int track_prepare(tl3d_ctx *ctx, int slot, const double R[9], const doubl
     return TL3D_OK;
 }
 
-// one pass and the step behind it (the sums in member order; final_pass 0: solve and pose update too)
-static int track_pass_step(tl3d_ctx *ctx, int slot, double scale, int min_weight, const tl3d_icp_params &p, int final_pass) {
+// one pass and the step behind it (the sums in member order; STEP_ITERATE: solve and pose update too)
+static int track_pass_step(tl3d_ctx *ctx, int slot, double scale, int min_weight, const tl3d_icp_params &p, StepKind kind) {
     tl3d_ctx::Track &tr = ctx->track;
     int rc = launch_track_pass(ctx->stream, ctx->cam, ctx->grid, ctx->slots[slot].depth, (float)scale, (float)ctx->cfg.min_depth,
-                               (float)ctx->cfg.max_depth, min_weight, p.stride, p.max_dist, ctx->tsdf, tr.state, final_pass, tr.slab);
+                               (float)ctx->cfg.max_depth, min_weight, p.stride, p.max_dist, ctx->tsdf, tr.state, kind, tr.slab);
     if (rc) return rc;
     const IcpLevel L = make_level(ctx->cam, p);
-    return launch_track_step(ctx->stream, tr.slab, track_members(L.Ws, L.Hs), tr.state, p.damping, p.eps, p.eig_rel, final_pass);
+    return launch_track_step(ctx->stream, tr.slab, track_members(L.Ws, L.Hs), tr.state, p.damping, p.eps, p.eig_rel, kind);
 }
 
 static int track_collect(tl3d_ctx *ctx) {
@@ -647,7 +647,7 @@ int tl3d_track_evaluate(tl3d_ctx *ctx, int slot, double scale, const double R[9]
     const tl3d_icp_params lv = {0, stride, max_dist};     // one pass at one stride; the rest 0 (the step of a final pass reads none of it)
     int rc = check_level(lv, LV_FINITE_GATE);           // max_dist below 1e18: the lanes and the batch take any positive one
     if (!rc) rc = track_prepare(ctx, slot, R, t);
-    if (!rc) rc = track_pass_step(ctx, slot, scale, min_weight, lv, 2);
+    if (!rc) rc = track_pass_step(ctx, slot, scale, min_weight, lv, step_kind(0, 0, true, true));
     if (!rc) rc = track_collect(ctx);
     if (rc) return rc;
     read_eval(ctx->track.host->sums, out);
@@ -665,8 +665,8 @@ int tl3d_track_frame(tl3d_ctx *ctx, int slot, double scale, const double R_init[
     if (!rc) rc = track_prepare(ctx, slot, R_init, t_init);
     // every launch of every level is enqueued now; launches behind a converged or failed level return at once
     for (int l = 0; l < n_levels && !rc; ++l) {
-        for (int it = 0; it < levels[l].iters && !rc; ++it) rc = track_pass_step(ctx, slot, scale, min_weight, levels[l], 0);
-        if (!rc) rc = track_pass_step(ctx, slot, scale, min_weight, levels[l], l == n_levels - 1 ? 2 : 1);
+        for (int it = 0; it <= levels[l].iters && !rc; ++it)
+            rc = track_pass_step(ctx, slot, scale, min_weight, levels[l], step_kind(it, levels[l].iters, l == n_levels - 1, false));
     }
     if (!rc) rc = track_collect(ctx);
     if (rc) return rc;
@@ -767,9 +767,8 @@ static int rgbd_run(tl3d_ctx *ctx, const tl3d_icp_pair *pairs, int n_pairs, cons
         TL3D_HIP(hipMemcpyAsync(b.states, &hs[i0], m * sizeof(RgbdState), hipMemcpyHostToDevice, ctx->stream));
         for (int l = 0; l < n_levels && !rc; ++l) {
             const tl3d_icp_params &p = levels[l].icp;
-            const int last = eval || l == n_levels - 1 ? 2 : 1;
             for (int it = 0; it <= (eval ? 0 : p.iters) && !rc; ++it) {
-                const int fin = it == (eval ? 0 : p.iters) ? last : 0;
+                const StepKind fin = step_kind(it, p.iters, l == n_levels - 1, eval);
                 rc = launch_rgbd_pass(ctx->stream, ctx->cam, b.pairs, (int)m, lv[l], b.states, fin, b.slab);
                 if (!rc) rc = launch_rgbd_step(ctx->stream, b.slab, (int)m, lv[l].members, b.states, levels[l].photo_weight, p.damping, p.eps, p.eig_rel, fin);
             }

@@ -12,7 +12,7 @@
 //                         order only decides which lanes share a wave, a thread's result depends on its own point alone.
 //   cloud_reduce_kernel   in input order with a shape that depends on n_src alone: thread t of the launch takes samples t, t + G, ...
 //                         (G = 256 cloud_members(n_src)), recomputes q and the rows from the stored index, adds them in that order;
-//                         then wave shuffle, LDS in wave order, one partial per workgroup.  cloud_step_kernel (kernels_icp.hip) adds
+//                         then wave shuffle, LDS in wave order, one partial per workgroup.  cloud_step_kernel (kernels_regstep.hip) adds
 //                         the partials in member order.
 // So the sums, and the pose, are the same bytes in every run, for every cell size and for every query order: nothing that varies
 // (fill order inside a cell, the cells' size, which lanes walk together) reaches a sum other than through an index that is itself
@@ -74,9 +74,9 @@ __global__ __launch_bounds__(256) void cloud_order_kernel(const float *__restric
 // order == nullptr: thread k serves sample k; else sample order[k]
 __global__ __launch_bounds__(256) void cloud_search_kernel(CellGrid g, const float *__restrict__ src, long long n_samp, int stride,
                                                            const unsigned *__restrict__ order, const unsigned *__restrict__ start, NnPointEval eval,
-                                                           double max_dist, const IcpState *__restrict__ state, int final_pass,
+                                                           double max_dist, const IcpState *__restrict__ state, StepKind kind,
                                                            int *__restrict__ index) {
-    if (state->over || (!final_pass && state->done)) return;      // set by EARLIER launches only: uniform over the grid
+    if (state->over || (kind == STEP_ITERATE && state->done)) return;      // set by EARLIER launches only: uniform over the grid
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= n_samp) return;
     const long long i = (order ? (long long)order[t] : t) * stride;
@@ -151,8 +151,8 @@ __device__ __forceinline__ constexpr int cloud_sum_slot(int k) {
 template <bool PLANE, bool SCALE>
 __global__ __launch_bounds__(256) void cloud_reduce_kernel(const float *__restrict__ src, long long n_samp, int stride, const float *__restrict__ tgt,
                                                            const float *__restrict__ nrm, const int *__restrict__ index,
-                                                           const IcpState *__restrict__ state, int final_pass, double *__restrict__ slab) {
-    if (state->over || (!final_pass && state->done)) return;
+                                                           const IcpState *__restrict__ state, StepKind kind, double *__restrict__ slab) {
+    if (state->over || (kind == STEP_ITERATE && state->done)) return;
     __shared__ double sm[4][CLOUD_SUMS];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const CloudPose P = cloud_pose(state);
@@ -287,17 +287,17 @@ int cloud_icp_run(tl3d_ctx *ctx, const float *src, long long n_src, const float 
         }
         const int passes = evaluate ? 1 : lv.iters + 1;
         for (int it = 0; it < passes; ++it) {
-            const int final_pass = it < passes - 1 ? 0 : (evaluate || l == n_levels - 1 ? 2 : 1);
+            const StepKind kind = step_kind(it, lv.iters, l == n_levels - 1, evaluate);
             hipLaunchKernelGGL(cloud_search_kernel, dim3(nb), dim3(256), 0, s, g, src, n_samp, lv.stride, ordered ? (const unsigned *)order : nullptr,
-                               (const unsigned *)tt.start, pe, lv.max_dist, (const IcpState *)state, final_pass, index);
+                               (const unsigned *)tt.start, pe, lv.max_dist, (const IcpState *)state, kind, index);
             const dim3 rg(members), rb(256);
 #define CLOUD_REDUCE(PL, SC) \
-    hipLaunchKernelGGL((cloud_reduce_kernel<PL, SC>), rg, rb, 0, s, src, n_samp, lv.stride, tgt, nrm, (const int *)index, (const IcpState *)state, final_pass, slab)
+    hipLaunchKernelGGL((cloud_reduce_kernel<PL, SC>), rg, rb, 0, s, src, n_samp, lv.stride, tgt, nrm, (const int *)index, (const IcpState *)state, kind, slab)
             if (nrm) { if (est) CLOUD_REDUCE(true, true); else CLOUD_REDUCE(true, false); }
             else     { if (est) CLOUD_REDUCE(false, true); else CLOUD_REDUCE(false, false); }
 #undef CLOUD_REDUCE
             CI_HIP(hipGetLastError());
-            rc = launch_cloud_step(s, slab, members, state, est, lv.damping, lv.eps, lv.eig_rel, final_pass);
+            rc = launch_cloud_step(s, slab, members, state, est, lv.damping, lv.eps, lv.eig_rel, kind);
             if (rc) return rc;
         }
     }

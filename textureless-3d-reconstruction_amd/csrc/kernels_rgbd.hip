@@ -32,7 +32,7 @@
 // Sums: fp64 sums of exact fp64 products of f32 values, the two systems apart (tl3d_internal.h: RGBD_SUMS).
 //
 // Work layout, as kernels_icp_eval.hip and kernels_track.hip: grid = (members, pairs); workgroup (m, p) takes samples m * 256 + tid,
-// + members * 256, ... of pair p and writes its 64 partial sums to slab[p][m]; rgbd_step_kernel (kernels_icp.hip, beside the solvers)
+// + members * 256, ... of pair p and writes its 64 partial sums to slab[p][m]; rgbd_step_kernel (kernels_regstep.hip)
 // adds them in member order, one wave per pair.  `members` is a function of the level geometry only and nothing is exchanged
 // between workgroups inside a launch: a pair's sums and pose are bit for bit the same in every run, whatever batch it is in and
 // wherever in it.  Two launches per iteration on the context's stream; the host enqueues every launch of every level and reads the
@@ -111,10 +111,10 @@ int launch_intensity(hipStream_t s, const Cam &cam, const float *depth, const ui
 // ---- the pass --------------------------------------------------------------------------------------------------------------------
 // 56 fp64 sums and 4 counts per lane, four samples per trip: 214 VGPRs, no scratch, two waves per SIMD
 __global__ __launch_bounds__(256) void rgbd_pass_kernel(Cam cam, const RgbdPair *__restrict__ pairs, RgbdLevel L, const RgbdState *__restrict__ states,
-                                                        int final_pass, double *__restrict__ slab) {
+                                                        StepKind kind, double *__restrict__ slab) {
     const int pair = blockIdx.y, member = blockIdx.x, members = gridDim.x;
     const RgbdState *st = states + pair;
-    if (st->icp.over || (!final_pass && st->icp.done)) return;    // set by EARLIER launches only: uniform over the pair's workgroups
+    if (st->icp.over || (kind == STEP_ITERATE && st->icp.done)) return;    // set by EARLIER launches only: uniform over the pair's workgroups
     __shared__ double sm[4][RGBD_SUMS];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const RgbdPair pr = pairs[pair];
@@ -272,9 +272,9 @@ int rgbd_members(int Ws, int Hs) {
 
 // one pass of every pair at the pose in its state; slab: [n_pairs][L.members][RGBD_SUMS] doubles; n_pairs <= 65535 (grid.y)
 int launch_rgbd_pass(hipStream_t s, const Cam &cam, const RgbdPair *pairs, int n_pairs, const RgbdLevel &L, const RgbdState *states,
-                     int final_pass, double *slab) {
+                     StepKind kind, double *slab) {
     if (n_pairs <= 0) return TL3D_OK;
-    hipLaunchKernelGGL(rgbd_pass_kernel, dim3(L.members, n_pairs), dim3(256), 0, s, cam, pairs, L, states, final_pass, slab);
+    hipLaunchKernelGGL(rgbd_pass_kernel, dim3(L.members, n_pairs), dim3(256), 0, s, cam, pairs, L, states, kind, slab);
     TL3D_HIP(hipGetLastError());
     return TL3D_OK;
 }

@@ -16,7 +16,7 @@
 // SIGN.  r(p_c) = trunc * F(M^-1 p_c) with M = (R, t) world -> camera.  J is the Jacobian of r for p_c -> exp(x) p_c = p_c + w x p_c +
 // v: dr = n_c . (w x p_c + v) = w . (p_c x n_c) + v . n_c.  Moving the point by exp(x) in the camera frame is moving the camera
 // by exp(-x): M <- se3_apply(y) M with y = -x, so dr / dy = -J.  The Gauss-Newton step solves (A + lam I) x = -b (what solve6_*
-// return) and the pose update applies y = -x (track_step_kernel, kernels_icp.hip).  tests/test_track_reference_cpu.py checks
+// return) and the pose update applies y = -x (track_step_kernel, kernels_regstep.hip).  tests/test_track_reference_cpu.py checks
 // d(e / 2) / dy = -b against central differences.
 // Sums: A = sum J J^T (21), b = sum J r (6), e = sum r^2, n_corr, n_src -- the head of IcpState::sums; per-sample values f32, the
 // sums fp64 sums of exact fp64 products (as icp_accumulate_core).
@@ -54,8 +54,8 @@ __host__ __device__ __forceinline__ void track_pose_f32(const double *T, float r
 }
 
 __global__ __launch_bounds__(256) void track_pass_kernel(Cam cam, Grid g, TrackArgs a, const int2 *__restrict__ pool,
-                                                         const IcpState *__restrict__ state, int final_pass, double *__restrict__ slab) {
-    if (state->over || (!final_pass && state->done)) return;      // set by EARLIER launches only: uniform over the grid
+                                                         const IcpState *__restrict__ state, StepKind kind, double *__restrict__ slab) {
+    if (state->over || (kind == STEP_ITERATE && state->done)) return;      // set by EARLIER launches only: uniform over the grid
     __shared__ double sm[4][32];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     float r[9], c[3], cg[3];
@@ -131,7 +131,7 @@ int track_members(int Ws, int Hs) {
 
 // one pass at the pose in state->T; slab: [track_members(Ws, Hs)][32] doubles
 int launch_track_pass(hipStream_t s, const Cam &cam, const Grid &g, const float *depth, float scale, float mind, float maxd, int min_weight,
-                      int stride, double max_dist, const int2 *tsdf, const IcpState *state, int final_pass, double *slab) {
+                      int stride, double max_dist, const int2 *tsdf, const IcpState *state, StepKind kind, double *slab) {
     TrackArgs a;
     a.depth = depth;
     a.scale = scale;
@@ -147,7 +147,7 @@ int launch_track_pass(hipStream_t s, const Cam &cam, const Grid &g, const float 
     a.tx = (a.Ws + 7) / 8;
     a.ty = (a.Hs + 7) / 8;
     const int members = track_members(a.Ws, a.Hs);
-    hipLaunchKernelGGL(track_pass_kernel, dim3(members), dim3(256), 0, s, cam, g, a, tsdf, state, final_pass, slab);
+    hipLaunchKernelGGL(track_pass_kernel, dim3(members), dim3(256), 0, s, cam, g, a, tsdf, state, kind, slab);
     TL3D_HIP(hipGetLastError());
     return TL3D_OK;
 }

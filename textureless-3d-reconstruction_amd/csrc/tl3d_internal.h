@@ -91,6 +91,17 @@ struct IcpState {                // lives in device memory for the whole ICP run
 };
 constexpr int ICP_SUM_E = 27, ICP_SUM_CORR = 28, ICP_SUM_SRC = 29;   // e, cnt and nsrc of IcpState::sums, for the host's read-outs (api_register.hip)
 
+// What a pass of tracking, colour or cloud registration (and the step behind it) is.  STEP_ITERATE: sums, solve, pose update; skipped
+// once the level is done.  STEP_END_LEVEL: sums only, at the level's last pose, and another level follows: the run is over when the
+// level failed or ended with fewer than 8 correspondences, else done / status / iters_run are re-armed (what a host does between
+// tl3d_icp_p2plane calls).  STEP_END_RUN: sums only; nothing follows.  (The pairwise ICP's own final_pass is a 0 / 1 flag.)
+enum StepKind : int { STEP_ITERATE = 0, STEP_END_LEVEL = 1, STEP_END_RUN = 2 };
+// pass `it` of a level with `updates` update passes: those iterate, the one after them ends the level; an evaluation is that last pass alone
+inline StepKind step_kind(int it, int updates, bool last_level, bool evaluate) {
+    if (!evaluate && it < updates) return STEP_ITERATE;
+    return last_level || evaluate ? STEP_END_RUN : STEP_END_LEVEL;
+}
+
 struct IcpRun {                  // per-run arguments of the ICP kernels, read from device memory so that a lane's
     const float *depth_src;      // kernel chain has constant launch arguments and can be replayed as a hipGraph
     const float4 *nmap_tgt;
@@ -657,18 +668,18 @@ int launch_icp_iteration(hipStream_t s, const Cam &cam, const IcpRun *run, int f
 int icp_eval_members(int Ws, int Hs);
 int launch_icp_eval(hipStream_t s, const Cam &cam, const IcpEvalPair *pairs, int n_pairs, int members, float mind, float maxd, float md2, int stride,
                     int Ws, int Hs, double *slab, double *out);
-// tracking against the TSDF (kernels_track.hip: the pass; kernels_icp.hip: the step, next to the solvers it uses)
+// tracking against the TSDF (kernels_track.hip: the pass; kernels_regstep.hip: the step)
 int track_members(int Ws, int Hs);
 int launch_track_pass(hipStream_t s, const Cam &cam, const Grid &g, const float *depth, float scale, float mind, float maxd, int min_weight,
-                      int stride, double max_dist, const int2 *tsdf, const IcpState *state, int final_pass, double *slab);
-int launch_track_step(hipStream_t s, const double *slab, int members, IcpState *state, double damping, double eps, double eig_rel, int final_pass);
-// joint point-to-plane + photometric registration (kernels_rgbd.hip: the intensity maps and the pass; kernels_icp.hip: the step)
+                      int stride, double max_dist, const int2 *tsdf, const IcpState *state, StepKind kind, double *slab);
+int launch_track_step(hipStream_t s, const double *slab, int members, IcpState *state, double damping, double eps, double eig_rel, StepKind kind);
+// joint point-to-plane + photometric registration (kernels_rgbd.hip: the intensity maps and the pass; kernels_regstep.hip: the step)
 int launch_intensity(hipStream_t s, const Cam &cam, const float *depth, const uint8_t *bgr, int radius, float jump, float4 *imap);
 int rgbd_members(int Ws, int Hs);
 int launch_rgbd_pass(hipStream_t s, const Cam &cam, const RgbdPair *pairs, int n_pairs, const RgbdLevel &L, const RgbdState *states,
-                     int final_pass, double *slab);
+                     StepKind kind, double *slab);
 int launch_rgbd_step(hipStream_t s, const double *slab, int n_pairs, int members, RgbdState *states, double photo_weight, double damping,
-                     double eps, double eig_rel, int final_pass);
+                     double eps, double eig_rel, StepKind kind);
 // extraction
 int launch_extract_count(hipStream_t s, const Grid &g, int mode, int min_count, int min_weight, double max_abs,
                          const int2 *tsdf, const unsigned long long *cen, unsigned *block_counts, int nblocks);
@@ -763,7 +774,7 @@ int nearest_triangles_run(tl3d_ctx *ctx, const float *query, long long nq, const
 int distance_summary_run(tl3d_ctx *ctx, const double *dist, long long n, const double *thresholds, int nthr, tl3d_distance_stats *out);
 double nn_default_cell_points(const double mn[3], const double mx[3], long long n);
 
-// registration of two point clouds (kernels_cloudicp.hip; the step kernel is kernels_icp.hip's): device pointers; the run starts at
+// registration of two point clouds (kernels_cloudicp.hip; the step kernel is kernels_regstep.hip's): device pointers; the run starts at
 // the pose in *state (device memory) and leaves its result there, enqueued on the context's stream behind one wait for the bounds
 constexpr int CLOUD_SUMS = 40;           // doubles per block partial: IcpState::sums, [30] the correspondences dropped for a zero normal
 constexpr int CLOUD_SUM_NO_NORMAL = 30;
@@ -771,7 +782,7 @@ int cloud_members(long long n_src);
 int cloud_icp_run(tl3d_ctx *ctx, const float *src, long long n_src, const float *tgt, long long n_tgt, const float *tgt_normals,
                   const tl3d_icp_params *levels, int n_levels, bool evaluate, double cell, IcpState *state, int *index_out);
 int launch_cloud_step(hipStream_t s, const double *slab, int members, IcpState *state, int est_scale, double damping, double eps,
-                      double eig_rel, int final_pass);
+                      double eig_rel, StepKind kind);
 
 // normals and surface variation by k-NN PCA (kernels_normals.hip); device pointers but the viewpoints (host), curvature may be null
 int normals_run(tl3d_ctx *ctx, const float *xyz, long long n, int k, double max_radius, double cell, const double *vp_host, long long n_vp,
