@@ -114,6 +114,11 @@ def main(argv=None):
                              "the scale weakly)")
     parser.add_argument("--compare-align-init", type=str, default=None, metavar="FILE",
                         help="with --compare-align: a 4x4 matrix (.npy or text) mapping reconstruction to scan, where the registration starts")
+    parser.add_argument("--compare-align-global", action="store_true",
+                        help="with --compare-align: find the start on the GPU (FPFH features + RANSAC), so the scan may lie anywhere; "
+                             "rigid only: not with --compare-align-scale or --compare-align-init")
+    parser.add_argument("--compare-align-global-voxel", type=float, default=None, metavar="M",
+                        help="with --compare-align-global: the subsampling voxel in metres (default 5 x the voxel size)")
     parser.add_argument("--cloud-normals", action="store_true",
                         help="give the fused cloud per-point normals on the GPU (PCA over the nearest neighbours, turned towards the "
                              "nearest camera) and write them as nx ny nz")
@@ -197,11 +202,14 @@ def main(argv=None):
             parser.error("--depth-filter: " + str(e))
     if args.compare_threshold and len(args.compare_threshold) > 8:
         parser.error("--compare-threshold: at most 8 thresholds")
-    if args.compare_align or args.compare_align_scale or args.compare_align_init:
+    if (args.compare_align or args.compare_align_scale or args.compare_align_init or args.compare_align_global
+            or args.compare_align_global_voxel is not None):
         from tl3d.pipeline import check_compare_options
         try:
             check_compare_options(argparse.Namespace(compare_to=args.compare_to, compare_align=args.compare_align,
-                                                     compare_align_scale=args.compare_align_scale, compare_align_init=args.compare_align_init))
+                                                     compare_align_scale=args.compare_align_scale, compare_align_init=args.compare_align_init,
+                                                     compare_align_global=args.compare_align_global,
+                                                     compare_align_global_voxel=args.compare_align_global_voxel))
         except ValueError as e:
             parser.error("--compare-align: " + str(e))
     if args.depth_filter and (args.gpus > 1 or world > 1):
@@ -254,7 +262,8 @@ def main(argv=None):
                                   compare_to=args.compare_to, compare_max_dist=args.compare_max_dist,
                                   compare_thresholds=tuple(args.compare_threshold) if args.compare_threshold else (0.005, 0.01, 0.02),
                                   compare_align=args.compare_align, compare_align_scale=args.compare_align_scale,
-                                  compare_align_init=args.compare_align_init)
+                                  compare_align_init=args.compare_align_init, compare_align_global=args.compare_align_global,
+                                  compare_align_global_voxel=args.compare_align_global_voxel)
     pipeline = DepthToReconstructionPipeline(config)
     # a rank decodes every frame on its host (pose chain and scale rule run over the whole sequence) and uploads its share
     streaming = args.stream and dist is None

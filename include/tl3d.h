@@ -879,6 +879,84 @@ int tl3d_cloud_register(tl3d_ctx *ctx, const float *src_hd, int64_t n_src, const
                         const float *tgt_normals_hd, const double T_init[16], double scale_init,
                         const tl3d_icp_params *levels, int n_levels, double cell_size, tl3d_icp_result *out);
 
+/* ---- global registration of two clouds: the front end that finds a start for tl3d_cloud_register ------------
+ * Four calls: subsample, FPFH descriptors, nearest-feature correspondences, RANSAC over three-correspondence samples.  Host or
+ * device pointers throughout (params, the result and the out_* words are host memory); no grid is needed.  All arithmetic is fp64 on
+ * the f32 inputs converted exactly, every operation rounded once, dot products and squared lengths summed in x, y, z order
+ * ((a + b) + c); tests/cloud_global_reference.py restates every sequence.  Every result is the same bytes in every run.
+ *
+ * Voxel subsample.  cell = floor(x / voxel) per axis (fp64 division), a lattice through (0, 0, 0); of every occupied voxel the member
+ * with the smallest index is kept.  index_out [n] receives the kept indices ascending (entries behind *out_n are not written),
+ * *out_n their number: a subset, so normals and colours follow by indexing.  n == 0 is TL3D_OK with *out_n = 0.
+ * TL3D_E_INVALID before any device work: a null ctx, xyz (with n > 0), index_out or out_n, n < 0 or n >= 2^31, a voxel that is not
+ * finite and > 0, an output that overlaps the input; from the bounds pass, with nothing written: a non-finite coordinate, or a
+ * cell with |cell| >= 2^20 on any axis (the three cells make one 63-bit key). */
+int tl3d_cloud_voxel_subsample(tl3d_ctx *ctx, const float *xyz_hd, int64_t n, double voxel, int32_t *index_out_hd, int64_t *out_n);
+
+/* FPFH (Rusu et al. 2009; the pair feature is PCL's and Open3D's).  Neighbourhood N(i): the list tl3d_estimate_normals builds for the
+ * same nb_neighbors (clamped to n) and max_radius (<= 0: none) -- the k smallest under (d2, index), then the members with
+ * d2 <= max_radius^2 -- less the members with d2 == 0 (the point itself, duplicates) and the members whose normal is exactly (0, 0, 0).
+ * Pair feature of (i, j), j in N(i), in list order: d = p_j - p_i, L = sqrt(d2), a1 = (n_i . d) / L, a2 = (n_j . d) / L.  When
+ * |a1| < |a2|: (ns, nt, d, f3) = (n_j, n_i, -d, -a2); otherwise (n_i, n_j, d, a1).  v = d x ns; a pair with |v| == 0 is skipped;
+ * v /= |v| (three divisions by sqrt(v . v)), w = ns x v, f2 = v . nt, f1 = atan2(w . nt, ns . nt).  Bins: b1 = clamp(floor(11 (f1 + pi)
+ * / (2 pi)), 0, 10), b2 = clamp(floor(11 (f2 + 1) / 2), 0, 10), b3 likewise from f3, each product before its division.  Normals are
+ * taken as given: they are not renormalised and their SIGN MATTERS (orient them by a rule that moves with the cloud).
+ * SPFH of i: the 33 integer counts c_i (b1, 11 + b2, 22 + b3 per counted pair) and the number of counted pairs m_i; the spfh_out row
+ * is c_i[0..32], m_i.  A point whose normal is (0, 0, 0) counts nothing.  A point with m_i == 0 has an all-zero FPFH row.  Otherwise
+ * S[b] = sum over j in N(i) with m_j > 0, in list order, of (100 c_j[b] / m_j) / d2_ij; each group of 11 bins with a sum > 0 (added in
+ * bin order) is multiplied by 100 / sum; F_i[b] = S[b] + 100 c_i[b] / m_i, rounded to f32 once.  Counts are exact and the fp64 sums
+ * run in the list's order: the bytes do not depend on cell_size (> 0; it only sets the search grid), fill order or run.
+ * nb_neighbors in [4, 64]; n == 0 is TL3D_OK.  TL3D_E_INVALID before any device work: a null ctx, xyz, normals or fpfh_out, n < 0 or
+ * n >= 2^31, nb_neighbors or cell_size out of range, a NaN max_radius, outputs that overlap an input or each other; from the bounds
+ * pass, with nothing written: a non-finite coordinate.  Normals must be finite. */
+int tl3d_cloud_fpfh(tl3d_ctx *ctx, const float *xyz_hd, const float *normals_hd, int64_t n, int nb_neighbors, double max_radius,
+                    double cell_size, float *fpfh_out_hd /* [n][33] */, int32_t *spfh_out_hd /* [n][34], may be NULL */);
+
+/* Nearest feature.  For every row of a [n_a][dim] the row of b [n_b][dim] minimising (d2, index): d2 = the fp64 sum over
+ * c = 0 .. dim - 1, in that order, of the squared fp64 difference; an exact tie goes to the smaller index.  index_out [n_a] and
+ * dist2_out [n_a] (either may be NULL); n_b == 0 gives -1 and +inf; a row none of whose distances is finite (an infinite or
+ * NaN feature) gets index 0 and +inf.  Brute force on purpose (33 dimensions defeat a cell grid): the
+ * call is refused when n_a * n_b > 2^34 -- a safety condition for a shared device, not a tuning value; subsample first.
+ * TL3D_E_INVALID before any device work: a null ctx, a null a or b with rows, negative sizes, n_a or n_b >= 2^31, dim outside
+ * [1, 64], n_a * n_b > 2^34, an output that overlaps an input or the other output. */
+int tl3d_feature_match(tl3d_ctx *ctx, const float *feat_a_hd, int64_t n_a, const float *feat_b_hd, int64_t n_b, int dim,
+                       int32_t *index_out_hd, double *dist2_out_hd);
+
+/* RANSAC over correspondences corr [m][2] = (source index, target index).  Hypothesis h = 0 .. n_hypotheses - 1 draws the three
+ * correspondence numbers i_j = mix(seed + 0x9E3779B97F4A7C15 * (3 h + j + 1)) mod m, j = 0, 1, 2, in wrapping u64 arithmetic; mix is
+ * the finaliser of MurmurHash3 (x ^= x >> 33; x *= 0xFF51AFD7ED558CCD; x ^= x >> 33; x *= 0xC4CEB9FE1A85EC53; x ^= x >> 33).
+ * Rejected (count -1) when two draws coincide; when for any of the point pairs (0,1), (1,2), (2,0) the source and target edge lengths
+ * ls, lt (sqrt of the squared length) have max == 0 or min(ls, lt) < edge_ratio * max(ls, lt); or when either triad is degenerate.
+ * Triad of three points, for source and target alike: x = (p1 - p0) / |p1 - p0|, z = x x (p2 - p0), degenerate unless |z| > 0,
+ * z /= |z|, y = z x x.  R_ij = (xt_i xs_j + yt_i ys_j) + zt_i zs_j; t = mt - R ms with the means ((p0 + p1) + p2) / 3.  No SVD.
+ * Score: the number of correspondences k with |(R s_k + t) - t_k|^2 <= max_dist * max_dist (one product on the right; a pair exactly
+ * on the threshold counts).  Winner: the maximum over (count, -h) -- the most inliers, the smaller h on a tie.
+ * status 1: a winner; status 2, T = I, best_h -1: nothing passed (m < 3 included).  count_out [n_hypotheses]
+ * (may be NULL): every hypothesis' count, or -1.  The edge-length test assumes ONE scale for both clouds.
+ * TL3D_E_INVALID before any device work: null ctx / params / out, null clouds or corr with entries, negative sizes, sizes >= 2^31,
+ * n_hypotheses outside [1, 2^24], a max_dist that is not finite and > 0, an edge_ratio outside [0, 1], reserved != 0, a count_out
+ * that overlaps an input; from the device passes in front of the draw, with nothing written: a non-finite coordinate, a
+ * correspondence that names a point outside its cloud. */
+typedef struct tl3d_ransac_params {
+    int64_t  n_hypotheses;
+    double   max_dist;
+    double   edge_ratio;        /* 0.9 is the usual value */
+    uint64_t seed;
+    int64_t  reserved;
+} tl3d_ransac_params;
+typedef struct tl3d_ransac_result {
+    double  T[16];              /* row-major, maps source to target */
+    int64_t best_h;
+    int64_t inliers;
+    int64_t n_passed;           /* hypotheses that were scored */
+    int64_t m;
+    int32_t status;
+    int32_t reserved;
+} tl3d_ransac_result;
+int tl3d_cloud_ransac(tl3d_ctx *ctx, const float *src_hd, int64_t n_src, const float *tgt_hd, int64_t n_tgt,
+                      const int32_t *corr_hd, int64_t m, const tl3d_ransac_params *params, tl3d_ransac_result *out,
+                      int32_t *count_out_hd);
+
 /* measurement */
 int tl3d_set_profile(tl3d_ctx *ctx, int count_records, int time_kernels);
 /* Noise-robust registration: normal maps built after this call come from the depth averaged over a (2 radius + 1)^2 window

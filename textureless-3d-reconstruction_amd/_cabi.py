@@ -30,6 +30,7 @@ SYMBOLS = [
     "tl3d_build_intensity_many", "tl3d_download_intensity", "tl3d_rgbd_evaluate_pairs", "tl3d_rgbd_register_pairs",
     "tl3d_nearest_points", "tl3d_nearest_triangles", "tl3d_distance_summary", "tl3d_set_nearest_query_order",
     "tl3d_cloud_evaluate", "tl3d_cloud_register",
+    "tl3d_cloud_voxel_subsample", "tl3d_cloud_fpfh", "tl3d_feature_match", "tl3d_cloud_ransac",
     "tl3d_set_profile", "tl3d_set_normal_smoothing", "tl3d_set_tsdf_pairing", "tl3d_tile_cache_info", "tl3d_class_cache_info", "tl3d_class_refine_info", "tl3d_get_stats", "tl3d_reset_stats", "tl3d_event_record", "tl3d_event_elapsed_ms",
 ]
 
@@ -97,6 +98,16 @@ class DistanceStats(C.Structure):
 class CloudEval(C.Structure):
     _fields_ = [("A", C.c_double * 28), ("b", C.c_double * 7), ("e", C.c_double), ("n_corr", C.c_int64), ("n_src", C.c_int64),
                 ("n_no_normal", C.c_int64)]
+
+
+class RansacParams(C.Structure):
+    _fields_ = [("n_hypotheses", C.c_int64), ("max_dist", C.c_double), ("edge_ratio", C.c_double), ("seed", C.c_uint64),
+                ("reserved", C.c_int64)]
+
+
+class RansacResult(C.Structure):
+    _fields_ = [("T", C.c_double * 16), ("best_h", C.c_int64), ("inliers", C.c_int64), ("n_passed", C.c_int64), ("m", C.c_int64),
+                ("status", C.c_int32), ("reserved", C.c_int32)]
 
 
 class DepthFilterParams(C.Structure):
@@ -290,6 +301,10 @@ def load():
         "tl3d_set_nearest_query_order": [vp, i32],
         "tl3d_cloud_evaluate": [vp, vp, i64, vp, i64, vp, vp, dbl, i32, dbl, dbl, i32, C.POINTER(CloudEval), vp],
         "tl3d_cloud_register": [vp, vp, i64, vp, i64, vp, vp, dbl, C.POINTER(IcpParams), i32, dbl, C.POINTER(IcpResult)],
+        "tl3d_cloud_voxel_subsample": [vp, vp, i64, dbl, vp, C.POINTER(i64)],
+        "tl3d_cloud_fpfh": [vp, vp, vp, i64, i32, dbl, dbl, vp, vp],
+        "tl3d_feature_match": [vp, vp, i64, vp, i64, i32, vp, vp],
+        "tl3d_cloud_ransac": [vp, vp, i64, vp, i64, vp, i64, C.POINTER(RansacParams), C.POINTER(RansacResult), vp],
         "tl3d_set_profile": [vp, i32, i32],
         "tl3d_set_tsdf_pairing": [vp, i32],
         "tl3d_get_stats": [vp, C.POINTER(Stats)],

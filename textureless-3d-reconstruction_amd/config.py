@@ -113,6 +113,15 @@ class ReconstructionConfig:
     compare_align: bool = False
     compare_align_scale: bool = False
     compare_align_init: Optional[object] = None
+    # compare_align_global: the registration's start comes from the global front end on the GPU
+    # (metrics.global_align_clouds: voxel subsample, FPFH, mutual nearest features, RANSAC), so the scan may lie ANYWHERE: no
+    # compare_align_init is needed, and none may be given with it.  compare_align_global_voxel: the subsampling voxel in metres
+    # (None: 5 x voxel_size).  stats["compare"]["alignment"]["global"] = {T, inliers, n_corr, n_passed, hypotheses, voxel, mutual}.
+    # Rigid only: refused together with compare_align_scale (the RANSAC's edge-length test assumes one scale).  Needs geometric
+    # features: on a single plane or a bare wall no sample passes and the local method starts from the identity as before.
+    # Needs compare_align.  Off: nothing changes.
+    compare_align_global: bool = False
+    compare_align_global_voxel: Optional[float] = None
     # normals (and surface variation) of the fused cloud: PCA over each point's cloud_normals_neighbors
     # nearest neighbours (Open3D's max_nn), none further than cloud_normals_radius metres (0: no limit), turned towards the nearest
     # kept camera; once over the whole cloud, after the outlier filter.  DepthToReconstructionPipeline.cloud_normals /

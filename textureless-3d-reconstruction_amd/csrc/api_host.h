@@ -115,6 +115,20 @@ struct ChunkHalves {
 // hipFree's implicit wait keeps work in flight from losing its memory.  Defined in tl3d_api.hip.
 int scratch_carve(tl3d_ctx *ctx, int stage, const size_t *bytes, int n, void **out, const char *what);
 
+// slots of a 64-bit key table that takes max_keys entries at most (keytab.h H3): the smallest power of two >= 1024 and >= 2 * max_keys
+inline size_t kt_slots(size_t max_keys) {
+    size_t cap = 1024;
+    while (cap < 2 * max_keys) cap <<= 1;                  // load <= 0.5
+    return cap;
+}
+
+// Every key of a 64-bit key table (keytab.h) EMPTY, behind what the stream holds already.  A caller that
+// keeps a 32-bit word beside each key carves it too; what it holds, and its fill if it needs one, are the caller's.
+inline int kt_reserve(tl3d_ctx *ctx, unsigned long long *keys, size_t slots) {
+    TL3D_HIP(hipMemsetAsync(keys, 0xFF, slots * sizeof(unsigned long long), ctx->stream));
+    return TL3D_OK;
+}
+
 // grow-on-demand device scratch of `need` elements: on failure the buffer is gone and its capacity 0
 template <class T> int grow(T **p, size_t *cap, size_t need, const char *what) {
     if (need <= *cap) return TL3D_OK;

@@ -27,20 +27,6 @@ static int cc_check_mesh(const uint32_t *tri, int64_t n_tri, int64_t n_vert, con
 static size_t mio_chunks(int64_t n_tri, int64_t n_vert) { return (size_t)chunks_of(n_vert) + (size_t)chunks_of(n_tri) + 2; }
 constexpr size_t MIO_INFO_BYTES = 8 * sizeof(unsigned long long);
 
-// slots of a table that takes max_keys entries at most (keytab.h H3): the smallest power of two >= 1024 and >= 2 * max_keys
-static size_t kt_slots(size_t max_keys) {
-    size_t cap = 1024;
-    while (cap < 2 * max_keys) cap <<= 1;                  // load <= 0.5
-    return cap;
-}
-
-// Every key of a 64-bit key table (keytab.h) EMPTY, behind what the stream holds already.  A caller that
-// keeps a 32-bit word beside each key carves it too; what it holds, and its fill if it needs one, are the caller's.
-static int kt_reserve(tl3d_ctx *ctx, unsigned long long *keys, size_t slots) {
-    TL3D_HIP(hipMemsetAsync(keys, 0xFF, slots * sizeof(unsigned long long), ctx->stream));
-    return TL3D_OK;
-}
-
 // The validation sequence of the calls that take one indexed mesh: the report words zeroed, the largest triangle index
 // (cc_validate_kernel) into word 0, the caller's own validator (`second`, if it has one) into word 1, one wait, and the refusal of
 // an index beyond n_vert.  *word1 = what `second` counted: the caller refuses it in its own words.  Nothing of the call indexes by

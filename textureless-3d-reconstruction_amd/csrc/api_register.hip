@@ -971,4 +971,140 @@ int tl3d_cloud_register(tl3d_ctx *ctx, const float *src, int64_t n_src, const fl
     return TL3D_OK;
 }
 
+// ------------------------------------------------------------------------------------------- global registration
+int tl3d_cloud_voxel_subsample(tl3d_ctx *ctx, const float *xyz, int64_t n, double voxel, int32_t *index_out, int64_t *out_n) {
+    REQUIRE(ctx && index_out && out_n, TL3D_E_INVALID, "null argument");
+    REQUIRE(n >= 0 && n < (1ll << 31) && (n == 0 || xyz), TL3D_E_INVALID, "bad point list (0 <= n < 2^31)");
+    REQUIRE(isfinite(voxel) && voxel > 0, TL3D_E_INVALID, "voxel must be finite and positive");
+    REQUIRE(!ranges_overlap(index_out, (size_t)n * 4, xyz, (size_t)n * 12), TL3D_E_INVALID, "the output aliases the input");
+    if (n == 0) {
+        *out_n = 0;
+        return TL3D_OK;
+    }
+    TL3D_HIP(hipSetDevice(ctx->device));
+    Staging st(ctx);
+    const float *dx;
+    int32_t *di;
+    int rc = st.in(xyz, (size_t)n * 12, &dx);
+    if (!rc) rc = st.out(index_out, (size_t)n * 4, &di);
+    if (rc) return rc;
+    long long kept = 0;
+    rc = voxel_subsample_run(ctx, dx, n, voxel, kt_slots((size_t)n), di, &kept);
+    if (rc) return rc;                                      // (a refusal leaves the caller's array and *out_n as they were)
+    if (di != index_out) {                                  // a host output: the kept prefix alone goes back
+        TL3D_HIP(hipMemcpyAsync(index_out, di, (size_t)kept * 4, hipMemcpyDeviceToHost, ctx->stream));
+        TL3D_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    *out_n = kept;
+    return TL3D_OK;
+}
+
+int tl3d_cloud_fpfh(tl3d_ctx *ctx, const float *xyz, const float *normals, int64_t n, int nb_neighbors, double max_radius, double cell_size,
+                    float *fpfh_out, int32_t *spfh_out) {
+    REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
+    REQUIRE(n >= 0 && n < (1ll << 31), TL3D_E_INVALID, "n %lld: indices need 0 <= n < 2^31", (long long)n);
+    REQUIRE(n == 0 || (xyz && normals && fpfh_out), TL3D_E_INVALID, "null argument");
+    REQUIRE(nb_neighbors >= 4 && nb_neighbors <= 64, TL3D_E_INVALID, "nb_neighbors must be in [4,64]");
+    REQUIRE(cell_size > 0 && isfinite(cell_size), TL3D_E_INVALID, "cell_size must be positive");
+    REQUIRE(!(max_radius != max_radius), TL3D_E_INVALID, "max_radius is not a number");
+    const size_t nb_x = (size_t)n * 12, nb_f = (size_t)n * 33 * 4, nb_s = (size_t)n * 34 * 4;
+    const void *ins[2] = {xyz, normals};
+    for (int i = 0; i < 2; ++i)
+        REQUIRE(!ranges_overlap(fpfh_out, nb_f, ins[i], nb_x) && !ranges_overlap(spfh_out, nb_s, ins[i], nb_x), TL3D_E_INVALID, "an output aliases an input");
+    REQUIRE(!ranges_overlap(fpfh_out, nb_f, spfh_out, nb_s), TL3D_E_INVALID, "the outputs alias each other");
+    if (n == 0) return TL3D_OK;
+    TL3D_HIP(hipSetDevice(ctx->device));
+    Staging st(ctx);
+    const float *dx, *dn;
+    float *df;
+    int32_t *dsp = nullptr;
+    int rc = st.in(xyz, nb_x, &dx);
+    if (!rc) rc = st.in(normals, nb_x, &dn);
+    if (!rc) rc = st.out(fpfh_out, nb_f, &df);
+    if (!rc && spfh_out) rc = st.out(spfh_out, nb_s, &dsp);
+    if (rc) return rc;
+    return st.finish(fpfh_run(ctx, dx, dn, n, nb_neighbors, max_radius, cell_size, df, dsp), true);
+}
+
+int tl3d_feature_match(tl3d_ctx *ctx, const float *feat_a, int64_t n_a, const float *feat_b, int64_t n_b, int dim, int32_t *index_out,
+                       double *dist2_out) {
+    REQUIRE(ctx != nullptr, TL3D_E_INVALID, "null ctx");
+    REQUIRE(n_a >= 0 && n_b >= 0 && n_a < (1ll << 31) && n_b < (1ll << 31), TL3D_E_INVALID, "n_a %lld, n_b %lld: sizes must be in [0, 2^31)",
+            (long long)n_a, (long long)n_b);
+    REQUIRE((n_a == 0 || feat_a) && (n_b == 0 || feat_b), TL3D_E_INVALID, "null feature array");
+    REQUIRE(dim >= 1 && dim <= 64, TL3D_E_INVALID, "dim must be in [1,64]");
+    REQUIRE(n_a == 0 || n_b <= (1ll << 34) / n_a, TL3D_E_INVALID,
+            "n_a %lld x n_b %lld exceeds 2^34 feature pairs: the match is brute force, subsample the clouds first", (long long)n_a, (long long)n_b);
+    const size_t nb_a = (size_t)n_a * dim * 4, nb_b = (size_t)n_b * dim * 4, nb_i = (size_t)n_a * 4, nb_d = (size_t)n_a * 8;
+    REQUIRE(!ranges_overlap(index_out, nb_i, feat_a, nb_a) && !ranges_overlap(index_out, nb_i, feat_b, nb_b) &&
+                !ranges_overlap(dist2_out, nb_d, feat_a, nb_a) && !ranges_overlap(dist2_out, nb_d, feat_b, nb_b),
+            TL3D_E_INVALID, "an output aliases an input");
+    REQUIRE(!ranges_overlap(index_out, nb_i, dist2_out, nb_d), TL3D_E_INVALID, "the outputs alias each other");
+    if (n_a == 0 || (!index_out && !dist2_out)) return TL3D_OK;
+    TL3D_HIP(hipSetDevice(ctx->device));
+    Staging st(ctx);
+    const float *da, *db = nullptr;
+    int32_t *di = nullptr;
+    double *dd = nullptr;
+    int rc = st.in(feat_a, nb_a, &da);
+    if (!rc && n_b) rc = st.in(feat_b, nb_b, &db);
+    if (!rc && index_out) rc = st.out(index_out, nb_i, &di);
+    if (!rc && dist2_out) rc = st.out(dist2_out, nb_d, &dd);
+    if (rc) return rc;
+    return st.finish(feature_match_run(ctx, da, n_a, db, n_b, dim, di, dd), true);
+}
+
+int tl3d_cloud_ransac(tl3d_ctx *ctx, const float *src, int64_t n_src, const float *tgt, int64_t n_tgt, const int32_t *corr, int64_t m,
+                      const tl3d_ransac_params *params, tl3d_ransac_result *out, int32_t *count_out) {
+    REQUIRE(ctx && params && out, TL3D_E_INVALID, "null argument");
+    REQUIRE(n_src >= 0 && (n_src == 0 || src), TL3D_E_INVALID, "bad source list");
+    REQUIRE(n_tgt >= 0 && (n_tgt == 0 || tgt), TL3D_E_INVALID, "bad target list");
+    REQUIRE(m >= 0 && (m == 0 || corr), TL3D_E_INVALID, "bad correspondence list");
+    REQUIRE(m == 0 || (n_src > 0 && n_tgt > 0), TL3D_E_INVALID, "correspondences into an empty cloud");
+    REQUIRE(n_src < (1ll << 31) && n_tgt < (1ll << 31) && m < (1ll << 31), TL3D_E_INVALID, "n_src %lld, n_tgt %lld, m %lld: sizes must stay below 2^31",
+            (long long)n_src, (long long)n_tgt, (long long)m);
+    const int64_t H = params->n_hypotheses;
+    REQUIRE(H >= 1 && H <= (1ll << 24), TL3D_E_INVALID, "n_hypotheses must be in [1, 2^24]");
+    REQUIRE(isfinite(params->max_dist) && params->max_dist > 0, TL3D_E_INVALID, "max_dist must be finite and positive");
+    REQUIRE(params->edge_ratio >= 0 && params->edge_ratio <= 1, TL3D_E_INVALID, "edge_ratio must be in [0,1]");
+    REQUIRE(params->reserved == 0, TL3D_E_INVALID, "reserved must be 0");
+    const size_t nb_c = (size_t)H * 4;
+    REQUIRE(!ranges_overlap(count_out, nb_c, src, (size_t)n_src * 12) && !ranges_overlap(count_out, nb_c, tgt, (size_t)n_tgt * 12) &&
+                !ranges_overlap(count_out, nb_c, corr, (size_t)m * 8),
+            TL3D_E_INVALID, "the output aliases an input");
+    if (m == 0) {                                           // nothing to draw from
+        if (count_out) {
+            TL3D_HIP(hipSetDevice(ctx->device));
+            Staging st(ctx);
+            int32_t *dc = nullptr;
+            int rc = st.out(count_out, nb_c, &dc);
+            if (rc) return rc;
+            TL3D_HIP(hipMemsetAsync(dc, 0xff, nb_c, ctx->stream));
+            rc = st.finish(TL3D_OK, true);
+            if (rc) return rc;
+        }
+        memset(out, 0, sizeof(*out));
+        out->T[0] = out->T[5] = out->T[10] = out->T[15] = 1.0;
+        out->best_h = -1;
+        out->status = 2;
+        return TL3D_OK;
+    }
+    TL3D_HIP(hipSetDevice(ctx->device));
+    Staging st(ctx);
+    const float *ds, *dt;
+    const int32_t *dcorr;
+    int32_t *dc = nullptr;
+    int rc = st.in(src, (size_t)n_src * 12, &ds);
+    if (!rc) rc = st.in(tgt, (size_t)n_tgt * 12, &dt);
+    if (!rc) rc = st.in(corr, (size_t)m * 8, &dcorr);
+    if (!rc && count_out) rc = st.out(count_out, nb_c, &dc);
+    if (rc) return rc;
+    tl3d_ransac_result res;
+    memset(&res, 0, sizeof(res));
+    rc = st.finish(ransac_run(ctx, ds, n_src, dt, n_tgt, dcorr, m, *params, &res, dc), true);
+    if (rc) return rc;
+    *out = res;
+    return TL3D_OK;
+}
+
 }  // extern "C"

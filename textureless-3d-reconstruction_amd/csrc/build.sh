@@ -16,7 +16,7 @@ fi
 OBJS=()
 PIDS=()
 mkdir -p "${BUILD}"
-for f in tl3d_api api_fuse api_mesh api_register kernels_backproject kernels_centroid kernels_tsdf_prep kernels_tsdf kernels_icp kernels_regstep kernels_icp_eval kernels_compact kernels_extract kernels_mesh kernels_meshcc kernels_meshsimplify kernels_meshsmooth kernels_meshweld kernels_raycast kernels_track kernels_rgbd kernels_cellgrid kernels_sor kernels_nearest kernels_cloudicp kernels_normals kernels_planes kernels_depthfilter kernels_grid; do
+for f in tl3d_api api_fuse api_mesh api_register kernels_backproject kernels_centroid kernels_tsdf_prep kernels_tsdf kernels_icp kernels_regstep kernels_icp_eval kernels_compact kernels_extract kernels_mesh kernels_meshcc kernels_meshsimplify kernels_meshsmooth kernels_meshweld kernels_raycast kernels_track kernels_rgbd kernels_cellgrid kernels_sor kernels_nearest kernels_cloudicp kernels_cloudglobal kernels_normals kernels_planes kernels_depthfilter kernels_grid; do
   src="${HERE}/${f}.hip"; obj="${BUILD}/${f}.o"
   stale=0                                          # no object yet, or the source or ANY header is newer than it
   for dep in "$src" "${HERE}"/*.h "${HERE}/../../include/tl3d.h"; do

@@ -143,6 +143,56 @@ __device__ __forceinline__ void cell_face_bound(double u, int c, int r, int n, d
     }
 }
 
+// ---- the k nearest of a point of the indexed list itself ------------------------------------------------------------------------------
+// What cloud normals (kernels_normals.hip) and the FPFH descriptors (kernels_cloudglobal.hip) search with: the k <= KMAX best
+// (d2, index) pairs around the point p of the sorted list (EmitPointIndex), in registers (ordered insert over static indices, as
+// sor_knn_kernel's list); the order is the PAIR's, so neither the fill order inside a cell (atomics) nor the cell size shows in which
+// points are kept or in the order they are listed.  The walk ends when no face of the walked cube has cells behind it, when the
+// k-th pair's d2 lies strictly under the bound of everything not yet walked (a tie further out may have the smaller index), or when
+// that bound exceeds md2 (the squared radius, INFINITY for none).  The bound is cell_face_bound's for a point inside the grid: the
+// other axes add nothing.  bd / bi must come in as INFINITY / 0x7fffffff; entries the list does not reach stay so.
+__device__ __forceinline__ bool knn_less(double a, int ai, double b, int bi) { return a < b || (a == b && ai < bi); }   // (a, ai) < (b, bi)
+
+template <int KMAX>
+__device__ __forceinline__ void cell_knn_search(const CellGrid &g, const unsigned *__restrict__ start, const float4 *__restrict__ sorted, double px,
+                                                double py, double pz, int k, double md2, double (&bd)[KMAX], int (&bi)[KMAX]) {
+    const double u0 = cell_u(px, g.ox, g.inv_cell), u1 = cell_u(py, g.oy, g.inv_cell), u2 = cell_u(pz, g.oz, g.inv_cell);
+    const int c0 = cell_clampi(u0, g.nx), c1 = cell_clampi(u1, g.ny), c2 = cell_clampi(u2, g.nz);
+    const double nmax = (double)max(g.nx, max(g.ny, g.nz)) + 1.0;
+    for (int r = 0;; ++r) {
+        cell_shell_walk(g, start, c0, c1, c2, r, [&](unsigned s, unsigned e) {
+            for (unsigned q = s; q < e; ++q) {
+                const float4 p = sorted[q];
+                const double dx = (double)p.x - px, dy = (double)p.y - py, dz = (double)p.z - pz;
+                double v = dx * dx + dy * dy + dz * dz;
+                int vi = __float_as_int(p.w);
+                if (knn_less(v, vi, bd[KMAX - 1], bi[KMAX - 1])) {
+#pragma unroll
+                    for (int j = 0; j < KMAX; ++j) {               // ordered insert, static indices -> registers
+                        const double b = bd[j];
+                        const int ib = bi[j];
+                        const bool sw = knn_less(v, vi, b, ib);
+                        bd[j] = sw ? v : b;
+                        bi[j] = sw ? vi : ib;
+                        v = sw ? b : v;
+                        vi = sw ? ib : vi;
+                    }
+                }
+            }
+        });
+        double bound2 = INFINITY;
+        bool open = false;
+        cell_face_bound(u0, c0, r, g.nx, nmax, g.cell, 0.0, bound2, open);
+        cell_face_bound(u1, c1, r, g.ny, nmax, g.cell, 0.0, bound2, open);
+        cell_face_bound(u2, c2, r, g.nz, nmax, g.cell, 0.0, bound2, open);
+        double kth = INFINITY;
+#pragma unroll
+        for (int j = 0; j < KMAX; ++j)
+            if (j == k - 1) kth = bd[j];
+        if (!open || kth < bound2 || bound2 > md2) break;
+    }
+}
+
 // ---- the nearest-point candidate ---------------------------------------------------------------------------------------------------
 // what a nearest search keeps (kernels_nearest.hip, kernels_cloudicp.hip): the minimum over the pair (d2, index), and the evaluation
 // of a run of a point target's sorted list against a query in fp64

@@ -6,12 +6,9 @@
 // original index beside the point.  Thread t serves the point in slot t of that sorted list, so the lanes of a wave are neighbours in
 // space and walk the same few cells; the result is scattered back by the original index.  (The sorted list IS the cell order of the
 // queries: the second build that the searches of kernels_nearest.hip need for a foreign query set has nothing to add here.)
-//   search   the shells of growing Chebyshev radius around the point's cell (cell_shell_walk).  The k best (d2, index) pairs live in
-//            registers (ordered insert over static indices, as sor_knn_kernel's list); the order is the PAIR's, so neither the fill
-//            order inside a cell (atomics) nor the cell size shows in which points are kept or in the order they are summed in.  The
-//            search ends when no face of the walked cube has cells behind it, when the k-th pair's d2 lies strictly under the bound
-//            of everything not yet walked (a tie further out may have the smaller index), or when that bound exceeds max_radius^2.
-//            The bound is cell_face_bound's (cellgrid.h) for a point inside the grid: the other axes add nothing.
+//   search   cell_knn_search (cellgrid.h, shared with the FPFH descriptors): the shells of growing Chebyshev radius around the
+//            point's cell, the k best (d2, index) pairs in registers; the order is the PAIR's, so neither the fill order inside a
+//            cell nor the cell size shows in which points are kept or in the order they are summed in.
 //   PCA      e_j = p_j - p_i fetched again by index (twice: mean, then centred products; the list cannot hold 64 points beside the
 //            pairs), all in fp64 in list order; sym3_eigen.h solves the 3x3.
 //   sign     the viewpoints pass through LDS in chunks of 256; nearest by (d2, index); n . (c - p) < 0 negates.
@@ -24,9 +21,6 @@
 namespace tl3d {
 
 constexpr int NRM_VP_CHUNK = 256;       // viewpoints per LDS chunk (one per thread of the block: 6 KB)
-
-// (a, ai) < (b, bi) in the order (d2, index)
-__device__ __forceinline__ bool nrm_less(double a, int ai, double b, int bi) { return a < b || (a == b && ai < bi); }
 
 template <int KMAX>
 __global__ __launch_bounds__(256) void normals_kernel(CellGrid g, const float *__restrict__ xyz, long long n, int k, double md2,
@@ -45,43 +39,7 @@ __global__ __launch_bounds__(256) void normals_kernel(CellGrid g, const float *_
 #pragma unroll
     for (int j = 0; j < KMAX; ++j) { bd[j] = INFINITY; bi[j] = 0x7fffffff; }
 
-    if (live) {
-        const double u0 = cell_u(px, g.ox, g.inv_cell), u1 = cell_u(py, g.oy, g.inv_cell), u2 = cell_u(pz, g.oz, g.inv_cell);
-        const int c0 = cell_clampi(u0, g.nx), c1 = cell_clampi(u1, g.ny), c2 = cell_clampi(u2, g.nz);
-        const double nmax = (double)max(g.nx, max(g.ny, g.nz)) + 1.0;
-        for (int r = 0;; ++r) {
-            cell_shell_walk(g, start, c0, c1, c2, r, [&](unsigned s, unsigned e) {
-                for (unsigned q = s; q < e; ++q) {
-                    const float4 p = sorted[q];
-                    const double dx = (double)p.x - px, dy = (double)p.y - py, dz = (double)p.z - pz;
-                    double v = dx * dx + dy * dy + dz * dz;
-                    int vi = __float_as_int(p.w);
-                    if (nrm_less(v, vi, bd[KMAX - 1], bi[KMAX - 1])) {
-#pragma unroll
-                        for (int j = 0; j < KMAX; ++j) {               // ordered insert, static indices -> registers
-                            const double b = bd[j];
-                            const int ib = bi[j];
-                            const bool sw = nrm_less(v, vi, b, ib);
-                            bd[j] = sw ? v : b;
-                            bi[j] = sw ? vi : ib;
-                            v = sw ? b : v;
-                            vi = sw ? ib : vi;
-                        }
-                    }
-                }
-            });
-            double bound2 = INFINITY;
-            bool open = false;
-            cell_face_bound(u0, c0, r, g.nx, nmax, g.cell, 0.0, bound2, open);
-            cell_face_bound(u1, c1, r, g.ny, nmax, g.cell, 0.0, bound2, open);
-            cell_face_bound(u2, c2, r, g.nz, nmax, g.cell, 0.0, bound2, open);
-            double kth = INFINITY;
-#pragma unroll
-            for (int j = 0; j < KMAX; ++j)
-                if (j == k - 1) kth = bd[j];
-            if (!open || kth < bound2 || bound2 > md2) break;
-        }
-    }
+    if (live) cell_knn_search<KMAX>(g, start, sorted, px, py, pz, k, md2, bd, bi);
 
     // the neighbourhood: the first k entries that exist and lie within the radius (the list is ordered: they are a prefix)
     int cnt = 0;

@@ -1,6 +1,6 @@
-// keytab.h -- the device half of the 64-bit key table that vertex clustering, the smoothing's edge list and the mesh weld share
-// ("The key table").  An open-addressing table of `mask + 1` words (a power of two), filled with 0xFF
-// by the host (kt_reserve, api_mesh.hip) before the call's first insert, probed linearly.  A table holds keys and nothing else: what
+// keytab.h -- the device half of the 64-bit key table that vertex clustering, the smoothing's edge list, the mesh weld and the
+// cloud's voxel subsample (kernels_cloudglobal.hip) share ("The key table").  An open-addressing table of
+// `mask + 1` words (a power of two), filled with 0xFF by the host (kt_reserve, api_host.h) before the call's first insert, probed linearly.  A table holds keys and nothing else: what
 // a user keeps beside a key (a leader, an output index) lives in an array of its own, indexed by the slot these functions return,
 // and its obligations (H2 of the user's file) stay with the user.
 //

@@ -788,6 +788,13 @@ int launch_cloud_step(hipStream_t s, const double *slab, int members, IcpState *
 int normals_run(tl3d_ctx *ctx, const float *xyz, long long n, int k, double max_radius, double cell, const double *vp_host, long long n_vp,
                 float *normal, float *curvature, long long *degenerate);
 
+// global registration (kernels_cloudglobal.hip): device pointers but the RANSAC's params and result (host).  slots: kt_slots(n).
+int voxel_subsample_run(tl3d_ctx *ctx, const float *xyz, long long n, double voxel, size_t slots, int *index_out, long long *kept);
+int fpfh_run(tl3d_ctx *ctx, const float *xyz, const float *nrm, long long n, int k, double max_radius, double cell, float *fpfh_out, int *spfh_out);
+int feature_match_run(tl3d_ctx *ctx, const float *fa, long long na, const float *fb, long long nb, int dim, int *index_out, double *dist2_out);
+int ransac_run(tl3d_ctx *ctx, const float *src, long long n_src, const float *tgt, long long n_tgt, const int *corr, long long m,
+               const tl3d_ransac_params &prm, tl3d_ransac_result *out, int *count_out);
+
 // planar regions of a cloud (kernels_planes.hip); device pointers but planes_hd (host or device) and counts (host); curvature may be null
 int planes_run(tl3d_ctx *ctx, const float *xyz, const float *nrm, const float *curv, long long n, const tl3d_plane_params &prm, double cell,
                int *plane_id, tl3d_plane *planes_hd, long long plane_cap, long long counts[4], bool *short_cap);

@@ -1233,6 +1233,91 @@ class FusionContext:
                                                 float(cell_size) if cell_size is not None else 0.0, C.byref(res)))
         return _icp_result_dicts(res)[0]
 
+    # ---- global registration: a start for register_clouds from anywhere (needs no grid) ----
+    @staticmethod
+    def _like(a, shape, dtype):
+        """An uninitialised output beside a: a device tensor for a device tensor, else a numpy array (dtype: a numpy type)."""
+        if hasattr(a, "data_ptr"):
+            import torch
+            return torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), device=a.device)
+        return np.empty(shape, dtype)
+
+    def voxel_subsample(self, xyz, voxel):
+        """int32 [kept], ascending: of every occupied voxel of the lattice through (0, 0, 0) (cell = floor(x / voxel)) the index of
+        the member with the smallest index (tl3d_cloud_voxel_subsample).  A subset: xyz[index], normals[index], ... follow by
+        indexing.  numpy in, numpy out; a device tensor in, a device tensor out."""
+        xyz = self._points(xyz)
+        n = len(xyz)
+        index = self._like(xyz, (n,), np.int32)
+        kept = C.c_int64(0)
+        abi.check(self._lib.tl3d_cloud_voxel_subsample(self._h, abi.ptr(xyz) if n else None, n, float(voxel), abi.ptr(index),
+                                                       C.byref(kept)))
+        return index[:kept.value]
+
+    def compute_fpfh(self, xyz, normals, nb_neighbors=48, max_radius=0.0, cell_size=None, spfh=False):
+        """FPFH descriptors float32 [n,33] (tl3d_cloud_fpfh), or (fpfh, spfh int32 [n,34]: the 33 pair counts and their number) with
+        spfh=True.  The neighbourhood is estimate_normals' list for the same nb_neighbors (4..64) and max_radius, less the point itself,
+        duplicates and members with a (0,0,0) normal.  The normals are taken as given and their SIGN MATTERS: orient them by a rule
+        that moves with the cloud (metrics.global_align_clouds uses the cloud's centroid as the viewpoint).  cell_size sets the
+        search grid only; the result does not depend on it.  numpy in, numpy out; device tensors in, device tensors out."""
+        xyz, normals = self._points(xyz), self._points(normals)
+        n = len(xyz)
+        assert len(normals) == n, f"{len(normals)} normals for {n} points"
+        fpfh = self._like(xyz, (n, 33), np.float32)
+        counts = self._like(xyz, (n, 34), np.int32) if spfh else None
+        cell = float(cell_size) if cell_size is not None else (float(max_radius) / 2 if max_radius and max_radius > 0 else
+                                                                (self.grid.voxel_size * 2 if self.grid else 0.01))
+        if n:
+            abi.check(self._lib.tl3d_cloud_fpfh(self._h, abi.ptr(xyz), abi.ptr(normals), n, int(nb_neighbors), float(max_radius), cell,
+                                                abi.ptr(fpfh), abi.ptr(counts)))
+        return (fpfh, counts) if spfh else fpfh
+
+    def match_features(self, feat_a, feat_b, dist2=False):
+        """int32 [n_a]: for every row of feat_a the row of feat_b with the smallest squared distance (fp64 sum over the columns in
+        order; an exact tie goes to the smaller index; -1 for an empty feat_b), or (index, dist2 float64 [n_a]) with dist2=True
+        (tl3d_feature_match).  Brute force: refused when n_a * n_b > 2^34 -- subsample first.  At most 64 columns."""
+        def rows(a):
+            if hasattr(a, "data_ptr"):
+                import torch
+                return a.to(dtype=torch.float32).contiguous()
+            return np.ascontiguousarray(a, dtype=np.float32)
+        feat_a, feat_b = rows(feat_a), rows(feat_b)
+        assert feat_a.ndim == 2 and feat_b.ndim == 2 and feat_a.shape[1] == feat_b.shape[1], "features must be [n, dim] with one dim"
+        na, nb, dim = feat_a.shape[0], feat_b.shape[0], feat_a.shape[1]
+        index = self._like(feat_a, (na,), np.int32)
+        d2 = self._like(feat_a, (na,), np.float64) if dist2 else None
+        abi.check(self._lib.tl3d_feature_match(self._h, abi.ptr(feat_a) if na else None, na, abi.ptr(feat_b) if nb else None, nb, int(dim),
+                                               abi.ptr(index) if na else None, abi.ptr(d2) if dist2 and na else None))
+        return (index, d2) if dist2 else index
+
+    def ransac_register(self, source, target, corr, hypotheses=100_000, max_dist=0.05, edge_ratio=0.9, seed=0, counts=False):
+        """RANSAC over correspondences corr int32 [m,2] = (source index, target index) (tl3d_cloud_ransac): `hypotheses` samples of
+        three correspondences drawn by a counter-based generator from `seed`, rejected unless the three edge lengths agree within
+        edge_ratio, posed by the triad construction and scored by the correspondences within max_dist.  A dict: T (4 x 4, source
+        to target; the identity when nothing passed), status (1: a winner; 2: nothing passed), best_h, inliers, n_passed (hypotheses
+        scored), m; with counts=True also counts (int32 per hypothesis, -1: rejected).  The same bytes in every run."""
+        source, target = self._points(source), self._points(target)
+        if hasattr(corr, "data_ptr"):
+            import torch
+            corr = corr.to(dtype=torch.int32).reshape(-1, 2).contiguous()
+        else:
+            corr = np.ascontiguousarray(corr, dtype=np.int32).reshape(-1, 2)
+        m = len(corr)
+        prm = abi.RansacParams(n_hypotheses=int(hypotheses), max_dist=float(max_dist), edge_ratio=float(edge_ratio),
+                               seed=int(seed) & (2 ** 64 - 1), reserved=0)
+        res = abi.RansacResult()
+        cnt = self._like(corr, (int(hypotheses),), np.int32) if counts else None
+
+        def p(a):
+            return abi.ptr(a) if a is not None and len(a) else None
+        abi.check(self._lib.tl3d_cloud_ransac(self._h, p(source), len(source), p(target), len(target), p(corr), m, C.byref(prm),
+                                              C.byref(res), p(cnt)))
+        out = dict(T=np.array(res.T[:], np.float64).reshape(4, 4), status=res.status, best_h=res.best_h, inliers=res.inliers,
+                   n_passed=res.n_passed, m=res.m)
+        if counts:
+            out["counts"] = cnt
+        return out
+
     # ---- measurement -----------------------------------------------------------------------
     def set_profile(self, count_records=False, time_kernels=False):
         abi.check(self._lib.tl3d_set_profile(self._h, int(count_records), int(time_kernels)))

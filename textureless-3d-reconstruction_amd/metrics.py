@@ -50,11 +50,74 @@ def move_points(points, T, scale=1.0):
     return (float(scale) * (p @ T[:3, :3].T) + T[:3, 3]).astype(np.float32)
 
 
-def align_clouds(ctx, a, b, b_normals=None, **kw):
+def _host_points(a):
+    import numpy as np
+    if hasattr(a, "data_ptr"):
+        a = a.detach().cpu().numpy()
+    return np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 3)
+
+
+def global_align_clouds(ctx, a, b, voxel, nb_neighbors=48, feature_radius=None, normal_neighbors=30, max_dist=None,
+                        hypotheses=100_000, seed=0, mutual=True) -> dict:
+    """A pose of cloud a in cloud b's frame from ANY start: the standard global front end, every stage on the
+    GPU.  In order: (1) voxel_subsample both clouds at `voxel`; (2) estimate_normals of each subsample (normal_neighbors, within
+    feature_radius) with the subsample's own fp64 centroid as the one viewpoint; (3) compute_fpfh (nb_neighbors within
+    feature_radius, default 5 voxels); (4) match_features both ways; (5) keep the pairs that choose each other, or with mutual off,
+    or when fewer than 3 % of a's points have such a partner, all pairs a -> b; (6) ransac_register (max_dist default 1.5 voxels).
+    The normals are estimated here, not taken from the caller, because the pair feature depends on each normal's SIGN, so both
+    clouds need one orientation rule that moves with the cloud: "towards the cloud's own centroid" is a function of the point set
+    alone, while normals turned towards a sensor, or signed arbitrarily, are not.
+    Returns ransac_register's dict (T, status, best_h, inliers, n_passed, m) with n_a and n_b (points after subsampling), n_corr,
+    n_mutual, mutual (whether the mutual pairs were used), hypotheses and voxel beside it.  status 2 and T = identity: no sample of
+    three correspondences kept its edge lengths -- a scene without geometric features (a single plane, a bare corridor wall) gives
+    the features nothing to tell its points apart by; symmetric objects have several answers; partial overlap moves the centroid
+    rule; rigid only (one scale)."""
+    import numpy as np
+    voxel = float(voxel)
+    radius = float(feature_radius) if feature_radius is not None else 5.0 * voxel
+    gate = float(max_dist) if max_dist is not None else 1.5 * voxel
+    feats, pts = [], []
+    for cloud in (a, b):
+        p = _host_points(cloud)
+        p = p[ctx.voxel_subsample(p, voxel)]
+        if len(p) >= 3:
+            c = p.astype(np.float64).mean(axis=0)
+            nrm = ctx.estimate_normals(p, nb_neighbors=int(normal_neighbors), max_radius=radius, viewpoints=c[None], cell_size=radius / 2)
+            f = ctx.compute_fpfh(p, nrm, nb_neighbors=int(nb_neighbors), max_radius=radius, cell_size=radius / 2)
+        else:
+            f = np.zeros((len(p), 33), np.float32)
+        pts.append(p)
+        feats.append(f)
+    ab = ctx.match_features(feats[0], feats[1])
+    ba = ctx.match_features(feats[1], feats[0])
+    ia = np.arange(len(ab), dtype=np.int32)
+    has = ab >= 0
+    is_mutual = has.copy()
+    is_mutual[has] = ba[ab[has]] == ia[has]
+    n_mutual = int(is_mutual.sum())
+    use_mutual = bool(mutual) and n_mutual >= 0.03 * len(ab)
+    keep = is_mutual if use_mutual else has
+    corr = np.ascontiguousarray(np.stack([ia[keep], ab[keep]], axis=1), dtype=np.int32)
+    res = ctx.ransac_register(pts[0], pts[1], corr, hypotheses=hypotheses, max_dist=gate, seed=seed)
+    res.update(n_a=len(pts[0]), n_b=len(pts[1]), n_corr=len(corr), n_mutual=n_mutual, mutual=use_mutual, hypotheses=int(hypotheses),
+               voxel=voxel)
+    return res
+
+
+def align_clouds(ctx, a, b, b_normals=None, global_kw=None, **kw):
     """Register cloud a onto cloud b (FusionContext.register_clouds; kw: T_init, scale_init, levels, estimate_scale, cell_size) and
     return (the result, a moved into b's frame: scale * R a + t, float32 on the host).  A local method: a must start within a gate
-    of b (T_init); estimate_scale needs a closed or bounded scene."""
+    of b (T_init); estimate_scale needs a closed or bounded scene.  T_init="global": the start comes from global_align_clouds
+    (global_kw: its keywords; `voxel` is required), whose dict is returned as the result's "global" entry."""
+    glob = None
+    if isinstance(kw.get("T_init"), str):
+        assert kw["T_init"] == "global", f"T_init {kw['T_init']!r}: a 4 x 4 matrix or \"global\""
+        assert global_kw and "voxel" in global_kw, "T_init=\"global\" needs global_kw with a voxel"
+        glob = global_align_clouds(ctx, a, b, **global_kw)
+        kw = dict(kw, T_init=glob["T"])
     res = ctx.register_clouds(a, b, b_normals, **kw)
+    if glob is not None:
+        res["global"] = glob
     if hasattr(a, "data_ptr"):
         a = a.detach().cpu().numpy()
     return res, move_points(a, res["T"], res["scale"])
@@ -63,7 +126,11 @@ def align_clouds(ctx, a, b, b_normals=None, **kw):
 def format_alignment(al: dict) -> str:
     """One line for the drivers, beside format_line."""
     t = al["T"][:3, 3] if hasattr(al["T"], "shape") else [row[3] for row in al["T"][:3]]
-    return (f"Align: status {al['status']}, {al['iters_run']} iterations, fitness {al['fitness']:.4f}, rmse {al['rmse']:.6g} m, "
+    start = ""
+    if "global" in al:
+        g = al["global"]
+        start = f"global start ({g['inliers']} of {g['n_corr']} feature pairs, {g['n_passed']} of {g['hypotheses']} samples scored), "
+    return (f"Align: {start}status {al['status']}, {al['iters_run']} iterations, fitness {al['fitness']:.4f}, rmse {al['rmse']:.6g} m, "
             f"scale {al['scale']:.6g}, t ({t[0]:.4f}, {t[1]:.4f}, {t[2]:.4f})")
 
 

@@ -187,8 +187,21 @@ def check_compare_options(cfg):
     align = bool(getattr(cfg, "compare_align", False))
     scale = bool(getattr(cfg, "compare_align_scale", False))
     init = getattr(cfg, "compare_align_init", None)
+    glob = bool(getattr(cfg, "compare_align_global", False))
+    gvoxel = getattr(cfg, "compare_align_global_voxel", None)
     if (scale or init is not None) and not align:
         raise ValueError("compare_align_scale / compare_align_init set how compare_align registers: they need compare_align = True")
+    if (glob or gvoxel is not None) and not align:
+        raise ValueError("compare_align_global / compare_align_global_voxel set where compare_align starts: they need compare_align = True")
+    if gvoxel is not None and not glob:
+        raise ValueError("compare_align_global_voxel is the global start's voxel: it needs compare_align_global = True")
+    if glob and init is not None:
+        raise ValueError("compare_align_global finds the start itself: it cannot be combined with compare_align_init")
+    if glob and scale:
+        raise ValueError("compare_align_global is rigid only (the RANSAC's edge-length test assumes one scale): it cannot be combined "
+                         "with compare_align_scale")
+    if gvoxel is not None and not (np.isfinite(float(gvoxel)) and float(gvoxel) > 0):
+        raise ValueError(f"compare_align_global_voxel must be finite and positive, got {gvoxel!r}")
     if not align:
         return None
     if not getattr(cfg, "compare_to", None):
@@ -732,9 +745,18 @@ class DepthToReconstructionPipeline:
             # vertices are moved on the host, in copies: what the run computed and writes stays in its own frame
             init = check_compare_options(cfg)
             normals = ctx.estimate_normals(ref)
-            res, cloud = metrics.align_clouds(ctx, cloud, ref, normals, T_init=init, estimate_scale=bool(cfg.compare_align_scale))
+            kw = {}
+            if getattr(cfg, "compare_align_global", False):
+                # the start from anywhere; when no sample passes T is the identity: the plain local start
+                init = "global"
+                kw["global_kw"] = dict(voxel=float(cfg.compare_align_global_voxel or 5.0 * cfg.voxel_size))
+            res, cloud = metrics.align_clouds(ctx, cloud, ref, normals, T_init=init, estimate_scale=bool(cfg.compare_align_scale), **kw)
             alignment = dict(T=res["T"].tolist(), scale=res["scale"], fitness=res["fitness"], rmse=res["rmse"], n_corr=res["n_corr"],
                              iters_run=res["iters_run"], status=res["status"])
+            if "global" in res:
+                g = res["global"]
+                alignment["global"] = dict(T=g["T"].tolist(), inliers=g["inliers"], n_corr=g["n_corr"], n_passed=g["n_passed"],
+                                           hypotheses=g["hypotheses"], voxel=g["voxel"], mutual=g["mutual"])
             if mesh_xyz is not None:
                 mesh_xyz = metrics.move_points(mesh_xyz, res["T"], res["scale"])
         out = metrics.compare_clouds(ctx, cloud, ref, thresholds=thr, max_dist=cfg.compare_max_dist)
